@@ -40,6 +40,7 @@ PCIE_PEAK_GBPS = 63.0                # PCIe Gen5 x16, spec (MI355X_MICROARCH.md 
 # (the cap on the workgroups of background build kernels -- library option build_workgroups -- is one per compute unit, the library's policy for
 # the device, counter "background_build_workgroups": with the strip ingest the alignment's short kernels get through beside it, r03: 14.23 -> 13.77 ms)
 HBM_PEAK_GBPS = 8000.0               # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs writes at most this much
 
 
 def cpu_baseline(pairs_np, cfg_kwargs, sample_pairs, per_thread, trials):
@@ -104,6 +105,9 @@ def main():
     ap.add_argument("--cpu-matches-per-thread", type=int, default=10)
     ap.add_argument("--cpu-trials", type=int, default=3)
     ap.add_argument("--records-out", default="", help="rank 0 writes the gathered result records of the last step here (.npy)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes what the timed path returned in its last timed step as "
+                    "DIR/<name>.npy (float64, one row per pair; a fixed, seeded sample of the rows beyond %d MB in all; condition_number only "
+                    "with --option condition_number=1, the library does not compute it otherwise)" % (DUMP_LIMIT_BYTES >> 20))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--build-workgroups", type=int, default=-1, help="cap on the workgroups of a background build kernel (library option build_workgroups; -1 = bench default)")
     ap.add_argument("--no-overlap", action="store_true", help="build each batch right before its match on one frame set (no build/match overlap)")
@@ -131,6 +135,8 @@ def main():
     ap.add_argument("--force-gather", action="store_true", help="run the N > 1 record path (process group, pinned staging, asynchronous all-gather, "
                     "drain) even with one rank: exercises the RCCL code path on a one-GPU box")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Started as plain `python bench.py --gpus N`: become the launcher -- one rank per GPU under torch.distributed.run on a free
@@ -249,6 +255,7 @@ def main():
         k = counter[0] % n_sets
         counter[0] += 1
         res = pipe.step(now=k, nxt=(k + 1) % n_sets)                    # next batch (with one set: this batch, built right before its match)
+        last["results"] = res
         last["T"] = res["transformation"].reshape(B, 4, 4)
         last["information"] = res["information"].reshape(B, 6, 6)
         last["loglik"] = res["loglik"]
@@ -345,6 +352,7 @@ def main():
 
     def lanes_collect():
         res = lanes.collect()
+        last["results"] = res
         last["T"] = res["transformation"].reshape(B, 4, 4).copy()
         last["information"] = res["information"].reshape(B, 6, 6).copy()
         last["loglik"] = res["loglik"].copy()
@@ -401,6 +409,7 @@ def main():
             elapsed_lanes = lanes_timed_loop()
             lanes_vs_one = float(np.abs(parallel.twists_of(last["T"]) - parallel.twists_of(one_lane_T)).max())
             last.update(keep_last)
+    timed_results = last["results"].copy()                             # (the legs below step the pipeline again)
     if lanes is not None:
         lanes.close()                                                   # (its frames and contexts go with it: the legs below run on the rank's own context)
         lanes = None
@@ -409,6 +418,13 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=comm_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # (condition_number is not computed, the library leaves it NaN, unless option condition_number is on: include/dvo_hip.h)
+        with_condition_number = any(kv.partition("=")[0] == "condition_number" and int(kv.partition("=")[2]) for kv in args.option)
+        outputs = {name: timed_results[name] for name in timed_results.dtype.names if name != "condition_number" or with_condition_number}
+        if gathering:
+            outputs["records"] = gathered[0]                           # every rank's records of the last step, as each rank receives them
+        dump_outputs(args.dump_outputs, outputs)
 
     # ---- everything below is outside the timed region -------------------------------------------------------
     if args.loop_only:
@@ -726,6 +742,21 @@ def main():
         if out is not None and args.force_gather:
             out["forced_gather"] = {"backend": args.backend, "world_size": world, "gather": gather_kind}
         print(json.dumps(out))
+
+
+def dump_outputs(path, arrays):
+    """name -> array with one row per pair: writes <path>/<name>.npy in float64.  If they exceed DUMP_LIMIT_BYTES in all, every array
+    keeps the same share of its rows, a sample drawn with a fixed seed, and <name>_rows.npy records which rows those are."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    share = 1.0 if total <= DUMP_LIMIT_BYTES else DUMP_LIMIT_BYTES / sum(a.nbytes + 8 * len(a) for a in arrays.values())
+    for name, a in arrays.items():
+        if share < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), max(1, int(len(a) * share)), replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _kernel_label(variant, pairs):

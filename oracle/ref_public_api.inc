@@ -3,7 +3,7 @@
 // (dvo_slam/include/dvo_slam/constraints/*.h) and the tracking front end (dvo_slam/include/dvo_slam/keyframe_tracker.h).
 // Included twice, with DVO_BRIDGE(name) naming the symbols:
 //   oracle/ref_bridge.cpp        ref_*     against the reference's own dvo_core headers and sources       -> oracle/_ref/libdvo_ref.so
-//   tests/dropin/dropin_bridge.cpp dropin_* against include/dvo/ (this engine's facade) + libdvo_hip.so   -> tests/dropin/_build/
+//   tests/dropin/dropin_bridge.cpp dropin_* against include/dvo/ (this engine's facade) + libdvo_hip.so   -> oracle/_ref/dropin/
 // so that the same caller code, and the reference's unmodified dvo_slam sources behind it, run once on the reference's CPU
 // tracker and once on the MI355X engine (tests/test_dropin.py compares the two).
 // Expects: <dvo/dense_tracking.h>, <dvo_slam/constraints/constraint_proposal_validator.h>, <dvo_slam/keyframe_tracker.h>,

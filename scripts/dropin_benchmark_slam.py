@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""The reference's own executable (dvo_benchmark/src/benchmark_slam.cpp, compiled unmodified, tests/dropin/Makefile) on a synthetic
+"""The reference's own executable (dvo_benchmark/src/benchmark_slam.cpp, compiled unmodified, oracle/dropin.mk) on a synthetic
 TUM-layout folder: once linked against this engine's facade (MI355X), once against the reference's own dvo_core (CPU twin), same
 command line.  Prints wall time, the executable's own "match" stopwatch (mean time of KeyframeTracker::update per frame, printed by
 the reference code every 100 frames) and the distance between the two trajectory files."""
@@ -10,7 +10,7 @@ import numpy as np
 from dvo_slam_amd import datagen, tum
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 201
-build = os.path.join(ROOT, "tests", "dropin", "_build")
+build = os.path.join(ROOT, "oracle", "_ref", "dropin")
 with tempfile.TemporaryDirectory() as root:
     seq = datagen.synth_sequence(31, n, 640, 480, depth_noise=2.0, grey_noise=4.0, exposure=0.02)
     tum.write_dataset(root, seq["grey"], seq["depth"], seq["poses"])

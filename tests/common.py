@@ -8,6 +8,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 GOLDEN = os.path.join(HERE, "golden")
+DROPIN_BUILD = os.path.join(ROOT, "oracle", "_ref", "dropin")      # oracle/dropin.mk: the reference's callers built on the facade
 
 from oracle import pyoracle as po   # noqa: E402
 from dvo_slam_amd import _lib as hl  # noqa: E402
@@ -210,18 +211,17 @@ _dropin = None
 
 
 def dropin_api():
-    """(library, "dropin_") for the api= argument of pyoracle's ref_* wrappers: tests/dropin/_build/libdvo_dropin.so = the
+    """(library, "dropin_") for the api= argument of pyoracle's ref_* wrappers: oracle/_ref/dropin/libdvo_dropin.so = the
     reference's unmodified dvo_slam sources + the shared caller code, compiled against include/dvo/ and linked with libdvo_hip.so.
     Built here when the reference tree is present (the built library travels to the GPU box); None when neither is there."""
     global _dropin
     if _dropin is None:
-        here = os.path.join(HERE, "dropin")
         import dvo_slam_amd
         dvo_slam_amd.build()
         po.build()
         if os.path.isdir("/root/reference/dvo_slam/src"):
-            subprocess.check_call(["make", "-C", here, "-s"])
-        path = os.path.join(here, "_build", "libdvo_dropin.so")
+            subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-f", "dropin.mk", "-s"])
+        path = os.path.join(DROPIN_BUILD, "libdvo_dropin.so")
         if not os.path.exists(path):
             return None
         L = C.CDLL(path)

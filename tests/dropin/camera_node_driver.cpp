@@ -1,6 +1,6 @@
 // tests/dropin/camera_node_driver.cpp -- TEST INFRASTRUCTURE: drives the reference's live-camera front end
 // dvo_ros::CameraDenseTracker (dvo_ros/src/camera_dense_tracking.cpp + camera_base.cpp, compiled UNMODIFIED against this engine's
-// facade, tests/dropin/Makefile) without a ROS master: a reconfigure call switches the synchronised image stream on
+// facade, oracle/dropin.mk) without a ROS master: a reconfigure call switches the synchronised image stream on
 // (handleConfig, camera_dense_tracking.cpp:106-172), then frames are handed to handleImages (:187-309) as sensor_msgs -- 8-bit
 // grey + 16-bit millimetre depth, the path through cv_bridge and SurfacePyramid::convertRawDepthImageSse -- and the accumulated
 // camera pose the node broadcasts on tf after every frame (:310-323) is returned.

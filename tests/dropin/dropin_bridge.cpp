@@ -1,4 +1,4 @@
-// tests/dropin/dropin_bridge.cpp -- TEST INFRASTRUCTURE (see the Makefile next to it).  C entry points that drive the reference's
+// tests/dropin/dropin_bridge.cpp -- TEST INFRASTRUCTURE (see oracle/dropin.mk).  C entry points that drive the reference's
 // own tracking front end / proposal validator / DenseTracker call pattern -- compiled here against include/dvo/ (the MI355X
 // engine's facade) -- with the very source text that oracle/ref_bridge.cpp compiles against the reference's dvo_core.
 #include <atomic>

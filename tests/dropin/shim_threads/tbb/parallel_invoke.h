@@ -1,6 +1,6 @@
 // tests/dropin/shim_threads/tbb/parallel_invoke.h -- TEST INFRASTRUCTURE.  Stand-in for tbb::parallel_invoke(f0, f1) that really runs the
 // two functors on two threads, like TBB does: f0 on a persistent worker thread, f1 on the caller.  The engine build of the reference's
-// front end (tests/dropin/Makefile) uses it so that LocalTracker's two concurrent match() calls (dvo_slam/src/local_tracker.cpp:180-184)
+// front end (oracle/dropin.mk) uses it so that LocalTracker's two concurrent match() calls (dvo_slam/src/local_tracker.cpp:180-184)
 // reach the engine the way they do under the real TBB -- from two threads at once.  (The CPU twin keeps the serial stand-in of
 // oracle/shim/tbb: its numbers are labelled accordingly.)
 #pragma once

@@ -2,10 +2,10 @@
 `python tests/golden/make_benchmark_slam_golden.py`).
 
 The reference's built target dvo_benchmark/src/benchmark_slam.cpp, compiled UNMODIFIED and linked with the reference's own
-dvo_core (tests/dropin/Makefile: _build/benchmark_slam_ref), is run on a synthetic TUM-layout folder (40 frames of 640x480, fr1
+dvo_core (oracle/dropin.mk: oracle/_ref/dropin/benchmark_slam_ref), is run on a synthetic TUM-layout folder (40 frames of 640x480, fr1
 intrinsics as the file hard-codes them, Kinect-model depth noise, intensity noise, exposure drift).  Stored: the trajectory file it
 writes, in two configurations (its own defaults; level 0 / strict), and checksums of the frames so that the GPU test -- which runs
-the SAME source file linked against this engine's facade (_build/benchmark_slam) on a regenerated folder -- can tell a generator drift
+the SAME source file linked against this engine's facade (oracle/_ref/dropin/benchmark_slam) on a regenerated folder -- can tell a generator drift
 from a tracking difference.
 """
 import hashlib
@@ -48,8 +48,8 @@ def run_target(exe, root, out, extra):
 
 
 if __name__ == "__main__":
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "dropin"), "-s"])
-    exe = os.path.join(ROOT, "tests", "dropin", "_build", "benchmark_slam_ref")
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-f", "dropin.mk", "-s"])
+    exe = os.path.join(ROOT, "oracle", "_ref", "dropin", "benchmark_slam_ref")
     store = dict(seq=np.array([SEQ["seed"], SEQ["n"], SEQ["w"], SEQ["h"]]), noise=np.array([SEQ["depth_noise"], SEQ["grey_noise"], SEQ["exposure"]]))
     with tempfile.TemporaryDirectory() as root:
         seq = make_folder(root)

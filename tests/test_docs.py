@@ -21,6 +21,8 @@ def test_cited_repository_paths_exist():
         text = open(os.path.join(ROOT, doc)).read()
         for p in sorted(set(cited_paths(text))):
             path = p.split("::")[0]
+            if path == "oracle/_ref":                                   # the directory the oracle's Makefile builds into
+                continue
             if re.search(r"_build/|/_ref/|gpurun_out|\.so$|/lib/|/bin/", path):      # built artefacts (git-ignored)
                 continue
             if not os.path.exists(os.path.join(ROOT, path)):
@@ -29,13 +31,10 @@ def test_cited_repository_paths_exist():
 
 
 def test_reference_citations_stay_within_the_cited_files():
-    """`file:line` citations of reference sources (headers, kernels, oracle, tests, documents) against the reference tree, when it is
-    there (the build container; the GPU box has no /root/reference)."""
+    """`file:line` citations of reference sources (headers, kernels, oracle, tests, documents) against the reference tree's file
+    list and line counts (tests/golden/reference_lines.json)."""
     import subprocess
     import sys
-    import pytest
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("no reference tree on this machine")
     out = subprocess.check_output([sys.executable, os.path.join(ROOT, "scripts", "check_citations.py")], text=True)
     head = out.splitlines()[0]
     assert int(head.split()[0]) > 300 and "; 0 out of range" in head, out

@@ -1,7 +1,7 @@
 """The drop-in claim, proven with the reference's own code: the reference's tracking front end
 (dvo_slam/src/{keyframe_tracker,local_tracker,local_map,tracking_result_evaluation,config}.cpp) and its loop-closure proposal
 validation (dvo_slam/src/constraints/*.cpp) are compiled UNMODIFIED against this engine's facade headers (include/dvo/) and
-linked with libdvo_hip.so (tests/dropin/Makefile).  The same caller code (oracle/ref_public_api.inc) then runs twice: behind
+linked with libdvo_hip.so (oracle/dropin.mk).  The same caller code (oracle/ref_public_api.inc) then runs twice: behind
 oracle/_ref it drives the reference's CPU DenseTracker, behind tests/dropin it drives the MI355X engine.  Compared here:
 whole matches iteration by iteration, the front end frame by frame, the validator's decisions over ten scenes, and the public
 fields of RgbdImage.
@@ -38,11 +38,11 @@ def test_dropin_library_is_the_reference_callers_on_this_engine():
     # the reference's own translation units are in there, compiled from /root/reference (symbols of dvo_slam::LocalTracker etc.),
     # and dvo::DenseTracker::match is NOT a symbol of its own: the facade is header-only and forwards to the C-ABI
     import subprocess
-    syms = subprocess.check_output(["nm", "-DC", "--defined-only", os.path.join(cm.HERE, "dropin", "_build", "libdvo_dropin.so")], text=True)
+    syms = subprocess.check_output(["nm", "-DC", "--defined-only", os.path.join(cm.DROPIN_BUILD, "libdvo_dropin.so")], text=True)
     assert "dvo_slam::LocalTracker::update" in syms and "dvo_slam::constraints::ConstraintProposalValidator::validate" in syms
     assert "dvo_slam::KeyframeTracker::update" in syms
     assert "computeResidualsSse" not in syms and "dvo::core::RgbdImage::calculateDerivativeX" not in syms
-    undefined = subprocess.check_output(["nm", "-D", "--undefined-only", os.path.join(cm.HERE, "dropin", "_build", "libdvo_dropin.so")], text=True)
+    undefined = subprocess.check_output(["nm", "-D", "--undefined-only", os.path.join(cm.DROPIN_BUILD, "libdvo_dropin.so")], text=True)
     assert "dvo_hip_match" in undefined and "dvo_hip_frame_create_f32" in undefined
 
 
@@ -186,15 +186,15 @@ def tum_folder(tmp_path_factory):
 
 
 def _target(name):
-    path = os.path.join(cm.HERE, "dropin", "_build", name)
+    path = os.path.join(cm.DROPIN_BUILD, name)
     if not os.path.exists(path):
-        pytest.skip("tests/dropin/_build/%s was not built (needs the reference tree at build time)" % name)
+        pytest.skip("oracle/_ref/dropin/%s was not built (needs the reference tree at build time)" % name)
     return path
 
 
 def test_benchmark_slam_binaries_are_the_reference_source_on_either_tracker(tum_folder):
-    """CPU tier.  _build/benchmark_slam is benchmark_slam.cpp + the reference's dvo_slam front end on libdvo_hip (no CPU tracker
-    inside); _build/benchmark_slam_ref is the same file on the reference's own dvo_core, and reproduces the committed golden."""
+    """CPU tier.  oracle/_ref/dropin/benchmark_slam is benchmark_slam.cpp + the reference's dvo_slam front end on libdvo_hip (no CPU tracker
+    inside); oracle/_ref/dropin/benchmark_slam_ref is the same file on the reference's own dvo_core, and reproduces the committed golden."""
     import subprocess
     mk, gold, root = tum_folder
     exe = _target("benchmark_slam")
@@ -297,14 +297,14 @@ def test_remaining_public_members_against_the_reference():
 def test_reference_live_camera_front_end_on_the_engine():
     """dvo_ros/src/camera_dense_tracking.cpp + camera_base.cpp -- the reference's live-camera node (the Affine3d&
     overload of match(), RgbdCameraPyramid::create per frame, SurfacePyramid::convertRawDepthImageSse, configtools.h) -- compiled
-    UNMODIFIED against the facade (tests/dropin/Makefile: libdvo_camera_node.so; ROS is stand-ins) and fed eight frames as sensor
+    UNMODIFIED against the facade (oracle/dropin.mk: libdvo_camera_node.so; ROS is stand-ins) and fed eight frames as sensor
     messages: the poses it broadcasts on tf equal the chain of matches made through the Python mirror of the C-ABI on the same planes."""
     import ctypes as C
     import dvo_slam_amd as d
     from dvo_slam_amd import datagen
-    path = os.path.join(cm.HERE, "dropin", "_build", "libdvo_camera_node.so")
+    path = os.path.join(cm.DROPIN_BUILD, "libdvo_camera_node.so")
     if not os.path.exists(path):
-        pytest.skip("tests/dropin/_build/libdvo_camera_node.so is not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/dropin/libdvo_camera_node.so is not built (needs the reference tree at build time)")
     L = C.CDLL(path)
     n, w, h = 8, 320, 240
     seq = datagen.synth_sequence(9, n, w, h)
@@ -383,8 +383,8 @@ def _loop_closures(edges):
 
 
 def test_keyframe_graph_binaries_are_the_reference_source():
-    """CPU tier.  _build/benchmark_slam_graph links dvo_slam/src/keyframe_graph.cpp (KeyframeGraphImpl, its TBB reduction body) and the
-    engine; _build/benchmark_slam_graph_ref the same file and the reference's own tracker."""
+    """CPU tier.  oracle/_ref/dropin/benchmark_slam_graph links dvo_slam/src/keyframe_graph.cpp (KeyframeGraphImpl, its TBB reduction body) and the
+    engine; oracle/_ref/dropin/benchmark_slam_graph_ref the same file and the reference's own tracker."""
     import subprocess
     need_dropin()
     exe, ref = _target("benchmark_slam_graph"), _target("benchmark_slam_graph_ref")
@@ -459,15 +459,15 @@ def test_reference_keyframe_graph_on_the_engine(tmp_path):
 def test_reference_live_slam_node_on_the_engine(tmp_path):
     """dvo_slam/src/camera_keyframe_tracking.cpp -- the reference's live SLAM node: sensor messages -> KeyframeTracker -> KeyframeGraph,
     reconfigure callbacks, graph publication on every map change, finalOptimization on request -- compiled UNMODIFIED against the facade
-    (tests/dropin/Makefile: libdvo_slam_node.so) and fed the there-and-back sweep as messages (mono8 + 32FC1 metres): it tracks and maps
+    (oracle/dropin.mk: libdvo_slam_node.so) and fed the there-and-back sweep as messages (mono8 + 32FC1 metres): it tracks and maps
     like the reference's executable benchmark_slam does on the same frames read from PNG files (same engine, same front and back end),
     and its last reconfigure call runs the final optimisation pass over all keyframes."""
     import ctypes as C
     from dvo_slam_amd import datagen
     need_dropin()
-    path = os.path.join(cm.HERE, "dropin", "_build", "libdvo_slam_node.so")
+    path = os.path.join(cm.DROPIN_BUILD, "libdvo_slam_node.so")
     if not os.path.exists(path):
-        pytest.skip("tests/dropin/_build/libdvo_slam_node.so is not built (needs the reference tree at build time)")
+        pytest.skip("oracle/_ref/dropin/libdvo_slam_node.so is not built (needs the reference tree at build time)")
     exe = _target("benchmark_slam_graph")
     root = str(tmp_path / "loop")
     n = _loop_folder(root)

@@ -185,6 +185,52 @@ def test_rccl_record_path_on_one_gpu(tmp_path):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("pairs, extra", [(12, ["--no-from-host", "--no-scaling-model", "--no-ref-compat", "--no-guard-stress"]),
+                                          (128, ["--lanes", "2", "--loop-only", "--option", "condition_number=1"])])
+def test_bench_dumps_what_its_last_timed_step_returned(tmp_path, pairs, extra):
+    """bench.py --dump-outputs: every field the results of the last timed step carry (one lane, or the lanes of --lanes), one finite float64
+    row per pair, the same as the records of that step; --steps is the number of timed steps the line reports.  condition_number is a field
+    only when option condition_number is on (the library leaves it NaN otherwise, include/dvo_hip.h)."""
+    from dvo_slam_amd.tracker import _RESULT_DTYPE
+    dump, rec = tmp_path / "dump", str(tmp_path / "records.npy")
+    b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--pairs", str(pairs), "--steps", "3", "--warmup", "1",
+                        "--no-cpu-baseline", "--records-out", rec, "--dump-outputs", str(dump)] + extra, capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-2000:]
+    j = json.loads([l for l in b.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0
+    names = [n for n in _RESULT_DTYPE.names if n != "condition_number" or "condition_number=1" in extra]
+    assert sorted(p.name for p in dump.iterdir()) == sorted(name + ".npy" for name in names)
+    out = {name: np.load(dump / (name + ".npy")) for name in names}
+    for name, a in out.items():
+        assert a.dtype == np.float64 and len(a) == pairs and np.isfinite(a).all(), name
+    if os.path.exists(rec):                                             # (--loop-only writes no records)
+        T = out["transformation"].reshape(pairs, 4, 4)
+        assert np.array_equal(par.pack_records(par.twists_of(T), out["information"], out["loglik"]), np.load(rec))
+
+
+def test_bench_dump_keeps_a_seeded_sample_within_the_limit(tmp_path, monkeypatch):
+    """CPU tier: beyond bench.DUMP_LIMIT_BYTES the dump keeps the same share of every array's rows, drawn with a fixed seed, and says which."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 << 10)
+    rng = np.random.default_rng(1)
+    arrays = {"transformation": rng.normal(size=(1000, 16)), "n_levels": np.full(1000, 4, np.int32), "records": rng.normal(size=(300, 32))}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == sorted(n + s for n in arrays for s in (".npy", "_rows.npy"))
+    assert sum((tmp_path / "a" / f).stat().st_size - 128 for f in files) <= 64 << 10          # (128 B: the .npy header)
+    for name, a in arrays.items():
+        rows = np.load(tmp_path / "a" / (name + "_rows.npy")).astype(np.int64)
+        kept = np.load(tmp_path / "a" / (name + ".npy"))
+        assert kept.dtype == np.float64 and 0 < len(rows) < len(a) and np.all(np.diff(rows) > 0)
+        assert np.array_equal(kept, a[rows].astype(np.float64))
+        assert np.array_equal(kept, np.load(tmp_path / "b" / (name + ".npy")))
+    bench.dump_outputs(str(tmp_path / "small"), {k: v[:10] for k, v in arrays.items()})
+    assert sorted(p.name for p in (tmp_path / "small").iterdir()) == sorted(n + ".npy" for n in arrays)
+
+
+@pytest.mark.gpu
 def test_native_gather_through_the_c_abi_world_of_one():
     """dvo_hip_comm_* / dvo_hip_gather_records_* called directly (no torch.distributed anywhere): a communicator of one rank on GPU 0, two
     gathers in flight at once (the double buffering a streaming caller relies on), a smaller share padded with zeros, and the error
