@@ -17,6 +17,7 @@
 // (align_mfma.hip) produces the same outputs 1.3x faster; variant 0 is kept as the independent second implementation the
 // parity tests compare it with.
 #include "align_common.h"
+#include "ref_order.h"
 
 namespace dvo_hip {
 
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(kBlock) void k_residual_reduce(
 template <int LOADS>
 __global__ __launch_bounds__(kBlock) void k_loglik(const LevelGeom g, const PairState* __restrict__ states, int n_pairs,
                                                    const float* __restrict__ partials, const float2* __restrict__ scratch,
-                                                   double* __restrict__ ll_partials, int blocks_per_pair) {
+                                                   double* __restrict__ ll_partials, int blocks_per_pair, const RefOrderPair* __restrict__ ref_order) {
   const int pair = pair_of_launch_index(g, blockIdx.y);       // (the slow lane of a batch: a list of pairs; the batch's own launches skip its pairs)
   if (pair < 0) return;
   if (!states[pair].active || states[pair].level != g.level) return;
@@ -127,6 +128,13 @@ __global__ __launch_bounds__(kBlock) void k_loglik(const LevelGeom g, const Pair
   __shared__ float stage[kScaleStageFloats];
   float C[3], P[4];
   reduce_partials_scale(partials, pair, g.tiles_x * g.tiles_y, stage, sh, sums);
+  if (ref_order) {                                            // (uniform; option "ref_order": n and S of the rank formula, ref_order.hip)
+    if (threadIdx.x == 0) {
+      sums[kAccN] = ref_order[pair].n;
+      for (int i = 0; i < 3; ++i) sums[kAccS + i] = ref_order[pair].S[i];
+    }
+    __syncthreads();
+  }
   const int n = scale_from_sums(sums, C, P);
   double total = 0.0;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -246,12 +254,13 @@ void launch_stream_mix(hipStream_t s, const PairPtrs* pairs, int n_pairs, int n_
 }
 
 void launch_loglik(hipStream_t s, const LevelGeom& g, const PairState* states, int n_pairs, const float* partials,
-                   const float2* scratch, double* ll_partials, int blocks_per_pair, bool one_schedule) {
+                   const float2* scratch, double* ll_partials, int blocks_per_pair, bool one_schedule, const RefOrderPair* ref_order) {
   // few pairs: the sweep is a handful of dependent round trips per lane, more loads in flight shorten it (one pair 0.52 -> 0.50 ms);
   // a full batch is bandwidth-bound and runs 6 % slower with the larger chunks
   // (one_schedule: the grouping of the partial sums must not follow the batch size -- option "deterministic")
-  if (n_pairs <= 16 && !one_schedule && !g.pair_list) k_loglik<8><<<dim3(blocks_per_pair, n_pairs), dim3(kBlock), 0, s>>>(g, states, n_pairs, partials, scratch, ll_partials, blocks_per_pair);
-  else k_loglik<4><<<dim3(blocks_per_pair, n_pairs), dim3(kBlock), 0, s>>>(g, states, n_pairs, partials, scratch, ll_partials, blocks_per_pair);
+  if (n_pairs <= 16 && !one_schedule && !g.pair_list)
+    k_loglik<8><<<dim3(blocks_per_pair, n_pairs), dim3(kBlock), 0, s>>>(g, states, n_pairs, partials, scratch, ll_partials, blocks_per_pair, ref_order);
+  else k_loglik<4><<<dim3(blocks_per_pair, n_pairs), dim3(kBlock), 0, s>>>(g, states, n_pairs, partials, scratch, ll_partials, blocks_per_pair, ref_order);
 }
 
 }  // namespace dvo_hip

@@ -26,6 +26,7 @@
 #include "device_types.h"
 #include "batch_policy.h"
 #include "launch.h"
+#include "ref_order.h"
 
 using namespace dvo_hip;
 
@@ -102,6 +103,7 @@ struct FrameLevel {
   float2* C = nullptr;         // {I, Z} of a current frame for the window sweep (null: not kept at this level)
   int cur_have = 0;            // flavours of the current-frame role that are built: kCurAB (A, B) | kCurC (C)
   bool selected = false;       // R / count built for (ithr, dthr) (reference role)
+  bool q3 = false;             // ... and its last selected pixel cleared if the count is odd (option "ref_order", ref_order.hip)
   float ithr = 0, dthr = 0;
 };
 
@@ -311,6 +313,8 @@ struct Workspace {
   hipStream_t tail_stream = nullptr;
   hipEvent_t tail_split = nullptr, tail_end = nullptr;
   DevBuf tail_partials, tail_scratch, tail_ll, tail_flags, tail_list;
+  // option "ref_order": the rows' records of a pass (RefOrderSeg, the largest level's height per pair) and the pairs' RefOrderPair
+  DevBuf ref_rows, ref_pairs;
 };
 
 // a helper thread of the concurrent pair groups (dvo_hip_context::opt_batch_groups) and the slice of the caller's batch it aligns
@@ -448,6 +452,9 @@ struct dvo_hip_context {
   long long coarse_launches = 0, coarse_levels = 0;
   int opt_deterministic = 0;       // a pair's record does not depend on the batch it is aligned in (see dvo_hip.h, option "deterministic")
   int opt_ref_compat = 0;          // projection and weights multiply with the HOST CPU's _mm_rcp_ps like the reference does
+  int opt_ref_order = 0;           // the reference's rank-dependent quirks Q3, Q6, Q7 (ref_order.hip; option "ref_order")
+  long long ref_order_passes = 0;  // steps enqueued with its scale passes (counter "ref_order_passes")
+  DevBuf ref_order_planes;         // the RefOrderPlane table of the Q3 edit
   DevBuf rcp_table;                // ... from this table, dumped from the instruction itself when the option is first switched on
   int rcp_shift = 0;
   int rcp_packed = 0;              // a 16-bit copy of the table lies behind it (LevelGeom::rcp_packed)
@@ -561,7 +568,8 @@ void workspace_destroy(Workspace& w) {
   (void)hipStreamSynchronize(w.stream);
   for (DevBuf& b : w.pair_ptrs) b.release();
   for (DevBuf* b : {&w.states, &w.partials, &w.scratch, &w.ll_partials, &w.lvl_stats, &w.it_stats, &w.results,
-                    &w.t_init, &w.counters, &w.exchange, &w.win_fallbacks, &w.pair_sums, &w.tail_partials, &w.tail_scratch, &w.tail_ll, &w.tail_flags, &w.tail_list})
+                    &w.t_init, &w.counters, &w.exchange, &w.win_fallbacks, &w.pair_sums, &w.tail_partials, &w.tail_scratch, &w.tail_ll, &w.tail_flags, &w.tail_list,
+                    &w.ref_rows, &w.ref_pairs})
     b->release();
   if (w.tail_stream) {
     (void)hipStreamSynchronize(w.tail_stream);
@@ -757,6 +765,13 @@ int dvo_hip_context_create(int device, dvo_hip_context** out) {
       dvo_hip_context_destroy(ctx);
       return DVO_HIP_ERR_INVALID;
     }
+  // DVO_HIP_REF_ORDER=1: the same for option "ref_order"
+  if (const char* env = std::getenv("DVO_HIP_REF_ORDER"))
+    if (env[0] == '1' && dvo_hip_set_option(ctx, "ref_order", 1) != DVO_HIP_OK) {
+      g_create_error = ctx->err;
+      dvo_hip_context_destroy(ctx);
+      return DVO_HIP_ERR_INVALID;
+    }
   *out = ctx;
   return DVO_HIP_OK;
 }
@@ -775,7 +790,7 @@ void dvo_hip_context_destroy(dvo_hip_context* ctx) {
     if (ev) (void)hipEventDestroy(ev);
   if (ctx->build_stream) (void)hipStreamDestroy(ctx->build_stream);
   for (DevBuf& b : ctx->build_tbl) b.release();
-  for (DevBuf* b : {&ctx->misc, &ctx->role_tbl_cur, &ctx->role_tbl_ref, &ctx->prep_tbl_cur, &ctx->prep_tbl_ref, &ctx->rcp_table}) b->release();
+  for (DevBuf* b : {&ctx->misc, &ctx->role_tbl_cur, &ctx->role_tbl_ref, &ctx->prep_tbl_cur, &ctx->prep_tbl_ref, &ctx->rcp_table, &ctx->ref_order_planes}) b->release();
   for (DevBuf& b : ctx->upload_buf) b.release();
   for (const dvo_hip_context::PooledBlock& b : ctx->frame_pool) (void)hipFree(b.p);
   ctx->frame_pool.clear();
@@ -1174,6 +1189,7 @@ int dvo_hip_frame_select(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, 
     FrameLevel& L = frame->lv[level];
     DVO_HIP_TRY(ctx, hipMemsetAsync(frame->sel_count + level, 0, sizeof(int), ctx->stream));
     launch_select_pack(ctx->stream, L.A, L.B, L.w * L.h, ithr, dthr, L.R, frame->sel_count + level, mask_dev);
+    L.q3 = false;                                            // (a fresh plane R)
   }
   int count = 0;
   DVO_HIP_TRY(ctx, hipMemcpyAsync(&count, frame->sel_count + level, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
@@ -1368,6 +1384,8 @@ int dvo_hip_level_iteration(dvo_hip_context* ctx, dvo_hip_frame* reference, dvo_
   hipStream_t s = ctx->stream;
   LevelGeom g = bp.geom[level];
   if (residuals_or_null) g.compact = 0;                        // (by pixel: one pair at every pixel's place)
+  Workspace& w0 = ctx->ws[0];
+  RefOrderPair* ref_order = ctx->opt_ref_order ? w0.ref_pairs.as<RefOrderPair>() : nullptr;   // (prepare_buffers: reserved under the option)
   const size_t npx = size_t(g.w) * g.h;
   DVO_HIP_TRY(ctx, ctx->misc.reserve(256 + sizeof(dvo_hip_iteration_out)));
   float* d_T = ctx->misc.as<float>();
@@ -1381,7 +1399,8 @@ int dvo_hip_level_iteration(dvo_hip_context* ctx, dvo_hip_frame* reference, dvo_
   const PairPtrs* pp = bp.pair_ptrs + size_t(level);
   launch_residual_reduce(s, ctx->opt_variant, bp.rpw[level], level == 0, g, pp, states, 1, ctx->ws[0].partials.as<float>(), ctx->ws[0].scratch.as<float2>(),
                          ctx->ws[0].win_fallbacks.as<unsigned long long>(), ctx->ws[0].f16_range_flag);
-  launch_loglik(s, g, states, 1, ctx->ws[0].partials.as<float>(), ctx->ws[0].scratch.as<float2>(), ctx->ws[0].ll_partials.as<double>(), kLlBlocksPerPair);
+  if (ref_order) launch_ref_order(s, g, states, 1, w0.scratch.as<float2>(), w0.ref_rows.as<RefOrderSeg>(), ref_order);
+  launch_loglik(s, g, states, 1, ctx->ws[0].partials.as<float>(), ctx->ws[0].scratch.as<float2>(), ctx->ws[0].ll_partials.as<double>(), kLlBlocksPerPair, false, ref_order);
   int n_sel = 0;
   DVO_HIP_TRY(ctx, hipMemcpyAsync(&n_sel, reference->sel_count + level, sizeof(int), hipMemcpyDeviceToHost, s));
   DVO_HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -1398,10 +1417,12 @@ int dvo_hip_level_iteration(dvo_hip_context* ctx, dvo_hip_frame* reference, dvo_
     pp = bp.pair_ptrs + size_t(level);
     launch_residual_reduce(s, 6, bp.rpw[level], level == 0, g, pp, states, 1, ctx->ws[0].partials.as<float>(), ctx->ws[0].scratch.as<float2>(),
                            ctx->ws[0].win_fallbacks.as<unsigned long long>());
-    launch_loglik(s, g, states, 1, ctx->ws[0].partials.as<float>(), ctx->ws[0].scratch.as<float2>(), ctx->ws[0].ll_partials.as<double>(), kLlBlocksPerPair);
+    if (ref_order) launch_ref_order(s, g, states, 1, w0.scratch.as<float2>(), w0.ref_rows.as<RefOrderSeg>(), ref_order);
+    launch_loglik(s, g, states, 1, ctx->ws[0].partials.as<float>(), ctx->ws[0].scratch.as<float2>(), ctx->ws[0].ll_partials.as<double>(), kLlBlocksPerPair, false, ref_order);
     DVO_HIP_TRY(ctx, hipStreamSynchronize(s));
   }
-  launch_single_shot_out(s, g, ctx->ws[0].partials.as<float>(), ctx->ws[0].ll_partials.as<double>(), kLlBlocksPerPair, n_sel, d_out);
+  launch_single_shot_out(s, g, ctx->ws[0].partials.as<float>(), ctx->ws[0].ll_partials.as<double>(), kLlBlocksPerPair, n_sel, d_out, ref_order);
+  if (ref_order) ctx->ref_order_passes += 1;
   DVO_HIP_TRY(ctx, hipMemcpyAsync(out, d_out, sizeof(dvo_hip_iteration_out), hipMemcpyDeviceToHost, s));
   if (residuals_or_null) DVO_HIP_TRY(ctx, hipMemcpyAsync(residuals_or_null, ctx->ws[0].scratch.p, npx * sizeof(float2), hipMemcpyDeviceToHost, s));
   DVO_HIP_TRY(ctx, hipStreamSynchronize(s));

@@ -124,7 +124,7 @@ bool level_uses_window(const dvo_hip_context* ctx, int w, int h) {
 }
 
 bool level_uses_small(const dvo_hip_context* ctx, int w, int h) {
-  return ctx->opt_small_sweep && ctx->opt_variant >= 8 && !ctx->opt_ref_compat && !level_uses_window(ctx, w, h) && level_is_linear(ctx, w) && small_sweep_takes(w, h);
+  return ctx->opt_small_sweep && ctx->opt_variant >= 8 && !ctx->opt_ref_compat && !ctx->opt_ref_order && !level_uses_window(ctx, w, h) && level_is_linear(ctx, w) && small_sweep_takes(w, h);
 }
 
 LevelGeom make_geom(const dvo_hip_context* ctx, const CameraGeom* cam, int level, int rows_per_wave) {
@@ -145,7 +145,8 @@ LevelGeom make_geom(const dvo_hip_context* ctx, const CameraGeom* cam, int level
   // (not under "ref_compat": a run that is compared with the reference's own numbers keeps every low part -- round-5 advisor finding)
   g.gram_hi_j = !ctx->opt_gram_lo_parts && !ctx->opt_deterministic && !ctx->opt_ref_compat && ctx->opt_variant == 8 && size_t(g.w) * g.h >= 150000 ? 1 : 0;
   g.small = level_uses_small(ctx, g.w, g.h) ? 1 : 0;
-  g.compact = ctx->opt_compact_residuals && ctx->opt_variant >= 8 && rows_per_wave == 4 && fast_sweep_supports(g) ? 1 : 0;   // (launch_residual_reduce's test)
+  // (not under "ref_order": its passes read the residual pairs by pixel, ref_order.hip)
+  g.compact = ctx->opt_compact_residuals && !ctx->opt_ref_order && ctx->opt_variant >= 8 && rows_per_wave == 4 && fast_sweep_supports(g) ? 1 : 0;   // (launch_residual_reduce's test)
   return g;
 }
 
@@ -294,6 +295,7 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
     for (int l = 0; l < levels; ++l) {   // new pixels: every cached role plane is stale (PointSelection::setRgbdImagePyramid)
       f->lv[l].cur_have = 0;
       f->lv[l].selected = false;
+      f->lv[l].q3 = false;
     }
     f->raw0 = grey != nullptr;
     f->raw_copy = false;
@@ -311,7 +313,7 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
     }
     wide = wide && aligned_to(host[i].grey, 4) && aligned_to(host[i].raw, 8) && aligned_to(staging_grey(f), 4);
     if (role == 0) f->lv[0].cur_have = flavor0;
-    if (role == 1) { f->lv[0].selected = true; f->lv[0].ithr = ithr; f->lv[0].dthr = dthr; }
+    if (role == 1) { f->lv[0].selected = true; f->lv[0].q3 = false; f->lv[0].ithr = ithr; f->lv[0].dthr = dthr; }
   }
   hipStream_t bs = ctx->build_stream;
   // (one of a few buffers: the one that already holds this very table -- a streaming caller re-ingests the same frame sets from the same
@@ -427,7 +429,7 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
         for (int l = l0; l <= l1; ++l) {
           FrameLevel& L = frames[i]->lv[l];
           if (role == 0) L.cur_have |= span.flavor[l];
-          else { L.selected = true; L.ithr = ithr; L.dthr = dthr; }
+          else { L.selected = true; L.q3 = false; L.ithr = ithr; L.dthr = dthr; }
         }
       if (eager) {
         const int rc2 = stamp_build(ctx, n, frames);
@@ -477,7 +479,7 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
         from_planes[miss].push_back(p);
       }
       if (role == 0) L.cur_have |= miss;
-      else { L.selected = true; L.ithr = ithr; L.dthr = dthr; }
+      else { L.selected = true; L.q3 = false; L.ithr = ithr; L.dthr = dthr; }
     }
     const FrameBuildPtrs* tbl = nullptr;
     for (int miss = 0; miss < 4; ++miss) {

@@ -10,7 +10,7 @@ void mirror_options(const dvo_hip_context* from, dvo_hip_context* to) {
   DVO_MIRROR(opt_condition_number); DVO_MIRROR(opt_fused_ll_pixels); DVO_MIRROR(opt_variant); DVO_MIRROR(opt_resident);
   DVO_MIRROR(opt_resident_rows); DVO_MIRROR(opt_resident_group); DVO_MIRROR(opt_resident_flags); DVO_MIRROR(opt_resident_cooperative);
   DVO_MIRROR(opt_sweep_tail); DVO_MIRROR(opt_coarse); DVO_MIRROR(opt_coarse_pixels); DVO_MIRROR(opt_coarse_wgs);
-  DVO_MIRROR(opt_deterministic); DVO_MIRROR(opt_small_sweep); DVO_MIRROR(opt_small_tiles); DVO_MIRROR(compute_units);
+  DVO_MIRROR(opt_deterministic); DVO_MIRROR(opt_ref_order); DVO_MIRROR(opt_small_sweep); DVO_MIRROR(opt_small_tiles); DVO_MIRROR(compute_units);
   DVO_MIRROR(opt_overlap_tails); DVO_MIRROR(opt_overlap_fraction); DVO_MIRROR(opt_tail_lists); DVO_MIRROR(opt_defer_ingest_pixels);
 #undef DVO_MIRROR
 }
@@ -44,7 +44,7 @@ void group_worker_main(GroupWorker* gw) {
 
 // how many groups a batch of n pairs is aligned in
 int batch_groups_of(const dvo_hip_context* ctx, int n) {
-  if (ctx->is_twin || ctx->opt_ref_compat || ctx->opt_deterministic) return 1;   // (the reciprocal table lives in the owner; one schedule per pair)
+  if (ctx->is_twin || ctx->opt_ref_compat || ctx->opt_deterministic || ctx->opt_ref_order) return 1;   // (the reciprocal table lives in the owner; one schedule per pair)
   // Asked for by name only.  Measured (round 6, streaming loop, one box): 1024 pairs 11.75 -> 11.1-11.9 ms per step with two groups,
   // 11.4-12.0 with three -- groups that start together stay in phase, and two sweeps of the same level side by side gain nothing; the
   // gain of several contexts on one GPU comes from running OUT of phase, which a streaming caller gets from lanes

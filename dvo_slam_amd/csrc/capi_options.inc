@@ -20,6 +20,7 @@ int dvo_hip_get_counter(dvo_hip_context* ctx, const char* key, long long* value)
   else if (std::strcmp(key, "listed_steps") == 0) *value = ctx->listed_steps;
   else if (std::strcmp(key, "tail_drains") == 0) *value = ctx->tail_drains;
   else if (std::strcmp(key, "tail_wait_us") == 0) *value = ctx->tail_wait_ns / 1000;
+  else if (std::strcmp(key, "ref_order_passes") == 0) *value = ctx->ref_order_passes;
   else if (std::strcmp(key, "coarse_launches") == 0) *value = ctx->coarse_launches;
   else if (std::strcmp(key, "coarse_levels") == 0) *value = ctx->coarse_levels;
   else if (std::strcmp(key, "window_fallbacks") == 0) {
@@ -66,6 +67,7 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value) {
   if (std::strcmp(key, "variant") == 0) {
     if (value != 0 && (value < 5 || value > 9))
       return fail(ctx, DVO_HIP_ERR_INVALID, "variant must be 0 (all-VALU schedule), 5 (matrix-core schedule), 6 or 7 (current-frame window staged in LDS, residuals bit-identical to the oracle's), 8 or 9 (the same with contracted arithmetic)");
+    if (ctx->opt_ref_order && value != 7 && value != 8) return fail(ctx, DVO_HIP_ERR_INVALID, "ref_order runs under variant 7 or 8");
     ctx->opt_variant = value;
     ctx->f32_gram_hold = 0;                                    // (a schedule asked for by name starts without history)
     return DVO_HIP_OK;
@@ -73,6 +75,12 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value) {
   if (std::strcmp(key, "rendezvous") == 0) {
     if (value != 0 && value != 1) return fail(ctx, DVO_HIP_ERR_INVALID, "rendezvous must be 0 or 1");
     ctx->opt_rendezvous = value;
+    return DVO_HIP_OK;
+  }
+  if (std::strcmp(key, "ref_order") == 0) {
+    if (value != 0 && value != 1) return fail(ctx, DVO_HIP_ERR_INVALID, "ref_order must be 0 or 1");
+    if (value && ctx->opt_variant != 7 && ctx->opt_variant != 8) return fail(ctx, DVO_HIP_ERR_INVALID, "ref_order runs under variant 7 or 8");
+    ctx->opt_ref_order = value;
     return DVO_HIP_OK;
   }
   if (std::strcmp(key, "deterministic") == 0) {

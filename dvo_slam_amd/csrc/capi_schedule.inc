@@ -10,6 +10,7 @@ struct BatchPlan {
   PairPtrs* pair_ptrs = nullptr; // device [levels][n] (null when the table only travels in kernel arguments)
   std::vector<PairPtrs> host_ptrs;   // the same table on the host
   int coarse_levels = 0;         // leading levels (first_level, first_level - 1, ...) the fused coarse-level kernel runs (plan_coarse)
+  bool ref_order = false;        // option "ref_order": every level on the launch path, with the passes of ref_order.hip
 };
 
 int validate_batch(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_frame* const* curs, const dvo_hip_config* cfg) {
@@ -42,6 +43,7 @@ void make_plan(const dvo_hip_context* ctx, const CameraGeom* cam, const dvo_hip_
   bp.prm.use_initial_estimate = cfg->use_initial_estimate;
   bp.prm.precision = cfg->precision;
   bp.prm.mu = cfg->mu;
+  bp.ref_order = ctx->opt_ref_order != 0;
   bp.prm.cap_iters = bp.cap_iters;
   bp.prm.cap_levels = bp.cap_levels;
   bp.prm.max_points_level0 = cam->w0 * cam->h0;
@@ -61,6 +63,35 @@ void make_plan(const dvo_hip_context* ctx, const CameraGeom* cam, const dvo_hip_
 int resident_levels_of(const dvo_hip_context* ctx, const dvo_hip_config* cfg, const CameraGeom* cam, int n, bool taps_missing);
 bool window_taps_missing(const dvo_hip_context* ctx, const dvo_hip_config* cfg, int n, dvo_hip_frame* const* curs);
 
+// Option "ref_order", Q3 (ref_order.hip::k_ref_order_drop_last): the reference planes R of a batch's levels lose the last selected pixel of
+// an odd selection, once per build of the plane (FrameLevel::q3).  The edit keeps the pixel it cleared in the frame's block of selection
+// counts and a match without the option puts it back (k_ref_order_restore): no plane is built again -- a reference frame ingested without
+// a copy of its raw planes could not be.
+int ref_order_planes(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, const dvo_hip_config* cfg) {
+  const bool edit = ctx->opt_ref_order != 0;
+  std::vector<RefOrderPlane> host;
+  for (int i = 0; i < n; ++i)
+    for (int l = cfg->last_level; l <= cfg->first_level; ++l) {
+      FrameLevel& L = refs[i]->lv[l];
+      if (L.q3 == edit) continue;                              // (also the second visit of a frame listed twice)
+      L.q3 = edit;
+      RefOrderPlane p;
+      p.R = L.R;
+      p.count = refs[i]->sel_count + l;
+      p.saved = ref_order_saved_slot(refs[i]->sel_count, l);
+      p.npx = L.w * L.h;
+      p.pad = 0;
+      host.push_back(p);
+    }
+  if (host.empty()) return DVO_HIP_OK;
+  DVO_HIP_TRY(ctx, ctx->ref_order_planes.reserve(host.size() * sizeof(RefOrderPlane)));
+  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->ref_order_planes.p, host.data(), host.size() * sizeof(RefOrderPlane)));
+  if (edit) launch_ref_order_drop_last(ctx->stream, ctx->ref_order_planes.as<RefOrderPlane>(), int(host.size()));
+  else launch_ref_order_restore(ctx->stream, ctx->ref_order_planes.as<RefOrderPlane>(), int(host.size()));
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  return DVO_HIP_OK;
+}
+
 int ensure_batch_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_frame* const* curs, const dvo_hip_config* cfg,
                        bool launch_path_only = false) {
   Range range("build");
@@ -79,6 +110,7 @@ int ensure_batch_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, 
   rc = ensure_roles(ctx, n, curs, 0, cfg->last_level, cfg->first_level, 0.0f, 0.0f, /*eager=*/false, want);
   if (rc == DVO_HIP_OK)
     rc = ensure_roles(ctx, n, refs, 1, cfg->last_level, cfg->first_level, cfg->intensity_derivative_threshold, cfg->depth_derivative_threshold);
+  if (rc == DVO_HIP_OK) rc = ref_order_planes(ctx, n, refs, cfg);
   return rc;
 }
 
@@ -99,6 +131,12 @@ int prepare_buffers(Workspace& w, const dvo_hip_config* cfg, dvo_hip_frame* cons
   DVO_WS_TRY(w, w.it_stats.reserve(size_t(n) * bp.cap_iters * sizeof(dvo_hip_iteration_stats)));
   DVO_WS_TRY(w, w.results.reserve(size_t(n) * sizeof(dvo_hip_result)));
   DVO_WS_TRY(w, w.pair_sums.reserve(size_t(n) * kPairSumsStride * sizeof(double)));
+  if (bp.ref_order) {
+    int max_h = 1;
+    for (int l = cfg->last_level; l <= cfg->first_level; ++l) max_h = std::max(max_h, bp.geom[l].h);
+    DVO_WS_TRY(w, w.ref_rows.reserve(size_t(n) * max_h * sizeof(RefOrderSeg)));
+    DVO_WS_TRY(w, w.ref_pairs.reserve(size_t(n) * sizeof(RefOrderPair)));
+  }
   DVO_WS_TRY(w, w.t_init.reserve(size_t(n) * 16 * sizeof(double)));
   // per-step tallies, and behind them one arrival word per pair (the sweeps' tail, solver_step.h): cleared together at the start of a batch
   DVO_WS_TRY(w, w.counters.reserve(size_t(bp.cap_iters + 8 + kResidentErrorWords) * sizeof(unsigned long long) + align_up(size_t(n) * sizeof(int), 8)));
@@ -285,7 +323,8 @@ bool window_taps_missing(const dvo_hip_context* ctx, const dvo_hip_config* cfg, 
 
 ResidentPlan plan_resident(const dvo_hip_context* ctx, const dvo_hip_config* cfg, const BatchPlan& bp, bool taps_missing) {
   ResidentPlan rp;
-  if (ctx->opt_resident == 0 || ctx->opt_deterministic) return rp;   // (deterministic: one path whatever the batch size, and that is the launch path)
+  // (deterministic: one path whatever the batch size, and that is the launch path; ref_order: its passes are the launch path's)
+  if (ctx->opt_resident == 0 || ctx->opt_deterministic || ctx->opt_ref_order) return rp;
   const int cus = ctx->compute_units > 0 ? ctx->compute_units : 256;
   // more pairs than compute units: the workgroups would run in shifts, and the launch path, which gives every phase the whole chip,
   // is as fast (measured: 256 pairs -3 %, 512 pairs +1.6 % against it).  (Not with a pinned group size: the caller asks for
@@ -350,7 +389,7 @@ constexpr int kCoarseMaxPixels = 160 * 120;
 
 void plan_coarse(const dvo_hip_context* ctx, const dvo_hip_config* cfg, BatchPlan& bp, const ResidentPlan& rp) {
   bp.coarse_levels = 0;
-  if (ctx->opt_coarse == 0 || rp.levels > 0 || ctx->opt_variant != 8) return;
+  if (ctx->opt_coarse == 0 || rp.levels > 0 || ctx->opt_variant != 8 || ctx->opt_ref_order) return;
   const int max_pixels = ctx->opt_coarse_pixels > 0 ? ctx->opt_coarse_pixels : kCoarseMaxPixels;
   for (int level = cfg->first_level; level >= cfg->last_level; --level) {
     if (bp.cam->w[level] * bp.cam->h[level] > max_pixels) break;
@@ -523,7 +562,7 @@ int run_batch(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_f
   const size_t main_steps = size_t(bp.cap_iters) + 8 + kResidentErrorWords;
   // The slow lane of a batch (option "overlap_tails"): see in front of the level loop below.  Batches whose levels are begun by launches
   // (beyond the solver steps' hand-over), the plain launch chain (no step in the sweep's tail), more than one level on this path.
-  bool overlap_batch = ctx->opt_overlap_tails != 0 && !policy.level_hand_over(n) && ctx->opt_sweep_tail == 0 && rp.levels == 0 && bp.coarse_levels == 0 &&
+  bool overlap_batch = ctx->opt_overlap_tails != 0 && !ctx->opt_ref_order && !policy.level_hand_over(n) && ctx->opt_sweep_tail == 0 && rp.levels == 0 && bp.coarse_levels == 0 &&
                        cfg->first_level > cfg->last_level;
   for (int l = cfg->last_level; l <= cfg->first_level; ++l)   // (the lane passes through every level: each one's sweep must take a list of pairs)
     overlap_batch = overlap_batch && sweep_takes_pair_list(ctx->opt_variant, bp.rpw[l], bp.geom[l]);
@@ -593,6 +632,7 @@ int run_batch(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_f
   float* partials = w.partials.as<float>();
   float2* scratch = w.scratch.as<float2>();
   double* ll_partials = w.ll_partials.as<double>();
+  RefOrderPair* const ref_order = bp.ref_order ? w.ref_pairs.as<RefOrderPair>() : nullptr;   // (option "ref_order")
   unsigned long long* tallies = w.counters.as<unsigned long long>();
   int* arrivals = reinterpret_cast<int*>(tallies + n_steps);
   const int per_level = cfg->max_iterations_per_level;
@@ -655,7 +695,8 @@ int run_batch(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_f
     const LevelGeom& g = bp.geom[level];
     LevelSchedule ls;
     const int fuse_opt = ctx->opt_fused_ll_pixels;
-    ls.fused_ll = g.w * g.h <= (fuse_opt > 0 ? fuse_opt : (policy.fused_loglik_on_large_levels(n) && !ctx->opt_deterministic ? kFusedLoglikMaxPixelsBatch : kFusedLoglikMaxPixels));
+    // (option "ref_order": the log-likelihood pass of its own on every level, k_loglik with the pairs' RefOrderPair)
+    ls.fused_ll = !bp.ref_order && g.w * g.h <= (fuse_opt > 0 ? fuse_opt : (policy.fused_loglik_on_large_levels(n) && !ctx->opt_deterministic ? kFusedLoglikMaxPixelsBatch : kFusedLoglikMaxPixels));
     ls.ll_blocks = ctx->opt_ll_blocks > 0 ? std::min(ctx->opt_ll_blocks, kLlBlocksPerPair)
                    : (!g.compact || ctx->opt_deterministic ? kLlBlocksPerPair : policy.loglik_blocks(n));
     ls.two_waves = ctx->opt_solver_waves == 2 ||
@@ -839,12 +880,16 @@ int run_batch(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_f
           Range range(kErr[level]);
           launch_residual_reduce(s, ctx->opt_variant, bp.rpw[level], level == 0, g_run, pp, states, n_run, partials, scratch, w.win_fallbacks.as<unsigned long long>(),
                                  w.f16_range_flag);
-          if (!fused_ll) launch_loglik(s, g_run, states, n_run, partials, scratch, ll_partials, ll_blocks, ctx->opt_deterministic != 0);
+          if (ref_order) {
+            launch_ref_order(s, g_run, states, n_run, scratch, w.ref_rows.as<RefOrderSeg>(), ref_order);
+            ctx->ref_order_passes += 1;
+          }
+          if (!fused_ll) launch_loglik(s, g_run, states, n_run, partials, scratch, ll_partials, ll_blocks, ctx->opt_deterministic != 0, ref_order);
         }
         if (g_run.pair_list) ctx->listed_steps += 1;
         Range range(kLinsys[level]);
         launch_solver_step(s, states, n_run, bp.prm, g_run, partials, ll_partials, ll_blocks, fused_ll ? scratch : nullptr, d_levels, d_iters,
-                           tallies + step, w.host_status + step, solver_two_waves, cfg->first_level - level, &next);   // (the level record every pair on this level is at: fetched with the state)
+                           tallies + step, w.host_status + step, solver_two_waves, cfg->first_level - level, &next, ref_order);   // (the level record every pair on this level is at: fetched with the state)
       }
     };
     int enqueued = std::min(per_sync, per_level);
@@ -875,7 +920,7 @@ int run_batch(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_f
     }
     int watched = step - 1;                                  // last step of the chunk whose outcome is awaited
     // (the slow lane: every level but the last may shed its stragglers to it -- on the last one nothing follows that they could run beside)
-    const bool list_tails = ctx->opt_tail_lists != 0 && !tail && !hand_over && sweep_takes_pair_list(ctx->opt_variant, bp.rpw[level], g);
+    const bool list_tails = ctx->opt_tail_lists != 0 && !bp.ref_order && !tail && !hand_over && sweep_takes_pair_list(ctx->opt_variant, bp.rpw[level], g);
     const bool may_shed = overlap_batch && level > cfg->last_level && !tail && sweep_takes_pair_list(ctx->opt_variant, bp.rpw[level], g);
     // Where an EMPTY step is expensive -- the dispatcher needs 95 us for the 307 200 workgroups of a 1024-pair finest-level sweep
     // that all exit at once, 114 us with its log-likelihood and solver launches -- the step ahead of the poll is not enqueued once
@@ -922,7 +967,7 @@ int run_batch(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_f
     if (hand_over && step - 1 <= watched) {
       Range range(kLinsys[level]);
       launch_solver_step(s, states, n, bp.prm, g, partials, ll_partials, ll_blocks, nullptr, d_levels, d_iters, tallies + step, w.host_status + step,
-                         solver_two_waves, cfg->first_level - level, &next);
+                         solver_two_waves, cfg->first_level - level, &next, ref_order);
       ++step;
     }
   }

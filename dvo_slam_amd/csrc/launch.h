@@ -7,6 +7,10 @@
 
 namespace dvo_hip {
 
+struct RefOrderSeg;
+struct RefOrderPair;
+struct RefOrderPlane;   // (ref_order.h)
+
 // pyramid_kernels.hip
 // raw ingest + pyramid levels 1..3 in one pass (levels beyond the fourth: launch_pyr_down)
 void launch_pyr_down(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h);
@@ -75,8 +79,15 @@ void launch_sweep_small(hipStream_t s, int rows_per_wave, const LevelGeom& g, co
 // scratch == null: read-only (one float per workgroup goes to `sink`, which must hold a float per (8 * 256)-pixel block)
 // window_planes: the planes the window sweep reads (reference 8 B + current {I, Z} 8 B) instead of the gathering sweep's 8 + 16 + 8 B
 void launch_stream_mix(hipStream_t s, const PairPtrs* pairs, int n_pairs, int n_px, float2* scratch, float* sink, bool window_planes = false);
+// ref_order (option "ref_order", ref_order.h): n and S of every pair from its RefOrderPair instead of the partial rows
 void launch_loglik(hipStream_t s, const LevelGeom& g, const PairState* states, int n_pairs, const float* partials,
-                   const float2* scratch, double* ll_partials, int blocks_per_pair, bool one_schedule = false);
+                   const float2* scratch, double* ll_partials, int blocks_per_pair, bool one_schedule = false, const RefOrderPair* ref_order = nullptr);
+
+// ref_order.hip (option "ref_order"): behind a sweep that stored the residual pairs by pixel, the rows' records (`rows`: g.h per pair) and
+// every pair's RefOrderPair; and the Q3 edit of reference planes
+void launch_ref_order(hipStream_t s, const LevelGeom& g, const PairState* states, int n_pairs, const float2* scratch, RefOrderSeg* rows, RefOrderPair* out);
+void launch_ref_order_drop_last(hipStream_t s, const RefOrderPlane* planes, int n_planes);
+void launch_ref_order_restore(hipStream_t s, const RefOrderPlane* planes, int n_planes);   // (the pixels the edit cleared, back)
 
 // align_resident.hip: levels first_level..last_level of every pair in one launch.  The n_pairs * group workgroups must fit the
 // device at once when group > 1 (one per compute unit); `cooperative` launches them through hipLaunchCooperativeKernel.
@@ -106,7 +117,8 @@ bool sweep_takes_pair_list(int variant, int rows_per_wave, const LevelGeom& g);
 void launch_solver_step(hipStream_t s, PairState* states, int n_pairs, SolverParams prm, LevelGeom g,
                         const float* partials, const double* ll_partials, int ll_blocks_per_pair, const float2* scratch_for_fused_ll,
                         dvo_hip_level_stats* levels, dvo_hip_iteration_stats* iters, unsigned long long* step_tally,
-                        int* host_status, bool two_waves = false, int level_slot_hint = -1, const NextLevel* next_or_null = nullptr);
+                        int* host_status, bool two_waves = false, int level_slot_hint = -1, const NextLevel* next_or_null = nullptr,
+                        const RefOrderPair* ref_order = nullptr);
 // the serial half of a step whose wide half ran in the sweep's tail (a.pair_sums)
 void launch_solver_serial(hipStream_t s, int n_pairs, LevelGeom g, const SolverStepArgs& a);
 void launch_finish(hipStream_t s, const PairState* states, int n_pairs, SolverParams prm,
@@ -116,6 +128,6 @@ void launch_finish(hipStream_t s, const PairState* states, int n_pairs, SolverPa
 void launch_force_active(hipStream_t s, PairState* states, int n_pairs);
 void launch_set_fixed_state(hipStream_t s, PairState* states, LevelGeom g, const float* T34_dev, const float* Pprev_dev, int first);
 void launch_single_shot_out(hipStream_t s, LevelGeom g, const float* partials, const double* ll_partials, int ll_blocks_per_pair,
-                            int n_selected, dvo_hip_iteration_out* out_dev);
+                            int n_selected, dvo_hip_iteration_out* out_dev, const RefOrderPair* ref_order = nullptr);
 
 }  // namespace dvo_hip

@@ -62,6 +62,17 @@ __global__ __launch_bounds__(WAVES * 64, MIN_WG) void k_solver_step(LevelGeom g,
   solver_step_body<WAVES>(L, g, a, pair);
 }
 
+// the step under option "ref_order": n, S and the log-likelihood tail of the pass from the pairs' RefOrderPair (ref_order.hip)
+__global__ __launch_bounds__(kBlock) void k_solver_step_ref_order(LevelGeom g, SolverStepArgs a, const RefOrderPair* __restrict__ ref_order) {
+  __shared__ SolverLds L;
+  const int pair = pair_of_launch_index(g, blockIdx.x);
+  if (pair < 0) {
+    if (threadIdx.x == 0) publish_step(a.step_tally, a.host_status, a.n_pairs, false);
+    return;
+  }
+  solver_step_body<kWavesPerBlock, kReduceInFlight, 16, 16, false, true>(L, g, a, pair, ref_order);
+}
+
 // The stragglers of a level (round 6, the slow lane -- capi_schedule.inc::run_batch): the pairs still active on `level` get a flag byte, and EVERY
 // flagged pair of the batch -- these and the ones of earlier levels -- goes into list[0 .. cap) in ascending order (-1 behind the last;
 // the host's `cap` adds up the counts its polls saw, which only shrink).  One workgroup: a batch has a few thousand pairs at most, and
@@ -133,11 +144,18 @@ __global__ void k_set_fixed_state(PairState* states, LevelGeom g, const float* _
 
 __global__ __launch_bounds__(kBlock) void k_single_shot_out(LevelGeom g, const float* __restrict__ partials,
                                                             const double* __restrict__ ll_partials, int ll_blocks_per_pair,
-                                                            int n_selected, dvo_hip_iteration_out* out) {
+                                                            int n_selected, dvo_hip_iteration_out* out, const RefOrderPair* __restrict__ ref_order) {
   __shared__ double sh[kWavesPerBlock * kAccStride];
   __shared__ double sums[kAccStride];
   float C[3], P[4];
   reduce_partials(partials, 0, g.tiles_x * g.tiles_y, sh, sums);
+  if (ref_order) {                                            // (option "ref_order")
+    if (threadIdx.x == 0) {
+      sums[kAccN] = ref_order->n;
+      for (int i = 0; i < 3; ++i) sums[kAccS + i] = ref_order->S[i];
+    }
+    __syncthreads();
+  }
   const int n = scale_from_sums(sums, C, P);
   const int tid = threadIdx.x;
   if (tid != 0) return;
@@ -148,6 +166,7 @@ __global__ __launch_bounds__(kBlock) void k_single_shot_out(LevelGeom g, const f
   for (int i = 0; i < 4; ++i) out->precision[i] = P[i];
   double ll_sum = 0.0;
   for (int b = 0; b < ll_blocks_per_pair; ++b) ll_sum += ll_partials[b];
+  if (ref_order) ll_sum -= ref_order->ll_tail;                // Q7
   const double det = double(P[0]) * double(P[3]) - double(P[1]) * double(P[2]);
   out->neg_loglik = -double(float(0.5 * double(n) * log(det) - 3.5 * ll_sum));   // float like the reference's (gn_step)
   const double p00 = double(P[0]), p01 = double(P[1]), p11 = double(P[3]);
@@ -189,9 +208,13 @@ int g_solver_occupancy = 0;   // (experiment: option "solver_occupancy")
 void launch_solver_step(hipStream_t s, PairState* states, int n_pairs, SolverParams prm, LevelGeom g,
                         const float* partials, const double* ll_partials, int ll_blocks_per_pair, const float2* scratch_for_fused_ll,
                         dvo_hip_level_stats* levels, dvo_hip_iteration_stats* iters, unsigned long long* step_tally, int* host_status, bool two_waves,
-                        int level_slot_hint, const NextLevel* next_or_null) {
+                        int level_slot_hint, const NextLevel* next_or_null, const RefOrderPair* ref_order) {
   const SolverStepArgs a = make_solver_step_args(states, n_pairs, prm, partials, ll_partials, ll_blocks_per_pair, scratch_for_fused_ll, levels, iters, step_tally,
                                                  host_status, level_slot_hint, next_or_null, nullptr);
+  if (ref_order) {
+    k_solver_step_ref_order<<<dim3(n_pairs), dim3(kBlock), 0, s>>>(g, a, ref_order);
+    return;
+  }
   // (two wavefronts: see solver_step_body; a level of at most 32 tiles -- 160 x 120, 80 x 60 -- of a batch beyond two workgroups per compute unit)
   if (two_waves) k_solver_step<2><<<dim3(n_pairs), dim3(128), 0, s>>>(g, a);
   else if (g_solver_occupancy == 3) k_solver_step<kWavesPerBlock, 3><<<dim3(n_pairs), dim3(kBlock), 0, s>>>(g, a);
@@ -219,8 +242,8 @@ void launch_set_fixed_state(hipStream_t s, PairState* states, LevelGeom g, const
 }
 
 void launch_single_shot_out(hipStream_t s, LevelGeom g, const float* partials, const double* ll_partials, int ll_blocks_per_pair,
-                            int n_selected, dvo_hip_iteration_out* out_dev) {
-  k_single_shot_out<<<dim3(1), dim3(kBlock), 0, s>>>(g, partials, ll_partials, ll_blocks_per_pair, n_selected, out_dev);
+                            int n_selected, dvo_hip_iteration_out* out_dev, const RefOrderPair* ref_order) {
+  k_single_shot_out<<<dim3(1), dim3(kBlock), 0, s>>>(g, partials, ll_partials, ll_blocks_per_pair, n_selected, out_dev, ref_order);
 }
 
 }  // namespace dvo_hip

@@ -11,6 +11,7 @@
 #pragma once
 #include "align_common.h"
 #include "solver_logic.h"
+#include "ref_order.h"
 
 // DVO_TAIL_CLOCKS (experiment build of one translation unit, scripts/r6_tailclk.py on a library built with -DDVO_TAIL_CLOCKS): where the time of a sweep's tail goes -- 100 MHz wall
 // clock, thread 0 of every workgroup (arrival) / of the pair's last workgroup (the rest); g_tail_clk[k] sums, g_tail_clk[8 + k] counts
@@ -70,8 +71,10 @@ __device__ __forceinline__ void publish_step(unsigned long long* step_tally, int
 // trips; the order of the additions and products does not depend on them).
 // PRE (round 6, k_solver_serial): the reduced sums and the four wavefronts' log-likelihood sums of the pass were formed in the sweep's
 // tail (sweep_tail_wide) and are read from SolverStepArgs::pair_sums -- the step is its serial half, any number of wavefronts.
-template <int WAVES, int REDUCE_IN_FLIGHT = kReduceInFlight, int LL_SLOTS = 16, int LL_LOADS = 16, bool PRE = false>
-__device__ __forceinline__ void solver_step_body(SolverLds& L, const LevelGeom& g, const SolverStepArgs& a, int pair) {
+// REF_ORDER (option "ref_order", k_solver_step_ref_order): n and S of the pass from the pair's RefOrderPair (ref_order.hip), and the
+// log-likelihood terms Q7 drops taken off the sum; the rest of the step -- the Gram contraction with P included -- follows from them.
+template <int WAVES, int REDUCE_IN_FLIGHT = kReduceInFlight, int LL_SLOTS = 16, int LL_LOADS = 16, bool PRE = false, bool REF_ORDER = false>
+__device__ __forceinline__ void solver_step_body(SolverLds& L, const LevelGeom& g, const SolverStepArgs& a, int pair, const RefOrderPair* ref_order = nullptr) {
   PairState& st = L.st;
   dvo_hip_level_stats& lvl = L.lvl;
   dvo_hip_iteration_stats& rec = L.recs[1];
@@ -112,6 +115,13 @@ __device__ __forceinline__ void solver_step_body(SolverLds& L, const LevelGeom& 
   } else {
     if (!a.scratch_for_fused_ll && threadIdx.x < 32) ll_mine = a.ll_partials[size_t(pair) * a.ll_blocks_per_pair + min(int(threadIdx.x), a.ll_blocks_per_pair - 1)];
     reduce_partials<WAVES, REDUCE_IN_FLIGHT>(a.partials, pair, g.tiles_x * g.tiles_y, L.sh, L.sums);   // same routine, same order as k_loglik: identical n, S, P
+    if constexpr (REF_ORDER) {
+      if (threadIdx.x == 0) {
+        L.sums[kAccN] = ref_order[pair].n;
+        for (int i = 0; i < 3; ++i) L.sums[kAccS + i] = ref_order[pair].S[i];
+      }
+      __syncthreads();
+    }
   }
   {
     unsigned* dst = reinterpret_cast<unsigned*>(&st);
@@ -231,6 +241,7 @@ __device__ __forceinline__ void solver_step_body(SolverLds& L, const LevelGeom& 
     } else {
       for (int b = 0; b < a.ll_blocks_per_pair; ++b) ll_sum += L.ll_stage[b];
     }
+    if constexpr (REF_ORDER) ll_sum -= ref_order[pair].ll_tail;   // Q7
     L.rec_index = st.n_iters_total;
     // gn_step addresses levels[n_levels - 1] and iters[n_iters_total]: hand it pointers biased so that those land in LDS
     SolverParams local = prm;

@@ -327,6 +327,16 @@ int dvo_hip_time_stream_mix(dvo_hip_context* ctx, int n_pairs,
  * mode, the same constraints except at pixels on a bound; under "variant" 7 residuals and constraint counts equal that oracle mode
  * bit for bit.  2 = as 1 with the table read through memory by every sweep -- the path of a CPU whose table has no 16-bit copy for
  * the contracted sweep to keep in LDS; test and measurement),
+ * "ref_order" (1: the reference's rank-dependent quirks -- Q3: an odd selection loses its last selected pixel (ValidPixels still
+ * counts it); Q6: the scale matrix pairs the constraints in raster order and uses the first residual of each pair twice; Q7: the
+ * log-likelihood sum drops its last n mod 50 terms -- so that Information and LogLikelihood follow the reference's own code.  With
+ * "ref_compat" 1, under "variant" 8 (the default: what DVO_HIP_REF_COMPAT=1 DVO_HIP_REF_ORDER=1 give) and 7 alike, Information lands
+ * 1e-4 ... 1.3e-2 of its largest entry from the reference's (median 1.8e-3 over 32 pairs), LogLikelihood 1e-6 ... 1.6e-4 -- as close
+ * as the oracle's float64 rendering of these quirks gets; without the option 20 %, and in the default mode about 6 times the
+ * reference's (README "What agrees with what").  Independent of "ref_compat"; "variant" 7 or 8 only.  Every level runs on the launch
+ * path with two extra passes per step (ref_order.hip); "resident", "coarse", "small_sweep", "sweep_tail", "overlap_tails",
+ * "tail_lists" and "batch_groups" are ignored.  Also switched on by DVO_HIP_REF_ORDER=1 when a context is created; default 0;
+ * cost: profiles/ref_order.txt),
  * "resident" (-1 default: small batches and coarse levels run in ONE launch per match, each pair owned by a group of resident
  * workgroups -- the latency path, DESIGN.md section 4: up to compute units / 4 pairs the coarse levels, up to 7/16 of the compute
  * units -- and from compute units / 8 pairs on when the current frames hold plane C without the taps, as a role-aware ingest of that
@@ -400,6 +410,8 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value);
  * "build_workgroups": one pair / one workgroup per compute unit),
  * "tail_steps" (Gauss-Newton steps of a batch enqueued as ONE launch, the sweep with the solver step in its tail, option "sweep_tail"),
  * "coarse_launches" / "coarse_levels" (the same for the fused coarse-level kernel, option "coarse"),
+ * "ref_order_passes" (Gauss-Newton steps ENQUEUED with the scale passes of option "ref_order" -- including the steps enqueued ahead of a
+ * poll, which do nothing for the pairs that have left the level -- and linearisations of dvo_hip_level_iteration under it),
  * "listed_steps" (Gauss-Newton steps launched over an active-pair list, option "tail_lists"),
  * "overlapped_tails" (levels that shed their last pairs to the slow lane, option "overlap_tails"), "overlapped_steps" (the
  * Gauss-Newton steps enqueued on the lane), "tail_drains" (batches that ended with a lane) and "tail_wait_us" (how long the host
