@@ -36,6 +36,117 @@ def load_golden(name):
     return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
 
 
+# ---- option "ref_order": the reference's rank quirks Q6 and Q7 restated in float64 ------------------------------------------------
+def mahalanobis_f32(r, P):
+    """r^T P r per row of r (float32, the order of pixel_math.h::mahalanobis, P row-major 2x2)"""
+    r = np.asarray(r, np.float32)
+    P = np.asarray(P, np.float32).reshape(2, 2)
+    return (r[:, 0] * P[0, 0] + r[:, 1] * P[1, 0]) * r[:, 0] + (r[:, 0] * P[0, 1] + r[:, 1] * P[1, 1]) * r[:, 1]
+
+
+def rank_formula(res, P_prev, first, weights=None):
+    """One pass of option "ref_order" from a residual plane [h, w, 2] in raster order (NaN: no constraint), written out over the
+    ranks k = 0 .. n-1 of the valid constraints, in float64:
+      n, S = sum_{k even} w_k r_k r_k^T + sum_{k odd} w_k r_{k-1} r_{k-1}^T  (Q6; entries 00, 01, 11),
+      cov = S / (n - 3) (float64; `P` is the float32 inverse of its float32 rounding, as the kernels form it),
+      kept = 50 floor(n / 50): the ranks [kept, n) leave the log-likelihood sum (Q7),
+      neg_ll = -(n/2 log det P - 7/2 sum_{k < kept} log(1 + 0.2 r_k^T P r_k))  (None where n < 6: no log-likelihood is formed).
+    The weights: 1 on a first pass, else float32 7 / (5 + r^T P_prev r) as the sweep forms them; `weights` (float32 per valid
+    constraint, in rank order) overrides both -- e.g. the host-reciprocal weights of option "ref_compat", which this formula does not
+    restate (its reference is the oracle's target mode)."""
+    r32 = np.asarray(res, np.float32).reshape(-1, 2)
+    r32 = r32[~np.isnan(r32[:, 0])]
+    r = r32.astype(np.float64)
+    n = len(r)
+    if weights is not None:
+        w = np.asarray(weights, np.float32).astype(np.float64)
+    elif first:
+        w = np.ones(n)
+    else:
+        w = (np.float32(7.0) / (np.float32(5.0) + mahalanobis_f32(r32, P_prev))).astype(np.float64)
+    rr = np.stack([r[:, 0] * r[:, 0], r[:, 0] * r[:, 1], r[:, 1] * r[:, 1]], 1)
+    lead = np.arange(n) & ~1                                   # the rank whose residual a constraint's term uses
+    S = (w[:, None] * rr[lead]).sum(0) if n else np.zeros(3)
+    kept = n // 50 * 50
+    out = dict(n=n, S=S, kept=kept, cov=None, P=None, neg_ll=None)
+    if n >= 4:
+        cov = S / (n - 3)
+        C32 = cov.astype(np.float32)
+        det = C32[0] * C32[2] - C32[1] * C32[1]
+        inv = np.float32(1.0) / det
+        P = np.array([[C32[2] * inv, -C32[1] * inv], [-C32[1] * inv, C32[0] * inv]], np.float32)
+        out.update(cov=cov, P=P)
+        if n >= 6:
+            q = mahalanobis_f32(r32, P).astype(np.float64)
+            detP = float(P[0, 0] * P[1, 1] - P[0, 1] * P[1, 0])
+            out["neg_ll"] = -(0.5 * n * np.log(detP) - 3.5 * np.log1p(0.2 * q[:kept]).sum())
+    return out
+
+
+def rank_classes(res, res_without_q3, n_selected):
+    """The rank classes a linearisation falls into (its residual plane under Q3 and the same state without Q3)"""
+    valid = ~np.isnan(res[:, :, 0])
+    counts = valid.sum(1)
+    n = int(counts.sum())
+    n_no_q3 = int((~np.isnan(res_without_q3[:, :, 0])).sum())
+    kept = n // 50 * 50
+    out = set()
+    if 6 <= n < 50:
+        out.add("n<50")
+    if n >= 50 and n % 50 == 0:
+        out.add("n%50==0")
+    if n % 50 == 49:
+        out.add("n%50==49")
+    if n >= 6:
+        out.add("odd" if n % 2 else "even")
+    if n_no_q3 == n + 1:
+        out.add("q3_removes")
+    if n_selected % 2 and n_no_q3 == n:
+        out.add("q3_last_gave_none")
+    if n_no_q3 == 6 and n == 5:
+        out.add("q3_6_to_5")
+    if 6 <= n and kept < n:
+        first = np.cumsum(counts) - counts                   # rank of each row's first constraint
+        row_kept = int(np.searchsorted(np.cumsum(counts), kept, side="right"))
+        row_last = int(np.searchsorted(np.cumsum(counts), n - 1, side="right"))
+        if first[row_kept] == kept:
+            out.add("tail_at_row_start")
+        if (counts[row_kept:row_last + 1] == 0).any():
+            out.add("tail_spans_empty_row")
+    return out
+
+
+# Inputs of one linearisation (level 0 of a synth(seed, w, h) pair, one pyramid level, T = exp(ty e_y), selection thresholds) that
+# together hit every rank class of option "ref_order" (rank_classes), found with the oracle's target mode on the CPU: (seed, w, h, ty,
+# intensity threshold, depth threshold, n, classes).  tests/test_ref_order_classes.py checks that the oracle still puts each row in its
+# classes; tests/test_gpu_ref_order_edges.py runs every row on the GPU.
+RANK_CLASSES = ("n<50", "n%50==0", "n%50==49", "odd", "even", "tail_at_row_start", "tail_spans_empty_row", "q3_removes",
+                "q3_last_gave_none", "q3_6_to_5")
+RANK_CLASS_TABLE = [
+    (3, 36, 20, 0.0, 50.0, 1e9, 49, ("n%50==49", "n<50", "odd", "q3_last_gave_none", "tail_at_row_start", "tail_spans_empty_row")),
+    (1, 36, 20, 0.0, 60.0, 1e9, 16, ("even", "n<50", "q3_removes", "tail_at_row_start", "tail_spans_empty_row")),
+    (3, 36, 20, 0.0, 10.0, 1e9, 350, ("even", "n%50==0")),
+    (5, 36, 20, 0.0, 70.0, 1e9, 5, ("q3_6_to_5", "q3_removes")),
+    (0, 36, 20, 0.0, 40.0, 1e9, 97, ("odd", "q3_last_gave_none", "tail_at_row_start")),
+    (0, 65, 49, 0.02, 50.0, 1e9, 83, ("odd", "tail_at_row_start", "tail_spans_empty_row")),
+    (2, 65, 49, 0.0, 30.0, 0.02, 1750, ("even", "n%50==0")),
+    (3, 65, 49, -0.02, 20.0, 1e9, 899, ("n%50==49", "odd", "q3_last_gave_none")),
+    (6, 65, 49, 0.0, 70.0, 1e9, 5, ("q3_6_to_5", "q3_removes")),
+    (1, 65, 49, 0.0, 70.0, 1e9, 6, ("even", "n<50", "q3_removes", "tail_at_row_start", "tail_spans_empty_row")),
+]
+
+
+def rank_class_row_oracle(row, want_residuals=True):
+    """the oracle's target mode on a row of RANK_CLASS_TABLE: (first-pass output, the same without Q3)"""
+    seed, w, h, ty, ithr, dthr = row[:6]
+    ref, cur = oracle_pyramids(synth(seed, w, h), 1)
+    T34 = po.se3_exp(np.array([0.0, ty, 0.0, 0.0, 0.0, 0.0]))[:3]
+    target = po.QUIRKS | po.Q_DROP_ODD | po.Q_LOGLIK_TAIL | po.X_PAIRING_F64
+    o = po.level_iteration(ref, cur, 0, T34, first=True, mode=target, ithr=ithr, dthr=dthr, want_residuals=want_residuals)
+    o_no_q3 = po.level_iteration(ref, cur, 0, T34, first=True, mode=target & ~po.Q_DROP_ODD, ithr=ithr, dthr=dthr, want_residuals=want_residuals)
+    return o, o_no_q3
+
+
 # ---- host emulation of the device headers (tests/emul/emul_device.cpp) ---------------------------------
 class EmulLevel(C.Structure):
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("fx", C.c_float), ("fy", C.c_float), ("ox", C.c_float), ("oy", C.c_float),

@@ -44,25 +44,6 @@ def run_emul(res, P_prev, first, host_rcp=False):
     return dict(n=int(out[0]), S=out[1:4], ll_all=out[4], ll_tail=out[5], neg_ll=out[6], cov=Cv, P=P.reshape(2, 2))
 
 
-def rank_formula(res, P_prev, first):
-    """S of Q6 and the Q7 tail written out over the ranks (raster order of the valid constraints), float64"""
-    r = res.reshape(-1, 2)
-    r = r[~np.isnan(r[:, 0])].astype(np.float64)
-    n = len(r)
-    if first:
-        w = np.ones(n)
-    else:
-        P = np.asarray(P_prev, np.float32).reshape(2, 2)
-        rf = r.astype(np.float32)
-        q = (rf[:, 0] * P[0, 0] + rf[:, 1] * P[1, 0]) * rf[:, 0] + (rf[:, 0] * P[0, 1] + rf[:, 1] * P[1, 1]) * rf[:, 1]
-        w = (np.float32(7.0) / (np.float32(5.0) + q)).astype(np.float64)
-    rr = np.stack([r[:, 0] * r[:, 0], r[:, 0] * r[:, 1], r[:, 1] * r[:, 1]], 1)
-    S = np.zeros(3)
-    for k in range(n):
-        S += w[k] * rr[k] if k % 2 == 0 else w[k] * rr[k - 1]
-    return n, S
-
-
 def synthetic_plane(rng, h, w, n_wanted, empty_rows=(), dense_rows=()):
     res = np.full((h, w, 2), np.nan, np.float32)
     free = [(v, u) for v in range(h) if v not in empty_rows for u in range(w)]
@@ -90,7 +71,8 @@ def test_join_equals_the_rank_formula_on_synthetic_masks(case, first):
     res = synthetic_plane(rng, case["h"], case["w"], case["n"], case.get("empty", ()), case.get("dense", ()))
     P_prev = [900.0, 3.0, 3.0, 2500.0]
     e = run_emul(res, P_prev, first)
-    n, S = rank_formula(res, P_prev, first)
+    f = cm.rank_formula(res, P_prev, first)
+    n, S = f["n"], f["S"]
     assert e["n"] == n
     assert np.allclose(e["S"], S, rtol=1e-12, atol=0)
     # rows that begin on odd ranks exist (the pairing crosses row boundaries)
@@ -149,7 +131,8 @@ def test_rank_formula_recipe_on_the_oracle_plane(oracle_pairs):
     T34 = po.se3_exp(np.array([0.0, -0.03, 0.0, 0.0, 0.0, 0.0]))[:3]
     for level in range(4):
         o = po.level_iteration(ref, cur, level, T34, first=True, mode=TARGET, want_residuals=True)
-        n, S = rank_formula(o["residuals"], None, True)
+        f = cm.rank_formula(o["residuals"], None, True)
+        n, S = f["n"], f["S"]
         assert n == o["n"]
         cov = S / (n - 3)                                     # (the oracle's is rounded to float32: half an ulp, 6e-8)
         assert np.abs(cov - o["cov"]).max() <= 1e-7 * np.abs(cov).max()
