@@ -19,6 +19,11 @@ cannot exercise HBM.
 Launch: `python bench.py --gpus 1 --steps K --warmup W`, or for N > 1
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 Rank 0 prints ONE JSON line.
+
+A plain run does only what `value` needs: set up, warm up, time the steps, write --records-out / --dump-outputs, print the line.
+Everything else runs with --full: the finest-level roofline and per-level kernel times, the latencies of one and two pairs, the
+PCIe-inclusive leg (`contract_value`), the ref_compat and f16-guard legs, the scaling model, the two-lane leg (and, with --lanes N,
+the one-lane loop it is compared with) and the CPU baseline.  The --no-* options below switch single legs of --full off.
 """
 import argparse
 import json
@@ -108,6 +113,8 @@ def main():
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="rank 0 writes what the timed path returned in its last timed step as "
                     "DIR/<name>.npy (float64, one row per pair; a fixed, seeded sample of the rows beyond %d MB in all; condition_number only "
                     "with --option condition_number=1, the library does not compute it otherwise)" % (DUMP_LIMIT_BYTES >> 20))
+    ap.add_argument("--full", action="store_true", help="after the timed loop, also run every leg beyond the headline figure (rooflines, "
+                    "latencies, PCIe-inclusive rate, ref_compat, f16 guard, scaling model, lanes, CPU baseline)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--build-workgroups", type=int, default=-1, help="cap on the workgroups of a background build kernel (library option build_workgroups; -1 = bench default)")
     ap.add_argument("--no-overlap", action="store_true", help="build each batch right before its match on one frame set (no build/match overlap)")
@@ -322,8 +329,9 @@ def main():
     # four -- while the host thread still spent 0.8 ms per step in front of the first launch, which a second lane hid; with that fixed
     # (capi_frames.inc::ensure_roles) two lanes are within +-2 % of one, box by box: 10.9-11.0 against 11.05-11.3 on one, 11.2 against 11.07 on
     # another.  The timed loop therefore runs on ONE lane unless --lanes asks for more; from three and a half pairs per compute unit on the
-    # two-lane loop is timed as a leg of its own and reported under "lanes")
-    lanes_leg = args.lanes == 0 and not args.no_overlap and not args.no_lanes_leg and not args.loop_only and 2 * B >= 7 * cus and world == 1
+    # two-lane loop is timed as a leg of its own with --full and reported under "lanes")
+    lanes_leg = (args.full and args.lanes == 0 and not args.no_overlap and not args.no_lanes_leg and not args.loop_only and 2 * B >= 7 * cus
+                 and world == 1)
     n_lanes = args.lanes if args.lanes > 0 else (2 if lanes_leg else 1)
     n_lanes = max(1, min(n_lanes, B // 64 if B >= 128 else 1))
     LANE_DEPTH = max(1, args.lane_depth)
@@ -397,10 +405,12 @@ def main():
         return time.perf_counter() - t0
 
     if lanes is not None and not lanes_leg:                             # --lanes N: the timed loop runs on the lanes
-        elapsed_one_lane = one_lane_loop()
-        one_lane_T = last["T"].copy()
+        if args.full:                                                   # (--full: the one-lane loop first, to compare with)
+            elapsed_one_lane = one_lane_loop()
+            one_lane_T = last["T"].copy()
         elapsed = elapsed_lanes = lanes_timed_loop()
-        lanes_vs_one = float(np.abs(parallel.twists_of(last["T"]) - parallel.twists_of(one_lane_T)).max())
+        if args.full:
+            lanes_vs_one = float(np.abs(parallel.twists_of(last["T"]) - parallel.twists_of(one_lane_T)).max())
     else:
         elapsed = elapsed_one_lane = one_lane_loop()
         if lanes is not None:                                           # the two-lane loop as a leg of its own (outside `value`)
@@ -437,13 +447,66 @@ def main():
                               "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "loop_only": True,
                               "config": {"pairs": n_total, "pairs_per_gpu": B, "lanes": n_lanes},
                               "counters": {k: ctx.counter(k) for k in ("overlapped_tails", "overlapped_steps", "tail_drains", "tail_wait_us")},
-                              "ms_per_step_one_lane": None if elapsed_lanes is None else round(elapsed_one_lane / args.steps * 1e3, 3)}))
+                              "ms_per_step_one_lane": (None if elapsed_lanes is None or elapsed_one_lane is None else
+                                                       round(elapsed_one_lane / args.steps * 1e3, 3))}))
         return
     twist_err = float(np.abs(parallel.twists_of(last["T"]) - pairs_np["xi_true"]).max())
     if args.records_out and rank == 0:
         full = gathered[0] if gathering else parallel.pack_records(parallel.twists_of(last["T"]), last["information"], last["loglik"])
         np.save(args.records_out, full)
     nan_results = int((~np.isfinite(last["T"]).all(axis=(1, 2)) | ~np.isfinite(last["information"]).all(axis=(1, 2))).sum())
+
+    def headline():
+        """The keys of the line a plain run prints: the timed loop, what it ran on, and its results against the true motion."""
+        return {
+            "metric": "frame-pair alignments/s (640x480, 4-level pyramid) + finest-level HBM GB/s vs roofline",
+            "value": round(n_total * args.steps / elapsed, 2), "unit": "alignments/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f32 (Gram operands exact f16 hi + lo pairs on every level, f32 accumulate)", "data": "synthetic",
+            "config": {"workload": "%d pairs (BASELINE config 4): independent 640x480 RGB-D frame pairs, seeds 0..%d, pair i on rank i mod %d, "
+                                   "4-level pyramid, FirstLevel=3, LastLevel=0, MaxIterationsPerLevel=100, Precision=5e-7, Mu=0; "
+                                   "step = every rank re-ingests the raw planes of its shard from HBM (pyramids, sampling planes, point "
+                                   "selection) and aligns it as one batch%s" % (
+                                       n_total, n_total - 1, world, "; build and match run back to back" if args.no_overlap else
+                                       "; the build of step k+1 (build stream) overlaps the match of step k, every step does one full build and one full match"),
+                       "pairs": n_total, "pairs_per_gpu": B, "width": W, "height": H,
+                       "lanes": ("%d lanes per GPU: the rank's pairs dealt to %d contexts of its GPU, a host thread each, that run their shards' steps out of phase "
+                                 "(dvo_stream_lanes_*, dvo_slam_amd/apps/stream_pipeline.cpp); a step = one full ingest + alignment of every pair, collected in "
+                                 "submission order at most %d steps behind" % (n_lanes, n_lanes, LANE_DEPTH)) if n_lanes > 1 and not lanes_leg else "1 lane",
+                       "parallelism": "independent pairs sharded round-robin over %d GPU(s) (fixed total: strong scaling), one all-gather of "
+                                      "256-B records per step%s" % (world, "" if not gathering else
+                                                                    " (ncclAllGather called by the C-ABI: dvo_hip_gather_records_*)" if gather_kind == "native"
+                                                                    else " (torch.distributed.all_gather)"),
+                       # (what the first keys of this line do NOT say by themselves -- SURVEY.md 8d quotes config 4 "incl. H2D": that is contract_value)
+                       "ingest": "hbm-resident raw planes (u8 grey + u16 depth per frame already in HBM when the timed region starts; the same loop "
+                                 "fed from pinned host memory, PCIe-inclusive, is contract_value, measured with --full)"},
+            "lanes": None if elapsed_lanes is None else {
+                "lanes": n_lanes, "ms_per_step": round(elapsed_lanes / args.steps * 1e3, 3), "value": round(n_total * args.steps / elapsed_lanes, 2),
+                "ms_per_step_one_lane": None if elapsed_one_lane is None else round(elapsed_one_lane / args.steps * 1e3, 3),
+                "timed_loop_runs_on": "one lane" if lanes_leg else "%d lanes" % n_lanes,
+                "build_workgroups_per_lane": lane_cap, "max_twist_difference_to_one_lane": lanes_vs_one,
+                "note": "the streaming loop over several contexts of the GPU, a host thread each, that run their shards' steps out of phase "
+                        "(dvo_stream_lanes_*, dvo_slam_amd/apps/stream_pipeline.cpp), timed like the main loop (EXACTLY `steps` full steps, submitted and "
+                        "collected inside the timed region).  Within +-2 % of the one-lane loop box by box since the host thread no longer spends "
+                        "0.8 ms per step in front of the first launch (round 6): reported, not `value`, unless --lanes asks for it; the one-lane "
+                        "figures are measured with --full"},
+            "max_twist_error_vs_truth": twist_err, "nan_results": nan_results, "full": args.full,
+        }
+
+    def finish(out):
+        if gathering:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            if args.force_gather:
+                out["forced_gather"] = {"backend": args.backend, "world_size": world, "gather": gather_kind}
+            print(json.dumps(out))
+
+    if not args.full:
+        finish(headline() if rank == 0 else None)
+        return
+
+    # ---- --full: the legs beyond the headline figure --------------------------------------------------------
     t_match0 = time.perf_counter()
     tracker.match_batch_arrays(refs, curs)
     match_only_ms = (time.perf_counter() - t_match0) * 1e3
@@ -687,38 +750,9 @@ def main():
 
     out = None
     if rank == 0:
-        value = n_total * args.steps / elapsed
-        out = {
-            "metric": "frame-pair alignments/s (640x480, 4-level pyramid) + finest-level HBM GB/s vs roofline",
-            "value": round(value, 2), "unit": "alignments/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32 (Gram operands exact f16 hi + lo pairs on every level, f32 accumulate)", "data": "synthetic",
-            "config": {"workload": "%d pairs (BASELINE config 4): independent 640x480 RGB-D frame pairs, seeds 0..%d, pair i on rank i mod %d, "
-                                   "4-level pyramid, FirstLevel=3, LastLevel=0, MaxIterationsPerLevel=100, Precision=5e-7, Mu=0; "
-                                   "step = every rank re-ingests the raw planes of its shard from HBM (pyramids, sampling planes, point "
-                                   "selection) and aligns it as one batch%s" % (
-                                       n_total, n_total - 1, world, "; build and match run back to back" if args.no_overlap else
-                                       "; the build of step k+1 (build stream) overlaps the match of step k, every step does one full build and one full match"),
-                       "pairs": n_total, "pairs_per_gpu": B, "width": W, "height": H,
-                       "lanes": ("%d lanes per GPU: the rank's pairs dealt to %d contexts of its GPU, a host thread each, that run their shards' steps out of phase "
-                                 "(dvo_stream_lanes_*, dvo_slam_amd/apps/stream_pipeline.cpp); a step = one full ingest + alignment of every pair, collected in "
-                                 "submission order at most %d steps behind" % (n_lanes, n_lanes, LANE_DEPTH)) if n_lanes > 1 and not lanes_leg else "1 lane",
-                       "parallelism": "independent pairs sharded round-robin over %d GPU(s) (fixed total: strong scaling), one all-gather of "
-                                      "256-B records per step%s" % (world, "" if not gathering else
-                                                                    " (ncclAllGather called by the C-ABI: dvo_hip_gather_records_*)" if gather_kind == "native"
-                                                                    else " (torch.distributed.all_gather)"),
-                       # (what the first keys of this line do NOT say by themselves -- SURVEY.md 8d quotes config 4 "incl. H2D": that is contract_value)
-                       "ingest": "hbm-resident raw planes (u8 grey + u16 depth per frame already in HBM when the timed region starts; the same loop "
-                                 "fed from pinned host memory, PCIe-inclusive, is contract_value)"},
+        out = headline()
+        out.update({
             "roofline": roofline,
-            "lanes": None if elapsed_lanes is None else {
-                "lanes": n_lanes, "ms_per_step": round(elapsed_lanes / args.steps * 1e3, 3), "value": round(n_total * args.steps / elapsed_lanes, 2),
-                "ms_per_step_one_lane": round(elapsed_one_lane / args.steps * 1e3, 3), "timed_loop_runs_on": "one lane" if lanes_leg else "%d lanes" % n_lanes,
-                "build_workgroups_per_lane": lane_cap, "max_twist_difference_to_one_lane": lanes_vs_one,
-                "note": "the streaming loop over several contexts of the GPU, a host thread each, that run their shards' steps out of phase "
-                        "(dvo_stream_lanes_*, dvo_slam_amd/apps/stream_pipeline.cpp), timed like the main loop (EXACTLY `steps` full steps, submitted and "
-                        "collected inside the timed region).  Within +-2 % of the one-lane loop box by box since the host thread no longer spends "
-                        "0.8 ms per step in front of the first launch (round 6): reported, not `value`, unless --lanes asks for it"},
             "match_only_ms_per_batch": round(match_only_ms, 3),
             "single_pair_ms": round(single_pair_ms, 3),
             "latency_ms": latency,
@@ -731,17 +765,10 @@ def main():
             "scaling_model": scaling_model,
             "config3": ("unmeasured: DVO_TUM_ROOT unset (no TUM RGB-D sequence on this box; tests/test_gpu_replay.py -k real replays one when it is)"
                         if not os.environ.get("DVO_TUM_ROOT") else "DVO_TUM_ROOT=%s: see tests/test_gpu_replay.py -k real" % os.environ["DVO_TUM_ROOT"]),
-            "max_twist_error_vs_truth": twist_err, "nan_results": nan_results,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pairs_np, cfg_kwargs, args.cpu_sample_pairs, args.cpu_matches_per_thread, args.cpu_trials)
-    if gathering:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        if out is not None and args.force_gather:
-            out["forced_gather"] = {"backend": args.backend, "world_size": world, "gather": gather_kind}
-        print(json.dumps(out))
+    finish(out)
 
 
 def dump_outputs(path, arrays):

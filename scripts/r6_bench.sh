@@ -15,8 +15,8 @@ PMC_PAIRS=1024 bash scripts/pmc.sh > $O/pmc.log 2>&1; tail -2 $O/pmc.log | cut -
 cp gpurun_out/pmc/pmc_finest_kernel.json profiles/pmc_finest_kernel.json 2>/dev/null; cp gpurun_out/pmc/pmc_finest_kernel.json $O/ 2>/dev/null
 bash scripts/r6_rooflines.sh > $O/rooflines.log 2>&1; tail -16 $O/rooflines.log | cut -c1-260
 cp $O/roof/kernel_rooflines.json profiles/r06_kernel_rooflines.json 2>/dev/null; cp $O/roof/kernel_rooflines.md profiles/r06_kernel_rooflines.md 2>/dev/null
-timeout 900 python bench.py --steps ${BENCH_STEPS:-20} --warmup 2 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench.json; tail -2 $O/bench.err
-( cd /tmp && timeout 600 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $O/prof -o bench -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-from-host --no-scaling-model --no-guard-stress > $O/prof_bench.log 2>&1 ); echo "rocprof rc=$?"
+timeout 900 python bench.py --full --steps ${BENCH_STEPS:-20} --warmup 2 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-400 $O/bench.json; tail -2 $O/bench.err
+( cd /tmp && timeout 600 rocprofv3 --kernel-trace --marker-trace --stats --output-format csv -d $O/prof -o bench -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-from-host --no-scaling-model --no-guard-stress > $O/prof_bench.log 2>&1 ); echo "rocprof rc=$?"
 f=$(find $O/prof -name "*kernel_trace.csv" | head -1); [ -n "$f" ] && python scripts/kernel_stats.py "$f" > $O/bench_kernel_stats_insitu.txt && head -30 $O/bench_kernel_stats_insitu.txt | cut -c1-200
 s=$(find $O/prof -name "*kernel_stats.csv" | head -1); [ -n "$s" ] && cp "$s" $O/bench_kernel_stats.csv
 m=$(find $O/prof -name "*marker*stats*.csv" | head -1); [ -n "$m" ] && cp "$m" $O/bench_marker_stats.csv

@@ -208,6 +208,37 @@ def test_bench_dumps_what_its_last_timed_step_returned(tmp_path, pairs, extra):
         assert np.array_equal(par.pack_records(par.twists_of(T), out["information"], out["loglik"]), np.load(rec))
 
 
+@pytest.mark.gpu
+def test_bench_runs_its_legs_only_with_full(tmp_path):
+    """A plain bench.py run prints the line of the timed loop alone; --full adds every leg after it (roofline, latencies, the
+    PCIe-inclusive rate, ref_compat, the f16 guard, the scaling model, the CPU baseline).  The timed loop is the same either way: what
+    the last timed step returned is dumped bit for bit alike (tile height and group size pinned)."""
+    common = ["--gpus", "1", "--pairs", "12", "--steps", "2", "--warmup", "1", "--rows-per-wave", "8", "--resident-group", "1"]
+    legs = ("roofline", "match_only_ms_per_batch", "single_pair_ms", "latency_ms", "contract_value", "from_host", "ref_compat",
+            "f16_guard_stress", "scaling_model", "config3", "cpu_baseline")
+    lines = {}
+    for kind, extra in (("plain", []), ("full", ["--full", "--cpu-sample-pairs", "2", "--cpu-matches-per-thread", "1", "--cpu-trials", "1"])):
+        b = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-outputs", str(tmp_path / kind)] + common + extra,
+                           capture_output=True, text=True, timeout=600)
+        assert b.returncode == 0, b.stderr[-2000:]
+        out = [l for l in b.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1
+        lines[kind] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for j in (plain, full):
+        assert j["steps"] == 2 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0 and j["nan_results"] == 0
+        assert j["unit"] == "alignments/s" and j["higher_is_better"] is True and j["max_twist_error_vs_truth"] < 1e-4
+    assert plain["full"] is False and not set(legs) & set(plain)
+    assert full["full"] is True and set(legs) <= set(full)
+    assert full["roofline"]["kernel_ms"] > 0 and full["latency_ms"]["pairs_1"] > 0 and full["contract_value"] > 0
+    assert full["ref_compat"]["value"] > 0 and full["f16_guard_stress"]["pairs_out_of_range"] == 1
+    assert full["scaling_model"]["ms_per_step_at_pairs_per_gpu"] and full["cpu_baseline"]["value"] > 0
+    names = sorted(p.name for p in (tmp_path / "plain").iterdir())
+    assert names and names == sorted(p.name for p in (tmp_path / "full").iterdir())
+    for name in names:
+        assert np.array_equal(np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)), name
+
+
 def test_bench_dump_keeps_a_seeded_sample_within_the_limit(tmp_path, monkeypatch):
     """CPU tier: beyond bench.DUMP_LIMIT_BYTES the dump keeps the same share of every array's rows, drawn with a fixed seed, and says which."""
     sys.path.insert(0, ROOT)
