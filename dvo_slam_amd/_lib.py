@@ -66,12 +66,17 @@ EXPORTS = [
     "dvo_hip_match", "dvo_hip_match_batch", "dvo_hip_level_iteration", "dvo_hip_time_residual_kernel", "dvo_hip_time_stream_mix",
     "dvo_hip_set_option", "dvo_hip_get_counter", "dvo_hip_version",
     "dvo_hip_frames_update_raw_device_as_ex", "dvo_hip_frames_update_raw_as_ex", "dvo_hip_flush_deferred", "dvo_hip_context_device",
+    "dvo_hip_frame_create_colour", "dvo_hip_frame_create_colour_device", "dvo_hip_frames_update_colour_device_as_ex",
+    "dvo_hip_frames_update_colour_as_ex",
     "dvo_hip_comm_get_unique_id", "dvo_hip_comm_create", "dvo_hip_comm_destroy", "dvo_hip_comm_rank", "dvo_hip_comm_size",
     "dvo_hip_comm_last_error", "dvo_hip_gather_records_begin", "dvo_hip_gather_records_end", "dvo_hip_gather_records",
 ]
 
 ROLE_CURRENT, ROLE_REFERENCE = 0, 1
 INGEST_DEFER, INGEST_NO_RAW_COPY = 1, 2
+# DVO_HIP_PIXEL_*: the formats of an 8-bit colour plane, and their bytes per pixel
+PIXEL_FORMATS = {"bgr8": 1, "rgb8": 2, "bgra8": 3, "rgba8": 4}
+PIXEL_CHANNELS = {"bgr8": 3, "rgb8": 3, "bgra8": 4, "rgba8": 4}
 COMM_ID_BYTES = 128
 
 
@@ -138,6 +143,13 @@ def lib():
     L.dvo_hip_version.restype = C.c_char_p
     L.dvo_hip_frames_update_raw_device_as_ex.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_float, C.c_int, C.POINTER(Config), C.c_uint]
     L.dvo_hip_frames_update_raw_as_ex.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_float, C.c_int, C.POINTER(Config), C.c_uint]
+    L.dvo_hip_frame_create_colour.argtypes = [vp, C.c_int, C.c_int, fp, vp, C.c_int, C.c_size_t, C.POINTER(C.c_uint16), C.c_float, C.c_int,
+                                              C.POINTER(vp)]
+    L.dvo_hip_frame_create_colour_device.argtypes = [vp, C.c_int, C.c_int, fp, vp, C.c_int, C.c_size_t, vp, C.c_float, C.c_int, C.POINTER(vp)]
+    L.dvo_hip_frames_update_colour_device_as_ex.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_size_t, C.POINTER(vp),
+                                                            C.c_float, C.c_int, C.POINTER(Config), C.c_uint]
+    L.dvo_hip_frames_update_colour_as_ex.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_size_t, C.POINTER(vp), C.c_float,
+                                                     C.c_int, C.POINTER(Config), C.c_uint]
     L.dvo_hip_flush_deferred.argtypes = [vp]
     L.dvo_hip_context_device.argtypes = [vp]
     L.dvo_hip_comm_get_unique_id.argtypes = [vp]

@@ -10,6 +10,7 @@
 #include <xmmintrin.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <atomic>
@@ -25,6 +26,7 @@
 #include "../../include/dvo_hip.h"
 #include "device_types.h"
 #include "batch_policy.h"
+#include "colour.h"
 #include "launch.h"
 #include "ref_order.h"
 
@@ -366,6 +368,7 @@ struct dvo_hip_context {
   long long rendezvous_pairs = 0;     // two-pair batches formed (counter "rendezvous_pairs")
   long long f16_range_repeats = 0; // batches repeated with the f32 Gram because a Jacobian left the f16 range (counter "f16_range_repeats")
   long long strip_ingests = 0;     // frames ingested by the strip kernel (ingest_strips.hip), counter "strip_ingests"
+  long long colour_ingests = 0;    // frames ingested from an 8-bit colour plane (colour.h), counter "colour_ingests"
   // Option "defer_ingest": a batched re-ingest (dvo_hip_frames_update_raw_device_as) is only recorded, and carried out by the next
   // dvo_hip_match_batch right behind the first launches of its first level (or by whatever entry point comes first).  A streaming
   // caller re-ingests the next batch and then aligns the current one: enqueueing the ingest first keeps the alignment's stream idle
@@ -374,6 +377,9 @@ struct dvo_hip_context {
   struct DeferredIngest {
     std::vector<dvo_hip_frame*> frames;
     std::vector<const void*> grey, raw;
+    std::vector<const void*> colour;   // (a colour ingest: the colour planes in place of `grey`, with their format and row pitch)
+    int colour_format = 0;
+    size_t colour_pitch = 0;
     float depth_scale;
     int role;
     dvo_hip_config cfg;
@@ -593,6 +599,14 @@ int fail(dvo_hip_context* ctx, int code, const char* msg) {
   if (ctx) ctx->err = msg;
   return code;
 }
+
+// The colour planes of a batch of frames (dvo_hip_frame_create_colour*, dvo_hip_frames_update_colour*): one DVO_HIP_PIXEL_* format and
+// one row pitch in bytes (resolved: never 0) for all of them
+struct ColourSource {
+  const void* const* planes;
+  int format;
+  size_t pitch;
+};
 
 #include "capi_frames.inc"     // cameras, frame allocation and build, role planes (ensure_roles)
 #include "capi_schedule.inc"   // batch plan, buffers, waits, resident / coarse plans, run_batch
@@ -906,12 +920,14 @@ int prepare_roles(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* fram
 }
 
 // ingest of device-resident raw planes, optionally straight into a role (role < 0: none)
+// (colour: colour planes in place of grey_dev, which is then null)
 int update_raw_device(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* grey_dev,
-                      const void* const* raw_depth_dev, float depth_scale, int role, const dvo_hip_config* cfg, bool keep_raw_copy = true) {
+                      const void* const* raw_depth_dev, float depth_scale, int role, const dvo_hip_config* cfg, bool keep_raw_copy = true,
+                      const ColourSource* colour = nullptr) {
   const bool ref = role == DVO_HIP_ROLE_REFERENCE;
   const int fused = role >= 0 && cfg->last_level == 0 ? (ref ? 1 : 0) : -1;   // level 0 is built in the same pass if it is used at all
   int rc = frames_build(ctx, n_frames, frames, grey_dev, raw_depth_dev, depth_scale, fused, ref ? cfg->intensity_derivative_threshold : 0.0f,
-                        ref ? cfg->depth_derivative_threshold : 0.0f, keep_raw_copy);
+                        ref ? cfg->depth_derivative_threshold : 0.0f, keep_raw_copy, colour);
   if (rc == DVO_HIP_OK && role >= 0) rc = prepare_roles(ctx, n_frames, frames, role, cfg);
   return rc;
 }
@@ -926,7 +942,9 @@ int flush_deferred(dvo_hip_context* ctx) {
     for (dvo_hip_frame* f : d.frames) f->deferred = 0;
     if (rc != DVO_HIP_OK) continue;
     ctx->deferred_ingests += 1;
-    rc = update_raw_device(ctx, int(d.frames.size()), d.frames.data(), d.grey.data(), d.raw.data(), d.depth_scale, d.role, &d.cfg, d.keep_raw_copy);
+    const ColourSource colour{d.colour.data(), d.colour_format, d.colour_pitch};
+    rc = update_raw_device(ctx, int(d.frames.size()), d.frames.data(), d.colour.empty() ? d.grey.data() : nullptr, d.raw.data(), d.depth_scale, d.role,
+                           d.role >= 0 ? &d.cfg : nullptr, d.keep_raw_copy, d.colour.empty() ? nullptr : &colour);
   }
   return rc;
 }
@@ -1068,6 +1086,198 @@ int dvo_hip_frames_update_raw_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_
   const int rc = check_prepare_args(ctx, n_frames, frames, role, cfg, "frames_update_raw_as_ex: bad argument");
   if (rc != DVO_HIP_OK) return rc;
   return update_raw_host(ctx, n_frames, frames, grey, raw_depth, depth_scale, role, cfg, (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
+}
+
+// ---- colour ingest (colour.h): the colour plane goes where the grey one went, the kernels convert it ----
+
+namespace {
+
+// Every argument of a colour ingest checked before any frame is touched.  role -1: a plain update (cfg ignored), else
+// check_prepare_args.  *pitch: the resolved row pitch.
+int check_colour_args(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour, int format, size_t colour_pitch,
+                      const void* const* raw_depth, int role, const dvo_hip_config* cfg, const char* who, size_t* pitch) {
+  if (!ctx) return DVO_HIP_ERR_INVALID;
+  if (role == -1) {
+    if (n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, who);
+    for (int i = 0; i < n_frames; ++i)
+      if (!frames[i] || frames[i]->cam != frames[0]->cam || frames[i]->levels != frames[0]->levels)
+        return fail(ctx, DVO_HIP_ERR_INVALID, "frames of one build batch must share camera and levels");
+  } else {
+    const int rc = check_prepare_args(ctx, n_frames, frames, role, cfg, who);
+    if (rc != DVO_HIP_OK) return rc;
+    for (int i = 0; i < n_frames; ++i)
+      if (frames[i]->levels != frames[0]->levels) return fail(ctx, DVO_HIP_ERR_INVALID, "frames of one build batch must share camera and levels");
+  }
+  const int channels = pixel_channels(format);
+  if (channels == 0) return fail(ctx, DVO_HIP_ERR_INVALID, "colour ingest: unknown pixel format (DVO_HIP_PIXEL_*)");
+  if (!colour || !raw_depth) return fail(ctx, DVO_HIP_ERR_INVALID, "colour ingest: null argument");
+  for (int i = 0; i < n_frames; ++i)
+    if (!colour[i] || !raw_depth[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "colour ingest: null entry");
+  const size_t tight = size_t(frames[0]->lv[0].w) * channels;
+  if (colour_pitch != 0 && colour_pitch < tight) return fail(ctx, DVO_HIP_ERR_INVALID, "colour ingest: colour_pitch < width * channels");
+  if (colour_pitch > size_t(INT_MAX)) return fail(ctx, DVO_HIP_ERR_INVALID, "colour ingest: colour_pitch above 2^31 - 1");
+  *pitch = colour_pitch ? colour_pitch : tight;
+  return DVO_HIP_OK;
+}
+
+// device planes; defer / keep_raw_copy as update_raw_device_as
+int update_colour_device_as(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour_dev, int format,
+                            size_t colour_pitch, const void* const* raw_depth_dev, float depth_scale, int role, const dvo_hip_config* cfg,
+                            int defer, int keep_raw_copy) {
+  size_t pitch = 0;
+  int rc = check_colour_args(ctx, n_frames, frames, colour_dev, format, colour_pitch, raw_depth_dev, role, cfg,
+                             "frames_update_colour_device_as_ex: bad argument", &pitch);
+  if (rc != DVO_HIP_OK) return rc;
+  const bool keep = keep_raw_copy < 0 ? ctx->opt_keep_raw_copy != 0 : keep_raw_copy != 0;
+  if (defer < 0 ? ctx->opt_defer_ingest != 0 : defer != 0) {
+    dvo_hip_context::DeferredIngest d;
+    d.frames.assign(frames, frames + n_frames);
+    d.colour.assign(colour_dev, colour_dev + n_frames);
+    d.colour_format = format;
+    d.colour_pitch = pitch;
+    d.raw.assign(raw_depth_dev, raw_depth_dev + n_frames);
+    d.depth_scale = depth_scale;
+    d.role = role;
+    if (role >= 0) d.cfg = *cfg;
+    d.keep_raw_copy = keep;
+    for (int i = 0; i < n_frames; ++i) frames[i]->deferred = 1;
+    ctx->deferred.push_back(std::move(d));
+    return DVO_HIP_OK;
+  }
+  DVO_FLUSH_DEFERRED(ctx);                                     // (nothing overtakes a recorded ingest)
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const ColourSource src{colour_dev, format, pitch};
+  return update_raw_device(ctx, n_frames, frames, nullptr, raw_depth_dev, depth_scale, role, role >= 0 ? cfg : nullptr, keep, &src);
+}
+
+// Host planes through the upload ring, as update_raw_host: a slot is [u16 depth][colour, tight rows], padded to an even size.  A frame
+// whose tight colour plane directly follows its depth plane moves in one transfer, and so does a run of such frames at the slot
+// stride; a padded host pitch is repacked by a 2-D transfer.
+int update_colour_host(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour, int format, size_t colour_pitch,
+                       const uint16_t* const* raw_depth, float depth_scale, int role, const dvo_hip_config* cfg, int keep_raw_copy) {
+  size_t pitch = 0;
+  int rc = check_colour_args(ctx, n_frames, frames, colour, format, colour_pitch, reinterpret_cast<const void* const*>(raw_depth), role, cfg,
+                             "frames_update_colour_as_ex: bad argument", &pitch);
+  if (rc != DVO_HIP_OK) return rc;
+  DVO_FLUSH_DEFERRED(ctx);
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int w = frames[0]->lv[0].w, h = frames[0]->lv[0].h;
+  const size_t n = size_t(w) * h, row = size_t(w) * pixel_channels(format);
+  const size_t slot_bytes = (n * 2 + row * h + 1) & ~size_t(1);
+  const unsigned b = ctx->upload_next++ % dvo_hip_context::kUploadRing;
+  DevBuf& buf = ctx->upload_buf[b];
+  rc = wait_for_ticket(ctx, ctx->upload_buf_seq[b], /*upload=*/true);   // (the previous contents may still be read by their build)
+  if (rc != DVO_HIP_OK) return rc;
+  if (buf.bytes < slot_bytes * size_t(n_frames)) {
+    DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->build_stream));   // growing = free + malloc
+    DVO_HIP_TRY(ctx, buf.reserve(slot_bytes * size_t(n_frames)));
+  }
+  char* base = buf.as<char>();
+  const bool tight = pitch == row;
+  for (int i = 0; i < n_frames;) {
+    const char* hd = reinterpret_cast<const char*>(raw_depth[i]);
+    if (!tight || reinterpret_cast<const char*>(colour[i]) != hd + n * 2) {   // separate planes: two transfers for this frame
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i, hd, n * 2, hipMemcpyHostToDevice, ctx->upload_stream));
+      if (tight) DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i + n * 2, colour[i], row * h, hipMemcpyHostToDevice, ctx->upload_stream));
+      else DVO_HIP_TRY(ctx, hipMemcpy2DAsync(base + slot_bytes * i + n * 2, row, colour[i], pitch, row, h, hipMemcpyHostToDevice, ctx->upload_stream));
+      ++i;
+      continue;
+    }
+    int j = i + 1;                                               // frames in the slot layout that follow each other in host memory
+    while (j < n_frames && reinterpret_cast<const char*>(raw_depth[j]) == hd + slot_bytes * size_t(j - i) &&
+           reinterpret_cast<const char*>(colour[j]) == reinterpret_cast<const char*>(raw_depth[j]) + n * 2)
+      ++j;
+    DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i, hd, slot_bytes * size_t(j - i) - (slot_bytes - n * 2 - row * h), hipMemcpyHostToDevice,
+                                    ctx->upload_stream));
+    i = j;
+  }
+  std::vector<const void*> c(static_cast<size_t>(n_frames)), r(static_cast<size_t>(n_frames));
+  for (int i = 0; i < n_frames; ++i) {
+    r[size_t(i)] = base + slot_bytes * i;
+    c[size_t(i)] = base + slot_bytes * i + n * 2;
+  }
+  DVO_HIP_TRY(ctx, hipEventRecord(ctx->upload_done, ctx->upload_stream));
+  DVO_HIP_TRY(ctx, hipStreamWaitEvent(ctx->build_stream, ctx->upload_done, 0));
+  const ColourSource src{c.data(), format, row};
+  rc = update_raw_device(ctx, n_frames, frames, nullptr, r.data(), depth_scale, role, role >= 0 ? cfg : nullptr,
+                         keep_raw_copy < 0 ? ctx->opt_keep_raw_copy != 0 : keep_raw_copy != 0, &src);
+  ctx->upload_buf_seq[b] = ctx->build_seq;          // the newest ticket is behind every reader of the buffer
+  return rc;
+}
+
+}  // namespace
+
+int dvo_hip_frames_update_colour_device_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour_dev,
+                                              int pixel_format, size_t colour_pitch, const void* const* raw_depth_dev, float depth_scale, int role,
+                                              const dvo_hip_config* cfg, unsigned flags) {
+  std::unique_lock<std::recursive_mutex> guard;
+  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
+  return update_colour_device_as(ctx, n_frames, frames, colour_dev, pixel_format, colour_pitch, raw_depth_dev, depth_scale, role, cfg,
+                                 (flags & DVO_HIP_INGEST_DEFER) ? 1 : 0, (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
+}
+
+int dvo_hip_frames_update_colour_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour,
+                                       int pixel_format, size_t colour_pitch, const uint16_t* const* raw_depth, float depth_scale, int role,
+                                       const dvo_hip_config* cfg, unsigned flags) {
+  std::unique_lock<std::recursive_mutex> guard;
+  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
+  return update_colour_host(ctx, n_frames, frames, colour, pixel_format, colour_pitch, raw_depth, depth_scale, role, cfg,
+                            (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
+}
+
+int dvo_hip_frame_create_colour(dvo_hip_context* ctx, int width, int height, const float K[4], const void* colour, int pixel_format,
+                                size_t colour_pitch, const uint16_t* raw_depth, float depth_scale, int levels, dvo_hip_frame** out) {
+  std::unique_lock<std::recursive_mutex> guard;
+  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
+  DVO_FLUSH_DEFERRED(ctx);
+  if (!ctx || !out || !colour || !raw_depth || !K) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_colour: null argument");
+  if (pixel_channels(pixel_format) == 0) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_colour: unknown pixel format (DVO_HIP_PIXEL_*)");
+  if (colour_pitch != 0 && colour_pitch < size_t(width > 0 ? width : 0) * pixel_channels(pixel_format))
+    return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_colour: colour_pitch < width * channels");
+  size_t raw_off;
+  dvo_hip_frame* f = nullptr;
+  int rc = frame_alloc(ctx, width, height, K, levels, &f, &raw_off);
+  if (rc != DVO_HIP_OK) return rc;
+  // (the frame's 3-B staging area cannot hold the colour plane: it goes through the upload buffers like a streaming ingest)
+  const void* c[1] = {colour};
+  const uint16_t* r[1] = {raw_depth};
+  rc = update_colour_host(ctx, 1, &f, c, pixel_format, colour_pitch, r, depth_scale, -1, nullptr, -1);
+  hipError_t e = hipSuccess;
+  if (rc == DVO_HIP_OK) e = sync_stream(ctx->build_stream);
+  if (e != hipSuccess) ctx->err = std::string("frame_create_colour: ") + hipGetErrorString(e);
+  if (e != hipSuccess || rc != DVO_HIP_OK) {
+    dvo_hip_frame_destroy(ctx, f);
+    return rc != DVO_HIP_OK ? rc : DVO_HIP_ERR_HIP;
+  }
+  *out = f;
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_frame_create_colour_device(dvo_hip_context* ctx, int width, int height, const float K[4], const void* colour_dev, int pixel_format,
+                                       size_t colour_pitch, const void* raw_depth_dev, float depth_scale, int levels, dvo_hip_frame** out) {
+  std::unique_lock<std::recursive_mutex> guard;
+  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
+  DVO_FLUSH_DEFERRED(ctx);
+  if (!ctx || !out || !colour_dev || !raw_depth_dev || !K) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_colour_device: null argument");
+  const int channels = pixel_channels(pixel_format);
+  if (channels == 0) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_colour_device: unknown pixel format (DVO_HIP_PIXEL_*)");
+  const size_t tight = size_t(width > 0 ? width : 0) * channels;
+  if ((colour_pitch != 0 && colour_pitch < tight) || colour_pitch > size_t(INT_MAX))
+    return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_colour_device: colour_pitch < width * channels or above 2^31 - 1");
+  size_t raw_off;
+  dvo_hip_frame* f = nullptr;
+  int rc = frame_alloc(ctx, width, height, K, levels, &f, &raw_off);
+  if (rc != DVO_HIP_OK) return rc;
+  const void* c[1] = {colour_dev};
+  const void* r[1] = {raw_depth_dev};
+  const ColourSource src{c, pixel_format, colour_pitch ? colour_pitch : tight};
+  rc = frames_build(ctx, 1, &f, nullptr, r, depth_scale, -1, 0.0f, 0.0f, true, &src);
+  if (rc != DVO_HIP_OK) {
+    dvo_hip_frame_destroy(ctx, f);
+    return rc;
+  }
+  *out = f;   // asynchronous (build stream): every later use of the frame is ordered after the build
+  return DVO_HIP_OK;
 }
 
 int dvo_hip_upload_wait(dvo_hip_context* ctx) {

@@ -251,6 +251,9 @@ void fill_build_ptrs(dvo_hip_frame* f, FrameBuildPtrs& p) {
   }
   for (int l = f->levels; l < kMaxLevels; ++l) p.C[l] = nullptr;
   p.sel_count = f->sel_count;
+  p.colour = nullptr;
+  p.colour_pitch = 0;
+  p.colour_format = 0;
 }
 
 // the frame's own staging area: [u16 depth][u8 grey], see frame_alloc
@@ -280,13 +283,17 @@ int eager_current_flavor(const dvo_hip_context* ctx, const CameraGeom* cam, int 
   return BatchPolicy(ctx->compute_units).ingest_skips_taps(n_frames) ? kCurC : (kCurAB | kCurC);
 }
 
+// colour: the frames' 8-bit colour planes in place of `grey` (null); the kernels convert them and leave grey in the frames' raw copies.
 int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const void* const* grey, const void* const* raw,
-                 float depth_scale, int role = -1, float ithr = 0.0f, float dthr = 0.0f, bool keep_raw_copy = true) {
+                 float depth_scale, int role = -1, float ithr = 0.0f, float dthr = 0.0f, bool keep_raw_copy = true,
+                 const ColourSource* colour = nullptr) {
   Range range("build");
   const CameraGeom* cam = frames[0]->cam;
   const int levels = frames[0]->levels;
   std::vector<FrameBuildPtrs> host(n);
   bool wide = cam->w[0] % 4 == 0;
+  const bool from_raw = grey || colour;
+  const int channels = colour ? pixel_channels(colour->format) : 0;
   const int flavor0 = eager_current_flavor(ctx, cam, 0, n);
   for (int i = 0; i < n; ++i) {
     dvo_hip_frame* f = frames[i];
@@ -297,13 +304,19 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
       f->lv[l].selected = false;
       f->lv[l].q3 = false;
     }
-    f->raw0 = grey != nullptr;
+    f->raw0 = from_raw;
     f->raw_copy = false;
     f->depth_scale = depth_scale;
-    if (!grey) continue;
-    host[i].grey = static_cast<const uint8_t*>(grey[i]);
+    if (!from_raw) continue;
+    if (colour) {
+      host[i].colour = static_cast<const uint8_t*>(colour->planes[i]);
+      host[i].colour_pitch = int(colour->pitch);
+      host[i].colour_format = colour->format;
+    } else {
+      host[i].grey = static_cast<const uint8_t*>(grey[i]);
+    }
     host[i].raw = static_cast<const uint16_t*>(raw[i]);
-    const bool in_place = host[i].raw == staging_depth(f) && host[i].grey == staging_grey(f);
+    const bool in_place = !colour && host[i].raw == staging_depth(f) && host[i].grey == staging_grey(f);
     if (in_place) {
       f->raw_copy = true;
     } else if (role < 0 || (role == 1 && keep_raw_copy)) {
@@ -311,7 +324,8 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
       host[i].keep_raw = staging_depth(f);
       f->raw_copy = true;
     }
-    wide = wide && aligned_to(host[i].grey, 4) && aligned_to(host[i].raw, 8) && aligned_to(staging_grey(f), 4);
+    wide = wide && (colour ? colour_strips_aligned(host[i].colour, colour->pitch, channels) : aligned_to(host[i].grey, 4)) &&
+           aligned_to(host[i].raw, 8) && aligned_to(staging_grey(f), 4);
     if (role == 0) f->lv[0].cur_have = flavor0;
     if (role == 1) { f->lv[0].selected = true; f->lv[0].q3 = false; f->lv[0].ithr = ithr; f->lv[0].dthr = dthr; }
   }
@@ -327,7 +341,7 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
   ctx->build_tbl_frames.assign(frames, frames + n);
   ctx->build_tbl_cur = &build_tbl;
   int built = 1;                                       // float ingest: level 0 is already in place
-  if (grey) {
+  if (from_raw) {
     // current frames: the {I, Z} plane of the pyramid levels the window sweep will read comes out of the same pass (no neighbours
     // needed), where the strip ingest runs (ingest_strips.hip)
     built = levels < 4 ? levels : 4;
@@ -339,8 +353,10 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
         for (int l = 1; l < built; ++l)
           if ((c_levels >> l & 1) && frames[i]->lv[l].C) frames[i]->lv[l].cur_have |= kCurC;
     }
-    launch_build_from_raw(bs, tbl, n, depth_scale, cam->w[0], cam->h[0], levels, role, wide, ithr, dthr, ctx->opt_build_workgroups, flavor0, c_levels);
+    launch_build_from_raw(bs, tbl, n, depth_scale, cam->w[0], cam->h[0], levels, role, wide, ithr, dthr, ctx->opt_build_workgroups, flavor0, c_levels,
+                          channels);
     if (ingest_strips_supports(cam->w[0], wide)) ctx->strip_ingests += n;
+    if (colour) ctx->colour_ingests += n;
   }
   for (int l = built; l < levels; ++l) launch_pyr_down(bs, tbl, n, l, cam->w[l - 1], cam->h[l - 1]);
   DVO_HIP_TRY(ctx, hipGetLastError());

@@ -134,6 +134,12 @@ struct FrameBuildPtrs {                // one frame of a batched pyramid build
   float2* R[kMaxLevels];
   float2* C[kMaxLevels];               // {I, Z} of a current frame (null: not kept at this level)
   int* sel_count;                      // one counter per level
+  // an 8-bit colour plane in place of `grey` (exactly one of the two is set; colour.h): DVO_HIP_PIXEL_* format, row stride in bytes.
+  // The kernels convert it to grey on the fly; keep_grey receives the converted grey.
+  // (the bytes per pixel are the kernels' template parameter, chosen at launch)
+  const uint8_t* colour;
+  int colour_pitch;
+  int colour_format;
 };
 
 // several pyramid levels of one camera for a launch that covers them all (k_derive_levels): 64 x 16 tiles, level l's tiles of a frame

@@ -16,6 +16,11 @@
 //   the four wavefronts of a workgroup take four vertically adjacent strips, so their shared halo rows meet in the CU's cache.
 // A current frame that is only read by the window sweep (plane C = {I, Z}, align_window.hip) needs no neighbours at all: TAPS = false
 // drops the halo rows, the edge columns and the differences.
+// CH = 3 / 4: the frame's 8-bit colour plane takes the grey plane's place (colour.h).  A lane reads its pixel pair as the 8 bytes of one
+// 4-byte-aligned window (3 channels: 6 bytes at an even offset, the window starts 2 bytes early when x % 4 == 2 and otherwise ends inside
+// pixel x + 2, never outside the row; 4 channels: 8 aligned bytes), converts it to the same two grey bytes the grey plane would hold,
+// and everything after that is the grey ingest's code.  BGR against RGB order is a wave-uniform choice of weights, not a variant.
+#include "colour.h"
 #include "global_ptr.h"
 #include "launch.h"
 
@@ -37,6 +42,20 @@ __device__ __forceinline__ float from_previous_lane(float v, float edge) {
 template <int CTRL>
 __device__ __forceinline__ float row_shifted(float v) {   // within a row of 16 lanes; the lanes that use it always have a source lane
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+
+// the 8 bytes that hold pixels x, x + 1 (x even) of a colour row with CH bytes per pixel (see the head of the file); two dword loads
+// the compiler merges into one 8-byte load (the window is 4-byte aligned only)
+template <int CH>
+__device__ __forceinline__ unsigned long long colour_pair_bits(Global<const uint8_t> row, int x) {
+  const Global<const unsigned> at = (Global<const unsigned>)(row + ((CH * x) & ~3));
+  return (unsigned long long)at[1] << 32 | at[0];
+}
+// the grey bytes of pixels x, x + 1 from colour_pair_bits: grey(x) | grey(x + 1) << 8, as a grey plane's 16-bit load would give them
+template <int CH>
+__device__ __forceinline__ unsigned colour_pair_grey(unsigned long long bits, int x, GreyWeights w) {
+  const int s = CH == 3 ? (x & 2) * 8 : 0;
+  return grey_at_bits(bits, s, w) | grey_at_bits(bits, s + 8 * CH, w) << 8;
 }
 
 }  // namespace
@@ -96,7 +115,8 @@ __device__ __forceinline__ int strip_role_planes(const float (&I)[TAPS ? kStripH
 // ROLE: -1 = none (raw copy + pyramid only), 0 = current, 1 = reference (R + selection count, counter zeroed before).
 // TAPS: level 0 needs the central differences (reference role; current role with the gathered taps A + B).
 // c_levels: bit l set = pyramid level l (1-3) also gets the current role's {I, Z} plane C.
-template <int ROLE, bool TAPS>
+// CH: 0 = the grey plane f.grey, 3 / 4 = the colour plane f.colour with 3 / 4 bytes per pixel.
+template <int ROLE, bool TAPS, int CH = 0>
 __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __restrict__ tbl, float scale, int w0, int h0, int levels,
                                                        float ithr, float dthr, int groups_x, int groups_y, int n_frames, int cur_flavor, int c_levels) {
 #pragma clang fp contract(off)
@@ -115,6 +135,9 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
     const auto raw = global_ptr(f.raw);
     const auto keep_grey = global_ptr(f.keep_grey);
     const auto keep_raw = global_ptr(f.keep_raw);
+    const auto colour = global_ptr(f.colour);                  // (CH > 0 only)
+    const size_t pitch = size_t(f.colour_pitch);
+    const GreyWeights gw = grey_weights(pixel_red_first(f.colour_format));
     // (the pointers of every plane the strip writes, read before the loads are issued: a scalar load further down would wait behind them)
     const auto R0 = global_ptr(f.R[0]);
     const auto A0 = global_ptr(f.A[0]);
@@ -133,25 +156,38 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
     // ---- every load of the strip, before anything is used ----
     constexpr int kFirst = TAPS ? -1 : 0, kRows = TAPS ? kStripH + 2 : kStripH;   // register row j = image row y0 + kFirst + j (clamped)
     unsigned g[kRows], d[kRows];
+    unsigned long long cb[CH ? kRows : 1];                      // (colour: the pixel pair's bytes, converted once every load is issued)
 #pragma unroll
     for (int j = 0; j < kRows; ++j) {
       const int y = min(max(y0 + kFirst + j, 0), h0 - 1);       // (scalar)
       const size_t row = size_t(y) * w0;
-      g[j] = *(Global<const uint16_t>)(grey + row + xl);
+      if (CH) cb[j] = colour_pair_bits<CH>(colour + size_t(y) * pitch, xl);
+      else g[j] = *(Global<const uint16_t>)(grey + row + xl);
       d[j] = *(Global<const uint32_t>)(raw + row + xl);
     }
     unsigned ge[kStripH], de[kStripH];                          // the strip's edge columns, rows y0 .. y0 + 7: lane 0 left, the others right
+    unsigned long long cbe[CH && TAPS ? kStripH : 1];           // (colour: the bytes of the pair that holds the edge column)
+    const int xe = lane == 0 ? max(sx * kStripW - 1, 0) : min(sx * kStripW + kStripW, w0 - 1);
     if (TAPS) {
-      const int xe = lane == 0 ? max(sx * kStripW - 1, 0) : min(sx * kStripW + kStripW, w0 - 1);
       const bool edge_lane = lane == 0 || lane == 63;
 #pragma unroll
       for (int r = 0; r < kStripH; ++r) {
         const size_t row = size_t(min(y0 + r, h0 - 1)) * w0;
         ge[r] = 0u; de[r] = 0u;
+        if (CH) cbe[r] = 0ull;
         if (edge_lane) {
-          ge[r] = grey[row + xe];
+          if (CH) cbe[r] = colour_pair_bits<CH>(colour + size_t(min(y0 + r, h0 - 1)) * pitch, xe & ~1);
+          else ge[r] = grey[row + xe];
           de[r] = raw[row + xe];
         }
+      }
+    }
+    if (CH) {
+#pragma unroll
+      for (int j = 0; j < kRows; ++j) g[j] = colour_pair_grey<CH>(cb[j], xl, gw);
+      if (TAPS) {
+#pragma unroll
+        for (int r = 0; r < kStripH; ++r) ge[r] = colour_pair_grey<CH>(cbe[r], xe & ~1, gw) >> (8 * (xe & 1)) & 0xffu;
       }
     }
     if (keep_grey && in_x) {                                    // the frame's own copy of its raw planes (for the other role, later)
@@ -296,18 +332,31 @@ void launch_derive_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames
 
 bool ingest_strips_supports(int w0, bool wide) { return wide && w0 % 4 == 0; }
 
+// (a colour plane: 3-byte pixels need 4-byte aligned rows, 4-byte pixels 8-byte aligned ones, see colour_pair_bits)
+bool colour_strips_aligned(const void* colour, size_t pitch, int channels) {
+  const size_t a = channels == 4 ? 8 : 4;
+  return reinterpret_cast<uintptr_t>(colour) % a == 0 && pitch % a == 0;
+}
+
 void launch_ingest_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role,
-                          float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels) {
+                          float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels) {
   const int gx = (w0 + kStripW - 1) / kStripW, gy = (h0 + kStripH * kStripsPerGroup - 1) / (kStripH * kStripsPerGroup);
   const long long total = (long long)gx * gy * n_frames;
   const dim3 grid(int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total)), block(256);
   const int lv = levels < 4 ? levels : 4;
-#define DVO_LAUNCH_STRIPS(ROLE, TAPS) \
-  k_ingest_strips<ROLE, TAPS><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, gx, gy, n_frames, cur_flavor, c_levels)
-  if (role == 1) DVO_LAUNCH_STRIPS(1, true);
-  else if (role == 0 && (cur_flavor & kCurAB)) DVO_LAUNCH_STRIPS(0, true);
-  else if (role == 0) DVO_LAUNCH_STRIPS(0, false);
-  else DVO_LAUNCH_STRIPS(-1, false);
+#define DVO_LAUNCH_STRIPS(ROLE, TAPS, CH) \
+  k_ingest_strips<ROLE, TAPS, CH><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, gx, gy, n_frames, cur_flavor, c_levels)
+#define DVO_LAUNCH_STRIPS_ROLE(CH)                                          \
+  do {                                                                      \
+    if (role == 1) DVO_LAUNCH_STRIPS(1, true, CH);                          \
+    else if (role == 0 && (cur_flavor & kCurAB)) DVO_LAUNCH_STRIPS(0, true, CH); \
+    else if (role == 0) DVO_LAUNCH_STRIPS(0, false, CH);                    \
+    else DVO_LAUNCH_STRIPS(-1, false, CH);                                  \
+  } while (0)
+  if (colour_channels == 3) DVO_LAUNCH_STRIPS_ROLE(3);
+  else if (colour_channels == 4) DVO_LAUNCH_STRIPS_ROLE(4);
+  else DVO_LAUNCH_STRIPS_ROLE(0);
+#undef DVO_LAUNCH_STRIPS_ROLE
 #undef DVO_LAUNCH_STRIPS
 }
 

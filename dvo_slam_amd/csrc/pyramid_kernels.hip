@@ -14,6 +14,7 @@
 //   R             float4 {Zsel, I, Idx, Idy} reference-side stream; Zsel = NaN where the selection
 //                 predicate rejects the pixel, so the reduce kernel needs no separate mask or list
 // These are bandwidth-trivial elementwise kernels; they are written for coalescing only.
+#include "colour.h"
 #include "global_ptr.h"
 #include "launch.h"
 
@@ -44,9 +45,11 @@ __device__ __forceinline__ void for_each_tile(int tiles_x, int tiles_y, int n_fr
 // (keep_grey / keep_raw) from which the other role can be derived later by the same kernel.
 // ROLE: -1 = none (copy + pyramid only), 0 = current (A, B), 1 = reference (R + selection count, counter zeroed before).
 // Arithmetic = the reference's ingest (surface_pyramid.cpp:65-105), k_pyr_down and derive_at: bit-identical planes.
+// CH = 3 / 4 (with WIDE = false): the grey value of a pixel comes from the frame's colour plane (colour.h) -- odd widths, unaligned
+// colour planes and padded pitches the strip ingest does not take; keep_grey receives the converted grey.
 constexpr int kB0W = 64, kB0H = 16, kB0Stride = 68;
 
-template <int ROLE, bool WIDE>
+template <int ROLE, bool WIDE, int CH = 0>
 __global__ __launch_bounds__(256) void k_build_from_raw(const FrameBuildPtrs* __restrict__ tbl, float scale, int w0, int h0, int levels,
                                                         float ithr, float dthr, int tiles_x, int tiles_y, int n_frames, int cur_flavor) {
 #pragma clang fp contract(off)
@@ -66,6 +69,13 @@ __global__ __launch_bounds__(256) void k_build_from_raw(const FrameBuildPtrs* __
     const auto raw = global_ptr(f.raw);
     const auto keep_grey = global_ptr(f.keep_grey);
     const auto keep_raw = global_ptr(f.keep_raw);
+    const auto colour = global_ptr(f.colour);                   // (CH > 0 only)
+    const size_t pitch = size_t(f.colour_pitch);
+    const GreyWeights gw = grey_weights(pixel_red_first(f.colour_format));
+    auto colour_grey = [&](int y, int x) -> uint8_t {          // (CH > 0 only)
+      const auto p = colour + size_t(y) * pitch + size_t(x) * CH;
+      return uint8_t(grey_of(p[0], p[1], p[2], gw));
+    };
     const auto A0 = global_ptr(f.A[0]);
     const auto B0 = global_ptr(f.B[0]);
     const auto C0 = global_ptr(f.C[0]);
@@ -120,7 +130,7 @@ __global__ __launch_bounds__(256) void k_build_from_raw(const FrameBuildPtrs* __
         const int r = i / (kB0W + 2), c = i - r * (kB0W + 2);
         const int yy = y0 - 1 + r, xx = x0 - 1 + c;
         const int y = min(max(yy, 0), h0 - 1), x = min(max(xx, 0), w0 - 1);
-        const uint8_t gv = grey[size_t(y) * w0 + x];
+        const uint8_t gv = CH ? colour_grey(y, x) : grey[size_t(y) * w0 + x];
         const uint16_t dv = raw[size_t(y) * w0 + x];
         sI[r][c] = float(gv);
         sZ[r][c] = depth_of(dv);
@@ -458,10 +468,10 @@ static int capped_grid(int tiles_x, int tiles_y, int n_frames, int max_workgroup
 }
 
 void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role, bool wide,
-                           float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels) {
+                           float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels) {
   if (ingest_strips_supports(w0, wide)) {
     if (role == 1) k_zero_counts<<<dim3((n_frames + 63) / 64), dim3(64), 0, s>>>(tbl, n_frames, 0);
-    launch_ingest_strips(s, tbl, n_frames, scale, w0, h0, levels, role, ithr, dthr, max_workgroups, cur_flavor, c_levels);
+    launch_ingest_strips(s, tbl, n_frames, scale, w0, h0, levels, role, ithr, dthr, max_workgroups, cur_flavor, c_levels, colour_channels);
     return;
   }
   const int tx = (w0 + kB0W - 1) / kB0W, ty = (h0 + kB0H - 1) / kB0H;
@@ -469,11 +479,18 @@ void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frame
   const int lv = levels < 4 ? levels : 4;
   if (role == 1) k_zero_counts<<<dim3((n_frames + 63) / 64), dim3(64), 0, s>>>(tbl, n_frames, 0);
 #define DVO_LAUNCH_B0(ROLE, WIDE) k_build_from_raw<ROLE, WIDE><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, tx, ty, n_frames, cur_flavor)
-  if (wide) {
+#define DVO_LAUNCH_B0_COLOUR(ROLE, CH) \
+  k_build_from_raw<ROLE, false, CH><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, tx, ty, n_frames, cur_flavor)
+  if (colour_channels == 3) {
+    if (role == 0) DVO_LAUNCH_B0_COLOUR(0, 3); else if (role == 1) DVO_LAUNCH_B0_COLOUR(1, 3); else DVO_LAUNCH_B0_COLOUR(-1, 3);
+  } else if (colour_channels == 4) {
+    if (role == 0) DVO_LAUNCH_B0_COLOUR(0, 4); else if (role == 1) DVO_LAUNCH_B0_COLOUR(1, 4); else DVO_LAUNCH_B0_COLOUR(-1, 4);
+  } else if (wide) {
     if (role == 0) DVO_LAUNCH_B0(0, true); else if (role == 1) DVO_LAUNCH_B0(1, true); else DVO_LAUNCH_B0(-1, true);
   } else {
     if (role == 0) DVO_LAUNCH_B0(0, false); else if (role == 1) DVO_LAUNCH_B0(1, false); else DVO_LAUNCH_B0(-1, false);
   }
+#undef DVO_LAUNCH_B0_COLOUR
 #undef DVO_LAUNCH_B0
 }
 

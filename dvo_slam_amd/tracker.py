@@ -297,6 +297,68 @@ class RgbdCameraPyramid:
         return RgbdImagePyramid(self, make, self.levels, timestamp)
 
 
+    def create_colour(self, colour_u8, depth_u16, pixel_format="bgr8", depth_scale=1.0 / 5000.0, timestamp=0.0):
+        """Ingest of an 8-bit colour plane [h, w, 3 | 4] + the u16 depth plane: the CV_BGR2GRAY conversion the reference's callers run on
+        the host (benchmark_slam.cpp:55-69) happens on the device (dvo_hip_frame_create_colour).  pixel_format: "bgr8" | "rgb8" |
+        "bgra8" | "rgba8"; rows may be padded (a view with a larger row stride), pixels must be contiguous."""
+        fmt, ch = _pixel_format(pixel_format)
+        Cl = _colour_plane(colour_u8, self.height, self.width, ch)
+        D = _depth_plane(depth_u16, self.height, self.width)
+
+        def make(levels):
+            ptr = C.c_void_p()
+            self.ctx.check(self.ctx._lib.dvo_hip_frame_create_colour(
+                self.ctx.ptr, self.width, self.height, _fp(self.K), C.c_void_p(Cl.ctypes.data), fmt, Cl.strides[0],
+                D.ctypes.data_as(C.POINTER(C.c_uint16)), depth_scale, levels, C.byref(ptr)))
+            return ptr
+        return RgbdImagePyramid(self, make, self.levels, timestamp)
+
+    def create_colour_device(self, colour_dev_ptr, pixel_format, pitch, depth_dev_ptr, depth_scale=1.0 / 5000.0, timestamp=0.0):
+        """A colour plane already resident in HBM (device pointer, row pitch in bytes, 0 = tight) + the u16 depth plane."""
+        fmt, ch = _pixel_format(pixel_format)
+        pitch = _pitch(pitch, self.width, ch)
+
+        def make(levels):
+            ptr = C.c_void_p()
+            self.ctx.check(self.ctx._lib.dvo_hip_frame_create_colour_device(
+                self.ctx.ptr, self.width, self.height, _fp(self.K), C.c_void_p(colour_dev_ptr), fmt, pitch, C.c_void_p(depth_dev_ptr),
+                depth_scale, levels, C.byref(ptr)))
+            return ptr
+        return RgbdImagePyramid(self, make, self.levels, timestamp)
+
+
+def _pixel_format(name):
+    if not isinstance(name, str) or name not in _lib.PIXEL_FORMATS:
+        raise ValueError("pixel_format must be one of %s, not %r" % (sorted(_lib.PIXEL_FORMATS), name))
+    return _lib.PIXEL_FORMATS[name], _lib.PIXEL_CHANNELS[name]
+
+
+def _pitch(pitch, width, channels):
+    pitch = int(pitch)
+    if pitch != 0 and pitch < width * channels:
+        raise ValueError("pitch %d < width * channels = %d" % (pitch, width * channels))
+    return pitch
+
+
+def _colour_plane(a, h, w, channels):
+    """a colour image [h, w, channels] of uint8 with contiguous pixels (rows may be padded)"""
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+        raise TypeError("colour plane must be a numpy uint8 array")
+    if a.shape != (h, w, channels):
+        raise ValueError("colour plane must have shape %s, not %s" % ((h, w, channels), a.shape))
+    if a.strides[1:] != (channels, 1) or a.strides[0] < w * channels:
+        a = np.ascontiguousarray(a)
+    return a
+
+
+def _depth_plane(a, h, w):
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint16:
+        raise TypeError("depth plane must be a numpy uint16 array")
+    if a.shape != (h, w):
+        raise ValueError("depth plane must have shape %s, not %s" % ((h, w), a.shape))
+    return np.ascontiguousarray(a)
+
+
 _ROLES = {"current": 0, "reference": 1}
 
 
@@ -391,6 +453,57 @@ def update_raw_host_batch(pyramids, grey_host, depth_host, depth_scale=1.0 / 500
     else:
         ccfg = config if isinstance(config, _lib.Config) else config.to_c()
         ctx.check(ctx._lib.dvo_hip_frames_update_raw_as(ctx.ptr, n, fr, g, z, depth_scale, _ROLES[role], C.byref(ccfg)))
+
+
+def _colour_call_args(pyramids, role, config):
+    if role is None:
+        return -1, None
+    if role not in _ROLES:
+        raise ValueError("role must be 'current', 'reference' or None, not %r" % (role,))
+    if config is None:
+        raise ValueError("a role needs a config")
+    return _ROLES[role], C.byref(config if isinstance(config, _lib.Config) else config.to_c())
+
+
+def update_colour_device_batch(pyramids, colour_dev_ptrs, depth_dev_ptrs, pixel_format="bgr8", pitch=0, depth_scale=1.0 / 5000.0, role=None,
+                               config=None, flags=0):
+    """Re-ingest 8-bit colour planes (device pointers, one format and row pitch in bytes for all, 0 = tight) + u16 depth planes into n
+    existing pyramids of one camera (dvo_hip_frames_update_colour_device_as_ex).  role None: a plain update; "current" / "reference"
+    with config: ingest and prepare in one pass.  flags: _lib.INGEST_DEFER | _lib.INGEST_NO_RAW_COPY."""
+    fmt, ch = _pixel_format(pixel_format)
+    pyr0 = pyramids[0]
+    pitch = _pitch(pitch, pyr0.camera.width, ch)
+    if len(colour_dev_ptrs) != len(pyramids) or len(depth_dev_ptrs) != len(pyramids):
+        raise ValueError("one colour and one depth plane per pyramid")
+    r, cfg = _colour_call_args(pyramids, role, config)
+    n = len(pyramids)
+    ctx = pyr0.ctx
+    fr, c, z = _handles(pyramids), _pointer_array(colour_dev_ptrs), _pointer_array(depth_dev_ptrs)
+    ctx.check(ctx._lib.dvo_hip_frames_update_colour_device_as_ex(ctx.ptr, n, fr, c, fmt, pitch, z, depth_scale, r, cfg, int(flags)))
+
+
+def update_colour_host_batch(pyramids, colour_host, depth_host, pixel_format="bgr8", depth_scale=1.0 / 5000.0, role=None, config=None, flags=0):
+    """Re-ingest 8-bit colour planes from HOST arrays ([h, w, 3 | 4] uint8, one format; rows may be padded by the same stride) + u16 depth
+    planes (C-contiguous) into n existing pyramids: DMA on the context's upload stream, then the batched build
+    (dvo_hip_frames_update_colour_as_ex).  The arrays must stay unchanged until upload_wait() or a match on these pyramids has returned."""
+    fmt, ch = _pixel_format(pixel_format)
+    cam = pyramids[0].camera
+    if len(colour_host) != len(pyramids) or len(depth_host) != len(pyramids):
+        raise ValueError("one colour and one depth plane per pyramid")
+    cols = [_colour_plane(a, cam.height, cam.width, ch) for a in colour_host]
+    deps = [_depth_plane(b, cam.height, cam.width) for b in depth_host]
+    if any(a is not b for a, b in zip(cols, colour_host)) or any(a is not b for a, b in zip(deps, depth_host)):
+        raise ValueError("host planes must be usable in place (pixels contiguous, depth C-contiguous): the transfer is asynchronous")
+    pitch = cols[0].strides[0]
+    if any(a.strides[0] != pitch for a in cols):
+        raise ValueError("every colour plane of a batch must have the same row stride")
+    r, cfg = _colour_call_args(pyramids, role, config)
+    n = len(pyramids)
+    ctx = pyramids[0].ctx
+    vp = C.c_void_p
+    c = (vp * n)(*[vp(a.ctypes.data) for a in cols])
+    z = (vp * n)(*[vp(b.ctypes.data) for b in deps])
+    ctx.check(ctx._lib.dvo_hip_frames_update_colour_as_ex(ctx.ptr, n, _handles(pyramids), c, fmt, pitch, z, depth_scale, r, cfg, int(flags)))
 
 
 def upload_wait(ctx):

@@ -174,6 +174,13 @@ class RgbdCameraPyramid {
   size_t numLevels() const { return levels_.size(); }
   // intensity CV_32FC1 0..255, depth CV_32FC1 metres with NaN = invalid (asserts at rgbd_image.cpp:350, 356)
   inline RgbdImagePyramidPtr create(const dvo::compat::ImageMat& base_intensity, const dvo::compat::ImageMat& base_depth);
+  // not in the reference: the pyramid of a colour frame as a camera delivers it -- an 8-bit colour plane (host memory, DVO_HIP_PIXEL_*
+  // format, row pitch in bytes, 0 = tight) and the u16 depth plane (tight).  The CV_BGR2GRAY conversion the reference's callers run
+  // before create (dvo_benchmark/src/benchmark_slam.cpp:55-69) and the depth scaling happen on the device (dvo_hip_frame_create_colour);
+  // the device frame is built here, with every level the size admits.  Level 0's host intensity / depth matrices are downloaded from
+  // the device like those of the other levels: when the pyramid is built with host mirrors on, else by syncHostMirrors().
+  inline RgbdImagePyramidPtr createFromColour(const void* colour, int pixel_format, size_t colour_pitch, const uint16_t* raw_depth,
+                                              float depth_scale = 1.0f / 5000.0f);
 
  private:
   std::vector<RgbdCameraPtr> levels_;
@@ -245,6 +252,9 @@ class RgbdImagePyramid {
     assert(dvo::compat::image_rows(intensity) == dvo::compat::image_rows(depth) && dvo::compat::image_cols(intensity) == dvo::compat::image_cols(depth));
     ctx_ = DeviceContext::current();
   }
+  // (RgbdCameraPyramid::createFromColour: a device frame built already, adopted)
+  RgbdImagePyramid(RgbdCameraPyramid& camera, dvo_hip_context* ctx, dvo_hip_frame* frame)
+      : camera_(camera), ctx_(ctx), frame_(frame), timestamp_(0) {}
   virtual ~RgbdImagePyramid() { if (frame_) dvo_hip_frame_destroy(ctx_, frame_); }
   RgbdImagePyramid(const RgbdImagePyramid&) = delete;
   RgbdImagePyramid& operator=(const RgbdImagePyramid&) = delete;
@@ -269,9 +279,11 @@ class RgbdImagePyramid {
     for (size_t l = levels_.size(); l < num_levels; ++l) {
       levels_.push_back(RgbdImagePtr(new RgbdImage(this, int(l), camera_.level(l))));
       levels_[l]->timestamp = timestamp_;
-      if (l == 0) {   // the caller's own matrices: valid without a download
+      if (l == 0 && !dvo::compat::image_empty(intensity_)) {   // the caller's own matrices: valid without a download
         levels_[0]->intensity = intensity_;
         levels_[0]->depth = depth_;
+      } else if (l == 0 && frame_ && RgbdImage::hostMirrors()) {   // (createFromColour: the grey the device converted)
+        levels_[0]->syncHostMirrors(RgbdImage::MirrorPlanes);
       }
     }
   }
@@ -310,6 +322,20 @@ inline RgbdImagePyramidPtr RgbdCameraPyramid::create(const dvo::compat::ImageMat
   return RgbdImagePyramidPtr(new RgbdImagePyramid(*this, base_intensity, base_depth));
 }
 
+inline RgbdImagePyramidPtr RgbdCameraPyramid::createFromColour(const void* colour, int pixel_format, size_t colour_pitch, const uint16_t* raw_depth,
+                                                               float depth_scale) {
+  const RgbdCamera& c0 = level(0);
+  int all = 1;
+  while (all < DVO_HIP_MAX_LEVELS && (c0.width() >> all) >= 2 && (c0.height() >> all) >= 2) ++all;
+  const float K[4] = {c0.intrinsics().fx(), c0.intrinsics().fy(), c0.intrinsics().ox(), c0.intrinsics().oy()};
+  dvo_hip_context* ctx = DeviceContext::current();
+  dvo_hip_frame* frame = 0;
+  if (!dvo_hip_check(ctx, dvo_hip_frame_create_colour(ctx, int(c0.width()), int(c0.height()), K, colour, pixel_format, colour_pitch, raw_depth,
+                                                      depth_scale, all, &frame), "dvo_hip_frame_create_colour"))
+    frame = 0;
+  return RgbdImagePyramidPtr(new RgbdImagePyramid(*this, ctx, frame));
+}
+
 inline void RgbdImage::buildAccelerationStructure() {
   if (!owner_) return;
   // The callers walk the levels of a new image (dvo_slam/src/local_tracker.cpp:163-169): the first call prepares every level that has
@@ -343,7 +369,8 @@ inline void RgbdImage::syncHostMirrors(unsigned what) {
     return;
   }
   const bool need_planes = (what & (MirrorPlanes | MirrorPointCloud | MirrorAcceleration)) != 0;
-  if (need_planes && level_ > 0 && dvo::compat::image_empty(intensity)) {
+  // (level 0 of a pyramid built from the caller's float matrices has them already; one built from a colour plane downloads its grey)
+  if (need_planes && dvo::compat::image_empty(intensity)) {
     download(0, intensity);
     download(1, depth);
   }

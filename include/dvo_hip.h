@@ -180,6 +180,40 @@ int dvo_hip_frames_update_raw_device_as_ex(dvo_hip_context* ctx, int n_frames, d
 int dvo_hip_frames_update_raw_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames,
                                     const uint8_t* const* grey, const uint16_t* const* raw_depth, float depth_scale,
                                     int role, const dvo_hip_config* cfg, unsigned flags);
+/* ---- colour ingest: an 8-bit colour plane + the u16 depth plane, converted to grey on the device ----------------------------
+ * Real frame sources deliver colour: the PNGs under a TUM sequence's rgb/ are RGB, OpenCV's imread hands over BGR, ROS cameras publish "bgr8" / "rgb8", camera
+ * SDKs emit 4-byte BGRA / RGBA surfaces.  The reference's callers convert on the host before RgbdCameraPyramid::create
+ * (dvo_benchmark/src/benchmark_slam.cpp:55-69, dvo_ros/src/camera_dense_tracking.cpp:222-224,
+ * dvo_slam/src/camera_keyframe_tracking.cpp:227-229); these entry points take the colour plane itself.  The grey value is OpenCV's
+ * CV_BGR2GRAY fixed point, (B*1868 + G*9617 + R*4899 + 8192) >> 14, and then goes through the grey ingest's pipeline unchanged: the
+ * same planes, bit for bit, as the grey entry points fed that grey plane.  The frame's copy of its raw planes stays grey u8 + depth u16
+ * (3 B per pixel), so a later role, a reselection and dvo_hip_frames_prepare work as after a grey ingest.
+ * colour_pitch = bytes from one row of the colour plane to the next, 0 = tight (width * channels); the depth plane is tight.
+ * DVO_HIP_ERR_INVALID, every frame left as it was: an unknown format, a null pointer or entry, 0 < colour_pitch < width * channels,
+ * colour_pitch >= 2^31. */
+#define DVO_HIP_PIXEL_BGR8 1  /* OpenCV imread, ROS "bgr8" */
+#define DVO_HIP_PIXEL_RGB8 2  /* TUM rgb PNGs, ROS "rgb8" */
+#define DVO_HIP_PIXEL_BGRA8 3 /* 4-byte pixels, alpha ignored */
+#define DVO_HIP_PIXEL_RGBA8 4
+/* the counterpart of dvo_hip_frame_create_raw: host planes (staged through the context's upload buffers) */
+int dvo_hip_frame_create_colour(dvo_hip_context* ctx, int width, int height, const float K[4], const void* colour, int pixel_format,
+                                size_t colour_pitch, const uint16_t* raw_depth, float depth_scale, int levels, dvo_hip_frame** out);
+/* the counterpart of dvo_hip_frame_create_raw_device: both planes in device memory */
+int dvo_hip_frame_create_colour_device(dvo_hip_context* ctx, int width, int height, const float K[4], const void* colour_dev,
+                                       int pixel_format, size_t colour_pitch, const void* raw_depth_dev, float depth_scale, int levels,
+                                       dvo_hip_frame** out);
+/* The counterparts of dvo_hip_frames_update_raw_device_as_ex / dvo_hip_frames_update_raw_as_ex.  role = DVO_HIP_ROLE_*, or -1 with
+ * cfg NULL for a plain update (dvo_hip_frames_update_raw_device / dvo_hip_frames_update_raw).  flags as there (DVO_HIP_INGEST_DEFER:
+ * device planes only, the request records the format and pitch).  From host memory a frame whose colour plane directly follows its depth
+ * plane (colour == (char*)(raw_depth + w*h), tight pitch) moves in one transfer, and so does a run of such frames that follow each other
+ * at a stride of (2 + channels)*w*h bytes rounded up to even. */
+int dvo_hip_frames_update_colour_device_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames,
+                                              const void* const* colour_dev, int pixel_format, size_t colour_pitch,
+                                              const void* const* raw_depth_dev, float depth_scale, int role, const dvo_hip_config* cfg,
+                                              unsigned flags);
+int dvo_hip_frames_update_colour_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour,
+                                       int pixel_format, size_t colour_pitch, const uint16_t* const* raw_depth, float depth_scale,
+                                       int role, const dvo_hip_config* cfg, unsigned flags);
 /* carries out every recorded ingest now; returns the first failure */
 int dvo_hip_flush_deferred(dvo_hip_context* ctx);
 int dvo_hip_upload_wait(dvo_hip_context* ctx);
@@ -431,6 +465,7 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value);
  * "rendezvous_pairs" (two-pair batches formed from concurrent single matches, see option "rendezvous"),
  * "strip_ingests" (frames whose raw planes went through the strip ingest, one 128 x 8 strip per wavefront -- even-width rows and
  * 4 / 8-byte aligned planes; the others take the tile kernel),
+ * "colour_ingests" (frames ingested from an 8-bit colour plane, dvo_hip_frame_create_colour* / dvo_hip_frames_update_colour*),
  * "warmup_wait_us" (the longest of the nine stream waits dvo_hip_context_create makes on trivial commands to warm up the runtime's wait
  * path, in microseconds: the first GPU process on a fresh box has been seen to spend 14-24 ms in its first wait),
  * "host_batches" and "host_ns_prepare" / "host_ns_enqueue" / "host_ns_wait" / "host_ns_finish" (nanoseconds the calling thread spent
