@@ -391,6 +391,7 @@ struct dvo_hip_context {
   int opt_keep_raw_copy = 1;       // 0: a frame ingested straight into the reference role keeps no copy of its raw planes (option "keep_raw_copy")
   long long deferred_ingests = 0;  // ingests carried out behind the first launches of a match (counter "deferred_ingests")
   int opt_build_workgroups = 0;    // cap on the workgroups of a build-stream kernel (0 = one per tile): background builds
+  int opt_stream_policy = 1;       // build-stream strip kernels stream raw planes and levels 0-1 non-temporally (option "stream_policy")
   int opt_tail_speculation = 0;    // 1: always enqueue the step ahead of the poll, also on the tail of a level whose empty step is costly (measurement)
   int opt_solver_waves = 0;        // wavefronts of a solver-step workgroup: 0 = by level and batch size, 2, 4
   int opt_ll_blocks = 0;           // workgroups per pair of the log-likelihood pass (0 = by batch size)

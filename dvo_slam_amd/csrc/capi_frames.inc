@@ -354,7 +354,7 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
           if ((c_levels >> l & 1) && frames[i]->lv[l].C) frames[i]->lv[l].cur_have |= kCurC;
     }
     launch_build_from_raw(bs, tbl, n, depth_scale, cam->w[0], cam->h[0], levels, role, wide, ithr, dthr, ctx->opt_build_workgroups, flavor0, c_levels,
-                          channels);
+                          channels, ctx->opt_stream_policy != 0);
     if (ingest_strips_supports(cam->w[0], wide)) ctx->strip_ingests += n;
     if (colour) ctx->colour_ingests += n;
   }
@@ -374,6 +374,7 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
   DevBuf& table = eager ? (role == 0 ? ctx->prep_tbl_cur : ctx->prep_tbl_ref) : (role == 0 ? ctx->role_tbl_cur : ctx->role_tbl_ref);
   hipStream_t stream = eager ? ctx->build_stream : ctx->stream;
   const int cap = eager ? ctx->opt_build_workgroups : 0;   // planes needed right now are built at full width
+  const bool stream_nt = eager && ctx->opt_stream_policy != 0;
   // Every frame is checked before the state of any is touched: a frame ingested straight into a role without a copy of its raw planes
   // (option "keep_raw_copy" 0) has nothing its level 0 could be derived from in another role, and the marks below -- planes "built" --
   // are set while the launches are still being gathered (round-5 advisor finding: the error used to leave earlier frames of the list
@@ -502,14 +503,15 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
       if (!from_planes[miss].empty()) {
         int rc = upload(from_planes[miss], &tbl);
         if (rc != DVO_HIP_OK) return rc;
-        if (role == 0) launch_derive_current(stream, tbl, int(from_planes[miss].size()), l, cam->w[l], cam->h[l], cap, miss);
-        else launch_derive_reference(stream, tbl, int(from_planes[miss].size()), l, cam->w[l], cam->h[l], ithr, dthr, cap);
+        if (role == 0) launch_derive_current(stream, tbl, int(from_planes[miss].size()), l, cam->w[l], cam->h[l], cap, miss, stream_nt);
+        else launch_derive_reference(stream, tbl, int(from_planes[miss].size()), l, cam->w[l], cam->h[l], ithr, dthr, cap, stream_nt);
         launched = true;
       }
       if (!from_raw[miss].empty()) {
         int rc = upload(from_raw[miss], &tbl, /*plane_pointers_only=*/false);
         if (rc != DVO_HIP_OK) return rc;
-        launch_build_from_raw(stream, tbl, int(from_raw[miss].size()), raw_scale, cam->w[0], cam->h[0], /*levels=*/1, role, cam->w[0] % 4 == 0, ithr, dthr, cap, miss);
+        launch_build_from_raw(stream, tbl, int(from_raw[miss].size()), raw_scale, cam->w[0], cam->h[0], /*levels=*/1, role, cam->w[0] % 4 == 0, ithr, dthr, cap, miss,
+                              0, 0, stream_nt);
         launched = true;
       }
     }

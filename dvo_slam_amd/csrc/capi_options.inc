@@ -227,6 +227,11 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value) {
     if (!value) DVO_FLUSH_DEFERRED(ctx);
     return DVO_HIP_OK;
   }
+  if (std::strcmp(key, "stream_policy") == 0) {
+    if (value != 0 && value != 1) return fail(ctx, DVO_HIP_ERR_INVALID, "stream_policy must be 0 or 1");
+    ctx->opt_stream_policy = value;
+    return DVO_HIP_OK;
+  }
   if (std::strcmp(key, "keep_raw_copy") == 0) {
     if (value != 0 && value != 1) return fail(ctx, DVO_HIP_ERR_INVALID, "keep_raw_copy must be 0 or 1");
     ctx->opt_keep_raw_copy = value;

@@ -18,10 +18,27 @@ template <typename T> __device__ __forceinline__ Global<T> global_ptr(T* p) { re
 typedef float GlobalF32x2 __attribute__((ext_vector_type(2)));
 typedef float GlobalF32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned GlobalU32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void gstore(Global<float2> p, float2 v) { *(Global<GlobalF32x2>)p = GlobalF32x2{v.x, v.y}; }
-__device__ __forceinline__ void gstore(Global<float4> p, float4 v) { *(Global<GlobalF32x4>)p = GlobalF32x4{v.x, v.y, v.z, v.w}; }
+
+// NT: the access carries the non-temporal policy (`nt`).  Lines a kernel streams that way do not displace what other kernels keep in the
+// Infinity Cache (scripts/ubench/cache_policy.hip): for planes read once, or read next only after many more bytes
+// than the cache holds have gone by.  Values are the same either way.
+template <bool NT, typename T>
+__device__ __forceinline__ T gld(Global<const T> p) {
+  if constexpr (NT) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+template <bool NT, typename T>
+__device__ __forceinline__ void gst(Global<T> p, T v) {
+  if constexpr (NT) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+template <bool NT = false>
+__device__ __forceinline__ void gstore(Global<float2> p, float2 v) { gst<NT>((Global<GlobalF32x2>)p, GlobalF32x2{v.x, v.y}); }
+template <bool NT = false>
+__device__ __forceinline__ void gstore(Global<float4> p, float4 v) { gst<NT>((Global<GlobalF32x4>)p, GlobalF32x4{v.x, v.y, v.z, v.w}); }
 // two adjacent float2 elements (16-byte aligned) in one store
-__device__ __forceinline__ void gstore_pair(Global<float2> p, float4 v) { *(Global<GlobalF32x4>)p = GlobalF32x4{v.x, v.y, v.z, v.w}; }
+template <bool NT = false>
+__device__ __forceinline__ void gstore_pair(Global<float2> p, float4 v) { gst<NT>((Global<GlobalF32x4>)p, GlobalF32x4{v.x, v.y, v.z, v.w}); }
 __device__ __forceinline__ float2 gload(Global<const float2> p) {
   const GlobalF32x2 v = *(Global<const GlobalF32x2>)p;
   return make_float2(v.x, v.y);

@@ -46,10 +46,10 @@ __device__ __forceinline__ float row_shifted(float v) {   // within a row of 16 
 
 // the 8 bytes that hold pixels x, x + 1 (x even) of a colour row with CH bytes per pixel (see the head of the file); two dword loads
 // the compiler merges into one 8-byte load (the window is 4-byte aligned only)
-template <int CH>
+template <int CH, bool NT>
 __device__ __forceinline__ unsigned long long colour_pair_bits(Global<const uint8_t> row, int x) {
   const Global<const unsigned> at = (Global<const unsigned>)(row + ((CH * x) & ~3));
-  return (unsigned long long)at[1] << 32 | at[0];
+  return (unsigned long long)gld<NT>(at + 1) << 32 | gld<NT>(at);
 }
 // the grey bytes of pixels x, x + 1 from colour_pair_bits: grey(x) | grey(x + 1) << 8, as a grey plane's 16-bit load would give them
 template <int CH>
@@ -63,7 +63,7 @@ __device__ __forceinline__ unsigned colour_pair_grey(unsigned long long bits, in
 // The role planes of a strip's 8 rows from its register rows: I / Z[j] = image row y0 + kFirst + j (clamped), kFirst = -1 with TAPS;
 // eI / eZ[r]: the strip's edge columns (lane 0: the column left of the strip, lane 63: the column right of it).  Returns the number of
 // selected pixels of the wavefront (ROLE 1).
-template <int ROLE, bool TAPS>
+template <int ROLE, bool TAPS, bool NT>
 __device__ __forceinline__ int strip_role_planes(const float (&I)[TAPS ? kStripH + 2 : kStripH][2], const float (&Z)[TAPS ? kStripH + 2 : kStripH][2],
                                                  const float (&eI)[kStripH], const float (&eZ)[kStripH], int x, int y0, int w0, int h0, bool in_x,
                                                  Global<float2> R0, Global<float4> A0, Global<float2> B0, Global<float2> C0, int cur_flavor,
@@ -95,18 +95,18 @@ __device__ __forceinline__ int strip_role_planes(const float (&I)[TAPS ? kStripH
                              (fabsf(idx0) > ithr || fabsf(idy0) > ithr || fabsf(zdx0) > dthr || fabsf(zdy0) > dthr);
             const bool ok1 = inside && z1 == z1 && zdx1 == zdx1 && zdy1 == zdy1 &&
                              (fabsf(idx1) > ithr || fabsf(idy1) > ithr || fabsf(zdx1) > dthr || fabsf(zdy1) > dthr);
-            if (inside) gstore_pair(R0 + at, make_float4(ok0 ? z0 : nanv, i0, ok1 ? z1 : nanv, i1));
+            if (inside) gstore_pair<NT>(R0 + at, make_float4(ok0 ? z0 : nanv, i0, ok1 ? z1 : nanv, i1));
             count += __popcll(__ballot(ok0)) + __popcll(__ballot(ok1));   // wave-uniform
           } else if (inside) {
             if (cur_flavor & kCurAB) {
-              gstore(A0 + at, make_float4(i0, z0, idx0, idy0));
-              gstore(A0 + at + 1, make_float4(i1, z1, idx1, idy1));
-              gstore_pair(B0 + at, make_float4(zdx0, zdy0, zdx1, zdy1));
+              gstore<NT>(A0 + at, make_float4(i0, z0, idx0, idy0));
+              gstore<NT>(A0 + at + 1, make_float4(i1, z1, idx1, idy1));
+              gstore_pair<NT>(B0 + at, make_float4(zdx0, zdy0, zdx1, zdy1));
             }
-            if (cur_flavor & kCurC) gstore_pair(C0 + at, make_float4(i0, z0, i1, z1));
+            if (cur_flavor & kCurC) gstore_pair<NT>(C0 + at, make_float4(i0, z0, i1, z1));
           }
         } else if (inside) {
-          gstore_pair(C0 + at, make_float4(i0, z0, i1, z1));
+          gstore_pair<NT>(C0 + at, make_float4(i0, z0, i1, z1));
         }
       }
   return count;
@@ -116,7 +116,9 @@ __device__ __forceinline__ int strip_role_planes(const float (&I)[TAPS ? kStripH
 // TAPS: level 0 needs the central differences (reference role; current role with the gathered taps A + B).
 // c_levels: bit l set = pyramid level l (1-3) also gets the current role's {I, Z} plane C.
 // CH: 0 = the grey plane f.grey, 3 / 4 = the colour plane f.colour with 3 / 4 bytes per pixel.
-template <int ROLE, bool TAPS, int CH = 0>
+// NT: the raw planes are read, and the planes of levels 0-1 and the raw copy written, with the non-temporal policy (global_ptr.h): a
+// background build beside the coarse levels of a match then leaves their planes in the Infinity Cache.  Levels 2-3 keep the default.
+template <int ROLE, bool TAPS, int CH = 0, bool NT = false>
 __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __restrict__ tbl, float scale, int w0, int h0, int levels,
                                                        float ithr, float dthr, int groups_x, int groups_y, int n_frames, int cur_flavor, int c_levels) {
 #pragma clang fp contract(off)
@@ -161,9 +163,9 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
     for (int j = 0; j < kRows; ++j) {
       const int y = min(max(y0 + kFirst + j, 0), h0 - 1);       // (scalar)
       const size_t row = size_t(y) * w0;
-      if (CH) cb[j] = colour_pair_bits<CH>(colour + size_t(y) * pitch, xl);
-      else g[j] = *(Global<const uint16_t>)(grey + row + xl);
-      d[j] = *(Global<const uint32_t>)(raw + row + xl);
+      if (CH) cb[j] = colour_pair_bits<CH, NT>(colour + size_t(y) * pitch, xl);
+      else g[j] = gld<NT>((Global<const uint16_t>)(grey + row + xl));
+      d[j] = gld<NT>((Global<const uint32_t>)(raw + row + xl));
     }
     unsigned ge[kStripH], de[kStripH];                          // the strip's edge columns, rows y0 .. y0 + 7: lane 0 left, the others right
     unsigned long long cbe[CH && TAPS ? kStripH : 1];           // (colour: the bytes of the pair that holds the edge column)
@@ -176,9 +178,9 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
         ge[r] = 0u; de[r] = 0u;
         if (CH) cbe[r] = 0ull;
         if (edge_lane) {
-          if (CH) cbe[r] = colour_pair_bits<CH>(colour + size_t(min(y0 + r, h0 - 1)) * pitch, xe & ~1);
-          else ge[r] = grey[row + xe];
-          de[r] = raw[row + xe];
+          if (CH) cbe[r] = colour_pair_bits<CH, NT>(colour + size_t(min(y0 + r, h0 - 1)) * pitch, xe & ~1);
+          else ge[r] = gld<NT>(grey + row + xe);
+          de[r] = gld<NT>(raw + row + xe);
         }
       }
     }
@@ -196,8 +198,8 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
         const int y = y0 + r;
         if (y < h0) {
           const size_t at = size_t(y) * w0 + x;
-          *(Global<uint16_t>)(keep_grey + at) = uint16_t(g[r - kFirst]);
-          *(Global<uint32_t>)(keep_raw + at) = d[r - kFirst];
+          gst<NT>((Global<uint16_t>)(keep_grey + at), uint16_t(g[r - kFirst]));
+          gst<NT>((Global<uint32_t>)(keep_raw + at), d[r - kFirst]);
         }
       }
     }
@@ -214,7 +216,7 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
 #pragma unroll
       for (int r = 0; r < kStripH; ++r) { eI[r] = float(ge[r]); eZ[r] = depth_of(de[r]); }
     }
-    const int count = ROLE >= 0 ? strip_role_planes<ROLE, TAPS>(I, Z, eI, eZ, x, y0, w0, h0, in_x, R0, A0, B0, C0, cur_flavor, ithr, dthr) : 0;
+    const int count = ROLE >= 0 ? strip_role_planes<ROLE, TAPS, NT>(I, Z, eI, eZ, x, y0, w0, h0, in_x, R0, A0, B0, C0, cur_flavor, ithr, dthr) : 0;
     if (ROLE == 1 && lane == 0 && count) atomicAdd((int*)sel_count, count);
 
     // ---- pyramid levels 1-3: 64 x 4, 32 x 2 and 16 x 1 pixels per strip; an out-of-image quad is never written ----
@@ -228,9 +230,9 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
       z1v[k] = Z[j][0];                                                 // top-left sample, NaN holes kept (Q18)
       if (x1 < w1 && y1 < h1) {
         const size_t at = size_t(y1) * w1 + x1;
-        I1[at] = m1[k];
-        Z1[at] = z1v[k];
-        if (want_c1) gstore(C1 + at, make_float2(m1[k], z1v[k]));
+        gst<NT>(I1 + at, m1[k]);
+        gst<NT>(Z1 + at, z1v[k]);
+        if (want_c1) gstore<NT>(C1 + at, make_float2(m1[k], z1v[k]));
       }
     }
     if (levels < 3) continue;
@@ -263,7 +265,8 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
 // same strips, the same role code, 8-byte loads of pixel pairs instead of the raw planes' 2 + 4 bytes.  Replaces k_derive_current /
 // k_derive_reference (one pixel per thread, ten scattered 4-byte loads each: 3 TB/s) for batches; a single camera frame's levels go
 // through k_derive_levels (one launch for all of them).
-template <int ROLE, bool TAPS>
+// NT: loads and stores with the non-temporal policy (the ingest's NT, for level 1 of a background build).
+template <int ROLE, bool TAPS, bool NT = false>
 __global__ __launch_bounds__(256) void k_derive_strips(const FrameBuildPtrs* __restrict__ tbl, int level, int w0, int h0, float ithr, float dthr,
                                                        int groups_x, int groups_y, int n_frames, int cur_flavor) {
 #pragma clang fp contract(off)
@@ -293,8 +296,8 @@ __global__ __launch_bounds__(256) void k_derive_strips(const FrameBuildPtrs* __r
     for (int j = 0; j < kRows; ++j) {
       const int y = min(max(y0 + kFirst + j, 0), h0 - 1);
       const size_t row = size_t(y) * w0;
-      const GlobalF32x2 iv = *(Global<const GlobalF32x2>)(Ip + row + xl);
-      const GlobalF32x2 zv = *(Global<const GlobalF32x2>)(Zp + row + xl);
+      const GlobalF32x2 iv = gld<NT>((Global<const GlobalF32x2>)(Ip + row + xl));
+      const GlobalF32x2 zv = gld<NT>((Global<const GlobalF32x2>)(Zp + row + xl));
       I[j][0] = iv.x; I[j][1] = iv.y;
       Z[j][0] = zv.x; Z[j][1] = zv.y;
     }
@@ -307,12 +310,12 @@ __global__ __launch_bounds__(256) void k_derive_strips(const FrameBuildPtrs* __r
         const size_t row = size_t(min(y0 + r, h0 - 1)) * w0;
         eI[r] = 0.0f; eZ[r] = 0.0f;
         if (edge_lane) {
-          eI[r] = Ip[row + xe];
-          eZ[r] = Zp[row + xe];
+          eI[r] = gld<NT>(Ip + row + xe);
+          eZ[r] = gld<NT>(Zp + row + xe);
         }
       }
     }
-    const int count = strip_role_planes<ROLE, TAPS>(I, Z, eI, eZ, x, y0, w0, h0, in_x, Rl, Al, Bl, Cl, cur_flavor, ithr, dthr);
+    const int count = strip_role_planes<ROLE, TAPS, NT>(I, Z, eI, eZ, x, y0, w0, h0, in_x, Rl, Al, Bl, Cl, cur_flavor, ithr, dthr);
     if (ROLE == 1 && lane == 0 && count) atomicAdd((int*)sel_count + level, count);
   }
 }
@@ -320,14 +323,21 @@ __global__ __launch_bounds__(256) void k_derive_strips(const FrameBuildPtrs* __r
 bool derive_strips_supports(int w) { return w % 2 == 0 && w >= 4; }
 
 // role 0: current (flavours cur_flavor), role 1: reference (the level's counters zeroed before by the caller's k_zero_counts)
+// stream_nt: the non-temporal policy at levels 0-1 (launch.h)
 void launch_derive_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int role, float ithr, float dthr,
-                          int max_workgroups, int cur_flavor) {
+                          int max_workgroups, int cur_flavor, bool stream_nt) {
   const int gx = (w + kStripW - 1) / kStripW, gy = (h + kStripH * kStripsPerGroup - 1) / (kStripH * kStripsPerGroup);
   const long long total = (long long)gx * gy * n_frames;
   const dim3 grid(int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total)), block(256);
-  if (role == 1) k_derive_strips<1, true><<<grid, block, 0, s>>>(tbl, level, w, h, ithr, dthr, gx, gy, n_frames, cur_flavor);
-  else if (cur_flavor & kCurAB) k_derive_strips<0, true><<<grid, block, 0, s>>>(tbl, level, w, h, ithr, dthr, gx, gy, n_frames, cur_flavor);
-  else k_derive_strips<0, false><<<grid, block, 0, s>>>(tbl, level, w, h, ithr, dthr, gx, gy, n_frames, cur_flavor);
+#define DVO_LAUNCH_DERIVE(ROLE, TAPS)                                                                                       \
+  do {                                                                                                                      \
+    if (stream_nt && level <= 1) k_derive_strips<ROLE, TAPS, true><<<grid, block, 0, s>>>(tbl, level, w, h, ithr, dthr, gx, gy, n_frames, cur_flavor); \
+    else k_derive_strips<ROLE, TAPS><<<grid, block, 0, s>>>(tbl, level, w, h, ithr, dthr, gx, gy, n_frames, cur_flavor);  \
+  } while (0)
+  if (role == 1) DVO_LAUNCH_DERIVE(1, true);
+  else if (cur_flavor & kCurAB) DVO_LAUNCH_DERIVE(0, true);
+  else DVO_LAUNCH_DERIVE(0, false);
+#undef DVO_LAUNCH_DERIVE
 }
 
 bool ingest_strips_supports(int w0, bool wide) { return wide && w0 % 4 == 0; }
@@ -339,13 +349,16 @@ bool colour_strips_aligned(const void* colour, size_t pitch, int channels) {
 }
 
 void launch_ingest_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role,
-                          float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels) {
+                          float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels, bool stream_nt) {
   const int gx = (w0 + kStripW - 1) / kStripW, gy = (h0 + kStripH * kStripsPerGroup - 1) / (kStripH * kStripsPerGroup);
   const long long total = (long long)gx * gy * n_frames;
   const dim3 grid(int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total)), block(256);
   const int lv = levels < 4 ? levels : 4;
-#define DVO_LAUNCH_STRIPS(ROLE, TAPS, CH) \
-  k_ingest_strips<ROLE, TAPS, CH><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, gx, gy, n_frames, cur_flavor, c_levels)
+#define DVO_LAUNCH_STRIPS(ROLE, TAPS, CH)                                                                                       \
+  do {                                                                                                                          \
+    if (stream_nt) k_ingest_strips<ROLE, TAPS, CH, true><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, gx, gy, n_frames, cur_flavor, c_levels); \
+    else k_ingest_strips<ROLE, TAPS, CH><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, gx, gy, n_frames, cur_flavor, c_levels); \
+  } while (0)
 #define DVO_LAUNCH_STRIPS_ROLE(CH)                                          \
   do {                                                                      \
     if (role == 1) DVO_LAUNCH_STRIPS(1, true, CH);                          \

@@ -20,25 +20,29 @@ void launch_pyr_down(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int
 // c_levels: bit l set = pyramid level l (1..3) also gets the current role's {I, Z} plane C in the same pass (ingest_strips.hip only:
 // ingest_strips_supports tells the caller whether the pass will honour it)
 // colour_channels: 0 = grey planes, 3 / 4 = every frame's colour plane (FrameBuildPtrs::colour) with that many bytes per pixel
+// stream_nt: the strip kernels read the raw planes and write the planes of levels 0-1 with the non-temporal policy (global_ptr.h; the
+// option "stream_policy" for the build stream's launches)
 void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role, bool wide,
-                           float ithr, float dthr, int max_workgroups, int cur_flavor = kCurAB, int c_levels = 0, int colour_channels = 0);
+                           float ithr, float dthr, int max_workgroups, int cur_flavor = kCurAB, int c_levels = 0, int colour_channels = 0,
+                           bool stream_nt = false);
 // ingest_strips.hip: the role planes of one level from the float planes I / Z in strips (even widths); role 1: counters zeroed before
 bool derive_strips_supports(int w);
 void launch_derive_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int role, float ithr, float dthr,
-                          int max_workgroups, int cur_flavor);
+                          int max_workgroups, int cur_flavor, bool stream_nt = false);
 // ingest_strips.hip: the same pass with one 128 x 8 strip per wavefront, registers only (even widths, aligned planes)
 bool ingest_strips_supports(int w0, bool wide);
 // a colour plane's share of `wide`: its address and row pitch suit the strip kernel's loads for `channels` bytes per pixel
 bool colour_strips_aligned(const void* colour, size_t pitch, int channels);
 // colour_channels: 0 = the grey plane of every frame, 3 / 4 = the colour plane (FrameBuildPtrs::colour) with that many bytes per pixel
 void launch_ingest_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role,
-                          float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels = 0);
-void launch_derive_current(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int max_workgroups, int cur_flavor = kCurAB);
+                          float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels = 0, bool stream_nt = false);
+void launch_derive_current(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int max_workgroups, int cur_flavor = kCurAB,
+                           bool stream_nt = false);
 // mode 0: A + B from C; 1: C from A; 2: R + selection count from C (the level's counters are zeroed first)
 void launch_from_current_plane(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int mode, float ithr, float dthr,
                                int max_workgroups);
 void launch_derive_reference(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, float ithr, float dthr,
-                             int max_workgroups);
+                             int max_workgroups, bool stream_nt = false);
 // the role planes (role 0: current, flavours per level in span.flavor; role 1: reference) of the levels span.l0 .. span.l1 in one launch
 void launch_derive_levels(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, const LevelSpan& span, int role, float ithr, float dthr,
                           int max_workgroups);

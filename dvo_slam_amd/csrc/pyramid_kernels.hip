@@ -468,10 +468,10 @@ static int capped_grid(int tiles_x, int tiles_y, int n_frames, int max_workgroup
 }
 
 void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role, bool wide,
-                           float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels) {
+                           float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels, bool stream_nt) {
   if (ingest_strips_supports(w0, wide)) {
     if (role == 1) k_zero_counts<<<dim3((n_frames + 63) / 64), dim3(64), 0, s>>>(tbl, n_frames, 0);
-    launch_ingest_strips(s, tbl, n_frames, scale, w0, h0, levels, role, ithr, dthr, max_workgroups, cur_flavor, c_levels, colour_channels);
+    launch_ingest_strips(s, tbl, n_frames, scale, w0, h0, levels, role, ithr, dthr, max_workgroups, cur_flavor, c_levels, colour_channels, stream_nt);
     return;
   }
   const int tx = (w0 + kB0W - 1) / kB0W, ty = (h0 + kB0H - 1) / kB0H;
@@ -500,9 +500,10 @@ void launch_pyr_down(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int
 }
 
 // (even widths: the strip form, ingest_strips.hip)
-void launch_derive_current(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int max_workgroups, int cur_flavor) {
+void launch_derive_current(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int max_workgroups, int cur_flavor,
+                           bool stream_nt) {
   if (derive_strips_supports(w)) {
-    launch_derive_strips(s, tbl, n_frames, level, w, h, 0, 0.0f, 0.0f, max_workgroups, cur_flavor);
+    launch_derive_strips(s, tbl, n_frames, level, w, h, 0, 0.0f, 0.0f, max_workgroups, cur_flavor, stream_nt);
     return;
   }
   const int tx = (w + 63) / 64, ty = (h + 3) / 4;
@@ -532,10 +533,10 @@ void launch_derive_levels(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames
 }
 
 void launch_derive_reference(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, float ithr, float dthr,
-                             int max_workgroups) {
+                             int max_workgroups, bool stream_nt) {
   k_zero_counts<<<dim3((n_frames + 63) / 64), dim3(64), 0, s>>>(tbl, n_frames, level);
   if (derive_strips_supports(w)) {
-    launch_derive_strips(s, tbl, n_frames, level, w, h, 1, ithr, dthr, max_workgroups, 0);
+    launch_derive_strips(s, tbl, n_frames, level, w, h, 1, ithr, dthr, max_workgroups, 0, stream_nt);
     return;
   }
   const int tx = (w + 63) / 64, ty = (h + 15) / 16;

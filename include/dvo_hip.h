@@ -340,6 +340,10 @@ int dvo_hip_time_stream_mix(dvo_hip_context* ctx, int n_pairs,
  * pixel, from which its other role -- or a selection with other thresholds -- is derived later; 0: no copy: such a frame serves as a
  * reference with the thresholds it was ingested for until it is ingested again, anything else fails with DVO_HIP_ERR_INVALID.  The
  * value in effect when the ingest is requested counts; dvo_slam_amd/apps/stream_pipeline.cpp switches it off for its reference frames),
+ * "stream_policy" (default 1: the strip kernels of a build on the build stream -- the ingest of raw planes and the role planes derived
+ * there -- read the raw planes and write the planes of levels 0-1 and the raw copy with the non-temporal cache policy, so that a
+ * background build does not push the planes of the coarse levels a running match re-reads out of the device's last-level cache; levels
+ * 2-3 keep the default policy.  Planes and records are the same bit for bit either way; 0: the default policy everywhere, for A/B runs),
  * "table_cache" (default 1: a small table -- plane pointers of the frames to build or the pairs to align, initial guesses -- is not sent
  * to the device again when the very bytes were last sent to the very address on the same stream and no device memory was freed since:
  * a streaming caller hands over the same frame sets step after step; counter "table_uploads_skipped"; 0 for measurement),
