@@ -67,7 +67,7 @@ EXPORTS = [
     "dvo_hip_set_option", "dvo_hip_get_counter", "dvo_hip_version",
     "dvo_hip_frames_update_raw_device_as_ex", "dvo_hip_frames_update_raw_as_ex", "dvo_hip_flush_deferred", "dvo_hip_context_device",
     "dvo_hip_frame_create_colour", "dvo_hip_frame_create_colour_device", "dvo_hip_frames_update_colour_device_as_ex",
-    "dvo_hip_frames_update_colour_as_ex",
+    "dvo_hip_frames_update_colour_as_ex", "dvo_hip_frames_set_selection", "dvo_hip_frames_clear_selection", "dvo_hip_frame_set_level_selection",
     "dvo_hip_comm_get_unique_id", "dvo_hip_comm_create", "dvo_hip_comm_destroy", "dvo_hip_comm_rank", "dvo_hip_comm_size",
     "dvo_hip_comm_last_error", "dvo_hip_gather_records_begin", "dvo_hip_gather_records_end", "dvo_hip_gather_records",
 ]
@@ -151,6 +151,9 @@ def lib():
     L.dvo_hip_frames_update_colour_as_ex.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_size_t, C.POINTER(vp), C.c_float,
                                                      C.c_int, C.POINTER(Config), C.c_uint]
     L.dvo_hip_flush_deferred.argtypes = [vp]
+    L.dvo_hip_frames_set_selection.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_size_t, C.c_int, C.c_float, C.c_float]
+    L.dvo_hip_frames_clear_selection.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    L.dvo_hip_frame_set_level_selection.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_uint8)]
     L.dvo_hip_context_device.argtypes = [vp]
     L.dvo_hip_comm_get_unique_id.argtypes = [vp]
     L.dvo_hip_comm_create.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]

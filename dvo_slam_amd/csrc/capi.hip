@@ -29,6 +29,7 @@
 #include "colour.h"
 #include "launch.h"
 #include "ref_order.h"
+#include "selection.h"
 
 using namespace dvo_hip;
 
@@ -106,6 +107,7 @@ struct FrameLevel {
   int cur_have = 0;            // flavours of the current-frame role that are built: kCurAB (A, B) | kCurC (C)
   bool selected = false;       // R / count built for (ithr, dthr) (reference role)
   bool q3 = false;             // ... and its last selected pixel cleared if the count is odd (option "ref_order", ref_order.hip)
+  bool explicit_sel = false;   // ... or R / count hold an accepted set the caller handed over (dvo_hip_frame_set_level_selection)
   float ithr = 0, dthr = 0;
 };
 
@@ -125,6 +127,13 @@ struct dvo_hip_frame {
   bool raw0 = false;
   bool raw_copy = false;
   float depth_scale = 0.0f;
+  // The caller selection of the reference role (dvo_hip_frames_set_selection): the frame's own copy of the level-0 mask (w0 bytes per
+  // row) and the depth range, applied by k_apply_selection wherever a plane R is built.  Kept across re-ingests.
+  bool sel_on = false;
+  bool sel_has_mask = false;
+  float sel_min = 0.0f, sel_max = INFINITY;
+  DevBuf sel_mask;
+  unsigned long long sel_visit = 0;   // (apply_selection: the call that last listed the frame)
 };
 
 // Small host -> device transfers (pointer tables, initial guesses) go through slots of pinned memory: from a pageable
@@ -479,6 +488,8 @@ struct dvo_hip_context {
   static constexpr size_t kFramePoolMaxBlocks = 64;
   Workspace ws[1];
   DevBuf misc, role_tbl_cur, role_tbl_ref, prep_tbl_cur, prep_tbl_ref;
+  DevBuf sel_tbl_main, sel_tbl_build;                 // tables of the caller-selection apply pass, one per stream (apply_selection)
+  unsigned long long sel_visits = 0;
   static const int kTableSlots = 4;
   DevBuf build_tbl[kTableSlots];   // (a few, picked by the list's first frame: see Workspace::pair_ptrs)
   DevBuf* build_tbl_cur = nullptr; // the one that holds the table of build_tbl_frames
@@ -805,7 +816,8 @@ void dvo_hip_context_destroy(dvo_hip_context* ctx) {
     if (ev) (void)hipEventDestroy(ev);
   if (ctx->build_stream) (void)hipStreamDestroy(ctx->build_stream);
   for (DevBuf& b : ctx->build_tbl) b.release();
-  for (DevBuf* b : {&ctx->misc, &ctx->role_tbl_cur, &ctx->role_tbl_ref, &ctx->prep_tbl_cur, &ctx->prep_tbl_ref, &ctx->rcp_table, &ctx->ref_order_planes}) b->release();
+  for (DevBuf* b : {&ctx->misc, &ctx->role_tbl_cur, &ctx->role_tbl_ref, &ctx->prep_tbl_cur, &ctx->prep_tbl_ref, &ctx->rcp_table, &ctx->ref_order_planes,
+                    &ctx->sel_tbl_main, &ctx->sel_tbl_build}) b->release();
   for (DevBuf& b : ctx->upload_buf) b.release();
   for (const dvo_hip_context::PooledBlock& b : ctx->frame_pool) (void)hipFree(b.p);
   ctx->frame_pool.clear();
@@ -1346,6 +1358,7 @@ void dvo_hip_frame_destroy(dvo_hip_context* ctx, dvo_hip_frame* frame) {
       if (ctx->build_stream) (void)hipStreamSynchronize(ctx->build_stream);
     }
   }
+  frame->sel_mask.release();
   frame->pool.release();
   delete frame;
 }
@@ -1392,6 +1405,7 @@ int dvo_hip_frame_select(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, 
     mask_dev = ctx->misc.as<uint8_t>();
   }
   dvo_hip_frame* one[1] = {frame};
+  if (frame->lv[level].explicit_sel) frame->lv[level].selected = false;   // (a selection for thresholds replaces an explicit one)
   int rc = wait_for_build(ctx, 1, one);
   if (rc == DVO_HIP_OK) rc = ensure_roles(ctx, 1, one, 1, level, level, ithr, dthr);
   if (rc == DVO_HIP_OK && mask_dev) rc = ensure_roles(ctx, 1, one, 0, level, level, 0.0f, 0.0f);
@@ -1400,13 +1414,102 @@ int dvo_hip_frame_select(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, 
     FrameLevel& L = frame->lv[level];
     DVO_HIP_TRY(ctx, hipMemsetAsync(frame->sel_count + level, 0, sizeof(int), ctx->stream));
     launch_select_pack(ctx->stream, L.A, L.B, L.w * L.h, ithr, dthr, L.R, frame->sel_count + level, mask_dev);
-    L.q3 = false;                                            // (a fresh plane R)
+    mark_selected(L, ithr, dthr);
+    rc = apply_selection(ctx, ctx->stream, 1, one, level, level, 0, mask_dev);
+    if (rc != DVO_HIP_OK) return rc;
   }
   int count = 0;
   DVO_HIP_TRY(ctx, hipMemcpyAsync(&count, frame->sel_count + level, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
   if (mask_or_null) DVO_HIP_TRY(ctx, hipMemcpyAsync(mask_or_null, mask_dev, n, hipMemcpyDeviceToHost, ctx->stream));
   DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (n_selected) *n_selected = count;
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_frames_set_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const uint8_t* const* masks,
+                                 size_t mask_pitch, int masks_on_device, float min_depth, float max_depth) {
+  std::unique_lock<std::recursive_mutex> guard;
+  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
+  DVO_FLUSH_DEFERRED(ctx);
+  if (!ctx || n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_selection: bad argument");
+  if (!(min_depth <= max_depth)) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_selection: need min_depth <= max_depth (no NaN)");
+  for (int i = 0; i < n_frames; ++i) {
+    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_selection: null frame");
+    const size_t w0 = size_t(frames[i]->lv[0].w);
+    if (masks && masks[i] && mask_pitch != 0 && mask_pitch < w0) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_selection: mask_pitch < width");
+  }
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t bs = ctx->build_stream;
+  bool any_mask = false, any_host = false;
+  for (int i = 0; i < n_frames; ++i) {
+    dvo_hip_frame* f = frames[i];
+    const uint8_t* m = masks ? masks[i] : nullptr;
+    const size_t w0 = size_t(f->lv[0].w), h0 = size_t(f->lv[0].h);
+    if (m) {
+      DVO_HIP_TRY(ctx, f->sel_mask.reserve(w0 * h0));
+      // on the build stream: behind every build that may still read the frame's previous mask, ahead of every later one
+      DVO_HIP_TRY(ctx, hipMemcpy2DAsync(f->sel_mask.p, w0, m, mask_pitch ? mask_pitch : w0, w0, h0,
+                                        masks_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, bs));
+      any_mask = true;
+      any_host = any_host || !masks_on_device;
+    }
+    f->sel_has_mask = m != nullptr;
+    f->sel_min = min_depth;
+    f->sel_max = max_depth;
+    f->sel_on = f->sel_has_mask || selection_range_on(min_depth, max_depth);
+    invalidate_reference_role(f);
+  }
+  if (any_mask) {
+    const int rc = stamp_build(ctx, n_frames, frames);
+    if (rc != DVO_HIP_OK) return rc;
+  }
+  if (any_host) DVO_HIP_TRY(ctx, hipStreamSynchronize(bs));   // (the caller may reuse a host mask at once)
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_frames_clear_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames) {
+  std::unique_lock<std::recursive_mutex> guard;
+  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
+  DVO_FLUSH_DEFERRED(ctx);
+  if (!ctx || n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_selection: bad argument");
+  for (int i = 0; i < n_frames; ++i)
+    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_selection: null frame");
+  for (int i = 0; i < n_frames; ++i) {
+    dvo_hip_frame* f = frames[i];
+    if (!f->sel_on) continue;
+    f->sel_on = f->sel_has_mask = false;
+    f->sel_min = 0.0f;
+    f->sel_max = INFINITY;
+    invalidate_reference_role(f);   // (the mask buffer is kept for the next selection)
+  }
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_frame_set_level_selection(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, const uint8_t* accepted) {
+  std::unique_lock<std::recursive_mutex> guard;
+  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
+  DVO_FLUSH_DEFERRED(ctx);
+  if (!ctx || !frame || level < 0 || level >= frame->levels) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_set_level_selection: bad argument");
+  if (!accepted) {                                           // drop the level's explicit set: the next use selects by thresholds again
+    FrameLevel& L = frame->lv[level];
+    if (L.explicit_sel) L.selected = L.explicit_sel = L.q3 = false;
+    return DVO_HIP_OK;
+  }
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  dvo_hip_frame* one[1] = {frame};
+  int rc = wait_for_build(ctx, 1, one);
+  if (rc == DVO_HIP_OK) rc = ensure_roles(ctx, 1, one, 0, level, level, 0.0f, 0.0f);   // (plane A holds the level's {I, Z})
+  if (rc != DVO_HIP_OK) return rc;
+  FrameLevel& L = frame->lv[level];
+  const size_t n = size_t(L.w) * L.h;
+  DVO_HIP_TRY(ctx, ctx->misc.reserve(n));
+  DVO_HIP_TRY(ctx, hipMemcpyAsync(ctx->misc.p, accepted, n, hipMemcpyHostToDevice, ctx->stream));
+  DVO_HIP_TRY(ctx, hipMemsetAsync(frame->sel_count + level, 0, sizeof(int), ctx->stream));
+  launch_pack_accepted(ctx->stream, L.A, ctx->misc.as<uint8_t>(), int(n), L.R, frame->sel_count + level);
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  mark_selected(L, 0.0f, 0.0f);
+  L.explicit_sel = true;
   return DVO_HIP_OK;
 }
 

@@ -31,6 +31,61 @@ int wait_for_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames) {
   return wait_for_ticket(ctx, need, /*upload=*/false);
 }
 
+// the reference role of a level is built for the thresholds (ithr, dthr), or holds an explicit accepted set (which no threshold replaces)
+bool ref_ready(const FrameLevel& L, float ithr, float dthr) { return L.selected && (L.explicit_sel || (L.ithr == ithr && L.dthr == dthr)); }
+
+void mark_selected(FrameLevel& L, float ithr, float dthr) {
+  L.selected = true;
+  L.explicit_sel = false;
+  L.q3 = false;                                              // (a fresh plane R)
+  L.ithr = ithr;
+  L.dthr = dthr;
+}
+
+// Setting, replacing or clearing a frame's caller selection: every reference-role selection of the frame is stale.
+void invalidate_reference_role(dvo_hip_frame* f) {
+  for (int l = 0; l < f->levels; ++l) {
+    f->lv[l].selected = false;
+    f->lv[l].explicit_sel = false;
+    f->lv[l].q3 = false;
+  }
+}
+
+// The caller selection of those of the n frames that carry one, over their planes R of levels l0 .. l1 just built on `stream` (one launch,
+// behind the kernel that built them).  Nothing is launched when no frame carries a selection.  report: dvo_hip_frame_select's mask (one
+// frame, one level).
+int apply_selection(dvo_hip_context* ctx, hipStream_t stream, int n, dvo_hip_frame* const* frames, int l0, int l1, int cap,
+                    uint8_t* report = nullptr) {
+  std::vector<SelectionApply> host;
+  const unsigned long long visit = ++ctx->sel_visits;
+  for (int i = 0; i < n; ++i) {
+    dvo_hip_frame* f = frames[i];
+    if (!f->sel_on || f->sel_visit == visit) continue;      // (a frame listed twice is applied once: its pixels would leave twice)
+    f->sel_visit = visit;
+    SelectionApply a;
+    for (int l = 0; l < kMaxLevels; ++l) a.R[l] = l < f->levels ? f->lv[l].R : nullptr;
+    a.sel_count = f->sel_count;
+    a.mask = f->sel_has_mask ? f->sel_mask.as<uint8_t>() : nullptr;
+    a.pitch = f->lv[0].w;
+    a.range_on = selection_range_on(f->sel_min, f->sel_max) ? 1 : 0;
+    a.min_depth = f->sel_min;
+    a.max_depth = f->sel_max;
+    a.report = report;
+    host.push_back(a);
+  }
+  if (host.empty()) return DVO_HIP_OK;
+  DevBuf& table = stream == ctx->build_stream ? ctx->sel_tbl_build : ctx->sel_tbl_main;
+  const size_t bytes = host.size() * sizeof(SelectionApply);
+  DVO_HIP_TRY(ctx, table.reserve(bytes));
+  DVO_HIP_TRY(ctx, ctx->tables.upload(stream, table.p, host.data(), bytes));
+  const CameraGeom* cam = frames[0]->cam;
+  LevelSpan span;
+  apply_selection_span(span, l0, l1, cam->w, cam->h);
+  launch_apply_selection(stream, table.as<SelectionApply>(), int(host.size()), span, cap);
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  return DVO_HIP_OK;
+}
+
 // The error word of a resident launch: one of a ring of words of Workspace::host_status indexed by the launch counter (the per-step
 // words start behind the ring).  A workgroup of an EARLIER launch that gives up late -- the host returns from the direct path as soon
 // as every pair is done, not when every workgroup has left -- raises its own launch's word, not the one the next batch has just reset.
@@ -302,6 +357,7 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
     for (int l = 0; l < levels; ++l) {   // new pixels: every cached role plane is stale (PointSelection::setRgbdImagePyramid)
       f->lv[l].cur_have = 0;
       f->lv[l].selected = false;
+      f->lv[l].explicit_sel = false;
       f->lv[l].q3 = false;
     }
     f->raw0 = from_raw;
@@ -327,7 +383,7 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
     wide = wide && (colour ? colour_strips_aligned(host[i].colour, colour->pitch, channels) : aligned_to(host[i].grey, 4)) &&
            aligned_to(host[i].raw, 8) && aligned_to(staging_grey(f), 4);
     if (role == 0) f->lv[0].cur_have = flavor0;
-    if (role == 1) { f->lv[0].selected = true; f->lv[0].q3 = false; f->lv[0].ithr = ithr; f->lv[0].dthr = dthr; }
+    if (role == 1) mark_selected(f->lv[0], ithr, dthr);
   }
   hipStream_t bs = ctx->build_stream;
   // (one of a few buffers: the one that already holds this very table -- a streaming caller re-ingests the same frame sets from the same
@@ -355,6 +411,10 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
     }
     launch_build_from_raw(bs, tbl, n, depth_scale, cam->w[0], cam->h[0], levels, role, wide, ithr, dthr, ctx->opt_build_workgroups, flavor0, c_levels,
                           channels, ctx->opt_stream_policy != 0);
+    if (role == 1) {
+      const int rc = apply_selection(ctx, bs, n, frames, 0, 0, ctx->opt_build_workgroups);
+      if (rc != DVO_HIP_OK) return rc;
+    }
     if (ingest_strips_supports(cam->w[0], wide)) ctx->strip_ingests += n;
     if (colour) ctx->colour_ingests += n;
   }
@@ -385,7 +445,7 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
       const FrameLevel& L = f->lv[0];
       if (!f->raw0 || L.cur_have != 0 || f->raw_copy) continue;
       const int want0 = role == 0 ? (cur_want ? cur_want[0] : kCurAB) & (L.C ? (kCurAB | kCurC) : kCurAB) : 0;
-      const bool need = role == 0 ? want0 != 0 : !(L.selected && L.ithr == ithr && L.dthr == dthr);
+      const bool need = role == 0 ? want0 != 0 : !ref_ready(L, ithr, dthr);
       if (need) return fail(ctx, DVO_HIP_ERR_INVALID, "frame has neither sampling planes nor a raw copy at level 0");
     }
   bool launched = false;
@@ -426,7 +486,7 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
         dvo_hip_frame* f = frames[i];
         const FrameLevel& L = f->lv[l];
         const int miss = role == 0 ? want & ~L.cur_have : 0;
-        const bool need = role == 0 ? miss != 0 : !(L.selected && L.ithr == ithr && L.dthr == dthr);
+        const bool need = role == 0 ? miss != 0 : !ref_ready(L, ithr, dthr);
         uniform = need && !(l == 0 && f->raw0) && (role == 1 || L.cur_have == 0) && (miss_all < 0 || miss == miss_all);
         miss_all = miss;
       }
@@ -446,8 +506,12 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
         for (int l = l0; l <= l1; ++l) {
           FrameLevel& L = frames[i]->lv[l];
           if (role == 0) L.cur_have |= span.flavor[l];
-          else { L.selected = true; L.q3 = false; L.ithr = ithr; L.dthr = dthr; }
+          else mark_selected(L, ithr, dthr);
         }
+      if (role == 1) {
+        const int rc = apply_selection(ctx, stream, n, frames, l0, l1, cap);
+        if (rc != DVO_HIP_OK) return rc;
+      }
       if (eager) {
         const int rc2 = stamp_build(ctx, n, frames);
         if (rc2 != DVO_HIP_OK) return rc2;
@@ -461,14 +525,14 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
     // sources, per frame: float planes I / Z (levels >= 1, and level 0 of frames created from float planes); at level 0 of a frame
     // ingested from raw planes: the other flavour of the current role, else the frame's copy of its raw planes
     std::vector<FrameBuildPtrs> from_planes[4], from_raw[4], ab_from_c, c_from_a, ref_from_c;
-    std::vector<dvo_hip_frame*> ref_from_ab;
+    std::vector<dvo_hip_frame*> ref_from_ab, selected;
     float raw_scale = 0.0f;
     bool deferred = false;                                   // frames of another depth scale than the launch gathered so far
     for (int i = 0; i < n; ++i) {
       dvo_hip_frame* f = frames[i];
       FrameLevel& L = f->lv[l];
       const int miss = role == 0 ? want & ~L.cur_have : 0;
-      const bool need = role == 0 ? miss != 0 : !(L.selected && L.ithr == ithr && L.dthr == dthr);
+      const bool need = role == 0 ? miss != 0 : !ref_ready(L, ithr, dthr);
       if (!need) continue;   // also skips the second visit of a frame that is listed twice
       FrameBuildPtrs p;
       fill_build_ptrs(f, p);
@@ -495,8 +559,12 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
       } else {
         from_planes[miss].push_back(p);
       }
-      if (role == 0) L.cur_have |= miss;
-      else { L.selected = true; L.q3 = false; L.ithr = ithr; L.dthr = dthr; }
+      if (role == 0) {
+        L.cur_have |= miss;
+      } else {
+        mark_selected(L, ithr, dthr);
+        selected.push_back(f);
+      }
     }
     const FrameBuildPtrs* tbl = nullptr;
     for (int miss = 0; miss < 4; ++miss) {
@@ -528,6 +596,10 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
       DVO_HIP_TRY(ctx, hipMemsetAsync(f->sel_count, 0, sizeof(int), stream));
       launch_select_pack(stream, L.A, L.B, L.w * L.h, ithr, dthr, L.R, f->sel_count, nullptr);
       launched = true;
+    }
+    if (!selected.empty()) {
+      const int rc = apply_selection(ctx, stream, int(selected.size()), selected.data(), l, l, cap);
+      if (rc != DVO_HIP_OK) return rc;
     }
     if (deferred) {   // frames of a second depth scale (one kernel launch takes one scale): rare, one more pass each
       if (eager && launched) {

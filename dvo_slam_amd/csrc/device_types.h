@@ -142,6 +142,17 @@ struct FrameBuildPtrs {                // one frame of a batched pyramid build
   int colour_format;
 };
 
+// one frame of the caller-selection apply pass (k_apply_selection; include/dvo_hip.h, dvo_hip_frames_set_selection; rule: selection.h)
+struct SelectionApply {
+  float2* R[kMaxLevels];               // the reference planes {Zsel, I}: Zsel becomes NaN where the selection rejects a pixel
+  int* sel_count;                      // one counter per level, lowered by the pixels that leave
+  const uint8_t* mask;                 // the level-0 mask (frame-owned copy), or null
+  int pitch;                           // its bytes per row
+  int range_on;                        // selection_range_on(min_depth, max_depth)
+  float min_depth, max_depth;
+  uint8_t* report;                     // (dvo_hip_frame_select, one level) the w x h selection mask, cleared where a pixel leaves; or null
+};
+
 // several pyramid levels of one camera for a launch that covers them all (k_derive_levels): 64 x 16 tiles, level l's tiles of a frame
 // are tile0[l] .. tile0[l + 1] - 1
 struct LevelSpan {

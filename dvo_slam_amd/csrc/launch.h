@@ -47,6 +47,12 @@ void launch_derive_reference(hipStream_t s, const FrameBuildPtrs* tbl, int n_fra
 void launch_derive_levels(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, const LevelSpan& span, int role, float ithr, float dthr,
                           int max_workgroups);
 void launch_select_pack(hipStream_t s, const float4* A, const float2* B, int n, float ithr, float dthr, float2* R, int* count, uint8_t* mask);
+// the caller selection (selection.h) over the reference planes R of levels span.l0 .. span.l1 of n frames, one launch; span.tile0 =
+// offsets of each level's 512-pixel blocks (apply_selection_span)
+void apply_selection_span(LevelSpan& span, int l0, int l1, const int* w, const int* h);
+void launch_apply_selection(hipStream_t s, const SelectionApply* tbl, int n_frames, const LevelSpan& span, int max_workgroups);
+// an explicit accepted set of one level: R = {Z where accepted[i] != 0, else NaN; I}, count = accepted entries (zeroed before)
+void launch_pack_accepted(hipStream_t s, const float4* A, const uint8_t* accepted, int n, float2* R, int* count);
 void launch_unpack_plane(hipStream_t s, const float4* A, const float2* B, int n, int plane, float* out);
 
 // align_kernels.hip / align_mfma.hip

@@ -17,6 +17,7 @@
 #include "colour.h"
 #include "global_ptr.h"
 #include "launch.h"
+#include "selection.h"
 
 namespace dvo_hip {
 
@@ -446,6 +447,60 @@ __global__ void k_select_pack(const float4* __restrict__ A, const float2* __rest
   if ((threadIdx.x & 63) == 0 && ballot) atomicAdd(count, __popcll(ballot));
 }
 
+// The caller selection of reference frames (selection.h) over their freshly built planes R: a selected pixel the mask or the depth
+// range rejects gets Zsel = NaN -- the sweeps already treat that as unselected -- and leaves the level's count.  A workgroup takes 512
+// pixels of one level of one frame (span.tile0: block offsets), a lane two of them, read 16 B at a time; stores only where a pixel
+// leaves.  The ref_order saved slots beside the counts are not touched (the pass always follows a fresh build, never a Q3 edit).
+__global__ __launch_bounds__(256) void k_apply_selection(const SelectionApply* __restrict__ tbl, const LevelSpan span, int n_frames) {
+  const int per_frame = span.tile0[span.l1 + 1], total = per_frame * n_frames;
+  for (int gi = blockIdx.x; gi < total; gi += gridDim.x) {
+    const int frame = gi / per_frame, t = gi - frame * per_frame;
+    int level = span.l0;
+    while (level < span.l1 && t >= span.tile0[level + 1]) ++level;
+    const int w = span.w[level], npx = w * span.h[level];
+    const SelectionApply& f = tbl[frame];
+    float2* R = f.R[level];
+    const int i0 = (t - span.tile0[level]) * 512 + int(threadIdx.x) * 2;
+    bool gone[2] = {false, false};
+    if (i0 < npx) {
+      float z[2];
+      if (i0 + 1 < npx) {                                       // (R is 256-byte aligned and i0 even: a 16-byte load)
+        const float4 two = *reinterpret_cast<const float4*>(R + i0);
+        z[0] = two.x; z[1] = two.z;
+      } else {
+        z[0] = R[i0].x; z[1] = __builtin_nanf("");
+      }
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int i = i0 + k;
+        if (z[k] == z[k]) {                                     // selected so far (a selected pixel has a finite depth)
+          const int y = i / w, x = i - y * w;
+          if (!selection_keeps(f.mask, size_t(f.pitch), level, x, y, z[k], f.range_on != 0, f.min_depth, f.max_depth)) {
+            R[i].x = __builtin_nanf("");
+            if (f.report) f.report[i] = 0;
+            gone[k] = true;
+          }
+        }
+      }
+    }
+    const int removed = __popcll(__ballot(gone[0])) + __popcll(__ballot(gone[1]));   // wave-uniform
+    if ((threadIdx.x & 63) == 0 && removed) atomicSub(f.sel_count + level, removed);
+  }
+}
+
+__global__ void k_pack_accepted(const float4* __restrict__ A, const uint8_t* __restrict__ accepted, int n, float2* __restrict__ R,
+                                int* __restrict__ count) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  bool ok = false;
+  if (i < n) {
+    const float4 a = A[i];
+    ok = accepted[i] != 0;
+    R[i] = make_float2(ok ? a.y : __builtin_nanf(""), a.x);
+  }
+  const unsigned long long ballot = __ballot(ok);
+  if ((threadIdx.x & 63) == 0 && ballot) atomicAdd(count, __popcll(ballot));
+}
+
 __global__ void k_unpack_plane(const float4* __restrict__ A, const float2* __restrict__ B, int n, int plane, float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -545,6 +600,27 @@ void launch_derive_reference(hipStream_t s, const FrameBuildPtrs* tbl, int n_fra
 
 void launch_select_pack(hipStream_t s, const float4* A, const float2* B, int n, float ithr, float dthr, float2* R, int* count, uint8_t* mask) {
   k_select_pack<<<dim3((n + 255) / 256), dim3(256), 0, s>>>(A, B, n, ithr, dthr, R, count, mask);
+}
+
+void apply_selection_span(LevelSpan& span, int l0, int l1, const int* w, const int* h) {
+  span.l0 = l0; span.l1 = l1;
+  int blocks = 0;
+  for (int l = l0; l <= l1; ++l) {
+    span.w[l] = w[l]; span.h[l] = h[l]; span.flavor[l] = 0;
+    span.tile0[l] = blocks;
+    blocks += (w[l] * h[l] + 511) / 512;
+  }
+  span.tile0[l1 + 1] = blocks;
+}
+
+void launch_apply_selection(hipStream_t s, const SelectionApply* tbl, int n_frames, const LevelSpan& span, int max_workgroups) {
+  const int total = span.tile0[span.l1 + 1] * n_frames;
+  const int grid = max_workgroups > 0 && total > max_workgroups ? max_workgroups : total;
+  k_apply_selection<<<dim3(grid), dim3(256), 0, s>>>(tbl, span, n_frames);
+}
+
+void launch_pack_accepted(hipStream_t s, const float4* A, const uint8_t* accepted, int n, float2* R, int* count) {
+  k_pack_accepted<<<dim3((n + 255) / 256), dim3(256), 0, s>>>(A, accepted, n, R, count);
 }
 
 void launch_unpack_plane(hipStream_t s, const float4* A, const float2* B, int n, int plane, float* out) {

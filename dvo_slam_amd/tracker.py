@@ -216,10 +216,29 @@ class RgbdImagePyramid:
     def build(self, num_levels):            # rgbd_image.cpp:156-172 (idempotent, only ever grows)
         if self.levels >= num_levels:
             return
+        sel = getattr(self, "_selection", None)
+        if sel is not None and sel[0] is not None and not isinstance(sel[0][0], np.ndarray):
+            # (the frame is made anew, and its mask would have to be read again from a device address that may have been freed)
+            raise ValueError("RgbdImagePyramid.build: the pyramid holds a selection from a device address; build it with all its levels "
+                             "before set_selection, or clear_selection first")
         if self.ptr:
             self.ctx._lib.dvo_hip_frame_destroy(self.ctx.ptr, self.ptr)
         self.ptr = self._make_frame(num_levels)
         self.levels = num_levels
+        if sel is not None:                                  # (a new frame: the selection is handed over again, from the host copy)
+            set_selection_batch([self], *sel)
+
+    def set_selection(self, mask=None, min_depth=0.0, max_depth=float("inf"), pitch=0):
+        """Caller selection of this frame's reference points (an extension over the reference API; include/dvo_hip.h,
+        dvo_hip_frames_set_selection): a level-0 mask -- a (height, width) uint8 numpy array, or a device address (e.g.
+        torch_tensor.data_ptr()) of height rows of `pitch` bytes (0 = width) -- and / or a depth range in metres.  Kept across
+        re-ingests until replaced or cleared.  The mask is copied at once; a pyramid that holds a mask given by device address cannot
+        grow more levels afterwards (build raises ValueError: the frame would be made anew from a mask that may be gone)."""
+        set_selection_batch([self], [mask] if mask is not None else None, min_depth, max_depth, pitch)
+
+    def clear_selection(self):
+        self._selection = None
+        self.ctx.check(self.ctx._lib.dvo_hip_frames_clear_selection(self.ctx.ptr, 1, (C.c_void_p * 1)(self.ptr)))
 
     compute = build                         # deprecated alias in the reference too
 
@@ -411,6 +430,64 @@ def update_raw_device_batch(pyramids, grey_dev_ptrs, depth_dev_ptrs, depth_scale
         ctx.check(ctx._lib.dvo_hip_frames_update_raw_device_as(ctx.ptr, n, fr, g, z, depth_scale, _ROLES[role], C.byref(ccfg)))
 
 
+def set_selection_batch(pyramids, masks=None, min_depth=0.0, max_depth=float("inf"), pitch=0):
+    """RgbdImagePyramid.set_selection for n pyramids of one context in one call.  masks: None, or one entry per pyramid -- None (no
+    mask), a (height, width) uint8 numpy array, or a device address; host arrays and device addresses are not mixed in one call."""
+    n = len(pyramids)
+    ctx = pyramids[0].ctx
+    ptrs, on_device, keep = None, 0, []
+    if masks is not None:
+        if len(masks) != n:
+            raise ValueError("set_selection_batch: one mask entry per pyramid")
+        kinds = {isinstance(m, np.ndarray) for m in masks if m is not None}
+        if len(kinds) > 1:
+            raise ValueError("set_selection_batch: host arrays and device addresses in one call")
+        on_device = 1 if kinds == {False} else 0
+        entries = []
+        for p, m in zip(pyramids, masks):
+            if m is None:
+                entries.append(None)
+            elif isinstance(m, np.ndarray):
+                c = p.camera
+                if m.dtype != np.uint8 or m.shape != (c.height, c.width):
+                    raise ValueError("set_selection_batch: a host mask is a (%d, %d) uint8 array" % (c.height, c.width))
+                m = np.ascontiguousarray(m)
+                keep.append(m)
+                entries.append(m.ctypes.data)
+            else:
+                entries.append(int(m))
+        ptrs = (C.c_void_p * n)(*entries)
+    ctx.check(ctx._lib.dvo_hip_frames_set_selection(ctx.ptr, n, _handles(pyramids), ptrs, pitch if on_device else 0, on_device,
+                                                    float(min_depth), float(max_depth)))
+    for i, p in enumerate(pyramids):
+        m = None if masks is None else masks[i]
+        if isinstance(m, np.ndarray):
+            m = np.array(m, np.uint8)                      # (kept for a frame that is built again with more levels)
+        p._selection = ([m] if m is not None else None, min_depth, max_depth, pitch)
+
+
+def clear_selection_batch(pyramids):
+    ctx = pyramids[0].ctx
+    for p in pyramids:
+        p._selection = None
+    ctx.check(ctx._lib.dvo_hip_frames_clear_selection(ctx.ptr, len(pyramids), _handles(pyramids)))
+
+
+def set_level_selection(pyramid, level, accepted):
+    """Explicit selection of one level (dvo_hip_frame_set_level_selection): `accepted`, a (height, width) array of that level, is the
+    exact accepted set (non-zero = selected) until the pyramid's pixels change or another selection is requested; None drops it."""
+    pyramid.build(level + 1)
+    if accepted is None:
+        pyramid.ctx.check(pyramid.ctx._lib.dvo_hip_frame_set_level_selection(pyramid.ctx.ptr, pyramid.ptr, level, None))
+        return
+    img = pyramid.level(level)
+    a = np.ascontiguousarray(accepted, dtype=np.uint8)
+    if a.shape != (img.height, img.width):
+        raise ValueError("set_level_selection: accepted is (%d, %d)" % (img.height, img.width))
+    pyramid.ctx.check(pyramid.ctx._lib.dvo_hip_frame_set_level_selection(pyramid.ctx.ptr, pyramid.ptr, level,
+                                                                         a.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+
 class PinnedRawPlanes:
     """Page-locked host memory for the raw planes of n frames (dvo_hip_host_alloc), laid out per frame as [u16 depth][u8 grey]
     so that a frame moves to the device in one transfer.  `depth[i]` / `grey[i]` are numpy views a decoder writes into."""
@@ -542,7 +619,8 @@ class PointSelection:
         return int(c.width * c.height * 0.25 ** level)
 
     def select(self, level, want_mask=False):
-        """Returns the number of selected points (and the uint8 mask if asked)."""
+        """Returns the number of selected points (and the uint8 mask if asked): the thresholds' selection combined with the
+        pyramid's caller selection (RgbdImagePyramid.set_selection)."""
         p = self.pyramid
         p.build(level + 1)
         n = C.c_int()

@@ -18,6 +18,8 @@
 #pragma once
 
 #include <cassert>
+#include <cmath>
+#include <cstring>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
@@ -294,19 +296,72 @@ class RgbdImagePyramid {
   double timestamp() const { return levels_.empty() ? timestamp_ : levels_[0]->timestamp; }   // rgbd_image.cpp: level(0).timestamp
   void timestamp(double t) { timestamp_ = t; for (size_t l = 0; l < levels_.size(); ++l) levels_[l]->timestamp = t; }
 
+  // ---- extension over the reference API: the caller selection of this frame's reference points (include/dvo_hip.h,
+  // dvo_hip_frames_set_selection).  A pixel of level l is selected as a reference point iff the predicate accepts it, the level-0 mask
+  // byte (x << l, y << l) is non-zero and its depth lies in [min, max].  Kept until replaced or cleared, across re-ingests; works with
+  // DenseTracker::match / matchBatch, LocalTracker and the validator unchanged.  The mask is copied at once (host memory).
+  void setSelectionMask(const uint8_t* mask, size_t pitch) {
+    const RgbdCamera& c0 = camera_.level(0);
+    const size_t w = c0.width(), h = c0.height(), p = pitch ? pitch : w;
+    selection_mask_.assign(w * h, 0);
+    for (size_t y = 0; y < h; ++y) std::memcpy(&selection_mask_[y * w], mask + y * p, w);
+    has_selection_mask_ = true;
+    pushSelection();
+  }
+  void setSelectionDepthRange(float min_depth, float max_depth) {
+    selection_min_ = min_depth;
+    selection_max_ = max_depth;
+    pushSelection();
+  }
+  void clearSelection() {
+    selection_mask_.clear();
+    has_selection_mask_ = false;
+    selection_min_ = 0.0f;
+    selection_max_ = INFINITY;
+    dvo_hip_frame* one[1] = {device_frame()};
+    dvo_hip_check(ctx_, dvo_hip_frames_clear_selection(ctx_, 1, one), "dvo_hip_frames_clear_selection");
+  }
+  // the caller selection's verdict on a point of level `level` (host side: PointSelection with a caller-defined predicate)
+  bool selectionKeeps(size_t level, size_t x, size_t y, float z) const {
+    if (has_selection_mask_ && selection_mask_[(y << level) * size_t(camera_.level(0).width()) + (x << level)] == 0) return false;
+    const bool range_on = selection_min_ > 0.0f || !(selection_max_ >= 3.402823466e+38f);
+    return !range_on || (selection_min_ <= z && z <= selection_max_);
+  }
+
   // engine handles (not in the reference API)
   dvo_hip_frame* device_frame() { build(1); return frame_; }
+  // The frame for a match whose reference points a stock predicate selects (thresholds): the accepted sets a caller-defined predicate
+  // left on the device (PointSelection, point_selection.h) are dropped first, so that they never stand in for the thresholds' selection.
+  dvo_hip_frame* reference_frame() {
+    dvo_hip_frame* f = device_frame();
+    for (int l = 0; explicit_levels_ != 0u && l < DVO_HIP_MAX_LEVELS; ++l)
+      if (explicit_levels_ >> l & 1u) dvo_hip_check(ctx_, dvo_hip_frame_set_level_selection(ctx_, f, l, nullptr), "dvo_hip_frame_set_level_selection");
+    explicit_levels_ = 0u;
+    return f;
+  }
+  // (PointSelection with a caller-defined predicate: level `level` holds an accepted set handed to the device)
+  void noteExplicitSelection(size_t level) { explicit_levels_ |= 1u << level; }
   size_t builtLevels() const { return levels_.size(); }
   dvo_hip_context* device_context() { return ctx_; }
   RgbdCameraPyramid& cameraPyramid() { return camera_; }
 
  private:
+  void pushSelection() {
+    dvo_hip_frame* one[1] = {device_frame()};
+    const uint8_t* masks[1] = {has_selection_mask_ ? selection_mask_.data() : nullptr};
+    dvo_hip_check(ctx_, dvo_hip_frames_set_selection(ctx_, 1, one, masks, 0, 0, selection_min_, selection_max_), "dvo_hip_frames_set_selection");
+  }
+
   RgbdCameraPyramid& camera_;
   dvo::compat::ImageMat intensity_, depth_;
   dvo_hip_context* ctx_;
   dvo_hip_frame* frame_;
   std::vector<RgbdImagePtr> levels_;
   double timestamp_;
+  std::vector<uint8_t> selection_mask_;
+  bool has_selection_mask_ = false;
+  float selection_min_ = 0.0f, selection_max_ = INFINITY;
+  unsigned explicit_levels_ = 0u;
 };
 
 inline RgbdImagePtr RgbdCamera::create(const dvo::compat::ImageMat& intensity, const dvo::compat::ImageMat& depth) const {

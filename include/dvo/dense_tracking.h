@@ -213,7 +213,13 @@ class DenseTracker {
     } else {
       result.setIdentity();
     }
-    const dvo_hip_config c = c_config(reference.predicate().intensityThreshold(), reference.predicate().depthThreshold());
+    // a caller-defined predicate (point_selection.h): its accepted sets go to the device first; they hold whatever thresholds ask
+    // (with debug on, select() keeps every level's selection mask for getDebugIndex, as the reference's match does)
+    const bool on_device = reference.deviceThresholds();
+    if (!on_device || reference.getDebug())
+      for (int l = cfg.LastLevel; l <= cfg.FirstLevel; ++l) reference.select(size_t(l));
+    const dvo_hip_config c = on_device ? c_config(reference.predicate().intensityThreshold(), reference.predicate().depthThreshold())
+                                       : c_config(0.0f, 0.0f);
     const int nl = cfg.FirstLevel - cfg.LastLevel + 1;
     const int cap = nl * cfg.MaxIterationsPerLevel;
     levels_.resize(size_t(nl));
@@ -221,7 +227,8 @@ class DenseTracker {
     dvo_hip_result r;
     dvo::compat::affine_to_rowmajor(result.Transformation, r.transformation);
     dvo_hip_context* ctx = current.device_context();
-    if (core::dvo_hip_check(ctx, dvo_hip_match(ctx, ref.device_frame(), current.device_frame(), &c, &r, levels_.data(), nl, iters_.data(), cap), "dvo_hip_match"))
+    dvo_hip_frame* ref_frame = on_device ? ref.reference_frame() : ref.device_frame();
+    if (core::dvo_hip_check(ctx, dvo_hip_match(ctx, ref_frame, current.device_frame(), &c, &r, levels_.data(), nl, iters_.data(), cap), "dvo_hip_match"))
       unpack(r, levels_.data(), iters_.data(), result);
     else
       result = Result();   // a failed device call reads as a NaN result, the reference's failure signal (Q16)
@@ -278,7 +285,7 @@ class DenseTracker {
       std::vector<dvo_hip_level_stats> lv(m * size_t(nl));
       std::vector<dvo_hip_iteration_stats> it(m * size_t(cap));
       for (size_t k = 0; k < m; ++k) {
-        refs[k] = references[idx[k]]->device_frame();
+        refs[k] = references[idx[k]]->reference_frame();
         curs[k] = currents[idx[k]]->device_frame();
         dvo::compat::affine_to_rowmajor(results[idx[k]]->Transformation, r[k].transformation);
       }
@@ -327,7 +334,7 @@ class DenseTracker {
     dvo::compat::ImageMat result = dvo::compat::image_create(h, w);
     float* r = dvo::compat::image_ptr_mut(result);
     dvo_hip_context* ctx = current.device_context();
-    const bool ok = core::dvo_hip_check(ctx, dvo_hip_level_iteration(ctx, reference.device_frame(), current.device_frame(), int(level),
+    const bool ok = core::dvo_hip_check(ctx, dvo_hip_level_iteration(ctx, reference.reference_frame(), current.device_frame(), int(level),
                                                                      selection_predicate_.intensity_threshold, selection_predicate_.depth_threshold,
                                                                      T34, P0, 1, &out, residuals.data()), "dvo_hip_level_iteration");
     for (size_t i = 0; i < size_t(w) * h; ++i) {

@@ -239,10 +239,46 @@ int dvo_hip_frame_info(const dvo_hip_frame* frame, int level, int* width, int* h
  * plane 0=intensity 1=depth 2=intensity_dx 3=intensity_dy 4=depth_dx 5=depth_dy */
 int dvo_hip_frame_download_plane(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, int plane, float* out);
 /* PointSelection::select (dvo_core/src/core/point_selection.cpp:89-152): number of reference
- * pixels that pass ValidPointAndGradientThresholdPredicate (point_selection.h:49-67).  Builds and
- * caches the reference-side packed plane of that level; optional w*h uint8 mask. */
+ * pixels that pass ValidPointAndGradientThresholdPredicate (point_selection.h:49-67) and the frame's
+ * caller selection (dvo_hip_frames_set_selection).  Builds and caches the reference-side packed
+ * plane of that level; optional w*h uint8 mask. */
 int dvo_hip_frame_select(dvo_hip_context* ctx, dvo_hip_frame* frame, int level,
                          float intensity_threshold, float depth_threshold, int* n_selected, uint8_t* mask_or_null);
+
+/* ---- caller selection of reference points (an extension over the reference's PointSelectionPredicate,
+ * dvo_core/include/dvo/core/point_selection.h:32-36, point_selection.cpp:119-152) ----------------------------------------------
+ * A frame can carry a CALLER SELECTION: an optional level-0 mask (uint8, mask_pitch bytes per row, 0 = tight) and an optional depth
+ * range [min_depth, max_depth] in metres (0 and +INFINITY = off: a range is on when min_depth > 0 or max_depth is finite).  At level l,
+ * pixel (x, y) of a frame in the REFERENCE role is selected iff
+ *   1. the threshold predicate of the match holds (ValidPointAndGradientThresholdPredicate, unchanged),
+ *   2. mask0[(y << l) * mask_pitch + (x << l)] != 0 -- the level-0 pixel whose depth the coarse pixel carries (the depth pyramid
+ *      subsamples, rgbd_image.cpp:128-140, 169); no mask pyramid is stored,
+ *   3. min_depth <= Z_l(x, y) <= max_depth (when the range is on).
+ * The per-level count (LevelStats::ValidPixels -- the reference's selected-point count --, dvo_hip_frame_select's count and mask)
+ * counts exactly these pixels.  Under option
+ * "ref_order" the Q3 edit (an odd selection loses its last selected pixel) applies after the caller selection.  The current role of the
+ * frame is untouched: a selection restricts only which reference points enter an alignment.
+ * The selection persists across re-ingests of the frame's pixels (like the intrinsics) until it is replaced or cleared.  Setting,
+ * replacing or clearing one invalidates the frame's reference-role selection at every level -- also one a speculative
+ * dvo_hip_frames_prepare made -- so that the next use rebuilds it; a frame ingested into the reference role without a copy of its raw
+ * planes (DVO_HIP_INGEST_NO_RAW_COPY) cannot be rebuilt: set its selection BEFORE that ingest.
+ * The mask is copied into memory the frame owns when it is set: a host mask (masks_on_device 0) may be reused as soon as the call returns
+ * (the call waits for the context's pending frame builds); a device mask follows the stream contract of
+ * dvo_hip_frames_update_raw_device (the copy runs asynchronously on the context's build stream: keep the plane unchanged until a later
+ * call that uses the frames has returned).  masks may be NULL, and so may any entry (that frame: no mask).
+ * Cost: one pass (k_apply_selection) behind every build of a plane R of a frame that carries a selection -- ~9 B per level-0 pixel, a
+ * third more for levels 1-3; nothing for frames without one. */
+int dvo_hip_frames_set_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const uint8_t* const* masks,
+                                 size_t mask_pitch, int masks_on_device, float min_depth, float max_depth);
+int dvo_hip_frames_clear_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames);
+/* Explicit selection of one level, for an arbitrary predicate evaluated by the caller: `accepted` (host memory, w x h bytes of that
+ * level) is the exact accepted set.  The reference-role plane selects Z where accepted != 0, and the count is the number of non-zero
+ * entries -- what the reference counts, points with a NaN depth included; the sweeps reject those as they reject any NaN depth.  It
+ * replaces the threshold predicate and the caller selection at that level, whatever thresholds a match asks for, until the frame's
+ * pixels change, its caller selection is set or cleared, dvo_hip_frame_select asks for a selection of that level, or the set is dropped
+ * (accepted = NULL: the level selects by the thresholds of its next use again; nothing happens where the level holds no explicit set).  Under "ref_order"
+ * the Q3 edit then drops the last selected pixel of FINITE depth where the reference may drop a NaN-depth point. */
+int dvo_hip_frame_set_level_selection(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, const uint8_t* accepted);
 
 /* ---- the hot path --------------------------------------------------------------------------- */
 /* DenseTracker::match(RgbdImagePyramid& reference, RgbdImagePyramid& current, Result&)
