@@ -385,10 +385,9 @@ struct dvo_hip_context {
   // is already on the coarsest level.
   struct DeferredIngest {
     std::vector<dvo_hip_frame*> frames;
-    std::vector<const void*> grey, raw;
-    std::vector<const void*> colour;   // (a colour ingest: the colour planes in place of `grey`, with their format and row pitch)
-    int colour_format = 0;
-    size_t colour_pitch = 0;
+    std::vector<const void*> planes, depth;   // (an IngestSource's arrays, copied; its format and resolved pitch)
+    int format = 0;
+    size_t pitch = 0;
     float depth_scale;
     int role;
     dvo_hip_config cfg;
@@ -524,7 +523,7 @@ namespace {
 int flush_deferred(dvo_hip_context* ctx);
 }
 
-// (every entry point that works on frames or streams begins with this, under the context's lock: nothing overtakes a recorded ingest)
+// carry out the recorded ingests, if any (under the context's lock): nothing overtakes a recorded ingest
 #define DVO_FLUSH_DEFERRED(ctx)                                     \
   do {                                                              \
     if ((ctx) && !(ctx)->deferred.empty()) {                        \
@@ -532,6 +531,15 @@ int flush_deferred(dvo_hip_context* ctx);
       if (rc_deferred__ != DVO_HIP_OK) return rc_deferred__;        \
     }                                                               \
   } while (0)
+
+// How an entry point begins.  DVO_LOCK: the context's lock for the rest of the function, if there is a context (a null one is refused by
+// the argument check that follows).  DVO_ENTER: the same, then the recorded ingests -- every entry point that works on frames or streams.
+#define DVO_LOCK(ctx)                                               \
+  std::unique_lock<std::recursive_mutex> guard;                     \
+  if (ctx) guard = std::unique_lock<std::recursive_mutex>((ctx)->mutex)
+#define DVO_ENTER(ctx) \
+  DVO_LOCK(ctx);       \
+  DVO_FLUSH_DEFERRED(ctx)
 
 namespace {
 
@@ -611,13 +619,20 @@ int fail(dvo_hip_context* ctx, int code, const char* msg) {
   if (ctx) ctx->err = msg;
   return code;
 }
+// (... "<entry point>: <rule>")
+int fail(dvo_hip_context* ctx, int code, const char* who, const char* rule) {
+  if (ctx) ctx->err = std::string(who) + ": " + rule;
+  return code;
+}
 
-// The colour planes of a batch of frames (dvo_hip_frame_create_colour*, dvo_hip_frames_update_colour*): one DVO_HIP_PIXEL_* format and
-// one row pitch in bytes (resolved: never 0) for all of them
-struct ColourSource {
-  const void* const* planes;
-  int format;
-  size_t pitch;
+// The raw planes of a batch of frames (capi_ingest.inc), in host or in device memory: an 8-bit intensity or colour plane and a u16 depth
+// plane per frame, one format and one row pitch for all of them
+struct IngestSource {
+  const void* const* planes;   // 8-bit planes
+  int format;                  // 0 = grey, one byte per pixel; else DVO_HIP_PIXEL_*
+  size_t pitch;                // bytes from one row of an 8-bit plane to the next (as the caller gave it, 0 = tight, until check_ingest resolves it)
+  const void* const* depth;    // u16 planes, tight
+  float depth_scale;
 };
 
 #include "capi_frames.inc"     // cameras, frame allocation and build, role planes (ensure_roles)
@@ -837,70 +852,18 @@ int dvo_hip_context_device(const dvo_hip_context* ctx) { return ctx ? ctx->devic
 
 #include "capi_options.inc"   // dvo_hip_get_counter, dvo_hip_set_option
 
-
-int dvo_hip_frame_create_raw(dvo_hip_context* ctx, int width, int height, const float K[4], const uint8_t* grey,
-                             const uint16_t* raw_depth, float depth_scale, int levels, dvo_hip_frame** out) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
-  if (!ctx || !out || !grey || !raw_depth || !K) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_raw: null argument");
-  size_t raw_off;
-  dvo_hip_frame* f = nullptr;
-  int rc = frame_alloc(ctx, width, height, K, levels, &f, &raw_off);
-  if (rc != DVO_HIP_OK) return rc;
-  const size_t n = size_t(width) * height;
-  char* stage = f->pool.as<char>() + raw_off;
-  uint16_t* d_raw = reinterpret_cast<uint16_t*>(stage);
-  uint8_t* d_grey = reinterpret_cast<uint8_t*>(stage + n * 2);
-  hipError_t e = hipMemcpyAsync(d_raw, raw_depth, n * 2, hipMemcpyHostToDevice, ctx->build_stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_grey, grey, n, hipMemcpyHostToDevice, ctx->build_stream);
-  if (e == hipSuccess) {
-    const void* g[1] = {d_grey};
-    const void* r[1] = {d_raw};
-    rc = frames_build(ctx, 1, &f, g, r, depth_scale);
-    if (rc == DVO_HIP_OK) e = sync_stream(ctx->build_stream);
-  }
-  if (e != hipSuccess) ctx->err = std::string("frame_create_raw: ") + hipGetErrorString(e);
-  if (e != hipSuccess || rc != DVO_HIP_OK) {
-    dvo_hip_frame_destroy(ctx, f);
-    return rc != DVO_HIP_OK ? rc : DVO_HIP_ERR_HIP;
-  }
-  *out = f;
-  return DVO_HIP_OK;
-}
-
-int dvo_hip_frame_create_raw_device(dvo_hip_context* ctx, int width, int height, const float K[4], const void* grey_dev,
-                                    const void* raw_depth_dev, float depth_scale, int levels, dvo_hip_frame** out) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
-  if (!ctx || !out || !grey_dev || !raw_depth_dev || !K) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_raw_device: null argument");
-  size_t raw_off;
-  dvo_hip_frame* f = nullptr;
-  int rc = frame_alloc(ctx, width, height, K, levels, &f, &raw_off);
-  if (rc != DVO_HIP_OK) return rc;
-  const void* g[1] = {grey_dev};
-  const void* r[1] = {raw_depth_dev};
-  rc = frames_build(ctx, 1, &f, g, r, depth_scale);
-  if (rc != DVO_HIP_OK) {
-    dvo_hip_frame_destroy(ctx, f);
-    return rc;
-  }
-  *out = f;   // asynchronous (build stream): every later use of the frame is ordered after the build
-  return DVO_HIP_OK;
-}
-
 namespace {
 
+// role and cfg of dvo_hip_frames_prepare and of a role-aware ingest, against the frames; `who` names the entry point in the error text
 int check_prepare_args(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, int role, const dvo_hip_config* cfg, const char* who) {
   if (!ctx || n_frames < 1 || !frames || !cfg || (role != DVO_HIP_ROLE_CURRENT && role != DVO_HIP_ROLE_REFERENCE))
-    return fail(ctx, DVO_HIP_ERR_INVALID, who);
+    return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
   if (cfg->first_level < cfg->last_level || cfg->last_level < 0 || cfg->first_level >= kMaxLevels)
-    return fail(ctx, DVO_HIP_ERR_INVALID, "need 0 <= last_level <= first_level < DVO_HIP_MAX_LEVELS");
+    return fail(ctx, DVO_HIP_ERR_INVALID, who, "need 0 <= last_level <= first_level < DVO_HIP_MAX_LEVELS");
   for (int i = 0; i < n_frames; ++i) {
-    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who);
+    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null entry");
     if (frames[i]->cam != frames[0]->cam || frames[i]->levels <= cfg->first_level)
-      return fail(ctx, DVO_HIP_ERR_INVALID, "frames must share the camera and have first_level + 1 levels");
+      return fail(ctx, DVO_HIP_ERR_INVALID, who, "frames must share the camera and have first_level + 1 levels");
   }
   return DVO_HIP_OK;
 }
@@ -932,371 +895,12 @@ int prepare_roles(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* fram
   return DVO_HIP_OK;
 }
 
-// ingest of device-resident raw planes, optionally straight into a role (role < 0: none)
-// (colour: colour planes in place of grey_dev, which is then null)
-int update_raw_device(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* grey_dev,
-                      const void* const* raw_depth_dev, float depth_scale, int role, const dvo_hip_config* cfg, bool keep_raw_copy = true,
-                      const ColourSource* colour = nullptr) {
-  const bool ref = role == DVO_HIP_ROLE_REFERENCE;
-  const int fused = role >= 0 && cfg->last_level == 0 ? (ref ? 1 : 0) : -1;   // level 0 is built in the same pass if it is used at all
-  int rc = frames_build(ctx, n_frames, frames, grey_dev, raw_depth_dev, depth_scale, fused, ref ? cfg->intensity_derivative_threshold : 0.0f,
-                        ref ? cfg->depth_derivative_threshold : 0.0f, keep_raw_copy, colour);
-  if (rc == DVO_HIP_OK && role >= 0) rc = prepare_roles(ctx, n_frames, frames, role, cfg);
-  return rc;
-}
-
-// carry out the recorded ingests (option "defer_ingest"), oldest first; the first failure is returned, the list is empty afterwards
-int flush_deferred(dvo_hip_context* ctx) {
-  if (ctx->deferred.empty()) return DVO_HIP_OK;
-  std::vector<dvo_hip_context::DeferredIngest> list;
-  list.swap(ctx->deferred);
-  int rc = DVO_HIP_OK;
-  for (dvo_hip_context::DeferredIngest& d : list) {
-    for (dvo_hip_frame* f : d.frames) f->deferred = 0;
-    if (rc != DVO_HIP_OK) continue;
-    ctx->deferred_ingests += 1;
-    const ColourSource colour{d.colour.data(), d.colour_format, d.colour_pitch};
-    rc = update_raw_device(ctx, int(d.frames.size()), d.frames.data(), d.colour.empty() ? d.grey.data() : nullptr, d.raw.data(), d.depth_scale, d.role,
-                           d.role >= 0 ? &d.cfg : nullptr, d.keep_raw_copy, d.colour.empty() ? nullptr : &colour);
-  }
-  return rc;
-}
-
 }  // namespace
 
-int dvo_hip_frames_update_raw_device(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* grey_dev,
-                                     const void* const* raw_depth_dev, float depth_scale) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
-  if (!ctx || n_frames < 1 || !frames || !grey_dev || !raw_depth_dev) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_update_raw_device: null argument");
-  for (int i = 0; i < n_frames; ++i)
-    if (!frames[i] || !grey_dev[i] || !raw_depth_dev[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_update_raw_device: null entry");
-  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  return update_raw_device(ctx, n_frames, frames, grey_dev, raw_depth_dev, depth_scale, -1, nullptr);
-}
-
-// defer / keep_raw_copy: -1 = what the context's options say ("defer_ingest", "keep_raw_copy"), 0 / 1 = for this call only
-static int update_raw_device_as(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* grey_dev,
-                                const void* const* raw_depth_dev, float depth_scale, int role, const dvo_hip_config* cfg, int defer, int keep_raw_copy) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  int rc = check_prepare_args(ctx, n_frames, frames, role, cfg, "frames_update_raw_device_as: bad argument");
-  if (rc != DVO_HIP_OK) return rc;
-  if (!grey_dev || !raw_depth_dev) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_update_raw_device_as: null argument");
-  for (int i = 0; i < n_frames; ++i)
-    if (!grey_dev[i] || !raw_depth_dev[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_update_raw_device_as: null entry");
-  const bool keep = keep_raw_copy < 0 ? ctx->opt_keep_raw_copy != 0 : keep_raw_copy != 0;
-  if (defer < 0 ? ctx->opt_defer_ingest != 0 : defer != 0) {
-    dvo_hip_context::DeferredIngest d;
-    d.frames.assign(frames, frames + n_frames);
-    d.grey.assign(grey_dev, grey_dev + n_frames);
-    d.raw.assign(raw_depth_dev, raw_depth_dev + n_frames);
-    d.depth_scale = depth_scale;
-    d.role = role;
-    d.cfg = *cfg;
-    d.keep_raw_copy = keep;
-    for (int i = 0; i < n_frames; ++i) frames[i]->deferred = 1;
-    ctx->deferred.push_back(std::move(d));
-    return DVO_HIP_OK;
-  }
-  DVO_FLUSH_DEFERRED(ctx);                                     // (nothing overtakes a recorded ingest)
-  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  return update_raw_device(ctx, n_frames, frames, grey_dev, raw_depth_dev, depth_scale, role, cfg, keep);
-}
-
-int dvo_hip_frames_update_raw_device_as(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* grey_dev,
-                                        const void* const* raw_depth_dev, float depth_scale, int role, const dvo_hip_config* cfg) {
-  return update_raw_device_as(ctx, n_frames, frames, grey_dev, raw_depth_dev, depth_scale, role, cfg, -1, -1);
-}
-
-int dvo_hip_frames_update_raw_device_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* grey_dev,
-                                           const void* const* raw_depth_dev, float depth_scale, int role, const dvo_hip_config* cfg, unsigned flags) {
-  return update_raw_device_as(ctx, n_frames, frames, grey_dev, raw_depth_dev, depth_scale, role, cfg, (flags & DVO_HIP_INGEST_DEFER) ? 1 : 0,
-                              (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
-}
-
-int dvo_hip_flush_deferred(dvo_hip_context* ctx) {
-  if (!ctx) return DVO_HIP_ERR_INVALID;
-  std::unique_lock<std::recursive_mutex> guard(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
-  return DVO_HIP_OK;
-}
-
-// Streaming ingest from HOST memory: DMA of the raw planes into a transfer buffer on the upload stream, then the batched
-// build on the build stream.  Returns at once; from pinned memory (dvo_hip_host_alloc) the transfers are truly asynchronous,
-// from pageable memory the runtime stages them (correct, but the call then blocks for most of the copy).
-static int update_raw_host(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const uint8_t* const* grey,
-                           const uint16_t* const* raw_depth, float depth_scale, int role, const dvo_hip_config* cfg, int keep_raw_copy = -1) {
-  if (!ctx || n_frames < 1 || !frames || !grey || !raw_depth) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_update_raw: null argument");
-  for (int i = 0; i < n_frames; ++i) {
-    if (!frames[i] || !grey[i] || !raw_depth[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_update_raw: null entry");
-    if (frames[i]->cam != frames[0]->cam) return fail(ctx, DVO_HIP_ERR_INVALID, "frames of one build batch must share camera and levels");
-  }
-  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t n = size_t(frames[0]->lv[0].w) * frames[0]->lv[0].h;
-  const size_t slot_bytes = (n * 3 + 1) & ~size_t(1);           // per frame: [u16 depth][u8 grey], padded to an even size
-  const unsigned b = ctx->upload_next++ % dvo_hip_context::kUploadRing;
-  DevBuf& buf = ctx->upload_buf[b];
-  // the previous contents of this buffer may still be read by the build they were uploaded for
-  int rc = wait_for_ticket(ctx, ctx->upload_buf_seq[b], /*upload=*/true);
-  if (rc != DVO_HIP_OK) return rc;
-  if (buf.bytes < slot_bytes * size_t(n_frames)) {
-    DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->build_stream));   // growing = free + malloc
-    DVO_HIP_TRY(ctx, buf.reserve(slot_bytes * size_t(n_frames)));
-  }
-  char* base = buf.as<char>();
-  std::vector<const void*> g(static_cast<size_t>(n_frames)), r(static_cast<size_t>(n_frames));
-  for (int i = 0; i < n_frames;) {
-    const char* hd = reinterpret_cast<const char*>(raw_depth[i]);
-    if (reinterpret_cast<const char*>(grey[i]) != hd + n * 2) {   // separate planes: two transfers for this frame
-      DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i, hd, n * 2, hipMemcpyHostToDevice, ctx->upload_stream));
-      DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i + n * 2, grey[i], n, hipMemcpyHostToDevice, ctx->upload_stream));
-      ++i;
-      continue;
-    }
-    int j = i + 1;                                               // frames in the slot layout that follow each other in host memory
-    while (j < n_frames && reinterpret_cast<const char*>(raw_depth[j]) == hd + slot_bytes * size_t(j - i) &&
-           reinterpret_cast<const char*>(grey[j]) == reinterpret_cast<const char*>(raw_depth[j]) + n * 2)
-      ++j;
-    DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i, hd, slot_bytes * size_t(j - i), hipMemcpyHostToDevice, ctx->upload_stream));
-    i = j;
-  }
-  for (int i = 0; i < n_frames; ++i) {
-    r[size_t(i)] = base + slot_bytes * i;
-    g[size_t(i)] = base + slot_bytes * i + n * 2;
-  }
-  DVO_HIP_TRY(ctx, hipEventRecord(ctx->upload_done, ctx->upload_stream));
-  DVO_HIP_TRY(ctx, hipStreamWaitEvent(ctx->build_stream, ctx->upload_done, 0));
-  rc = update_raw_device(ctx, n_frames, frames, g.data(), r.data(), depth_scale, role, cfg, keep_raw_copy < 0 ? ctx->opt_keep_raw_copy != 0 : keep_raw_copy != 0);
-  ctx->upload_buf_seq[b] = ctx->build_seq;          // the newest ticket is behind every reader of the buffer
-  return rc;
-}
-
-int dvo_hip_frames_update_raw(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const uint8_t* const* grey,
-                              const uint16_t* const* raw_depth, float depth_scale) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
-  return update_raw_host(ctx, n_frames, frames, grey, raw_depth, depth_scale, -1, nullptr);
-}
-
-int dvo_hip_frames_update_raw_as(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const uint8_t* const* grey,
-                                 const uint16_t* const* raw_depth, float depth_scale, int role, const dvo_hip_config* cfg) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
-  const int rc = check_prepare_args(ctx, n_frames, frames, role, cfg, "frames_update_raw_as: bad argument");
-  if (rc != DVO_HIP_OK) return rc;
-  return update_raw_host(ctx, n_frames, frames, grey, raw_depth, depth_scale, role, cfg);
-}
-
-int dvo_hip_frames_update_raw_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const uint8_t* const* grey,
-                                    const uint16_t* const* raw_depth, float depth_scale, int role, const dvo_hip_config* cfg, unsigned flags) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
-  const int rc = check_prepare_args(ctx, n_frames, frames, role, cfg, "frames_update_raw_as_ex: bad argument");
-  if (rc != DVO_HIP_OK) return rc;
-  return update_raw_host(ctx, n_frames, frames, grey, raw_depth, depth_scale, role, cfg, (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
-}
-
-// ---- colour ingest (colour.h): the colour plane goes where the grey one went, the kernels convert it ----
-
-namespace {
-
-// Every argument of a colour ingest checked before any frame is touched.  role -1: a plain update (cfg ignored), else
-// check_prepare_args.  *pitch: the resolved row pitch.
-int check_colour_args(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour, int format, size_t colour_pitch,
-                      const void* const* raw_depth, int role, const dvo_hip_config* cfg, const char* who, size_t* pitch) {
-  if (!ctx) return DVO_HIP_ERR_INVALID;
-  if (role == -1) {
-    if (n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, who);
-    for (int i = 0; i < n_frames; ++i)
-      if (!frames[i] || frames[i]->cam != frames[0]->cam || frames[i]->levels != frames[0]->levels)
-        return fail(ctx, DVO_HIP_ERR_INVALID, "frames of one build batch must share camera and levels");
-  } else {
-    const int rc = check_prepare_args(ctx, n_frames, frames, role, cfg, who);
-    if (rc != DVO_HIP_OK) return rc;
-    for (int i = 0; i < n_frames; ++i)
-      if (frames[i]->levels != frames[0]->levels) return fail(ctx, DVO_HIP_ERR_INVALID, "frames of one build batch must share camera and levels");
-  }
-  const int channels = pixel_channels(format);
-  if (channels == 0) return fail(ctx, DVO_HIP_ERR_INVALID, "colour ingest: unknown pixel format (DVO_HIP_PIXEL_*)");
-  if (!colour || !raw_depth) return fail(ctx, DVO_HIP_ERR_INVALID, "colour ingest: null argument");
-  for (int i = 0; i < n_frames; ++i)
-    if (!colour[i] || !raw_depth[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "colour ingest: null entry");
-  const size_t tight = size_t(frames[0]->lv[0].w) * channels;
-  if (colour_pitch != 0 && colour_pitch < tight) return fail(ctx, DVO_HIP_ERR_INVALID, "colour ingest: colour_pitch < width * channels");
-  if (colour_pitch > size_t(INT_MAX)) return fail(ctx, DVO_HIP_ERR_INVALID, "colour ingest: colour_pitch above 2^31 - 1");
-  *pitch = colour_pitch ? colour_pitch : tight;
-  return DVO_HIP_OK;
-}
-
-// device planes; defer / keep_raw_copy as update_raw_device_as
-int update_colour_device_as(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour_dev, int format,
-                            size_t colour_pitch, const void* const* raw_depth_dev, float depth_scale, int role, const dvo_hip_config* cfg,
-                            int defer, int keep_raw_copy) {
-  size_t pitch = 0;
-  int rc = check_colour_args(ctx, n_frames, frames, colour_dev, format, colour_pitch, raw_depth_dev, role, cfg,
-                             "frames_update_colour_device_as_ex: bad argument", &pitch);
-  if (rc != DVO_HIP_OK) return rc;
-  const bool keep = keep_raw_copy < 0 ? ctx->opt_keep_raw_copy != 0 : keep_raw_copy != 0;
-  if (defer < 0 ? ctx->opt_defer_ingest != 0 : defer != 0) {
-    dvo_hip_context::DeferredIngest d;
-    d.frames.assign(frames, frames + n_frames);
-    d.colour.assign(colour_dev, colour_dev + n_frames);
-    d.colour_format = format;
-    d.colour_pitch = pitch;
-    d.raw.assign(raw_depth_dev, raw_depth_dev + n_frames);
-    d.depth_scale = depth_scale;
-    d.role = role;
-    if (role >= 0) d.cfg = *cfg;
-    d.keep_raw_copy = keep;
-    for (int i = 0; i < n_frames; ++i) frames[i]->deferred = 1;
-    ctx->deferred.push_back(std::move(d));
-    return DVO_HIP_OK;
-  }
-  DVO_FLUSH_DEFERRED(ctx);                                     // (nothing overtakes a recorded ingest)
-  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const ColourSource src{colour_dev, format, pitch};
-  return update_raw_device(ctx, n_frames, frames, nullptr, raw_depth_dev, depth_scale, role, role >= 0 ? cfg : nullptr, keep, &src);
-}
-
-// Host planes through the upload ring, as update_raw_host: a slot is [u16 depth][colour, tight rows], padded to an even size.  A frame
-// whose tight colour plane directly follows its depth plane moves in one transfer, and so does a run of such frames at the slot
-// stride; a padded host pitch is repacked by a 2-D transfer.
-int update_colour_host(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour, int format, size_t colour_pitch,
-                       const uint16_t* const* raw_depth, float depth_scale, int role, const dvo_hip_config* cfg, int keep_raw_copy) {
-  size_t pitch = 0;
-  int rc = check_colour_args(ctx, n_frames, frames, colour, format, colour_pitch, reinterpret_cast<const void* const*>(raw_depth), role, cfg,
-                             "frames_update_colour_as_ex: bad argument", &pitch);
-  if (rc != DVO_HIP_OK) return rc;
-  DVO_FLUSH_DEFERRED(ctx);
-  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const int w = frames[0]->lv[0].w, h = frames[0]->lv[0].h;
-  const size_t n = size_t(w) * h, row = size_t(w) * pixel_channels(format);
-  const size_t slot_bytes = (n * 2 + row * h + 1) & ~size_t(1);
-  const unsigned b = ctx->upload_next++ % dvo_hip_context::kUploadRing;
-  DevBuf& buf = ctx->upload_buf[b];
-  rc = wait_for_ticket(ctx, ctx->upload_buf_seq[b], /*upload=*/true);   // (the previous contents may still be read by their build)
-  if (rc != DVO_HIP_OK) return rc;
-  if (buf.bytes < slot_bytes * size_t(n_frames)) {
-    DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->build_stream));   // growing = free + malloc
-    DVO_HIP_TRY(ctx, buf.reserve(slot_bytes * size_t(n_frames)));
-  }
-  char* base = buf.as<char>();
-  const bool tight = pitch == row;
-  for (int i = 0; i < n_frames;) {
-    const char* hd = reinterpret_cast<const char*>(raw_depth[i]);
-    if (!tight || reinterpret_cast<const char*>(colour[i]) != hd + n * 2) {   // separate planes: two transfers for this frame
-      DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i, hd, n * 2, hipMemcpyHostToDevice, ctx->upload_stream));
-      if (tight) DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i + n * 2, colour[i], row * h, hipMemcpyHostToDevice, ctx->upload_stream));
-      else DVO_HIP_TRY(ctx, hipMemcpy2DAsync(base + slot_bytes * i + n * 2, row, colour[i], pitch, row, h, hipMemcpyHostToDevice, ctx->upload_stream));
-      ++i;
-      continue;
-    }
-    int j = i + 1;                                               // frames in the slot layout that follow each other in host memory
-    while (j < n_frames && reinterpret_cast<const char*>(raw_depth[j]) == hd + slot_bytes * size_t(j - i) &&
-           reinterpret_cast<const char*>(colour[j]) == reinterpret_cast<const char*>(raw_depth[j]) + n * 2)
-      ++j;
-    DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i, hd, slot_bytes * size_t(j - i) - (slot_bytes - n * 2 - row * h), hipMemcpyHostToDevice,
-                                    ctx->upload_stream));
-    i = j;
-  }
-  std::vector<const void*> c(static_cast<size_t>(n_frames)), r(static_cast<size_t>(n_frames));
-  for (int i = 0; i < n_frames; ++i) {
-    r[size_t(i)] = base + slot_bytes * i;
-    c[size_t(i)] = base + slot_bytes * i + n * 2;
-  }
-  DVO_HIP_TRY(ctx, hipEventRecord(ctx->upload_done, ctx->upload_stream));
-  DVO_HIP_TRY(ctx, hipStreamWaitEvent(ctx->build_stream, ctx->upload_done, 0));
-  const ColourSource src{c.data(), format, row};
-  rc = update_raw_device(ctx, n_frames, frames, nullptr, r.data(), depth_scale, role, role >= 0 ? cfg : nullptr,
-                         keep_raw_copy < 0 ? ctx->opt_keep_raw_copy != 0 : keep_raw_copy != 0, &src);
-  ctx->upload_buf_seq[b] = ctx->build_seq;          // the newest ticket is behind every reader of the buffer
-  return rc;
-}
-
-}  // namespace
-
-int dvo_hip_frames_update_colour_device_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour_dev,
-                                              int pixel_format, size_t colour_pitch, const void* const* raw_depth_dev, float depth_scale, int role,
-                                              const dvo_hip_config* cfg, unsigned flags) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  return update_colour_device_as(ctx, n_frames, frames, colour_dev, pixel_format, colour_pitch, raw_depth_dev, depth_scale, role, cfg,
-                                 (flags & DVO_HIP_INGEST_DEFER) ? 1 : 0, (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
-}
-
-int dvo_hip_frames_update_colour_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour,
-                                       int pixel_format, size_t colour_pitch, const uint16_t* const* raw_depth, float depth_scale, int role,
-                                       const dvo_hip_config* cfg, unsigned flags) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  return update_colour_host(ctx, n_frames, frames, colour, pixel_format, colour_pitch, raw_depth, depth_scale, role, cfg,
-                            (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
-}
-
-int dvo_hip_frame_create_colour(dvo_hip_context* ctx, int width, int height, const float K[4], const void* colour, int pixel_format,
-                                size_t colour_pitch, const uint16_t* raw_depth, float depth_scale, int levels, dvo_hip_frame** out) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
-  if (!ctx || !out || !colour || !raw_depth || !K) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_colour: null argument");
-  if (pixel_channels(pixel_format) == 0) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_colour: unknown pixel format (DVO_HIP_PIXEL_*)");
-  if (colour_pitch != 0 && colour_pitch < size_t(width > 0 ? width : 0) * pixel_channels(pixel_format))
-    return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_colour: colour_pitch < width * channels");
-  size_t raw_off;
-  dvo_hip_frame* f = nullptr;
-  int rc = frame_alloc(ctx, width, height, K, levels, &f, &raw_off);
-  if (rc != DVO_HIP_OK) return rc;
-  // (the frame's 3-B staging area cannot hold the colour plane: it goes through the upload buffers like a streaming ingest)
-  const void* c[1] = {colour};
-  const uint16_t* r[1] = {raw_depth};
-  rc = update_colour_host(ctx, 1, &f, c, pixel_format, colour_pitch, r, depth_scale, -1, nullptr, -1);
-  hipError_t e = hipSuccess;
-  if (rc == DVO_HIP_OK) e = sync_stream(ctx->build_stream);
-  if (e != hipSuccess) ctx->err = std::string("frame_create_colour: ") + hipGetErrorString(e);
-  if (e != hipSuccess || rc != DVO_HIP_OK) {
-    dvo_hip_frame_destroy(ctx, f);
-    return rc != DVO_HIP_OK ? rc : DVO_HIP_ERR_HIP;
-  }
-  *out = f;
-  return DVO_HIP_OK;
-}
-
-int dvo_hip_frame_create_colour_device(dvo_hip_context* ctx, int width, int height, const float K[4], const void* colour_dev, int pixel_format,
-                                       size_t colour_pitch, const void* raw_depth_dev, float depth_scale, int levels, dvo_hip_frame** out) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
-  if (!ctx || !out || !colour_dev || !raw_depth_dev || !K) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_colour_device: null argument");
-  const int channels = pixel_channels(pixel_format);
-  if (channels == 0) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_colour_device: unknown pixel format (DVO_HIP_PIXEL_*)");
-  const size_t tight = size_t(width > 0 ? width : 0) * channels;
-  if ((colour_pitch != 0 && colour_pitch < tight) || colour_pitch > size_t(INT_MAX))
-    return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_colour_device: colour_pitch < width * channels or above 2^31 - 1");
-  size_t raw_off;
-  dvo_hip_frame* f = nullptr;
-  int rc = frame_alloc(ctx, width, height, K, levels, &f, &raw_off);
-  if (rc != DVO_HIP_OK) return rc;
-  const void* c[1] = {colour_dev};
-  const void* r[1] = {raw_depth_dev};
-  const ColourSource src{c, pixel_format, colour_pitch ? colour_pitch : tight};
-  rc = frames_build(ctx, 1, &f, nullptr, r, depth_scale, -1, 0.0f, 0.0f, true, &src);
-  if (rc != DVO_HIP_OK) {
-    dvo_hip_frame_destroy(ctx, f);
-    return rc;
-  }
-  *out = f;   // asynchronous (build stream): every later use of the frame is ordered after the build
-  return DVO_HIP_OK;
-}
+#include "capi_ingest.inc"   // the raw-frame ingest: dvo_hip_frame_create_*, dvo_hip_frames_update_*, dvo_hip_flush_deferred
 
 int dvo_hip_upload_wait(dvo_hip_context* ctx) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
+  DVO_ENTER(ctx);
   if (!ctx) return DVO_HIP_ERR_INVALID;
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
@@ -1304,8 +908,7 @@ int dvo_hip_upload_wait(dvo_hip_context* ctx) {
 }
 
 int dvo_hip_host_alloc(dvo_hip_context* ctx, size_t bytes, void** out) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
+  DVO_LOCK(ctx);
   if (!ctx || !out || bytes == 0) return fail(ctx, DVO_HIP_ERR_INVALID, "host_alloc: bad argument");
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   DVO_HIP_TRY(ctx, hipHostMalloc(out, bytes, hipHostMallocDefault));
@@ -1313,34 +916,22 @@ int dvo_hip_host_alloc(dvo_hip_context* ctx, size_t bytes, void** out) {
 }
 
 void dvo_hip_host_free(dvo_hip_context* ctx, void* p) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
+  DVO_LOCK(ctx);
   if (!p) return;
   if (ctx) (void)hipSetDevice(ctx->device);
   (void)hipHostFree(p);
 }
 
 int dvo_hip_frames_prepare(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, int role, const dvo_hip_config* cfg) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
-  const int rc = check_prepare_args(ctx, n_frames, frames, role, cfg, "frames_prepare: bad argument");
+  DVO_ENTER(ctx);
+  const int rc = check_prepare_args(ctx, n_frames, frames, role, cfg, "frames_prepare");
   if (rc != DVO_HIP_OK) return rc;
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   return prepare_roles(ctx, n_frames, frames, role, cfg);
 }
 
-int dvo_hip_frame_update_raw_device(dvo_hip_context* ctx, dvo_hip_frame* frame, const void* grey_dev, const void* raw_depth_dev,
-                                    float depth_scale) {
-  dvo_hip_frame* f[1] = {frame};
-  const void* g[1] = {grey_dev};
-  const void* r[1] = {raw_depth_dev};
-  return dvo_hip_frames_update_raw_device(ctx, 1, f, g, r, depth_scale);
-}
-
 void dvo_hip_frame_destroy(dvo_hip_context* ctx, dvo_hip_frame* frame) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
+  DVO_LOCK(ctx);
   if (!frame) return;
   if (ctx && !ctx->deferred.empty()) (void)flush_deferred(ctx);   // (a recorded ingest may name this frame)
   if (ctx) {
@@ -1372,9 +963,7 @@ int dvo_hip_frame_info(const dvo_hip_frame* frame, int level, int* width, int* h
 }
 
 int dvo_hip_frame_download_plane(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, int plane, float* out) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
+  DVO_ENTER(ctx);
   if (!ctx || !frame || !out || level < 0 || level >= frame->levels || plane < 0 || plane > 5)
     return fail(ctx, DVO_HIP_ERR_INVALID, "frame_download_plane: bad argument");
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1393,9 +982,7 @@ int dvo_hip_frame_download_plane(dvo_hip_context* ctx, dvo_hip_frame* frame, int
 
 int dvo_hip_frame_select(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, float ithr, float dthr, int* n_selected,
                          uint8_t* mask_or_null) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
+  DVO_ENTER(ctx);
   if (!ctx || !frame || level < 0 || level >= frame->levels) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_select: bad argument");
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t n = size_t(frame->lv[level].w) * frame->lv[level].h;
@@ -1428,9 +1015,7 @@ int dvo_hip_frame_select(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, 
 
 int dvo_hip_frames_set_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const uint8_t* const* masks,
                                  size_t mask_pitch, int masks_on_device, float min_depth, float max_depth) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
+  DVO_ENTER(ctx);
   if (!ctx || n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_selection: bad argument");
   if (!(min_depth <= max_depth)) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_selection: need min_depth <= max_depth (no NaN)");
   for (int i = 0; i < n_frames; ++i) {
@@ -1468,9 +1053,7 @@ int dvo_hip_frames_set_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_fra
 }
 
 int dvo_hip_frames_clear_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
+  DVO_ENTER(ctx);
   if (!ctx || n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_selection: bad argument");
   for (int i = 0; i < n_frames; ++i)
     if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_selection: null frame");
@@ -1486,9 +1069,7 @@ int dvo_hip_frames_clear_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_f
 }
 
 int dvo_hip_frame_set_level_selection(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, const uint8_t* accepted) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
+  DVO_ENTER(ctx);
   if (!ctx || !frame || level < 0 || level >= frame->levels) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_set_level_selection: bad argument");
   if (!accepted) {                                           // drop the level's explicit set: the next use selects by thresholds again
     FrameLevel& L = frame->lv[level];
@@ -1516,8 +1097,7 @@ int dvo_hip_frame_set_level_selection(dvo_hip_context* ctx, dvo_hip_frame* frame
 int dvo_hip_match_batch(dvo_hip_context* ctx, int n_pairs, dvo_hip_frame* const* references, dvo_hip_frame* const* currents,
                         const dvo_hip_config* cfg, dvo_hip_result* results, dvo_hip_level_stats* levels, int cap_levels,
                         dvo_hip_iteration_stats* iters, int cap_iters) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
+  DVO_LOCK(ctx);
   if (!results) return fail(ctx, DVO_HIP_ERR_INVALID, "match: results is null");
   int rc = validate_batch(ctx, n_pairs, references, currents, cfg);
   if (rc != DVO_HIP_OK) return rc;
@@ -1678,9 +1258,7 @@ int dvo_hip_match(dvo_hip_context* ctx, dvo_hip_frame* reference, dvo_hip_frame*
 int dvo_hip_level_iteration(dvo_hip_context* ctx, dvo_hip_frame* reference, dvo_hip_frame* current, int level, float ithr,
                             float dthr, const float T34[12], const float P_prev[4], int first_iteration_on_level,
                             dvo_hip_iteration_out* out, float* residuals_or_null) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
+  DVO_ENTER(ctx);
   if (!ctx || !reference || !current || !T34 || !P_prev || !out) return fail(ctx, DVO_HIP_ERR_INVALID, "level_iteration: null argument");
   dvo_hip_config cfg;
   std::memset(&cfg, 0, sizeof(cfg));
@@ -1753,9 +1331,7 @@ int dvo_hip_level_iteration(dvo_hip_context* ctx, dvo_hip_frame* reference, dvo_
 
 int dvo_hip_time_residual_kernel(dvo_hip_context* ctx, int n_pairs, dvo_hip_frame* const* references, dvo_hip_frame* const* currents,
                                  int level, int warm_iterations, int reps, float* avg_ms) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
+  DVO_ENTER(ctx);
   if (!avg_ms || reps < 1 || warm_iterations < 0) return fail(ctx, DVO_HIP_ERR_INVALID, "time_residual_kernel: bad argument");
   dvo_hip_config cfg;
   std::memset(&cfg, 0, sizeof(cfg));
@@ -1815,9 +1391,7 @@ int dvo_hip_time_residual_kernel(dvo_hip_context* ctx, int n_pairs, dvo_hip_fram
 
 int dvo_hip_time_stream_mix(dvo_hip_context* ctx, int n_pairs, dvo_hip_frame* const* references, dvo_hip_frame* const* currents,
                             int level, int with_write, int reps, float* avg_ms) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
+  DVO_ENTER(ctx);
   if (!avg_ms || reps < 1) return fail(ctx, DVO_HIP_ERR_INVALID, "time_stream_mix: bad argument");
   dvo_hip_config cfg;
   std::memset(&cfg, 0, sizeof(cfg));

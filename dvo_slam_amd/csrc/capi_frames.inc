@@ -317,7 +317,7 @@ uint8_t* staging_grey(dvo_hip_frame* f) { return f->pool.as<uint8_t>() + size_t(
 
 bool aligned_to(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
-// RgbdImagePyramid::build (rgbd_image.cpp:156-172) for n frames of one camera.  From float planes (grey == null: level 0 is
+// RgbdImagePyramid::build (rgbd_image.cpp:156-172) for n frames of one camera.  From float planes (src == null: level 0 is
 // already in place): the pyr-down chain, one launch per level for the whole batch; derived planes are built lazily per role
 // (ensure_roles), like the reference's buildAccelerationStructure / PointSelection caches.  From raw planes: one fused pass
 // (k_build_from_raw) that also writes level 0 in role `role` (-1: not known yet, 0: current, 1: reference with the given
@@ -338,21 +338,22 @@ int eager_current_flavor(const dvo_hip_context* ctx, const CameraGeom* cam, int 
   return BatchPolicy(ctx->compute_units).ingest_skips_taps(n_frames) ? kCurC : (kCurAB | kCurC);
 }
 
-// colour: the frames' 8-bit colour planes in place of `grey` (null); the kernels convert them and leave grey in the frames' raw copies.
-int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const void* const* grey, const void* const* raw,
-                 float depth_scale, int role = -1, float ithr = 0.0f, float dthr = 0.0f, bool keep_raw_copy = true,
-                 const ColourSource* colour = nullptr) {
+// src: device planes whose pitch is resolved, of frames that share camera and levels (check_ingest has seen to both).  From a colour
+// source the kernels convert and leave grey in the frames' raw copies.
+int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource* src, int role = -1, float ithr = 0.0f,
+                 float dthr = 0.0f, bool keep_raw_copy = true) {
   Range range("build");
   const CameraGeom* cam = frames[0]->cam;
   const int levels = frames[0]->levels;
   std::vector<FrameBuildPtrs> host(n);
   bool wide = cam->w[0] % 4 == 0;
-  const bool from_raw = grey || colour;
-  const int channels = colour ? pixel_channels(colour->format) : 0;
+  const bool from_raw = src != nullptr;
+  const bool colour = from_raw && src->format != 0;
+  const int channels = colour ? pixel_channels(src->format) : 0;
+  const float depth_scale = from_raw ? src->depth_scale : 0.0f;
   const int flavor0 = eager_current_flavor(ctx, cam, 0, n);
   for (int i = 0; i < n; ++i) {
     dvo_hip_frame* f = frames[i];
-    if (f->cam != cam || f->levels != levels) return fail(ctx, DVO_HIP_ERR_INVALID, "frames of one build batch must share camera and levels");
     fill_build_ptrs(f, host[i]);
     for (int l = 0; l < levels; ++l) {   // new pixels: every cached role plane is stale (PointSelection::setRgbdImagePyramid)
       f->lv[l].cur_have = 0;
@@ -365,13 +366,13 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
     f->depth_scale = depth_scale;
     if (!from_raw) continue;
     if (colour) {
-      host[i].colour = static_cast<const uint8_t*>(colour->planes[i]);
-      host[i].colour_pitch = int(colour->pitch);
-      host[i].colour_format = colour->format;
+      host[i].colour = static_cast<const uint8_t*>(src->planes[i]);
+      host[i].colour_pitch = int(src->pitch);
+      host[i].colour_format = src->format;
     } else {
-      host[i].grey = static_cast<const uint8_t*>(grey[i]);
+      host[i].grey = static_cast<const uint8_t*>(src->planes[i]);
     }
-    host[i].raw = static_cast<const uint16_t*>(raw[i]);
+    host[i].raw = static_cast<const uint16_t*>(src->depth[i]);
     const bool in_place = !colour && host[i].raw == staging_depth(f) && host[i].grey == staging_grey(f);
     if (in_place) {
       f->raw_copy = true;
@@ -380,7 +381,7 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
       host[i].keep_raw = staging_depth(f);
       f->raw_copy = true;
     }
-    wide = wide && (colour ? colour_strips_aligned(host[i].colour, colour->pitch, channels) : aligned_to(host[i].grey, 4)) &&
+    wide = wide && (colour ? colour_strips_aligned(host[i].colour, src->pitch, channels) : aligned_to(host[i].grey, 4)) &&
            aligned_to(host[i].raw, 8) && aligned_to(staging_grey(f), 4);
     if (role == 0) f->lv[0].cur_have = flavor0;
     if (role == 1) mark_selected(f->lv[0], ithr, dthr);

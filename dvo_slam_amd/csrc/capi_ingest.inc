@@ -1,0 +1,336 @@
+// capi_ingest.inc -- the raw-frame ingest: dvo_hip_frame_create_*, dvo_hip_frames_update_raw* / _colour*, dvo_hip_flush_deferred.  Every
+// entry point describes its planes as one IngestSource (grey is the one-channel pixel format) and goes through one checker (check_ingest),
+// one routine that records or builds (ingest) and, from host memory, one walker of the upload ring (upload_planes); the entry points
+// themselves translate flags and name themselves.  Textually included by capi.hip inside its extern "C" block, where an unnamed
+// namespace does not keep a function's name out of the library's symbol table: the helpers are static.
+
+// bytes per pixel of an IngestSource's 8-bit plane, 0 for an unknown format
+static int source_channels(int format) { return format == 0 ? 1 : pixel_channels(format); }
+// the pixel_format argument of a colour entry point as an IngestSource's format: 0 is grey in here and no DVO_HIP_PIXEL_* to a caller
+static int colour_format(int pixel_format) { return pixel_channels(pixel_format) ? pixel_format : -1; }
+
+// The planes of an ingest of n frames `width` pixels wide: format, arrays and their entries, the pitch rules; resolves src->pitch.  With
+// `frames` (entries not null), in the same pass: they share camera and levels -- a camera is shared by frames of any level count
+// (get_camera), and frames_build writes one table and launches once per level for all of them.
+static int check_source(dvo_hip_context* ctx, const char* who, int n, dvo_hip_frame* const* frames, int width, IngestSource* src) {
+  const int channels = source_channels(src->format);
+  if (channels == 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "unknown pixel format (DVO_HIP_PIXEL_*)");
+  if (!src->planes || !src->depth) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null argument");
+  for (int i = 0; i < n; ++i) {
+    if (frames && (!frames[i] || frames[i]->cam != frames[0]->cam || frames[i]->levels != frames[0]->levels))
+      return fail(ctx, DVO_HIP_ERR_INVALID, who, "frames of one build batch must share camera and levels");
+    if (!src->planes[i] || !src->depth[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null entry");
+  }
+  const size_t tight = size_t(width > 0 ? width : 0) * channels;
+  if (src->pitch != 0 && src->pitch < tight) return fail(ctx, DVO_HIP_ERR_INVALID, who, "pitch < width * channels");
+  if (src->pitch > size_t(INT_MAX)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "pitch above 2^31 - 1");
+  if (src->pitch == 0) src->pitch = tight;
+  return DVO_HIP_OK;
+}
+
+// Every argument of an ingest, checked before any frame is touched and before any transfer is enqueued.  role -1 where the entry point
+// admits a plain update (plain_ok; cfg ignored), else check_prepare_args.
+static int check_ingest(dvo_hip_context* ctx, const char* who, int n_frames, dvo_hip_frame* const* frames, IngestSource* src, bool plain_ok, int role,
+                        const dvo_hip_config* cfg) {
+  if (!ctx) return DVO_HIP_ERR_INVALID;
+  if (plain_ok && role == -1) {
+    if (n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+    if (!frames[0]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null entry");
+  } else {
+    const int rc = check_prepare_args(ctx, n_frames, frames, role, cfg, who);
+    if (rc != DVO_HIP_OK) return rc;
+  }
+  return check_source(ctx, who, n_frames, frames, frames[0]->lv[0].w, src);
+}
+
+namespace {   // (flush_deferred is declared there at the head of capi.hip, for DVO_FLUSH_DEFERRED)
+
+// ingest of device-resident raw planes, optionally straight into a role (role < 0: none, cfg not read)
+int update_raw_device(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const IngestSource& src, int role, const dvo_hip_config* cfg,
+                      bool keep_raw_copy) {
+  const bool ref = role == DVO_HIP_ROLE_REFERENCE;
+  const int fused = role >= 0 && cfg->last_level == 0 ? (ref ? 1 : 0) : -1;   // level 0 is built in the same pass if it is used at all
+  int rc = frames_build(ctx, n_frames, frames, &src, fused, ref ? cfg->intensity_derivative_threshold : 0.0f,
+                        ref ? cfg->depth_derivative_threshold : 0.0f, keep_raw_copy);
+  if (rc == DVO_HIP_OK && role >= 0) rc = prepare_roles(ctx, n_frames, frames, role, cfg);
+  return rc;
+}
+
+// carry out the recorded ingests (option "defer_ingest"), oldest first; the first failure is returned, the list is empty afterwards
+int flush_deferred(dvo_hip_context* ctx) {
+  if (ctx->deferred.empty()) return DVO_HIP_OK;
+  std::vector<dvo_hip_context::DeferredIngest> list;
+  list.swap(ctx->deferred);
+  int rc = DVO_HIP_OK;
+  for (dvo_hip_context::DeferredIngest& d : list) {
+    for (dvo_hip_frame* f : d.frames) f->deferred = 0;
+    if (rc != DVO_HIP_OK) continue;
+    ctx->deferred_ingests += 1;
+    const IngestSource src{d.planes.data(), d.format, d.pitch, d.depth.data(), d.depth_scale};
+    rc = update_raw_device(ctx, int(d.frames.size()), d.frames.data(), src, d.role, d.role >= 0 ? &d.cfg : nullptr, d.keep_raw_copy);
+  }
+  return rc;
+}
+
+}  // namespace
+
+// Host planes into the next buffer of the upload ring, on the upload stream; the build stream waits for them.  The planes land in slots
+// of [u16 depth][8-bit plane, rows of `row` bytes, tight], each padded to an even size; planes[i] / depth[i]: where frame i's went,
+// *ring: the buffer.  From pinned memory (dvo_hip_host_alloc) the transfers are truly asynchronous, from pageable memory the runtime
+// stages them (correct, but the call then blocks for most of the copy).  A frame whose tight 8-bit plane directly follows its depth plane
+// moves in one transfer, and so does a run of such frames at the slot stride (without the last slot's padding, which may lie past the
+// end of the caller's buffer); a padded host pitch is repacked by a 2-D transfer.
+static int upload_planes(dvo_hip_context* ctx, int n_frames, int w, int h, size_t row, const IngestSource& host, const void** planes, const void** depth,
+                         unsigned* ring) {
+  const size_t n = size_t(w) * h, plane = row * h;
+  const size_t slot_bytes = (n * 2 + plane + 1) & ~size_t(1);
+  const unsigned b = ctx->upload_next++ % dvo_hip_context::kUploadRing;
+  DevBuf& buf = ctx->upload_buf[b];
+  // the previous contents of this buffer may still be read by the build they were uploaded for
+  const int rc = wait_for_ticket(ctx, ctx->upload_buf_seq[b], /*upload=*/true);
+  if (rc != DVO_HIP_OK) return rc;
+  if (buf.bytes < slot_bytes * size_t(n_frames)) {
+    DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->build_stream));   // growing = free + malloc
+    DVO_HIP_TRY(ctx, buf.reserve(slot_bytes * size_t(n_frames)));
+  }
+  char* base = buf.as<char>();
+  const bool tight = host.pitch == row;
+  for (int i = 0; i < n_frames;) {
+    const char* hd = static_cast<const char*>(host.depth[i]);
+    if (!tight || static_cast<const char*>(host.planes[i]) != hd + n * 2) {   // separate planes: two transfers for this frame
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i, hd, n * 2, hipMemcpyHostToDevice, ctx->upload_stream));
+      if (tight) DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i + n * 2, host.planes[i], plane, hipMemcpyHostToDevice, ctx->upload_stream));
+      else DVO_HIP_TRY(ctx, hipMemcpy2DAsync(base + slot_bytes * i + n * 2, row, host.planes[i], host.pitch, row, h, hipMemcpyHostToDevice, ctx->upload_stream));
+      ++i;
+      continue;
+    }
+    int j = i + 1;                                               // frames in the slot layout that follow each other in host memory
+    while (j < n_frames && static_cast<const char*>(host.depth[j]) == hd + slot_bytes * size_t(j - i) &&
+           static_cast<const char*>(host.planes[j]) == static_cast<const char*>(host.depth[j]) + n * 2)
+      ++j;
+    DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i, hd, slot_bytes * size_t(j - i) - (slot_bytes - n * 2 - plane), hipMemcpyHostToDevice,
+                                    ctx->upload_stream));
+    i = j;
+  }
+  for (int i = 0; i < n_frames; ++i) {
+    depth[i] = base + slot_bytes * i;
+    planes[i] = base + slot_bytes * i + n * 2;
+  }
+  DVO_HIP_TRY(ctx, hipEventRecord(ctx->upload_done, ctx->upload_stream));
+  DVO_HIP_TRY(ctx, hipStreamWaitEvent(ctx->build_stream, ctx->upload_done, 0));
+  *ring = b;
+  return DVO_HIP_OK;
+}
+
+// The ingest behind every entry point: validate, then record the request (device planes, option "defer_ingest" / DVO_HIP_INGEST_DEFER)
+// or carry out what is recorded and build -- a call that is refused or that records flushes nothing.  host_planes: the planes go
+// through the upload ring first (streaming ingest from HOST memory: DMA on the upload stream, then the batched build on the build
+// stream; returns at once).  defer / keep_raw_copy: -1 = what the context's options say ("defer_ingest", "keep_raw_copy"), 0 / 1 = for
+// this call.
+static int ingest(dvo_hip_context* ctx, const char* who, int n_frames, dvo_hip_frame* const* frames, IngestSource src, bool host_planes, bool plain_ok, int role,
+                  const dvo_hip_config* cfg, int defer, int keep_raw_copy) {
+  int rc = check_ingest(ctx, who, n_frames, frames, &src, plain_ok, role, cfg);
+  if (rc != DVO_HIP_OK) return rc;
+  const bool keep = keep_raw_copy < 0 ? ctx->opt_keep_raw_copy != 0 : keep_raw_copy != 0;
+  if (!host_planes && (defer < 0 ? ctx->opt_defer_ingest != 0 : defer != 0)) {
+    dvo_hip_context::DeferredIngest d;
+    d.frames.assign(frames, frames + n_frames);
+    d.planes.assign(src.planes, src.planes + n_frames);
+    d.depth.assign(src.depth, src.depth + n_frames);
+    d.format = src.format;
+    d.pitch = src.pitch;
+    d.depth_scale = src.depth_scale;
+    d.role = role;
+    if (role >= 0) d.cfg = *cfg;
+    d.keep_raw_copy = keep;
+    for (int i = 0; i < n_frames; ++i) frames[i]->deferred = 1;
+    ctx->deferred.push_back(std::move(d));
+    return DVO_HIP_OK;
+  }
+  DVO_FLUSH_DEFERRED(ctx);                                     // (nothing overtakes a recorded ingest)
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!host_planes) return update_raw_device(ctx, n_frames, frames, src, role, cfg, keep);
+  std::vector<const void*> planes(static_cast<size_t>(n_frames)), depth(static_cast<size_t>(n_frames));
+  const size_t row = size_t(frames[0]->lv[0].w) * source_channels(src.format);
+  unsigned ring = 0;
+  rc = upload_planes(ctx, n_frames, frames[0]->lv[0].w, frames[0]->lv[0].h, row, src, planes.data(), depth.data(), &ring);
+  if (rc != DVO_HIP_OK) return rc;
+  const IngestSource uploaded{planes.data(), src.format, row, depth.data(), src.depth_scale};
+  rc = update_raw_device(ctx, n_frames, frames, uploaded, role, cfg, keep);
+  ctx->upload_buf_seq[ring] = ctx->build_seq;          // the newest ticket is behind every reader of the buffer
+  return rc;
+}
+
+// The end of every dvo_hip_frame_create_*: rc / e = what building frame f came to; a frame that failed is destroyed, a good one handed over.
+static int frame_create_finish(dvo_hip_context* ctx, const char* who, dvo_hip_frame* f, int rc, hipError_t e, dvo_hip_frame** out) {
+  if (e != hipSuccess) ctx->err = std::string(who) + ": " + hipGetErrorString(e);
+  if (e != hipSuccess || rc != DVO_HIP_OK) {
+    dvo_hip_frame_destroy(ctx, f);
+    return rc != DVO_HIP_OK ? rc : DVO_HIP_ERR_HIP;
+  }
+  *out = f;
+  return DVO_HIP_OK;
+}
+
+// A new frame from one frame's raw planes.  The routes differ for reasons:
+enum CreateRoute {
+  kCreateStaged,     // host planes copied into the frame's own 3-B staging area on the build stream: that IS the frame's raw copy, for free
+  kCreateUploaded,   // host planes through the upload ring like a streaming ingest (the staging area cannot hold a colour plane)
+  kCreateDevice      // device planes; asynchronous (build stream): every later use of the frame is ordered after the build
+};
+static int frame_create_raw(dvo_hip_context* ctx, const char* who, int width, int height, const float K[4], int levels, IngestSource src, CreateRoute route,
+                            dvo_hip_frame** out) {
+  if (!ctx || !out || !K) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null argument");
+  int rc = check_source(ctx, who, 1, nullptr, width, &src);
+  if (rc != DVO_HIP_OK) return rc;
+  size_t raw_off;
+  dvo_hip_frame* f = nullptr;
+  rc = frame_alloc(ctx, width, height, K, levels, &f, &raw_off);
+  if (rc != DVO_HIP_OK) return rc;
+  hipError_t e = hipSuccess;
+  const void* staged_grey[1] = {staging_grey(f)};
+  const void* staged_depth[1] = {staging_depth(f)};
+  if (route == kCreateStaged) {
+    const size_t n = size_t(width) * height;
+    e = hipMemcpyAsync(staging_depth(f), src.depth[0], n * 2, hipMemcpyHostToDevice, ctx->build_stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(staging_grey(f), src.planes[0], n, hipMemcpyHostToDevice, ctx->build_stream);
+    src.planes = staged_grey;
+    src.depth = staged_depth;
+  }
+  if (e == hipSuccess) rc = ingest(ctx, who, 1, &f, src, route == kCreateUploaded, /*plain_ok=*/true, -1, nullptr, 0, 1);
+  if (e == hipSuccess && rc == DVO_HIP_OK && route != kCreateDevice) e = sync_stream(ctx->build_stream);   // the caller's host buffers may go away
+  return frame_create_finish(ctx, who, f, rc, e, out);
+}
+
+int dvo_hip_frame_create_f32(dvo_hip_context* ctx, int width, int height, const float K[4], const float* intensity,
+                             const float* depth, int levels, dvo_hip_frame** out) {
+  DVO_ENTER(ctx);
+  if (!ctx || !out || !intensity || !depth || !K) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_f32", "null argument");
+  size_t raw_off;
+  dvo_hip_frame* f = nullptr;
+  int rc = frame_alloc(ctx, width, height, K, levels, &f, &raw_off);
+  if (rc != DVO_HIP_OK) return rc;
+  const size_t n = size_t(width) * height;
+  hipError_t e = hipMemcpyAsync(f->lv[0].I, intensity, n * 4, hipMemcpyHostToDevice, ctx->build_stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(f->lv[0].Z, depth, n * 4, hipMemcpyHostToDevice, ctx->build_stream);
+  if (e == hipSuccess) e = hipMemsetAsync(f->sel_count, 0, sizeof(int) * kMaxLevels, ctx->build_stream);
+  if (e == hipSuccess) {
+    rc = frames_build(ctx, 1, &f, /*src=*/nullptr);
+    if (rc == DVO_HIP_OK) e = sync_stream(ctx->build_stream);   // the caller's host buffers may go away
+  }
+  return frame_create_finish(ctx, "frame_create_f32", f, rc, e, out);
+}
+
+int dvo_hip_frame_create_raw(dvo_hip_context* ctx, int width, int height, const float K[4], const uint8_t* grey,
+                             const uint16_t* raw_depth, float depth_scale, int levels, dvo_hip_frame** out) {
+  DVO_ENTER(ctx);
+  const void* g[1] = {grey};
+  const void* r[1] = {raw_depth};
+  return frame_create_raw(ctx, "frame_create_raw", width, height, K, levels, IngestSource{g, 0, 0, r, depth_scale}, kCreateStaged, out);
+}
+
+int dvo_hip_frame_create_raw_device(dvo_hip_context* ctx, int width, int height, const float K[4], const void* grey_dev,
+                                    const void* raw_depth_dev, float depth_scale, int levels, dvo_hip_frame** out) {
+  DVO_ENTER(ctx);
+  const void* g[1] = {grey_dev};
+  const void* r[1] = {raw_depth_dev};
+  return frame_create_raw(ctx, "frame_create_raw_device", width, height, K, levels, IngestSource{g, 0, 0, r, depth_scale}, kCreateDevice, out);
+}
+
+int dvo_hip_frame_create_colour(dvo_hip_context* ctx, int width, int height, const float K[4], const void* colour, int pixel_format,
+                                size_t colour_pitch, const uint16_t* raw_depth, float depth_scale, int levels, dvo_hip_frame** out) {
+  DVO_ENTER(ctx);
+  const void* c[1] = {colour};
+  const void* r[1] = {raw_depth};
+  return frame_create_raw(ctx, "frame_create_colour", width, height, K, levels, IngestSource{c, colour_format(pixel_format), colour_pitch, r, depth_scale},
+                          kCreateUploaded, out);
+}
+
+int dvo_hip_frame_create_colour_device(dvo_hip_context* ctx, int width, int height, const float K[4], const void* colour_dev, int pixel_format,
+                                       size_t colour_pitch, const void* raw_depth_dev, float depth_scale, int levels, dvo_hip_frame** out) {
+  DVO_ENTER(ctx);
+  const void* c[1] = {colour_dev};
+  const void* r[1] = {raw_depth_dev};
+  return frame_create_raw(ctx, "frame_create_colour_device", width, height, K, levels,
+                          IngestSource{c, colour_format(pixel_format), colour_pitch, r, depth_scale}, kCreateDevice, out);
+}
+
+// ---- re-ingest of existing frames.  The grey entry points from device memory with a role and both colour ones validate first and flush
+// only when they are about to build (inside ingest); the others carry out what is recorded on entry, like every other entry point. ----
+
+int dvo_hip_frames_update_raw_device(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* grey_dev,
+                                     const void* const* raw_depth_dev, float depth_scale) {
+  DVO_ENTER(ctx);
+  return ingest(ctx, "frames_update_raw_device", n_frames, frames, IngestSource{grey_dev, 0, 0, raw_depth_dev, depth_scale}, /*host_planes=*/false,
+                /*plain_ok=*/true, -1, nullptr, 0, 1);
+}
+
+int dvo_hip_frame_update_raw_device(dvo_hip_context* ctx, dvo_hip_frame* frame, const void* grey_dev, const void* raw_depth_dev,
+                                    float depth_scale) {
+  dvo_hip_frame* f[1] = {frame};
+  const void* g[1] = {grey_dev};
+  const void* r[1] = {raw_depth_dev};
+  return dvo_hip_frames_update_raw_device(ctx, 1, f, g, r, depth_scale);
+}
+
+int dvo_hip_frames_update_raw_device_as(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* grey_dev,
+                                        const void* const* raw_depth_dev, float depth_scale, int role, const dvo_hip_config* cfg) {
+  DVO_LOCK(ctx);
+  return ingest(ctx, "frames_update_raw_device_as", n_frames, frames, IngestSource{grey_dev, 0, 0, raw_depth_dev, depth_scale}, /*host_planes=*/false,
+                /*plain_ok=*/false, role, cfg, -1, -1);
+}
+
+int dvo_hip_frames_update_raw_device_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* grey_dev,
+                                           const void* const* raw_depth_dev, float depth_scale, int role, const dvo_hip_config* cfg, unsigned flags) {
+  DVO_LOCK(ctx);
+  return ingest(ctx, "frames_update_raw_device_as_ex", n_frames, frames, IngestSource{grey_dev, 0, 0, raw_depth_dev, depth_scale}, /*host_planes=*/false,
+                /*plain_ok=*/false, role, cfg, (flags & DVO_HIP_INGEST_DEFER) ? 1 : 0, (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
+}
+
+int dvo_hip_flush_deferred(dvo_hip_context* ctx) {
+  if (!ctx) return DVO_HIP_ERR_INVALID;
+  DVO_ENTER(ctx);
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_frames_update_raw(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const uint8_t* const* grey,
+                              const uint16_t* const* raw_depth, float depth_scale) {
+  DVO_ENTER(ctx);
+  const IngestSource src{reinterpret_cast<const void* const*>(grey), 0, 0, reinterpret_cast<const void* const*>(raw_depth), depth_scale};
+  return ingest(ctx, "frames_update_raw", n_frames, frames, src, /*host_planes=*/true, /*plain_ok=*/true, -1, nullptr, 0, 1);
+}
+
+int dvo_hip_frames_update_raw_as(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const uint8_t* const* grey,
+                                 const uint16_t* const* raw_depth, float depth_scale, int role, const dvo_hip_config* cfg) {
+  DVO_ENTER(ctx);
+  const IngestSource src{reinterpret_cast<const void* const*>(grey), 0, 0, reinterpret_cast<const void* const*>(raw_depth), depth_scale};
+  return ingest(ctx, "frames_update_raw_as", n_frames, frames, src, /*host_planes=*/true, /*plain_ok=*/false, role, cfg, 0, -1);
+}
+
+int dvo_hip_frames_update_raw_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const uint8_t* const* grey,
+                                    const uint16_t* const* raw_depth, float depth_scale, int role, const dvo_hip_config* cfg, unsigned flags) {
+  DVO_ENTER(ctx);
+  const IngestSource src{reinterpret_cast<const void* const*>(grey), 0, 0, reinterpret_cast<const void* const*>(raw_depth), depth_scale};
+  return ingest(ctx, "frames_update_raw_as_ex", n_frames, frames, src, /*host_planes=*/true, /*plain_ok=*/false, role, cfg, 0,
+                (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
+}
+
+// ---- colour (colour.h): the colour plane goes where the grey one went, the kernels convert it ----
+
+int dvo_hip_frames_update_colour_device_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour_dev,
+                                              int pixel_format, size_t colour_pitch, const void* const* raw_depth_dev, float depth_scale, int role,
+                                              const dvo_hip_config* cfg, unsigned flags) {
+  DVO_LOCK(ctx);
+  return ingest(ctx, "frames_update_colour_device_as_ex", n_frames, frames,
+                IngestSource{colour_dev, colour_format(pixel_format), colour_pitch, raw_depth_dev, depth_scale}, /*host_planes=*/false, /*plain_ok=*/true, role,
+                cfg, (flags & DVO_HIP_INGEST_DEFER) ? 1 : 0, (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
+}
+
+int dvo_hip_frames_update_colour_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour,
+                                       int pixel_format, size_t colour_pitch, const uint16_t* const* raw_depth, float depth_scale, int role,
+                                       const dvo_hip_config* cfg, unsigned flags) {
+  DVO_LOCK(ctx);
+  return ingest(ctx, "frames_update_colour_as_ex", n_frames, frames,
+                IngestSource{colour, colour_format(pixel_format), colour_pitch, reinterpret_cast<const void* const*>(raw_depth), depth_scale},
+                /*host_planes=*/true, /*plain_ok=*/true, role, cfg, 0, (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
+}

@@ -51,8 +51,7 @@ int dvo_hip_get_counter(dvo_hip_context* ctx, const char* key, long long* value)
 }
 
 int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
+  DVO_LOCK(ctx);
   if (!ctx || !key) return DVO_HIP_ERR_INVALID;
   if (std::strcmp(key, "rows_per_wave") == 0) {
     if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8 && value != 16)
@@ -249,31 +248,4 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value) {
     return DVO_HIP_OK;
   }
   return fail(ctx, DVO_HIP_ERR_INVALID, "unknown option");
-}
-
-int dvo_hip_frame_create_f32(dvo_hip_context* ctx, int width, int height, const float K[4], const float* intensity,
-                             const float* depth, int levels, dvo_hip_frame** out) {
-  std::unique_lock<std::recursive_mutex> guard;
-  if (ctx) guard = std::unique_lock<std::recursive_mutex>(ctx->mutex);
-  DVO_FLUSH_DEFERRED(ctx);
-  if (!ctx || !out || !intensity || !depth || !K) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create_f32: null argument");
-  size_t raw_off;
-  dvo_hip_frame* f = nullptr;
-  int rc = frame_alloc(ctx, width, height, K, levels, &f, &raw_off);
-  if (rc != DVO_HIP_OK) return rc;
-  const size_t n = size_t(width) * height;
-  hipError_t e = hipMemcpyAsync(f->lv[0].I, intensity, n * 4, hipMemcpyHostToDevice, ctx->build_stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(f->lv[0].Z, depth, n * 4, hipMemcpyHostToDevice, ctx->build_stream);
-  if (e == hipSuccess) e = hipMemsetAsync(f->sel_count, 0, sizeof(int) * kMaxLevels, ctx->build_stream);
-  if (e == hipSuccess) {
-    rc = frames_build(ctx, 1, &f, nullptr, nullptr, 0.0f);
-    if (rc == DVO_HIP_OK) e = sync_stream(ctx->build_stream);   // the caller's host buffers may go away
-  }
-  if (e != hipSuccess) ctx->err = std::string("frame_create_f32: ") + hipGetErrorString(e);
-  if (e != hipSuccess || rc != DVO_HIP_OK) {
-    dvo_hip_frame_destroy(ctx, f);
-    return rc != DVO_HIP_OK ? rc : DVO_HIP_ERR_HIP;
-  }
-  *out = f;
-  return DVO_HIP_OK;
 }

@@ -361,6 +361,24 @@ def test_bad_arguments_are_refused_and_change_nothing():
     assert L.dvo_hip_frame_create_colour(ctx.ptr, 640, 480, fp, None, 1, 0, None, 2e-4, 4, C.byref(out)) == _lib.ERR_INVALID
     assert not out.value
     assert ctx.counter("colour_ingests") == c0
+    # A grey ingest of frames with differing level counts is refused like a colour one, before any frame is touched and before any
+    # transfer is enqueued (frames of any level count share a camera).  The refused calls carry another depth scale and other thresholds
+    # than frames[0] was ingested with: a frame whose marks the call had reset would derive its level 0 anew with those.
+    short = blank_frames(camera(ctx, 640, 480, p["K"], 3), 1)[0]
+    mixed = (vp * 2)(frames[0].ptr, short.ptr)
+    tg = torch.full((480, 640), 77, dtype=torch.uint8, device="cuda")
+    hg, hz = np.full((480, 640), 77, np.uint8), np.ascontiguousarray(p["depth_cur"], np.uint16)
+    other = d.Config(FirstLevel=2, LastLevel=0, IntensityDerivativeThreshold=1.0, DepthDerivativeThreshold=0.5).to_c()
+    s0 = ctx.counter("strip_ingests")
+    assert L.dvo_hip_frames_update_raw_device(ctx.ptr, 2, mixed, (vp * 2)(tg.data_ptr(), tg.data_ptr()), good_z, 1e-3) == _lib.ERR_INVALID
+    assert L.dvo_hip_frames_update_raw_as_ex(ctx.ptr, 2, mixed, (vp * 2)(hg.ctypes.data, hg.ctypes.data), (vp * 2)(hz.ctypes.data, hz.ctypes.data),
+                                             1e-3, 1, C.byref(other), 0) == _lib.ERR_INVALID
+    d.upload_wait(ctx)
+    assert ctx.counter("strip_ingests") == s0
+    # ... and frames[0] still serves as a reference: the record of a pair ingested the same way that no refused call has named
+    control = blank_frames(cam, 2)
+    run_update(control, [in_format(bgr_ref, "bgr8"), in_format(bgr_cur, "bgr8")], [p["depth_ref"], p["depth_cur"]], "bgr8", "device", "reference", 4)
+    assert_records_identical(match_records(ctx, config(4), [frames[0]], [frames[1]]), match_records(ctx, config(4), [control[0]], [control[1]]))
     for f, bgr, z in ((frames[0], bgr_ref, p["depth_ref"]), (frames[1], bgr_cur, p["depth_cur"])):
         assert_frame_equals_oracle(f, oracle_pyramid(bgr, z, p["K"], 4), 4, "after refused calls")
 
