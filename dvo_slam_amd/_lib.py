@@ -70,6 +70,8 @@ EXPORTS = [
     "dvo_hip_frames_update_colour_as_ex", "dvo_hip_frames_set_selection", "dvo_hip_frames_clear_selection", "dvo_hip_frame_set_level_selection",
     "dvo_hip_comm_get_unique_id", "dvo_hip_comm_create", "dvo_hip_comm_destroy", "dvo_hip_comm_rank", "dvo_hip_comm_size",
     "dvo_hip_comm_last_error", "dvo_hip_gather_records_begin", "dvo_hip_gather_records_end", "dvo_hip_gather_records",
+    "dvo_hip_frame_create_f32_device", "dvo_hip_frames_update_f32_device_as_ex", "dvo_hip_frames_update_f32_as_ex",
+    "dvo_hip_frames_update_colour_f32depth_device_as_ex", "dvo_hip_frames_update_colour_f32depth_as_ex",
 ]
 
 ROLE_CURRENT, ROLE_REFERENCE = 0, 1
@@ -77,6 +79,12 @@ INGEST_DEFER, INGEST_NO_RAW_COPY = 1, 2
 # DVO_HIP_PIXEL_*: the formats of an 8-bit colour plane, and their bytes per pixel
 PIXEL_FORMATS = {"bgr8": 1, "rgb8": 2, "bgra8": 3, "rgba8": 4}
 PIXEL_CHANNELS = {"bgr8": 3, "rgb8": 3, "bgra8": 4, "rgba8": 4}
+# ... and of the image plane that comes with a float depth plane (dvo_hip_frames_update_colour_f32depth*): grey8 as well
+MIXED_PIXEL_FORMATS = dict(PIXEL_FORMATS, grey8=0)
+MIXED_PIXEL_CHANNELS = dict(PIXEL_CHANNELS, grey8=1)
+PIXEL_F32 = 5
+DEPTH_U16, DEPTH_F32 = 0, 1
+DEPTH_FORMATS = {"u16": DEPTH_U16, "f32": DEPTH_F32}
 COMM_ID_BYTES = 128
 
 
@@ -150,6 +158,15 @@ def lib():
                                                             C.c_float, C.c_int, C.POINTER(Config), C.c_uint]
     L.dvo_hip_frames_update_colour_as_ex.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_size_t, C.POINTER(vp), C.c_float,
                                                      C.c_int, C.POINTER(Config), C.c_uint]
+    L.dvo_hip_frame_create_f32_device.argtypes = [vp, C.c_int, C.c_int, fp, vp, vp, C.c_int, C.POINTER(vp)]
+    L.dvo_hip_frames_update_f32_device_as_ex.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_size_t, C.POINTER(vp), C.c_size_t,
+                                                         C.c_float, C.c_int, C.POINTER(Config), C.c_uint]
+    L.dvo_hip_frames_update_f32_as_ex.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_size_t, C.POINTER(vp), C.c_size_t, C.c_float,
+                                                  C.c_int, C.POINTER(Config), C.c_uint]
+    L.dvo_hip_frames_update_colour_f32depth_device_as_ex.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_size_t,
+                                                                     C.POINTER(vp), C.c_size_t, C.c_float, C.c_int, C.POINTER(Config), C.c_uint]
+    L.dvo_hip_frames_update_colour_f32depth_as_ex.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_size_t, C.POINTER(vp),
+                                                              C.c_size_t, C.c_float, C.c_int, C.POINTER(Config), C.c_uint]
     L.dvo_hip_flush_deferred.argtypes = [vp]
     L.dvo_hip_frames_set_selection.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_size_t, C.c_int, C.c_float, C.c_float]
     L.dvo_hip_frames_clear_selection.argtypes = [vp, C.c_int, C.POINTER(vp)]

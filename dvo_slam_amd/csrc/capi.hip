@@ -378,6 +378,7 @@ struct dvo_hip_context {
   long long f16_range_repeats = 0; // batches repeated with the f32 Gram because a Jacobian left the f16 range (counter "f16_range_repeats")
   long long strip_ingests = 0;     // frames ingested by the strip kernel (ingest_strips.hip), counter "strip_ingests"
   long long colour_ingests = 0;    // frames ingested from an 8-bit colour plane (colour.h), counter "colour_ingests"
+  long long f32_ingests = 0;       // frames ingested from a float depth plane (DVO_HIP_DEPTH_F32), counter "f32_ingests"
   // Option "defer_ingest": a batched re-ingest (dvo_hip_frames_update_raw_device_as) is only recorded, and carried out by the next
   // dvo_hip_match_batch right behind the first launches of its first level (or by whatever entry point comes first).  A streaming
   // caller re-ingests the next batch and then aligns the current one: enqueueing the ingest first keeps the alignment's stream idle
@@ -388,6 +389,8 @@ struct dvo_hip_context {
     std::vector<const void*> planes, depth;   // (an IngestSource's arrays, copied; its format and resolved pitch)
     int format = 0;
     size_t pitch = 0;
+    int depth_format = 0;
+    size_t depth_pitch = 0;
     float depth_scale;
     int role;
     dvo_hip_config cfg;
@@ -628,11 +631,13 @@ int fail(dvo_hip_context* ctx, int code, const char* who, const char* rule) {
 // The raw planes of a batch of frames (capi_ingest.inc), in host or in device memory: an 8-bit intensity or colour plane and a u16 depth
 // plane per frame, one format and one row pitch for all of them
 struct IngestSource {
-  const void* const* planes;   // 8-bit planes
-  int format;                  // 0 = grey, one byte per pixel; else DVO_HIP_PIXEL_*
-  size_t pitch;                // bytes from one row of an 8-bit plane to the next (as the caller gave it, 0 = tight, until check_ingest resolves it)
-  const void* const* depth;    // u16 planes, tight
+  const void* const* planes;   // image planes
+  int format;                  // 0 = grey, one byte per pixel; else DVO_HIP_PIXEL_* (DVO_HIP_PIXEL_F32: one float per pixel)
+  size_t pitch;                // bytes from one row of an image plane to the next (as the caller gave it, 0 = tight, until check_ingest resolves it)
+  const void* const* depth;    // depth planes: u16, tight; or float (DVO_HIP_DEPTH_F32) with a pitch of their own
   float depth_scale;
+  int depth_format = DVO_HIP_DEPTH_U16;
+  size_t depth_pitch = 0;      // float depth: bytes from one row to the next, 0 = tight until check_ingest resolves it (u16 depth: unused)
 };
 
 #include "capi_frames.inc"     // cameras, frame allocation and build, role planes (ensure_roles)

@@ -309,6 +309,9 @@ void fill_build_ptrs(dvo_hip_frame* f, FrameBuildPtrs& p) {
   p.colour = nullptr;
   p.colour_pitch = 0;
   p.colour_format = 0;
+  p.depth_f32 = nullptr;
+  p.depth_pitch = 0;
+  p.keep_planes = 0;
 }
 
 // the frame's own staging area: [u16 depth][u8 grey], see frame_alloc
@@ -348,8 +351,11 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
   std::vector<FrameBuildPtrs> host(n);
   bool wide = cam->w[0] % 4 == 0;
   const bool from_raw = src != nullptr;
-  const bool colour = from_raw && src->format != 0;
-  const int channels = colour ? pixel_channels(src->format) : 0;
+  const bool image_f32 = from_raw && src->format == DVO_HIP_PIXEL_F32;
+  const bool depth_f32 = from_raw && src->depth_format == DVO_HIP_DEPTH_F32;
+  const bool colour = from_raw && src->format != 0 && !image_f32;
+  const int channels = image_f32 ? kChF32 : colour ? pixel_channels(src->format) : 0;   // (the kernels' CH)
+  if (image_f32) wide = cam->w[0] % 2 == 0;
   const float depth_scale = from_raw ? src->depth_scale : 0.0f;
   const int flavor0 = eager_current_flavor(ctx, cam, 0, n);
   for (int i = 0; i < n; ++i) {
@@ -365,12 +371,30 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
     f->raw_copy = false;
     f->depth_scale = depth_scale;
     if (!from_raw) continue;
-    if (colour) {
+    if (colour || image_f32) {
       host[i].colour = static_cast<const uint8_t*>(src->planes[i]);
       host[i].colour_pitch = int(src->pitch);
       host[i].colour_format = src->format;
     } else {
       host[i].grey = static_cast<const uint8_t*>(src->planes[i]);
+      host[i].colour_pitch = int(src->pitch);   // (read with float depth only: the u16 entry points take tight grey planes)
+    }
+    if (depth_f32) {
+      // Float depth: the frame's raw copy is its float planes I / Z of level 0 -- the state of a frame created from float planes
+      // (raw0 false), so another role, a reselection and a download derive from them like there.  Without a copy the frame is a
+      // raw-ingested one that has nothing but the role planes just written.
+      host[i].depth_f32 = static_cast<const float*>(src->depth[i]);
+      host[i].depth_pitch = int(src->depth_pitch);
+      if (role < 0 || (role == 1 && keep_raw_copy)) {
+        host[i].keep_planes = 1;
+        f->raw0 = false;
+      }
+      wide = wide && f32_strips_aligned(host[i].depth_f32, src->depth_pitch) &&
+             (image_f32 ? f32_strips_aligned(host[i].colour, src->pitch)
+                        : colour ? colour_strips_aligned(host[i].colour, src->pitch, channels) : aligned_to(host[i].grey, 2) && src->pitch % 2 == 0);
+      if (role == 0) f->lv[0].cur_have = flavor0;
+      if (role == 1) mark_selected(f->lv[0], ithr, dthr);
+      continue;
     }
     host[i].raw = static_cast<const uint16_t*>(src->depth[i]);
     const bool in_place = !colour && host[i].raw == staging_depth(f) && host[i].grey == staging_grey(f);
@@ -403,7 +427,8 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
     // needed), where the strip ingest runs (ingest_strips.hip)
     built = levels < 4 ? levels : 4;
     int c_levels = 0;
-    if (role == 0 && ingest_strips_supports(cam->w[0], wide)) {
+    const bool strips = ingest_strips_supports(cam->w[0], wide, image_f32);
+    if (role == 0 && strips) {
       for (int l = 1; l < built; ++l)
         if (eager_current_flavor(ctx, cam, l, n) & kCurC) c_levels |= 1 << l;
       for (int i = 0; i < n; ++i)
@@ -411,13 +436,14 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
           if ((c_levels >> l & 1) && frames[i]->lv[l].C) frames[i]->lv[l].cur_have |= kCurC;
     }
     launch_build_from_raw(bs, tbl, n, depth_scale, cam->w[0], cam->h[0], levels, role, wide, ithr, dthr, ctx->opt_build_workgroups, flavor0, c_levels,
-                          channels, ctx->opt_stream_policy != 0);
+                          channels, ctx->opt_stream_policy != 0, depth_f32);
     if (role == 1) {
       const int rc = apply_selection(ctx, bs, n, frames, 0, 0, ctx->opt_build_workgroups);
       if (rc != DVO_HIP_OK) return rc;
     }
-    if (ingest_strips_supports(cam->w[0], wide)) ctx->strip_ingests += n;
+    if (strips) ctx->strip_ingests += n;
     if (colour) ctx->colour_ingests += n;
+    if (depth_f32) ctx->f32_ingests += n;
   }
   for (int l = built; l < levels; ++l) launch_pyr_down(bs, tbl, n, l, cam->w[l - 1], cam->h[l - 1]);
   DVO_HIP_TRY(ctx, hipGetLastError());

@@ -1,11 +1,13 @@
-// capi_ingest.inc -- the raw-frame ingest: dvo_hip_frame_create_*, dvo_hip_frames_update_raw* / _colour*, dvo_hip_flush_deferred.  Every
-// entry point describes its planes as one IngestSource (grey is the one-channel pixel format) and goes through one checker (check_ingest),
+// capi_ingest.inc -- the raw-frame ingest: dvo_hip_frame_create_*, dvo_hip_frames_update_raw* / _colour* / _f32*, dvo_hip_flush_deferred.  Every
+// entry point describes its planes as one IngestSource (grey is the one-channel pixel format, float planes are a pixel and a depth format) and goes through one checker (check_ingest),
 // one routine that records or builds (ingest) and, from host memory, one walker of the upload ring (upload_planes); the entry points
 // themselves translate flags and name themselves.  Textually included by capi.hip inside its extern "C" block, where an unnamed
 // namespace does not keep a function's name out of the library's symbol table: the helpers are static.
 
-// bytes per pixel of an IngestSource's 8-bit plane, 0 for an unknown format
-static int source_channels(int format) { return format == 0 ? 1 : pixel_channels(format); }
+// bytes per pixel of an IngestSource's image plane, 0 for an unknown format
+static int source_channels(int format) { return format == 0 ? 1 : format == DVO_HIP_PIXEL_F32 ? 4 : pixel_channels(format); }
+// the pixel_format argument of a float-depth entry point: DVO_HIP_PIXEL_GREY8 (0) is the grey plane there
+static int mixed_format(int pixel_format) { return pixel_format == DVO_HIP_PIXEL_GREY8 || pixel_channels(pixel_format) ? pixel_format : -1; }
 // the pixel_format argument of a colour entry point as an IngestSource's format: 0 is grey in here and no DVO_HIP_PIXEL_* to a caller
 static int colour_format(int pixel_format) { return pixel_channels(pixel_format) ? pixel_format : -1; }
 
@@ -13,18 +15,31 @@ static int colour_format(int pixel_format) { return pixel_channels(pixel_format)
 // `frames` (entries not null), in the same pass: they share camera and levels -- a camera is shared by frames of any level count
 // (get_camera), and frames_build writes one table and launches once per level for all of them.
 static int check_source(dvo_hip_context* ctx, const char* who, int n, dvo_hip_frame* const* frames, int width, IngestSource* src) {
-  const int channels = source_channels(src->format);
+  const int channels = src->format < 0 ? 0 : source_channels(src->format);
   if (channels == 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "unknown pixel format (DVO_HIP_PIXEL_*)");
+  const bool image_f32 = src->format == DVO_HIP_PIXEL_F32, depth_f32 = src->depth_format == DVO_HIP_DEPTH_F32;
+  if (!depth_f32 && src->depth_format != DVO_HIP_DEPTH_U16) return fail(ctx, DVO_HIP_ERR_INVALID, who, "unknown depth format (DVO_HIP_DEPTH_*)");
+  if (image_f32 && !depth_f32) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a float image plane needs a float depth plane");
   if (!src->planes || !src->depth) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null argument");
   for (int i = 0; i < n; ++i) {
     if (frames && (!frames[i] || frames[i]->cam != frames[0]->cam || frames[i]->levels != frames[0]->levels))
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "frames of one build batch must share camera and levels");
     if (!src->planes[i] || !src->depth[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null entry");
+    if ((image_f32 && !aligned_to(src->planes[i], 4)) || (depth_f32 && !aligned_to(src->depth[i], 4)))
+      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a float plane must be 4-byte aligned");
   }
   const size_t tight = size_t(width > 0 ? width : 0) * channels;
   if (src->pitch != 0 && src->pitch < tight) return fail(ctx, DVO_HIP_ERR_INVALID, who, "pitch < width * channels");
   if (src->pitch > size_t(INT_MAX)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "pitch above 2^31 - 1");
   if (src->pitch == 0) src->pitch = tight;
+  if (image_f32 && src->pitch % 4 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a float plane's pitch must be a multiple of 4");
+  if (depth_f32) {
+    const size_t tight_z = size_t(width > 0 ? width : 0) * 4;
+    if (src->depth_pitch != 0 && src->depth_pitch < tight_z) return fail(ctx, DVO_HIP_ERR_INVALID, who, "depth pitch < width * 4");
+    if (src->depth_pitch > size_t(INT_MAX)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "depth pitch above 2^31 - 1");
+    if (src->depth_pitch % 4 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a float plane's pitch must be a multiple of 4");
+    if (src->depth_pitch == 0) src->depth_pitch = tight_z;
+  }
   return DVO_HIP_OK;
 }
 
@@ -66,7 +81,7 @@ int flush_deferred(dvo_hip_context* ctx) {
     for (dvo_hip_frame* f : d.frames) f->deferred = 0;
     if (rc != DVO_HIP_OK) continue;
     ctx->deferred_ingests += 1;
-    const IngestSource src{d.planes.data(), d.format, d.pitch, d.depth.data(), d.depth_scale};
+    const IngestSource src{d.planes.data(), d.format, d.pitch, d.depth.data(), d.depth_scale, d.depth_format, d.depth_pitch};
     rc = update_raw_device(ctx, int(d.frames.size()), d.frames.data(), src, d.role, d.role >= 0 ? &d.cfg : nullptr, d.keep_raw_copy);
   }
   return rc;
@@ -75,15 +90,19 @@ int flush_deferred(dvo_hip_context* ctx) {
 }  // namespace
 
 // Host planes into the next buffer of the upload ring, on the upload stream; the build stream waits for them.  The planes land in slots
-// of [u16 depth][8-bit plane, rows of `row` bytes, tight], each padded to an even size; planes[i] / depth[i]: where frame i's went,
+// of [depth: u16, or float rows of `zrow` = 4 w bytes, tight][image plane, rows of `row` bytes, tight], each padded to an even size (to a
+// multiple of 8 with a float plane in it: the strip kernel's rows); planes[i] / depth[i]: where frame i's went,
 // *ring: the buffer.  From pinned memory (dvo_hip_host_alloc) the transfers are truly asynchronous, from pageable memory the runtime
 // stages them (correct, but the call then blocks for most of the copy).  A frame whose tight 8-bit plane directly follows its depth plane
 // moves in one transfer, and so does a run of such frames at the slot stride (without the last slot's padding, which may lie past the
 // end of the caller's buffer); a padded host pitch is repacked by a 2-D transfer.
 static int upload_planes(dvo_hip_context* ctx, int n_frames, int w, int h, size_t row, const IngestSource& host, const void** planes, const void** depth,
                          unsigned* ring) {
-  const size_t n = size_t(w) * h, plane = row * h;
-  const size_t slot_bytes = (n * 2 + plane + 1) & ~size_t(1);
+  const bool depth_f32 = host.depth_format == DVO_HIP_DEPTH_F32;
+  const size_t plane = row * h;
+  const size_t zrow = size_t(w) * (depth_f32 ? 4 : 2), zplane = zrow * h;
+  const bool ztight = !depth_f32 || host.depth_pitch == zrow;
+  const size_t slot_bytes = depth_f32 ? (zplane + plane + 7) & ~size_t(7) : (zplane + plane + 1) & ~size_t(1);
   const unsigned b = ctx->upload_next++ % dvo_hip_context::kUploadRing;
   DevBuf& buf = ctx->upload_buf[b];
   // the previous contents of this buffer may still be read by the build they were uploaded for
@@ -94,27 +113,28 @@ static int upload_planes(dvo_hip_context* ctx, int n_frames, int w, int h, size_
     DVO_HIP_TRY(ctx, buf.reserve(slot_bytes * size_t(n_frames)));
   }
   char* base = buf.as<char>();
-  const bool tight = host.pitch == row;
+  const bool tight = host.pitch == row && ztight;
   for (int i = 0; i < n_frames;) {
     const char* hd = static_cast<const char*>(host.depth[i]);
-    if (!tight || static_cast<const char*>(host.planes[i]) != hd + n * 2) {   // separate planes: two transfers for this frame
-      DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i, hd, n * 2, hipMemcpyHostToDevice, ctx->upload_stream));
-      if (tight) DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i + n * 2, host.planes[i], plane, hipMemcpyHostToDevice, ctx->upload_stream));
-      else DVO_HIP_TRY(ctx, hipMemcpy2DAsync(base + slot_bytes * i + n * 2, row, host.planes[i], host.pitch, row, h, hipMemcpyHostToDevice, ctx->upload_stream));
+    if (!tight || static_cast<const char*>(host.planes[i]) != hd + zplane) {   // separate planes: two transfers for this frame
+      if (ztight) DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i, hd, zplane, hipMemcpyHostToDevice, ctx->upload_stream));
+      else DVO_HIP_TRY(ctx, hipMemcpy2DAsync(base + slot_bytes * i, zrow, hd, host.depth_pitch, zrow, h, hipMemcpyHostToDevice, ctx->upload_stream));
+      if (host.pitch == row) DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i + zplane, host.planes[i], plane, hipMemcpyHostToDevice, ctx->upload_stream));
+      else DVO_HIP_TRY(ctx, hipMemcpy2DAsync(base + slot_bytes * i + zplane, row, host.planes[i], host.pitch, row, h, hipMemcpyHostToDevice, ctx->upload_stream));
       ++i;
       continue;
     }
     int j = i + 1;                                               // frames in the slot layout that follow each other in host memory
     while (j < n_frames && static_cast<const char*>(host.depth[j]) == hd + slot_bytes * size_t(j - i) &&
-           static_cast<const char*>(host.planes[j]) == static_cast<const char*>(host.depth[j]) + n * 2)
+           static_cast<const char*>(host.planes[j]) == static_cast<const char*>(host.depth[j]) + zplane)
       ++j;
-    DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i, hd, slot_bytes * size_t(j - i) - (slot_bytes - n * 2 - plane), hipMemcpyHostToDevice,
+    DVO_HIP_TRY(ctx, hipMemcpyAsync(base + slot_bytes * i, hd, slot_bytes * size_t(j - i) - (slot_bytes - zplane - plane), hipMemcpyHostToDevice,
                                     ctx->upload_stream));
     i = j;
   }
   for (int i = 0; i < n_frames; ++i) {
     depth[i] = base + slot_bytes * i;
-    planes[i] = base + slot_bytes * i + n * 2;
+    planes[i] = base + slot_bytes * i + zplane;
   }
   DVO_HIP_TRY(ctx, hipEventRecord(ctx->upload_done, ctx->upload_stream));
   DVO_HIP_TRY(ctx, hipStreamWaitEvent(ctx->build_stream, ctx->upload_done, 0));
@@ -139,6 +159,8 @@ static int ingest(dvo_hip_context* ctx, const char* who, int n_frames, dvo_hip_f
     d.depth.assign(src.depth, src.depth + n_frames);
     d.format = src.format;
     d.pitch = src.pitch;
+    d.depth_format = src.depth_format;
+    d.depth_pitch = src.depth_pitch;
     d.depth_scale = src.depth_scale;
     d.role = role;
     if (role >= 0) d.cfg = *cfg;
@@ -155,7 +177,7 @@ static int ingest(dvo_hip_context* ctx, const char* who, int n_frames, dvo_hip_f
   unsigned ring = 0;
   rc = upload_planes(ctx, n_frames, frames[0]->lv[0].w, frames[0]->lv[0].h, row, src, planes.data(), depth.data(), &ring);
   if (rc != DVO_HIP_OK) return rc;
-  const IngestSource uploaded{planes.data(), src.format, row, depth.data(), src.depth_scale};
+  const IngestSource uploaded{planes.data(), src.format, row, depth.data(), src.depth_scale, src.depth_format, size_t(frames[0]->lv[0].w) * 4};
   rc = update_raw_device(ctx, n_frames, frames, uploaded, role, cfg, keep);
   ctx->upload_buf_seq[ring] = ctx->build_seq;          // the newest ticket is behind every reader of the buffer
   return rc;
@@ -332,5 +354,58 @@ int dvo_hip_frames_update_colour_as_ex(dvo_hip_context* ctx, int n_frames, dvo_h
   DVO_LOCK(ctx);
   return ingest(ctx, "frames_update_colour_as_ex", n_frames, frames,
                 IngestSource{colour, colour_format(pixel_format), colour_pitch, reinterpret_cast<const void* const*>(raw_depth), depth_scale},
+                /*host_planes=*/true, /*plain_ok=*/true, role, cfg, 0, (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
+}
+
+// ---- float planes: a float image and / or a float depth plane go where the 8-bit and the u16 plane went, the kernels read them as
+// they are (DVO_HIP_PIXEL_F32, DVO_HIP_DEPTH_F32); the frame's raw copy is then its own float planes of level 0 (frames_build) ----
+
+int dvo_hip_frame_create_f32_device(dvo_hip_context* ctx, int width, int height, const float K[4], const void* intensity_dev, const void* depth_dev,
+                                    int levels, dvo_hip_frame** out) {
+  DVO_ENTER(ctx);
+  const void* i[1] = {intensity_dev};
+  const void* z[1] = {depth_dev};
+  return frame_create_raw(ctx, "frame_create_f32_device", width, height, K, levels, IngestSource{i, DVO_HIP_PIXEL_F32, 0, z, 1.0f, DVO_HIP_DEPTH_F32, 0},
+                          kCreateDevice, out);
+}
+
+int dvo_hip_frames_update_f32_device_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* intensity_dev,
+                                           size_t intensity_pitch, const void* const* depth_dev, size_t depth_pitch, float depth_scale, int role,
+                                           const dvo_hip_config* cfg, unsigned flags) {
+  DVO_LOCK(ctx);
+  return ingest(ctx, "frames_update_f32_device_as_ex", n_frames, frames,
+                IngestSource{intensity_dev, DVO_HIP_PIXEL_F32, intensity_pitch, depth_dev, depth_scale, DVO_HIP_DEPTH_F32, depth_pitch},
+                /*host_planes=*/false, /*plain_ok=*/true, role, cfg, (flags & DVO_HIP_INGEST_DEFER) ? 1 : 0, (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
+}
+
+int dvo_hip_frames_update_f32_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const float* const* intensity,
+                                    size_t intensity_pitch, const float* const* depth, size_t depth_pitch, float depth_scale, int role,
+                                    const dvo_hip_config* cfg, unsigned flags) {
+  DVO_LOCK(ctx);
+  if (ctx && (flags & DVO_HIP_INGEST_DEFER)) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_update_f32_as_ex", "DVO_HIP_INGEST_DEFER takes device planes");
+  return ingest(ctx, "frames_update_f32_as_ex", n_frames, frames,
+                IngestSource{reinterpret_cast<const void* const*>(intensity), DVO_HIP_PIXEL_F32, intensity_pitch,
+                             reinterpret_cast<const void* const*>(depth), depth_scale, DVO_HIP_DEPTH_F32, depth_pitch},
+                /*host_planes=*/true, /*plain_ok=*/true, role, cfg, 0, (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
+}
+
+int dvo_hip_frames_update_colour_f32depth_device_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour_dev,
+                                                       int pixel_format, size_t colour_pitch, const void* const* depth_dev, size_t depth_pitch,
+                                                       float depth_scale, int role, const dvo_hip_config* cfg, unsigned flags) {
+  DVO_LOCK(ctx);
+  return ingest(ctx, "frames_update_colour_f32depth_device_as_ex", n_frames, frames,
+                IngestSource{colour_dev, mixed_format(pixel_format), colour_pitch, depth_dev, depth_scale, DVO_HIP_DEPTH_F32, depth_pitch},
+                /*host_planes=*/false, /*plain_ok=*/true, role, cfg, (flags & DVO_HIP_INGEST_DEFER) ? 1 : 0, (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
+}
+
+int dvo_hip_frames_update_colour_f32depth_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour,
+                                                int pixel_format, size_t colour_pitch, const float* const* depth, size_t depth_pitch, float depth_scale,
+                                                int role, const dvo_hip_config* cfg, unsigned flags) {
+  DVO_LOCK(ctx);
+  if (ctx && (flags & DVO_HIP_INGEST_DEFER))
+    return fail(ctx, DVO_HIP_ERR_INVALID, "frames_update_colour_f32depth_as_ex", "DVO_HIP_INGEST_DEFER takes device planes");
+  return ingest(ctx, "frames_update_colour_f32depth_as_ex", n_frames, frames,
+                IngestSource{colour, mixed_format(pixel_format), colour_pitch, reinterpret_cast<const void* const*>(depth), depth_scale, DVO_HIP_DEPTH_F32,
+                             depth_pitch},
                 /*host_planes=*/true, /*plain_ok=*/true, role, cfg, 0, (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
 }

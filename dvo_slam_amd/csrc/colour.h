@@ -1,4 +1,4 @@
-// colour.h -- 8-bit colour pixels to the 8-bit grey the ingest works on: OpenCV's CV_BGR2GRAY fixed point (ITU-R BT.601 weights with
+// colour.h -- the source conversions of the ingest.  Float depth: depth_of_f32 at the end.  8-bit colour pixels to the 8-bit grey the ingest works on: OpenCV's CV_BGR2GRAY fixed point (ITU-R BT.601 weights with
 // 14 fractional bits), the conversion the reference's callers run on the host before RgbdCameraPyramid::create
 // (dvo_benchmark/src/benchmark_slam.cpp:55-69, dvo_ros/src/camera_dense_tracking.cpp:222-224).  Shared by the ingest kernels
 // (ingest_strips.hip, pyramid_kernels.hip) and the host compiler of the CPU tier (tests/test_colour_ingest.py).
@@ -32,6 +32,16 @@ DVO_HD unsigned grey_of(unsigned c0, unsigned c1, unsigned c2, GreyWeights w) { 
 // grey of the pixel whose bytes sit at bit `shift` of `bits` (bytes shift / 8 .. shift / 8 + 2)
 DVO_HD unsigned grey_at_bits(unsigned long long bits, int shift, GreyWeights w) {
   return grey_of(unsigned(bits >> shift) & 0xffu, unsigned(bits >> (shift + 8)) & 0xffu, unsigned(bits >> (shift + 16)) & 0xffu, w);
+}
+
+// The value a float depth plane's pixel is stored as (DVO_HIP_DEPTH_F32): metres times the caller's scale, ONE rounding of its own -- never
+// contracted into the differences and means that follow it.  Nothing else: NaN (a hole) stays NaN; 0, negative values and infinities
+// are taken as they are.  scale 1 is exact.
+DVO_HD float depth_of_f32(float z, float scale) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return z * scale;
 }
 
 }  // namespace dvo_hip

@@ -140,7 +140,17 @@ struct FrameBuildPtrs {                // one frame of a batched pyramid build
   const uint8_t* colour;
   int colour_pitch;
   int colour_format;
+  // Float sources (the kernels' template parameters CH = kChF32 / ZF, chosen at launch).  A float image plane (one float per pixel,
+  // 0..255, taken as is) travels in `colour` / `colour_pitch` like a colour plane.  A float depth plane (metres, NaN = hole, stored as
+  // z * scale) takes the place of `raw`, with a row stride of its own in bytes.  keep_planes != 0: the float planes I[0] / Z[0] receive
+  // level 0 -- the raw copy of a frame whose depth came as float (keep_grey / keep_raw stay null).  A grey plane that comes with float
+  // depth has rows of colour_pitch bytes.
+  const float* depth_f32;
+  int depth_pitch;
+  int keep_planes;
 };
+
+constexpr int kChF32 = 32;             // CH of the ingest kernels for a float image plane (3 / 4: bytes per colour pixel, 0: grey)
 
 // one frame of the caller-selection apply pass (k_apply_selection; include/dvo_hip.h, dvo_hip_frames_set_selection; rule: selection.h)
 struct SelectionApply {

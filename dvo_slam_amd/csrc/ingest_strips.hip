@@ -20,6 +20,11 @@
 // 4-byte-aligned window (3 channels: 6 bytes at an even offset, the window starts 2 bytes early when x % 4 == 2 and otherwise ends inside
 // pixel x + 2, never outside the row; 4 channels: 8 aligned bytes), converts it to the same two grey bytes the grey plane would hold,
 // and everything after that is the grey ingest's code.  BGR against RGB order is a wave-uniform choice of weights, not a variant.
+// Float sources: CH = kChF32 reads the image as one float per pixel (0..255, taken as is), ZF the depth as float metres (NaN = hole,
+// stored as z * scale, rounded on its own).  A lane's pixel pair is then ONE 8-byte load per float plane and row (512 B per wavefront
+// and instruction, rows 8-byte aligned) instead of 2 + 4 bytes; the conversion is the only difference, everything behind it is shared.
+// A float-depth frame's raw copy is its own float planes I / Z of level 0 (FrameBuildPtrs::keep_planes), written with the NT policy
+// like the u8 / u16 copy.
 #include "colour.h"
 #include "global_ptr.h"
 #include "launch.h"
@@ -115,14 +120,18 @@ __device__ __forceinline__ int strip_role_planes(const float (&I)[TAPS ? kStripH
 // ROLE: -1 = none (raw copy + pyramid only), 0 = current, 1 = reference (R + selection count, counter zeroed before).
 // TAPS: level 0 needs the central differences (reference role; current role with the gathered taps A + B).
 // c_levels: bit l set = pyramid level l (1-3) also gets the current role's {I, Z} plane C.
-// CH: 0 = the grey plane f.grey, 3 / 4 = the colour plane f.colour with 3 / 4 bytes per pixel.
+// CH: 0 = the grey plane f.grey, 3 / 4 = the colour plane f.colour with 3 / 4 bytes per pixel,
+// kChF32 = the float image plane in f.colour (8-byte aligned rows of f.colour_pitch bytes).
 // NT: the raw planes are read, and the planes of levels 0-1 and the raw copy written, with the non-temporal policy (global_ptr.h): a
 // background build beside the coarse levels of a match then leaves their planes in the Infinity Cache.  Levels 2-3 keep the default.
-template <int ROLE, bool TAPS, int CH = 0, bool NT = false>
+// ZF: the depth plane is f.depth_f32 (float metres, 8-byte aligned rows of f.depth_pitch bytes) instead of the u16 plane f.raw.
+template <int ROLE, bool TAPS, int CH = 0, bool NT = false, bool ZF = false>
 __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __restrict__ tbl, float scale, int w0, int h0, int levels,
                                                        float ithr, float dthr, int groups_x, int groups_y, int n_frames, int cur_flavor, int c_levels) {
 #pragma clang fp contract(off)
   static_assert(ROLE != 1 || TAPS, "the selection predicate needs the differences");
+  static_assert(CH != kChF32 || ZF, "a float image comes with float depth");
+  constexpr bool IF = CH == kChF32, COL = CH == 3 || CH == 4;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int w1 = w0 >> 1, h1 = h0 >> 1, w2 = w1 >> 1, h2 = h1 >> 1, w3 = w2 >> 1, h3 = h2 >> 1;
   const float nanv = __builtin_nanf("");
@@ -140,6 +149,10 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
     const auto colour = global_ptr(f.colour);                  // (CH > 0 only)
     const size_t pitch = size_t(f.colour_pitch);
     const GreyWeights gw = grey_weights(pixel_red_first(f.colour_format));
+    const auto depth_f = (Global<const uint8_t>)global_ptr(f.depth_f32);   // (ZF only; rows are addressed in bytes)
+    const size_t zpitch = size_t(f.depth_pitch);
+    const bool keep_planes = ZF && f.keep_planes != 0;
+    const auto I0 = global_ptr(f.I[0]), Z0 = global_ptr(f.Z[0]);
     // (the pointers of every plane the strip writes, read before the loads are issued: a scalar load further down would wait behind them)
     const auto R0 = global_ptr(f.R[0]);
     const auto A0 = global_ptr(f.A[0]);
@@ -158,33 +171,42 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
     // ---- every load of the strip, before anything is used ----
     constexpr int kFirst = TAPS ? -1 : 0, kRows = TAPS ? kStripH + 2 : kStripH;   // register row j = image row y0 + kFirst + j (clamped)
     unsigned g[kRows], d[kRows];
-    unsigned long long cb[CH ? kRows : 1];                      // (colour: the pixel pair's bytes, converted once every load is issued)
+    unsigned long long cb[COL ? kRows : 1];                     // (colour: the pixel pair's bytes, converted once every load is issued)
+    GlobalF32x2 fi[IF ? kRows : 1], fz[ZF ? kRows : 1];         // (float planes: the pixel pair itself)
 #pragma unroll
     for (int j = 0; j < kRows; ++j) {
       const int y = min(max(y0 + kFirst + j, 0), h0 - 1);       // (scalar)
       const size_t row = size_t(y) * w0;
-      if (CH) cb[j] = colour_pair_bits<CH, NT>(colour + size_t(y) * pitch, xl);
-      else g[j] = gld<NT>((Global<const uint16_t>)(grey + row + xl));
-      d[j] = gld<NT>((Global<const uint32_t>)(raw + row + xl));
+      if (COL) cb[j] = colour_pair_bits<CH, NT>(colour + size_t(y) * pitch, xl);
+      else if (IF) fi[j] = gld<NT>((Global<const GlobalF32x2>)(colour + size_t(y) * pitch + size_t(xl) * 4));
+      else g[j] = gld<NT>((Global<const uint16_t>)(grey + (ZF ? size_t(y) * pitch : row) + xl));   // (with float depth: a grey plane has a pitch)
+      if (ZF) fz[j] = gld<NT>((Global<const GlobalF32x2>)(depth_f + size_t(y) * zpitch + size_t(xl) * 4));
+      else d[j] = gld<NT>((Global<const uint32_t>)(raw + row + xl));
     }
     unsigned ge[kStripH], de[kStripH];                          // the strip's edge columns, rows y0 .. y0 + 7: lane 0 left, the others right
-    unsigned long long cbe[CH && TAPS ? kStripH : 1];           // (colour: the bytes of the pair that holds the edge column)
+    unsigned long long cbe[COL && TAPS ? kStripH : 1];          // (colour: the bytes of the pair that holds the edge column)
+    float fie[IF && TAPS ? kStripH : 1], fze[ZF && TAPS ? kStripH : 1];
     const int xe = lane == 0 ? max(sx * kStripW - 1, 0) : min(sx * kStripW + kStripW, w0 - 1);
     if (TAPS) {
       const bool edge_lane = lane == 0 || lane == 63;
 #pragma unroll
       for (int r = 0; r < kStripH; ++r) {
         const size_t row = size_t(min(y0 + r, h0 - 1)) * w0;
+        const size_t ye = size_t(min(y0 + r, h0 - 1));
         ge[r] = 0u; de[r] = 0u;
-        if (CH) cbe[r] = 0ull;
+        if (COL) cbe[r] = 0ull;
+        if (IF) fie[r] = 0.0f;
+        if (ZF) fze[r] = 0.0f;
         if (edge_lane) {
-          if (CH) cbe[r] = colour_pair_bits<CH, NT>(colour + size_t(min(y0 + r, h0 - 1)) * pitch, xe & ~1);
-          else ge[r] = gld<NT>(grey + row + xe);
-          de[r] = gld<NT>(raw + row + xe);
+          if (COL) cbe[r] = colour_pair_bits<CH, NT>(colour + ye * pitch, xe & ~1);
+          else if (IF) fie[r] = gld<NT>((Global<const float>)(colour + ye * pitch + size_t(xe) * 4));
+          else ge[r] = gld<NT>(grey + (ZF ? ye * pitch : row) + xe);
+          if (ZF) fze[r] = gld<NT>((Global<const float>)(depth_f + ye * zpitch + size_t(xe) * 4));
+          else de[r] = gld<NT>(raw + row + xe);
         }
       }
     }
-    if (CH) {
+    if (COL) {
 #pragma unroll
       for (int j = 0; j < kRows; ++j) g[j] = colour_pair_grey<CH>(cb[j], xl, gw);
       if (TAPS) {
@@ -192,7 +214,7 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
         for (int r = 0; r < kStripH; ++r) ge[r] = colour_pair_grey<CH>(cbe[r], xe & ~1, gw) >> (8 * (xe & 1)) & 0xffu;
       }
     }
-    if (keep_grey && in_x) {                                    // the frame's own copy of its raw planes (for the other role, later)
+    if (!ZF && keep_grey && in_x) {                             // the frame's own copy of its raw planes (for the other role, later)
 #pragma unroll
       for (int r = 0; r < kStripH; ++r) {
         const int y = y0 + r;
@@ -206,15 +228,31 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
     float I[kRows][2], Z[kRows][2];
 #pragma unroll
     for (int j = 0; j < kRows; ++j) {
-      I[j][0] = float(g[j] & 0xffu); I[j][1] = float(g[j] >> 8);
-      Z[j][0] = depth_of(d[j] & 0xffffu); Z[j][1] = depth_of(d[j] >> 16);
+      if (IF) { I[j][0] = fi[j].x; I[j][1] = fi[j].y; }
+      else { I[j][0] = float(g[j] & 0xffu); I[j][1] = float(g[j] >> 8); }
+      if (ZF) { Z[j][0] = depth_of_f32(fz[j].x, scale); Z[j][1] = depth_of_f32(fz[j].y, scale); }   // (colour.h)
+      else { Z[j][0] = depth_of(d[j] & 0xffffu); Z[j][1] = depth_of(d[j] >> 16); }
+    }
+    if (ZF && keep_planes && in_x) {                            // float depth: the frame's raw copy is its float planes I / Z of level 0
+#pragma unroll
+      for (int r = 0; r < kStripH; ++r) {
+        const int y = y0 + r;
+        if (y < h0) {
+          const size_t at = size_t(y) * w0 + x;
+          gst<NT>((Global<GlobalF32x2>)(I0 + at), GlobalF32x2{I[r - kFirst][0], I[r - kFirst][1]});
+          gst<NT>((Global<GlobalF32x2>)(Z0 + at), GlobalF32x2{Z[r - kFirst][0], Z[r - kFirst][1]});
+        }
+      }
     }
 
     // ---- level 0 in the frame's role ----
     float eI[kStripH], eZ[kStripH];
     if (TAPS) {
 #pragma unroll
-      for (int r = 0; r < kStripH; ++r) { eI[r] = float(ge[r]); eZ[r] = depth_of(de[r]); }
+      for (int r = 0; r < kStripH; ++r) {
+        eI[r] = IF ? fie[r] : float(ge[r]);
+        eZ[r] = ZF ? depth_of_f32(fze[r], scale) : depth_of(de[r]);
+      }
     }
     const int count = ROLE >= 0 ? strip_role_planes<ROLE, TAPS, NT>(I, Z, eI, eZ, x, y0, w0, h0, in_x, R0, A0, B0, C0, cur_flavor, ithr, dthr) : 0;
     if (ROLE == 1 && lane == 0 && count) atomicAdd((int*)sel_count, count);
@@ -340,7 +378,11 @@ void launch_derive_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames
 #undef DVO_LAUNCH_DERIVE
 }
 
-bool ingest_strips_supports(int w0, bool wide) { return wide && w0 % 4 == 0; }
+// (a float image with float depth: every even width; the 8-bit planes' loads want rows of 4 pixels)
+bool ingest_strips_supports(int w0, bool wide, bool f32_image) { return wide && w0 % (f32_image ? 2 : 4) == 0; }
+
+// (a float plane: the lanes' 8-byte pixel pairs)
+bool f32_strips_aligned(const void* plane, size_t pitch) { return reinterpret_cast<uintptr_t>(plane) % 8 == 0 && pitch % 8 == 0; }
 
 // (a colour plane: 3-byte pixels need 4-byte aligned rows, 4-byte pixels 8-byte aligned ones, see colour_pair_bits)
 bool colour_strips_aligned(const void* colour, size_t pitch, int channels) {
@@ -349,15 +391,23 @@ bool colour_strips_aligned(const void* colour, size_t pitch, int channels) {
 }
 
 void launch_ingest_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role,
-                          float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels, bool stream_nt) {
+                          float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels, bool stream_nt,
+                          bool depth_f32) {
   const int gx = (w0 + kStripW - 1) / kStripW, gy = (h0 + kStripH * kStripsPerGroup - 1) / (kStripH * kStripsPerGroup);
   const long long total = (long long)gx * gy * n_frames;
   const dim3 grid(int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total)), block(256);
   const int lv = levels < 4 ? levels : 4;
+#define DVO_LAUNCH_STRIPS_NT(ROLE, TAPS, CH, NT)                                                                                \
+  do {                                                                                                                          \
+    if (CH == kChF32 || depth_f32)                                                                                              \
+      k_ingest_strips<ROLE, TAPS, CH, NT, true><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, gx, gy, n_frames, cur_flavor, c_levels); \
+    else                                                                                                                        \
+      k_ingest_strips<ROLE, TAPS, CH == kChF32 ? 0 : CH, NT><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, gx, gy, n_frames, cur_flavor, c_levels); \
+  } while (0)
 #define DVO_LAUNCH_STRIPS(ROLE, TAPS, CH)                                                                                       \
   do {                                                                                                                          \
-    if (stream_nt) k_ingest_strips<ROLE, TAPS, CH, true><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, gx, gy, n_frames, cur_flavor, c_levels); \
-    else k_ingest_strips<ROLE, TAPS, CH><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, gx, gy, n_frames, cur_flavor, c_levels); \
+    if (stream_nt) DVO_LAUNCH_STRIPS_NT(ROLE, TAPS, CH, true);                                                                  \
+    else DVO_LAUNCH_STRIPS_NT(ROLE, TAPS, CH, false);                                                                           \
   } while (0)
 #define DVO_LAUNCH_STRIPS_ROLE(CH)                                          \
   do {                                                                      \
@@ -368,9 +418,11 @@ void launch_ingest_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames
   } while (0)
   if (colour_channels == 3) DVO_LAUNCH_STRIPS_ROLE(3);
   else if (colour_channels == 4) DVO_LAUNCH_STRIPS_ROLE(4);
+  else if (colour_channels == kChF32) DVO_LAUNCH_STRIPS_ROLE(kChF32);
   else DVO_LAUNCH_STRIPS_ROLE(0);
 #undef DVO_LAUNCH_STRIPS_ROLE
 #undef DVO_LAUNCH_STRIPS
+#undef DVO_LAUNCH_STRIPS_NT
 }
 
 }  // namespace dvo_hip

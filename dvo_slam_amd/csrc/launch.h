@@ -19,23 +19,29 @@ void launch_pyr_down(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int
 // cur_flavor (role 0): which planes of the current role are written, kCurAB | kCurC (device_types.h)
 // c_levels: bit l set = pyramid level l (1..3) also gets the current role's {I, Z} plane C in the same pass (ingest_strips.hip only:
 // ingest_strips_supports tells the caller whether the pass will honour it)
-// colour_channels: 0 = grey planes, 3 / 4 = every frame's colour plane (FrameBuildPtrs::colour) with that many bytes per pixel
+// colour_channels: 0 = grey planes, 3 / 4 = every frame's colour plane (FrameBuildPtrs::colour) with that many bytes per pixel,
+// kChF32 = a float image plane there; depth_f32: float depth planes (FrameBuildPtrs::depth_f32) instead of the u16 ones
 // stream_nt: the strip kernels read the raw planes and write the planes of levels 0-1 with the non-temporal policy (global_ptr.h; the
 // option "stream_policy" for the build stream's launches)
 void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role, bool wide,
                            float ithr, float dthr, int max_workgroups, int cur_flavor = kCurAB, int c_levels = 0, int colour_channels = 0,
-                           bool stream_nt = false);
+                           bool stream_nt = false, bool depth_f32 = false);
 // ingest_strips.hip: the role planes of one level from the float planes I / Z in strips (even widths); role 1: counters zeroed before
 bool derive_strips_supports(int w);
 void launch_derive_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int role, float ithr, float dthr,
                           int max_workgroups, int cur_flavor, bool stream_nt = false);
 // ingest_strips.hip: the same pass with one 128 x 8 strip per wavefront, registers only (even widths, aligned planes)
-bool ingest_strips_supports(int w0, bool wide);
+// f32_image: the image plane is float (with float depth): every even width qualifies, the 8-bit planes want a multiple of 4
+bool ingest_strips_supports(int w0, bool wide, bool f32_image = false);
+// a float plane's share of `wide`: address and row pitch are 8-byte aligned (a lane loads its pixel pair in one piece)
+bool f32_strips_aligned(const void* plane, size_t pitch);
 // a colour plane's share of `wide`: its address and row pitch suit the strip kernel's loads for `channels` bytes per pixel
 bool colour_strips_aligned(const void* colour, size_t pitch, int channels);
-// colour_channels: 0 = the grey plane of every frame, 3 / 4 = the colour plane (FrameBuildPtrs::colour) with that many bytes per pixel
+// colour_channels: 0 = the grey plane of every frame, 3 / 4 = the colour plane (FrameBuildPtrs::colour) with that many bytes per pixel,
+// kChF32 = a float image plane there; depth_f32: the depth plane is FrameBuildPtrs::depth_f32 (always so with a float image)
 void launch_ingest_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role,
-                          float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels = 0, bool stream_nt = false);
+                          float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels = 0, bool stream_nt = false,
+                          bool depth_f32 = false);
 void launch_derive_current(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int max_workgroups, int cur_flavor = kCurAB,
                            bool stream_nt = false);
 // mode 0: A + B from C; 1: C from A; 2: R + selection count from C (the level's counters are zeroed first)

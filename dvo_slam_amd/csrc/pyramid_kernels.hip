@@ -48,12 +48,17 @@ __device__ __forceinline__ void for_each_tile(int tiles_x, int tiles_y, int n_fr
 // Arithmetic = the reference's ingest (surface_pyramid.cpp:65-105), k_pyr_down and derive_at: bit-identical planes.
 // CH = 3 / 4 (with WIDE = false): the grey value of a pixel comes from the frame's colour plane (colour.h) -- odd widths, unaligned
 // colour planes and padded pitches the strip ingest does not take; keep_grey receives the converted grey.
+// CH = kChF32 / ZF (with WIDE = false): a float image plane / a float depth plane (ingest_strips.hip's float sources) at odd widths and
+// rows that are not 8-byte aligned; with ZF the raw copy goes to the float planes I / Z of level 0 (keep_planes).
 constexpr int kB0W = 64, kB0H = 16, kB0Stride = 68;
 
-template <int ROLE, bool WIDE, int CH = 0>
+template <int ROLE, bool WIDE, int CH = 0, bool ZF = false>
 __global__ __launch_bounds__(256) void k_build_from_raw(const FrameBuildPtrs* __restrict__ tbl, float scale, int w0, int h0, int levels,
                                                         float ithr, float dthr, int tiles_x, int tiles_y, int n_frames, int cur_flavor) {
 #pragma clang fp contract(off)
+  static_assert(!(WIDE && (CH || ZF)), "colour and float planes take the narrow loads");
+  static_assert(CH != kChF32 || ZF, "a float image comes with float depth");
+  constexpr bool IF = CH == kChF32, COL = CH == 3 || CH == 4;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // 32 x 8 threads, one 2 x 2 quad each
   const int w1 = w0 >> 1, h1 = h0 >> 1;
   const int w2 = w1 >> 1, h2 = h1 >> 1, w3 = w2 >> 1, h3 = h2 >> 1;
@@ -73,10 +78,14 @@ __global__ __launch_bounds__(256) void k_build_from_raw(const FrameBuildPtrs* __
     const auto colour = global_ptr(f.colour);                   // (CH > 0 only)
     const size_t pitch = size_t(f.colour_pitch);
     const GreyWeights gw = grey_weights(pixel_red_first(f.colour_format));
-    auto colour_grey = [&](int y, int x) -> uint8_t {          // (CH > 0 only)
-      const auto p = colour + size_t(y) * pitch + size_t(x) * CH;
+    auto colour_grey = [&](int y, int x) -> uint8_t {          // (CH = 3 / 4 only)
+      const auto p = colour + size_t(y) * pitch + size_t(x) * (COL ? CH : 0);
       return uint8_t(grey_of(p[0], p[1], p[2], gw));
     };
+    const auto depth_f = (Global<const uint8_t>)global_ptr(f.depth_f32);   // (ZF only; rows are addressed in bytes)
+    const size_t zpitch = size_t(f.depth_pitch);
+    const bool keep_planes = ZF && f.keep_planes != 0;
+    const auto I0 = global_ptr(f.I[0]), Z0 = global_ptr(f.Z[0]);
     const auto A0 = global_ptr(f.A[0]);
     const auto B0 = global_ptr(f.B[0]);
     const auto C0 = global_ptr(f.C[0]);
@@ -131,13 +140,24 @@ __global__ __launch_bounds__(256) void k_build_from_raw(const FrameBuildPtrs* __
         const int r = i / (kB0W + 2), c = i - r * (kB0W + 2);
         const int yy = y0 - 1 + r, xx = x0 - 1 + c;
         const int y = min(max(yy, 0), h0 - 1), x = min(max(xx, 0), w0 - 1);
-        const uint8_t gv = CH ? colour_grey(y, x) : grey[size_t(y) * w0 + x];
-        const uint16_t dv = raw[size_t(y) * w0 + x];
-        sI[r][c] = float(gv);
-        sZ[r][c] = depth_of(dv);
-        if (keep_grey && yy == y && xx == x && r >= 1 && r <= kB0H && c >= 1 && c <= kB0W) {
-          keep_grey[size_t(y) * w0 + x] = gv;
-          keep_raw[size_t(y) * w0 + x] = dv;
+        const bool own = yy == y && xx == x && r >= 1 && r <= kB0H && c >= 1 && c <= kB0W;   // a pixel of this tile, not of its border
+        const uint8_t gv = COL ? colour_grey(y, x) : IF ? uint8_t(0) : grey[size_t(y) * (ZF ? pitch : size_t(w0)) + x];   // (with float depth: a grey plane has a pitch)
+        const float iv = IF ? *(Global<const float>)(colour + size_t(y) * pitch + size_t(x) * 4) : float(gv);
+        sI[r][c] = iv;
+        if (ZF) {
+          const float zv = depth_of_f32(*(Global<const float>)(depth_f + size_t(y) * zpitch + size_t(x) * 4), scale);   // (colour.h)
+          sZ[r][c] = zv;
+          if (keep_planes && own) {
+            I0[size_t(y) * w0 + x] = iv;
+            Z0[size_t(y) * w0 + x] = zv;
+          }
+        } else {
+          const uint16_t dv = raw[size_t(y) * w0 + x];
+          sZ[r][c] = depth_of(dv);
+          if (keep_grey && own) {
+            keep_grey[size_t(y) * w0 + x] = gv;
+            keep_raw[size_t(y) * w0 + x] = dv;
+          }
         }
       }
     }
@@ -523,10 +543,13 @@ static int capped_grid(int tiles_x, int tiles_y, int n_frames, int max_workgroup
 }
 
 void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role, bool wide,
-                           float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels, bool stream_nt) {
-  if (ingest_strips_supports(w0, wide)) {
+                           float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels, bool stream_nt,
+                           bool depth_f32) {
+  depth_f32 = depth_f32 || colour_channels == kChF32;
+  if (ingest_strips_supports(w0, wide, colour_channels == kChF32)) {
     if (role == 1) k_zero_counts<<<dim3((n_frames + 63) / 64), dim3(64), 0, s>>>(tbl, n_frames, 0);
-    launch_ingest_strips(s, tbl, n_frames, scale, w0, h0, levels, role, ithr, dthr, max_workgroups, cur_flavor, c_levels, colour_channels, stream_nt);
+    launch_ingest_strips(s, tbl, n_frames, scale, w0, h0, levels, role, ithr, dthr, max_workgroups, cur_flavor, c_levels, colour_channels, stream_nt,
+                         depth_f32);
     return;
   }
   const int tx = (w0 + kB0W - 1) / kB0W, ty = (h0 + kB0H - 1) / kB0H;
@@ -536,7 +559,16 @@ void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frame
 #define DVO_LAUNCH_B0(ROLE, WIDE) k_build_from_raw<ROLE, WIDE><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, tx, ty, n_frames, cur_flavor)
 #define DVO_LAUNCH_B0_COLOUR(ROLE, CH) \
   k_build_from_raw<ROLE, false, CH><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, tx, ty, n_frames, cur_flavor)
-  if (colour_channels == 3) {
+#define DVO_LAUNCH_B0_ZF(ROLE, CH) \
+  k_build_from_raw<ROLE, false, CH, true><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, tx, ty, n_frames, cur_flavor)
+#define DVO_LAUNCH_B0_ZF_ROLE(CH) \
+  do { if (role == 0) DVO_LAUNCH_B0_ZF(0, CH); else if (role == 1) DVO_LAUNCH_B0_ZF(1, CH); else DVO_LAUNCH_B0_ZF(-1, CH); } while (0)
+  if (depth_f32) {
+    if (colour_channels == 3) DVO_LAUNCH_B0_ZF_ROLE(3);
+    else if (colour_channels == 4) DVO_LAUNCH_B0_ZF_ROLE(4);
+    else if (colour_channels == kChF32) DVO_LAUNCH_B0_ZF_ROLE(kChF32);
+    else DVO_LAUNCH_B0_ZF_ROLE(0);
+  } else if (colour_channels == 3) {
     if (role == 0) DVO_LAUNCH_B0_COLOUR(0, 3); else if (role == 1) DVO_LAUNCH_B0_COLOUR(1, 3); else DVO_LAUNCH_B0_COLOUR(-1, 3);
   } else if (colour_channels == 4) {
     if (role == 0) DVO_LAUNCH_B0_COLOUR(0, 4); else if (role == 1) DVO_LAUNCH_B0_COLOUR(1, 4); else DVO_LAUNCH_B0_COLOUR(-1, 4);
@@ -545,6 +577,8 @@ void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frame
   } else {
     if (role == 0) DVO_LAUNCH_B0(0, false); else if (role == 1) DVO_LAUNCH_B0(1, false); else DVO_LAUNCH_B0(-1, false);
   }
+#undef DVO_LAUNCH_B0_ZF_ROLE
+#undef DVO_LAUNCH_B0_ZF
 #undef DVO_LAUNCH_B0_COLOUR
 #undef DVO_LAUNCH_B0
 }

@@ -345,6 +345,22 @@ class RgbdCameraPyramid:
             return ptr
         return RgbdImagePyramid(self, make, self.levels, timestamp)
 
+    def create_f32_device(self, intensity_dev_ptr, depth_dev_ptr, timestamp=0.0):
+        """Float32 planes already resident in HBM (device pointers, both tight: e.g. torch tensors' data_ptr()): intensity 0..255,
+        depth in metres with NaN = invalid -- create() without the trip through the host (dvo_hip_frame_create_f32_device).  The planes
+        must stay valid until the pyramid's first use has been waited for."""
+        for p in (intensity_dev_ptr, depth_dev_ptr):
+            if not isinstance(p, (int, np.integer)) or isinstance(p, bool) or int(p) == 0 or int(p) % 4 != 0:
+                raise ValueError("a float plane needs a non-null device address that is a multiple of 4, not %r" % (p,))
+
+        def make(levels):
+            ptr = C.c_void_p()
+            self.ctx.check(self.ctx._lib.dvo_hip_frame_create_f32_device(
+                self.ctx.ptr, self.width, self.height, _fp(self.K), C.c_void_p(int(intensity_dev_ptr)), C.c_void_p(int(depth_dev_ptr)), levels,
+                C.byref(ptr)))
+            return ptr
+        return RgbdImagePyramid(self, make, self.levels, timestamp)
+
 
 def _pixel_format(name):
     if not isinstance(name, str) or name not in _lib.PIXEL_FORMATS:
@@ -542,33 +558,129 @@ def _colour_call_args(pyramids, role, config):
     return _ROLES[role], C.byref(config if isinstance(config, _lib.Config) else config.to_c())
 
 
+def _depth_format(name):
+    if not isinstance(name, str) or name not in _lib.DEPTH_FORMATS:
+        raise ValueError("depth_format must be one of %s, not %r" % (sorted(_lib.DEPTH_FORMATS), name))
+    return _lib.DEPTH_FORMATS[name]
+
+
+def _mixed_pixel_format(name):
+    """the image formats that come with a float depth plane: the colour formats and "grey8" ([h, w] or [h, w, 1] uint8)"""
+    if not isinstance(name, str) or name not in _lib.MIXED_PIXEL_FORMATS:
+        raise ValueError("pixel_format must be one of %s, not %r" % (sorted(_lib.MIXED_PIXEL_FORMATS), name))
+    return _lib.MIXED_PIXEL_FORMATS[name], _lib.MIXED_PIXEL_CHANNELS[name]
+
+
+def _f32_pitch(pitch, width, what):
+    pitch = int(pitch)
+    if pitch != 0 and pitch < width * 4:
+        raise ValueError("%s pitch %d < width * 4 = %d" % (what, pitch, width * 4))
+    if pitch % 4 != 0:
+        raise ValueError("%s pitch %d is no multiple of 4" % (what, pitch))
+    return pitch
+
+
+def _f32_plane(a, h, w, what):
+    """a float32 image [h, w] whose pixels are contiguous (rows may be padded by a multiple of 4 bytes), usable in place"""
+    if not isinstance(a, np.ndarray) or a.dtype != np.float32:
+        raise TypeError("%s plane must be a numpy float32 array" % what)
+    if a.shape != (h, w):
+        raise ValueError("%s plane must have shape %s, not %s" % (what, (h, w), a.shape))
+    if a.strides[1] != 4 or a.strides[0] < w * 4 or a.strides[0] % 4 != 0:
+        raise ValueError("%s plane must have contiguous pixels and rows at least width * 4 bytes apart: the transfer is asynchronous" % what)
+    return a
+
+
+def _one_pitch(planes, what):
+    pitch = planes[0].strides[0]
+    if any(a.strides[0] != pitch for a in planes):
+        raise ValueError("every %s plane of a batch must have the same row stride" % what)
+    return pitch
+
+
+def update_f32_device_batch(pyramids, intensity_ptrs, depth_ptrs, intensity_pitch=0, depth_pitch=0, depth_scale=1.0, role=None, config=None,
+                            flags=0):
+    """Re-ingest float32 planes (device pointers: intensity 0..255, depth in metres * depth_scale with NaN = hole; one row pitch in bytes
+    per kind for all, 0 = tight) into n existing pyramids of one camera (dvo_hip_frames_update_f32_device_as_ex).  role None: a plain
+    update; "current" / "reference" with config: ingest and prepare in one pass.  flags: _lib.INGEST_DEFER | _lib.INGEST_NO_RAW_COPY."""
+    pyr0 = pyramids[0]
+    ipitch = _f32_pitch(intensity_pitch, pyr0.camera.width, "intensity")
+    zpitch = _f32_pitch(depth_pitch, pyr0.camera.width, "depth")
+    if len(intensity_ptrs) != len(pyramids) or len(depth_ptrs) != len(pyramids):
+        raise ValueError("one intensity and one depth plane per pyramid")
+    r, cfg = _colour_call_args(pyramids, role, config)
+    n = len(pyramids)
+    ctx = pyr0.ctx
+    fr, i, z = _handles(pyramids), _pointer_array(intensity_ptrs), _pointer_array(depth_ptrs)
+    ctx.check(ctx._lib.dvo_hip_frames_update_f32_device_as_ex(ctx.ptr, n, fr, i, ipitch, z, zpitch, depth_scale, r, cfg, int(flags)))
+
+
+def update_f32_host_batch(pyramids, intensity_host, depth_host, depth_scale=1.0, role=None, config=None, flags=0):
+    """Re-ingest float32 planes from HOST arrays ([h, w] float32 views with contiguous pixels; the row stride of each kind, the same for
+    the whole batch, is taken from the views) into n existing pyramids: DMA on the context's upload stream, then the batched build
+    (dvo_hip_frames_update_f32_as_ex).  The arrays must stay unchanged until upload_wait() or a match on these pyramids has returned.
+    flags: _lib.INGEST_NO_RAW_COPY (a host ingest cannot be deferred)."""
+    cam = pyramids[0].camera
+    if len(intensity_host) != len(pyramids) or len(depth_host) != len(pyramids):
+        raise ValueError("one intensity and one depth plane per pyramid")
+    if int(flags) & _lib.INGEST_DEFER:
+        raise ValueError("INGEST_DEFER takes device planes")
+    ints = [_f32_plane(a, cam.height, cam.width, "intensity") for a in intensity_host]
+    deps = [_f32_plane(b, cam.height, cam.width, "depth") for b in depth_host]
+    ipitch, zpitch = _one_pitch(ints, "intensity"), _one_pitch(deps, "depth")
+    r, cfg = _colour_call_args(pyramids, role, config)
+    n = len(pyramids)
+    ctx = pyramids[0].ctx
+    vp = C.c_void_p
+    i = (vp * n)(*[vp(a.ctypes.data) for a in ints])
+    z = (vp * n)(*[vp(b.ctypes.data) for b in deps])
+    ctx.check(ctx._lib.dvo_hip_frames_update_f32_as_ex(ctx.ptr, n, _handles(pyramids), i, ipitch, z, zpitch, depth_scale, r, cfg, int(flags)))
+
+
 def update_colour_device_batch(pyramids, colour_dev_ptrs, depth_dev_ptrs, pixel_format="bgr8", pitch=0, depth_scale=1.0 / 5000.0, role=None,
-                               config=None, flags=0):
+                               config=None, flags=0, depth_format="u16", depth_pitch=0):
     """Re-ingest 8-bit colour planes (device pointers, one format and row pitch in bytes for all, 0 = tight) + u16 depth planes into n
     existing pyramids of one camera (dvo_hip_frames_update_colour_device_as_ex).  role None: a plain update; "current" / "reference"
-    with config: ingest and prepare in one pass.  flags: _lib.INGEST_DEFER | _lib.INGEST_NO_RAW_COPY."""
-    fmt, ch = _pixel_format(pixel_format)
+    with config: ingest and prepare in one pass.  flags: _lib.INGEST_DEFER | _lib.INGEST_NO_RAW_COPY.
+    depth_format "f32": the depth planes are float32 metres with NaN = hole and a row pitch of their own (depth_pitch, bytes, 0 = tight;
+    dvo_hip_frames_update_colour_f32depth_device_as_ex); pixel_format may then also be "grey8".  Mind depth_scale: 1.0 for metres."""
+    zf = _depth_format(depth_format) == _lib.DEPTH_F32
+    fmt, ch = _mixed_pixel_format(pixel_format) if zf else _pixel_format(pixel_format)
     pyr0 = pyramids[0]
     pitch = _pitch(pitch, pyr0.camera.width, ch)
+    if zf:
+        depth_pitch = _f32_pitch(depth_pitch, pyr0.camera.width, "depth")
+    elif int(depth_pitch) != 0:
+        raise ValueError("a u16 depth plane is tight: depth_pitch goes with depth_format 'f32'")
     if len(colour_dev_ptrs) != len(pyramids) or len(depth_dev_ptrs) != len(pyramids):
         raise ValueError("one colour and one depth plane per pyramid")
     r, cfg = _colour_call_args(pyramids, role, config)
     n = len(pyramids)
     ctx = pyr0.ctx
     fr, c, z = _handles(pyramids), _pointer_array(colour_dev_ptrs), _pointer_array(depth_dev_ptrs)
-    ctx.check(ctx._lib.dvo_hip_frames_update_colour_device_as_ex(ctx.ptr, n, fr, c, fmt, pitch, z, depth_scale, r, cfg, int(flags)))
+    if zf:
+        ctx.check(ctx._lib.dvo_hip_frames_update_colour_f32depth_device_as_ex(ctx.ptr, n, fr, c, fmt, pitch, z, depth_pitch, depth_scale, r, cfg,
+                                                                              int(flags)))
+    else:
+        ctx.check(ctx._lib.dvo_hip_frames_update_colour_device_as_ex(ctx.ptr, n, fr, c, fmt, pitch, z, depth_scale, r, cfg, int(flags)))
 
 
-def update_colour_host_batch(pyramids, colour_host, depth_host, pixel_format="bgr8", depth_scale=1.0 / 5000.0, role=None, config=None, flags=0):
+def update_colour_host_batch(pyramids, colour_host, depth_host, pixel_format="bgr8", depth_scale=1.0 / 5000.0, role=None, config=None, flags=0,
+                             depth_format="u16"):
     """Re-ingest 8-bit colour planes from HOST arrays ([h, w, 3 | 4] uint8, one format; rows may be padded by the same stride) + u16 depth
     planes (C-contiguous) into n existing pyramids: DMA on the context's upload stream, then the batched build
-    (dvo_hip_frames_update_colour_as_ex).  The arrays must stay unchanged until upload_wait() or a match on these pyramids has returned."""
-    fmt, ch = _pixel_format(pixel_format)
+    (dvo_hip_frames_update_colour_as_ex).  The arrays must stay unchanged until upload_wait() or a match on these pyramids has returned.
+    depth_format "f32": the depth planes are [h, w] float32 views (metres, NaN = hole; rows may be padded by the same stride;
+    dvo_hip_frames_update_colour_f32depth_as_ex); pixel_format may then also be "grey8" ([h, w, 1] uint8).  Mind depth_scale: 1.0 for metres."""
+    zf = _depth_format(depth_format) == _lib.DEPTH_F32
+    fmt, ch = _mixed_pixel_format(pixel_format) if zf else _pixel_format(pixel_format)
     cam = pyramids[0].camera
     if len(colour_host) != len(pyramids) or len(depth_host) != len(pyramids):
         raise ValueError("one colour and one depth plane per pyramid")
+    if zf and int(flags) & _lib.INGEST_DEFER:
+        raise ValueError("INGEST_DEFER takes device planes")
     cols = [_colour_plane(a, cam.height, cam.width, ch) for a in colour_host]
-    deps = [_depth_plane(b, cam.height, cam.width) for b in depth_host]
+    deps = [_f32_plane(b, cam.height, cam.width, "depth") if zf else _depth_plane(b, cam.height, cam.width) for b in depth_host]
     if any(a is not b for a, b in zip(cols, colour_host)) or any(a is not b for a, b in zip(deps, depth_host)):
         raise ValueError("host planes must be usable in place (pixels contiguous, depth C-contiguous): the transfer is asynchronous")
     pitch = cols[0].strides[0]
@@ -580,7 +692,11 @@ def update_colour_host_batch(pyramids, colour_host, depth_host, pixel_format="bg
     vp = C.c_void_p
     c = (vp * n)(*[vp(a.ctypes.data) for a in cols])
     z = (vp * n)(*[vp(b.ctypes.data) for b in deps])
-    ctx.check(ctx._lib.dvo_hip_frames_update_colour_as_ex(ctx.ptr, n, _handles(pyramids), c, fmt, pitch, z, depth_scale, r, cfg, int(flags)))
+    if zf:
+        ctx.check(ctx._lib.dvo_hip_frames_update_colour_f32depth_as_ex(ctx.ptr, n, _handles(pyramids), c, fmt, pitch, z, _one_pitch(deps, "depth"),
+                                                                       depth_scale, r, cfg, int(flags)))
+    else:
+        ctx.check(ctx._lib.dvo_hip_frames_update_colour_as_ex(ctx.ptr, n, _handles(pyramids), c, fmt, pitch, z, depth_scale, r, cfg, int(flags)))
 
 
 def upload_wait(ctx):

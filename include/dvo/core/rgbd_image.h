@@ -183,6 +183,11 @@ class RgbdCameraPyramid {
   // the device like those of the other levels: when the pyramid is built with host mirrors on, else by syncHostMirrors().
   inline RgbdImagePyramidPtr createFromColour(const void* colour, int pixel_format, size_t colour_pitch, const uint16_t* raw_depth,
                                               float depth_scale = 1.0f / 5000.0f);
+  // not in the reference: the pyramid of two float planes that already live in DEVICE memory (both tight; intensity 0..255, depth in
+  // metres with NaN = invalid -- a filtered, rendered or predicted depth image), without a trip through the host
+  // (dvo_hip_frame_create_f32_device).  The build is asynchronous: the planes must stay valid until the pyramid's first use has been
+  // waited for.  Host matrices as after createFromColour: downloaded when host mirrors are on, else by syncHostMirrors().
+  inline RgbdImagePyramidPtr createFromFloatDevice(const void* intensity_dev, const void* depth_dev);
 
  private:
   std::vector<RgbdCameraPtr> levels_;
@@ -293,6 +298,38 @@ class RgbdImagePyramid {
     build(idx + 1);
     return *levels_[idx];
   }
+  // not in the reference: new float matrices into this pyramid's EXISTING device frame (dvo_hip_frames_update_f32_as_ex) -- the
+  // streaming form of RgbdCameraPyramid::create for every camera image.  No new frame, the handle stays (a PointSelection keeps it), and
+  // so does the caller selection.  level(0).intensity / depth are rebound to the new matrices; whatever other host mirrors a level held
+  // is dropped and, with host mirrors on, downloaded again.  Before the first build() it only swaps the matrices.  Returns once the
+  // matrices' pixels have left the host (they may be reused).
+  void update(const dvo::compat::ImageMat& intensity, const dvo::compat::ImageMat& depth) {
+    assert(dvo::compat::image_is_float1(intensity) && dvo::compat::image_is_float1(depth));
+    assert(dvo::compat::image_rows(intensity) == dvo::compat::image_rows(depth) && dvo::compat::image_cols(intensity) == dvo::compat::image_cols(depth));
+    intensity_ = intensity;
+    depth_ = depth;
+    if (!frame_) return;
+    const float* i[1] = {dvo::compat::image_ptr(intensity_)};
+    const float* z[1] = {dvo::compat::image_ptr(depth_)};
+    dvo_hip_frame* one[1] = {frame_};
+    if (dvo_hip_check(ctx_, dvo_hip_frames_update_f32_as_ex(ctx_, 1, one, i, 0, z, 0, 1.0f, -1, nullptr, 0u), "dvo_hip_frames_update_f32_as_ex"))
+      dvo_hip_check(ctx_, dvo_hip_upload_wait(ctx_), "dvo_hip_upload_wait");
+    explicit_levels_ = 0u;   // (new pixels: the device dropped every accepted set)
+    for (size_t l = 0; l < levels_.size(); ++l) {
+      RgbdImage& image = *levels_[l];
+      unsigned had = 0u;
+      if (l > 0 && !dvo::compat::image_empty(image.intensity)) had |= RgbdImage::MirrorPlanes;
+      if (!dvo::compat::image_empty(image.intensity_dx)) had |= RgbdImage::MirrorDerivatives;
+      if (image.pointcloud.cols() > 0) had |= RgbdImage::MirrorPointCloud;
+      if (image.acceleration.rows > 0) had |= RgbdImage::MirrorAcceleration;
+      image.intensity = l == 0 ? intensity_ : dvo::compat::ImageMat();
+      image.depth = l == 0 ? depth_ : dvo::compat::ImageMat();
+      image.intensity_dx = image.intensity_dy = image.depth_dx = image.depth_dy = dvo::compat::ImageMat();
+      image.pointcloud = RgbdImage::PointCloud();
+      image.acceleration = dvo::compat::AccelerationMat();
+      if (had != 0u && RgbdImage::hostMirrors()) image.syncHostMirrors(had);
+    }
+  }
   double timestamp() const { return levels_.empty() ? timestamp_ : levels_[0]->timestamp; }   // rgbd_image.cpp: level(0).timestamp
   void timestamp(double t) { timestamp_ = t; for (size_t l = 0; l < levels_.size(); ++l) levels_[l]->timestamp = t; }
 
@@ -387,6 +424,19 @@ inline RgbdImagePyramidPtr RgbdCameraPyramid::createFromColour(const void* colou
   dvo_hip_frame* frame = 0;
   if (!dvo_hip_check(ctx, dvo_hip_frame_create_colour(ctx, int(c0.width()), int(c0.height()), K, colour, pixel_format, colour_pitch, raw_depth,
                                                       depth_scale, all, &frame), "dvo_hip_frame_create_colour"))
+    frame = 0;
+  return RgbdImagePyramidPtr(new RgbdImagePyramid(*this, ctx, frame));
+}
+
+inline RgbdImagePyramidPtr RgbdCameraPyramid::createFromFloatDevice(const void* intensity_dev, const void* depth_dev) {
+  const RgbdCamera& c0 = level(0);
+  int all = 1;
+  while (all < DVO_HIP_MAX_LEVELS && (c0.width() >> all) >= 2 && (c0.height() >> all) >= 2) ++all;
+  const float K[4] = {c0.intrinsics().fx(), c0.intrinsics().fy(), c0.intrinsics().ox(), c0.intrinsics().oy()};
+  dvo_hip_context* ctx = DeviceContext::current();
+  dvo_hip_frame* frame = 0;
+  if (!dvo_hip_check(ctx, dvo_hip_frame_create_f32_device(ctx, int(c0.width()), int(c0.height()), K, intensity_dev, depth_dev, all, &frame),
+                     "dvo_hip_frame_create_f32_device"))
     frame = 0;
   return RgbdImagePyramidPtr(new RgbdImagePyramid(*this, ctx, frame));
 }

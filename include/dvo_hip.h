@@ -214,6 +214,59 @@ int dvo_hip_frames_update_colour_device_as_ex(dvo_hip_context* ctx, int n_frames
 int dvo_hip_frames_update_colour_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour,
                                        int pixel_format, size_t colour_pitch, const uint16_t* const* raw_depth, float depth_scale,
                                        int role, const dvo_hip_config* cfg, unsigned flags);
+/* ---- float planes: a float32 intensity and / or depth plane, host or device, into existing frames --------------------------------
+ * The reference's class API hands over float matrices (RgbdCameraPyramid::create(intensity, depth)), ROS drivers publish registered depth
+ * as "32FC1" metres with NaN holes next to a "bgr8" / "mono8" image (dvo_ros/src/camera_dense_tracking.cpp:231-240), and a filtered,
+ * rendered or predicted depth image is a float tensor in device memory.  These entry points are the streaming ingest for such planes:
+ * they re-ingest into existing frames, build level 0 straight into `role`, can be deferred, and take the same strip kernels.
+ *   image plane  DVO_HIP_PIXEL_F32: one float per pixel, 0..255, taken as is (no clamp, no rounding); its pitch follows the colour
+ *                pitch rules, in bytes, 0 = tight (width * 4).  Or an 8-bit plane: DVO_HIP_PIXEL_GREY8 (one byte per pixel) or one of
+ *                the four colour formats, converted as by the colour ingest.
+ *   depth plane  DVO_HIP_DEPTH_F32: one float per pixel, metres, NaN = hole, with a pitch of its own in bytes, 0 = tight (width * 4).
+ *                The stored depth is z * depth_scale, one rounding of its own (depth_scale 1 is exact; float millimetres are
+ *                depth_scale 1e-3f).  Nothing else is done to a value: NaN stays NaN (a hole); 0, negative values and +-infinity are
+ *                stored as they are (times depth_scale), exactly as dvo_hip_frame_create_f32 stores them -- 0 is NOT a hole here (it is
+ *                in a u16 plane, DVO_HIP_DEPTH_U16).  Such pixels then behave as in the reference: an infinite depth or depth
+ *                difference fails the selection's finiteness test or warps out of the image, a depth <= 0 warps behind the camera.
+ *   supported    F32 image + F32 depth; GREY8 / BGR8 / RGB8 / BGRA8 / RGBA8 image + F32 depth.  F32 image + U16 depth: DVO_HIP_ERR_INVALID.
+ *   alignment    float planes and their pitches must be multiples of 4 bytes (DVO_HIP_ERR_INVALID otherwise).  The strip kernel takes
+ *                frames of even width whose float rows are 8-byte aligned (address and pitch; an 8-bit image plane under the colour
+ *                ingest's rules, width a multiple of 4); everything else takes the tile kernel.  Same planes either way.
+ *   raw copy     every frame owns float planes I and Z of level 0; after an ingest with float depth THEY are the frame's raw copy (I holds
+ *                the converted grey as float after an 8-bit image), the u8 / u16 staging area is not used.  A later role, other
+ *                thresholds, dvo_hip_frame_select, dvo_hip_frames_prepare, a caller selection and dvo_hip_frame_download_plane work as
+ *                after any other ingest, and a frame may alternate between u8 / u16 and float ingests.  DVO_HIP_INGEST_NO_RAW_COPY and
+ *                option "keep_raw_copy" mean what they mean above: no copy, the other role is refused with DVO_HIP_ERR_INVALID.
+ * role = DVO_HIP_ROLE_*, or -1 with cfg NULL for a plain update.  flags: DVO_HIP_INGEST_DEFER (device planes only -- the host entry
+ * points refuse it; the request records both formats and both pitches) | DVO_HIP_INGEST_NO_RAW_COPY.  Host planes go through the upload
+ * buffers in slots of [depth][image]; a frame whose tight image plane directly follows its tight depth plane moves in one transfer, a run
+ * of such frames at a stride of the two planes' bytes rounded up to 8 in one, and padded pitches are repacked by a 2-D transfer.
+ * DVO_HIP_ERR_INVALID, every frame and counter left as it was: an unknown format, F32 image + U16 depth, a null array or entry, a pitch
+ * below width * 4 (or width * channels), a pitch above 2^31 - 1, a misaligned float plane, frames of differing cameras or level
+ * counts, DVO_HIP_INGEST_DEFER with host planes. */
+#define DVO_HIP_PIXEL_GREY8 0 /* one byte per pixel; the float-depth entry points only (the colour entry points refuse it) */
+#define DVO_HIP_PIXEL_F32 5   /* one float per pixel, 0..255 */
+#define DVO_HIP_DEPTH_U16 0   /* 0 -> NaN, else value * depth_scale */
+#define DVO_HIP_DEPTH_F32 1   /* metres * depth_scale, NaN = hole */
+/* the device counterpart of dvo_hip_frame_create_f32 (both planes tight): asynchronous on the build stream like
+ * dvo_hip_frame_create_raw_device; the planes must stay valid until the frame's first use has been waited for */
+int dvo_hip_frame_create_f32_device(dvo_hip_context* ctx, int width, int height, const float K[4], const void* intensity_dev,
+                                    const void* depth_dev, int levels, dvo_hip_frame** out);
+int dvo_hip_frames_update_f32_device_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames,
+                                           const void* const* intensity_dev, size_t intensity_pitch, const void* const* depth_dev,
+                                           size_t depth_pitch, float depth_scale, int role, const dvo_hip_config* cfg, unsigned flags);
+int dvo_hip_frames_update_f32_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const float* const* intensity,
+                                    size_t intensity_pitch, const float* const* depth, size_t depth_pitch, float depth_scale, int role,
+                                    const dvo_hip_config* cfg, unsigned flags);
+/* an 8-bit image plane (DVO_HIP_PIXEL_GREY8 or a colour format) + a float depth plane: a ROS "bgr8" + "32FC1" pair */
+int dvo_hip_frames_update_colour_f32depth_device_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames,
+                                                       const void* const* colour_dev, int pixel_format, size_t colour_pitch,
+                                                       const void* const* depth_dev, size_t depth_pitch, float depth_scale, int role,
+                                                       const dvo_hip_config* cfg, unsigned flags);
+int dvo_hip_frames_update_colour_f32depth_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames,
+                                                const void* const* colour, int pixel_format, size_t colour_pitch,
+                                                const float* const* depth, size_t depth_pitch, float depth_scale, int role,
+                                                const dvo_hip_config* cfg, unsigned flags);
 /* carries out every recorded ingest now; returns the first failure */
 int dvo_hip_flush_deferred(dvo_hip_context* ctx);
 int dvo_hip_upload_wait(dvo_hip_context* ctx);
@@ -506,6 +559,8 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value);
  * "strip_ingests" (frames whose raw planes went through the strip ingest, one 128 x 8 strip per wavefront -- even-width rows and
  * 4 / 8-byte aligned planes; the others take the tile kernel),
  * "colour_ingests" (frames ingested from an 8-bit colour plane, dvo_hip_frame_create_colour* / dvo_hip_frames_update_colour*),
+ * "f32_ingests" (frames ingested from a float depth plane, dvo_hip_frame_create_f32_device / dvo_hip_frames_update_f32* /
+ * dvo_hip_frames_update_colour_f32depth*; "strip_ingests" counts those of them that took the strip kernel),
  * "warmup_wait_us" (the longest of the nine stream waits dvo_hip_context_create makes on trivial commands to warm up the runtime's wait
  * path, in microseconds: the first GPU process on a fresh box has been seen to spend 14-24 ms in its first wait),
  * "host_batches" and "host_ns_prepare" / "host_ns_enqueue" / "host_ns_wait" / "host_ns_finish" (nanoseconds the calling thread spent
