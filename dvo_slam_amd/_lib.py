@@ -57,6 +57,11 @@ class IterationOut(C.Structure):
                 ("neg_loglik", C.c_double), ("A", C.c_double * 36), ("b", C.c_double * 6), ("sum_w", C.c_double)]
 
 
+class Lens(C.Structure):
+    """dvo_hip_lens: K_raw = fx fy ox oy of the raw image, D = k1 k2 p1 p2 k3 k4 k5 k6 (OpenCV / ROS plumb_bob, rational_polynomial)."""
+    _fields_ = [("K_raw", C.c_float * 4), ("D", C.c_float * 8), ("rectify_depth", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/dvo_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "dvo_hip_context_create", "dvo_hip_context_destroy", "dvo_hip_last_error", "dvo_hip_context_stream",
@@ -72,6 +77,7 @@ EXPORTS = [
     "dvo_hip_comm_last_error", "dvo_hip_gather_records_begin", "dvo_hip_gather_records_end", "dvo_hip_gather_records",
     "dvo_hip_frame_create_f32_device", "dvo_hip_frames_update_f32_device_as_ex", "dvo_hip_frames_update_f32_as_ex",
     "dvo_hip_frames_update_colour_f32depth_device_as_ex", "dvo_hip_frames_update_colour_f32depth_as_ex",
+    "dvo_hip_frames_set_lens", "dvo_hip_frames_clear_lens",
 ]
 
 ROLE_CURRENT, ROLE_REFERENCE = 0, 1
@@ -171,6 +177,9 @@ def lib():
     L.dvo_hip_frames_set_selection.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_size_t, C.c_int, C.c_float, C.c_float]
     L.dvo_hip_frames_clear_selection.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.dvo_hip_frame_set_level_selection.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_uint8)]
+    if hasattr(L, "dvo_hip_frames_set_lens"):   # (DVO_HIP_LIBRARY may name an older build for an A/B: it has no lens, a call raises AttributeError)
+        L.dvo_hip_frames_set_lens.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(Lens)]
+        L.dvo_hip_frames_clear_lens.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.dvo_hip_context_device.argtypes = [vp]
     L.dvo_hip_comm_get_unique_id.argtypes = [vp]
     L.dvo_hip_comm_create.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]

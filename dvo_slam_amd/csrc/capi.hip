@@ -134,6 +134,10 @@ struct dvo_hip_frame {
   float sel_min = 0.0f, sel_max = INFINITY;
   DevBuf sel_mask;
   unsigned long long sel_visit = 0;   // (apply_selection: the call that last listed the frame)
+  // The lens of the frame's camera (dvo_hip_frames_set_lens, lens.h): every later ingest rectifies the caller's planes into the frame's
+  // float planes of level 0 first (rectify_frames).  The frame's, not the camera's: CameraGeom describes the rectified image.
+  bool lens_on = false;
+  dvo_hip_lens lens = {};
 };
 
 // Small host -> device transfers (pointer tables, initial guesses) go through slots of pinned memory: from a pageable
@@ -379,6 +383,7 @@ struct dvo_hip_context {
   long long strip_ingests = 0;     // frames ingested by the strip kernel (ingest_strips.hip), counter "strip_ingests"
   long long colour_ingests = 0;    // frames ingested from an 8-bit colour plane (colour.h), counter "colour_ingests"
   long long f32_ingests = 0;       // frames ingested from a float depth plane (DVO_HIP_DEPTH_F32), counter "f32_ingests"
+  long long lens_ingests = 0;      // frames rectified at ingest (dvo_hip_frames_set_lens), counter "lens_ingests"
   // Option "defer_ingest": a batched re-ingest (dvo_hip_frames_update_raw_device_as) is only recorded, and carried out by the next
   // dvo_hip_match_batch right behind the first launches of its first level (or by whatever entry point comes first).  A streaming
   // caller re-ingests the next batch and then aligns the current one: enqueueing the ingest first keeps the alignment's stream idle
@@ -492,6 +497,7 @@ struct dvo_hip_context {
   DevBuf misc, role_tbl_cur, role_tbl_ref, prep_tbl_cur, prep_tbl_ref;
   DevBuf sel_tbl_main, sel_tbl_build;                 // tables of the caller-selection apply pass, one per stream (apply_selection)
   unsigned long long sel_visits = 0;
+  DevBuf lens_tbl;                                    // table of the rectify pass (rectify_frames; allocated by the first lens ingest)
   static const int kTableSlots = 4;
   DevBuf build_tbl[kTableSlots];   // (a few, picked by the list's first frame: see Workspace::pair_ptrs)
   DevBuf* build_tbl_cur = nullptr; // the one that holds the table of build_tbl_frames
@@ -837,7 +843,7 @@ void dvo_hip_context_destroy(dvo_hip_context* ctx) {
   if (ctx->build_stream) (void)hipStreamDestroy(ctx->build_stream);
   for (DevBuf& b : ctx->build_tbl) b.release();
   for (DevBuf* b : {&ctx->misc, &ctx->role_tbl_cur, &ctx->role_tbl_ref, &ctx->prep_tbl_cur, &ctx->prep_tbl_ref, &ctx->rcp_table, &ctx->ref_order_planes,
-                    &ctx->sel_tbl_main, &ctx->sel_tbl_build}) b->release();
+                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl}) b->release();
   for (DevBuf& b : ctx->upload_buf) b.release();
   for (const dvo_hip_context::PooledBlock& b : ctx->frame_pool) (void)hipFree(b.p);
   ctx->frame_pool.clear();
@@ -1069,6 +1075,39 @@ int dvo_hip_frames_clear_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_f
     f->sel_min = 0.0f;
     f->sel_max = INFINITY;
     invalidate_reference_role(f);   // (the mask buffer is kept for the next selection)
+  }
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_frames_set_lens(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const dvo_hip_lens* lens) {
+  DVO_ENTER(ctx);                                              // (a recorded ingest of these frames is carried out with the lens it was recorded under)
+  if (!ctx || n_frames < 1 || !frames || !lens) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_lens: bad argument");
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(lens->K_raw[k])) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_lens: K_raw is not finite");
+  for (int k = 0; k < 8; ++k)
+    if (!std::isfinite(lens->D[k])) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_lens: D is not finite");
+  if (!(lens->K_raw[0] > 0.0f) || !(lens->K_raw[1] > 0.0f)) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_lens: need fx_raw > 0 and fy_raw > 0");
+  for (int i = 0; i < n_frames; ++i)
+    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_lens: null frame");
+  for (int i = 0; i < n_frames; ++i) {
+    dvo_hip_frame* f = frames[i];
+    f->lens_on = true;
+    std::memcpy(f->lens.K_raw, lens->K_raw, sizeof f->lens.K_raw);
+    std::memcpy(f->lens.D, lens->D, sizeof f->lens.D);
+    f->lens.rectify_depth = lens->rectify_depth != 0 ? 1 : 0;   // (lenses are compared bytewise: one spelling of "on", reserved ignored)
+    f->lens.reserved = 0;
+  }
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_frames_clear_lens(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames) {
+  DVO_ENTER(ctx);
+  if (!ctx || n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_lens: bad argument");
+  for (int i = 0; i < n_frames; ++i)
+    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_lens: null frame");
+  for (int i = 0; i < n_frames; ++i) {
+    frames[i]->lens_on = false;
+    frames[i]->lens = dvo_hip_lens{};
   }
   return DVO_HIP_OK;
 }

@@ -341,6 +341,33 @@ int eager_current_flavor(const dvo_hip_context* ctx, const CameraGeom* cam, int 
   return BatchPolicy(ctx->compute_units).ingest_skips_taps(n_frames) ? kCurC : (kCurAB | kCurC);
 }
 
+// The rectify pass of n frames that carry a lens (the same one: check_source), on the build stream: the caller's planes `src` through the
+// lens into each frame's own float planes I / Z of level 0, depth conversion included (lens.h, rectify.hip).  What follows in
+// frames_build is the float ingest of those planes, read where they lie: no staging, nothing the context owns but the pointer table.
+int rectify_frames(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource& src) {
+  const CameraGeom* cam = frames[0]->cam;
+  const dvo_hip_lens& lens = frames[0]->lens;
+  const bool image_f32 = src.format == DVO_HIP_PIXEL_F32, depth_f32 = src.depth_format == DVO_HIP_DEPTH_F32;
+  std::vector<RectifyPtrs> host(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) host[i] = RectifyPtrs{src.planes[i], src.depth[i], frames[i]->lv[0].I, frames[i]->lv[0].Z};
+  RectifyArgs a;
+  a.map = lens_prepare(cam->K0, lens.K_raw, lens.D);
+  a.w = cam->w[0];
+  a.h = cam->h[0];
+  a.image_pitch = int(src.pitch);
+  a.depth_pitch = depth_f32 ? int(src.depth_pitch) : cam->w[0] * 2;   // (u16 depth planes are tight)
+  a.red_first = pixel_red_first(src.format) ? 1 : 0;
+  a.rectify_depth = lens.rectify_depth;
+  a.depth_scale = src.depth_scale;
+  const size_t bytes = host.size() * sizeof(RectifyPtrs);
+  DVO_HIP_TRY(ctx, ctx->lens_tbl.reserve(bytes));
+  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->build_stream, ctx->lens_tbl.p, host.data(), bytes));
+  launch_rectify(ctx->build_stream, ctx->lens_tbl.as<RectifyPtrs>(), n, a, image_f32 ? kChF32 : pixel_channels(src.format), depth_f32,
+                 ctx->opt_build_workgroups, ctx->opt_stream_policy != 0);
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  return DVO_HIP_OK;
+}
+
 // src: device planes whose pitch is resolved, of frames that share camera and levels (check_ingest has seen to both).  From a colour
 // source the kernels convert and leave grey in the frames' raw copies.
 int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource* src, int role = -1, float ithr = 0.0f,
@@ -348,6 +375,23 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
   Range range("build");
   const CameraGeom* cam = frames[0]->cam;
   const int levels = frames[0]->levels;
+  // Frames that carry a lens: the caller's planes are rectified into the frames' float planes of level 0 (depth scaled there), and the
+  // ingest below is the float ingest of THOSE planes, in place -- the frame ends as a lens-less frame fed the rectified pair would.
+  const bool lens = src != nullptr && frames[0]->lens_on;
+  std::vector<const void*> rect_planes;
+  IngestSource rectified;
+  if (lens) {
+    const int rc = rectify_frames(ctx, n, frames, *src);
+    if (rc != DVO_HIP_OK) return rc;
+    rect_planes.resize(2 * size_t(n));
+    for (int i = 0; i < n; ++i) {
+      rect_planes[size_t(i)] = frames[i]->lv[0].I;
+      rect_planes[size_t(n) + i] = frames[i]->lv[0].Z;
+    }
+    const size_t row = size_t(cam->w[0]) * 4;
+    rectified = IngestSource{rect_planes.data(), DVO_HIP_PIXEL_F32, row, rect_planes.data() + n, 1.0f, DVO_HIP_DEPTH_F32, row};
+    src = &rectified;
+  }
   std::vector<FrameBuildPtrs> host(n);
   bool wide = cam->w[0] % 4 == 0;
   const bool from_raw = src != nullptr;
@@ -386,7 +430,7 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
       host[i].depth_f32 = static_cast<const float*>(src->depth[i]);
       host[i].depth_pitch = int(src->depth_pitch);
       if (role < 0 || (role == 1 && keep_raw_copy)) {
-        host[i].keep_planes = 1;
+        host[i].keep_planes = lens ? 0 : 1;                    // (rectified planes already lie where the copy goes: nothing is written twice)
         f->raw0 = false;
       }
       wide = wide && f32_strips_aligned(host[i].depth_f32, src->depth_pitch) &&
@@ -444,6 +488,7 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
     if (strips) ctx->strip_ingests += n;
     if (colour) ctx->colour_ingests += n;
     if (depth_f32) ctx->f32_ingests += n;
+    if (lens) ctx->lens_ingests += n;
   }
   for (int l = built; l < levels; ++l) launch_pyr_down(bs, tbl, n, l, cam->w[l - 1], cam->h[l - 1]);
   DVO_HIP_TRY(ctx, hipGetLastError());

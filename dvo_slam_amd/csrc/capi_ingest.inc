@@ -24,6 +24,9 @@ static int check_source(dvo_hip_context* ctx, const char* who, int n, dvo_hip_fr
   for (int i = 0; i < n; ++i) {
     if (frames && (!frames[i] || frames[i]->cam != frames[0]->cam || frames[i]->levels != frames[0]->levels))
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "frames of one build batch must share camera and levels");
+    // (one rectify launch per ingest, one lens per launch: rectify_frames)
+    if (frames && (frames[i]->lens_on != frames[0]->lens_on || std::memcmp(&frames[i]->lens, &frames[0]->lens, sizeof(dvo_hip_lens)) != 0))
+      return fail(ctx, DVO_HIP_ERR_INVALID, who, "frames of one ingest must carry the same lens, or none (dvo_hip_frames_set_lens)");
     if (!src->planes[i] || !src->depth[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null entry");
     if ((image_f32 && !aligned_to(src->planes[i], 4)) || (depth_f32 && !aligned_to(src->depth[i], 4)))
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "a float plane must be 4-byte aligned");
@@ -39,6 +42,20 @@ static int check_source(dvo_hip_context* ctx, const char* who, int n, dvo_hip_fr
     if (src->depth_pitch > size_t(INT_MAX)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "depth pitch above 2^31 - 1");
     if (src->depth_pitch % 4 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a float plane's pitch must be a multiple of 4");
     if (src->depth_pitch == 0) src->depth_pitch = tight_z;
+  }
+  // A frame with a lens is rectified INTO its own float planes of level 0 (rectify_frames) while the pass gathers taps from the caller's
+  // planes: a source that lies in those planes -- the in-place float ingest of a lens-less frame -- would be read while it is overwritten.
+  if (frames && frames[0]->lens_on) {
+    const size_t h = size_t(frames[0]->lv[0].h), own = size_t(width) * h * 4;
+    const size_t image_bytes = src->pitch * h, depth_bytes = (depth_f32 ? src->depth_pitch : size_t(width) * 2) * h;
+    auto overlaps = [](const void* a, size_t na, const void* b, size_t nb) {
+      const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+      return x < y + nb && y < x + na;
+    };
+    for (int i = 0; i < n; ++i)
+      for (const void* mine : {static_cast<const void*>(frames[i]->lv[0].I), static_cast<const void*>(frames[i]->lv[0].Z)})
+        if (overlaps(src->planes[i], image_bytes, mine, own) || overlaps(src->depth[i], depth_bytes, mine, own))
+          return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a lens cannot be ingested from its own level-0 planes");
   }
   return DVO_HIP_OK;
 }

@@ -34,6 +34,7 @@ int dvo_hip_get_counter(dvo_hip_context* ctx, const char* key, long long* value)
   else if (std::strcmp(key, "strip_ingests") == 0) *value = ctx->strip_ingests;
   else if (std::strcmp(key, "colour_ingests") == 0) *value = ctx->colour_ingests;
   else if (std::strcmp(key, "f32_ingests") == 0) *value = ctx->f32_ingests;
+  else if (std::strcmp(key, "lens_ingests") == 0) *value = ctx->lens_ingests;
   else if (std::strcmp(key, "warmup_wait_us") == 0) *value = ctx->warmup_wait_us;
   else if (std::strcmp(key, "rendezvous_pairs") == 0) {
     std::lock_guard<std::mutex> lock(ctx->rendezvous_mutex);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "hd_compat.h"
+#include "lens.h"
 
 #include "../../include/dvo_hip.h"
 
@@ -151,6 +152,24 @@ struct FrameBuildPtrs {                // one frame of a batched pyramid build
 };
 
 constexpr int kChF32 = 32;             // CH of the ingest kernels for a float image plane (3 / 4: bytes per colour pixel, 0: grey)
+
+// one frame of the rectify pass (k_rectify, rectify.hip; include/dvo_hip.h, dvo_hip_frames_set_lens): the caller's raw planes and the
+// frame's own float planes of level 0 that receive the rectified image and depth
+struct RectifyPtrs {
+  const void* image;                   // grey8, a colour format or float, rows of RectifyArgs::image_pitch bytes
+  const void* depth;                   // u16 (tight) or float, rows of RectifyArgs::depth_pitch bytes
+  float* I;
+  float* Z;
+};
+// ... and what the frames of one launch share: the lens over their camera, the plane geometry and the depth conversion
+struct RectifyArgs {
+  LensMap map;                         // lens.h
+  int w, h;
+  int image_pitch, depth_pitch;        // bytes
+  int red_first;                       // a colour format whose first byte is red (colour.h)
+  int rectify_depth;                   // 0: the depth plane is taken pixel for pixel
+  float depth_scale;
+};
 
 // one frame of the caller-selection apply pass (k_apply_selection; include/dvo_hip.h, dvo_hip_frames_set_selection; rule: selection.h)
 struct SelectionApply {

@@ -61,6 +61,12 @@ void launch_apply_selection(hipStream_t s, const SelectionApply* tbl, int n_fram
 void launch_pack_accepted(hipStream_t s, const float4* A, const uint8_t* accepted, int n, float2* R, int* count);
 void launch_unpack_plane(hipStream_t s, const float4* A, const float2* B, int n, int plane, float* out);
 
+// rectify.hip: the raw planes of n frames through one lens into their float planes I / Z of level 0 (lens.h).  channels: 0 = grey8, 3 / 4 =
+// a colour plane with that many bytes per pixel, kChF32 = a float image; depth_f32: float depth planes, else u16.  stream_nt: raw planes
+// read and float planes written with the non-temporal policy (option "stream_policy")
+void launch_rectify(hipStream_t s, const RectifyPtrs* tbl, int n_frames, const RectifyArgs& a, int channels, bool depth_f32, int max_workgroups,
+                    bool stream_nt);
+
 // align_kernels.hip / align_mfma.hip
 // variant 5 (default): Gram accumulation on the matrix cores (align_mfma.hip); variant 0: the all-VALU schedule with the DPP + LDS
 // two-stage reduction (align_kernels.hip).  Same outputs.

@@ -227,6 +227,9 @@ class RgbdImagePyramid:
         self.levels = num_levels
         if sel is not None:                                  # (a new frame: the selection is handed over again, from the host copy)
             set_selection_batch([self], *sel)
+        lens = getattr(self, "_lens", None)
+        if lens is not None:                                 # (... and so is the lens)
+            set_lens_batch([self], *lens)
 
     def set_selection(self, mask=None, min_depth=0.0, max_depth=float("inf"), pitch=0):
         """Caller selection of this frame's reference points (an extension over the reference API; include/dvo_hip.h,
@@ -239,6 +242,16 @@ class RgbdImagePyramid:
     def clear_selection(self):
         self._selection = None
         self.ctx.check(self.ctx._lib.dvo_hip_frames_clear_selection(self.ctx.ptr, 1, (C.c_void_p * 1)(self.ptr)))
+
+    def set_lens(self, K_raw, D, rectify_depth=True):
+        """Lens of this frame's camera (an extension over the reference API, whose nodes sit behind a CPU rectifier; include/dvo_hip.h,
+        dvo_hip_frames_set_lens): K_raw = (fx, fy, ox, oy) of the raw image, D = 4, 5 or 8 OpenCV coefficients k1 k2 p1 p2 [k3 [k4 k5
+        k6]].  Every later update_* of this pyramid takes its planes as raw camera planes and rectifies them on the device first.  Kept
+        across re-ingests until replaced or cleared.  rectify_depth=False: the depth plane is taken pixel for pixel."""
+        set_lens_batch([self], K_raw, D, rectify_depth)
+
+    def clear_lens(self):
+        clear_lens_batch([self])
 
     compute = build                         # deprecated alias in the reference too
 
@@ -487,6 +500,57 @@ def clear_selection_batch(pyramids):
     for p in pyramids:
         p._selection = None
     ctx.check(ctx._lib.dvo_hip_frames_clear_selection(ctx.ptr, len(pyramids), _handles(pyramids)))
+
+
+def lens_struct(K_raw, D, rectify_depth=True):
+    """dvo_hip_lens from K_raw (4 finite floats, fx and fy positive) and D (4, 5 or 8 finite floats, padded with zeros); raises before
+    anything reaches the library."""
+    for name, a in (("K_raw", K_raw), ("D", D)):
+        if a is None or (isinstance(a, np.ndarray) and a.dtype.kind not in "fiu"):
+            raise TypeError("set_lens: %s must be real numbers" % name)
+    try:
+        k = np.asarray(K_raw, np.float64)
+        d = np.asarray(D, np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("set_lens: K_raw and D must be sequences of real numbers")
+    if k.shape != (4,):
+        raise ValueError("set_lens: K_raw is (fx, fy, ox, oy)")
+    if d.ndim != 1 or d.shape[0] not in (4, 5, 8):
+        raise ValueError("set_lens: D has 4, 5 or 8 coefficients (k1 k2 p1 p2 [k3 [k4 k5 k6]])")
+    with np.errstate(over="ignore"):
+        k32, d32 = k.astype(np.float32), d.astype(np.float32)
+    if not (np.isfinite(k32).all() and np.isfinite(d32).all()):
+        raise ValueError("set_lens: K_raw and D must be finite")
+    if not (k32[0] > 0 and k32[1] > 0):
+        raise ValueError("set_lens: fx_raw and fy_raw must be positive")
+    if not isinstance(rectify_depth, (bool, int, np.bool_, np.integer)):
+        raise TypeError("set_lens: rectify_depth is a bool")
+    lens = _lib.Lens()
+    lens.K_raw[:] = [float(v) for v in k32]
+    lens.D[:] = [float(v) for v in d32] + [0.0] * (8 - d32.shape[0])
+    lens.rectify_depth = 1 if rectify_depth else 0
+    lens.reserved = 0
+    return lens
+
+
+def set_lens_batch(pyramids, K_raw, D, rectify_depth=True):
+    """RgbdImagePyramid.set_lens for n pyramids of one context in one call (they then carry equal lenses, as one ingest call wants)."""
+    lens = lens_struct(K_raw, D, rectify_depth)
+    if len(pyramids) < 1:
+        raise ValueError("set_lens_batch: no pyramids")
+    ctx = pyramids[0].ctx
+    ctx.check(ctx._lib.dvo_hip_frames_set_lens(ctx.ptr, len(pyramids), _handles(pyramids), C.byref(lens)))
+    for p in pyramids:
+        p._lens = (list(lens.K_raw), list(lens.D), bool(lens.rectify_depth))   # (kept for a frame that is built again with more levels)
+
+
+def clear_lens_batch(pyramids):
+    if len(pyramids) < 1:
+        raise ValueError("clear_lens_batch: no pyramids")
+    ctx = pyramids[0].ctx
+    ctx.check(ctx._lib.dvo_hip_frames_clear_lens(ctx.ptr, len(pyramids), _handles(pyramids)))
+    for p in pyramids:
+        p._lens = None
 
 
 def set_level_selection(pyramid, level, accepted):

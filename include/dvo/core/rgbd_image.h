@@ -318,12 +318,13 @@ class RgbdImagePyramid {
     for (size_t l = 0; l < levels_.size(); ++l) {
       RgbdImage& image = *levels_[l];
       unsigned had = 0u;
-      if (l > 0 && !dvo::compat::image_empty(image.intensity)) had |= RgbdImage::MirrorPlanes;
+      if ((l > 0 || has_lens_) && !dvo::compat::image_empty(image.intensity)) had |= RgbdImage::MirrorPlanes;
       if (!dvo::compat::image_empty(image.intensity_dx)) had |= RgbdImage::MirrorDerivatives;
       if (image.pointcloud.cols() > 0) had |= RgbdImage::MirrorPointCloud;
       if (image.acceleration.rows > 0) had |= RgbdImage::MirrorAcceleration;
-      image.intensity = l == 0 ? intensity_ : dvo::compat::ImageMat();
-      image.depth = l == 0 ? depth_ : dvo::compat::ImageMat();
+      // (with a lens the matrices are RAW camera planes: level 0 is what the device rectified, mirrored like every other level)
+      image.intensity = l == 0 && !has_lens_ ? intensity_ : dvo::compat::ImageMat();
+      image.depth = l == 0 && !has_lens_ ? depth_ : dvo::compat::ImageMat();
       image.intensity_dx = image.intensity_dy = image.depth_dx = image.depth_dy = dvo::compat::ImageMat();
       image.pointcloud = RgbdImage::PointCloud();
       image.acceleration = dvo::compat::AccelerationMat();
@@ -358,6 +359,32 @@ class RgbdImagePyramid {
     dvo_hip_frame* one[1] = {device_frame()};
     dvo_hip_check(ctx_, dvo_hip_frames_clear_selection(ctx_, 1, one), "dvo_hip_frames_clear_selection");
   }
+  // ---- extension over the reference API: the lens of this frame's camera (include/dvo_hip.h, dvo_hip_frames_set_lens; the reference's
+  // nodes sit behind a CPU rectifier, dvo_ros/src/camera_base.cpp:30-31).  K_raw = fx fy ox oy of the raw image, D = k1 k2 p1 p2 k3 k4
+  // k5 k6 (OpenCV / ROS plumb_bob, rational_polynomial; zeros switch terms off).  Every later update() takes its matrices as raw camera
+  // planes and rectifies them on the device first; the matrices the pyramid was created from were ingested as they are.  Kept until
+  // replaced or cleared.  rectify_depth false: the depth matrix is taken pixel for pixel.  Returns false where the engine refuses the lens.
+  // Host mirrors: update() under a lens does NOT rebind level(0).intensity / depth to the caller's matrices (they are raw camera planes,
+  // not the frame's pixels).  With host mirrors on, level 0 is downloaded like every other level that held a mirror; with host mirrors
+  // off, level(0).intensity / depth are EMPTY matrices after such an update -- ask for them with syncHostMirrors -- and they stay so after
+  // clearLens() until the next update() binds the caller's matrices again.
+  bool setLens(const float K_raw[4], const float D[8], bool rectify_depth = true) {
+    dvo_hip_lens lens;
+    std::memcpy(lens.K_raw, K_raw, sizeof lens.K_raw);
+    std::memcpy(lens.D, D, sizeof lens.D);
+    lens.rectify_depth = rectify_depth ? 1 : 0;
+    lens.reserved = 0;
+    dvo_hip_frame* one[1] = {device_frame()};
+    if (!dvo_hip_check(ctx_, dvo_hip_frames_set_lens(ctx_, 1, one, &lens), "dvo_hip_frames_set_lens")) return false;
+    has_lens_ = true;
+    return true;
+  }
+  void clearLens() {
+    dvo_hip_frame* one[1] = {device_frame()};
+    dvo_hip_check(ctx_, dvo_hip_frames_clear_lens(ctx_, 1, one), "dvo_hip_frames_clear_lens");
+    has_lens_ = false;
+  }
+  bool hasLens() const { return has_lens_; }
   // the caller selection's verdict on a point of level `level` (host side: PointSelection with a caller-defined predicate)
   bool selectionKeeps(size_t level, size_t x, size_t y, float z) const {
     if (has_selection_mask_ && selection_mask_[(y << level) * size_t(camera_.level(0).width()) + (x << level)] == 0) return false;
@@ -397,6 +424,7 @@ class RgbdImagePyramid {
   double timestamp_;
   std::vector<uint8_t> selection_mask_;
   bool has_selection_mask_ = false;
+  bool has_lens_ = false;
   float selection_min_ = 0.0f, selection_max_ = INFINITY;
   unsigned explicit_levels_ = 0u;
 };

@@ -333,6 +333,58 @@ int dvo_hip_frames_clear_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_f
  * the Q3 edit then drops the last selected pixel of FINITE depth where the reference may drop a NaN-depth point. */
 int dvo_hip_frame_set_level_selection(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, const uint8_t* accepted);
 
+/* ---- lens distortion: raw camera frames, rectified on the device at ingest (an extension: the reference's nodes subscribe to
+ * image_rect topics, dvo_ros/src/camera_base.cpp:30-31, behind a CPU image_proc stage) -------------------------------------------
+ * A frame can carry a LENS: the intrinsics K_raw = {fx, fy, ox, oy} of the raw camera image and the coefficients
+ * D = {k1, k2, p1, p2, k3, k4, k5, k6} of OpenCV's / ROS' "plumb_bob" (k4 = k5 = k6 = 0) or "rational_polynomial" model; zeros switch
+ * terms off.  Every later dvo_hip_frames_update_* / dvo_hip_frame_update_* of such a frame takes its planes as RAW camera planes and
+ * rectifies them first, before anything else happens to them: the rectified pixel (u, v) of the frame -- whose own K stays the pinhole
+ * model every alignment uses -- is looked up at
+ *   x = (u - ox) / fx,  y = (v - oy) / fy,  r2 = x x + y y,  radial = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3)
+ *   sx = fx_raw (x radial + 2 p1 x y + p2 (r2 + 2 x^2)) + ox_raw,   sy = fy_raw (y radial + p1 (r2 + 2 y^2) + 2 p2 x y) + oy_raw
+ * (closed form, float32, operation order fixed in dvo_slam_amd/csrc/lens.h; D = 0 with K_raw = K maps every pixel exactly onto itself).
+ * The pixel is valid iff 0 <= sx <= w - 1 and 0 <= sy <= h - 1.  A valid pixel's intensity is the float bilinear blend of the four
+ * source taps (an 8-bit colour tap converted to grey first, the result NOT rounded back to 8 bits: a float intensity taken as is,
+ * like DVO_HIP_PIXEL_F32); its depth is the converted depth (u16: 0 -> NaN, else value * depth_scale; float: value * depth_scale) of the
+ * NEAREST source pixel (int(sx + 0.5), int(sy + 0.5)) -- never a blend, so that no surface is invented across a depth edge -- or, with
+ * rectify_depth = 0, of pixel (u, v) itself (depth that is rendered, or rectified already).  An invalid pixel has I = 0 and Z = NaN
+ * (also with rectify_depth = 0): it is selected by no reference and matched by no current frame.
+ *   ownership    the lens belongs to the FRAME, like the caller selection: it persists across re-ingests until it is replaced or
+ *                cleared, and it is no part of the frame's camera -- frames with and without a lens, and with different lenses, align
+ *                with each other in one dvo_hip_match_batch as long as they share K.
+ *   scope        every dvo_hip_frames_update_* / dvo_hip_frame_update_* entry point, every format, host or device planes, role-aware or
+ *                plain, DVO_HIP_INGEST_DEFER and DVO_HIP_INGEST_NO_RAW_COPY included.  dvo_hip_frame_create_* ingests its planes as
+ *                they are: there is no frame yet that could carry a lens (create, set the lens, update).
+ *   pending      setting or clearing a lens first carries out every recorded ingest (DVO_HIP_INGEST_DEFER), so a recorded ingest runs
+ *                with the lens its frames carried when it was recorded.
+ *   batches      the frames of ONE ingest call carry bytewise equal lenses (rectify_depth compared as 0 / 1, reserved ignored), or none:
+ *                anything else is DVO_HIP_ERR_INVALID and leaves every frame as it was.  So does setting a NULL lens, a non-finite
+ *                value, or fx_raw <= 0 or fy_raw <= 0.
+ *   aliasing     the pass writes the frame's own float planes of level 0 while it gathers taps from the caller's planes, so a frame that
+ *                carries a lens cannot be ingested from planes that overlap its own level-0 planes I / Z (the in-place float ingest of
+ *                a lens-less frame): DVO_HIP_ERR_INVALID, every frame left as it was.  Planes that overlap ANOTHER frame's level-0 planes
+ *                of the same call are not checked and must not be passed.
+ *   raw copy     after a lens ingest the frame is in the state of a frame WITHOUT a lens that was fed the rectified float pair through
+ *                dvo_hip_frames_update_f32* with depth_scale 1, bit for bit: its raw copy is the rectified float planes I / Z of
+ *                level 0, and a later role, other thresholds, dvo_hip_frame_select, dvo_hip_frames_prepare,
+ *                dvo_hip_frame_download_plane, DVO_HIP_INGEST_NO_RAW_COPY and the caller selection work as there.  The selection mask
+ *                is in rectified coordinates.
+ *   counters     "lens_ingests" counts the frames rectified.  The ingest behind the pass is a float ingest and is counted as one:
+ *                "f32_ingests" counts such a frame (whatever its source formats), "strip_ingests" counts it where the strip kernel
+ *                takes float planes (even widths), "colour_ingests" does not count it.
+ *   cost         one pass (k_rectify, rectify.hip) at the head of the ingest, on the build stream: the map is computed per pixel in
+ *                registers (no table), the pass reads the caller's planes and writes 8 B per pixel into the frame's own level-0 planes,
+ *                which the float ingest then reads in place; no staging memory.  Frames without a lens take the path they always
+ *                took: nothing is launched or allocated for them (profiles/lens_ingest.md). */
+typedef struct {
+  float K_raw[4];        /* fx, fy, ox, oy of the raw camera image */
+  float D[8];            /* k1 k2 p1 p2 k3 k4 k5 k6 */
+  int32_t rectify_depth; /* 0: only the image plane is rectified, the depth plane is taken pixel for pixel */
+  int32_t reserved;      /* 0 */
+} dvo_hip_lens;
+int dvo_hip_frames_set_lens(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const dvo_hip_lens* lens);
+int dvo_hip_frames_clear_lens(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames);
+
 /* ---- the hot path --------------------------------------------------------------------------- */
 /* DenseTracker::match(RgbdImagePyramid& reference, RgbdImagePyramid& current, Result&)
  * (dvo_core/src/dense_tracking.cpp:123-376).  `levels`/`iters` may be NULL (no statistics).
@@ -561,6 +613,7 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value);
  * "colour_ingests" (frames ingested from an 8-bit colour plane, dvo_hip_frame_create_colour* / dvo_hip_frames_update_colour*),
  * "f32_ingests" (frames ingested from a float depth plane, dvo_hip_frame_create_f32_device / dvo_hip_frames_update_f32* /
  * dvo_hip_frames_update_colour_f32depth*; "strip_ingests" counts those of them that took the strip kernel),
+ * "lens_ingests" (frames rectified at ingest because they carry a lens, dvo_hip_frames_set_lens; each is also one of "f32_ingests"),
  * "warmup_wait_us" (the longest of the nine stream waits dvo_hip_context_create makes on trivial commands to warm up the runtime's wait
  * path, in microseconds: the first GPU process on a fresh box has been seen to spend 14-24 ms in its first wait),
  * "host_batches" and "host_ns_prepare" / "host_ns_enqueue" / "host_ns_wait" / "host_ns_finish" (nanoseconds the calling thread spent
