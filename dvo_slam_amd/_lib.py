@@ -62,12 +62,17 @@ class Lens(C.Structure):
     _fields_ = [("K_raw", C.c_float * 4), ("D", C.c_float * 8), ("rectify_depth", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DepthRig(C.Structure):
+    """dvo_hip_depth_rig: K_depth = fx fy ox oy of the depth sensor's image, T = row-major 3 x 4 [R | t], depth sensor -> colour camera."""
+    _fields_ = [("K_depth", C.c_float * 4), ("T", C.c_float * 12), ("reserved", C.c_int32 * 2)]
+
+
 # every symbol include/dvo_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "dvo_hip_context_create", "dvo_hip_context_destroy", "dvo_hip_last_error", "dvo_hip_context_stream",
     "dvo_hip_device_count", "dvo_hip_frame_create_f32", "dvo_hip_frame_create_raw", "dvo_hip_frame_create_raw_device",
     "dvo_hip_frame_update_raw_device", "dvo_hip_frames_update_raw_device", "dvo_hip_frames_update_raw", "dvo_hip_frames_update_raw_device_as", "dvo_hip_frames_update_raw_as", "dvo_hip_upload_wait",
-    "dvo_hip_host_alloc", "dvo_hip_host_free", "dvo_hip_frames_prepare", "dvo_hip_frame_destroy", "dvo_hip_frame_info", "dvo_hip_frame_download_plane", "dvo_hip_frame_select",
+    "dvo_hip_host_alloc", "dvo_hip_host_free", "dvo_hip_frames_prepare", "dvo_hip_frame_destroy", "dvo_hip_frame_info", "dvo_hip_frame_device_planes", "dvo_hip_frame_download_plane", "dvo_hip_frame_select",
     "dvo_hip_match", "dvo_hip_match_batch", "dvo_hip_level_iteration", "dvo_hip_time_residual_kernel", "dvo_hip_time_stream_mix",
     "dvo_hip_set_option", "dvo_hip_get_counter", "dvo_hip_version",
     "dvo_hip_frames_update_raw_device_as_ex", "dvo_hip_frames_update_raw_as_ex", "dvo_hip_flush_deferred", "dvo_hip_context_device",
@@ -78,6 +83,7 @@ EXPORTS = [
     "dvo_hip_frame_create_f32_device", "dvo_hip_frames_update_f32_device_as_ex", "dvo_hip_frames_update_f32_as_ex",
     "dvo_hip_frames_update_colour_f32depth_device_as_ex", "dvo_hip_frames_update_colour_f32depth_as_ex",
     "dvo_hip_frames_set_lens", "dvo_hip_frames_clear_lens",
+    "dvo_hip_frames_set_depth_rig", "dvo_hip_frames_clear_depth_rig",
 ]
 
 ROLE_CURRENT, ROLE_REFERENCE = 0, 1
@@ -142,6 +148,8 @@ def lib():
     L.dvo_hip_frame_destroy.argtypes = [vp, vp]
     L.dvo_hip_frame_destroy.restype = None
     L.dvo_hip_frame_info.argtypes = [vp, C.c_int, ip, ip, fp]
+    if hasattr(L, "dvo_hip_frame_device_planes"):
+        L.dvo_hip_frame_device_planes.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp)]
     L.dvo_hip_frame_download_plane.argtypes = [vp, vp, C.c_int, C.c_int, fp]
     L.dvo_hip_frame_select.argtypes = [vp, vp, C.c_int, C.c_float, C.c_float, ip, C.POINTER(C.c_uint8)]
     L.dvo_hip_match.argtypes = [vp, vp, vp, C.POINTER(Config), C.POINTER(Result), C.POINTER(LevelStats), C.c_int,
@@ -180,6 +188,9 @@ def lib():
     if hasattr(L, "dvo_hip_frames_set_lens"):   # (DVO_HIP_LIBRARY may name an older build for an A/B: it has no lens, a call raises AttributeError)
         L.dvo_hip_frames_set_lens.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(Lens)]
         L.dvo_hip_frames_clear_lens.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    if hasattr(L, "dvo_hip_frames_set_depth_rig"):   # (likewise: an older build has no depth rig)
+        L.dvo_hip_frames_set_depth_rig.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(DepthRig)]
+        L.dvo_hip_frames_clear_depth_rig.argtypes = [vp, C.c_int, C.POINTER(vp)]
     L.dvo_hip_context_device.argtypes = [vp]
     L.dvo_hip_comm_get_unique_id.argtypes = [vp]
     L.dvo_hip_comm_create.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]

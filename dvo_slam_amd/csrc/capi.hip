@@ -138,6 +138,10 @@ struct dvo_hip_frame {
   // float planes of level 0 first (rectify_frames).  The frame's, not the camera's: CameraGeom describes the rectified image.
   bool lens_on = false;
   dvo_hip_lens lens = {};
+  // The depth rig of the frame's sensors (dvo_hip_frames_set_depth_rig, depth_rig.h): every later ingest takes its depth plane as the depth
+  // sensor's own image and registers it into the frame's float plane Z of level 0 first (register_frames), ahead of the lens pass.
+  bool rig_on = false;
+  dvo_hip_depth_rig rig = {};
 };
 
 // Small host -> device transfers (pointer tables, initial guesses) go through slots of pinned memory: from a pageable
@@ -384,6 +388,7 @@ struct dvo_hip_context {
   long long colour_ingests = 0;    // frames ingested from an 8-bit colour plane (colour.h), counter "colour_ingests"
   long long f32_ingests = 0;       // frames ingested from a float depth plane (DVO_HIP_DEPTH_F32), counter "f32_ingests"
   long long lens_ingests = 0;      // frames rectified at ingest (dvo_hip_frames_set_lens), counter "lens_ingests"
+  long long depth_registrations = 0;   // frames whose depth was registered at ingest (dvo_hip_frames_set_depth_rig), counter "depth_registrations"
   // Option "defer_ingest": a batched re-ingest (dvo_hip_frames_update_raw_device_as) is only recorded, and carried out by the next
   // dvo_hip_match_batch right behind the first launches of its first level (or by whatever entry point comes first).  A streaming
   // caller re-ingests the next batch and then aligns the current one: enqueueing the ingest first keeps the alignment's stream idle
@@ -498,6 +503,7 @@ struct dvo_hip_context {
   DevBuf sel_tbl_main, sel_tbl_build;                 // tables of the caller-selection apply pass, one per stream (apply_selection)
   unsigned long long sel_visits = 0;
   DevBuf lens_tbl;                                    // table of the rectify pass (rectify_frames; allocated by the first lens ingest)
+  DevBuf rig_tbl;                                     // table of the register pass (register_frames; allocated by the first rig ingest)
   static const int kTableSlots = 4;
   DevBuf build_tbl[kTableSlots];   // (a few, picked by the list's first frame: see Workspace::pair_ptrs)
   DevBuf* build_tbl_cur = nullptr; // the one that holds the table of build_tbl_frames
@@ -843,7 +849,7 @@ void dvo_hip_context_destroy(dvo_hip_context* ctx) {
   if (ctx->build_stream) (void)hipStreamDestroy(ctx->build_stream);
   for (DevBuf& b : ctx->build_tbl) b.release();
   for (DevBuf* b : {&ctx->misc, &ctx->role_tbl_cur, &ctx->role_tbl_ref, &ctx->prep_tbl_cur, &ctx->prep_tbl_ref, &ctx->rcp_table, &ctx->ref_order_planes,
-                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl}) b->release();
+                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl, &ctx->rig_tbl}) b->release();
   for (DevBuf& b : ctx->upload_buf) b.release();
   for (const dvo_hip_context::PooledBlock& b : ctx->frame_pool) (void)hipFree(b.p);
   ctx->frame_pool.clear();
@@ -973,6 +979,13 @@ int dvo_hip_frame_info(const dvo_hip_frame* frame, int level, int* width, int* h
   return DVO_HIP_OK;
 }
 
+int dvo_hip_frame_device_planes(const dvo_hip_frame* frame, int level, void** intensity_dev, void** depth_dev) {
+  if (!frame || level < 0 || level >= frame->levels) return DVO_HIP_ERR_INVALID;
+  if (intensity_dev) *intensity_dev = frame->lv[level].I;
+  if (depth_dev) *depth_dev = frame->lv[level].Z;
+  return DVO_HIP_OK;
+}
+
 int dvo_hip_frame_download_plane(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, int plane, float* out) {
   DVO_ENTER(ctx);
   if (!ctx || !frame || !out || level < 0 || level >= frame->levels || plane < 0 || plane > 5)
@@ -1089,6 +1102,10 @@ int dvo_hip_frames_set_lens(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* c
   if (!(lens->K_raw[0] > 0.0f) || !(lens->K_raw[1] > 0.0f)) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_lens: need fx_raw > 0 and fy_raw > 0");
   for (int i = 0; i < n_frames; ++i)
     if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_lens: null frame");
+  // (a depth rig projects into the rectified pinhole K: its output is rectified depth already)
+  for (int i = 0; i < n_frames; ++i)
+    if (frames[i]->rig_on && lens->rectify_depth != 0)
+      return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_lens: a frame that carries a depth rig takes a lens with rectify_depth = 0 only");
   for (int i = 0; i < n_frames; ++i) {
     dvo_hip_frame* f = frames[i];
     f->lens_on = true;
@@ -1108,6 +1125,39 @@ int dvo_hip_frames_clear_lens(dvo_hip_context* ctx, int n_frames, dvo_hip_frame*
   for (int i = 0; i < n_frames; ++i) {
     frames[i]->lens_on = false;
     frames[i]->lens = dvo_hip_lens{};
+  }
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_frames_set_depth_rig(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const dvo_hip_depth_rig* rig) {
+  DVO_ENTER(ctx);                                              // (a recorded ingest of these frames is carried out with the rig it was recorded under)
+  if (!ctx || n_frames < 1 || !frames || !rig) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: bad argument");
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(rig->K_depth[k])) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: K_depth is not finite");
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(rig->T[k])) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: T is not finite");
+  if (!(rig->K_depth[0] > 0.0f) || !(rig->K_depth[1] > 0.0f)) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: need fx_d > 0 and fy_d > 0");
+  if (rig->reserved[0] != 0 || rig->reserved[1] != 0) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: reserved must be 0");
+  for (int i = 0; i < n_frames; ++i)
+    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: null frame");
+  for (int i = 0; i < n_frames; ++i)
+    if (frames[i]->lens_on && frames[i]->lens.rectify_depth != 0)
+      return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: the frame's lens rectifies depth (a rig's output is rectified already: rectify_depth = 0)");
+  for (int i = 0; i < n_frames; ++i) {
+    frames[i]->rig_on = true;
+    frames[i]->rig = *rig;                                     // (rigs are compared bytewise: reserved is 0, there is no padding)
+  }
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_frames_clear_depth_rig(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames) {
+  DVO_ENTER(ctx);
+  if (!ctx || n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_depth_rig: bad argument");
+  for (int i = 0; i < n_frames; ++i)
+    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_depth_rig: null frame");
+  for (int i = 0; i < n_frames; ++i) {
+    frames[i]->rig_on = false;
+    frames[i]->rig = dvo_hip_depth_rig{};
   }
   return DVO_HIP_OK;
 }

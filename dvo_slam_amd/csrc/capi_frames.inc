@@ -368,6 +368,28 @@ int rectify_frames(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, co
   return DVO_HIP_OK;
 }
 
+// The register pass of n frames that carry a depth rig (the same one: check_source), on the build stream: the depth sensor's planes of
+// `src` through the rig into each frame's own float plane Z of level 0, depth conversion included (depth_rig.h, depth_register.hip): a
+// fill with the hole pattern, then the scatter.  What follows in frames_build reads Z where it lies as float depth of scale 1.
+int register_frames(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource& src) {
+  const CameraGeom* cam = frames[0]->cam;
+  const bool depth_f32 = src.depth_format == DVO_HIP_DEPTH_F32;
+  std::vector<DepthRigPtrs> host(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) host[i] = DepthRigPtrs{src.depth[i], frames[i]->lv[0].Z};
+  DepthRigArgs a;
+  a.map = depth_rig_prepare(cam->K0, frames[0]->rig);
+  a.w = cam->w[0];
+  a.h = cam->h[0];
+  a.depth_pitch = depth_f32 ? int(src.depth_pitch) : cam->w[0] * 2;   // (u16 depth planes are tight)
+  a.depth_scale = src.depth_scale;
+  const size_t bytes = host.size() * sizeof(DepthRigPtrs);
+  DVO_HIP_TRY(ctx, ctx->rig_tbl.reserve(bytes));
+  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->build_stream, ctx->rig_tbl.p, host.data(), bytes));
+  launch_depth_register(ctx->build_stream, ctx->rig_tbl.as<DepthRigPtrs>(), n, a, depth_f32, ctx->opt_build_workgroups, ctx->opt_stream_policy != 0);
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  return DVO_HIP_OK;
+}
+
 // src: device planes whose pitch is resolved, of frames that share camera and levels (check_ingest has seen to both).  From a colour
 // source the kernels convert and leave grey in the frames' raw copies.
 int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource* src, int role = -1, float ithr = 0.0f,
@@ -377,6 +399,25 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
   const int levels = frames[0]->levels;
   // Frames that carry a lens: the caller's planes are rectified into the frames' float planes of level 0 (depth scaled there), and the
   // ingest below is the float ingest of THOSE planes, in place -- the frame ends as a lens-less frame fed the rectified pair would.
+  // Frames that carry a depth rig: the depth sensor's plane is registered into the frames' float plane Z of level 0 first (depth scaled
+  // there), and everything below -- the lens pass, the ingest -- takes the caller's image plane in its own format with float depth of
+  // scale 1 read from THAT plane, in place: the frame ends as a rig-less frame fed the image and the registered plane would.  Under a
+  // lens (rectify_depth 0: dvo_hip_frames_set_depth_rig) each lane of k_rectify reads and writes only its own element of Z.
+  // Without a lens the ingest keeps its planes (keep_planes 1) and so stores Z back into the plane it reads, while other waves still
+  // read their halo rows from it.  That is harmless only because the conversion is the identity here -- float depth of scale 1, z * 1.0f,
+  // keeps every bit pattern, a NaN's payload included (kDepthRigHole is a quiet NaN) -- so a halo read sees the same bits before and
+  // after a neighbour's store.  A conversion that changes any bit would need keep_planes 0 for Z, as under a lens.
+  const bool rig = src != nullptr && frames[0]->rig_on;
+  std::vector<const void*> reg_planes;
+  IngestSource registered;
+  if (rig) {
+    const int rc = register_frames(ctx, n, frames, *src);
+    if (rc != DVO_HIP_OK) return rc;
+    reg_planes.resize(size_t(n));
+    for (int i = 0; i < n; ++i) reg_planes[size_t(i)] = frames[i]->lv[0].Z;
+    registered = IngestSource{src->planes, src->format, src->pitch, reg_planes.data(), 1.0f, DVO_HIP_DEPTH_F32, size_t(cam->w[0]) * 4};
+    src = &registered;
+  }
   const bool lens = src != nullptr && frames[0]->lens_on;
   std::vector<const void*> rect_planes;
   IngestSource rectified;
@@ -489,6 +530,7 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
     if (colour) ctx->colour_ingests += n;
     if (depth_f32) ctx->f32_ingests += n;
     if (lens) ctx->lens_ingests += n;
+    if (rig) ctx->depth_registrations += n;
   }
   for (int l = built; l < levels; ++l) launch_pyr_down(bs, tbl, n, l, cam->w[l - 1], cam->h[l - 1]);
   DVO_HIP_TRY(ctx, hipGetLastError());

@@ -27,6 +27,9 @@ static int check_source(dvo_hip_context* ctx, const char* who, int n, dvo_hip_fr
     // (one rectify launch per ingest, one lens per launch: rectify_frames)
     if (frames && (frames[i]->lens_on != frames[0]->lens_on || std::memcmp(&frames[i]->lens, &frames[0]->lens, sizeof(dvo_hip_lens)) != 0))
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "frames of one ingest must carry the same lens, or none (dvo_hip_frames_set_lens)");
+    // (likewise one register pass per ingest, one depth rig per launch: register_frames)
+    if (frames && (frames[i]->rig_on != frames[0]->rig_on || std::memcmp(&frames[i]->rig, &frames[0]->rig, sizeof(dvo_hip_depth_rig)) != 0))
+      return fail(ctx, DVO_HIP_ERR_INVALID, who, "frames of one ingest must carry the same depth rig, or none (dvo_hip_frames_set_depth_rig)");
     if (!src->planes[i] || !src->depth[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null entry");
     if ((image_f32 && !aligned_to(src->planes[i], 4)) || (depth_f32 && !aligned_to(src->depth[i], 4)))
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "a float plane must be 4-byte aligned");
@@ -56,6 +59,18 @@ static int check_source(dvo_hip_context* ctx, const char* who, int n, dvo_hip_fr
       for (const void* mine : {static_cast<const void*>(frames[i]->lv[0].I), static_cast<const void*>(frames[i]->lv[0].Z)})
         if (overlaps(src->planes[i], image_bytes, mine, own) || overlaps(src->depth[i], depth_bytes, mine, own))
           return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a lens cannot be ingested from its own level-0 planes");
+  }
+  // A frame with a depth rig is registered INTO its own float plane Z of level 0 (register_frames), a scatter: a source that lies in
+  // that plane -- depth or image -- would be overwritten by the fill before it is read.
+  if (frames && frames[0]->rig_on) {
+    const size_t h = size_t(frames[0]->lv[0].h), own = size_t(width) * h * 4;
+    const size_t image_bytes = src->pitch * h, depth_bytes = (depth_f32 ? src->depth_pitch : size_t(width) * 2) * h;
+    for (int i = 0; i < n; ++i) {
+      const uintptr_t y = reinterpret_cast<uintptr_t>(frames[i]->lv[0].Z);
+      const uintptr_t x = reinterpret_cast<uintptr_t>(src->depth[i]), c = reinterpret_cast<uintptr_t>(src->planes[i]);
+      if ((x < y + own && y < x + depth_bytes) || (c < y + own && y < c + image_bytes))
+        return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a depth rig cannot be ingested from its own level-0 plane Z");
+    }
   }
   return DVO_HIP_OK;
 }

@@ -35,6 +35,9 @@ int dvo_hip_get_counter(dvo_hip_context* ctx, const char* key, long long* value)
   else if (std::strcmp(key, "colour_ingests") == 0) *value = ctx->colour_ingests;
   else if (std::strcmp(key, "f32_ingests") == 0) *value = ctx->f32_ingests;
   else if (std::strcmp(key, "lens_ingests") == 0) *value = ctx->lens_ingests;
+  // (frames whose depth plane went through a depth rig, register_frames; and the bytes of the pass's pointer table: 0 until the first one)
+  else if (std::strcmp(key, "depth_registrations") == 0) *value = ctx->depth_registrations;
+  else if (std::strcmp(key, "depth_rig_table_bytes") == 0) *value = (long long)ctx->rig_tbl.bytes;
   else if (std::strcmp(key, "warmup_wait_us") == 0) *value = ctx->warmup_wait_us;
   else if (std::strcmp(key, "rendezvous_pairs") == 0) {
     std::lock_guard<std::mutex> lock(ctx->rendezvous_mutex);

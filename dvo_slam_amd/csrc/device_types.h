@@ -5,6 +5,7 @@
 
 #include "hd_compat.h"
 #include "lens.h"
+#include "depth_rig.h"
 
 #include "../../include/dvo_hip.h"
 
@@ -168,6 +169,20 @@ struct RectifyArgs {
   int image_pitch, depth_pitch;        // bytes
   int red_first;                       // a colour format whose first byte is red (colour.h)
   int rectify_depth;                   // 0: the depth plane is taken pixel for pixel
+  float depth_scale;
+};
+
+// one frame of the register pass (k_depth_fill, k_depth_register, depth_register.hip; include/dvo_hip.h, dvo_hip_frames_set_depth_rig): the
+// depth sensor's plane and the frame's own float plane Z of level 0, the z-buffer that receives the registered depth
+struct DepthRigPtrs {
+  const void* depth;                   // u16 (tight) or float, rows of DepthRigArgs::depth_pitch bytes
+  float* Z;
+};
+// ... and what the frames of one launch share: the rig over their camera, the plane geometry and the depth conversion
+struct DepthRigArgs {
+  DepthRigMap map;                     // depth_rig.h
+  int w, h;
+  int depth_pitch;                     // bytes
   float depth_scale;
 };
 

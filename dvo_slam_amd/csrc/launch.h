@@ -67,6 +67,12 @@ void launch_unpack_plane(hipStream_t s, const float4* A, const float2* B, int n,
 void launch_rectify(hipStream_t s, const RectifyPtrs* tbl, int n_frames, const RectifyArgs& a, int channels, bool depth_f32, int max_workgroups,
                     bool stream_nt);
 
+// depth_register.hip: the depth planes of n frames through one depth rig into their float plane Z of level 0 (depth_rig.h): a fill of
+// the z-buffers with the hole pattern, then the forward scatter with an atomic minimum.  depth_f32: float depth planes, else u16.
+// stream_nt: the depth planes are read with the non-temporal policy (option "stream_policy"); the z-buffer is written at the default one
+void launch_depth_register(hipStream_t s, const DepthRigPtrs* tbl, int n_frames, const DepthRigArgs& a, bool depth_f32, int max_workgroups,
+                           bool stream_nt);
+
 // align_kernels.hip / align_mfma.hip
 // variant 5 (default): Gram accumulation on the matrix cores (align_mfma.hip); variant 0: the all-VALU schedule with the DPP + LDS
 // two-stage reduction (align_kernels.hip).  Same outputs.

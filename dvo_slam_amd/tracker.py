@@ -230,6 +230,9 @@ class RgbdImagePyramid:
         lens = getattr(self, "_lens", None)
         if lens is not None:                                 # (... and so is the lens)
             set_lens_batch([self], *lens)
+        rig = getattr(self, "_depth_rig", None)
+        if rig is not None:                                  # (... and the depth rig)
+            set_depth_rig_batch([self], *rig)
 
     def set_selection(self, mask=None, min_depth=0.0, max_depth=float("inf"), pitch=0):
         """Caller selection of this frame's reference points (an extension over the reference API; include/dvo_hip.h,
@@ -252,6 +255,17 @@ class RgbdImagePyramid:
 
     def clear_lens(self):
         clear_lens_batch([self])
+
+    def set_depth_rig(self, K_depth, T):
+        """Depth rig of this frame's sensors (an extension over the reference API, whose nodes sit behind a CPU depth_image_proc/register
+        stage; include/dvo_hip.h, dvo_hip_frames_set_depth_rig): K_depth = (fx, fy, ox, oy) of the depth sensor's image, T = the 3 x 4 or
+        4 x 4 transform [R | t] from depth-sensor to colour-camera coordinates in metres.  Every later update_* of this pyramid takes its
+        depth plane as the depth sensor's own image and registers it into the colour camera on the device first.  Kept across
+        re-ingests until replaced or cleared."""
+        set_depth_rig_batch([self], K_depth, T)
+
+    def clear_depth_rig(self):
+        clear_depth_rig_batch([self])
 
     compute = build                         # deprecated alias in the reference too
 
@@ -551,6 +565,60 @@ def clear_lens_batch(pyramids):
     ctx.check(ctx._lib.dvo_hip_frames_clear_lens(ctx.ptr, len(pyramids), _handles(pyramids)))
     for p in pyramids:
         p._lens = None
+
+
+def depth_rig_struct(K_depth, T):
+    """dvo_hip_depth_rig from K_depth (4 finite floats, fx and fy positive) and T (3 x 4, 4 x 4 with a last row of 0 0 0 1, or 12 finite
+    floats row-major: [R | t], depth sensor -> colour camera, metres); raises before anything reaches the library."""
+    for name, a in (("K_depth", K_depth), ("T", T)):
+        if a is None or (isinstance(a, np.ndarray) and a.dtype.kind not in "fiu"):
+            raise TypeError("set_depth_rig: %s must be real numbers" % name)
+    try:
+        k = np.asarray(K_depth, np.float64)
+        t = np.asarray(T, np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("set_depth_rig: K_depth and T must be sequences of real numbers")
+    if k.shape != (4,):
+        raise ValueError("set_depth_rig: K_depth is (fx, fy, ox, oy)")
+    if t.shape == (4, 4):
+        if not np.array_equal(t[3], [0.0, 0.0, 0.0, 1.0]):
+            raise ValueError("set_depth_rig: the last row of a 4 x 4 T is 0 0 0 1")
+        t = t[:3]
+    if t.shape == (12,):
+        t = t.reshape(3, 4)
+    if t.shape != (3, 4):
+        raise ValueError("set_depth_rig: T is 3 x 4 (or 4 x 4, or 12 values row-major): [R | t]")
+    with np.errstate(over="ignore"):
+        k32, t32 = k.astype(np.float32), t.astype(np.float32)
+    if not (np.isfinite(k32).all() and np.isfinite(t32).all()):
+        raise ValueError("set_depth_rig: K_depth and T must be finite")
+    if not (k32[0] > 0 and k32[1] > 0):
+        raise ValueError("set_depth_rig: fx_d and fy_d must be positive")
+    rig = _lib.DepthRig()
+    rig.K_depth[:] = [float(v) for v in k32]
+    rig.T[:] = [float(v) for v in t32.reshape(-1)]
+    rig.reserved[:] = [0, 0]
+    return rig
+
+
+def set_depth_rig_batch(pyramids, K_depth, T):
+    """RgbdImagePyramid.set_depth_rig for n pyramids of one context in one call (they then carry equal rigs, as one ingest call wants)."""
+    rig = depth_rig_struct(K_depth, T)
+    if len(pyramids) < 1:
+        raise ValueError("set_depth_rig_batch: no pyramids")
+    ctx = pyramids[0].ctx
+    ctx.check(ctx._lib.dvo_hip_frames_set_depth_rig(ctx.ptr, len(pyramids), _handles(pyramids), C.byref(rig)))
+    for p in pyramids:
+        p._depth_rig = (list(rig.K_depth), list(rig.T))      # (kept for a frame that is built again with more levels)
+
+
+def clear_depth_rig_batch(pyramids):
+    if len(pyramids) < 1:
+        raise ValueError("clear_depth_rig_batch: no pyramids")
+    ctx = pyramids[0].ctx
+    ctx.check(ctx._lib.dvo_hip_frames_clear_depth_rig(ctx.ptr, len(pyramids), _handles(pyramids)))
+    for p in pyramids:
+        p._depth_rig = None
 
 
 def set_level_selection(pyramid, level, accepted):

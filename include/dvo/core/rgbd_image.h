@@ -318,13 +318,15 @@ class RgbdImagePyramid {
     for (size_t l = 0; l < levels_.size(); ++l) {
       RgbdImage& image = *levels_[l];
       unsigned had = 0u;
-      if ((l > 0 || has_lens_) && !dvo::compat::image_empty(image.intensity)) had |= RgbdImage::MirrorPlanes;
+      const bool raw_planes = has_lens_ || has_rig_;
+      if ((l > 0 || raw_planes) && !dvo::compat::image_empty(image.intensity)) had |= RgbdImage::MirrorPlanes;
       if (!dvo::compat::image_empty(image.intensity_dx)) had |= RgbdImage::MirrorDerivatives;
       if (image.pointcloud.cols() > 0) had |= RgbdImage::MirrorPointCloud;
       if (image.acceleration.rows > 0) had |= RgbdImage::MirrorAcceleration;
-      // (with a lens the matrices are RAW camera planes: level 0 is what the device rectified, mirrored like every other level)
-      image.intensity = l == 0 && !has_lens_ ? intensity_ : dvo::compat::ImageMat();
-      image.depth = l == 0 && !has_lens_ ? depth_ : dvo::compat::ImageMat();
+      // (with a lens or a depth rig the matrices are RAW sensor planes: level 0 is what the device rectified / registered, mirrored like
+      // every other level)
+      image.intensity = l == 0 && !raw_planes ? intensity_ : dvo::compat::ImageMat();
+      image.depth = l == 0 && !raw_planes ? depth_ : dvo::compat::ImageMat();
       image.intensity_dx = image.intensity_dy = image.depth_dx = image.depth_dy = dvo::compat::ImageMat();
       image.pointcloud = RgbdImage::PointCloud();
       image.acceleration = dvo::compat::AccelerationMat();
@@ -385,6 +387,33 @@ class RgbdImagePyramid {
     has_lens_ = false;
   }
   bool hasLens() const { return has_lens_; }
+  // ---- extension over the reference API: the depth rig of this frame's sensors (include/dvo_hip.h, dvo_hip_frames_set_depth_rig; the
+  // reference's nodes subscribe to depth_registered topics behind a CPU depth_image_proc/register stage, dvo_ros/src/camera_base.cpp:30-33).
+  // depth_K = the intrinsics of the depth sensor's image, colour_from_depth = the rigid transform from depth-sensor to colour-camera
+  // coordinates in metres (Eigen::Affine3f, Eigen::Affine3d or dvo::compat::Affine3d: anything whose matrix()(i, j) reads a 4 x 4).  Every
+  // later update() takes its depth matrix as the depth sensor's own image and registers it on the device first; the matrices the pyramid
+  // was created from were ingested as they are.  Kept until replaced or cleared.  Returns false where the engine refuses the rig (a
+  // non-finite value, a focal length <= 0, a lens that rectifies depth).  Host mirrors: as under a lens, update() under a rig does NOT
+  // rebind level(0).intensity / depth to the caller's matrices (the depth matrix is the depth sensor's image, not the frame's depth):
+  // level 0 is mirrored from the device like every other level, and is empty with host mirrors off until syncHostMirrors asks for it.
+  template <typename Transform>
+  bool setDepthRig(const IntrinsicMatrix& depth_K, const Transform& colour_from_depth) {
+    dvo_hip_depth_rig rig;
+    rig.K_depth[0] = depth_K.fx(); rig.K_depth[1] = depth_K.fy(); rig.K_depth[2] = depth_K.ox(); rig.K_depth[3] = depth_K.oy();
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 4; ++j) rig.T[i * 4 + j] = float(colour_from_depth.matrix()(i, j));
+    rig.reserved[0] = rig.reserved[1] = 0;
+    dvo_hip_frame* one[1] = {device_frame()};
+    if (!dvo_hip_check(ctx_, dvo_hip_frames_set_depth_rig(ctx_, 1, one, &rig), "dvo_hip_frames_set_depth_rig")) return false;
+    has_rig_ = true;
+    return true;
+  }
+  void clearDepthRig() {
+    dvo_hip_frame* one[1] = {device_frame()};
+    dvo_hip_check(ctx_, dvo_hip_frames_clear_depth_rig(ctx_, 1, one), "dvo_hip_frames_clear_depth_rig");
+    has_rig_ = false;
+  }
+  bool hasDepthRig() const { return has_rig_; }
   // the caller selection's verdict on a point of level `level` (host side: PointSelection with a caller-defined predicate)
   bool selectionKeeps(size_t level, size_t x, size_t y, float z) const {
     if (has_selection_mask_ && selection_mask_[(y << level) * size_t(camera_.level(0).width()) + (x << level)] == 0) return false;
@@ -425,6 +454,7 @@ class RgbdImagePyramid {
   std::vector<uint8_t> selection_mask_;
   bool has_selection_mask_ = false;
   bool has_lens_ = false;
+  bool has_rig_ = false;
   float selection_min_ = 0.0f, selection_max_ = INFINITY;
   unsigned explicit_levels_ = 0u;
 };

@@ -288,6 +288,11 @@ void dvo_hip_host_free(dvo_hip_context* ctx, void* p);
 int dvo_hip_frames_prepare(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, int role, const dvo_hip_config* cfg);
 void dvo_hip_frame_destroy(dvo_hip_context* ctx, dvo_hip_frame* frame);
 int dvo_hip_frame_info(const dvo_hip_frame* frame, int level, int* width, int* height, float K[4]);
+/* where the tight float planes I / Z of one level lie in device memory (width * height floats each; either pointer may be NULL): what
+ * the aliasing rules of the float, lens and depth-rig ingests speak of.  They hold the frame's pixels only where the frame keeps its
+ * raw copy in them (a frame built from float planes); the engine writes them on the build stream.  A diagnostic aid for tests and tools
+ * that probe those rules, not a data path: the planes stay the engine's, and their layout may change with it. */
+int dvo_hip_frame_device_planes(const dvo_hip_frame* frame, int level, void** intensity_dev, void** depth_dev);
 /* host mirror of one plane of one level (RgbdImage public fields, rgbd_image.h:161-179):
  * plane 0=intensity 1=depth 2=intensity_dx 3=intensity_dy 4=depth_dx 5=depth_dy */
 int dvo_hip_frame_download_plane(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, int plane, float* out);
@@ -384,6 +389,58 @@ typedef struct {
 } dvo_hip_lens;
 int dvo_hip_frames_set_lens(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const dvo_hip_lens* lens);
 int dvo_hip_frames_clear_lens(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames);
+
+/* ---- depth rig: raw depth from a second sensor, registered into the colour camera on the device at ingest (an extension: the
+ * reference's nodes subscribe to camera/depth_registered/image_rect_raw, dvo_ros/src/camera_base.cpp:30-33, behind a CPU
+ * depth_image_proc/register stage) ----------------------------------------------------------------------------------------------
+ * A frame can carry a DEPTH RIG: the intrinsics K_depth = {fx_d, fy_d, ox_d, oy_d} of the depth sensor's image (same width x height as
+ * the frame) and T = [R | t], the row-major 3 x 4 transform from depth-sensor coordinates to colour-camera coordinates in metres.
+ * Every later dvo_hip_frames_update_* / dvo_hip_frame_update_* of such a frame takes its DEPTH plane as the depth sensor's own image
+ * and registers it first, before anything else happens: for every source pixel (u, v) of converted depth z (u16: 0 -> NaN, else
+ * value * depth_scale; float: value * depth_scale) that is finite and > 0,
+ *   X = (u - ox_d) / fx_d * z,  Y = (v - oy_d) / fy_d * z,  P' = R (X, Y, z) + t;   skipped unless P'.z is finite and > 0
+ *   u' = fx P'.x / P'.z + ox,   v' = fy P'.y / P'.z + oy  (the frame's own K);      skipped unless -0.5 <= u' < w - 0.5, -0.5 <= v' < h - 0.5
+ *   Z[int(floor(v' + 0.5))][int(floor(u' + 0.5))] = min(that element, P'.z)
+ * into a plane that starts as NaN everywhere (float32, operation order fixed in dvo_slam_amd/csrc/depth_rig.h; the result does not
+ * depend on the order of the pixels).  These are the semantics of ROS' depth_image_proc/register WITHOUT hole filling: a nearest-pixel
+ * forward scatter, the nearest surface wins, target pixels that nothing lands on stay holes (NaN).  R is not checked for
+ * orthonormality.  The image plane is taken as it comes.
+ *   ownership    the rig belongs to the FRAME, like the lens and the caller selection: it persists across re-ingests until it is
+ *                replaced or cleared, and it is no part of the frame's camera -- frames with and without a rig align with each other
+ *                in one dvo_hip_match_batch as long as they share K.
+ *   scope        every dvo_hip_frames_update_* / dvo_hip_frame_update_* entry point in the format combinations it accepts today, host
+ *                or device planes, role-aware or plain, DVO_HIP_INGEST_DEFER and DVO_HIP_INGEST_NO_RAW_COPY included.
+ *                dvo_hip_frame_create_* ingests its planes as they are: create, set the rig, then update.
+ *   pending      setting or clearing a rig first carries out every recorded ingest (DVO_HIP_INGEST_DEFER), so a recorded ingest runs
+ *                with the rig its frames carried when it was recorded.
+ *   batches      the frames of ONE ingest call carry bytewise equal rigs, or none: anything else is DVO_HIP_ERR_INVALID and leaves
+ *                every frame as it was.  So does setting a NULL rig, a non-finite value, fx_d <= 0 or fy_d <= 0, or a non-zero reserved.
+ *   lens         registration projects into the frame's rectified pinhole K, so its output is rectified depth already: a frame carries a
+ *                rig and a lens only if the lens has rectify_depth = 0.  Setting a rig on a frame whose lens has rectify_depth != 0, or
+ *                such a lens on a frame with a rig, is DVO_HIP_ERR_INVALID and changes nothing.  The order is: register, then the
+ *                lens pass on the image plane; pixels the lens leaves invalid still end with Z = NaN.
+ *   aliasing     the pass fills and scatters into the frame's own float plane Z of level 0, so a depth plane or an image plane that
+ *                overlaps that plane is DVO_HIP_ERR_INVALID, every frame left as it was.  Planes that overlap ANOTHER frame's level-0 planes of the same call
+ *                are not checked and must not be passed.
+ *   raw copy     after a rig ingest the frame is in the state of a frame WITHOUT a rig that was fed the same image plane and the
+ *                registered plane through the float-depth entry point of that image format (dvo_hip_frames_update_f32* /
+ *                dvo_hip_frames_update_colour_f32depth*, depth_scale 1), bit for bit: its raw copy is its float planes I / Z of level
+ *                0, and a later role, dvo_hip_frame_select, dvo_hip_frame_download_plane, DVO_HIP_INGEST_NO_RAW_COPY and the caller
+ *                selection work as there.
+ *   counters     "depth_registrations" counts the frames registered.  The ingest behind the pass is a float-depth ingest and is
+ *                counted as one: "f32_ingests" counts such a frame, "strip_ingests" and "colour_ingests" count as for that ingest.
+ *   cost         two launches (k_depth_fill, k_depth_register, depth_register.hip) at the head of the ingest, on the build stream, ahead
+ *                of the lens pass: 4 B per pixel filled, 2-4 B read and one 4-byte atomic minimum per valid pixel, no staging memory.
+ *                Device times of the two kernels are NOT MEASURED yet (profiles/depth_registration.md says how to take them).
+ *                Frames without a rig take the path they always took: nothing is launched or allocated for them (DESIGN.md section
+ *                3, profiles/depth_registration.md). */
+typedef struct {
+  float K_depth[4];    /* fx, fy, ox, oy of the depth sensor's image (same width x height as the frame) */
+  float T[12];         /* row-major 3x4 [R | t]: depth-sensor coordinates -> colour-camera coordinates, metres */
+  int32_t reserved[2]; /* 0 */
+} dvo_hip_depth_rig;
+int dvo_hip_frames_set_depth_rig(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const dvo_hip_depth_rig* rig);
+int dvo_hip_frames_clear_depth_rig(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames);
 
 /* ---- the hot path --------------------------------------------------------------------------- */
 /* DenseTracker::match(RgbdImagePyramid& reference, RgbdImagePyramid& current, Result&)
@@ -614,6 +671,9 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value);
  * "f32_ingests" (frames ingested from a float depth plane, dvo_hip_frame_create_f32_device / dvo_hip_frames_update_f32* /
  * dvo_hip_frames_update_colour_f32depth*; "strip_ingests" counts those of them that took the strip kernel),
  * "lens_ingests" (frames rectified at ingest because they carry a lens, dvo_hip_frames_set_lens; each is also one of "f32_ingests"),
+ * "depth_registrations" (frames whose depth plane was registered at ingest because they carry a depth rig,
+ * dvo_hip_frames_set_depth_rig; each is also one of "f32_ingests") and "depth_rig_table_bytes" (the size of that pass's pointer table:
+ * 0 until the first such frame is ingested),
  * "warmup_wait_us" (the longest of the nine stream waits dvo_hip_context_create makes on trivial commands to warm up the runtime's wait
  * path, in microseconds: the first GPU process on a fresh box has been seen to spend 14-24 ms in its first wait),
  * "host_batches" and "host_ns_prepare" / "host_ns_enqueue" / "host_ns_wait" / "host_ns_finish" (nanoseconds the calling thread spent
