@@ -67,6 +67,13 @@ class DepthRig(C.Structure):
     _fields_ = [("K_depth", C.c_float * 4), ("T", C.c_float * 12), ("reserved", C.c_int32 * 2)]
 
 
+class MapStats(C.Structure):
+    """struct dvo_hip_map_stats: the statistics of a keyframe map (dvo_hip_map_stats)."""
+    _fields_ = [("occupied", C.c_uint64), ("points", C.c_uint64), ("dropped", C.c_uint64), ("out_of_range", C.c_uint64),
+                ("unusable", C.c_uint64), ("over_limit", C.c_uint64), ("capacity", C.c_uint64), ("updates", C.c_uint64),
+                ("reserved", C.c_uint64 * 8)]
+
+
 # every symbol include/dvo_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "dvo_hip_context_create", "dvo_hip_context_destroy", "dvo_hip_last_error", "dvo_hip_context_stream",
@@ -84,6 +91,8 @@ EXPORTS = [
     "dvo_hip_frames_update_colour_f32depth_device_as_ex", "dvo_hip_frames_update_colour_f32depth_as_ex",
     "dvo_hip_frames_set_lens", "dvo_hip_frames_clear_lens",
     "dvo_hip_frames_set_depth_rig", "dvo_hip_frames_clear_depth_rig",
+    "dvo_hip_map_create", "dvo_hip_map_destroy", "dvo_hip_map_clear", "dvo_hip_map_insert", "dvo_hip_map_stats", "dvo_hip_map_extract",
+    "dvo_hip_frames_world_points",
 ]
 
 ROLE_CURRENT, ROLE_REFERENCE = 0, 1
@@ -191,6 +200,16 @@ def lib():
     if hasattr(L, "dvo_hip_frames_set_depth_rig"):   # (likewise: an older build has no depth rig)
         L.dvo_hip_frames_set_depth_rig.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(DepthRig)]
         L.dvo_hip_frames_clear_depth_rig.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    if hasattr(L, "dvo_hip_map_create"):   # (likewise: an older build has no keyframe map)
+        dp = C.POINTER(C.c_double)
+        L.dvo_hip_map_create.argtypes = [vp, C.c_float, C.c_size_t, C.POINTER(vp)]
+        L.dvo_hip_map_destroy.argtypes = [vp, vp]
+        L.dvo_hip_map_destroy.restype = None
+        L.dvo_hip_map_clear.argtypes = [vp, vp]
+        L.dvo_hip_map_insert.argtypes = [vp, vp, C.c_int, C.POINTER(vp), dp, C.c_int, C.c_float, C.c_float]
+        L.dvo_hip_map_stats.argtypes = [vp, vp, C.POINTER(MapStats)]
+        L.dvo_hip_map_extract.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
+        L.dvo_hip_frames_world_points.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.c_int, C.c_float, C.c_float, C.POINTER(vp), C.c_int]
     L.dvo_hip_context_device.argtypes = [vp]
     L.dvo_hip_comm_get_unique_id.argtypes = [vp]
     L.dvo_hip_comm_create.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]

@@ -1,0 +1,281 @@
+// capi_map.inc -- the keyframe map behind the C-ABI (include/dvo_hip.h, dvo_hip_map_* and dvo_hip_frames_world_points; semantics:
+// cloud_map.h; kernels: cloud_map.hip).  Every launch runs on the context's main stream, behind the build-stream work that wrote the frames
+// and behind every recorded ingest, as a match does; arguments are checked before anything is launched or changed.  Textually included
+// by capi.hip inside its extern "C" block.
+struct dvo_hip_map {
+  dvo_hip_context* ctx = nullptr;
+  float leaf = 0.0f;
+  size_t capacity = 0;                 // slots, a power of two
+  DevBuf slots, counters;
+  unsigned long long candidates = 0, dropped = 0;   // kMapCntCandidates, kMapCntDropped as last read back (zero after a clear)
+};
+static_assert(sizeof(struct dvo_hip_map_stats) == 128 && offsetof(struct dvo_hip_map_stats, reserved) == 64, "dvo_hip_map_stats: 8 fields and 8 reserved words");
+
+namespace {
+
+MapTable map_table(const dvo_hip_map* map) {
+  MapTable t;
+  t.slots = map->slots.as<MapSlot>();
+  t.counters = map->counters.as<unsigned long long>();
+  t.capacity = map->capacity;
+  t.leaf = map->leaf;
+  return t;
+}
+
+// frames, poses, level and depth range of a keyframe-map call; `who` names the entry point in the error text
+int check_map_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float min_depth,
+                     float max_depth, const char* who) {
+  if (!ctx || n_frames < 1 || !frames || !poses) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  if (!(min_depth <= max_depth)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "need min_depth <= max_depth (no NaN)");
+  long long blocks = 0;
+  for (int i = 0; i < n_frames; ++i) {
+    const dvo_hip_frame* f = frames[i];
+    if (!f) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null frame");
+    if (std::find(ctx->cameras.begin(), ctx->cameras.end(), f->cam) == ctx->cameras.end())
+      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame of another context");
+    if (level < 0 || level >= f->levels) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame does not have that level");
+    blocks += (static_cast<long long>(f->lv[level].w) * f->lv[level].h + 255) / 256;
+  }
+  if (blocks > 0x7fffffffll) return fail(ctx, DVO_HIP_ERR_INVALID, who, "too many pixels for one call");
+  return DVO_HIP_OK;
+}
+
+// The frame table of one launch on the main stream: the {I, Z} pairs of `level` come from plane C where the frame holds it, else from the
+// taps A (built now where missing: what dvo_hip_frame_download_plane reads planes 0 and 1 from).  outs (may be null): MapFrame::out.
+int upload_map_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float* const* outs,
+                      int* total_blocks) {
+  int rc = wait_for_build(ctx, n_frames, frames);
+  if (rc != DVO_HIP_OK) return rc;
+  // the taps of the frames that hold neither flavour at this level, one ensure_roles per camera (it takes frames of one camera)
+  std::vector<dvo_hip_frame*> missing;
+  for (int i = 0; i < n_frames; ++i) {
+    const FrameLevel& L = frames[i]->lv[level];
+    if (!((L.cur_have & kCurC) && L.C) && !(L.cur_have & kCurAB)) missing.push_back(frames[i]);
+  }
+  while (!missing.empty()) {
+    std::vector<dvo_hip_frame*> group, rest;
+    for (dvo_hip_frame* f : missing) (f->cam == missing[0]->cam ? group : rest).push_back(f);
+    rc = ensure_roles(ctx, int(group.size()), group.data(), 0, level, level, 0.0f, 0.0f);
+    if (rc != DVO_HIP_OK) return rc;
+    missing.swap(rest);
+  }
+  std::vector<MapFrame> host(size_t(n_frames) + 1);
+  int blocks = 0;
+  for (int i = 0; i < n_frames; ++i) {
+    const dvo_hip_frame* f = frames[i];
+    const FrameLevel& L = f->lv[level];
+    MapFrame& m = host[size_t(i)];
+    const bool from_c = (L.cur_have & kCurC) && L.C;
+    m.iz = from_c ? reinterpret_cast<const float*>(L.C) : reinterpret_cast<const float*>(L.A);
+    m.stride = from_c ? 2 : 4;
+    m.out = outs ? outs[i] : nullptr;
+    m.pose = map_pose_prepare(poses + size_t(i) * 16);
+    std::memcpy(m.K, f->cam->K[level], sizeof m.K);
+    m.w = L.w;
+    m.h = L.h;
+    m.first_block = blocks;
+    blocks += (L.w * L.h + 255) / 256;
+  }
+  std::memset(&host[size_t(n_frames)], 0, sizeof(MapFrame));
+  host[size_t(n_frames)].first_block = blocks;
+  const size_t bytes = host.size() * sizeof(MapFrame);
+  DVO_HIP_TRY(ctx, ctx->map_tbl.reserve(bytes));
+  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->map_tbl.p, host.data(), bytes));
+  *total_blocks = blocks;
+  return DVO_HIP_OK;
+}
+
+// (only k_map_insert moves the candidates and the dropped points, and every insert ends with this read: the map's copy of them is current)
+int read_map_counters(dvo_hip_context* ctx, dvo_hip_map* map, unsigned long long out[kMapCounters]) {
+  DVO_HIP_TRY(ctx, hipMemcpyAsync(out, map->counters.p, sizeof(unsigned long long) * kMapCounters, hipMemcpyDeviceToHost, ctx->stream));
+  DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  map->candidates = out[kMapCntCandidates];
+  map->dropped = out[kMapCntDropped];
+  return DVO_HIP_OK;
+}
+
+int check_map(dvo_hip_context* ctx, const dvo_hip_map* map, const char* who) {
+  if (!ctx || !map) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  if (map->ctx != ctx) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a map of another context");
+  return DVO_HIP_OK;
+}
+
+}  // namespace
+
+int dvo_hip_map_create(dvo_hip_context* ctx, float leaf, size_t capacity_slots, dvo_hip_map** out) {
+  DVO_LOCK(ctx);
+  if (!ctx || !out) return fail(ctx, DVO_HIP_ERR_INVALID, "map_create: bad argument");
+  *out = nullptr;
+  if (!(leaf > 0.0f && leaf < INFINITY)) return fail(ctx, DVO_HIP_ERR_INVALID, "map_create: the leaf size must be finite and > 0");
+  if (capacity_slots > (size_t(1) << 32)) return fail(ctx, DVO_HIP_ERR_INVALID, "map_create: at most 2^32 slots");
+  size_t capacity = 64;
+  while (capacity < capacity_slots) capacity *= 2;
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  dvo_hip_map* map = new dvo_hip_map();
+  map->ctx = ctx;
+  map->leaf = leaf;
+  map->capacity = capacity;
+  hipError_t e = map->slots.reserve(capacity * sizeof(MapSlot));
+  if (e == hipSuccess) e = map->counters.reserve(sizeof(unsigned long long) * kMapCounters);
+  if (e == hipSuccess) {
+    launch_map_clear(ctx->stream, map_table(map));
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) {
+    map->slots.release();
+    map->counters.release();
+    delete map;
+    ctx->err = std::string("map_create: ") + hipGetErrorString(e);
+    return DVO_HIP_ERR_HIP;
+  }
+  *out = map;
+  return DVO_HIP_OK;
+}
+
+void dvo_hip_map_destroy(dvo_hip_context* ctx, dvo_hip_map* map) {
+  DVO_LOCK(ctx);
+  if (!map) return;
+  if (ctx) {
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+  }
+  map->slots.release();
+  map->counters.release();
+  delete map;
+}
+
+int dvo_hip_map_clear(dvo_hip_context* ctx, dvo_hip_map* map) {
+  DVO_LOCK(ctx);
+  const int rc = check_map(ctx, map, "map_clear");
+  if (rc != DVO_HIP_OK) return rc;
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  launch_map_clear(ctx->stream, map_table(map));
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  map->candidates = map->dropped = 0;
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_map_insert(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level,
+                       float min_depth, float max_depth) {
+  DVO_ENTER(ctx);
+  int rc = check_map(ctx, map, "map_insert");
+  if (rc == DVO_HIP_OK) rc = check_map_frames(ctx, n_frames, frames, poses, level, min_depth, max_depth, "map_insert");
+  if (rc != DVO_HIP_OK) return rc;
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const unsigned long long candidates_before = map->candidates, dropped_before = map->dropped;
+  unsigned long long after[kMapCounters];
+  int blocks = 0;
+  rc = upload_map_frames(ctx, n_frames, frames, poses, level, nullptr, &blocks);
+  if (rc != DVO_HIP_OK) return rc;
+  launch_map_insert(ctx->stream, ctx->map_tbl.as<MapFrame>(), n_frames, blocks, map_table(map), min_depth, max_depth);
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  rc = read_map_counters(ctx, map, after);
+  if (rc != DVO_HIP_OK) return rc;
+  const unsigned long long dropped = after[kMapCntDropped] - dropped_before;
+  ctx->map_inserts += n_frames;
+  ctx->map_points += (long long)(after[kMapCntCandidates] - candidates_before - dropped);
+  ctx->map_dropped += (long long)dropped;
+  if (dropped != 0) return fail(ctx, DVO_HIP_ERR_CAPACITY, "map_insert: the table dropped points (no free slot within the probe bound); the map keeps what it took");
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_map_stats(dvo_hip_context* ctx, dvo_hip_map* map, struct dvo_hip_map_stats* out) {
+  DVO_LOCK(ctx);
+  const int rc0 = check_map(ctx, map, "map_stats");
+  if (rc0 != DVO_HIP_OK) return rc0;
+  if (!out) return fail(ctx, DVO_HIP_ERR_INVALID, "map_stats: bad argument");
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DVO_HIP_TRY(ctx, launch_map_extract(ctx->stream, map_table(map), 0, nullptr, nullptr, nullptr));   // (counts the voxels over the limit)
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  unsigned long long c[kMapCounters];
+  const int rc = read_map_counters(ctx, map, c);
+  if (rc != DVO_HIP_OK) return rc;
+  std::memset(out, 0, sizeof *out);
+  out->occupied = c[kMapCntOccupied];
+  out->points = c[kMapCntCandidates] - c[kMapCntDropped];
+  out->dropped = c[kMapCntDropped];
+  out->out_of_range = c[kMapCntOutOfRange];
+  out->unusable = c[kMapCntUnusable];
+  out->over_limit = c[kMapCntOverLimit];
+  out->capacity = map->capacity;
+  out->updates = c[kMapCntUpdates];
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_map_extract(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_points, float* xyzi, uint32_t* counts_or_null, uint64_t* keys_or_null,
+                        int out_on_device, size_t* n_points) {
+  DVO_LOCK(ctx);
+  const int rc0 = check_map(ctx, map, "map_extract");
+  if (rc0 != DVO_HIP_OK) return rc0;
+  if (!n_points || (max_points > 0 && !xyzi)) return fail(ctx, DVO_HIP_ERR_INVALID, "map_extract: bad argument");
+  if (out_on_device && xyzi && reinterpret_cast<uintptr_t>(xyzi) % 16 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, "map_extract: a device xyzi must be 16-byte aligned");
+  *n_points = 0;
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const MapTable t = map_table(map);
+  unsigned long long c[kMapCounters];
+  // how many there are (and whether a voxel is over the limit), then the records: a host destination is staged for just that many
+  DVO_HIP_TRY(ctx, launch_map_extract(ctx->stream, t, 0, nullptr, nullptr, nullptr));
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  int rc = read_map_counters(ctx, map, c);
+  if (rc != DVO_HIP_OK) return rc;
+  const unsigned long long occupied = c[kMapCntCursor], over = c[kMapCntOverLimit];
+  const size_t take = size_t(occupied < max_points ? occupied : max_points);
+  if (take > 0) {
+    float4* d_xyzi = reinterpret_cast<float4*>(xyzi);
+    uint32_t* d_counts = counts_or_null;
+    unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(keys_or_null);
+    if (!out_on_device) {
+      DVO_HIP_TRY(ctx, ctx->map_stage.reserve(take * 28));
+      d_xyzi = ctx->map_stage.as<float4>();
+      d_keys = keys_or_null ? reinterpret_cast<unsigned long long*>(ctx->map_stage.as<char>() + take * 16) : nullptr;
+      d_counts = counts_or_null ? reinterpret_cast<uint32_t*>(ctx->map_stage.as<char>() + take * 24) : nullptr;
+    }
+    DVO_HIP_TRY(ctx, launch_map_extract(ctx->stream, t, take, d_xyzi, d_counts, d_keys));
+    DVO_HIP_TRY(ctx, hipGetLastError());
+    if (!out_on_device) {
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(xyzi, d_xyzi, take * 16, hipMemcpyDeviceToHost, ctx->stream));
+      if (keys_or_null) DVO_HIP_TRY(ctx, hipMemcpyAsync(keys_or_null, d_keys, take * 8, hipMemcpyDeviceToHost, ctx->stream));
+      if (counts_or_null) DVO_HIP_TRY(ctx, hipMemcpyAsync(counts_or_null, d_counts, take * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  *n_points = take;
+  if (occupied > max_points) return fail(ctx, DVO_HIP_ERR_CAPACITY, "map_extract: max_points is smaller than the number of occupied voxels (dvo_hip_map_stats)");
+  if (over != 0) return fail(ctx, DVO_HIP_ERR_CAPACITY, "map_extract: a voxel holds more than 2^20 points; its sums may have wrapped");
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_frames_world_points(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float min_depth,
+                                float max_depth, float* const* out, int out_on_device) {
+  DVO_ENTER(ctx);
+  int rc = check_map_frames(ctx, n_frames, frames, poses, level, min_depth, max_depth, "frames_world_points");
+  if (rc != DVO_HIP_OK) return rc;
+  if (!out) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_world_points: bad argument");
+  size_t pixels = 0;
+  for (int i = 0; i < n_frames; ++i) {
+    if (!out[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_world_points: null output");
+    if (out_on_device && reinterpret_cast<uintptr_t>(out[i]) % 16 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_world_points: a device output must be 16-byte aligned");
+    pixels += size_t(frames[i]->lv[level].w) * frames[i]->lv[level].h;
+  }
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<float*> staged;
+  if (!out_on_device) {
+    DVO_HIP_TRY(ctx, ctx->map_stage.reserve(pixels * 16));
+    staged.resize(size_t(n_frames));
+    size_t at = 0;
+    for (int i = 0; i < n_frames; ++i) {
+      staged[size_t(i)] = ctx->map_stage.as<float>() + at * 4;
+      at += size_t(frames[i]->lv[level].w) * frames[i]->lv[level].h;
+    }
+  }
+  int blocks = 0;
+  rc = upload_map_frames(ctx, n_frames, frames, poses, level, out_on_device ? out : staged.data(), &blocks);
+  if (rc != DVO_HIP_OK) return rc;
+  launch_world_points(ctx->stream, ctx->map_tbl.as<MapFrame>(), n_frames, blocks, min_depth, max_depth);
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  if (!out_on_device)
+    for (int i = 0; i < n_frames; ++i)
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(out[i], staged[size_t(i)], size_t(frames[i]->lv[level].w) * frames[i]->lv[level].h * 16, hipMemcpyDeviceToHost, ctx->stream));
+  DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return DVO_HIP_OK;
+}

@@ -38,6 +38,10 @@ int dvo_hip_get_counter(dvo_hip_context* ctx, const char* key, long long* value)
   // (frames whose depth plane went through a depth rig, register_frames; and the bytes of the pass's pointer table: 0 until the first one)
   else if (std::strcmp(key, "depth_registrations") == 0) *value = ctx->depth_registrations;
   else if (std::strcmp(key, "depth_rig_table_bytes") == 0) *value = (long long)ctx->rig_tbl.bytes;
+  // (the keyframe map, capi_map.inc: frames inserted, points the maps took, points they dropped)
+  else if (std::strcmp(key, "map_inserts") == 0) *value = ctx->map_inserts;
+  else if (std::strcmp(key, "map_points") == 0) *value = ctx->map_points;
+  else if (std::strcmp(key, "map_dropped") == 0) *value = ctx->map_dropped;
   else if (std::strcmp(key, "warmup_wait_us") == 0) *value = ctx->warmup_wait_us;
   else if (std::strcmp(key, "rendezvous_pairs") == 0) {
     std::lock_guard<std::mutex> lock(ctx->rendezvous_mutex);

@@ -1,0 +1,196 @@
+// cloud_map.hip -- the keyframe map on the device (cloud_map.h; include/dvo_hip.h, dvo_hip_map_* and dvo_hip_frames_world_points): the
+// {I, Z} pairs of one pyramid level of n keyframes under their poses -> the organised world cloud of every frame (k_world_points), or one
+// voxel-grid map of all of them (k_map_insert into an open-addressing table of integer sums, k_map_extract out of it, k_map_clear).
+//
+// Both per-pixel kernels run over frames x pixels in one launch: a lane owns one pixel, a wavefront 64 consecutive pixels in raster order,
+// a workgroup 256; frames of different sizes share the launch, a workgroup finds its frame by bisecting the table's first_block column.
+// k_world_points stores one 16-byte record per lane, coalesced.
+// k_map_insert reads 8 B per pixel.  Neighbouring pixels very often share a voxel, so before anything goes to memory the wavefront folds
+// every run of consecutive lanes that hold the same key into the run's first lane: a segmented suffix sum over the lanes (__shfl_down,
+// six steps, three packed words: a run of at most 64 points keeps every sum below 2^16 resp. 2^18).  Unusable, out-of-range and inactive
+// lanes break a run.  Only a run's first lane probes the table -- a relaxed load of the slot's key, and a 64-bit atomicCAS where it reads
+// empty; a key never changes once set, so a stale read can only send a lane to the CAS, which decides -- and issues the adds: three
+// vector memory atomics whose return value is not used ({n, sx} and {sy, sz} as 64-bit words, si as a 32-bit one; relaxed, agent
+// scope).  The probe loop is a `for` over kMapMaxProbes: it never spins and never waits for another lane; a run that finds no slot is
+// counted as dropped.  All sums are integers, so the table is the same bit for bit with and without the folding, in any order of
+// arrival.  DVO_MAP_COMBINE_RUNS=0 builds the plain one-lane-one-point form (profiles/keyframe_map.md has both).
+// k_map_extract compacts the occupied slots into the caller's arrays, one atomic add of the active-lane count per wavefront on the
+// output cursor, bounded by max_points; the order of the output is unspecified.  No LDS, no barriers, 256-thread workgroups.
+#include "global_ptr.h"
+#include "launch.h"
+#include "cloud_map.h"
+
+#ifndef DVO_MAP_COMBINE_RUNS
+#define DVO_MAP_COMBINE_RUNS 1
+#endif
+
+namespace dvo_hip {
+
+namespace {
+
+typedef unsigned GlobalU32x4 __attribute__((ext_vector_type(4)));
+
+// the frame that owns workgroup b: first_block is strictly increasing (every frame has at least one pixel), tbl[n_frames] ends the list
+__device__ __forceinline__ int map_frame_of(const MapFrame* __restrict__ tbl, int n_frames, int b) {
+  int lo = 0, hi = n_frames;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (tbl[mid].first_block <= b) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ void wave_count(unsigned long long* counter, unsigned long long mask, int lane) {
+  if (lane == 0 && mask != 0) (void)__hip_atomic_fetch_add(counter, (unsigned long long)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256) void k_world_points(const MapFrame* __restrict__ tbl, int n_frames, float min_depth, float max_depth) {
+#pragma clang fp contract(off)
+  const MapFrame& f = tbl[map_frame_of(tbl, n_frames, int(blockIdx.x))];
+  const int i = (int(blockIdx.x) - f.first_block) * 256 + int(threadIdx.x);
+  if (i >= f.w * f.h) return;
+  const GlobalF32x2 iz = *(Global<const GlobalF32x2>)global_ptr(f.iz + size_t(i) * f.stride);
+  const float K[4] = {f.K[0], f.K[1], f.K[2], f.K[3]};
+  float P[3];
+  const bool usable = map_world_point(f.pose, K, i % f.w, i / f.w, iz.y, min_depth, max_depth, P);
+  const float hole = __uint_as_float(kMapHole);
+  const GlobalF32x4 rec = {usable ? P[0] : hole, usable ? P[1] : hole, usable ? P[2] : hole, iz.x};
+  *((Global<GlobalF32x4>)global_ptr(f.out) + i) = rec;
+}
+
+template <bool COMBINE>
+__global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__ tbl, int n_frames, MapTable m, float min_depth, float max_depth) {
+#pragma clang fp contract(off)
+  const MapFrame& f = tbl[map_frame_of(tbl, n_frames, int(blockIdx.x))];
+  const int i = (int(blockIdx.x) - f.first_block) * 256 + int(threadIdx.x);
+  const int lane = int(threadIdx.x) & 63;
+  const bool active = i < f.w * f.h;
+  bool unusable = false, out_of_range = false, valid = false;
+  unsigned long long key = 0;
+  uint32_t q[4] = {0, 0, 0, 0};
+  if (active) {
+    const GlobalF32x2 iz = *(Global<const GlobalF32x2>)global_ptr(f.iz + size_t(i) * f.stride);
+    const float K[4] = {f.K[0], f.K[1], f.K[2], f.K[3]};
+    float P[3];
+    uint64_t k = 0;
+    if (!map_world_point(f.pose, K, i % f.w, i / f.w, iz.y, min_depth, max_depth, P)) unusable = true;
+    else if (!map_key_of(P, iz.x, m.leaf, &k, q)) out_of_range = true;
+    else valid = true;
+    key = k;
+  }
+  const unsigned long long validmask = __ballot(valid);
+  wave_count(m.counters + kMapCntUnusable, __ballot(unusable), lane);
+  wave_count(m.counters + kMapCntOutOfRange, __ballot(out_of_range), lane);
+  wave_count(m.counters + kMapCntCandidates, validmask, lane);
+
+  // what this lane adds: {qx | qy << 16}, {qz | n << 16}, qi
+  uint32_t a = valid ? q[0] | q[1] << 16 : 0u, b = valid ? q[2] | 1u << 16 : 0u, c = valid ? q[3] : 0u;
+  bool leader = valid;
+  if constexpr (COMBINE) {
+    const unsigned long long prev_key = __shfl_up(key, 1);
+    const bool prev_valid = lane > 0 && ((validmask >> (lane - 1)) & 1ull) != 0;
+    leader = valid && !(prev_valid && prev_key == key);
+    const unsigned long long breaks = __ballot(leader) | ~validmask;   // lanes that do not continue the run of the lane before them
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t ua = __shfl_down(a, d), ub = __shfl_down(b, d), uc = __shfl_down(c, d);
+      // lanes lane + 1 .. lane + d all continue this lane's run: lane + d holds the sum of the next (up to) d lanes of the same run
+      const bool same_run = lane + d < 64 && ((breaks >> (lane + 1)) & ((1ull << d) - 1ull)) == 0;
+      if (same_run) { a += ua; b += ub; c += uc; }
+    }
+  }
+  const uint32_t n = b >> 16, sx = a & 0xffffu, sy = a >> 16, sz = b & 0xffffu, si = c;
+  bool placed = false, claimed = false;
+  if (leader) {
+    const unsigned long long mask = m.capacity - 1;
+    unsigned long long at = map_hash(key, m.capacity);
+    for (int p = 0; p < kMapMaxProbes; ++p, at = (at + 1) & mask) {
+      MapSlot* slot = m.slots + at;                          // (at <= capacity - 1: inside the table)
+      unsigned long long* words = reinterpret_cast<unsigned long long*>(slot);
+      unsigned long long seen = __hip_atomic_load(words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (seen == kMapEmptyKey) {
+        seen = atomicCAS(words, (unsigned long long)kMapEmptyKey, key);
+        if (seen == kMapEmptyKey) { claimed = true; seen = key; }
+      }
+      if (seen != key) continue;
+      (void)__hip_atomic_fetch_add(words + 1, (unsigned long long)n | (unsigned long long)sx << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      (void)__hip_atomic_fetch_add(words + 2, (unsigned long long)sy | (unsigned long long)sz << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      (void)__hip_atomic_fetch_add(&slot->si, si, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      placed = true;
+      break;
+    }
+    if (!placed) (void)__hip_atomic_fetch_add(m.counters + kMapCntDropped, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  wave_count(m.counters + kMapCntUpdates, __ballot(placed), lane);
+  wave_count(m.counters + kMapCntOccupied, __ballot(claimed), lane);
+}
+
+// xyzi == null: count only (occupied slots into the cursor, voxels over the limit)
+__global__ __launch_bounds__(256) void k_map_extract(MapTable m, unsigned long long max_points, float4* __restrict__ xyzi, uint32_t* __restrict__ counts,
+                                                     unsigned long long* __restrict__ keys) {
+#pragma clang fp contract(off)
+  const int lane = int(threadIdx.x) & 63;
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  // (capacity and the stride are multiples of 64: the lanes of a wavefront leave the loop together)
+  for (unsigned long long at = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; at < m.capacity; at += stride) {
+    const auto words = (Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(m.slots + at));
+    const GlobalU32x4 lo = words[0], hi = words[1];         // key | n sx, sy sz si pad
+    const unsigned long long key = (unsigned long long)lo.x | (unsigned long long)lo.y << 32;
+    const uint32_t n = lo.z;
+    const bool occupied = key != kMapEmptyKey && n > 0;
+    const unsigned long long mask = __ballot(occupied);
+    wave_count(m.counters + kMapCntOverLimit, __ballot(occupied && n > kMapVoxelMaxPoints), lane);
+    unsigned long long base = 0;
+    if (lane == 0 && mask != 0)
+      base = __hip_atomic_fetch_add(m.counters + kMapCntCursor, (unsigned long long)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    base = __shfl(base, 0);
+    const unsigned long long idx = base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
+    if (occupied && xyzi && idx < max_points) {              // (idx < max_points: inside the caller's arrays)
+      float rec[4];
+      map_extract_voxel(key, n, lo.w, hi.x, hi.y, hi.z, m.leaf, rec);
+      gstore((Global<float4>)global_ptr(xyzi) + idx, make_float4(rec[0], rec[1], rec[2], rec[3]));
+      if (counts) counts[idx] = n;
+      if (keys) keys[idx] = key;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_map_clear(MapTable m) {
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  const GlobalU32x4 lo = {0xffffffffu, 0xffffffffu, 0u, 0u}, hi = {0u, 0u, 0u, 0u};
+  for (unsigned long long at = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; at < m.capacity; at += stride) {
+    const auto words = (Global<GlobalU32x4>)global_ptr(reinterpret_cast<GlobalU32x4*>(m.slots + at));
+    words[0] = lo;
+    words[1] = hi;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < kMapCounters) m.counters[threadIdx.x] = 0ull;
+}
+
+int table_grid(unsigned long long capacity) {
+  const unsigned long long blocks = (capacity + 255) / 256;
+  return int(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
+}
+
+}  // namespace
+
+void launch_world_points(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, float min_depth, float max_depth) {
+  k_world_points<<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, min_depth, max_depth);
+}
+
+void launch_map_insert(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth) {
+  k_map_insert<DVO_MAP_COMBINE_RUNS != 0><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+}
+
+bool map_insert_combines_runs() { return DVO_MAP_COMBINE_RUNS != 0; }
+
+hipError_t launch_map_extract(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys) {
+  const hipError_t e = hipMemsetAsync(m.counters + kMapCntOverLimit, 0, 2 * sizeof(unsigned long long), s);   // kMapCntOverLimit, kMapCntCursor
+  if (e != hipSuccess) return e;
+  k_map_extract<<<dim3(table_grid(m.capacity)), dim3(256), 0, s>>>(m, max_points, xyzi, counts, keys);
+  return hipSuccess;
+}
+
+void launch_map_clear(hipStream_t s, const MapTable& m) { k_map_clear<<<dim3(table_grid(m.capacity)), dim3(256), 0, s>>>(m); }
+
+}  // namespace dvo_hip

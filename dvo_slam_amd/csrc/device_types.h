@@ -6,6 +6,7 @@
 #include "hd_compat.h"
 #include "lens.h"
 #include "depth_rig.h"
+#include "cloud_map.h"
 
 #include "../../include/dvo_hip.h"
 
@@ -185,6 +186,27 @@ struct DepthRigArgs {
   int depth_pitch;                     // bytes
   float depth_scale;
 };
+
+// one frame of a keyframe-map launch (k_world_points, k_map_insert, cloud_map.hip; include/dvo_hip.h, dvo_hip_map_insert): where the {I, Z}
+// pairs of the level lie, the pose and the level's geometry.  Frames of different sizes share a launch: each owns the workgroups
+// first_block .. first_block + ceil(w * h / 256) - 1 (the table ends with one more entry that carries only the launch's block count).
+struct MapFrame {
+  const float* iz;                     // pixel i: I at iz[i * stride], Z at iz[i * stride + 1] (plane C: stride 2; the taps A: stride 4)
+  float* out;                          // k_world_points: w * h records {P.x, P.y, P.z, I}; unused by k_map_insert
+  MapPose pose;                        // cloud_map.h
+  float K[4];
+  int w, h, stride;
+  int first_block;
+};
+// the table and the counters of a map as the kernels see them; counters: kMapCnt* (cloud_map.hip)
+struct MapTable {
+  MapSlot* slots;
+  unsigned long long* counters;
+  unsigned long long capacity;         // a power of two
+  float leaf;
+};
+constexpr int kMapCntCandidates = 0, kMapCntDropped = 1, kMapCntOutOfRange = 2, kMapCntUnusable = 3, kMapCntUpdates = 4, kMapCntOccupied = 5,
+              kMapCntOverLimit = 6, kMapCntCursor = 7, kMapCounters = 8;
 
 // one frame of the caller-selection apply pass (k_apply_selection; include/dvo_hip.h, dvo_hip_frames_set_selection; rule: selection.h)
 struct SelectionApply {

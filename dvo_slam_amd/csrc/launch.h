@@ -73,6 +73,17 @@ void launch_rectify(hipStream_t s, const RectifyPtrs* tbl, int n_frames, const R
 void launch_depth_register(hipStream_t s, const DepthRigPtrs* tbl, int n_frames, const DepthRigArgs& a, bool depth_f32, int max_workgroups,
                            bool stream_nt);
 
+// cloud_map.hip: the keyframe map (cloud_map.h).  tbl: n_frames entries and one more whose first_block is total_blocks, the launch's grid.
+// launch_world_points: every frame's organised cloud into MapFrame::out.  launch_map_insert: every usable pixel into the table m (with the
+// wavefront's run folding unless the library was built with DVO_MAP_COMBINE_RUNS=0: map_insert_combines_runs).  launch_map_extract: the
+// occupied slots into xyzi / counts / keys (null: not wanted; xyzi null: count only), at most max_points; zeroes and then sets the
+// counters kMapCntCursor (occupied slots seen) and kMapCntOverLimit.  launch_map_clear: keys empty, sums and all counters zero.
+void launch_world_points(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, float min_depth, float max_depth);
+void launch_map_insert(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth);
+bool map_insert_combines_runs();
+hipError_t launch_map_extract(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys);
+void launch_map_clear(hipStream_t s, const MapTable& m);
+
 // align_kernels.hip / align_mfma.hip
 // variant 5 (default): Gram accumulation on the matrix cores (align_mfma.hip); variant 0: the all-VALU schedule with the DPP + LDS
 // two-stage reduction (align_kernels.hip).  Same outputs.

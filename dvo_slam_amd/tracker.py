@@ -621,6 +621,128 @@ def clear_depth_rig_batch(pyramids):
         p._depth_rig = None
 
 
+def _map_frames_args(pyramids, poses, level, min_depth, max_depth, who):
+    """(n, poses as a contiguous [n, 4, 4] float64 array) of a keyframe-map call, or ValueError / TypeError: nothing reaches the library
+    with a pose that is not 4 x 4, mismatched lengths, a level a pyramid does not have or an empty depth range."""
+    n = len(pyramids)
+    if n < 1:
+        raise ValueError("%s: no pyramids" % who)
+    try:
+        T = np.ascontiguousarray(poses, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("%s: poses must be real numbers, one 4 x 4 matrix per pyramid" % who)
+    if T.ndim == 2 and n == 1:
+        T = T[None]
+    if T.ndim != 3 or T.shape[1:] != (4, 4):
+        raise ValueError("%s: a pose is a 4 x 4 matrix (camera -> world), got shape %s" % (who, T.shape))
+    if T.shape[0] != n:
+        raise ValueError("%s: %d pyramids but %d poses" % (who, n, T.shape[0]))
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+        raise TypeError("%s: level must be an integer" % who)
+    for p in pyramids:
+        if not 0 <= level < p.levels:
+            raise ValueError("%s: a pyramid of %d levels has no level %d" % (who, p.levels, level))
+        if p.ctx is not pyramids[0].ctx:
+            raise ValueError("%s: the pyramids belong to different contexts" % who)
+    if not float(min_depth) <= float(max_depth):
+        raise ValueError("%s: need min_depth <= max_depth (no NaN)" % who)
+    return n, T
+
+
+def world_points_batch(pyramids, poses, level=0, min_depth=0.0, max_depth=float("inf"), device=False):
+    """The organised world clouds of n keyframes (dvo_hip_frames_world_points; the reference's AsyncPointCloudBuilder::BuildJob::build):
+    per pyramid an [h, w, 4] float32 array {P.x, P.y, P.z, I} of level `level` under its 4 x 4 pose (camera -> world); unusable pixels
+    have NaN in x, y, z.  device=True: torch tensors on the GPU instead of numpy arrays."""
+    n, T = _map_frames_args(pyramids, poses, level, min_depth, max_depth, "world_points_batch")
+    ctx = pyramids[0].ctx
+    shapes = []
+    for p in pyramids:
+        w, h = C.c_int(), C.c_int()
+        ctx.check(ctx._lib.dvo_hip_frame_info(p.ptr, level, C.byref(w), C.byref(h), None))
+        shapes.append((h.value, w.value, 4))
+    if device:
+        import torch
+        out = [torch.empty(s, dtype=torch.float32, device="cuda:%d" % ctx.device) for s in shapes]
+        ptrs = device_pointer_array([t.data_ptr() for t in out])
+    else:
+        out = [np.empty(s, np.float32) for s in shapes]
+        ptrs = device_pointer_array([a.ctypes.data for a in out])
+    ctx.check(ctx._lib.dvo_hip_frames_world_points(ctx.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)), int(level),
+                                                   float(min_depth), float(max_depth), ptrs, 1 if device else 0))
+    return out
+
+
+class KeyframeMap:
+    """A voxel-grid map of keyframes on the device (dvo_hip_map_*; the reference's PointCloudAggregator::build with an exact per-voxel
+    centroid): insert() fuses one level of n pyramids under their poses, extract() returns one point per occupied voxel.  The result
+    does not depend on the order of insertion.  capacity: slots of the table, rounded up to a power of two; keep it at least four
+    times the number of voxels (stats())."""
+
+    def __init__(self, ctx=None, leaf=0.01, capacity=1 << 22):
+        leaf = float(leaf)
+        if not (leaf > 0.0 and leaf < float("inf")):
+            raise ValueError("KeyframeMap: the leaf size must be finite and > 0")
+        if int(capacity) < 1:
+            raise ValueError("KeyframeMap: capacity must be positive")
+        self.ctx = ctx or default_context()
+        self.leaf = leaf
+        self.ptr = C.c_void_p()
+        self.ctx.check(self.ctx._lib.dvo_hip_map_create(self.ctx.ptr, leaf, int(capacity), C.byref(self.ptr)))
+
+    def insert(self, pyramids, poses, level=0, min_depth=0.0, max_depth=float("inf")):
+        """Every usable point of `level` of the pyramids under their 4 x 4 poses (camera -> world).  Raises DvoHipError with code
+        ERR_CAPACITY if the table dropped points; the map keeps what it took."""
+        n, T = _map_frames_args(pyramids, poses, level, min_depth, max_depth, "KeyframeMap.insert")
+        if pyramids[0].ctx is not self.ctx:
+            raise ValueError("KeyframeMap.insert: the pyramids belong to another context than the map")
+        self.ctx.check(self.ctx._lib.dvo_hip_map_insert(self.ctx.ptr, self.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)),
+                                                        int(level), float(min_depth), float(max_depth)))
+
+    def clear(self):
+        self.ctx.check(self.ctx._lib.dvo_hip_map_clear(self.ctx.ptr, self.ptr))
+
+    def stats(self):
+        """dict: occupied, points, dropped, out_of_range, unusable, over_limit, capacity, updates"""
+        s = _lib.MapStats()
+        self.ctx.check(self.ctx._lib.dvo_hip_map_stats(self.ctx.ptr, self.ptr, C.byref(s)))
+        return {name: int(getattr(s, name)) for name, _ in _lib.MapStats._fields_ if name != "reserved"}
+
+    def extract(self, sort=False, device=False, max_points=None):
+        """(xyzi [n, 4] float32, counts [n] uint32, keys [n] uint64): one record per occupied voxel, in no particular order unless
+        sort=True (by key, on the host).  device=True: torch tensors on the GPU (counts as int32, keys as int64: the same bits)."""
+        if sort and device:
+            raise ValueError("KeyframeMap.extract: sort=True orders on the host; extract to the host, or sort the device tensors by key")
+        cap = self.stats()["occupied"] if max_points is None else int(max_points)
+        got = C.c_size_t(0)
+        if device:
+            import torch
+            dev = "cuda:%d" % self.ctx.device
+            xyzi = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
+            counts = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+            keys = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+            ptrs = (xyzi.data_ptr(), counts.data_ptr(), keys.data_ptr())
+        else:
+            xyzi, counts, keys = np.empty((max(cap, 1), 4), np.float32), np.empty(max(cap, 1), np.uint32), np.empty(max(cap, 1), np.uint64)
+            ptrs = (xyzi.ctypes.data, counts.ctypes.data, keys.ctypes.data)
+        self.ctx.check(self.ctx._lib.dvo_hip_map_extract(self.ctx.ptr, self.ptr, cap, ptrs[0], ptrs[1], ptrs[2], 1 if device else 0, C.byref(got)))
+        xyzi, counts, keys = xyzi[:got.value], counts[:got.value], keys[:got.value]
+        if sort:
+            order = np.argsort(keys, kind="stable")
+            xyzi, counts, keys = xyzi[order], counts[order], keys[order]
+        return xyzi, counts, keys
+
+    def close(self):
+        if getattr(self, "ptr", None) and self.ctx.ptr:
+            self.ctx._lib.dvo_hip_map_destroy(self.ctx.ptr, self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def set_level_selection(pyramid, level, accepted):
     """Explicit selection of one level (dvo_hip_frame_set_level_selection): `accepted`, a (height, width) array of that level, is the
     exact accepted set (non-zero = selected) until the pyramid's pixels change or another selection is requested; None drops it."""

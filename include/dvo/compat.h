@@ -176,6 +176,19 @@ inline void pointcloud_resize(PointCloud& p, size_t n) { p.d.resize(n * 4); }
 inline float* pointcloud_ptr(PointCloud& p) { return p.d.data(); }
 #endif
 
+// A cloud of points with intensity, the stand-in for pcl::PointCloud<pcl::PointXYZRGB> in the visualization classes (there is no PCL
+// here): parallel vectors, width x height as PCL organises a cloud (height 1: unorganised)
+struct IntensityPointCloud {
+  typedef shared_ptr<IntensityPointCloud> Ptr;
+  std::vector<float> x, y, z, intensity;
+  size_t width, height;
+  IntensityPointCloud() : width(0), height(1) {}
+  size_t size() const { return x.size(); }
+  void resize(size_t n) { x.resize(n); y.resize(n); z.resize(n); intensity.resize(n); }
+  // (PCL's default point: the origin)
+  void push_back_default() { x.push_back(0.0f); y.push_back(0.0f); z.push_back(0.0f); intensity.push_back(0.0f); width = x.size(); height = 1; }
+};
+
 #ifdef DVO_HIP_USE_OPENCV
 typedef cv::Mat ImageMat;
 inline const float* image_ptr(const ImageMat& m) { return m.ptr<float>(); }

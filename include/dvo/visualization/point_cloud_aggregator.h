@@ -1,0 +1,107 @@
+// dvo/visualization/point_cloud_aggregator.h -- the downsampled map of the registered keyframes, fused on the device.
+// Stands in for dvo::visualization::PointCloudAggregator (dvo_core/include/dvo/visualization/point_cloud_aggregator.h:36-52,
+// dvo_core/src/visualization/point_cloud_aggregator.cpp:49-109).  The reference registers cloud builders by name and, on build(),
+// concatenates every step-th cloud (step = max(size / 50, 1), in name order) and filters the sum with a 1 cm voxel grid.  Here a
+// keyframe is registered as its device pyramid and its pose; build() clears a device map (include/dvo_hip.h, dvo_hip_map_*), inserts
+// the same subset in ONE launch and returns one point per voxel, sorted by voxel key.  An empty aggregator returns one default point,
+// as the reference does.  The voxel's point is the exact centroid quantised to leaf / 1024 -- NOT PCL's ApproximateVoxelGrid, whose
+// output depends on the order of insertion.
+#pragma once
+
+#include <algorithm>
+#include <map>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "dvo/visualization/async_point_cloud_builder.h"
+
+namespace dvo {
+namespace visualization {
+
+class PointCloudAggregator {
+ public:
+  typedef AsyncPointCloudBuilder::PointCloud PointCloud;
+
+  // capacity_slots: the device table (32 bytes per slot); keep it at least four times the voxels of the map
+  explicit PointCloudAggregator(size_t capacity_slots = size_t(1) << 22) : capacity_(capacity_slots), ctx_(0), map_(0) {}
+  ~PointCloudAggregator() {
+    if (map_) dvo_hip_map_destroy(ctx_, map_);
+  }
+
+  void add(const std::string& name, const dvo::core::RgbdImagePyramidPtr& pyramid, const dvo::compat::Affine3d& pose) {
+    Entry e;
+    e.pyramid = pyramid;
+    e.pose = pose;
+    clouds_[name] = e;
+  }
+  void remove(const std::string& name) { clouds_.erase(name); }
+  size_t size() const { return clouds_.size(); }
+
+  PointCloud::Ptr build() {
+    PointCloud::Ptr cloud(new PointCloud);
+    if (clouds_.empty()) {
+      cloud->push_back_default();
+      return cloud;
+    }
+    std::vector<dvo_hip_frame*> frames;
+    std::vector<double> poses;
+    const size_t step = std::max(clouds_.size() / size_t(50), size_t(1));
+    size_t k = 0;
+    for (std::map<std::string, Entry>::iterator it = clouds_.begin(); it != clouds_.end(); ++it, ++k) {
+      if ((k % step) != 0) continue;
+      frames.push_back(it->second.pyramid->device_frame());
+      double T[16];
+      dvo::compat::affine_to_rowmajor(it->second.pose, T);
+      poses.insert(poses.end(), T, T + 16);
+    }
+    dvo_hip_context* ctx = clouds_.begin()->second.pyramid->device_context();
+    if (map_ && ctx != ctx_) {
+      dvo_hip_map_destroy(ctx_, map_);
+      map_ = 0;
+    }
+    ctx_ = ctx;
+    using dvo::core::dvo_hip_check;
+    if (!map_ && !dvo_hip_check(ctx_, dvo_hip_map_create(ctx_, 0.01f, capacity_, &map_), "dvo_hip_map_create")) return cloud;
+    if (!dvo_hip_check(ctx_, dvo_hip_map_clear(ctx_, map_), "dvo_hip_map_clear")) return cloud;
+    if (!dvo_hip_check(ctx_, dvo_hip_map_insert(ctx_, map_, int(frames.size()), frames.data(), poses.data(), 0, 0.0f, INFINITY), "dvo_hip_map_insert"))
+      return cloud;
+    struct dvo_hip_map_stats stats;
+    if (!dvo_hip_check(ctx_, dvo_hip_map_stats(ctx_, map_, &stats), "dvo_hip_map_stats")) return cloud;
+    const size_t n = size_t(stats.occupied);
+    std::vector<float> xyzi(4 * std::max(n, size_t(1)));
+    std::vector<uint64_t> keys(std::max(n, size_t(1)));
+    size_t got = 0;
+    if (!dvo_hip_check(ctx_, dvo_hip_map_extract(ctx_, map_, n, xyzi.data(), 0, keys.data(), 0, &got), "dvo_hip_map_extract")) return cloud;
+    std::vector<size_t> order(got);
+    std::iota(order.begin(), order.end(), size_t(0));
+    std::sort(order.begin(), order.end(), [&keys](size_t a, size_t b) { return keys[a] < keys[b]; });
+    cloud->resize(got);
+    cloud->width = got;
+    cloud->height = 1;
+    for (size_t i = 0; i < got; ++i) {
+      const float* p = &xyzi[4 * order[i]];
+      cloud->x[i] = p[0];
+      cloud->y[i] = p[1];
+      cloud->z[i] = p[2];
+      cloud->intensity[i] = p[3];
+    }
+    return cloud;
+  }
+
+ private:
+  struct Entry {
+    dvo::core::RgbdImagePyramidPtr pyramid;
+    dvo::compat::Affine3d pose;
+  };
+  PointCloudAggregator(const PointCloudAggregator&);
+  PointCloudAggregator& operator=(const PointCloudAggregator&);
+
+  std::map<std::string, Entry> clouds_;
+  size_t capacity_;
+  dvo_hip_context* ctx_;
+  dvo_hip_map* map_;
+};
+
+}  // namespace visualization
+}  // namespace dvo

@@ -442,6 +442,78 @@ typedef struct {
 int dvo_hip_frames_set_depth_rig(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const dvo_hip_depth_rig* rig);
 int dvo_hip_frames_clear_depth_rig(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames);
 
+/* ---- keyframe map: world point clouds and a voxel-grid map of n keyframes, on the device ---------------------------------------------
+ * Stands in for the reference's map building: AsyncPointCloudBuilder::BuildJob::build
+ * (dvo_core/src/visualization/async_point_cloud_builder.cpp:61-110: pose.cast<float>() * image.pointcloud plus intensity, every pixel of a
+ * keyframe), PointCloudAggregator::build (dvo_core/src/visualization/point_cloud_aggregator.cpp:74-109: the clouds of up to ~50 keyframes
+ * concatenated and downsampled with a 1 cm voxel grid) and its caller dvo_ros/src/visualization/ros_camera_trajectory_visualizer.cpp.
+ * The keyframes already lie in device memory: fusing them reads 8 B per pixel, and only the finished map crosses to the host.
+ *   world point  pixel (u, v) of level `level` (intrinsics K of that level), depth z, intensity I, pose T = [R | t] (camera -> world, the
+ *                row-major 4 x 4 double of dvo_hip_result::transformation, converted to float once per frame):
+ *                X = (u - ox) / fx * z, Y = (v - oy) / fy * z (the (u - ox) / fx template of the RgbdCamera constructor,
+ *                dvo_core/src/core/rgbd_image.cpp:186-204, times z in RgbdCamera::buildPointCloud, rgbd_image.cpp:245-262), P = R (X, Y, z) + t.  USABLE iff z is finite and > 0, min_depth <= z <= max_depth (0 and +INFINITY: the range is off,
+ *                as in dvo_hip_frames_set_selection) and P is finite.  I and z are exactly what dvo_hip_frame_download_plane returns for
+ *                planes 0 and 1 of that level -- of a frame with a lens or a depth rig: the rectified / registered planes.
+ *   voxel        leaf > 0 (float).  Per axis i = floor(P / leaf), which must lie in -2^20 .. 2^20 - 1 (else the point is OUT OF RANGE:
+ *                counted, skipped); the offset inside the voxel is truncated to a 1024th of the leaf, the intensity rounded to a 16th
+ *                and clamped into [0, 4095 / 16].  key = (ix + 2^20) << 42 | (iy + 2^20) << 21 | (iz + 2^20).
+ *   sums         a voxel holds its point count n and the integer sums of the quantised offsets and intensities (uint32 each).  Up to
+ *                2^20 points per voxel no sum can wrap; a voxel with more is reported (over_limit, and by dvo_hip_map_extract), decided
+ *                from n alone.  Integer sums do not depend on the order of the additions: the map is the same BIT FOR BIT whatever
+ *                order the device visits the pixels in, however the frames are split over calls -- and equal to the host build of
+ *                dvo_slam_amd/csrc/cloud_map.h, where the operation order of all of this is fixed.
+ *   table        open addressing, capacity a power of two, linear probing with a fixed bound of 128 probes.  A point that finds neither
+ *                its voxel nor a free slot within the bound is DROPPED and counted; nothing ever waits or retries.
+ *   extraction   per voxel x = (ix + (sx / n + 0.5) / 1024) * leaf in double, rounded to float once (y, z likewise), intensity =
+ *                si / n / 16: per axis within leaf / 2048 of the true centroid of the voxel's points, the intensity within 1 / 32.
+ *                This is NOT PCL's ApproximateVoxelGrid, whose output depends on the order of insertion and on a 2048-entry hash
+ *                history.
+ *   streams      every call runs on the context's main stream behind the build-stream work that wrote the frames, and carries out every
+ *                recorded ingest first (DVO_HIP_INGEST_DEFER), as a match does.  Calls return when their result is complete.
+ *   refusals     a null or foreign frame or map, a level a frame does not have, a null pose or output, min_depth > max_depth or NaN:
+ *                DVO_HIP_ERR_INVALID, nothing launched, nothing changed.
+ *   cost         profiles/keyframe_map.md. */
+typedef struct dvo_hip_map dvo_hip_map;
+/* (a struct tag beside the function of the same name, like stat(2): `struct dvo_hip_map_stats s; dvo_hip_map_stats(ctx, map, &s);`) */
+struct dvo_hip_map_stats {
+  uint64_t occupied;      /* voxels in the table */
+  uint64_t points;        /* points the table took */
+  uint64_t dropped;       /* usable points in range that found no slot within the probe bound */
+  uint64_t out_of_range;  /* usable points beyond +-2^20 voxels on some axis */
+  uint64_t unusable;      /* pixels without a usable point */
+  uint64_t over_limit;    /* voxels that hold more than 2^20 points */
+  uint64_t capacity;      /* slots */
+  uint64_t updates;       /* slot updates issued: runs of neighbouring pixels that share a voxel go to the table as one */
+  uint64_t reserved[8];   /* 0 */
+};
+/* capacity_slots is rounded up to a power of two, at least 64 (32 bytes per slot); a leaf that is not finite and > 0 is
+ * DVO_HIP_ERR_INVALID.  Keep the table at most a quarter full (dvo_hip_map_stats): probe sequences then stay far below the bound.
+ * A map belongs to its context and is destroyed before it. */
+int dvo_hip_map_create(dvo_hip_context* ctx, float leaf, size_t capacity_slots, dvo_hip_map** out);
+void dvo_hip_map_destroy(dvo_hip_context* ctx, dvo_hip_map* map);
+/* every slot empty, every sum and statistic zero (after a pose-graph optimisation: clear, then insert under the new poses) */
+int dvo_hip_map_clear(dvo_hip_context* ctx, dvo_hip_map* map);
+/* PointCloudAggregator::build's concatenate + filter for n frames (point_cloud_aggregator.cpp:95-106) in one launch: every usable point
+ * of level `level` of every frame, under poses[16 * i ..], into the map.  Frames of different sizes and cameras may share a call.
+ * DVO_HIP_ERR_CAPACITY if the call dropped a point -- the map keeps what it took, the statistics say how many -- else DVO_HIP_OK.
+ * To answer that, the call WAITS for the main stream (one read-back of the map's counters behind the launch; dvo_hip_map_stats and
+ * dvo_hip_map_extract wait likewise): it drains whatever was queued before it, so it does not belong between pipelined matches. */
+int dvo_hip_map_insert(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses /* n x 16 */,
+                       int level, float min_depth, float max_depth);
+int dvo_hip_map_stats(dvo_hip_context* ctx, dvo_hip_map* map, struct dvo_hip_map_stats* out);
+/* The downsampled cloud (what point_cloud_aggregator.cpp:105-108 returns): one record {x, y, z, intensity} per voxel into xyzi, its point
+ * count and key into counts / keys where those are not NULL; host arrays, or device arrays (xyzi 16-byte aligned) with out_on_device.
+ * The ORDER is unspecified and may differ from call to call: sort by key to compare.  *n_points = records written (<= max_points).
+ * DVO_HIP_ERR_CAPACITY if the map holds more voxels than max_points -- the first max_points found are written, nothing beyond -- or if
+ * a voxel is over the 2^20 limit (everything is written; that voxel's record is unreliable). */
+int dvo_hip_map_extract(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_points, float* xyzi, uint32_t* counts_or_null,
+                        uint64_t* keys_or_null, int out_on_device, size_t* n_points);
+/* AsyncPointCloudBuilder::BuildJob::build for n frames (async_point_cloud_builder.cpp:61-110): the ORGANISED cloud, w x h records
+ * {P.x, P.y, P.z, I} per frame in raster order into out[i] (host, or device and 16-byte aligned with out_on_device); an unusable pixel
+ * has a quiet NaN (0x7FC00000) in x, y and z and its I as it is. */
+int dvo_hip_frames_world_points(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses /* n x 16 */,
+                                int level, float min_depth, float max_depth, float* const* out, int out_on_device);
+
 /* ---- the hot path --------------------------------------------------------------------------- */
 /* DenseTracker::match(RgbdImagePyramid& reference, RgbdImagePyramid& current, Result&)
  * (dvo_core/src/dense_tracking.cpp:123-376).  `levels`/`iters` may be NULL (no statistics).
@@ -674,6 +746,9 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value);
  * "depth_registrations" (frames whose depth plane was registered at ingest because they carry a depth rig,
  * dvo_hip_frames_set_depth_rig; each is also one of "f32_ingests") and "depth_rig_table_bytes" (the size of that pass's pointer table:
  * 0 until the first such frame is ingested),
+ * "map_inserts" (frames dvo_hip_map_insert has launched into a map of this context), "map_points" (the points those maps took) and
+ * "map_dropped" (the points they dropped for want of a slot; a call that drops any returns DVO_HIP_ERR_CAPACITY).  Refused calls count
+ * nothing, dvo_hip_map_clear resets none of them,
  * "warmup_wait_us" (the longest of the nine stream waits dvo_hip_context_create makes on trivial commands to warm up the runtime's wait
  * path, in microseconds: the first GPU process on a fresh box has been seen to spend 14-24 ms in its first wait),
  * "host_batches" and "host_ns_prepare" / "host_ns_enqueue" / "host_ns_wait" / "host_ns_finish" (nanoseconds the calling thread spent
