@@ -74,6 +74,12 @@ class MapStats(C.Structure):
                 ("reserved", C.c_uint64 * 8)]
 
 
+class RenderParams(C.Structure):
+    """dvo_hip_render_params: how a view of a keyframe map is rendered (dvo_hip_map_render)."""
+    _fields_ = [("min_depth", C.c_float), ("max_depth", C.c_float), ("splat", C.c_float), ("max_splat", C.c_int32),
+                ("min_points", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 # every symbol include/dvo_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "dvo_hip_context_create", "dvo_hip_context_destroy", "dvo_hip_last_error", "dvo_hip_context_stream",
@@ -93,6 +99,7 @@ EXPORTS = [
     "dvo_hip_frames_set_depth_rig", "dvo_hip_frames_clear_depth_rig",
     "dvo_hip_map_create", "dvo_hip_map_destroy", "dvo_hip_map_clear", "dvo_hip_map_insert", "dvo_hip_map_stats", "dvo_hip_map_extract",
     "dvo_hip_frames_world_points",
+    "dvo_hip_render_params_default", "dvo_hip_map_render", "dvo_hip_map_render_frames", "dvo_hip_time_map_render",
 ]
 
 ROLE_CURRENT, ROLE_REFERENCE = 0, 1
@@ -210,6 +217,13 @@ def lib():
         L.dvo_hip_map_stats.argtypes = [vp, vp, C.POINTER(MapStats)]
         L.dvo_hip_map_extract.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
         L.dvo_hip_frames_world_points.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.c_int, C.c_float, C.c_float, C.POINTER(vp), C.c_int]
+    if hasattr(L, "dvo_hip_map_render"):   # (likewise: an older build renders no views)
+        dp, rp = C.POINTER(C.c_double), C.POINTER(RenderParams)
+        L.dvo_hip_render_params_default.argtypes = []
+        L.dvo_hip_render_params_default.restype = RenderParams
+        L.dvo_hip_map_render.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, fp, dp, rp, C.POINTER(vp), C.POINTER(vp), C.c_int]
+        L.dvo_hip_map_render_frames.argtypes = [vp, vp, C.c_int, C.POINTER(vp), dp, rp, C.c_int, C.POINTER(Config), C.c_uint]
+        L.dvo_hip_time_map_render.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, fp, dp, rp, C.c_int, fp]
     L.dvo_hip_context_device.argtypes = [vp]
     L.dvo_hip_comm_get_unique_id.argtypes = [vp]
     L.dvo_hip_comm_create.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]

@@ -391,6 +391,7 @@ struct dvo_hip_context {
   long long lens_ingests = 0;      // frames rectified at ingest (dvo_hip_frames_set_lens), counter "lens_ingests"
   long long depth_registrations = 0;   // frames whose depth was registered at ingest (dvo_hip_frames_set_depth_rig), counter "depth_registrations"
   long long map_inserts = 0, map_points = 0, map_dropped = 0;   // frames / points a keyframe map took, points it dropped (dvo_hip_map_insert); counters of the same names
+  long long map_renders = 0;       // views rendered out of a keyframe map (dvo_hip_map_render, dvo_hip_map_render_frames), counter "map_renders"
   // Option "defer_ingest": a batched re-ingest (dvo_hip_frames_update_raw_device_as) is only recorded, and carried out by the next
   // dvo_hip_match_batch right behind the first launches of its first level (or by whatever entry point comes first).  A streaming
   // caller re-ingests the next batch and then aligns the current one: enqueueing the ingest first keeps the alignment's stream idle
@@ -507,6 +508,8 @@ struct dvo_hip_context {
   DevBuf lens_tbl;                                    // table of the rectify pass (rectify_frames; allocated by the first lens ingest)
   DevBuf rig_tbl;                                     // table of the register pass (register_frames; allocated by the first rig ingest)
   DevBuf map_tbl, map_stage;                          // the frame table of a keyframe-map launch and the staging area of results that go to host memory (capi_map.inc)
+  DevBuf render_tbl, render_zbuf, render_planes;      // a render's view table, its z-buffers and -- dvo_hip_map_render_frames -- the planes the frames ingest (capi_map.inc)
+  hipEvent_t render_done = nullptr;                   // recorded behind a render on the main stream: the build stream's ingest waits for it
   static const int kTableSlots = 4;
   DevBuf build_tbl[kTableSlots];   // (a few, picked by the list's first frame: see Workspace::pair_ptrs)
   DevBuf* build_tbl_cur = nullptr; // the one that holds the table of build_tbl_frames
@@ -790,6 +793,7 @@ int dvo_hip_context_create(int device, dvo_hip_context** out) {
   for (int i = 0; i < dvo_hip_context::kBuildRing && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&ctx->build_events[i], hipEventDisableTiming);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&ctx->upload_stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->upload_done, hipEventDisableTiming);
+  if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->render_done, hipEventDisableTiming);
   if (e != hipSuccess) {
     g_create_error = std::string("context setup (build stream): ") + hipGetErrorString(e);
     dvo_hip_context_destroy(ctx);
@@ -852,7 +856,8 @@ void dvo_hip_context_destroy(dvo_hip_context* ctx) {
   if (ctx->build_stream) (void)hipStreamDestroy(ctx->build_stream);
   for (DevBuf& b : ctx->build_tbl) b.release();
   for (DevBuf* b : {&ctx->misc, &ctx->role_tbl_cur, &ctx->role_tbl_ref, &ctx->prep_tbl_cur, &ctx->prep_tbl_ref, &ctx->rcp_table, &ctx->ref_order_planes,
-                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl, &ctx->rig_tbl, &ctx->map_tbl, &ctx->map_stage}) b->release();
+                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl, &ctx->rig_tbl, &ctx->map_tbl, &ctx->map_stage, &ctx->render_tbl, &ctx->render_zbuf, &ctx->render_planes}) b->release();
+  if (ctx->render_done) (void)hipEventDestroy(ctx->render_done);
   for (DevBuf& b : ctx->upload_buf) b.release();
   for (const dvo_hip_context::PooledBlock& b : ctx->frame_pool) (void)hipFree(b.p);
   ctx->frame_pool.clear();
@@ -918,7 +923,7 @@ int prepare_roles(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* fram
 }  // namespace
 
 #include "capi_ingest.inc"   // the raw-frame ingest: dvo_hip_frame_create_*, dvo_hip_frames_update_*, dvo_hip_flush_deferred
-#include "capi_map.inc"      // the keyframe map: dvo_hip_map_*, dvo_hip_frames_world_points
+#include "capi_map.inc"      // the keyframe map: dvo_hip_map_*, dvo_hip_frames_world_points, dvo_hip_map_render*
 
 int dvo_hip_upload_wait(dvo_hip_context* ctx) {
   DVO_ENTER(ctx);

@@ -279,3 +279,209 @@ int dvo_hip_frames_world_points(dvo_hip_context* ctx, int n_frames, dvo_hip_fram
   DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return DVO_HIP_OK;
 }
+
+// ---- views of the map (map_render.h; kernels: map_render.hip) ----
+
+namespace {
+
+// params (null: the defaults), size, K and poses of a render; *args = what the kernels take
+int check_render(dvo_hip_context* ctx, const dvo_hip_map* map, int n_views, int width, int height, const float* K, const double* poses,
+                 const dvo_hip_render_params* params, RenderArgs* args, const char* who) {
+  const int rc = check_map(ctx, map, who);
+  if (rc != DVO_HIP_OK) return rc;
+  if (n_views < 1 || !K || !poses) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  if (width < 1 || height < 1 || width > (1 << 24) || height > (1 << 24) || (long long)width * height * n_views > 0x7fffffffll)
+    return fail(ctx, DVO_HIP_ERR_INVALID, who, "need a positive size of at most 2^24 a side and 2^31 - 1 pixels in all views");
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(K[k])) return fail(ctx, DVO_HIP_ERR_INVALID, who, "K must be finite");
+  if (!(K[0] > 0.0f && K[1] > 0.0f)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "need fx > 0 and fy > 0");
+  const dvo_hip_render_params p = params ? *params : dvo_hip_render_params_default();
+  if (!(p.min_depth <= p.max_depth)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "need min_depth <= max_depth (no NaN)");
+  if (!(p.splat > 0.0f && p.splat <= 4.0f)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "splat must lie in (0, 4]");
+  if (p.max_splat < 1 || p.max_splat > kRenderMaxSplat || p.max_splat % 2 == 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "max_splat must be odd, 1 .. 15");
+  if (p.min_points < 1) return fail(ctx, DVO_HIP_ERR_INVALID, who, "min_points must be at least 1");
+  if (p.reserved[0] != 0 || p.reserved[1] != 0 || p.reserved[2] != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a reserved field is not 0");
+  args->min_depth = p.min_depth;
+  args->max_depth = p.max_depth;
+  args->splat = p.splat;
+  args->leaf = map->leaf;
+  args->max_splat = p.max_splat;
+  args->min_points = p.min_points;
+  return DVO_HIP_OK;
+}
+
+// the view table of a render on the main stream: n MapView, then n RenderPlanes; and the z-buffers
+int upload_views(dvo_hip_context* ctx, int n_views, int width, int height, const float* K, const double* poses, float* const* I, float* const* Z) {
+  const size_t views_bytes = size_t(n_views) * sizeof(MapView), bytes = views_bytes + size_t(n_views) * sizeof(RenderPlanes);
+  std::vector<char> host(bytes);
+  for (int i = 0; i < n_views; ++i) {
+    const MapView v = map_view_prepare(poses + size_t(i) * 16, K, width, height);
+    const RenderPlanes o = {I[i], Z[i]};
+    std::memcpy(host.data() + size_t(i) * sizeof(MapView), &v, sizeof v);
+    std::memcpy(host.data() + views_bytes + size_t(i) * sizeof(RenderPlanes), &o, sizeof o);
+  }
+  DVO_HIP_TRY(ctx, ctx->render_tbl.reserve(bytes));
+  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->render_tbl.p, host.data(), bytes));
+  DVO_HIP_TRY(ctx, ctx->render_zbuf.reserve(size_t(n_views) * size_t(width) * size_t(height) * sizeof(unsigned long long)));
+  return DVO_HIP_OK;
+}
+
+const MapView* render_views(const dvo_hip_context* ctx) { return ctx->render_tbl.as<MapView>(); }
+const RenderPlanes* render_outs(const dvo_hip_context* ctx, int n_views) {
+  return reinterpret_cast<const RenderPlanes*>(ctx->render_tbl.as<char>() + size_t(n_views) * sizeof(MapView));
+}
+
+}  // namespace
+static_assert(sizeof(dvo_hip_render_params) == 32, "dvo_hip_render_params: five fields and three reserved words");
+static_assert(sizeof(MapView) % alignof(RenderPlanes) == 0, "the planes' table lies behind the views");
+
+dvo_hip_render_params dvo_hip_render_params_default(void) {
+  dvo_hip_render_params p;
+  std::memset(&p, 0, sizeof p);
+  p.min_depth = 0.0f;
+  p.max_depth = INFINITY;
+  p.splat = 2.0f;
+  p.max_splat = 7;
+  p.min_points = 1;
+  return p;
+}
+
+int dvo_hip_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float K[4], const double* poses,
+                       const dvo_hip_render_params* params, float* const* intensity_out, float* const* depth_out, int out_on_device) {
+  DVO_ENTER(ctx);
+  RenderArgs args;
+  const int rc0 = check_render(ctx, map, n_views, width, height, K, poses, params, &args, "map_render");
+  if (rc0 != DVO_HIP_OK) return rc0;
+  if (!intensity_out || !depth_out) return fail(ctx, DVO_HIP_ERR_INVALID, "map_render: bad argument");
+  for (int i = 0; i < n_views; ++i) {
+    if (!intensity_out[i] || !depth_out[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "map_render: null output");
+    if (out_on_device && (!aligned_to(intensity_out[i], 16) || !aligned_to(depth_out[i], 16)))
+      return fail(ctx, DVO_HIP_ERR_INVALID, "map_render: a device plane must be 16-byte aligned");
+  }
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t pixels = size_t(width) * size_t(height), plane = (pixels * 4 + 15) & ~size_t(15);
+  std::vector<float*> si, sz;
+  if (!out_on_device) {
+    DVO_HIP_TRY(ctx, ctx->map_stage.reserve(plane * 2 * size_t(n_views)));
+    for (int i = 0; i < n_views; ++i) {
+      si.push_back(reinterpret_cast<float*>(ctx->map_stage.as<char>() + plane * (2 * size_t(i))));
+      sz.push_back(reinterpret_cast<float*>(ctx->map_stage.as<char>() + plane * (2 * size_t(i) + 1)));
+    }
+  }
+  const int rc = upload_views(ctx, n_views, width, height, K, poses, out_on_device ? intensity_out : si.data(), out_on_device ? depth_out : sz.data());
+  if (rc != DVO_HIP_OK) return rc;
+  launch_map_render(ctx->stream, map_table(map), render_views(ctx), render_outs(ctx, n_views), n_views, (long long)pixels, args,
+                    ctx->render_zbuf.as<unsigned long long>());
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  ctx->map_renders += n_views;
+  if (!out_on_device) {
+    for (int i = 0; i < n_views; ++i) {
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(intensity_out[i], si[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(depth_out[i], sz[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_map_render_frames(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses,
+                              const dvo_hip_render_params* params, int role, const dvo_hip_config* cfg, unsigned flags) {
+  DVO_ENTER(ctx);
+  const char* who = "map_render_frames";
+  int rc = check_map(ctx, map, who);
+  if (rc != DVO_HIP_OK) return rc;
+  if (n_frames < 1 || !frames || !poses) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  if (flags & DVO_HIP_INGEST_DEFER) return fail(ctx, DVO_HIP_ERR_INVALID, who, "DVO_HIP_INGEST_DEFER: a render is not recorded");
+  for (int i = 0; i < n_frames; ++i) {
+    const dvo_hip_frame* f = frames[i];
+    if (!f) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null frame");
+    if (std::find(ctx->cameras.begin(), ctx->cameras.end(), f->cam) == ctx->cameras.end())
+      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame of another context");
+    if (f->lens_on || f->rig_on)
+      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a lens or a depth rig takes raw sensor planes; rendered planes are rectified and registered already");
+  }
+  const CameraGeom* cam = frames[0]->cam;
+  const int width = frames[0]->lv[0].w, height = frames[0]->lv[0].h;
+  RenderArgs args;
+  rc = check_render(ctx, map, n_frames, width, height, cam->K[0], poses, params, &args, who);
+  if (rc != DVO_HIP_OK) return rc;
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // the planes the frames ingest: scratch of the context.  Its last readers are the builds of the previous call's frames, which the main
+  // stream waits for at the end of that call
+  const size_t pixels = size_t(width) * size_t(height), plane = (pixels * 4 + 255) & ~size_t(255);
+  DVO_HIP_TRY(ctx, ctx->render_planes.reserve(plane * 2 * size_t(n_frames)));
+  std::vector<float*> pi, pz;
+  std::vector<const void*> ci, cz;
+  for (int i = 0; i < n_frames; ++i) {
+    pi.push_back(reinterpret_cast<float*>(ctx->render_planes.as<char>() + plane * (2 * size_t(i))));
+    pz.push_back(reinterpret_cast<float*>(ctx->render_planes.as<char>() + plane * (2 * size_t(i) + 1)));
+    ci.push_back(pi.back());
+    cz.push_back(pz.back());
+  }
+  IngestSource src{ci.data(), DVO_HIP_PIXEL_F32, 0, cz.data(), 1.0f, DVO_HIP_DEPTH_F32, 0};
+  IngestSource probe = src;
+  rc = check_ingest(ctx, who, n_frames, frames, &probe, /*plain_ok=*/true, role, cfg);   // (role, cfg, one camera: before anything is launched)
+  if (rc != DVO_HIP_OK) return rc;
+  rc = upload_views(ctx, n_frames, width, height, cam->K[0], poses, pi.data(), pz.data());
+  if (rc != DVO_HIP_OK) return rc;
+  launch_map_render(ctx->stream, map_table(map), render_views(ctx), render_outs(ctx, n_frames), n_frames, (long long)pixels, args,
+                    ctx->render_zbuf.as<unsigned long long>());
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  DVO_HIP_TRY(ctx, hipEventRecord(ctx->render_done, ctx->stream));
+  DVO_HIP_TRY(ctx, hipStreamWaitEvent(ctx->build_stream, ctx->render_done, 0));
+  ctx->map_renders += n_frames;
+  rc = ingest(ctx, who, n_frames, frames, src, /*host_planes=*/false, /*plain_ok=*/true, role, cfg, 0, (flags & DVO_HIP_INGEST_NO_RAW_COPY) ? 0 : 1);
+  if (rc != DVO_HIP_OK) return rc;
+  return wait_for_build(ctx, n_frames, frames);              // (the next render into the scratch planes runs behind this ingest)
+}
+
+int dvo_hip_time_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float K[4], const double* poses,
+                            const dvo_hip_render_params* params, int reps, float ms[3]) {
+  DVO_ENTER(ctx);
+  RenderArgs args;
+  int rc = check_render(ctx, map, n_views, width, height, K, poses, params, &args, "time_map_render");
+  if (rc != DVO_HIP_OK) return rc;
+  if (reps < 1 || reps > 1000 || !ms) return fail(ctx, DVO_HIP_ERR_INVALID, "time_map_render: bad argument");
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t pixels = size_t(width) * size_t(height), plane = (pixels * 4 + 255) & ~size_t(255);
+  DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->build_stream));   // (the scratch planes may still be read by an ingest)
+  DVO_HIP_TRY(ctx, ctx->render_planes.reserve(plane * 2 * size_t(n_views)));
+  std::vector<float*> pi, pz;
+  for (int i = 0; i < n_views; ++i) {
+    pi.push_back(reinterpret_cast<float*>(ctx->render_planes.as<char>() + plane * (2 * size_t(i))));
+    pz.push_back(reinterpret_cast<float*>(ctx->render_planes.as<char>() + plane * (2 * size_t(i) + 1)));
+  }
+  rc = upload_views(ctx, n_views, width, height, K, poses, pi.data(), pz.data());
+  if (rc != DVO_HIP_OK) return rc;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipError_t e = hipSuccess;
+  for (hipEvent_t& x : ev)
+    if (e == hipSuccess) e = hipEventCreate(&x);
+  std::vector<float> t[3];
+  unsigned long long* zbuf = ctx->render_zbuf.as<unsigned long long>();
+  const MapTable table = map_table(map);
+  for (int r = 0; r < reps && e == hipSuccess; ++r) {
+    e = hipEventRecord(ev[0], ctx->stream);
+    launch_render_fill(ctx->stream, zbuf, (long long)pixels * n_views);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
+    launch_render_splat(ctx->stream, table, render_views(ctx), n_views, args, zbuf);
+    if (e == hipSuccess) e = hipEventRecord(ev[2], ctx->stream);
+    launch_render_resolve(ctx->stream, zbuf, render_outs(ctx, n_views), n_views, (long long)pixels);
+    if (e == hipSuccess) e = hipEventRecord(ev[3], ctx->stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventSynchronize(ev[3]);
+    for (int k = 0; k < 3 && e == hipSuccess; ++k) {
+      float one = 0.0f;
+      e = hipEventElapsedTime(&one, ev[k], ev[k + 1]);
+      t[k].push_back(one);
+    }
+  }
+  for (hipEvent_t x : ev)
+    if (x) (void)hipEventDestroy(x);
+  DVO_HIP_TRY(ctx, e);
+  for (int k = 0; k < 3; ++k) {
+    std::sort(t[k].begin(), t[k].end());
+    ms[k] = t[k][t[k].size() / 2];
+  }
+  return DVO_HIP_OK;
+}

@@ -7,6 +7,7 @@
 #include "lens.h"
 #include "depth_rig.h"
 #include "cloud_map.h"
+#include "map_render.h"
 
 #include "../../include/dvo_hip.h"
 
@@ -204,6 +205,11 @@ struct MapTable {
   unsigned long long* counters;
   unsigned long long capacity;         // a power of two
   float leaf;
+};
+// the tight float planes of one rendered view (k_render_resolve, map_render.hip; include/dvo_hip.h, dvo_hip_map_render)
+struct RenderPlanes {
+  float* I;
+  float* Z;
 };
 constexpr int kMapCntCandidates = 0, kMapCntDropped = 1, kMapCntOutOfRange = 2, kMapCntUnusable = 3, kMapCntUpdates = 4, kMapCntOccupied = 5,
               kMapCntOverLimit = 6, kMapCntCursor = 7, kMapCounters = 8;

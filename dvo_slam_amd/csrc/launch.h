@@ -84,6 +84,16 @@ bool map_insert_combines_runs();
 hipError_t launch_map_extract(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys);
 void launch_map_clear(hipStream_t s, const MapTable& m);
 
+// map_render.hip: views of the keyframe map (map_render.h).  n_views views of `pixels` = w * h pixels each; zbuf: pixels * n_views
+// elements.  launch_render_fill: every element ~0.  launch_render_splat: every voxel of the table into every view, an atomic minimum per
+// covered pixel.  launch_render_resolve: the z-buffers into the planes out[view].  launch_map_render: the three, in that order.
+void launch_render_fill(hipStream_t s, unsigned long long* zbuf, long long elements);
+void launch_render_splat(hipStream_t s, const MapTable& m, const MapView* views, int n_views, const RenderArgs& a, unsigned long long* zbuf);
+void launch_render_resolve(hipStream_t s, const unsigned long long* zbuf, const RenderPlanes* out, int n_views, long long pixels);
+void launch_map_render(hipStream_t s, const MapTable& m, const MapView* views, const RenderPlanes* out, int n_views, long long pixels, const RenderArgs& a,
+                       unsigned long long* zbuf);
+bool map_render_preloads();
+
 // align_kernels.hip / align_mfma.hip
 // variant 5 (default): Gram accumulation on the matrix cores (align_mfma.hip); variant 0: the all-VALU schedule with the DPP + LDS
 // two-stage reduction (align_kernels.hip).  Same outputs.

@@ -672,6 +672,69 @@ def world_points_batch(pyramids, poses, level=0, min_depth=0.0, max_depth=float(
     return out
 
 
+RENDER_DEFAULTS = dict(min_depth=0.0, max_depth=float("inf"), splat=2.0, max_splat=7, min_points=1)   # dvo_hip_render_params_default
+
+
+def render_params_struct(**params):
+    """dvo_hip_render_params from keyword arguments (min_depth, max_depth, splat, max_splat, min_points; the rest as
+    dvo_hip_render_params_default gives them), or ValueError / TypeError: nothing reaches the library with a value it would refuse."""
+    unknown = set(params) - set(RENDER_DEFAULTS)
+    if unknown:
+        raise TypeError("render: unknown parameter(s) %s; known: %s" % (sorted(unknown), sorted(RENDER_DEFAULTS)))
+    p = dict(RENDER_DEFAULTS, **params)
+    for k in ("max_splat", "min_points"):
+        if isinstance(p[k], bool) or not isinstance(p[k], (int, np.integer)):
+            raise TypeError("render: %s must be an integer" % k)
+    lo, hi, splat = float(p["min_depth"]), float(p["max_depth"]), float(p["splat"])
+    if not lo <= hi:
+        raise ValueError("render: need min_depth <= max_depth (no NaN)")
+    if not 0.0 < splat <= 4.0:
+        raise ValueError("render: splat must lie in (0, 4]")
+    if not 1 <= p["max_splat"] <= 15 or p["max_splat"] % 2 == 0:
+        raise ValueError("render: max_splat must be odd, 1 .. 15")
+    if not 1 <= p["min_points"] < 1 << 32:
+        raise ValueError("render: min_points must be at least 1")
+    out = _lib.RenderParams()
+    out.min_depth, out.max_depth, out.splat, out.max_splat, out.min_points = lo, hi, splat, int(p["max_splat"]), int(p["min_points"])
+    return out
+
+
+def _render_poses(poses, n, who):
+    """poses as a contiguous [n, 4, 4] float64 array (n None: as many as there are; one 4 x 4 matrix is one view)"""
+    try:
+        T = np.ascontiguousarray(poses, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("%s: poses must be real numbers, one 4 x 4 matrix per view" % who)
+    if T.ndim == 2 and n in (None, 1):
+        T = T[None]
+    if T.ndim != 3 or T.shape[1:] != (4, 4) or T.shape[0] < 1:
+        raise ValueError("%s: a pose is a 4 x 4 matrix (camera -> world), got shape %s" % (who, T.shape))
+    if n is not None and T.shape[0] != n:
+        raise ValueError("%s: %d pyramids but %d poses" % (who, n, T.shape[0]))
+    return T
+
+
+def _render_view_args(K, width, height, poses, who):
+    """(K as float32[4], width, height, poses [n, 4, 4]) of KeyframeMap.render, or ValueError / TypeError"""
+    for name, v in (("width", width), ("height", height)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError("%s: %s must be an integer" % (who, name))
+        if not 1 <= v <= 1 << 24:
+            raise ValueError("%s: %s must be positive (and at most 2^24)" % (who, name))
+    try:
+        K = np.ascontiguousarray(K, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise TypeError("%s: K must be four real numbers fx, fy, ox, oy" % who)
+    if K.shape != (4,):
+        raise ValueError("%s: K is fx, fy, ox, oy, got shape %s" % (who, K.shape))
+    if not np.all(np.isfinite(K)) or not (K[0] > 0 and K[1] > 0):
+        raise ValueError("%s: K must be finite with fx > 0 and fy > 0" % who)
+    T = _render_poses(poses, None, who)
+    if int(width) * int(height) * T.shape[0] > (1 << 31) - 1:
+        raise ValueError("%s: more than 2^31 - 1 pixels in one call" % who)
+    return K, int(width), int(height), T
+
+
 class KeyframeMap:
     """A voxel-grid map of keyframes on the device (dvo_hip_map_*; the reference's PointCloudAggregator::build with an exact per-voxel
     centroid): insert() fuses one level of n pyramids under their poses, extract() returns one point per occupied voxel.  The result
@@ -730,6 +793,51 @@ class KeyframeMap:
             order = np.argsort(keys, kind="stable")
             xyzi, counts, keys = xyzi[order], counts[order], keys[order]
         return xyzi, counts, keys
+
+    def render(self, K, width, height, poses, device=False, **params):
+        """Views of the map (dvo_hip_map_render): the nearest voxel per pixel of a width x height pinhole camera K = fx, fy, ox, oy at
+        each 4 x 4 pose (camera -> world).  Returns (I, Z), float32 arrays of shape (n, height, width): intensity (0 where nothing was
+        seen) and depth in metres (NaN where nothing was seen).  device=True: torch tensors on the GPU, ordered on the context's stream.
+        params: min_depth, max_depth, splat, max_splat, min_points (render_params_struct)."""
+        K, width, height, T = _render_view_args(K, width, height, poses, "KeyframeMap.render")
+        rp = render_params_struct(**params)
+        n = T.shape[0]
+        if device:
+            import torch
+            dev = "cuda:%d" % self.ctx.device
+            pad = (width * height + 3) // 4 * 4             # (every view's plane 16-byte aligned: views apart by a multiple of 4 floats)
+            I, Z = (torch.empty(n * pad, dtype=torch.float32, device=dev).as_strided((n, height, width), (pad, width, 1)) for _ in range(2))
+            ip, zp = ([t[k].data_ptr() for k in range(n)] for t in (I, Z))
+        else:
+            I, Z = np.empty((n, height, width), np.float32), np.empty((n, height, width), np.float32)
+            ip, zp = ([a[k].ctypes.data for k in range(n)] for a in (I, Z))
+        self.ctx.check(self.ctx._lib.dvo_hip_map_render(self.ctx.ptr, self.ptr, n, width, height, K.ctypes.data_as(C.POINTER(C.c_float)),
+                                                        T.ctypes.data_as(C.POINTER(C.c_double)), C.byref(rp), device_pointer_array(ip),
+                                                        device_pointer_array(zp), 1 if device else 0))
+        return I, Z
+
+    def render_into(self, pyramids, poses, role=None, config=None, flags=0, **params):
+        """Views of the map straight into existing pyramids of one camera (dvo_hip_map_render_frames): pyramid i becomes the frame that the
+        planes render() gives for its own size and K at poses[i] would make, without the planes leaving the device.  role None: a plain
+        update; "current" / "reference" with config: ingest and prepare in one pass.  flags: _lib.INGEST_NO_RAW_COPY."""
+        who = "KeyframeMap.render_into"
+        n = len(pyramids)
+        if n < 1:
+            raise ValueError("%s: no pyramids" % who)
+        T = _render_poses(poses, n, who)
+        for p in pyramids:
+            if p.ctx is not self.ctx:
+                raise ValueError("%s: the pyramids belong to another context than the map" % who)
+            if p.camera is not pyramids[0].camera:
+                raise ValueError("%s: the pyramids of one call share a camera" % who)
+            if getattr(p, "_lens", None) is not None or getattr(p, "_depth_rig", None) is not None:
+                raise ValueError("%s: a pyramid that carries a lens or a depth rig takes raw sensor planes, not rendered ones" % who)
+        if int(flags) & _lib.INGEST_DEFER:
+            raise ValueError("%s: a render cannot be deferred" % who)
+        rp = render_params_struct(**params)
+        r, cfg = _colour_call_args(pyramids, role, config)
+        self.ctx.check(self.ctx._lib.dvo_hip_map_render_frames(self.ctx.ptr, self.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)),
+                                                               C.byref(rp), r, cfg, int(flags)))
 
     def close(self):
         if getattr(self, "ptr", None) and self.ctx.ptr:

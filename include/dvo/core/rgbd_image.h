@@ -314,11 +314,23 @@ class RgbdImagePyramid {
     dvo_hip_frame* one[1] = {frame_};
     if (dvo_hip_check(ctx_, dvo_hip_frames_update_f32_as_ex(ctx_, 1, one, i, 0, z, 0, 1.0f, -1, nullptr, 0u), "dvo_hip_frames_update_f32_as_ex"))
       dvo_hip_check(ctx_, dvo_hip_upload_wait(ctx_), "dvo_hip_upload_wait");
+    refreshMirrors(has_lens_ || has_rig_);
+  }
+  // the device frame's pixels were replaced on the device (PointCloudAggregator::renderInto): the host matrices are dropped, every
+  // level is mirrored from the device like the levels above 0
+  void deviceFrameChanged() {
+    intensity_ = dvo::compat::ImageMat();
+    depth_ = dvo::compat::ImageMat();
+    refreshMirrors(true);
+  }
+
+ private:
+  // after new pixels: raw_planes = level 0 is not the caller's matrices
+  void refreshMirrors(const bool raw_planes) {
     explicit_levels_ = 0u;   // (new pixels: the device dropped every accepted set)
     for (size_t l = 0; l < levels_.size(); ++l) {
       RgbdImage& image = *levels_[l];
       unsigned had = 0u;
-      const bool raw_planes = has_lens_ || has_rig_;
       if ((l > 0 || raw_planes) && !dvo::compat::image_empty(image.intensity)) had |= RgbdImage::MirrorPlanes;
       if (!dvo::compat::image_empty(image.intensity_dx)) had |= RgbdImage::MirrorDerivatives;
       if (image.pointcloud.cols() > 0) had |= RgbdImage::MirrorPointCloud;
@@ -333,6 +345,8 @@ class RgbdImagePyramid {
       if (had != 0u && RgbdImage::hostMirrors()) image.syncHostMirrors(had);
     }
   }
+
+ public:
   double timestamp() const { return levels_.empty() ? timestamp_ : levels_[0]->timestamp; }   // rgbd_image.cpp: level(0).timestamp
   void timestamp(double t) { timestamp_ = t; for (size_t l = 0; l < levels_.size(); ++l) levels_[l]->timestamp = t; }
 

@@ -6,6 +6,8 @@
 // the same subset in ONE launch and returns one point per voxel, sorted by voxel key.  An empty aggregator returns one default point,
 // as the reference does.  The voxel's point is the exact centroid quantised to leaf / 1024 -- NOT PCL's ApproximateVoxelGrid, whose
 // output depends on the order of insertion.
+// Not in the reference: render() and renderInto() give the map built last as a model view -- an RgbdImagePyramid seen from a pose
+// (include/dvo_hip.h, dvo_hip_map_render / dvo_hip_map_render_frames) -- that a DenseTracker can align a new frame against.
 #pragma once
 
 #include <algorithm>
@@ -87,6 +89,37 @@ class PointCloudAggregator {
       cloud->intensity[i] = p[3];
     }
     return cloud;
+  }
+
+  // A view of the map build() made last, as a pyramid of `camera` seen from `pose` (camera -> world): intensity 0 and depth NaN where
+  // the map shows nothing.  The planes come to the host once, as the pyramid's own matrices.  Null before the first build().
+  dvo::core::RgbdImagePyramidPtr render(dvo::core::RgbdCameraPyramid& camera, const dvo::compat::Affine3d& pose,
+                                        const dvo_hip_render_params& params = dvo_hip_render_params_default()) {
+    if (!map_) return dvo::core::RgbdImagePyramidPtr();
+    const dvo::core::RgbdCamera& c0 = camera.level(0);
+    const int w = int(c0.width()), h = int(c0.height());
+    const float K[4] = {c0.intrinsics().fx(), c0.intrinsics().fy(), c0.intrinsics().ox(), c0.intrinsics().oy()};
+    double T[16];
+    dvo::compat::affine_to_rowmajor(pose, T);
+    dvo::compat::ImageMat I = dvo::compat::image_create(h, w), Z = dvo::compat::image_create(h, w);
+    float* i[1] = {dvo::compat::image_ptr_mut(I)};
+    float* z[1] = {dvo::compat::image_ptr_mut(Z)};
+    if (!dvo::core::dvo_hip_check(ctx_, dvo_hip_map_render(ctx_, map_, 1, w, h, K, T, &params, i, z, 0), "dvo_hip_map_render"))
+      return dvo::core::RgbdImagePyramidPtr();
+    dvo::core::DeviceContext::Scope scope(ctx_);   // (the pyramid belongs to the map's context)
+    return camera.create(I, Z);
+  }
+  // The streaming form: the view goes straight into `pyramid`'s existing device frame (its own size and intrinsics), without leaving
+  // the device; the pyramid then behaves as after RgbdImagePyramid::update() with the rendered planes.
+  bool renderInto(dvo::core::RgbdImagePyramid& pyramid, const dvo::compat::Affine3d& pose,
+                  const dvo_hip_render_params& params = dvo_hip_render_params_default()) {
+    if (!map_ || pyramid.device_context() != ctx_) return false;
+    double T[16];
+    dvo::compat::affine_to_rowmajor(pose, T);
+    dvo_hip_frame* one[1] = {pyramid.device_frame()};
+    if (!dvo::core::dvo_hip_check(ctx_, dvo_hip_map_render_frames(ctx_, map_, 1, one, T, &params, -1, 0, 0u), "dvo_hip_map_render_frames")) return false;
+    pyramid.deviceFrameChanged();
+    return true;
   }
 
  private:

@@ -514,6 +514,77 @@ int dvo_hip_map_extract(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_point
 int dvo_hip_frames_world_points(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses /* n x 16 */,
                                 int level, float min_depth, float max_depth, float* const* out, int out_on_device);
 
+/* ---- views of the keyframe map: model images to track against ---------------------------------------------------------------------------
+ * Not in the reference, which only draws its map in a PCL window.  The map is projected into a pinhole camera at a pose, the nearest
+ * surface per pixel, and comes back as tight float planes I (0..255) and Z (metres, NaN = hole) -- the planes the float ingest above
+ * takes ("a filtered, rendered or predicted depth image").  With them a caller tracks a frame against the fused model instead of one
+ * noisy keyframe (with the parameters "tracking" below names, not the defaults), checks a loop closure against the model, tests a new depth image for outliers, or looks at the map from any pose
+ * without hauling a cloud to the host.
+ *   view         width, height, K = {fx, fy, ox, oy} and a pose T = [R | t] (camera -> world, the row-major 4 x 4 double of
+ *                dvo_hip_result::transformation, as everywhere in the map API); its inverse (R^T, -R^T t) is formed once per view in
+ *                double and rounded to float once.
+ *   source       every voxel of the map with min_points <= n <= 2^20 points; its record {x, y, z, I} is exactly what
+ *                dvo_hip_map_extract reports.  p = R^T P - R^T t; the voxel is skipped unless p.z is finite and > 0 and lies within
+ *                [min_depth, max_depth] (0 and +INFINITY: the range is off).  u' = fx p.x / p.z + ox, v' = fy p.y / p.z + oy.
+ *   footprint    a flat square of the voxel's size times `splat`: hx = splat * 0.5 * leaf * fx / p.z (hy with fy); the voxel covers
+ *                the pixel centres u in [ceil(u' - hx), floor(u' + hx)], v likewise; an axis on which that range is empty takes the one
+ *                nearest pixel floor(u' + 0.5).  Each range is then cut to at most max_splat pixels centred on the nearest pixel and
+ *                clipped to the image.  splat is a float in (0, 4], max_splat an odd integer in 1 .. 15.
+ *   z-buffer     per pixel the minimum of uint64(bits(p.z)) << 32 | bits(max(I, 0)) over the voxels that cover it: the nearest voxel,
+ *                and of voxels at the same depth the one with the LOWER intensity.  A minimum over integers: the planes are the same BIT
+ *                FOR BIT whatever order the device visits the voxels in and whatever order the map was filled in -- and equal to the
+ *                host build of dvo_slam_amd/csrc/map_render.h, where the operation order of all of this is fixed.
+ *   planes       a pixel no voxel covers is a hole: Z = NaN (0x7FC00000), I = 0.  Else Z = p.z of the winning voxel and I its intensity.
+ *                The depth is constant across a footprint (no surface normal), a foreground silhouette grows by up to splat * leaf / 2,
+ *                and nothing fills holes.  With the default splat (2) a fronto-parallel surface whose voxels are all occupied has no
+ *                hole as long as 2 hx + 1 <= max_splat, wherever the centroids lie inside their voxels.
+ *   tracking     the defaults favour a view without holes, NOT tracking: grown silhouettes put foreground depth on background pixels,
+ *                and where near objects stand before a far background that misleads the alignment.  On the project's 128 x 96 scene
+ *                (objects at 0.3 m before a background metres away, leaf 0.02; profiles/map_render.md) a frame aligned against the
+ *                default view ends 0.054 from the true relative pose (twist, max-abs) where the keyframe itself gives 0.0089 and the
+ *                motion is 0.021; with max_splat = 1 the view gives 0.0088, with splat = 1 and min_depth = 0.6 0.0071.  For model
+ *                views to track against use max_splat = 1 (one pixel per voxel: needs a leaf of about a pixel or less at the depths
+ *                seen) or a splat <= 1 with a depth range that drops the near field.
+ *   streams      a render runs on the context's main stream, behind every insert and clear of the map (they run there too), and
+ *                carries out every recorded ingest first, as dvo_hip_map_insert does.  dvo_hip_map_render reads nothing but the
+ *                table, which only the main stream writes, so unlike an insert it makes no wait on the build stream.  The z-buffers are scratch of the context, grown
+ *                on demand and reused.  dvo_hip_map_render to HOST planes returns when they are complete; to DEVICE planes it returns
+ *                at once and the planes are ordered on the context's stream (dvo_hip_context_stream).  dvo_hip_map_render_frames makes
+ *                the build stream wait for the render and ingests there: the frames are ordered like after any other device ingest.
+ *   refusals     DVO_HIP_ERR_INVALID, nothing launched, nothing changed, no counter moved: a null or foreign map, frame, pose or
+ *                output; n <= 0; a size that is not positive, above 2^24 on a side or above 2^31 - 1 pixels for the views of one
+ *                call; a K that is not finite or has fx or fy <= 0; splat outside (0, 4]; max_splat even or outside 1 .. 15;
+ *                min_points of 0; min_depth > max_depth or a NaN bound; a reserved field that is not 0; a device plane that is not
+ *                16-byte aligned; for dvo_hip_map_render_frames also DVO_HIP_INGEST_DEFER, frames of differing cameras, and a frame
+ *                that carries a lens or a depth rig (the planes are rectified and registered already).
+ *   cost         profiles/map_render.md: 8 B per pixel filled, 8 B per slot and 32 B per voxel read, one 8-byte atomic per covered
+ *                pixel, 16 B per pixel resolved; per VIEW, so 16 views cost 16 times one.  Counter "map_renders" counts views. */
+typedef struct {
+  float min_depth, max_depth; /* of p.z; 0 and +INFINITY: off */
+  float splat;                /* footprint in voxel sizes, (0, 4] */
+  int32_t max_splat;          /* pixels per axis at most: odd, 1 .. 15 */
+  uint32_t min_points;        /* voxels with fewer points are not drawn; >= 1 */
+  uint32_t reserved[3];       /* 0 */
+} dvo_hip_render_params;
+/* min_depth 0, max_depth +INFINITY, splat 2, max_splat 7, min_points 1 */
+dvo_hip_render_params dvo_hip_render_params_default(void);
+/* n_views views of width x height under K, view i at poses[16 * i ..]: plane I into intensity_out[i], Z into depth_out[i], width *
+ * height floats each, tight; host arrays, or device arrays (16-byte aligned) with out_on_device.  params NULL: the defaults. */
+int dvo_hip_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float K[4],
+                       const double* poses /* n x 16 */, const dvo_hip_render_params* params, float* const* intensity_out,
+                       float* const* depth_out, int out_on_device);
+/* The same straight into frames: frame i's own level-0 size and K are view i (all frames of a call share a camera, as the ingest
+ * demands), and the rendered planes go through the float-depth device ingest -- the code path of dvo_hip_frames_update_f32_device_as_ex
+ * with depth_scale 1; role, cfg and DVO_HIP_INGEST_NO_RAW_COPY mean what they mean there, DVO_HIP_INGEST_DEFER is refused.
+ * Afterwards a frame is, bit for bit, a frame that was fed the planes dvo_hip_map_render gives for the same view. */
+int dvo_hip_map_render_frames(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames,
+                              const double* poses /* n x 16 */, const dvo_hip_render_params* params, int role, const dvo_hip_config* cfg,
+                              unsigned flags);
+/* measurement (scripts/map_render_rate.py): renders the views `reps` times into scratch planes of the context with HIP events around each
+ * kernel; ms[0..2] = the medians of k_render_fill, k_map_render and k_render_resolve in milliseconds.  Counts nothing. */
+int dvo_hip_time_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float K[4],
+                            const double* poses /* n x 16 */, const dvo_hip_render_params* params, int reps, float ms[3]);
+
 /* ---- the hot path --------------------------------------------------------------------------- */
 /* DenseTracker::match(RgbdImagePyramid& reference, RgbdImagePyramid& current, Result&)
  * (dvo_core/src/dense_tracking.cpp:123-376).  `levels`/`iters` may be NULL (no statistics).
@@ -749,6 +820,7 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value);
  * "map_inserts" (frames dvo_hip_map_insert has launched into a map of this context), "map_points" (the points those maps took) and
  * "map_dropped" (the points they dropped for want of a slot; a call that drops any returns DVO_HIP_ERR_CAPACITY).  Refused calls count
  * nothing, dvo_hip_map_clear resets none of them,
+ * "map_renders" (views dvo_hip_map_render and dvo_hip_map_render_frames have rendered; a refused call counts nothing),
  * "warmup_wait_us" (the longest of the nine stream waits dvo_hip_context_create makes on trivial commands to warm up the runtime's wait
  * path, in microseconds: the first GPU process on a fresh box has been seen to spend 14-24 ms in its first wait),
  * "host_batches" and "host_ns_prepare" / "host_ns_enqueue" / "host_ns_wait" / "host_ns_finish" (nanoseconds the calling thread spent
