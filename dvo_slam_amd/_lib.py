@@ -71,7 +71,7 @@ class MapStats(C.Structure):
     """struct dvo_hip_map_stats: the statistics of a keyframe map (dvo_hip_map_stats)."""
     _fields_ = [("occupied", C.c_uint64), ("points", C.c_uint64), ("dropped", C.c_uint64), ("out_of_range", C.c_uint64),
                 ("unusable", C.c_uint64), ("over_limit", C.c_uint64), ("capacity", C.c_uint64), ("updates", C.c_uint64),
-                ("reserved", C.c_uint64 * 8)]
+                ("vacant", C.c_uint64), ("removed", C.c_uint64), ("unmatched", C.c_uint64), ("reserved", C.c_uint64 * 5)]
 
 
 class RenderParams(C.Structure):
@@ -98,7 +98,7 @@ EXPORTS = [
     "dvo_hip_frames_set_lens", "dvo_hip_frames_clear_lens",
     "dvo_hip_frames_set_depth_rig", "dvo_hip_frames_clear_depth_rig",
     "dvo_hip_map_create", "dvo_hip_map_destroy", "dvo_hip_map_clear", "dvo_hip_map_insert", "dvo_hip_map_stats", "dvo_hip_map_extract",
-    "dvo_hip_frames_world_points",
+    "dvo_hip_frames_world_points", "dvo_hip_map_remove", "dvo_hip_map_move", "dvo_hip_map_rehash",
     "dvo_hip_render_params_default", "dvo_hip_map_render", "dvo_hip_map_render_frames", "dvo_hip_time_map_render",
 ]
 
@@ -217,6 +217,10 @@ def lib():
         L.dvo_hip_map_stats.argtypes = [vp, vp, C.POINTER(MapStats)]
         L.dvo_hip_map_extract.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
         L.dvo_hip_frames_world_points.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.c_int, C.c_float, C.c_float, C.POINTER(vp), C.c_int]
+    if hasattr(L, "dvo_hip_map_remove"):   # (likewise: an older build's map can only grow)
+        L.dvo_hip_map_remove.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_double), C.c_int, C.c_float, C.c_float]
+        L.dvo_hip_map_move.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_float, C.c_float]
+        L.dvo_hip_map_rehash.argtypes = [vp, vp, C.c_size_t]
     if hasattr(L, "dvo_hip_map_render"):   # (likewise: an older build renders no views)
         dp, rp = C.POINTER(C.c_double), C.POINTER(RenderParams)
         L.dvo_hip_render_params_default.argtypes = []

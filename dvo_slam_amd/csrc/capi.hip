@@ -391,6 +391,7 @@ struct dvo_hip_context {
   long long lens_ingests = 0;      // frames rectified at ingest (dvo_hip_frames_set_lens), counter "lens_ingests"
   long long depth_registrations = 0;   // frames whose depth was registered at ingest (dvo_hip_frames_set_depth_rig), counter "depth_registrations"
   long long map_inserts = 0, map_points = 0, map_dropped = 0;   // frames / points a keyframe map took, points it dropped (dvo_hip_map_insert); counters of the same names
+  long long map_removes = 0, map_rehashes = 0;   // frames subtracted from a keyframe map (dvo_hip_map_remove, dvo_hip_map_move), tables rebuilt (dvo_hip_map_rehash); counters of the same names
   long long map_renders = 0;       // views rendered out of a keyframe map (dvo_hip_map_render, dvo_hip_map_render_frames), counter "map_renders"
   // Option "defer_ingest": a batched re-ingest (dvo_hip_frames_update_raw_device_as) is only recorded, and carried out by the next
   // dvo_hip_match_batch right behind the first launches of its first level (or by whatever entry point comes first).  A streaming

@@ -7,9 +7,10 @@ struct dvo_hip_map {
   float leaf = 0.0f;
   size_t capacity = 0;                 // slots, a power of two
   DevBuf slots, counters;
-  unsigned long long candidates = 0, dropped = 0;   // kMapCntCandidates, kMapCntDropped as last read back (zero after a clear)
+  // kMapCntCandidates, kMapCntDropped and kMapCntUnmatched as last read back (zero after a clear)
+  unsigned long long candidates = 0, dropped = 0, unmatched = 0;
 };
-static_assert(sizeof(struct dvo_hip_map_stats) == 128 && offsetof(struct dvo_hip_map_stats, reserved) == 64, "dvo_hip_map_stats: 8 fields and 8 reserved words");
+static_assert(sizeof(struct dvo_hip_map_stats) == 128 && offsetof(struct dvo_hip_map_stats, reserved) == 88, "dvo_hip_map_stats: 11 fields and 5 reserved words");
 
 namespace {
 
@@ -24,7 +25,7 @@ MapTable map_table(const dvo_hip_map* map) {
 
 // frames, poses, level and depth range of a keyframe-map call; `who` names the entry point in the error text
 int check_map_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float min_depth,
-                     float max_depth, const char* who) {
+                     float max_depth, const char* who, int entries_per_frame = 1) {
   if (!ctx || n_frames < 1 || !frames || !poses) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
   if (!(min_depth <= max_depth)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "need min_depth <= max_depth (no NaN)");
   long long blocks = 0;
@@ -34,23 +35,33 @@ int check_map_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* f
     if (std::find(ctx->cameras.begin(), ctx->cameras.end(), f->cam) == ctx->cameras.end())
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame of another context");
     if (level < 0 || level >= f->levels) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame does not have that level");
-    blocks += (static_cast<long long>(f->lv[level].w) * f->lv[level].h + 255) / 256;
+    blocks += entries_per_frame * ((static_cast<long long>(f->lv[level].w) * f->lv[level].h + 255) / 256);
   }
   if (blocks > 0x7fffffffll) return fail(ctx, DVO_HIP_ERR_INVALID, who, "too many pixels for one call");
   return DVO_HIP_OK;
 }
 
+// one entry of a launch's frame table: a frame under a pose, added (+1) or -- dvo_hip_map_remove, dvo_hip_map_move -- subtracted (-1)
+struct MapEntry {
+  dvo_hip_frame* frame;
+  MapPose pose;
+  int sign;
+  float* out;                          // MapFrame::out (k_world_points), else null
+};
+
 // The frame table of one launch on the main stream: the {I, Z} pairs of `level` come from plane C where the frame holds it, else from the
-// taps A (built now where missing: what dvo_hip_frame_download_plane reads planes 0 and 1 from).  outs (may be null): MapFrame::out.
-int upload_map_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float* const* outs,
-                      int* total_blocks) {
-  int rc = wait_for_build(ctx, n_frames, frames);
+// taps A (built now where missing: what dvo_hip_frame_download_plane reads planes 0 and 1 from).  A frame may stand in several entries.
+int upload_map_entries(dvo_hip_context* ctx, const std::vector<MapEntry>& entries, int level, int* total_blocks) {
+  std::vector<dvo_hip_frame*> frames;
+  for (const MapEntry& e : entries)
+    if (std::find(frames.begin(), frames.end(), e.frame) == frames.end()) frames.push_back(e.frame);
+  int rc = wait_for_build(ctx, int(frames.size()), frames.data());
   if (rc != DVO_HIP_OK) return rc;
   // the taps of the frames that hold neither flavour at this level, one ensure_roles per camera (it takes frames of one camera)
   std::vector<dvo_hip_frame*> missing;
-  for (int i = 0; i < n_frames; ++i) {
-    const FrameLevel& L = frames[i]->lv[level];
-    if (!((L.cur_have & kCurC) && L.C) && !(L.cur_have & kCurAB)) missing.push_back(frames[i]);
+  for (dvo_hip_frame* f : frames) {
+    const FrameLevel& L = f->lv[level];
+    if (!((L.cur_have & kCurC) && L.C) && !(L.cur_have & kCurAB)) missing.push_back(f);
   }
   while (!missing.empty()) {
     std::vector<dvo_hip_frame*> group, rest;
@@ -59,25 +70,26 @@ int upload_map_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* 
     if (rc != DVO_HIP_OK) return rc;
     missing.swap(rest);
   }
-  std::vector<MapFrame> host(size_t(n_frames) + 1);
+  std::vector<MapFrame> host(entries.size() + 1);
   int blocks = 0;
-  for (int i = 0; i < n_frames; ++i) {
-    const dvo_hip_frame* f = frames[i];
+  for (size_t i = 0; i < entries.size(); ++i) {
+    const dvo_hip_frame* f = entries[i].frame;
     const FrameLevel& L = f->lv[level];
-    MapFrame& m = host[size_t(i)];
+    MapFrame& m = host[i];
     const bool from_c = (L.cur_have & kCurC) && L.C;
     m.iz = from_c ? reinterpret_cast<const float*>(L.C) : reinterpret_cast<const float*>(L.A);
     m.stride = from_c ? 2 : 4;
-    m.out = outs ? outs[i] : nullptr;
-    m.pose = map_pose_prepare(poses + size_t(i) * 16);
+    m.out = entries[i].out;
+    m.pose = entries[i].pose;
     std::memcpy(m.K, f->cam->K[level], sizeof m.K);
     m.w = L.w;
     m.h = L.h;
     m.first_block = blocks;
+    m.sign = entries[i].sign;
     blocks += (L.w * L.h + 255) / 256;
   }
-  std::memset(&host[size_t(n_frames)], 0, sizeof(MapFrame));
-  host[size_t(n_frames)].first_block = blocks;
+  std::memset(&host[entries.size()], 0, sizeof(MapFrame));
+  host[entries.size()].first_block = blocks;
   const size_t bytes = host.size() * sizeof(MapFrame);
   DVO_HIP_TRY(ctx, ctx->map_tbl.reserve(bytes));
   DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->map_tbl.p, host.data(), bytes));
@@ -85,12 +97,22 @@ int upload_map_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* 
   return DVO_HIP_OK;
 }
 
-// (only k_map_insert moves the candidates and the dropped points, and every insert ends with this read: the map's copy of them is current)
+// ... of n frames under poses[16 * i ..], all added.  outs (may be null): MapFrame::out.
+int upload_map_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float* const* outs,
+                      int* total_blocks) {
+  std::vector<MapEntry> entries;
+  for (int i = 0; i < n_frames; ++i) entries.push_back(MapEntry{frames[i], map_pose_prepare(poses + size_t(i) * 16), 1, outs ? outs[i] : nullptr});
+  return upload_map_entries(ctx, entries, level, total_blocks);
+}
+
+// (only k_map_insert moves the candidates, the dropped and the unmatched points, and every insert, remove and move ends with this read:
+// the map's copy of them is current)
 int read_map_counters(dvo_hip_context* ctx, dvo_hip_map* map, unsigned long long out[kMapCounters]) {
   DVO_HIP_TRY(ctx, hipMemcpyAsync(out, map->counters.p, sizeof(unsigned long long) * kMapCounters, hipMemcpyDeviceToHost, ctx->stream));
   DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   map->candidates = out[kMapCntCandidates];
   map->dropped = out[kMapCntDropped];
+  map->unmatched = out[kMapCntUnmatched];
   return DVO_HIP_OK;
 }
 
@@ -151,7 +173,7 @@ int dvo_hip_map_clear(dvo_hip_context* ctx, dvo_hip_map* map) {
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   launch_map_clear(ctx->stream, map_table(map));
   DVO_HIP_TRY(ctx, hipGetLastError());
-  map->candidates = map->dropped = 0;
+  map->candidates = map->dropped = map->unmatched = 0;
   return DVO_HIP_OK;
 }
 
@@ -179,6 +201,126 @@ int dvo_hip_map_insert(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo
   return DVO_HIP_OK;
 }
 
+namespace {
+
+// dvo_hip_map_remove (poses_new null) and dvo_hip_map_move: one launch of k_map_insert over signed entries
+int map_update(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses_old, const double* poses_new,
+               bool move, int level, float min_depth, float max_depth, const char* who) {
+  int rc = check_map(ctx, map, who);
+  if (rc == DVO_HIP_OK) rc = check_map_frames(ctx, n_frames, frames, poses_old, level, min_depth, max_depth, who, move ? 2 : 1);
+  if (rc != DVO_HIP_OK) return rc;
+  if (move && !poses_new) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  if (map->dropped != 0)
+    return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map has dropped points since its last clear or rehash: what it holds of a frame is not known (dvo_hip_map_rehash into a larger table, or dvo_hip_map_clear)");
+  std::vector<MapEntry> entries;
+  int removes = 0, inserts = 0;
+  for (int i = 0; i < n_frames; ++i) {
+    const MapPose from = map_pose_prepare(poses_old + size_t(i) * 16);
+    if (move) {
+      const MapPose to = map_pose_prepare(poses_new + size_t(i) * 16);
+      if (std::memcmp(&from, &to, sizeof from) == 0) continue;   // (the same twelve floats: the same points, nothing to do)
+      entries.push_back(MapEntry{frames[i], from, -1, nullptr});
+      entries.push_back(MapEntry{frames[i], to, 1, nullptr});
+      ++inserts;
+    } else {
+      entries.push_back(MapEntry{frames[i], from, -1, nullptr});
+    }
+    ++removes;
+  }
+  if (entries.empty()) return DVO_HIP_OK;
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const unsigned long long candidates_before = map->candidates, dropped_before = map->dropped, unmatched_before = map->unmatched;
+  unsigned long long after[kMapCounters];
+  int blocks = 0;
+  rc = upload_map_entries(ctx, entries, level, &blocks);
+  if (rc != DVO_HIP_OK) return rc;
+  launch_map_update(ctx->stream, ctx->map_tbl.as<MapFrame>(), int(entries.size()), blocks, map_table(map), min_depth, max_depth);
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  rc = read_map_counters(ctx, map, after);
+  if (rc != DVO_HIP_OK) return rc;
+  const unsigned long long dropped = after[kMapCntDropped] - dropped_before, unmatched = after[kMapCntUnmatched] - unmatched_before;
+  ctx->map_removes += removes;
+  ctx->map_inserts += inserts;
+  ctx->map_points += (long long)(after[kMapCntCandidates] - candidates_before - dropped);
+  ctx->map_dropped += (long long)dropped;
+  if (dropped != 0) return fail(ctx, DVO_HIP_ERR_CAPACITY, who, "the table dropped points (no free slot within the probe bound); the map keeps what it took");
+  if (unmatched != 0) {
+    ctx->err = std::string(who) + ": " + std::to_string(unmatched) +
+               " points found no voxel to leave (not the frame content, level, pose or depth range of the insertion?); the map keeps what it did";
+    return DVO_HIP_ERR_INVALID;
+  }
+  return DVO_HIP_OK;
+}
+
+}  // namespace
+
+int dvo_hip_map_remove(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level,
+                       float min_depth, float max_depth) {
+  DVO_ENTER(ctx);
+  return map_update(ctx, map, n_frames, frames, poses, nullptr, false, level, min_depth, max_depth, "map_remove");
+}
+
+int dvo_hip_map_move(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses_old,
+                     const double* poses_new, int level, float min_depth, float max_depth) {
+  DVO_ENTER(ctx);
+  return map_update(ctx, map, n_frames, frames, poses_old, poses_new, true, level, min_depth, max_depth, "map_move");
+}
+
+int dvo_hip_map_rehash(dvo_hip_context* ctx, dvo_hip_map* map, size_t capacity_slots) {
+  DVO_ENTER(ctx);
+  const int rc0 = check_map(ctx, map, "map_rehash");
+  if (rc0 != DVO_HIP_OK) return rc0;
+  const size_t capacity = capacity_slots ? capacity_slots : map->capacity;
+  if (capacity < 64 || capacity > (size_t(1) << 32) || (capacity & (capacity - 1)) != 0)
+    return fail(ctx, DVO_HIP_ERR_INVALID, "map_rehash: the capacity must be a power of two, 64 .. 2^32 slots (0: as it is)");
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // the second table and its counters: both tables exist during this call only
+  DevBuf slots, counters;
+  hipError_t e = slots.reserve(capacity * sizeof(MapSlot));
+  if (e == hipSuccess) e = counters.reserve(sizeof(unsigned long long) * kMapCounters);
+  unsigned long long was[kMapCounters], now[kMapCounters];
+  if (e == hipSuccess) {
+    MapTable to = map_table(map);
+    to.slots = slots.as<MapSlot>();
+    to.counters = counters.as<unsigned long long>();
+    to.capacity = capacity;
+    launch_map_rehash(ctx->stream, map_table(map), to);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(was, map->counters.p, sizeof was, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(now, counters.p, sizeof now, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  const bool fits = e == hipSuccess && now[kMapCntDropped] == 0;
+  if (fits) {
+    // points is unchanged (what was dropped is forgotten), occupied = the live voxels, the histories are carried over
+    now[kMapCntCandidates] = was[kMapCntCandidates] - was[kMapCntDropped];
+    for (int k : {kMapCntOutOfRange, kMapCntUnusable, kMapCntUpdates, kMapCntRemoving, kMapCntUnmatched}) now[k] = was[k];
+    e = hipMemcpyAsync(counters.p, now, sizeof now, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  }
+  if (e != hipSuccess || !fits) {
+    if (e != hipSuccess) (void)hipStreamSynchronize(ctx->stream);   // (nothing still writes the table that is freed)
+    slots.release();
+    counters.release();
+    if (e != hipSuccess) {
+      ctx->err = std::string("map_rehash: ") + hipGetErrorString(e);
+      return DVO_HIP_ERR_HIP;
+    }
+    ctx->err = "map_rehash: " + std::to_string(now[kMapCntDropped]) + " voxels found no slot in the new table within the probe bound; the map is unchanged";
+    return DVO_HIP_ERR_CAPACITY;
+  }
+  std::swap(map->slots, slots);
+  std::swap(map->counters, counters);
+  slots.release();
+  counters.release();
+  map->capacity = capacity;
+  map->candidates = now[kMapCntCandidates];
+  map->dropped = 0;
+  map->unmatched = now[kMapCntUnmatched];
+  ctx->map_rehashes += 1;
+  return DVO_HIP_OK;
+}
+
 int dvo_hip_map_stats(dvo_hip_context* ctx, dvo_hip_map* map, struct dvo_hip_map_stats* out) {
   DVO_LOCK(ctx);
   const int rc0 = check_map(ctx, map, "map_stats");
@@ -192,13 +334,16 @@ int dvo_hip_map_stats(dvo_hip_context* ctx, dvo_hip_map* map, struct dvo_hip_map
   if (rc != DVO_HIP_OK) return rc;
   std::memset(out, 0, sizeof *out);
   out->occupied = c[kMapCntOccupied];
-  out->points = c[kMapCntCandidates] - c[kMapCntDropped];
+  out->removed = c[kMapCntRemoving] - c[kMapCntUnmatched];
+  out->points = c[kMapCntCandidates] - c[kMapCntDropped] - out->removed;
   out->dropped = c[kMapCntDropped];
   out->out_of_range = c[kMapCntOutOfRange];
   out->unusable = c[kMapCntUnusable];
   out->over_limit = c[kMapCntOverLimit];
   out->capacity = map->capacity;
   out->updates = c[kMapCntUpdates];
+  out->vacant = c[kMapCntVacant];
+  out->unmatched = c[kMapCntUnmatched];
   return DVO_HIP_OK;
 }
 

@@ -40,6 +40,8 @@ int dvo_hip_get_counter(dvo_hip_context* ctx, const char* key, long long* value)
   else if (std::strcmp(key, "depth_rig_table_bytes") == 0) *value = (long long)ctx->rig_tbl.bytes;
   // (the keyframe map, capi_map.inc: frames inserted, points the maps took, points they dropped)
   else if (std::strcmp(key, "map_inserts") == 0) *value = ctx->map_inserts;
+  else if (std::strcmp(key, "map_removes") == 0) *value = ctx->map_removes;
+  else if (std::strcmp(key, "map_rehashes") == 0) *value = ctx->map_rehashes;
   else if (std::strcmp(key, "map_renders") == 0) *value = ctx->map_renders;
   else if (std::strcmp(key, "map_points") == 0) *value = ctx->map_points;
   else if (std::strcmp(key, "map_dropped") == 0) *value = ctx->map_dropped;

@@ -3,7 +3,7 @@
 // of the reference's map building -- AsyncPointCloudBuilder::BuildJob::build (dvo_core/src/visualization/async_point_cloud_builder.cpp:61-110:
 // pose.cast<float>() * image.pointcloud, plus intensity) and PointCloudAggregator::build (point_cloud_aggregator.cpp:74-109: concatenate,
 // then a 1 cm voxel grid) -- with an EXACT per-voxel centroid in place of PCL's ApproximateVoxelGrid.  Shared by the kernels
-// (cloud_map.hip: k_world_points, k_map_insert, k_map_extract, k_map_clear) and the host compiler of the CPU tier (tests/test_cloud_map.py),
+// (cloud_map.hip: k_world_points, k_map_insert, k_map_rehash, k_map_extract, k_map_clear) and the host compiler of the CPU tier (tests/test_cloud_map.py),
 // which is the yardstick the device results are compared with bit for bit: float32 throughout (the extraction alone is double), compiled
 // without contraction (clang: the pragma below; a host compiler: -ffp-contract=off), division correctly rounded on both sides.  Every
 // product, quotient and sum is rounded on its own, left to right as parenthesised.
@@ -28,6 +28,28 @@
 //   x = (double(ix) + (double(sx) / double(n) + 0.5) / 1024.0) * double(leaf)   (y, z likewise);   intensity = double(si) / double(n) / 16.0
 // Each point's offset is truncated to a 1024th of the leaf and the half step is added back, so per axis the result lies within
 // leaf / 2048 of the true centroid of the voxel's points (plus float32 rounding); the intensity within 1 / 32.
+//
+// Removal (dvo_hip_map_remove, the - half of dvo_hip_map_move; k_map_insert over a frame whose sign is -1).  A frame leaves the map by the
+// road it came: usable / out of range / key / q[0..3] of every pixel are computed exactly as at insertion (map_world_point, map_key_of,
+// the same pose cast, level and depth range), and the key is LOOKED UP with the insertion's probe sequence.  A lookup never claims a slot:
+// one that meets an empty slot, or exhausts kMapMaxProbes, leaves the point UNMATCHED -- counted, nothing subtracted.  From a found slot
+// the point is subtracted as whole words: {n, sx} and {sy, sz} take one 64-bit two's-complement add each (map_word, map_negate), si one
+// 32-bit add.  That is the exact inverse of the insertion's three adds, carries between the halves included, so removing what was
+// inserted restores the slot bit for bit -- also for a voxel beyond kMapVoxelMaxPoints, whose low halves have carried into the high ones.
+// Additions and subtractions may interleave within a launch: every field is at all times its old total, minus some of what EARLIER
+// launches added, plus some of the new points -- never negative, so no borrow crosses a half-word.
+// A slot whose n returns to 0 keeps its key.  It is VACANT (map_slot_vacant): skipped by the extraction and by a render (neither is
+// live, map_slot_live), still no stop on anybody's probe path -- keys never leave their slots, so bounded linear probing stays valid
+// without tombstones -- and still counted in `occupied`.  The frame's unusable and out-of-range pixels leave those two counts as well:
+// points, out_of_range and unusable describe the frames the map holds now.
+// PRECONDITION.  Removal is exact only for points the table took, and the caller passes the same frame content, level, pose and depth
+// range as at insertion; a mismatch shows up as unmatched > 0.  A mismatched point that happens to meet a voxel of other points is
+// subtracted from THAT voxel -- the map cannot tell -- and a voxel that loses more than it holds wraps and reads as over the limit.  A map that has dropped points since its last clear or rehash refuses a removal: what was dropped cannot be told
+// from what was taken.
+// Rehash (dvo_hip_map_rehash; k_map_rehash).  A second table of a given capacity (a power of two) takes every LIVE slot of the first with
+// its five sums unchanged; vacant slots stay behind.  Live keys are unique in the old table: whoever claims a slot of the new one (one
+// 64-bit CAS, the same probe sequence and bound) is its only writer and stores the sums plainly.  A record that finds no slot is counted,
+// and the new table replaces the old one only if there was none; else the map is unchanged.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -128,6 +150,14 @@ DVO_HD uint64_t map_hash(uint64_t key, uint64_t capacity) {
   key ^= key >> 33;
   return key & (capacity - 1);
 }
+
+// a slot that holds a voxel; and one whose points have all been removed (the key stays: Removal above)
+DVO_HD bool map_slot_live(uint64_t key, uint32_t n) { return key != kMapEmptyKey && n > 0u; }
+DVO_HD bool map_slot_vacant(uint64_t key, uint32_t n) { return key != kMapEmptyKey && n == 0u; }
+
+// two neighbouring sums as the 64-bit word the table adds them in ({n, sx}: n low; {sy, sz}: sy low), and what to add to take a word back
+DVO_HD uint64_t map_word(uint32_t lo, uint32_t hi) { return uint64_t(lo) | uint64_t(hi) << 32; }
+DVO_HD uint64_t map_negate(uint64_t word) { return uint64_t(0) - word; }
 
 // a voxel's record: out[0..2] the centroid, out[3] the mean intensity
 DVO_HD void map_extract_voxel(uint64_t key, uint32_t n, uint32_t sx, uint32_t sy, uint32_t sz, uint32_t si, float leaf, float out[4]) {

@@ -1,6 +1,7 @@
 // cloud_map.hip -- the keyframe map on the device (cloud_map.h; include/dvo_hip.h, dvo_hip_map_* and dvo_hip_frames_world_points): the
 // {I, Z} pairs of one pyramid level of n keyframes under their poses -> the organised world cloud of every frame (k_world_points), or one
-// voxel-grid map of all of them (k_map_insert into an open-addressing table of integer sums, k_map_extract out of it, k_map_clear).
+// voxel-grid map of all of them (k_map_insert into -- and out of -- an open-addressing table of integer sums, k_map_extract out of it,
+// k_map_rehash into a second table, k_map_clear).
 //
 // Both per-pixel kernels run over frames x pixels in one launch: a lane owns one pixel, a wavefront 64 consecutive pixels in raster order,
 // a workgroup 256; frames of different sizes share the launch, a workgroup finds its frame by bisecting the table's first_block column.
@@ -14,6 +15,12 @@
 // scope).  The probe loop is a `for` over kMapMaxProbes: it never spins and never waits for another lane; a run that finds no slot is
 // counted as dropped.  All sums are integers, so the table is the same bit for bit with and without the folding, in any order of
 // arrival.  DVO_MAP_COMBINE_RUNS=0 builds the plain one-lane-one-point form (profiles/keyframe_map.md has both).
+// The MIXED instantiation of k_map_insert reads a sign per frame (MapFrame::sign; a workgroup, and so a wavefront and every run, lies in
+// one frame): a frame with sign -1 is REMOVED (cloud_map.h, Removal) -- the same classification, keys and run folding, but the leader only
+// looks its key up (a relaxed load per probe, no CAS: an empty slot ends the lookup, the run is unmatched) and adds the two's complement
+// of the three words.  A move of n keyframes is one launch over 2n entries.  The instantiation without MIXED is the pure insert as it
+// was.  k_map_rehash walks the old table like k_map_extract (32 B per slot) and places every live slot in a second, cleared table: the
+// lane that wins the slot's CAS is its only writer (live keys are unique) and stores the 24 bytes of sums with plain vector stores.
 // k_map_extract compacts the occupied slots into the caller's arrays, one atomic add of the active-lane count per wavefront on the
 // output cursor, bounded by max_points; the order of the output is unspecified.  No LDS, no barriers, 256-thread workgroups.
 #include "global_ptr.h"
@@ -29,6 +36,7 @@ namespace dvo_hip {
 namespace {
 
 typedef unsigned GlobalU32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned GlobalU32x2 __attribute__((ext_vector_type(2)));
 
 // the frame that owns workgroup b: first_block is strictly increasing (every frame has at least one pixel), tbl[n_frames] ends the list
 __device__ __forceinline__ int map_frame_of(const MapFrame* __restrict__ tbl, int n_frames, int b) {
@@ -45,6 +53,11 @@ __device__ __forceinline__ void wave_count(unsigned long long* counter, unsigned
   if (lane == 0 && mask != 0) (void)__hip_atomic_fetch_add(counter, (unsigned long long)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ... or, for a frame that is being removed, the count taken back (two's complement: the counter holds what the map's frames added)
+__device__ __forceinline__ void wave_uncount(unsigned long long* counter, unsigned long long mask, int lane) {
+  if (lane == 0 && mask != 0) (void)__hip_atomic_fetch_add(counter, 0ull - (unsigned long long)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 __global__ __launch_bounds__(256) void k_world_points(const MapFrame* __restrict__ tbl, int n_frames, float min_depth, float max_depth) {
 #pragma clang fp contract(off)
   const MapFrame& f = tbl[map_frame_of(tbl, n_frames, int(blockIdx.x))];
@@ -59,12 +72,14 @@ __global__ __launch_bounds__(256) void k_world_points(const MapFrame* __restrict
   *((Global<GlobalF32x4>)global_ptr(f.out) + i) = rec;
 }
 
-template <bool COMBINE>
+// MIXED: the frames carry signs (a remove or a move); without it every frame is inserted and MapFrame::sign is not read
+template <bool COMBINE, bool MIXED>
 __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__ tbl, int n_frames, MapTable m, float min_depth, float max_depth) {
 #pragma clang fp contract(off)
   const MapFrame& f = tbl[map_frame_of(tbl, n_frames, int(blockIdx.x))];
   const int i = (int(blockIdx.x) - f.first_block) * 256 + int(threadIdx.x);
   const int lane = int(threadIdx.x) & 63;
+  const bool minus = MIXED && f.sign < 0;                    // (uniform over the workgroup)
   const bool active = i < f.w * f.h;
   bool unusable = false, out_of_range = false, valid = false;
   unsigned long long key = 0;
@@ -80,9 +95,15 @@ __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__
     key = k;
   }
   const unsigned long long validmask = __ballot(valid);
-  wave_count(m.counters + kMapCntUnusable, __ballot(unusable), lane);
-  wave_count(m.counters + kMapCntOutOfRange, __ballot(out_of_range), lane);
-  wave_count(m.counters + kMapCntCandidates, validmask, lane);
+  if (minus) {
+    wave_uncount(m.counters + kMapCntUnusable, __ballot(unusable), lane);
+    wave_uncount(m.counters + kMapCntOutOfRange, __ballot(out_of_range), lane);
+    wave_count(m.counters + kMapCntRemoving, validmask, lane);
+  } else {
+    wave_count(m.counters + kMapCntUnusable, __ballot(unusable), lane);
+    wave_count(m.counters + kMapCntOutOfRange, __ballot(out_of_range), lane);
+    wave_count(m.counters + kMapCntCandidates, validmask, lane);
+  }
 
   // what this lane adds: {qx | qy << 16}, {qz | n << 16}, qi
   uint32_t a = valid ? q[0] | q[1] << 16 : 0u, b = valid ? q[2] | 1u << 16 : 0u, c = valid ? q[3] : 0u;
@@ -110,23 +131,27 @@ __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__
       unsigned long long* words = reinterpret_cast<unsigned long long*>(slot);
       unsigned long long seen = __hip_atomic_load(words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (seen == kMapEmptyKey) {
+        // a lookup never claims: the key was set by an earlier launch or not at all, and behind an empty slot it cannot lie
+        if (minus) break;
         seen = atomicCAS(words, (unsigned long long)kMapEmptyKey, key);
         if (seen == kMapEmptyKey) { claimed = true; seen = key; }
       }
       if (seen != key) continue;
-      (void)__hip_atomic_fetch_add(words + 1, (unsigned long long)n | (unsigned long long)sx << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      (void)__hip_atomic_fetch_add(words + 2, (unsigned long long)sy | (unsigned long long)sz << 32, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      (void)__hip_atomic_fetch_add(&slot->si, si, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned long long w1 = map_word(n, sx), w2 = map_word(sy, sz);
+      (void)__hip_atomic_fetch_add(words + 1, minus ? map_negate(w1) : w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      (void)__hip_atomic_fetch_add(words + 2, minus ? map_negate(w2) : w2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      (void)__hip_atomic_fetch_add(&slot->si, minus ? 0u - si : si, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       placed = true;
       break;
     }
-    if (!placed) (void)__hip_atomic_fetch_add(m.counters + kMapCntDropped, (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!placed)
+      (void)__hip_atomic_fetch_add(m.counters + (minus ? kMapCntUnmatched : kMapCntDropped), (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   wave_count(m.counters + kMapCntUpdates, __ballot(placed), lane);
   wave_count(m.counters + kMapCntOccupied, __ballot(claimed), lane);
 }
 
-// xyzi == null: count only (occupied slots into the cursor, voxels over the limit)
+// xyzi == null: count only (live slots into the cursor, voxels over the limit, vacant slots)
 __global__ __launch_bounds__(256) void k_map_extract(MapTable m, unsigned long long max_points, float4* __restrict__ xyzi, uint32_t* __restrict__ counts,
                                                      unsigned long long* __restrict__ keys) {
 #pragma clang fp contract(off)
@@ -138,9 +163,10 @@ __global__ __launch_bounds__(256) void k_map_extract(MapTable m, unsigned long l
     const GlobalU32x4 lo = words[0], hi = words[1];         // key | n sx, sy sz si pad
     const unsigned long long key = (unsigned long long)lo.x | (unsigned long long)lo.y << 32;
     const uint32_t n = lo.z;
-    const bool occupied = key != kMapEmptyKey && n > 0;
+    const bool occupied = map_slot_live(key, n);
     const unsigned long long mask = __ballot(occupied);
     wave_count(m.counters + kMapCntOverLimit, __ballot(occupied && n > kMapVoxelMaxPoints), lane);
+    if (!xyzi) wave_count(m.counters + kMapCntVacant, __ballot(map_slot_vacant(key, n)), lane);
     unsigned long long base = 0;
     if (lane == 0 && mask != 0)
       base = __hip_atomic_fetch_add(m.counters + kMapCntCursor, (unsigned long long)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -153,6 +179,38 @@ __global__ __launch_bounds__(256) void k_map_extract(MapTable m, unsigned long l
       if (counts) counts[idx] = n;
       if (keys) keys[idx] = key;
     }
+  }
+}
+
+// every live slot of `from` into `to` (cleared, its counters zero): to's kMapCntOccupied counts the slots claimed, its kMapCntDropped
+// the records that found none within the probe bound
+__global__ __launch_bounds__(256) void k_map_rehash(MapTable from, MapTable to) {
+  const int lane = int(threadIdx.x) & 63;
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x, mask = to.capacity - 1;
+  // (capacity and the stride are multiples of 64: the lanes of a wavefront leave the loop together)
+  for (unsigned long long src = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; src < from.capacity; src += stride) {
+    const auto in = (Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(from.slots + src));
+    const GlobalU32x4 lo = in[0], hi = in[1];               // key | n sx, sy sz si pad
+    const unsigned long long key = (unsigned long long)lo.x | (unsigned long long)lo.y << 32;
+    const bool live = map_slot_live(key, lo.z);
+    bool placed = false;
+    if (live) {
+      unsigned long long at = map_hash(key, to.capacity);
+      for (int p = 0; p < kMapMaxProbes; ++p, at = (at + 1) & mask) {
+        MapSlot* slot = to.slots + at;                        // (at <= capacity - 1: inside the new table)
+        unsigned long long* words = reinterpret_cast<unsigned long long*>(slot);
+        // (every key differs from this one: a slot is this lane's iff its CAS wins it)
+        if (__hip_atomic_load(words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != kMapEmptyKey) continue;
+        if (atomicCAS(words, (unsigned long long)kMapEmptyKey, key) != kMapEmptyKey) continue;
+        const GlobalU32x2 n_sx = {lo.z, lo.w};
+        *(Global<GlobalU32x2>)global_ptr(reinterpret_cast<GlobalU32x2*>(words + 1)) = n_sx;
+        *(Global<GlobalU32x4>)global_ptr(reinterpret_cast<GlobalU32x4*>(words + 2)) = hi;
+        placed = true;
+        break;
+      }
+    }
+    wave_count(to.counters + kMapCntOccupied, __ballot(placed), lane);
+    wave_count(to.counters + kMapCntDropped, __ballot(live && !placed), lane);
   }
 }
 
@@ -179,13 +237,23 @@ void launch_world_points(hipStream_t s, const MapFrame* tbl, int n_frames, int t
 }
 
 void launch_map_insert(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth) {
-  k_map_insert<DVO_MAP_COMBINE_RUNS != 0><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+  k_map_insert<DVO_MAP_COMBINE_RUNS != 0, false><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+}
+
+void launch_map_update(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth) {
+  k_map_insert<DVO_MAP_COMBINE_RUNS != 0, true><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+}
+
+void launch_map_rehash(hipStream_t s, const MapTable& from, const MapTable& to) {
+  k_map_clear<<<dim3(table_grid(to.capacity)), dim3(256), 0, s>>>(to);
+  k_map_rehash<<<dim3(table_grid(from.capacity)), dim3(256), 0, s>>>(from, to);
 }
 
 bool map_insert_combines_runs() { return DVO_MAP_COMBINE_RUNS != 0; }
 
 hipError_t launch_map_extract(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys) {
-  const hipError_t e = hipMemsetAsync(m.counters + kMapCntOverLimit, 0, 2 * sizeof(unsigned long long), s);   // kMapCntOverLimit, kMapCntCursor
+  static_assert(kMapCntCursor == kMapCntOverLimit + 1 && kMapCntVacant == kMapCntOverLimit + 2, "what a pass counts lies together");
+  const hipError_t e = hipMemsetAsync(m.counters + kMapCntOverLimit, 0, 3 * sizeof(unsigned long long), s);
   if (e != hipSuccess) return e;
   k_map_extract<<<dim3(table_grid(m.capacity)), dim3(256), 0, s>>>(m, max_points, xyzi, counts, keys);
   return hipSuccess;

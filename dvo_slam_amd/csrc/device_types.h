@@ -188,9 +188,10 @@ struct DepthRigArgs {
   float depth_scale;
 };
 
-// one frame of a keyframe-map launch (k_world_points, k_map_insert, cloud_map.hip; include/dvo_hip.h, dvo_hip_map_insert): where the {I, Z}
-// pairs of the level lie, the pose and the level's geometry.  Frames of different sizes share a launch: each owns the workgroups
-// first_block .. first_block + ceil(w * h / 256) - 1 (the table ends with one more entry that carries only the launch's block count).
+// one frame of a keyframe-map launch (k_world_points, k_map_insert, cloud_map.hip; include/dvo_hip.h, dvo_hip_map_insert / _remove / _move):
+// where the {I, Z} pairs of the level lie, the pose and the level's geometry.  Frames of different sizes share a launch: each owns the
+// workgroups first_block .. first_block + ceil(w * h / 256) - 1 (the table ends with one more entry that carries only the launch's block
+// count).  A frame may stand in a table twice: a move lists it under its old pose with sign -1 and under its new one with sign +1.
 struct MapFrame {
   const float* iz;                     // pixel i: I at iz[i * stride], Z at iz[i * stride + 1] (plane C: stride 2; the taps A: stride 4)
   float* out;                          // k_world_points: w * h records {P.x, P.y, P.z, I}; unused by k_map_insert
@@ -198,6 +199,7 @@ struct MapFrame {
   float K[4];
   int w, h, stride;
   int first_block;
+  int sign;                            // k_map_insert: +1 the frame's points are added, -1 they are subtracted (cloud_map.h, Removal)
 };
 // the table and the counters of a map as the kernels see them; counters: kMapCnt* (cloud_map.hip)
 struct MapTable {
@@ -211,8 +213,10 @@ struct RenderPlanes {
   float* I;
   float* Z;
 };
+// (kMapCntOverLimit .. kMapCntVacant are what a pass of k_map_extract counts: contiguous, zeroed before every pass.  kMapCntRemoving: the
+// usable points in range of the frames a launch subtracts -- its kMapCntCandidates; kMapCntUnmatched of them found no voxel to leave)
 constexpr int kMapCntCandidates = 0, kMapCntDropped = 1, kMapCntOutOfRange = 2, kMapCntUnusable = 3, kMapCntUpdates = 4, kMapCntOccupied = 5,
-              kMapCntOverLimit = 6, kMapCntCursor = 7, kMapCounters = 8;
+              kMapCntOverLimit = 6, kMapCntCursor = 7, kMapCntVacant = 8, kMapCntRemoving = 9, kMapCntUnmatched = 10, kMapCounters = 11;
 
 // one frame of the caller-selection apply pass (k_apply_selection; include/dvo_hip.h, dvo_hip_frames_set_selection; rule: selection.h)
 struct SelectionApply {

@@ -77,9 +77,14 @@ void launch_depth_register(hipStream_t s, const DepthRigPtrs* tbl, int n_frames,
 // launch_world_points: every frame's organised cloud into MapFrame::out.  launch_map_insert: every usable pixel into the table m (with the
 // wavefront's run folding unless the library was built with DVO_MAP_COMBINE_RUNS=0: map_insert_combines_runs).  launch_map_extract: the
 // occupied slots into xyzi / counts / keys (null: not wanted; xyzi null: count only), at most max_points; zeroes and then sets the
-// counters kMapCntCursor (occupied slots seen) and kMapCntOverLimit.  launch_map_clear: keys empty, sums and all counters zero.
+// counters kMapCntCursor (live slots seen), kMapCntOverLimit and -- counting only -- kMapCntVacant.  launch_map_clear: keys empty, sums
+// and all counters zero.  launch_map_update: launch_map_insert over frames that carry signs (MapFrame::sign): those with -1 are removed.
+// launch_map_rehash: clears `to` (its counters too) and places every live slot of `from` in it; to's kMapCntOccupied and kMapCntDropped
+// (records without a slot) say how that went.
 void launch_world_points(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, float min_depth, float max_depth);
 void launch_map_insert(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth);
+void launch_map_update(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth);
+void launch_map_rehash(hipStream_t s, const MapTable& from, const MapTable& to);
 bool map_insert_combines_runs();
 hipError_t launch_map_extract(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys);
 void launch_map_clear(hipStream_t s, const MapTable& m);

@@ -672,6 +672,18 @@ def world_points_batch(pyramids, poses, level=0, min_depth=0.0, max_depth=float(
     return out
 
 
+def _rehash_capacity(capacity):
+    """the capacity_slots of dvo_hip_map_rehash (None: 0, keep), or ValueError / TypeError"""
+    if capacity is None:
+        return 0
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)):
+        raise TypeError("KeyframeMap.rehash: capacity must be an integer (or None: as it is)")
+    capacity = int(capacity)
+    if not 64 <= capacity <= 1 << 32 or capacity & (capacity - 1):
+        raise ValueError("KeyframeMap.rehash: capacity must be a power of two, 64 .. 2^32")
+    return capacity
+
+
 RENDER_DEFAULTS = dict(min_depth=0.0, max_depth=float("inf"), splat=2.0, max_splat=7, min_points=1)   # dvo_hip_render_params_default
 
 
@@ -761,11 +773,38 @@ class KeyframeMap:
         self.ctx.check(self.ctx._lib.dvo_hip_map_insert(self.ctx.ptr, self.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)),
                                                         int(level), float(min_depth), float(max_depth)))
 
+    def remove(self, pyramids, poses, level=0, min_depth=0.0, max_depth=float("inf")):
+        """The inverse of insert() (dvo_hip_map_remove): the same pyramids -- with the content they had then -- poses, level and depth range
+        take their points out of the map again, exactly.  Raises DvoHipError with code ERR_INVALID if points found no voxel to leave
+        (stats()["unmatched"]) or if the map has dropped points since its last clear() or rehash()."""
+        n, T = _map_frames_args(pyramids, poses, level, min_depth, max_depth, "KeyframeMap.remove")
+        if pyramids[0].ctx is not self.ctx:
+            raise ValueError("KeyframeMap.remove: the pyramids belong to another context than the map")
+        self.ctx.check(self.ctx._lib.dvo_hip_map_remove(self.ctx.ptr, self.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)),
+                                                        int(level), float(min_depth), float(max_depth)))
+
+    def move(self, pyramids, poses_old, poses_new, level=0, min_depth=0.0, max_depth=float("inf")):
+        """After a pose-graph optimisation (dvo_hip_map_move): the pyramids leave the map under poses_old and enter it under poses_new in
+        one launch, bit for bit remove(poses_old) followed by insert(poses_new); a pyramid whose pose stays is skipped."""
+        n, T_old = _map_frames_args(pyramids, poses_old, level, min_depth, max_depth, "KeyframeMap.move")
+        T_new = _map_frames_args(pyramids, poses_new, level, min_depth, max_depth, "KeyframeMap.move")[1]
+        if pyramids[0].ctx is not self.ctx:
+            raise ValueError("KeyframeMap.move: the pyramids belong to another context than the map")
+        dp = C.POINTER(C.c_double)
+        self.ctx.check(self.ctx._lib.dvo_hip_map_move(self.ctx.ptr, self.ptr, n, _handles(pyramids), T_old.ctypes.data_as(dp), T_new.ctypes.data_as(dp),
+                                                      int(level), float(min_depth), float(max_depth)))
+
+    def rehash(self, capacity=None):
+        """Rebuilds the table (dvo_hip_map_rehash) with `capacity` slots, a power of two of at least 64 (None: as many as it has): vacant
+        slots are reclaimed, the voxels keep their sums.  Raises DvoHipError with code ERR_CAPACITY, the map unchanged, if they do not fit."""
+        capacity = _rehash_capacity(capacity)
+        self.ctx.check(self.ctx._lib.dvo_hip_map_rehash(self.ctx.ptr, self.ptr, capacity))
+
     def clear(self):
         self.ctx.check(self.ctx._lib.dvo_hip_map_clear(self.ctx.ptr, self.ptr))
 
     def stats(self):
-        """dict: occupied, points, dropped, out_of_range, unusable, over_limit, capacity, updates"""
+        """dict: occupied, points, dropped, out_of_range, unusable, over_limit, capacity, updates, vacant, removed, unmatched"""
         s = _lib.MapStats()
         self.ctx.check(self.ctx._lib.dvo_hip_map_stats(self.ctx.ptr, self.ptr, C.byref(s)))
         return {name: int(getattr(s, name)) for name, _ in _lib.MapStats._fields_ if name != "reserved"}

@@ -6,7 +6,14 @@
 // the same subset in ONE launch and returns one point per voxel, sorted by voxel key.  An empty aggregator returns one default point,
 // as the reference does.  The voxel's point is the exact centroid quantised to leaf / 1024 -- NOT PCL's ApproximateVoxelGrid, whose
 // output depends on the order of insertion.
-// Not in the reference: render() and renderInto() give the map built last as a model view -- an RgbdImagePyramid seen from a pose
+// Not in the reference: setIncremental(true) keeps the device map between builds and makes it FOLLOW the registered keyframes instead of
+// rebuilding it: build() then issues at most one dvo_hip_map_remove (keyframes that left, or whose pyramid was replaced), one
+// dvo_hip_map_move (keyframes whose pose changed: a pose-graph optimisation) and one dvo_hip_map_insert (new ones) for the difference to
+// what the map holds, and rehashes the table at its capacity when the vacated slots outnumber the live voxels.  All sums are integers,
+// so the cloud is the one the rebuild gives, bit for bit.  It falls back to the rebuild while the every-step-th subsampling is active
+// (step > 1: from 100 keyframes on), when a call reports a lack of capacity or unmatched points, and when the context changed.  A
+// registered pyramid must keep its content while it is in the map (update() it only after remove(), or add() it again afterwards).
+// Also not in the reference: render() and renderInto() give the map built last as a model view -- an RgbdImagePyramid seen from a pose
 // (include/dvo_hip.h, dvo_hip_map_render / dvo_hip_map_render_frames) -- that a DenseTracker can align a new frame against.
 #pragma once
 
@@ -26,7 +33,7 @@ class PointCloudAggregator {
   typedef AsyncPointCloudBuilder::PointCloud PointCloud;
 
   // capacity_slots: the device table (32 bytes per slot); keep it at least four times the voxels of the map
-  explicit PointCloudAggregator(size_t capacity_slots = size_t(1) << 22) : capacity_(capacity_slots), ctx_(0), map_(0) {}
+  explicit PointCloudAggregator(size_t capacity_slots = size_t(1) << 22) : capacity_(capacity_slots), ctx_(0), map_(0), incremental_(false) {}
   ~PointCloudAggregator() {
     if (map_) dvo_hip_map_destroy(ctx_, map_);
   }
@@ -39,6 +46,12 @@ class PointCloudAggregator {
   }
   void remove(const std::string& name) { clouds_.erase(name); }
   size_t size() const { return clouds_.size(); }
+  // off (the default): every build() clears the map and inserts every keyframe.  on: build() updates the map by the difference
+  void setIncremental(bool on) {
+    incremental_ = on;
+    if (!on) held_.clear();
+  }
+  bool incremental() const { return incremental_; }
 
   PointCloud::Ptr build() {
     PointCloud::Ptr cloud(new PointCloud);
@@ -46,6 +59,11 @@ class PointCloudAggregator {
       cloud->push_back_default();
       return cloud;
     }
+    if (incremental_ && clouds_.size() / size_t(50) <= size_t(1)) {
+      dvo_hip_context* now = clouds_.begin()->second.pyramid->device_context();
+      if (map_ && now == ctx_ && !held_.empty() && update()) return extract(cloud);
+    }
+    held_.clear();
     std::vector<dvo_hip_frame*> frames;
     std::vector<double> poses;
     const size_t step = std::max(clouds_.size() / size_t(50), size_t(1));
@@ -68,27 +86,8 @@ class PointCloudAggregator {
     if (!dvo_hip_check(ctx_, dvo_hip_map_clear(ctx_, map_), "dvo_hip_map_clear")) return cloud;
     if (!dvo_hip_check(ctx_, dvo_hip_map_insert(ctx_, map_, int(frames.size()), frames.data(), poses.data(), 0, 0.0f, INFINITY), "dvo_hip_map_insert"))
       return cloud;
-    struct dvo_hip_map_stats stats;
-    if (!dvo_hip_check(ctx_, dvo_hip_map_stats(ctx_, map_, &stats), "dvo_hip_map_stats")) return cloud;
-    const size_t n = size_t(stats.occupied);
-    std::vector<float> xyzi(4 * std::max(n, size_t(1)));
-    std::vector<uint64_t> keys(std::max(n, size_t(1)));
-    size_t got = 0;
-    if (!dvo_hip_check(ctx_, dvo_hip_map_extract(ctx_, map_, n, xyzi.data(), 0, keys.data(), 0, &got), "dvo_hip_map_extract")) return cloud;
-    std::vector<size_t> order(got);
-    std::iota(order.begin(), order.end(), size_t(0));
-    std::sort(order.begin(), order.end(), [&keys](size_t a, size_t b) { return keys[a] < keys[b]; });
-    cloud->resize(got);
-    cloud->width = got;
-    cloud->height = 1;
-    for (size_t i = 0; i < got; ++i) {
-      const float* p = &xyzi[4 * order[i]];
-      cloud->x[i] = p[0];
-      cloud->y[i] = p[1];
-      cloud->z[i] = p[2];
-      cloud->intensity[i] = p[3];
-    }
-    return cloud;
+    if (incremental_ && step == 1) held_ = clouds_;
+    return extract(cloud);
   }
 
   // A view of the map build() made last, as a pyramid of `camera` seen from `pose` (camera -> world): intensity 0 and depth NaN where
@@ -130,10 +129,79 @@ class PointCloudAggregator {
   PointCloudAggregator(const PointCloudAggregator&);
   PointCloudAggregator& operator=(const PointCloudAggregator&);
 
+  // the map's live voxels into `cloud`, sorted by key
+  PointCloud::Ptr extract(PointCloud::Ptr cloud) {
+    using dvo::core::dvo_hip_check;
+    struct dvo_hip_map_stats stats;
+    if (!dvo_hip_check(ctx_, dvo_hip_map_stats(ctx_, map_, &stats), "dvo_hip_map_stats")) return cloud;
+    const size_t n = size_t(stats.occupied - stats.vacant);
+    std::vector<float> xyzi(4 * std::max(n, size_t(1)));
+    std::vector<uint64_t> keys(std::max(n, size_t(1)));
+    size_t got = 0;
+    if (!dvo_hip_check(ctx_, dvo_hip_map_extract(ctx_, map_, n, xyzi.data(), 0, keys.data(), 0, &got), "dvo_hip_map_extract")) return cloud;
+    std::vector<size_t> order(got);
+    std::iota(order.begin(), order.end(), size_t(0));
+    std::sort(order.begin(), order.end(), [&keys](size_t a, size_t b) { return keys[a] < keys[b]; });
+    cloud->resize(got);
+    cloud->width = got;
+    cloud->height = 1;
+    for (size_t i = 0; i < got; ++i) {
+      const float* p = &xyzi[4 * order[i]];
+      cloud->x[i] = p[0];
+      cloud->y[i] = p[1];
+      cloud->z[i] = p[2];
+      cloud->intensity[i] = p[3];
+    }
+    return cloud;
+  }
+
+  // The difference between what the map holds (held_) and what is registered (clouds_, all of it: no subsampling), as at most one
+  // remove, one move and one insert; false: the map is in doubt and is to be rebuilt.
+  bool update() {
+    std::vector<dvo_hip_frame*> gone, moved, fresh;
+    std::vector<double> gone_poses, moved_from, moved_to, fresh_poses;
+    double T[16], U[16];
+    for (std::map<std::string, Entry>::iterator it = held_.begin(); it != held_.end(); ++it) {
+      std::map<std::string, Entry>::iterator now = clouds_.find(it->first);
+      dvo::compat::affine_to_rowmajor(it->second.pose, T);
+      if (now == clouds_.end() || now->second.pyramid != it->second.pyramid) {
+        gone.push_back(it->second.pyramid->device_frame());
+        gone_poses.insert(gone_poses.end(), T, T + 16);
+        continue;
+      }
+      dvo::compat::affine_to_rowmajor(now->second.pose, U);
+      if (std::equal(T, T + 16, U)) continue;
+      moved.push_back(it->second.pyramid->device_frame());
+      moved_from.insert(moved_from.end(), T, T + 16);
+      moved_to.insert(moved_to.end(), U, U + 16);
+    }
+    for (std::map<std::string, Entry>::iterator it = clouds_.begin(); it != clouds_.end(); ++it) {
+      std::map<std::string, Entry>::iterator was = held_.find(it->first);
+      if (was != held_.end() && was->second.pyramid == it->second.pyramid) continue;
+      if (it->second.pyramid->device_context() != ctx_) return false;
+      dvo::compat::affine_to_rowmajor(it->second.pose, T);
+      fresh.push_back(it->second.pyramid->device_frame());
+      fresh_poses.insert(fresh_poses.end(), T, T + 16);
+    }
+    // (a call that fails -- capacity, unmatched points, a map that has dropped points -- leaves the rebuild to put things right)
+    if (!gone.empty() && dvo_hip_map_remove(ctx_, map_, int(gone.size()), gone.data(), gone_poses.data(), 0, 0.0f, INFINITY) != DVO_HIP_OK) return false;
+    if (!moved.empty() &&
+        dvo_hip_map_move(ctx_, map_, int(moved.size()), moved.data(), moved_from.data(), moved_to.data(), 0, 0.0f, INFINITY) != DVO_HIP_OK)
+      return false;
+    if (!fresh.empty() && dvo_hip_map_insert(ctx_, map_, int(fresh.size()), fresh.data(), fresh_poses.data(), 0, 0.0f, INFINITY) != DVO_HIP_OK) return false;
+    held_ = clouds_;
+    struct dvo_hip_map_stats stats;
+    if (dvo_hip_map_stats(ctx_, map_, &stats) != DVO_HIP_OK) return false;
+    if (stats.vacant > stats.occupied - stats.vacant && dvo_hip_map_rehash(ctx_, map_, 0) != DVO_HIP_OK) return false;
+    return true;
+  }
+
   std::map<std::string, Entry> clouds_;
+  std::map<std::string, Entry> held_;   // incremental mode: what the device map holds, as inserted (empty: nothing is known, rebuild)
   size_t capacity_;
   dvo_hip_context* ctx_;
   dvo_hip_map* map_;
+  bool incremental_;
 };
 
 }  // namespace visualization

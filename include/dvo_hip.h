@@ -472,26 +472,34 @@ int dvo_hip_frames_clear_depth_rig(dvo_hip_context* ctx, int n_frames, dvo_hip_f
  *                recorded ingest first (DVO_HIP_INGEST_DEFER), as a match does.  Calls return when their result is complete.
  *   refusals     a null or foreign frame or map, a level a frame does not have, a null pose or output, min_depth > max_depth or NaN:
  *                DVO_HIP_ERR_INVALID, nothing launched, nothing changed.
- *   cost         profiles/keyframe_map.md. */
+ *   updates      the map follows the pose graph without being rebuilt: dvo_hip_map_remove takes a keyframe's points out again,
+ *                dvo_hip_map_move re-poses keyframes (a loop closure) in one launch, dvo_hip_map_rehash reclaims the slots they vacated
+ *                and resizes the table.  All sums are integers filled by integer adds, so subtracting what a keyframe added restores
+ *                the table's words BIT FOR BIT: after a removal the extraction and every render equal those of a map that never held
+ *                the keyframe (dvo_slam_amd/csrc/cloud_map.h, Removal and Rehash).
+ *   cost         profiles/keyframe_map.md, profiles/keyframe_map_update.md. */
 typedef struct dvo_hip_map dvo_hip_map;
 /* (a struct tag beside the function of the same name, like stat(2): `struct dvo_hip_map_stats s; dvo_hip_map_stats(ctx, map, &s);`) */
 struct dvo_hip_map_stats {
-  uint64_t occupied;      /* voxels in the table */
-  uint64_t points;        /* points the table took */
+  uint64_t occupied;      /* slots that hold a key: the voxels in the table, vacant ones included */
+  uint64_t points;        /* points the table holds: those it took less those removed */
   uint64_t dropped;       /* usable points in range that found no slot within the probe bound */
-  uint64_t out_of_range;  /* usable points beyond +-2^20 voxels on some axis */
-  uint64_t unusable;      /* pixels without a usable point */
+  uint64_t out_of_range;  /* usable points beyond +-2^20 voxels on some axis (of the frames the map holds: a removal takes its own back) */
+  uint64_t unusable;      /* pixels without a usable point (likewise) */
   uint64_t over_limit;    /* voxels that hold more than 2^20 points */
   uint64_t capacity;      /* slots */
-  uint64_t updates;       /* slot updates issued: runs of neighbouring pixels that share a voxel go to the table as one */
-  uint64_t reserved[8];   /* 0 */
+  uint64_t updates;       /* slot updates issued, additions and subtractions: runs of neighbouring pixels that share a voxel go to the table as one */
+  uint64_t vacant;        /* slots whose points have all been removed: they keep their key until dvo_hip_map_rehash (occupied - vacant voxels are live) */
+  uint64_t removed;       /* points subtracted by dvo_hip_map_remove / dvo_hip_map_move */
+  uint64_t unmatched;     /* points a removal did not find in the table: nothing was subtracted for them */
+  uint64_t reserved[5];   /* 0 */
 };
 /* capacity_slots is rounded up to a power of two, at least 64 (32 bytes per slot); a leaf that is not finite and > 0 is
  * DVO_HIP_ERR_INVALID.  Keep the table at most a quarter full (dvo_hip_map_stats): probe sequences then stay far below the bound.
  * A map belongs to its context and is destroyed before it. */
 int dvo_hip_map_create(dvo_hip_context* ctx, float leaf, size_t capacity_slots, dvo_hip_map** out);
 void dvo_hip_map_destroy(dvo_hip_context* ctx, dvo_hip_map* map);
-/* every slot empty, every sum and statistic zero (after a pose-graph optimisation: clear, then insert under the new poses) */
+/* every slot empty, every sum and statistic zero (after a pose-graph optimisation there is no need to: dvo_hip_map_move) */
 int dvo_hip_map_clear(dvo_hip_context* ctx, dvo_hip_map* map);
 /* PointCloudAggregator::build's concatenate + filter for n frames (point_cloud_aggregator.cpp:95-106) in one launch: every usable point
  * of level `level` of every frame, under poses[16 * i ..], into the map.  Frames of different sizes and cameras may share a call.
@@ -500,6 +508,31 @@ int dvo_hip_map_clear(dvo_hip_context* ctx, dvo_hip_map* map);
  * dvo_hip_map_extract wait likewise): it drains whatever was queued before it, so it does not belong between pipelined matches. */
 int dvo_hip_map_insert(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses /* n x 16 */,
                        int level, float min_depth, float max_depth);
+/* The inverse of dvo_hip_map_insert: every usable point of level `level` of every frame, under poses[16 * i ..], out of the map again.
+ * The caller passes what it passed to the insertion -- the same frame CONTENT (a frame re-ingested since is another frame), level, pose and
+ * depth range: every point then finds its voxel and is subtracted from it, exactly (integer sums), and the map is, bit for bit in what
+ * dvo_hip_map_extract and dvo_hip_map_render give, the map that never held the frames.  A voxel that loses all its points becomes VACANT:
+ * no longer extracted or rendered, but its slot keeps the key (dvo_hip_map_stats: vacant) until dvo_hip_map_rehash.  A point that does
+ * not find its voxel is UNMATCHED: counted, nothing subtracted; a call that leaves any returns DVO_HIP_ERR_INVALID with the count in
+ * dvo_hip_last_error -- the map keeps what the call did, the statistics say how many.  Streams, waiting and refusals as for
+ * dvo_hip_map_insert, and one more: a map that has DROPPED points since its last clear or rehash does not know what it holds of a
+ * frame and refuses (DVO_HIP_ERR_INVALID, nothing launched, nothing changed). */
+int dvo_hip_map_remove(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses /* n x 16 */,
+                       int level, float min_depth, float max_depth);
+/* After a pose-graph optimisation: the frames leave the map under poses_old and enter it under poses_new, in ONE launch over 2 n
+ * entries -- bit for bit dvo_hip_map_remove(poses_old) followed by dvo_hip_map_insert(poses_new).  A frame whose two poses are equal
+ * once converted to float is left out of the launch (a call in which every frame is returns DVO_HIP_OK and launches nothing).
+ * DVO_HIP_ERR_CAPACITY if the call dropped a point (its insertions can), else DVO_HIP_ERR_INVALID if it left unmatched points, else
+ * DVO_HIP_OK; refusals as for dvo_hip_map_remove. */
+int dvo_hip_map_move(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses_old /* n x 16 */,
+                     const double* poses_new /* n x 16 */, int level, float min_depth, float max_depth);
+/* Rebuilds the table with capacity_slots slots (a power of two, 64 .. 2^32; 0: as many as it has; anything else is
+ * DVO_HIP_ERR_INVALID): every live voxel moves with its sums unchanged, vacant slots are reclaimed.  Afterwards occupied = the live
+ * voxels, vacant = 0, dropped = 0 (a map that dropped points takes removals again; the dropped points themselves stay lost), points
+ * and the other statistics are as before.  DVO_HIP_ERR_CAPACITY if a voxel finds no slot in the new table within the probe bound: the
+ * map is then unchanged.  A second table exists during the call: the old one is freed on success, the new one on failure.  Runs on the
+ * main stream and waits for it, like dvo_hip_map_insert. */
+int dvo_hip_map_rehash(dvo_hip_context* ctx, dvo_hip_map* map, size_t capacity_slots);
 int dvo_hip_map_stats(dvo_hip_context* ctx, dvo_hip_map* map, struct dvo_hip_map_stats* out);
 /* The downsampled cloud (what point_cloud_aggregator.cpp:105-108 returns): one record {x, y, z, intensity} per voxel into xyzi, its point
  * count and key into counts / keys where those are not NULL; host arrays, or device arrays (xyzi 16-byte aligned) with out_on_device.
@@ -817,9 +850,11 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value);
  * "depth_registrations" (frames whose depth plane was registered at ingest because they carry a depth rig,
  * dvo_hip_frames_set_depth_rig; each is also one of "f32_ingests") and "depth_rig_table_bytes" (the size of that pass's pointer table:
  * 0 until the first such frame is ingested),
- * "map_inserts" (frames dvo_hip_map_insert has launched into a map of this context), "map_points" (the points those maps took) and
- * "map_dropped" (the points they dropped for want of a slot; a call that drops any returns DVO_HIP_ERR_CAPACITY).  Refused calls count
- * nothing, dvo_hip_map_clear resets none of them,
+ * "map_inserts" (frames dvo_hip_map_insert and dvo_hip_map_move have launched into a map of this context), "map_points" (the points those
+ * maps took) and "map_dropped" (the points they dropped for want of a slot; a call that drops any returns DVO_HIP_ERR_CAPACITY),
+ * "map_removes" (frames dvo_hip_map_remove and dvo_hip_map_move have launched out of a map; a frame whose pose a move leaves as it is
+ * counts in neither) and "map_rehashes" (tables dvo_hip_map_rehash has replaced).  Refused calls count nothing, dvo_hip_map_clear resets
+ * none of them,
  * "map_renders" (views dvo_hip_map_render and dvo_hip_map_render_frames have rendered; a refused call counts nothing),
  * "warmup_wait_us" (the longest of the nine stream waits dvo_hip_context_create makes on trivial commands to warm up the runtime's wait
  * path, in microseconds: the first GPU process on a fresh box has been seen to spend 14-24 ms in its first wait),
