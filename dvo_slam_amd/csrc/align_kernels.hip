@@ -68,7 +68,7 @@ __global__ __launch_bounds__(kBlock) void k_residual_reduce(
     const int v_r = row0 + k;
     if (k < RPW && col_ok && v_r < g.h) {
       // the reference plane holds {Zsel, I}; the intensity gradient is the clamped central difference of the frame build
-      // (pyramid_kernels.hip::derive_at), recomputed here from the four neighbours
+      // (image_model.h::derive_at), recomputed here from the four neighbours
       const int at = v_r * g.w + u_r;
       const float2 zi = refR[at];
       const float left = refR[at - (u_r > 0 ? 1 : 0)].y, right = refR[at + (u_r < g.w - 1 ? 1 : 0)].y;

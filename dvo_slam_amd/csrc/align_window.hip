@@ -8,7 +8,7 @@
 // image, loads that window of the 8-byte {I, Z} plane ONCE, coalesced, into LDS (256 B per clock), and every lane then reads the
 // 4 x 4 neighbourhood of its tap corner from LDS (12 x ds_read_b64) and derives the four gradient channels itself -- the clamped
 // central differences of rgbd_image.cpp:419-489, same operation order as the frame build, hence the same bits as the stored
-// planes A / B (pyramid_kernels.hip::derive_at).  HBM / L2 traffic of the current frame drops from 24 B to 8 B per pixel (x the
+// planes A / B (image_model.h::derive_at).  HBM / L2 traffic of the current frame drops from 24 B to 8 B per pixel (x the
 // window's halo), the vector L1 sees ~30 B per pixel instead of 120.
 //
 //   phase A  per wavefront: stream its 4 reference rows, project (dense_tracking_impl.cpp:148-203), keep the projection in

@@ -79,8 +79,7 @@ int apply_selection(dvo_hip_context* ctx, hipStream_t stream, int n, dvo_hip_fra
   DVO_HIP_TRY(ctx, table.reserve(bytes));
   DVO_HIP_TRY(ctx, ctx->tables.upload(stream, table.p, host.data(), bytes));
   const CameraGeom* cam = frames[0]->cam;
-  LevelSpan span;
-  apply_selection_span(span, l0, l1, cam->w, cam->h);
+  const LevelSpan span = level_span(l0, l1, cam->w, cam->h, /*pixel_blocks=*/true);
   launch_apply_selection(stream, table.as<SelectionApply>(), int(host.size()), span, cap);
   DVO_HIP_TRY(ctx, hipGetLastError());
   return DVO_HIP_OK;
@@ -456,6 +455,8 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
     f->raw_copy = false;
     f->depth_scale = depth_scale;
     if (!from_raw) continue;
+    if (role == 0) f->lv[0].cur_have = flavor0;
+    if (role == 1) mark_selected(f->lv[0], ithr, dthr);
     if (colour || image_f32) {
       host[i].colour = static_cast<const uint8_t*>(src->planes[i]);
       host[i].colour_pitch = int(src->pitch);
@@ -477,8 +478,6 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
       wide = wide && f32_strips_aligned(host[i].depth_f32, src->depth_pitch) &&
              (image_f32 ? f32_strips_aligned(host[i].colour, src->pitch)
                         : colour ? colour_strips_aligned(host[i].colour, src->pitch, channels) : aligned_to(host[i].grey, 2) && src->pitch % 2 == 0);
-      if (role == 0) f->lv[0].cur_have = flavor0;
-      if (role == 1) mark_selected(f->lv[0], ithr, dthr);
       continue;
     }
     host[i].raw = static_cast<const uint16_t*>(src->depth[i]);
@@ -492,8 +491,6 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
     }
     wide = wide && (colour ? colour_strips_aligned(host[i].colour, src->pitch, channels) : aligned_to(host[i].grey, 4)) &&
            aligned_to(host[i].raw, 8) && aligned_to(staging_grey(f), 4);
-    if (role == 0) f->lv[0].cur_have = flavor0;
-    if (role == 1) mark_selected(f->lv[0], ithr, dthr);
   }
   hipStream_t bs = ctx->build_stream;
   // (one of a few buffers: the one that already holds this very table -- a streaming caller re-ingests the same frame sets from the same
@@ -520,7 +517,7 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
         for (int l = 1; l < built; ++l)
           if ((c_levels >> l & 1) && frames[i]->lv[l].C) frames[i]->lv[l].cur_have |= kCurC;
     }
-    launch_build_from_raw(bs, tbl, n, depth_scale, cam->w[0], cam->h[0], levels, role, wide, ithr, dthr, ctx->opt_build_workgroups, flavor0, c_levels,
+    launch_build_from_raw(bs, tbl, n, depth_scale, cam->w[0], cam->h[0], levels, role, strips, ithr, dthr, ctx->opt_build_workgroups, flavor0, c_levels,
                           channels, ctx->opt_stream_policy != 0, depth_f32);
     if (role == 1) {
       const int rc = apply_selection(ctx, bs, n, frames, 0, 0, ctx->opt_build_workgroups);
@@ -549,6 +546,15 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
   hipStream_t stream = eager ? ctx->build_stream : ctx->stream;
   const int cap = eager ? ctx->opt_build_workgroups : 0;   // planes needed right now are built at full width
   const bool stream_nt = eager && ctx->opt_stream_policy != 0;
+  // What frame f lacks at level l.  Current role: `miss` = the flavours wanted there (plane C only where the camera's frames have one)
+  // that the frame does not hold; reference role: whether its selection stands for these thresholds (miss 0).
+  struct Lack { int miss; bool need; };
+  auto lack_of = [&](const dvo_hip_frame* f, int l) -> Lack {
+    const FrameLevel& L = f->lv[l];
+    if (role != 0) return Lack{0, !ref_ready(L, ithr, dthr)};
+    const int want = (cur_want ? cur_want[l] : kCurAB) & (L.C ? (kCurAB | kCurC) : kCurAB);
+    return Lack{want & ~L.cur_have, (want & ~L.cur_have) != 0};
+  };
   // Every frame is checked before the state of any is touched: a frame ingested straight into a role without a copy of its raw planes
   // (option "keep_raw_copy" 0) has nothing its level 0 could be derived from in another role, and the marks below -- planes "built" --
   // are set while the launches are still being gathered (round-5 advisor finding: the error used to leave earlier frames of the list
@@ -556,11 +562,8 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
   if (l0 == 0)
     for (int i = 0; i < n; ++i) {
       const dvo_hip_frame* f = frames[i];
-      const FrameLevel& L = f->lv[0];
-      if (!f->raw0 || L.cur_have != 0 || f->raw_copy) continue;
-      const int want0 = role == 0 ? (cur_want ? cur_want[0] : kCurAB) & (L.C ? (kCurAB | kCurC) : kCurAB) : 0;
-      const bool need = role == 0 ? want0 != 0 : !ref_ready(L, ithr, dthr);
-      if (need) return fail(ctx, DVO_HIP_ERR_INVALID, "frame has neither sampling planes nor a raw copy at level 0");
+      if (!f->raw0 || f->lv[0].cur_have != 0 || f->raw_copy) continue;
+      if (lack_of(f, 0).need) return fail(ctx, DVO_HIP_ERR_INVALID, "frame has neither sampling planes nor a raw copy at level 0");
     }
   bool launched = false;
   int uploads = 0;                                           // table slices used so far (each launch reads its own)
@@ -585,30 +588,22 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
   // frame that has just been built): ONE launch for all levels (k_derive_levels) instead of a table upload, a counter reset and a
   // launch per level.
   if (l1 > l0) {
-    LevelSpan span;
-    span.l0 = l0; span.l1 = l1;
+    LevelSpan span = level_span(l0, l1, cam->w, cam->h);
     bool uniform = n <= 64;                                                             // (the check below is quadratic; large batches come through the ingest.
     // Round 6: the size test used to FOLLOW the double loop -- 524 288 comparisons per role of a 1024-pair batch, 0.4 ms of the host
     // thread in front of every streaming step's first launch)
     for (int i = 0; i < n && uniform; ++i)
       for (int j = 0; j < i && uniform; ++j) uniform = frames[i] != frames[j];        // (a frame listed twice: the general path skips its second visit)
-    int tiles = 0;
     for (int l = l0; l <= l1 && uniform; ++l) {
-      const int want = role == 0 ? (cur_want ? cur_want[l] : kCurAB) & (frames[0]->lv[l].C ? (kCurAB | kCurC) : kCurAB) : 0;
       int miss_all = -1;
       for (int i = 0; i < n && uniform; ++i) {
-        dvo_hip_frame* f = frames[i];
-        const FrameLevel& L = f->lv[l];
-        const int miss = role == 0 ? want & ~L.cur_have : 0;
-        const bool need = role == 0 ? miss != 0 : !ref_ready(L, ithr, dthr);
-        uniform = need && !(l == 0 && f->raw0) && (role == 1 || L.cur_have == 0) && (miss_all < 0 || miss == miss_all);
-        miss_all = miss;
+        const dvo_hip_frame* f = frames[i];
+        const Lack lack = lack_of(f, l);
+        uniform = lack.need && !(l == 0 && f->raw0) && (role == 1 || f->lv[l].cur_have == 0) && (miss_all < 0 || lack.miss == miss_all);
+        miss_all = lack.miss;
       }
-      span.w[l] = cam->w[l]; span.h[l] = cam->h[l]; span.flavor[l] = miss_all;
-      span.tile0[l] = tiles;
-      tiles += ((cam->w[l] + 63) / 64) * ((cam->h[l] + 15) / 16);
+      span.flavor[l] = miss_all;
     }
-    span.tile0[l1 + 1] = tiles;
     if (uniform) {
       std::vector<FrameBuildPtrs> host(n);
       for (int i = 0; i < n; ++i) fill_build_ptrs(frames[i], host[i]);
@@ -635,7 +630,6 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
     }
   }
   for (int l = l0; l <= l1; ++l) {
-    const int want = role == 0 ? (cur_want ? cur_want[l] : kCurAB) & (frames[0]->lv[l].C ? (kCurAB | kCurC) : kCurAB) : 0;
     // sources, per frame: float planes I / Z (levels >= 1, and level 0 of frames created from float planes); at level 0 of a frame
     // ingested from raw planes: the other flavour of the current role, else the frame's copy of its raw planes
     std::vector<FrameBuildPtrs> from_planes[4], from_raw[4], ab_from_c, c_from_a, ref_from_c;
@@ -645,9 +639,9 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
     for (int i = 0; i < n; ++i) {
       dvo_hip_frame* f = frames[i];
       FrameLevel& L = f->lv[l];
-      const int miss = role == 0 ? want & ~L.cur_have : 0;
-      const bool need = role == 0 ? miss != 0 : !ref_ready(L, ithr, dthr);
-      if (!need) continue;   // also skips the second visit of a frame that is listed twice
+      const Lack lack = lack_of(f, l);
+      const int miss = lack.miss;
+      if (!lack.need) continue;   // also skips the second visit of a frame that is listed twice
       FrameBuildPtrs p;
       fill_build_ptrs(f, p);
       if (l == 0 && f->raw0) {
@@ -692,8 +686,8 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
       if (!from_raw[miss].empty()) {
         int rc = upload(from_raw[miss], &tbl, /*plane_pointers_only=*/false);
         if (rc != DVO_HIP_OK) return rc;
-        launch_build_from_raw(stream, tbl, int(from_raw[miss].size()), raw_scale, cam->w[0], cam->h[0], /*levels=*/1, role, cam->w[0] % 4 == 0, ithr, dthr, cap, miss,
-                              0, 0, stream_nt);
+        launch_build_from_raw(stream, tbl, int(from_raw[miss].size()), raw_scale, cam->w[0], cam->h[0], /*levels=*/1, role,
+                              ingest_strips_supports(cam->w[0], /*wide=*/true), ithr, dthr, cap, miss, 0, 0, stream_nt);
         launched = true;
       }
     }

@@ -2,9 +2,9 @@
 // strip per WAVEFRONT, everything in registers: no LDS, no barriers.
 //
 // Same arithmetic as k_build_from_raw (pyramid_kernels.hip), which remains the path for odd widths and unaligned planes -- the
-// reference's ingest (dvo_core/src/core/surface_pyramid.cpp:65-105), 2x2-mean pyr-down and depth subsampling
-// (dvo_core/src/core/rgbd_image.cpp:38-55, 127-139), clamped central differences (rgbd_image.cpp:419-489) and the selection predicate
-// (dvo_core/src/core/point_selection.cpp:89-152): bit-identical planes.  What changed is how the work is laid out on the machine.
+// reference's ingest (dvo_core/src/core/surface_pyramid.cpp:65-105) and, from image_model.h, the 2x2-mean pyr-down, the depth
+// subsampling, the clamped central differences and the selection predicate: bit-identical planes.  What differs is how the work is
+// laid out on the machine.
 // k_build_from_raw gives a 64 x 16 tile to a 256-thread workgroup that converts it into LDS and meets at three barriers; a
 // workgroup has 3 KB of loads in flight in two dependent rounds and the kernel moves 14 B per pixel at 1.7 of the 8 TB/s (1024
 // frames of 640 x 480: 2.6 ms, the largest single item of a bench step after the finest-level sweeps).  Here
@@ -26,7 +26,9 @@
 // A float-depth frame's raw copy is its own float planes I / Z of level 0 (FrameBuildPtrs::keep_planes), written with the NT policy
 // like the u8 / u16 copy.
 #include "colour.h"
+#include "dispatch.h"
 #include "global_ptr.h"
+#include "image_model.h"
 #include "launch.h"
 
 namespace dvo_hip {
@@ -84,22 +86,20 @@ __device__ __forceinline__ int strip_role_planes(const float (&I)[TAPS ? kStripH
         const size_t at = size_t(y) * w0 + x;
         const float i0 = I[j][0], i1 = I[j][1], z0 = Z[j][0], z1 = Z[j][1];
         if (TAPS) {
-          // column x - 1 of the pair's first pixel: the previous lane's second pixel (lane 0: the edge column), clamped at the image
-          // border like the reference's derivative code; column x + 2 of the second pixel likewise
+          // column x - 1 of the pair's first pixel: the previous lane's second pixel (lane 0: the edge column); at the image border the
+          // pixel itself, which is what the clamped index reads (image_model.h); column x + 2 of the second pixel likewise
           const float ie = eI[r], ze = eZ[r];
           const float il_n = from_previous_lane(i1, ie), zl_n = from_previous_lane(z1, ze);
           const float ir_n = from_next_lane(i0, ie), zr_n = from_next_lane(z0, ze);
           const float il = x > 0 ? il_n : i0, zl = x > 0 ? zl_n : z0;
           const float ir = x + 2 < w0 ? ir_n : i1, zr = x + 2 < w0 ? zr_n : z1;
-          const float idx0 = (i1 - il) * 0.5f, idx1 = (ir - i0) * 0.5f;
-          const float zdx0 = (z1 - zl) * 0.5f, zdx1 = (zr - z0) * 0.5f;
-          const float idy0 = (I[j + 1][0] - I[j - 1][0]) * 0.5f, idy1 = (I[j + 1][1] - I[j - 1][1]) * 0.5f;
-          const float zdy0 = (Z[j + 1][0] - Z[j - 1][0]) * 0.5f, zdy1 = (Z[j + 1][1] - Z[j - 1][1]) * 0.5f;
+          const float idx0 = central_difference(il, i1), idx1 = central_difference(i0, ir);
+          const float zdx0 = central_difference(zl, z1), zdx1 = central_difference(z0, zr);
+          const float idy0 = central_difference(I[j - 1][0], I[j + 1][0]), idy1 = central_difference(I[j - 1][1], I[j + 1][1]);
+          const float zdy0 = central_difference(Z[j - 1][0], Z[j + 1][0]), zdy1 = central_difference(Z[j - 1][1], Z[j + 1][1]);
           if (ROLE == 1) {
-            const bool ok0 = inside && z0 == z0 && zdx0 == zdx0 && zdy0 == zdy0 &&
-                             (fabsf(idx0) > ithr || fabsf(idy0) > ithr || fabsf(zdx0) > dthr || fabsf(zdy0) > dthr);
-            const bool ok1 = inside && z1 == z1 && zdx1 == zdx1 && zdy1 == zdy1 &&
-                             (fabsf(idx1) > ithr || fabsf(idy1) > ithr || fabsf(zdx1) > dthr || fabsf(zdy1) > dthr);
+            const bool ok0 = inside && selects(z0, idx0, idy0, zdx0, zdy0, ithr, dthr);
+            const bool ok1 = inside && selects(z1, idx1, idy1, zdx1, zdy1, ithr, dthr);
             if (inside) gstore_pair<NT>(R0 + at, make_float4(ok0 ? z0 : nanv, i0, ok1 ? z1 : nanv, i1));
             count += __popcll(__ballot(ok0)) + __popcll(__ballot(ok1));   // wave-uniform
           } else if (inside) {
@@ -264,8 +264,8 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int j = 2 * k - kFirst, y1 = sy * 4 + k;
-      m1[k] = (I[j][0] + I[j][1] + I[j + 1][0] + I[j + 1][1]) / 4.0f;   // same summation order as the reference
-      z1v[k] = Z[j][0];                                                 // top-left sample, NaN holes kept (Q18)
+      m1[k] = mean_2x2(I[j][0], I[j][1], I[j + 1][0], I[j + 1][1]);
+      z1v[k] = depth_subsample(Z[j][0]);
       if (x1 < w1 && y1 < h1) {
         const size_t at = size_t(y1) * w1 + x1;
         gst<NT>(I1 + at, m1[k]);
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
       const int y2 = sy * 2 + m;
-      m2[m] = (m1[2 * m] + row_shifted<kDppRowShl1>(m1[2 * m]) + m1[2 * m + 1] + row_shifted<kDppRowShl1>(m1[2 * m + 1])) / 4.0f;
+      m2[m] = mean_2x2(m1[2 * m], row_shifted<kDppRowShl1>(m1[2 * m]), m1[2 * m + 1], row_shifted<kDppRowShl1>(m1[2 * m + 1]));
       if ((lane & 1) == 0 && x2 < w2 && y2 < h2) {
         const size_t at = size_t(y2) * w2 + x2;
         I2[at] = m2[m];
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
     }
     if (levels < 4) continue;
     const int x3 = x1 >> 2, y3 = sy;
-    const float m3 = (m2[0] + row_shifted<kDppRowShl2>(m2[0]) + m2[1] + row_shifted<kDppRowShl2>(m2[1])) / 4.0f;
+    const float m3 = mean_2x2(m2[0], row_shifted<kDppRowShl2>(m2[0]), m2[1], row_shifted<kDppRowShl2>(m2[1]));
     if ((lane & 3) == 0 && x3 < w3 && y3 < h3) {
       const size_t at = size_t(y3) * w3 + x3;
       I3[at] = m3;
@@ -300,9 +300,9 @@ __global__ __launch_bounds__(256) void k_ingest_strips(const FrameBuildPtrs* __r
 }
 
 // The role planes of ONE pyramid level from the float planes I / Z (levels >= 1, and level 0 of frames created from float planes): the
-// same strips, the same role code, 8-byte loads of pixel pairs instead of the raw planes' 2 + 4 bytes.  Replaces k_derive_current /
-// k_derive_reference (one pixel per thread, ten scattered 4-byte loads each: 3 TB/s) for batches; a single camera frame's levels go
-// through k_derive_levels (one launch for all of them).
+// same strips, the same role code, 8-byte loads of pixel pairs instead of the raw planes' 2 + 4 bytes.  Takes the batches; odd widths
+// and a single camera frame's levels (one launch for all of them) go through k_derive_levels (one pixel per thread, ten scattered
+// 4-byte loads each: 3 TB/s).
 // NT: loads and stores with the non-temporal policy (the ingest's NT, for level 1 of a background build).
 template <int ROLE, bool TAPS, bool NT = false>
 __global__ __launch_bounds__(256) void k_derive_strips(const FrameBuildPtrs* __restrict__ tbl, int level, int w0, int h0, float ithr, float dthr,
@@ -360,22 +360,21 @@ __global__ __launch_bounds__(256) void k_derive_strips(const FrameBuildPtrs* __r
 
 bool derive_strips_supports(int w) { return w % 2 == 0 && w >= 4; }
 
-// role 0: current (flavours cur_flavor), role 1: reference (the level's counters zeroed before by the caller's k_zero_counts)
+// role 0: current (flavours cur_flavor), role 1: reference (the level's counters zeroed before by the caller)
 // stream_nt: the non-temporal policy at levels 0-1 (launch.h)
 void launch_derive_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int role, float ithr, float dthr,
                           int max_workgroups, int cur_flavor, bool stream_nt) {
   const int gx = (w + kStripW - 1) / kStripW, gy = (h + kStripH * kStripsPerGroup - 1) / (kStripH * kStripsPerGroup);
   const long long total = (long long)gx * gy * n_frames;
   const dim3 grid(int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total)), block(256);
-#define DVO_LAUNCH_DERIVE(ROLE, TAPS)                                                                                       \
-  do {                                                                                                                      \
-    if (stream_nt && level <= 1) k_derive_strips<ROLE, TAPS, true><<<grid, block, 0, s>>>(tbl, level, w, h, ithr, dthr, gx, gy, n_frames, cur_flavor); \
-    else k_derive_strips<ROLE, TAPS><<<grid, block, 0, s>>>(tbl, level, w, h, ithr, dthr, gx, gy, n_frames, cur_flavor);  \
-  } while (0)
-  if (role == 1) DVO_LAUNCH_DERIVE(1, true);
-  else if (cur_flavor & kCurAB) DVO_LAUNCH_DERIVE(0, true);
-  else DVO_LAUNCH_DERIVE(0, false);
-#undef DVO_LAUNCH_DERIVE
+  auto launch = [&](auto ROLE, auto TAPS) {
+    with_bool(stream_nt && level <= 1, [&](auto NT) {
+      k_derive_strips<decltype(ROLE)::value, decltype(TAPS)::value, decltype(NT)::value>
+          <<<grid, block, 0, s>>>(tbl, level, w, h, ithr, dthr, gx, gy, n_frames, cur_flavor);
+    });
+  };
+  if (role == 1) launch(std::integral_constant<int, 1>{}, std::true_type{});
+  else with_bool((cur_flavor & kCurAB) != 0, [&](auto TAPS) { launch(std::integral_constant<int, 0>{}, TAPS); });
 }
 
 // (a float image with float depth: every even width; the 8-bit planes' loads want rows of 4 pixels)
@@ -397,32 +396,26 @@ void launch_ingest_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames
   const long long total = (long long)gx * gy * n_frames;
   const dim3 grid(int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total)), block(256);
   const int lv = levels < 4 ? levels : 4;
-#define DVO_LAUNCH_STRIPS_NT(ROLE, TAPS, CH, NT)                                                                                \
-  do {                                                                                                                          \
-    if (CH == kChF32 || depth_f32)                                                                                              \
-      k_ingest_strips<ROLE, TAPS, CH, NT, true><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, gx, gy, n_frames, cur_flavor, c_levels); \
-    else                                                                                                                        \
-      k_ingest_strips<ROLE, TAPS, CH == kChF32 ? 0 : CH, NT><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, gx, gy, n_frames, cur_flavor, c_levels); \
-  } while (0)
-#define DVO_LAUNCH_STRIPS(ROLE, TAPS, CH)                                                                                       \
-  do {                                                                                                                          \
-    if (stream_nt) DVO_LAUNCH_STRIPS_NT(ROLE, TAPS, CH, true);                                                                  \
-    else DVO_LAUNCH_STRIPS_NT(ROLE, TAPS, CH, false);                                                                           \
-  } while (0)
-#define DVO_LAUNCH_STRIPS_ROLE(CH)                                          \
-  do {                                                                      \
-    if (role == 1) DVO_LAUNCH_STRIPS(1, true, CH);                          \
-    else if (role == 0 && (cur_flavor & kCurAB)) DVO_LAUNCH_STRIPS(0, true, CH); \
-    else if (role == 0) DVO_LAUNCH_STRIPS(0, false, CH);                    \
-    else DVO_LAUNCH_STRIPS(-1, false, CH);                                  \
-  } while (0)
-  if (colour_channels == 3) DVO_LAUNCH_STRIPS_ROLE(3);
-  else if (colour_channels == 4) DVO_LAUNCH_STRIPS_ROLE(4);
-  else if (colour_channels == kChF32) DVO_LAUNCH_STRIPS_ROLE(kChF32);
-  else DVO_LAUNCH_STRIPS_ROLE(0);
-#undef DVO_LAUNCH_STRIPS_ROLE
-#undef DVO_LAUNCH_STRIPS
-#undef DVO_LAUNCH_STRIPS_NT
+  // TAPS follows the role: the reference role always, the current role with the gathered taps, never without a role
+  with_value<1, 0, -1>(role, [&](auto ROLE) {
+    constexpr int kRole = decltype(ROLE)::value;
+    auto launch = [&](auto TAPS) {
+      with_value<3, 4, kChF32, 0>(colour_channels, [&](auto CH) {
+        with_bool(depth_f32 || colour_channels == kChF32, [&](auto ZF) {
+          with_bool(stream_nt, [&](auto NT) {
+            constexpr int kCh = decltype(CH)::value;
+            constexpr bool kZf = decltype(ZF)::value;
+            if constexpr (kCh != kChF32 || kZf)
+              k_ingest_strips<kRole, decltype(TAPS)::value, kCh, decltype(NT)::value, kZf>
+                  <<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, gx, gy, n_frames, cur_flavor, c_levels);
+          });
+        });
+      });
+    };
+    if constexpr (kRole == 1) launch(std::true_type{});
+    else if constexpr (kRole == -1) launch(std::false_type{});
+    else with_bool((cur_flavor & kCurAB) != 0, launch);
+  });
 }
 
 }  // namespace dvo_hip

@@ -15,15 +15,15 @@ struct RefOrderPlane;   // (ref_order.h)
 // raw ingest + pyramid levels 1..3 in one pass (levels beyond the fourth: launch_pyr_down)
 void launch_pyr_down(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h);
 // max_workgroups > 0 caps the grid (the kernels walk the tiles with a grid stride): background build next to an alignment
-// level 0 in role `role` (-1 none, 0 current, 1 reference) + pyramid levels 1..3 straight from raw planes; `wide`: 4-pixel aligned rows
+// level 0 in role `role` (-1 none, 0 current, 1 reference) + pyramid levels 1..3 straight from raw planes; `strips`: through the strip
+// ingest (ingest_strips.hip; the caller asks ingest_strips_supports once and counts and plans by the same answer), else in 64 x 16 tiles
 // cur_flavor (role 0): which planes of the current role are written, kCurAB | kCurC (device_types.h)
-// c_levels: bit l set = pyramid level l (1..3) also gets the current role's {I, Z} plane C in the same pass (ingest_strips.hip only:
-// ingest_strips_supports tells the caller whether the pass will honour it)
+// c_levels: bit l set = pyramid level l (1..3) also gets the current role's {I, Z} plane C in the same pass (with `strips` only)
 // colour_channels: 0 = grey planes, 3 / 4 = every frame's colour plane (FrameBuildPtrs::colour) with that many bytes per pixel,
 // kChF32 = a float image plane there; depth_f32: float depth planes (FrameBuildPtrs::depth_f32) instead of the u16 ones
 // stream_nt: the strip kernels read the raw planes and write the planes of levels 0-1 with the non-temporal policy (global_ptr.h; the
 // option "stream_policy" for the build stream's launches)
-void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role, bool wide,
+void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role, bool strips,
                            float ithr, float dthr, int max_workgroups, int cur_flavor = kCurAB, int c_levels = 0, int colour_channels = 0,
                            bool stream_nt = false, bool depth_f32 = false);
 // ingest_strips.hip: the role planes of one level from the float planes I / Z in strips (even widths); role 1: counters zeroed before
@@ -31,7 +31,8 @@ bool derive_strips_supports(int w);
 void launch_derive_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int role, float ithr, float dthr,
                           int max_workgroups, int cur_flavor, bool stream_nt = false);
 // ingest_strips.hip: the same pass with one 128 x 8 strip per wavefront, registers only (even widths, aligned planes)
-// f32_image: the image plane is float (with float depth): every even width qualifies, the 8-bit planes want a multiple of 4
+// wide: every plane's address and pitch suit the strip loads (f32_strips_aligned, colour_strips_aligned; 8-bit grey and u16 depth: 4-pixel
+// groups).  f32_image: the image plane is float (with float depth): every even width qualifies, the 8-bit planes want a multiple of 4
 bool ingest_strips_supports(int w0, bool wide, bool f32_image = false);
 // a float plane's share of `wide`: address and row pitch are 8-byte aligned (a lane loads its pixel pair in one piece)
 bool f32_strips_aligned(const void* plane, size_t pitch);
@@ -42,6 +43,7 @@ bool colour_strips_aligned(const void* colour, size_t pitch, int channels);
 void launch_ingest_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role,
                           float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels = 0, bool stream_nt = false,
                           bool depth_f32 = false);
+// the role planes of one level from the float planes I / Z: the strips at even widths, launch_derive_levels over the one level at odd ones
 void launch_derive_current(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int max_workgroups, int cur_flavor = kCurAB,
                            bool stream_nt = false);
 // mode 0: A + B from C; 1: C from A; 2: R + selection count from C (the level's counters are zeroed first)
@@ -49,13 +51,15 @@ void launch_from_current_plane(hipStream_t s, const FrameBuildPtrs* tbl, int n_f
                                int max_workgroups);
 void launch_derive_reference(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, float ithr, float dthr,
                              int max_workgroups, bool stream_nt = false);
-// the role planes (role 0: current, flavours per level in span.flavor; role 1: reference) of the levels span.l0 .. span.l1 in one launch
+// the role planes (role 0: current, flavours per level in span.flavor; role 1: reference, counters zeroed here) of the levels
+// span.l0 .. span.l1 in one launch of 64 x 16 tiles
 void launch_derive_levels(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, const LevelSpan& span, int role, float ithr, float dthr,
                           int max_workgroups);
 void launch_select_pack(hipStream_t s, const float4* A, const float2* B, int n, float ithr, float dthr, float2* R, int* count, uint8_t* mask);
-// the caller selection (selection.h) over the reference planes R of levels span.l0 .. span.l1 of n frames, one launch; span.tile0 =
-// offsets of each level's 512-pixel blocks (apply_selection_span)
-void apply_selection_span(LevelSpan& span, int l0, int l1, const int* w, const int* h);
+// the levels l0 .. l1 of a camera (w, h: indexed by level) as a span; tile0 = offsets of each level's 64 x 16 tiles (k_derive_levels), or
+// with pixel_blocks of its 512-pixel blocks (k_apply_selection).  flavor: zero, the caller's to set
+LevelSpan level_span(int l0, int l1, const int* w, const int* h, bool pixel_blocks = false);
+// the caller selection (selection.h) over the reference planes R of levels span.l0 .. span.l1 of n frames, one launch (a pixel_blocks span)
 void launch_apply_selection(hipStream_t s, const SelectionApply* tbl, int n_frames, const LevelSpan& span, int max_workgroups);
 // an explicit accepted set of one level: R = {Z where accepted[i] != 0, else NaN; I}, count = accepted entries (zeroed before)
 void launch_pack_accepted(hipStream_t s, const float4* A, const uint8_t* accepted, int n, float2* R, int* count);

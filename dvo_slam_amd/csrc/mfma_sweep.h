@@ -120,7 +120,7 @@ __device__ __forceinline__ void mfma_sweep_tile(const LevelGeom& g, const float*
     return r;
   };
   // the reference quad {Zsel, I, Idx, Idy} the per-pixel stages work on: the gradient is the reference's central difference
-  // 0.5 (next - previous), same operation order as the frame build (pyramid_kernels.hip::derive_at), hence the same bits
+  // 0.5 (next - previous), same operation order as the frame build (image_model.h::derive_at), hence the same bits
   auto ref_quad = [&](const RefRow& r) {
     float left, right;
     if constexpr (LINEAR) {

@@ -7,7 +7,8 @@
 //   accel struct  dvo_core/src/core/rgbd_image.cpp:534-543   (8 interleaved float channels, 32 B/pixel)
 //   selection     dvo_core/src/core/point_selection.cpp:89-152, point_selection.h:49-67
 // is done here on the GPU, one launch per pyramid level for a whole batch of frames (blockIdx.z = frame),
-// so a frame upload is two raw planes and every derived plane stays in HBM.  Layout (all float32):
+// so a frame upload is two raw planes and every derived plane stays in HBM.  The per-pixel arithmetic (mean, subsample, differences,
+// predicate) is image_model.h's; the kernels here only lay it out.  Layout (all float32):
 //   I, Z          planar, 4 B/pixel each (pyr-down and derivative source; built when the frame is ingested)
 //   A             float4 {I, Z, Idx, Idy}  current-side sampling plane, one 16-B tap per bilinear corner
 //   B             float2 {Zdx, Zdy}        current-side sampling plane,  8-B tap
@@ -15,7 +16,9 @@
 //                 predicate rejects the pixel, so the reduce kernel needs no separate mask or list
 // These are bandwidth-trivial elementwise kernels; they are written for coalescing only.
 #include "colour.h"
+#include "dispatch.h"
 #include "global_ptr.h"
+#include "image_model.h"
 #include "launch.h"
 #include "selection.h"
 
@@ -35,28 +38,40 @@ __device__ __forceinline__ void for_each_tile(int tiles_x, int tiles_y, int n_fr
   }
 }
 
+// The selection count of a tile of a 4-wavefront workgroup: `count` is wave-uniform; one LDS word per wavefront, added in a fixed order,
+// ONE atomic per tile (one per wavefront-row serialised a whole kernel on 128 addresses).  Holds one barrier; the caller puts another
+// between this and its next call (the words are rewritten).  The counter must have been zeroed on the stream before.
+__device__ __forceinline__ void add_tile_count(int count, int wave, int lane, int* counter) {
+  __shared__ int wave_counts[4];
+  if (lane == 0) wave_counts[wave] = count;
+  __syncthreads();
+  if (wave == 0 && lane == 0) {
+    const int total = (wave_counts[0] + wave_counts[1]) + (wave_counts[2] + wave_counts[3]);
+    if (total) atomicAdd(counter, total);
+  }
+}
+
 // Level 0 straight from the raw planes, in the role the frame is about to play, plus pyramid levels 1-3: one pass over
 // 3 B per pixel instead of  raw -> float I, Z (8 B written)  followed by  I, Z (+ halo) -> role planes (8 B read again).
-// A 32 x 8 workgroup owns a 64 x 16 tile; the tile and its one-pixel border are converted into LDS with 4- and 8-byte
-// loads (WIDE: rows and plane addresses are 4-pixel aligned), border coordinates clamped like the reference's derivative
-// code (rgbd_image.cpp:419-489), so pixels past the image edge hold the edge value.  Then every thread derives its 2 x 2
-// quad from LDS and folds pyramid levels 1-3 (2 x 2 means through LDS, same summation order as k_pyr_down).  Float I / Z planes
+// A 32 x 8 workgroup owns a 64 x 16 tile; the tile and its one-pixel border are converted into LDS pixel by pixel (rows that
+// allow wider loads take the strip ingest, ingest_strips.hip), border coordinates clamped like the reference's derivative
+// code (image_model.h), so pixels past the image edge hold the edge value.  Then every thread derives its 2 x 2
+// quad from LDS and folds pyramid levels 1-3 (2 x 2 means through LDS).  Float I / Z planes
 // of level 0 are never written:
 // a frame built this way keeps either its current-role planes (which hold everything) or a 3-B copy of the raw planes
 // (keep_grey / keep_raw) from which the other role can be derived later by the same kernel.
 // ROLE: -1 = none (copy + pyramid only), 0 = current (A, B), 1 = reference (R + selection count, counter zeroed before).
-// Arithmetic = the reference's ingest (surface_pyramid.cpp:65-105), k_pyr_down and derive_at: bit-identical planes.
-// CH = 3 / 4 (with WIDE = false): the grey value of a pixel comes from the frame's colour plane (colour.h) -- odd widths, unaligned
+// Arithmetic = the reference's ingest (surface_pyramid.cpp:65-105) and image_model.h: bit-identical planes.
+// CH = 3 / 4: the grey value of a pixel comes from the frame's colour plane (colour.h) -- odd widths, unaligned
 // colour planes and padded pitches the strip ingest does not take; keep_grey receives the converted grey.
-// CH = kChF32 / ZF (with WIDE = false): a float image plane / a float depth plane (ingest_strips.hip's float sources) at odd widths and
+// CH = kChF32 / ZF: a float image plane / a float depth plane (ingest_strips.hip's float sources) at odd widths and
 // rows that are not 8-byte aligned; with ZF the raw copy goes to the float planes I / Z of level 0 (keep_planes).
 constexpr int kB0W = 64, kB0H = 16, kB0Stride = 68;
 
-template <int ROLE, bool WIDE, int CH = 0, bool ZF = false>
+template <int ROLE, int CH = 0, bool ZF = false>
 __global__ __launch_bounds__(256) void k_build_from_raw(const FrameBuildPtrs* __restrict__ tbl, float scale, int w0, int h0, int levels,
                                                         float ithr, float dthr, int tiles_x, int tiles_y, int n_frames, int cur_flavor) {
 #pragma clang fp contract(off)
-  static_assert(!(WIDE && (CH || ZF)), "colour and float planes take the narrow loads");
   static_assert(CH != kChF32 || ZF, "a float image comes with float depth");
   constexpr bool IF = CH == kChF32, COL = CH == 3 || CH == 4;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // 32 x 8 threads, one 2 x 2 quad each
@@ -66,7 +81,6 @@ __global__ __launch_bounds__(256) void k_build_from_raw(const FrameBuildPtrs* __
   __shared__ float sZ[kB0H + 2][kB0Stride];
   __shared__ float s1[8][32];
   __shared__ float s2[4][16];
-  __shared__ int wave_counts[4];
   const float nanv = __builtin_nanf("");
   for_each_tile(tiles_x, tiles_y, n_frames, [&](int bx, int by, int frame) {
     const FrameBuildPtrs& f = tbl[frame];
@@ -95,69 +109,27 @@ __global__ __launch_bounds__(256) void k_build_from_raw(const FrameBuildPtrs* __
     const int x0 = bx * kB0W, y0 = by * kB0H;
     auto depth_of = [&](uint16_t d) { return d == 0 ? nanv : float(d) * scale; };
     // ---- tile + border into LDS (column c of the slab = image column x0 - 1 + c, row r = image row y0 - 1 + r, clamped) ----
-    if (WIDE) {
-      for (int i = threadIdx.x; i < (kB0H + 2) * (kB0W / 4); i += 256) {
-        const int r = i / (kB0W / 4), qd = i - r * (kB0W / 4);
-        const int yy = y0 - 1 + r, y = min(max(yy, 0), h0 - 1);
-        const int x = x0 + 4 * qd;
-        const size_t at = size_t(y) * w0 + x;
-        if (x + 3 < w0) {
-          const unsigned gbits = *(Global<const unsigned>)(grey + at);
-          const GlobalU32x2 dbits = *(Global<const GlobalU32x2>)(raw + at);
-          const uchar4 gq = make_uchar4(gbits & 0xffu, gbits >> 8 & 0xffu, gbits >> 16 & 0xffu, gbits >> 24);
-          const ushort4 dq = make_ushort4(dbits.x & 0xffffu, dbits.x >> 16, dbits.y & 0xffffu, dbits.y >> 16);
-          float* di = &sI[r][1 + 4 * qd];
-          float* dz = &sZ[r][1 + 4 * qd];
-          di[0] = float(gq.x); di[1] = float(gq.y); di[2] = float(gq.z); di[3] = float(gq.w);
-          dz[0] = depth_of(dq.x); dz[1] = depth_of(dq.y); dz[2] = depth_of(dq.z); dz[3] = depth_of(dq.w);
-          if (keep_grey && yy == y && r >= 1 && r <= kB0H) {
-            *(Global<unsigned>)(keep_grey + at) = gbits;
-            *(Global<GlobalU32x2>)(keep_raw + at) = dbits;
-          }
-        } else {
-          for (int k = 0; k < 4; ++k) {
-            const int xc = min(x + k, w0 - 1);
-            const uint8_t gv = grey[size_t(y) * w0 + xc];
-            const uint16_t dv = raw[size_t(y) * w0 + xc];
-            sI[r][1 + 4 * qd + k] = float(gv);
-            sZ[r][1 + 4 * qd + k] = depth_of(dv);
-            if (keep_grey && yy == y && r >= 1 && r <= kB0H && x + k < w0) {
-              keep_grey[size_t(y) * w0 + xc] = gv;
-              keep_raw[size_t(y) * w0 + xc] = dv;
-            }
-          }
+    for (int i = threadIdx.x; i < (kB0H + 2) * (kB0W + 2); i += 256) {
+      const int r = i / (kB0W + 2), c = i - r * (kB0W + 2);
+      const int yy = y0 - 1 + r, xx = x0 - 1 + c;
+      const int y = clamp_index(yy, h0), x = clamp_index(xx, w0);
+      const bool own = yy == y && xx == x && r >= 1 && r <= kB0H && c >= 1 && c <= kB0W;   // a pixel of this tile, not of its border
+      const uint8_t gv = COL ? colour_grey(y, x) : IF ? uint8_t(0) : grey[size_t(y) * (ZF ? pitch : size_t(w0)) + x];   // (with float depth: a grey plane has a pitch)
+      const float iv = IF ? *(Global<const float>)(colour + size_t(y) * pitch + size_t(x) * 4) : float(gv);
+      sI[r][c] = iv;
+      if (ZF) {
+        const float zv = depth_of_f32(*(Global<const float>)(depth_f + size_t(y) * zpitch + size_t(x) * 4), scale);   // (colour.h)
+        sZ[r][c] = zv;
+        if (keep_planes && own) {
+          I0[size_t(y) * w0 + x] = iv;
+          Z0[size_t(y) * w0 + x] = zv;
         }
-      }
-      if (threadIdx.x < 2 * (kB0H + 2)) {                       // the two border columns
-        const int r = threadIdx.x >> 1, side = threadIdx.x & 1;
-        const int y = min(max(y0 - 1 + r, 0), h0 - 1);
-        const int x = side ? min(x0 + kB0W, w0 - 1) : max(x0 - 1, 0);
-        sI[r][side ? kB0W + 1 : 0] = float(grey[size_t(y) * w0 + x]);
-        sZ[r][side ? kB0W + 1 : 0] = depth_of(raw[size_t(y) * w0 + x]);
-      }
-    } else {
-      for (int i = threadIdx.x; i < (kB0H + 2) * (kB0W + 2); i += 256) {
-        const int r = i / (kB0W + 2), c = i - r * (kB0W + 2);
-        const int yy = y0 - 1 + r, xx = x0 - 1 + c;
-        const int y = min(max(yy, 0), h0 - 1), x = min(max(xx, 0), w0 - 1);
-        const bool own = yy == y && xx == x && r >= 1 && r <= kB0H && c >= 1 && c <= kB0W;   // a pixel of this tile, not of its border
-        const uint8_t gv = COL ? colour_grey(y, x) : IF ? uint8_t(0) : grey[size_t(y) * (ZF ? pitch : size_t(w0)) + x];   // (with float depth: a grey plane has a pitch)
-        const float iv = IF ? *(Global<const float>)(colour + size_t(y) * pitch + size_t(x) * 4) : float(gv);
-        sI[r][c] = iv;
-        if (ZF) {
-          const float zv = depth_of_f32(*(Global<const float>)(depth_f + size_t(y) * zpitch + size_t(x) * 4), scale);   // (colour.h)
-          sZ[r][c] = zv;
-          if (keep_planes && own) {
-            I0[size_t(y) * w0 + x] = iv;
-            Z0[size_t(y) * w0 + x] = zv;
-          }
-        } else {
-          const uint16_t dv = raw[size_t(y) * w0 + x];
-          sZ[r][c] = depth_of(dv);
-          if (keep_grey && own) {
-            keep_grey[size_t(y) * w0 + x] = gv;
-            keep_raw[size_t(y) * w0 + x] = dv;
-          }
+      } else {
+        const uint16_t dv = raw[size_t(y) * w0 + x];
+        sZ[r][c] = depth_of(dv);
+        if (keep_grey && own) {
+          keep_grey[size_t(y) * w0 + x] = gv;
+          keep_raw[size_t(y) * w0 + x] = dv;
         }
       }
     }
@@ -176,8 +148,8 @@ __global__ __launch_bounds__(256) void k_build_from_raw(const FrameBuildPtrs* __
         bool ok = false;
         if (x < w0 && y < h0) {
           const float i0 = sI[r][c], z0 = sZ[r][c];
-          const float idx = (sI[r][c + 1] - sI[r][c - 1]) * 0.5f, idy = (sI[r + 1][c] - sI[r - 1][c]) * 0.5f;
-          const float zdx = (sZ[r][c + 1] - sZ[r][c - 1]) * 0.5f, zdy = (sZ[r + 1][c] - sZ[r - 1][c]) * 0.5f;
+          const float idx = central_difference(sI[r][c - 1], sI[r][c + 1]), idy = central_difference(sI[r - 1][c], sI[r + 1][c]);
+          const float zdx = central_difference(sZ[r][c - 1], sZ[r][c + 1]), zdy = central_difference(sZ[r - 1][c], sZ[r + 1][c]);
           const size_t at = size_t(y) * w0 + x;
           if (ROLE == 0) {
             // the current role comes in two flavours (device_types.h kCurAB / kCurC): the gathered taps of the gathering sweep and
@@ -188,31 +160,28 @@ __global__ __launch_bounds__(256) void k_build_from_raw(const FrameBuildPtrs* __
             }
             if (cur_flavor & kCurC) gstore(C0 + at, make_float2(i0, z0));
           } else {
-            ok = z0 == z0 && zdx == zdx && zdy == zdy && (fabsf(idx) > ithr || fabsf(idy) > ithr || fabsf(zdx) > dthr || fabsf(zdy) > dthr);
+            ok = selects(z0, idx, idy, zdx, zdy, ithr, dthr);
             gstore(R0 + at, make_float2(ok ? z0 : nanv, i0));
           }
         }
         if (ROLE == 1) count += __popcll(__ballot(ok));         // wave-uniform
       }
     }
-    if (ROLE == 1 && (threadIdx.x & 63) == 0) wave_counts[threadIdx.x >> 6] = count;
     // ---- pyramid levels 1-3 (16 x 4 and 8 x 2 pixels of levels 2 and 3 per tile; an out-of-image quad is never written) ----
     const int r = 2 * ty + 1, c = 2 * tx + 1;
-    const float i1 = (sI[r][c] + sI[r][c + 1] + sI[r + 1][c] + sI[r + 1][c + 1]) / 4.0f;   // same summation order as the reference
-    const float z00 = sZ[r][c];
+    const float i1 = mean_2x2(sI[r][c], sI[r][c + 1], sI[r + 1][c], sI[r + 1][c + 1]);
+    const float z00 = depth_subsample(sZ[r][c]);
     if (levels >= 2 && x1 < w1 && y1 < h1) {
       I1[size_t(y1) * w1 + x1] = i1;
-      Z1[size_t(y1) * w1 + x1] = z00;                       // top-left sample, NaN holes kept (Q18)
+      Z1[size_t(y1) * w1 + x1] = z00;
     }
     s1[ty][tx] = i1;
-    __syncthreads();                                             // s1 and wave_counts complete; sI / sZ free for the next tile
-    if (ROLE == 1 && threadIdx.x == 0) {
-      const int total = (wave_counts[0] + wave_counts[1]) + (wave_counts[2] + wave_counts[3]);
-      if (total) atomicAdd(f.sel_count, total);
-    }
+    // (one barrier either way: s1 complete, sI / sZ free for the next tile)
+    if (ROLE == 1) add_tile_count(count, threadIdx.x >> 6, threadIdx.x & 63, f.sel_count);
+    else __syncthreads();
     const int x2 = x1 >> 1, y2 = y1 >> 1;
     if ((tx & 1) == 0 && (ty & 1) == 0) {
-      const float i2 = (s1[ty][tx] + s1[ty][tx + 1] + s1[ty + 1][tx] + s1[ty + 1][tx + 1]) / 4.0f;
+      const float i2 = mean_2x2(s1[ty][tx], s1[ty][tx + 1], s1[ty + 1][tx], s1[ty + 1][tx + 1]);
       if (levels >= 3 && x2 < w2 && y2 < h2) {
         I2[size_t(y2) * w2 + x2] = i2;
         Z2[size_t(y2) * w2 + x2] = z00;
@@ -223,11 +192,11 @@ __global__ __launch_bounds__(256) void k_build_from_raw(const FrameBuildPtrs* __
     if (levels >= 4 && (tx & 3) == 0 && (ty & 3) == 0) {
       const int x3 = x1 >> 2, y3 = y1 >> 2, cx = tx >> 1, cy = ty >> 1;
       if (x3 < w3 && y3 < h3) {
-        I3[size_t(y3) * w3 + x3] = (s2[cy][cx] + s2[cy][cx + 1] + s2[cy + 1][cx] + s2[cy + 1][cx + 1]) / 4.0f;
+        I3[size_t(y3) * w3 + x3] = mean_2x2(s2[cy][cx], s2[cy][cx + 1], s2[cy + 1][cx], s2[cy + 1][cx + 1]);
         Z3[size_t(y3) * w3 + x3] = z00;
       }
     }
-    __syncthreads();                                             // s1, s2, wave_counts free for the next tile of this workgroup
+    __syncthreads();                                             // s1, s2, the tile count's words free for the next tile of this workgroup
   });
 }
 
@@ -244,65 +213,33 @@ __global__ void k_pyr_down(const FrameBuildPtrs* __restrict__ tbl, int level, in
   if (x >= ow || y >= oh) return;
   const auto r0 = I + size_t(2 * y) * w + 2 * x;
   const auto r1 = r0 + w;
-  outI[size_t(y) * ow + x] = (r0[0] + r0[1] + r1[0] + r1[1]) / 4.0f;   // same summation order as the reference
-  outZ[size_t(y) * ow + x] = Z[size_t(2 * y) * w + 2 * x];             // top-left sample, NaN holes kept (Q18)
+  outI[size_t(y) * ow + x] = mean_2x2(r0[0], r0[1], r1[0], r1[1]);
+  outZ[size_t(y) * ow + x] = depth_subsample(Z[size_t(2 * y) * w + 2 * x]);
 }
 
-// Central differences with clamped borders (rgbd_image.cpp:419-489).  The derived planes are built per ROLE, like the
-// reference builds them lazily: a frame that is only ever a current frame gets A + B (buildAccelerationStructure,
+// The pixel sources of derive_at (image_model.h: clamped central differences): the planar float planes I / Z of a level, or the
+// interleaved {I, Z} plane C of a frame that has been a current frame of the window sweep.  The derived planes are built per ROLE, like
+// the reference builds them lazily: a frame that is only ever a current frame gets A + B (buildAccelerationStructure,
 // rgbd_image.cpp:534-543), a frame that is only ever a reference gets R + the selection count (PointSelection::select,
 // point_selection.cpp:89-152).
-struct Derivs {
-  float i0, z0, idx, idy, zdx, zdy;
+struct PlanarSource {
+  Global<const float> I, Z;
+  int w;
+  __device__ __forceinline__ float2 operator()(int x, int y) const { return make_float2(I[size_t(y) * w + x], Z[size_t(y) * w + x]); }
+};
+struct InterleavedSource {
+  Global<const float2> C;
+  int w;
+  __device__ __forceinline__ float2 operator()(int x, int y) const { return gload(C + size_t(y) * w + x); }
 };
 
-__device__ __forceinline__ Derivs derive_at(Global<const float> I, Global<const float> Z, int w, int h, int x, int y) {
-#pragma clang fp contract(off)
-  const int xp = max(x - 1, 0), xn = min(x + 1, w - 1);
-  const int yp = max(y - 1, 0), yn = min(y + 1, h - 1);
-  const size_t row = size_t(y) * w;
-  Derivs d;
-  d.i0 = I[row + x];
-  d.z0 = Z[row + x];
-  d.idx = (I[row + xn] - I[row + xp]) * 0.5f;
-  d.idy = (I[size_t(yn) * w + x] - I[size_t(yp) * w + x]) * 0.5f;
-  d.zdx = (Z[row + xn] - Z[row + xp]) * 0.5f;
-  d.zdy = (Z[size_t(yn) * w + x] - Z[size_t(yp) * w + x]) * 0.5f;
-  return d;
-}
-
-// current-frame role: the two sampling planes
-__global__ void k_derive_current(const FrameBuildPtrs* __restrict__ tbl, int level, int w, int h, int tiles_x, int tiles_y, int n_frames, int cur_flavor) {
-  for_each_tile(tiles_x, tiles_y, n_frames, [&](int bx, int by, int frame) {
-    const FrameBuildPtrs& f = tbl[frame];
-    const auto I = global_ptr<const float>(f.I[level]);         // (global_ptr.h: read once, global address space)
-    const auto Z = global_ptr<const float>(f.Z[level]);
-    const auto A = global_ptr(f.A[level]);
-    const auto B = global_ptr(f.B[level]);
-    const auto C = global_ptr(f.C[level]);
-    const int x = bx * 64 + threadIdx.x;
-    const int y = by * 4 + threadIdx.y;
-    if (x >= w || y >= h) return;
-    if (cur_flavor == kCurC) {                                  // (uniform) only the {I, Z} pair: no neighbours to read
-      gstore(C + size_t(y) * w + x, make_float2(I[size_t(y) * w + x], Z[size_t(y) * w + x]));
-      return;
-    }
-    const Derivs d = derive_at(I, Z, w, h, x, y);
-    gstore(A + size_t(y) * w + x, make_float4(d.i0, d.z0, d.idx, d.idy));
-    gstore(B + size_t(y) * w + x, make_float2(d.zdx, d.zdy));
-    if (cur_flavor & kCurC) gstore(C + size_t(y) * w + x, make_float2(d.i0, d.z0));
-  });
-}
-
-// A frame that holds only one flavour of the current role at a level gets the other: the taps A + B from the {I, Z} plane C (the
-// clamped central differences of derive_at, same operation order: bit-identical planes), or C from A.  MODE 2: the reference role
+// A frame that holds only one flavour of the current role at a level gets the other: the taps A + B from the {I, Z} plane C
+// (derive_at over the interleaved plane: bit-identical planes), or C from A.  MODE 2: the reference role
 // (R + selection count, counter zeroed before) from C -- PointSelection over a frame that has been a current frame of the window
 // sweep so far.
 template <int MODE>
 __global__ void k_from_current_plane(const FrameBuildPtrs* __restrict__ tbl, int level, int w, int h, float ithr, float dthr,
                                      int tiles_x, int tiles_y, int n_frames) {
-#pragma clang fp contract(off)
-  __shared__ int wave_counts[4];
   for_each_tile(tiles_x, tiles_y, n_frames, [&](int bx, int by, int frame) {
     const FrameBuildPtrs& f = tbl[frame];
     const auto A = global_ptr(f.A[level]);                      // (global_ptr.h: read once, global address space)
@@ -318,75 +255,31 @@ __global__ void k_from_current_plane(const FrameBuildPtrs* __restrict__ tbl, int
         const float4 a = gload((Global<const float4>)(A + at));
         gstore(Cw + at, make_float2(a.x, a.y));
       } else {
-        const auto C = global_ptr<const float2>(f.C[level]);
-        const int xp = max(x - 1, 0), xn = min(x + 1, w - 1), yp = max(y - 1, 0), yn = min(y + 1, h - 1);
-        const float2 c = gload(C + at), l = gload(C + size_t(y) * w + xp), r = gload(C + size_t(y) * w + xn), u = gload(C + size_t(yp) * w + x), d = gload(C + size_t(yn) * w + x);
-        const float idx = (r.x - l.x) * 0.5f, idy = (d.x - u.x) * 0.5f, zdx = (r.y - l.y) * 0.5f, zdy = (d.y - u.y) * 0.5f;
+        const Derivs d = derive_at(InterleavedSource{global_ptr<const float2>(f.C[level]), w}, w, h, x, y);
         if (MODE == 0) {
-          gstore(A + at, make_float4(c.x, c.y, idx, idy));
-          gstore(B + at, make_float2(zdx, zdy));
+          gstore(A + at, make_float4(d.i0, d.z0, d.idx, d.idy));
+          gstore(B + at, make_float2(d.zdx, d.zdy));
         } else {
-          ok = c.y == c.y && zdx == zdx && zdy == zdy && (fabsf(idx) > ithr || fabsf(idy) > ithr || fabsf(zdx) > dthr || fabsf(zdy) > dthr);
-          gstore(R + at, make_float2(ok ? c.y : __builtin_nanf(""), c.x));
+          ok = selects(d.z0, d.idx, d.idy, d.zdx, d.zdy, ithr, dthr);
+          gstore(R + at, make_float2(ok ? d.z0 : __builtin_nanf(""), d.i0));
         }
       }
     }
     if (MODE == 2) {
-      const int count = __popcll(__ballot(ok));
-      if (threadIdx.x == 0) wave_counts[threadIdx.y] = count;
-      __syncthreads();
-      if (threadIdx.x == 0 && threadIdx.y == 0) {
-        const int total = (wave_counts[0] + wave_counts[1]) + (wave_counts[2] + wave_counts[3]);
-        if (total) atomicAdd(f.sel_count + level, total);
-      }
-      __syncthreads();
+      add_tile_count(__popcll(__ballot(ok)), threadIdx.y, threadIdx.x, f.sel_count + level);
+      __syncthreads();                                          // the tile count's words are rewritten by the next tile
     }
-  });
-}
-
-// reference role: the streamed plane with the selection predicate folded into Z; counts the selected pixels.
-// The counter of (frame, level) must have been zeroed on the stream before.  A workgroup sweeps a 64 x 16 pixel
-// tile and issues ONE atomic for it (one atomic per wavefront-row serialised the whole kernel on 128 addresses).
-__global__ void k_derive_reference(const FrameBuildPtrs* __restrict__ tbl, int level, int w, int h, float ithr, float dthr,
-                                   int tiles_x, int tiles_y, int n_frames) {
-  __shared__ int wave_counts[4];
-  for_each_tile(tiles_x, tiles_y, n_frames, [&](int bx, int by, int frame) {
-    const FrameBuildPtrs& f = tbl[frame];
-    const auto I = global_ptr<const float>(f.I[level]);         // (global_ptr.h: read once, global address space)
-    const auto Z = global_ptr<const float>(f.Z[level]);
-    const auto R = global_ptr(f.R[level]);
-    const int x = bx * 64 + threadIdx.x;
-    int count = 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int y = (by * 4 + r) * 4 + threadIdx.y;
-      bool ok = false;
-      if (x < w && y < h) {
-        const Derivs d = derive_at(I, Z, w, h, x, y);
-        ok = d.z0 == d.z0 && d.zdx == d.zdx && d.zdy == d.zdy &&
-             (fabsf(d.idx) > ithr || fabsf(d.idy) > ithr || fabsf(d.zdx) > dthr || fabsf(d.zdy) > dthr);
-        gstore(R + size_t(y) * w + x, make_float2(ok ? d.z0 : __builtin_nanf(""), d.i0));
-      }
-      count += __popcll(__ballot(ok));      // wave-uniform
-    }
-    if (threadIdx.x == 0) wave_counts[threadIdx.y] = count;
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) {
-      const int total = (wave_counts[0] + wave_counts[1]) + (wave_counts[2] + wave_counts[3]);
-      if (total) atomicAdd(f.sel_count + level, total);
-    }
-    __syncthreads();                        // wave_counts is rewritten by the next tile
   });
 }
 
 // The role planes of SEVERAL pyramid levels of a set of frames in one launch (a single camera frame: levels 1-3 are 6000 pixels
 // together; one launch per level, each with its table upload and counter reset, is 9-12 launches of 4 microseconds of work and 8 of
-// launch latency each -- the largest item of a tracking front end's frame after the match itself).  Same arithmetic as
-// k_derive_current / k_derive_reference (derive_at): bit-identical planes.  A workgroup takes a 64 x 16 tile of one level of one frame.
-// ROLE 0: current (flavour per level: LevelSpan::flavor), ROLE 1: reference (counters of the levels zeroed before).
+// launch latency each -- the largest item of a tracking front end's frame after the match itself); with a one-level span, the path of
+// a level of odd width, which the strips (ingest_strips.hip) do not take.  A workgroup takes a 64 x 16 tile of one level of one frame.
+// ROLE 0: current, the two sampling planes (flavour per level: LevelSpan::flavor).  ROLE 1: reference, the streamed plane with the
+// selection predicate folded into Z, and the count of selected pixels (counters of the levels zeroed before).
 template <int ROLE>
 __global__ __launch_bounds__(256) void k_derive_levels(const FrameBuildPtrs* __restrict__ tbl, const LevelSpan span, int n_frames, float ithr, float dthr) {
-  __shared__ int wave_counts[4];
   const int per_frame = span.tile0[span.l1 + 1], total = per_frame * n_frames;
   for (int gi = blockIdx.x; gi < total; gi += gridDim.x) {
     const int frame = gi / per_frame, t = gi - frame * per_frame;
@@ -413,14 +306,13 @@ __global__ __launch_bounds__(256) void k_derive_levels(const FrameBuildPtrs* __r
         if (ROLE == 0 && flavor == kCurC) {                     // (uniform) only the {I, Z} pair: no neighbours to read
           gstore(C + at, make_float2(I[at], Z[at]));
         } else {
-          const Derivs d = derive_at(I, Z, w, h, x, y);
+          const Derivs d = derive_at(PlanarSource{I, Z, w}, w, h, x, y);
           if (ROLE == 0) {
             gstore(A + at, make_float4(d.i0, d.z0, d.idx, d.idy));
             gstore(B + at, make_float2(d.zdx, d.zdy));
             if (flavor & kCurC) gstore(C + at, make_float2(d.i0, d.z0));
           } else {
-            ok = d.z0 == d.z0 && d.zdx == d.zdx && d.zdy == d.zdy &&
-                 (fabsf(d.idx) > ithr || fabsf(d.idy) > ithr || fabsf(d.zdx) > dthr || fabsf(d.zdy) > dthr);
+            ok = selects(d.z0, d.idx, d.idy, d.zdx, d.zdy, ithr, dthr);
             gstore(R + at, make_float2(ok ? d.z0 : __builtin_nanf(""), d.i0));
           }
         }
@@ -428,13 +320,8 @@ __global__ __launch_bounds__(256) void k_derive_levels(const FrameBuildPtrs* __r
       if (ROLE == 1) count += __popcll(__ballot(ok));           // wave-uniform
     }
     if (ROLE == 1) {
-      if (threadIdx.x == 0) wave_counts[threadIdx.y] = count;
-      __syncthreads();
-      if (threadIdx.x == 0 && threadIdx.y == 0) {
-        const int sum = (wave_counts[0] + wave_counts[1]) + (wave_counts[2] + wave_counts[3]);
-        if (sum) atomicAdd(f.sel_count + level, sum);
-      }
-      __syncthreads();                                          // wave_counts is rewritten by the next tile
+      add_tile_count(count, threadIdx.y, threadIdx.x, f.sel_count + level);
+      __syncthreads();                                          // the tile count's words are rewritten by the next tile
     }
   }
 }
@@ -445,11 +332,6 @@ __global__ void k_zero_counts_levels(const FrameBuildPtrs* __restrict__ tbl, int
     for (int l = l0; l <= l1; ++l) tbl[i].sel_count[l] = 0;
 }
 
-__global__ void k_zero_counts(const FrameBuildPtrs* __restrict__ tbl, int n_frames, int level) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_frames) tbl[i].sel_count[level] = 0;
-}
-
 // re-selection with other thresholds (PointSelection with a different predicate), one frame
 __global__ void k_select_pack(const float4* __restrict__ A, const float2* __restrict__ B, int n, float ithr, float dthr,
                               float2* __restrict__ R, int* __restrict__ count, uint8_t* __restrict__ mask) {
@@ -458,8 +340,7 @@ __global__ void k_select_pack(const float4* __restrict__ A, const float2* __rest
   if (i < n) {
     const float4 a = A[i];
     const float2 b = B[i];
-    ok = a.y == a.y && b.x == b.x && b.y == b.y &&
-         (fabsf(a.z) > ithr || fabsf(a.w) > ithr || fabsf(b.x) > dthr || fabsf(b.y) > dthr);
+    ok = selects(a.y, a.z, a.w, b.x, b.y, ithr, dthr);
     R[i] = make_float2(ok ? a.y : __builtin_nanf(""), a.x);
     if (mask) mask[i] = ok ? 1 : 0;
   }
@@ -542,12 +423,38 @@ static int capped_grid(int tiles_x, int tiles_y, int n_frames, int max_workgroup
   return int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total);
 }
 
-void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role, bool wide,
+static void zero_counts(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int l0, int l1) {
+  k_zero_counts_levels<<<dim3((n_frames + 63) / 64), dim3(64), 0, s>>>(tbl, n_frames, l0, l1);
+}
+
+LevelSpan level_span(int l0, int l1, const int* w, const int* h, bool pixel_blocks) {
+  LevelSpan span{};
+  span.l0 = l0; span.l1 = l1;
+  int units = 0;
+  for (int l = l0; l <= l1; ++l) {
+    span.w[l] = w[l]; span.h[l] = h[l];
+    span.tile0[l] = units;
+    units += pixel_blocks ? (w[l] * h[l] + 511) / 512 : ((w[l] + 63) / 64) * ((h[l] + 15) / 16);
+  }
+  span.tile0[l1 + 1] = units;
+  return span;
+}
+
+// one level of k_derive_levels: the form of launch_derive_current / launch_derive_reference at odd widths
+static LevelSpan one_level_span(int level, int w, int h, int flavor) {
+  int ws[kMaxLevels] = {}, hs[kMaxLevels] = {};
+  ws[level] = w; hs[level] = h;
+  LevelSpan span = level_span(level, level, ws, hs);
+  span.flavor[level] = flavor;
+  return span;
+}
+
+void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, float scale, int w0, int h0, int levels, int role, bool strips,
                            float ithr, float dthr, int max_workgroups, int cur_flavor, int c_levels, int colour_channels, bool stream_nt,
                            bool depth_f32) {
   depth_f32 = depth_f32 || colour_channels == kChF32;
-  if (ingest_strips_supports(w0, wide, colour_channels == kChF32)) {
-    if (role == 1) k_zero_counts<<<dim3((n_frames + 63) / 64), dim3(64), 0, s>>>(tbl, n_frames, 0);
+  if (role == 1) zero_counts(s, tbl, n_frames, 0, 0);
+  if (strips) {
     launch_ingest_strips(s, tbl, n_frames, scale, w0, h0, levels, role, ithr, dthr, max_workgroups, cur_flavor, c_levels, colour_channels, stream_nt,
                          depth_f32);
     return;
@@ -555,32 +462,16 @@ void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frame
   const int tx = (w0 + kB0W - 1) / kB0W, ty = (h0 + kB0H - 1) / kB0H;
   const dim3 grid(capped_grid(tx, ty, n_frames, max_workgroups)), block(256);
   const int lv = levels < 4 ? levels : 4;
-  if (role == 1) k_zero_counts<<<dim3((n_frames + 63) / 64), dim3(64), 0, s>>>(tbl, n_frames, 0);
-#define DVO_LAUNCH_B0(ROLE, WIDE) k_build_from_raw<ROLE, WIDE><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, tx, ty, n_frames, cur_flavor)
-#define DVO_LAUNCH_B0_COLOUR(ROLE, CH) \
-  k_build_from_raw<ROLE, false, CH><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, tx, ty, n_frames, cur_flavor)
-#define DVO_LAUNCH_B0_ZF(ROLE, CH) \
-  k_build_from_raw<ROLE, false, CH, true><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, tx, ty, n_frames, cur_flavor)
-#define DVO_LAUNCH_B0_ZF_ROLE(CH) \
-  do { if (role == 0) DVO_LAUNCH_B0_ZF(0, CH); else if (role == 1) DVO_LAUNCH_B0_ZF(1, CH); else DVO_LAUNCH_B0_ZF(-1, CH); } while (0)
-  if (depth_f32) {
-    if (colour_channels == 3) DVO_LAUNCH_B0_ZF_ROLE(3);
-    else if (colour_channels == 4) DVO_LAUNCH_B0_ZF_ROLE(4);
-    else if (colour_channels == kChF32) DVO_LAUNCH_B0_ZF_ROLE(kChF32);
-    else DVO_LAUNCH_B0_ZF_ROLE(0);
-  } else if (colour_channels == 3) {
-    if (role == 0) DVO_LAUNCH_B0_COLOUR(0, 3); else if (role == 1) DVO_LAUNCH_B0_COLOUR(1, 3); else DVO_LAUNCH_B0_COLOUR(-1, 3);
-  } else if (colour_channels == 4) {
-    if (role == 0) DVO_LAUNCH_B0_COLOUR(0, 4); else if (role == 1) DVO_LAUNCH_B0_COLOUR(1, 4); else DVO_LAUNCH_B0_COLOUR(-1, 4);
-  } else if (wide) {
-    if (role == 0) DVO_LAUNCH_B0(0, true); else if (role == 1) DVO_LAUNCH_B0(1, true); else DVO_LAUNCH_B0(-1, true);
-  } else {
-    if (role == 0) DVO_LAUNCH_B0(0, false); else if (role == 1) DVO_LAUNCH_B0(1, false); else DVO_LAUNCH_B0(-1, false);
-  }
-#undef DVO_LAUNCH_B0_ZF_ROLE
-#undef DVO_LAUNCH_B0_ZF
-#undef DVO_LAUNCH_B0_COLOUR
-#undef DVO_LAUNCH_B0
+  with_value<0, 1, -1>(role, [&](auto ROLE) {
+    with_value<3, 4, kChF32, 0>(colour_channels, [&](auto CH) {
+      with_bool(depth_f32, [&](auto ZF) {
+        constexpr int kCh = decltype(CH)::value;
+        constexpr bool kZf = decltype(ZF)::value;
+        if constexpr (kCh != kChF32 || kZf)
+          k_build_from_raw<decltype(ROLE)::value, kCh, kZf><<<grid, block, 0, s>>>(tbl, scale, w0, h0, lv, ithr, dthr, tx, ty, n_frames, cur_flavor);
+      });
+    });
+  });
 }
 
 void launch_pyr_down(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h) {
@@ -588,63 +479,46 @@ void launch_pyr_down(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int
   k_pyr_down<<<dim3((ow + 63) / 64, (oh + 3) / 4, n_frames), dim3(64, 4), 0, s>>>(tbl, level, w, h);
 }
 
-// (even widths: the strip form, ingest_strips.hip)
+// (even widths: the strip form, ingest_strips.hip; odd ones: k_derive_levels over the one level)
 void launch_derive_current(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int max_workgroups, int cur_flavor,
                            bool stream_nt) {
   if (derive_strips_supports(w)) {
     launch_derive_strips(s, tbl, n_frames, level, w, h, 0, 0.0f, 0.0f, max_workgroups, cur_flavor, stream_nt);
     return;
   }
-  const int tx = (w + 63) / 64, ty = (h + 3) / 4;
-  k_derive_current<<<dim3(capped_grid(tx, ty, n_frames, max_workgroups)), dim3(64, 4), 0, s>>>(tbl, level, w, h, tx, ty, n_frames, cur_flavor);
+  launch_derive_levels(s, tbl, n_frames, one_level_span(level, w, h, cur_flavor), 0, 0.0f, 0.0f, max_workgroups);
 }
 
 void launch_from_current_plane(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int mode, float ithr, float dthr,
                                int max_workgroups) {
   const int tx = (w + 63) / 64, ty = (h + 3) / 4;
   const dim3 grid(capped_grid(tx, ty, n_frames, max_workgroups)), block(64, 4);
-  if (mode == 2) k_zero_counts<<<dim3((n_frames + 63) / 64), dim3(64), 0, s>>>(tbl, n_frames, level);
-  if (mode == 0) k_from_current_plane<0><<<grid, block, 0, s>>>(tbl, level, w, h, ithr, dthr, tx, ty, n_frames);
-  else if (mode == 1) k_from_current_plane<1><<<grid, block, 0, s>>>(tbl, level, w, h, ithr, dthr, tx, ty, n_frames);
-  else k_from_current_plane<2><<<grid, block, 0, s>>>(tbl, level, w, h, ithr, dthr, tx, ty, n_frames);
+  if (mode == 2) zero_counts(s, tbl, n_frames, level, level);
+  with_value<0, 1, 2>(mode, [&](auto MODE) {
+    k_from_current_plane<decltype(MODE)::value><<<grid, block, 0, s>>>(tbl, level, w, h, ithr, dthr, tx, ty, n_frames);
+  });
 }
 
 void launch_derive_levels(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, const LevelSpan& span, int role, float ithr, float dthr,
                           int max_workgroups) {
   const int total = span.tile0[span.l1 + 1] * n_frames;
   const dim3 grid(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total), block(64, 4);
-  if (role == 1) {
-    k_zero_counts_levels<<<dim3((n_frames + 63) / 64), dim3(64), 0, s>>>(tbl, n_frames, span.l0, span.l1);
-    k_derive_levels<1><<<grid, block, 0, s>>>(tbl, span, n_frames, ithr, dthr);
-  } else {
-    k_derive_levels<0><<<grid, block, 0, s>>>(tbl, span, n_frames, ithr, dthr);
-  }
+  if (role == 1) zero_counts(s, tbl, n_frames, span.l0, span.l1);
+  with_value<1, 0>(role, [&](auto ROLE) { k_derive_levels<decltype(ROLE)::value><<<grid, block, 0, s>>>(tbl, span, n_frames, ithr, dthr); });
 }
 
 void launch_derive_reference(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, float ithr, float dthr,
                              int max_workgroups, bool stream_nt) {
-  k_zero_counts<<<dim3((n_frames + 63) / 64), dim3(64), 0, s>>>(tbl, n_frames, level);
   if (derive_strips_supports(w)) {
+    zero_counts(s, tbl, n_frames, level, level);
     launch_derive_strips(s, tbl, n_frames, level, w, h, 1, ithr, dthr, max_workgroups, 0, stream_nt);
     return;
   }
-  const int tx = (w + 63) / 64, ty = (h + 15) / 16;
-  k_derive_reference<<<dim3(capped_grid(tx, ty, n_frames, max_workgroups)), dim3(64, 4), 0, s>>>(tbl, level, w, h, ithr, dthr, tx, ty, n_frames);
+  launch_derive_levels(s, tbl, n_frames, one_level_span(level, w, h, 0), 1, ithr, dthr, max_workgroups);
 }
 
 void launch_select_pack(hipStream_t s, const float4* A, const float2* B, int n, float ithr, float dthr, float2* R, int* count, uint8_t* mask) {
   k_select_pack<<<dim3((n + 255) / 256), dim3(256), 0, s>>>(A, B, n, ithr, dthr, R, count, mask);
-}
-
-void apply_selection_span(LevelSpan& span, int l0, int l1, const int* w, const int* h) {
-  span.l0 = l0; span.l1 = l1;
-  int blocks = 0;
-  for (int l = l0; l <= l1; ++l) {
-    span.w[l] = w[l]; span.h[l] = h[l]; span.flavor[l] = 0;
-    span.tile0[l] = blocks;
-    blocks += (w[l] * h[l] + 511) / 512;
-  }
-  span.tile0[l1 + 1] = blocks;
 }
 
 void launch_apply_selection(hipStream_t s, const SelectionApply* tbl, int n_frames, const LevelSpan& span, int max_workgroups) {

@@ -41,7 +41,10 @@ def test_library_loaded_and_device_present(gpu_ctx):
 @pytest.mark.parametrize("w,h,levels", [(640, 480, 4), (160, 120, 3), (100, 76, 2),
                                         # the strip ingest (even rows of 4-pixel groups): ragged last strip, heights that are no multiple of
                                         # the 8-row strip or of the 32-row group, odd coarser levels; a one-strip image
-                                        (140, 62, 3), (388, 122, 4), (128, 8, 2), (132, 34, 4)])
+                                        (140, 62, 3), (388, 122, 4), (128, 8, 2), (132, 34, 4),
+                                        # the tile kernels: level 1 of 65 x 17 (odd width: k_derive_levels over one level, two tile columns and
+                                        # rows, the second of each one pixel); the tile ingest and the float-plane derive at an odd level 0
+                                        (130, 34, 2), (65, 17, 1)])
 def test_pyramid_planes_bit_exact(gpu_ctx, w, h, levels):
     pair = cm.synth(17, w, h)
     oref, _ = cm.oracle_pyramids(pair, levels)
@@ -1152,7 +1155,8 @@ def test_streaming_upload_from_host_memory(gpu_ctx):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("w,h,levels", [(320, 240, 3), (102, 78, 3), (640, 480, 4), (140, 62, 3), (388, 122, 4)])
+@pytest.mark.parametrize("w,h,levels", [(320, 240, 3), (102, 78, 3), (640, 480, 4), (140, 62, 3), (388, 122, 4),
+                                        (65, 33, 2)])    # the tile ingest in both roles, the other role from the raw copy and from plane C
 def test_role_aware_ingest_is_bit_identical(gpu_ctx, w, h, levels):
     """dvo_hip_frames_update_raw_as: level 0 written straight from the raw planes into the role's planes (no float planes at
     level 0, 4-pixel-wide loads when the rows allow it).  Same planes, same selection, same alignment results as frames built
