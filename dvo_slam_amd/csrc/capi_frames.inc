@@ -97,6 +97,10 @@ const int kFusedLoglikMaxPixelsBatch = 320 * 240;  // batches of 512 pairs and m
 
 // RgbdCameraPyramid::build (rgbd_image.cpp:283-296) + RgbdCamera ctor template (:186-204)
 int get_camera(dvo_hip_context* ctx, int w, int h, const float K[4], int levels, const CameraGeom** out) {
+  // (before anything is allocated or compared: a NaN would go into the tx / ty tables and into the memcmp key below)
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(K[k])) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create: K must be finite");
+  if (!(K[0] > 0.0f && K[1] > 0.0f)) return fail(ctx, DVO_HIP_ERR_INVALID, "frame_create: need fx > 0 and fy > 0");
   // one geometry per (size, intrinsics), with the tables of every level the size admits: frames of one camera share it
   // whatever level count each was created with (a batch only needs FirstLevel + 1 levels on each pyramid)
   for (CameraGeom* c : ctx->cameras)

@@ -122,7 +122,8 @@ int dvo_hip_device_count(void);
  * (dvo_core/include/dvo/core/rgbd_image.h:127-147,242-262; rgbd_image.cpp:156-172,283-296,419-543)
  * Builds the whole device-resident pyramid: 2x2-mean intensity, subsampled depth, halved
  * intrinsics, clamped central-difference derivatives, interleaved sampling planes.
- * K = {fx, fy, ox, oy} of level 0.  `levels` = Config::getNumLevels() = FirstLevel + 1. */
+ * K = {fx, fy, ox, oy} of level 0.  `levels` = Config::getNumLevels() = FirstLevel + 1.
+ * Every dvo_hip_frame_create_* refuses a K that is not finite or has fx <= 0 or fy <= 0 with DVO_HIP_ERR_INVALID, before it allocates. */
 int dvo_hip_frame_create_f32(dvo_hip_context* ctx, int width, int height, const float K[4],
                              const float* intensity /* 0..255 */, const float* depth /* metres, NaN invalid */,
                              int levels, dvo_hip_frame** out);

@@ -16,10 +16,11 @@ from dvo_slam_amd import _lib as hl  # noqa: E402
 _pairs = {}
 
 
-def synth(seed, w=640, h=480):
-    key = (seed, w, h)
+def synth(seed, w=640, h=480, K=None):
+    """K: the intrinsics [fx, fy, ox, oy] the pair is rendered with (tests/cameras.py); None = fr1 scaled to the width"""
+    key = (seed, w, h, None if K is None else np.asarray(K, np.float32).tobytes())
     if key not in _pairs:
-        _pairs[key] = po.synth_pair(seed, w, h)
+        _pairs[key] = po.synth_pair(seed, w, h, K)
     return _pairs[key]
 
 
