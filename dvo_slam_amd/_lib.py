@@ -80,6 +80,29 @@ class RenderParams(C.Structure):
                 ("min_points", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class GraphParams(C.Structure):
+    """dvo_hip_graph_params: the schedule of a pose-graph optimisation (dvo_hip_graph_optimize)."""
+    _fields_ = [("max_iterations", C.c_int32), ("cg_max_iterations", C.c_int32), ("cg_tolerance", C.c_double),
+                ("min_relative_decrease", C.c_double), ("initial_damping_scale", C.c_double), ("reserved", C.c_double * 3)]
+
+
+class GraphIteration(C.Structure):
+    """dvo_hip_graph_iteration: one Levenberg-Marquardt trial."""
+    _fields_ = [("cost_before", C.c_double), ("cost_after", C.c_double), ("damping", C.c_double), ("cg_iterations", C.c_int32),
+                ("cg_status", C.c_int32), ("accepted", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GraphReport(C.Structure):
+    """dvo_hip_graph_report: what an optimisation did."""
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("accepted", C.c_int32), ("cg_iterations", C.c_int32),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("final_damping", C.c_double), ("reserved", C.c_double * 4)]
+
+
+# DVO_HIP_GRAPH_*: the status of an optimisation, and DVO_HIP_GRAPH_CG_*: of one conjugate-gradient solve
+GRAPH_STATUS = {0: "converged", 1: "iteration_cap", 2: "damping_overflow", 3: "stalled", 4: "nothing_to_do"}
+GRAPH_CG_STATUS = {1: "converged", 2: "breakdown", 3: "cholesky", 4: "zero_rhs", 5: "iteration_cap"}
+GRAPH_MAX_VERTICES, GRAPH_MAX_EDGES = 1 << 20, 1 << 22
+
 # every symbol include/dvo_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "dvo_hip_context_create", "dvo_hip_context_destroy", "dvo_hip_last_error", "dvo_hip_context_stream",
@@ -100,6 +123,9 @@ EXPORTS = [
     "dvo_hip_map_create", "dvo_hip_map_destroy", "dvo_hip_map_clear", "dvo_hip_map_insert", "dvo_hip_map_stats", "dvo_hip_map_extract",
     "dvo_hip_frames_world_points", "dvo_hip_map_remove", "dvo_hip_map_move", "dvo_hip_map_rehash",
     "dvo_hip_render_params_default", "dvo_hip_map_render", "dvo_hip_map_render_frames", "dvo_hip_time_map_render",
+    "dvo_hip_graph_create", "dvo_hip_graph_destroy", "dvo_hip_graph_set_vertices", "dvo_hip_graph_set_poses", "dvo_hip_graph_set_edges",
+    "dvo_hip_graph_params_default", "dvo_hip_graph_optimize", "dvo_hip_graph_get_poses", "dvo_hip_graph_edge_stats",
+    "dvo_hip_graph_linearise", "dvo_hip_graph_multiply",
 ]
 
 ROLE_CURRENT, ROLE_REFERENCE = 0, 1
@@ -228,6 +254,21 @@ def lib():
         L.dvo_hip_map_render.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, fp, dp, rp, C.POINTER(vp), C.POINTER(vp), C.c_int]
         L.dvo_hip_map_render_frames.argtypes = [vp, vp, C.c_int, C.POINTER(vp), dp, rp, C.c_int, C.POINTER(Config), C.c_uint]
         L.dvo_hip_time_map_render.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, fp, dp, rp, C.c_int, fp]
+    if hasattr(L, "dvo_hip_graph_create"):   # (likewise: an older build optimises no pose graph)
+        dp, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        L.dvo_hip_graph_create.argtypes = [vp, C.POINTER(vp)]
+        L.dvo_hip_graph_destroy.argtypes = [vp, vp]
+        L.dvo_hip_graph_destroy.restype = None
+        L.dvo_hip_graph_set_vertices.argtypes = [vp, vp, C.c_int, dp, C.POINTER(C.c_uint8)]
+        L.dvo_hip_graph_set_poses.argtypes = [vp, vp, C.c_int, dp]
+        L.dvo_hip_graph_set_edges.argtypes = [vp, vp, C.c_int, i32p, i32p, dp, dp, dp]
+        L.dvo_hip_graph_params_default.argtypes = []
+        L.dvo_hip_graph_params_default.restype = GraphParams
+        L.dvo_hip_graph_optimize.argtypes = [vp, vp, C.POINTER(GraphParams), C.POINTER(GraphReport), C.POINTER(GraphIteration), C.c_int]
+        L.dvo_hip_graph_get_poses.argtypes = [vp, vp, C.c_int, dp]
+        L.dvo_hip_graph_edge_stats.argtypes = [vp, vp, C.c_int, dp, dp]
+        L.dvo_hip_graph_linearise.argtypes = [vp, vp, dp, dp, dp, dp, dp, dp]
+        L.dvo_hip_graph_multiply.argtypes = [vp, vp, C.c_double, dp, dp, dp, dp, dp, dp]
     L.dvo_hip_context_device.argtypes = [vp]
     L.dvo_hip_comm_get_unique_id.argtypes = [vp]
     L.dvo_hip_comm_create.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]

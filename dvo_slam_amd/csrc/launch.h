@@ -103,6 +103,23 @@ void launch_map_render(hipStream_t s, const MapTable& m, const MapView* views, c
                        unsigned long long* zbuf);
 bool map_render_preloads();
 
+// pose_graph.hip: the stages of the pose-graph optimiser (pose_graph.h), kPgBlock edges or vertices per workgroup.  *_partials: one
+// double per workgroup, a subtree of the scalar's tree (rz_partials: two rows of them).  launch_pg_linearise: every edge's record at
+// `poses` (with_blocks: the weighted blocks too) and the partials of the cost.  launch_pg_gather: D and b of every vertex and each
+// workgroup's largest diagonal entry.  launch_pg_cg_init: the preconditioner and the start of a solve (st cleared by the caller).
+// launch_pg_multiply / launch_pg_cg_update: iteration `it` of the solve; both return at once when it has ended (given: the multiply of
+// the p stored at kPgP0, the test hook).  launch_pg_apply: the step into `out`.  launch_pg_reduce: out[0], out[1] = the trees over a, b.
+struct PgGraph;
+struct PgCgState;
+void launch_pg_linearise(hipStream_t s, const PgGraph& g, const double* poses, bool with_blocks, double* cost_partials);
+void launch_pg_gather(hipStream_t s, const PgGraph& g, double* max_partials);
+void launch_pg_cg_init(hipStream_t s, const PgGraph& g, PgCgState* st, double lambda, double* rz_partials);
+void launch_pg_multiply(hipStream_t s, const PgGraph& g, PgCgState* st, const double* rz_partials, double* pap_partials, int it, double lambda,
+                        double tolerance, bool given);
+void launch_pg_cg_update(hipStream_t s, const PgGraph& g, PgCgState* st, const double* pap_partials, double* rz_partials, int it);
+void launch_pg_apply(hipStream_t s, const PgGraph& g, double lambda, const double* poses, double* out, double* scale_partials);
+void launch_pg_reduce(hipStream_t s, const double* a, int n_a, const double* b, int n_b, double* out);
+
 // align_kernels.hip / align_mfma.hip
 // variant 5 (default): Gram accumulation on the matrix cores (align_mfma.hip); variant 0: the all-VALU schedule with the DPP + LDS
 // two-stage reduction (align_kernels.hip).  Same outputs.

@@ -894,6 +894,86 @@ int dvo_hip_gather_records_begin(dvo_hip_comm* comm, const void* mine, size_t by
 int dvo_hip_gather_records_end(dvo_hip_comm* comm, int ticket, void* all, size_t all_bytes);
 int dvo_hip_gather_records(dvo_hip_comm* comm, const void* mine, size_t bytes_mine, size_t bytes_per_rank, void* all, size_t all_bytes);
 
+/* ---- the keyframe pose graph, optimised on the device -----------------------------------------------------------------------------
+ * The reference's back end builds a g2o graph of VertexSE3 / EdgeSE3 with an optional Cauchy kernel and runs Levenberg-Marquardt on it
+ * after every keyframe and at the end of a sequence (dvo_slam/src/keyframe_graph.cpp:256-285, 475-489, 840-845; the local map's:
+ * dvo_slam/src/local_map.cpp:79-88, 208-213).  A dvo_hip_graph is that problem and that step: Levenberg-Marquardt with g2o's
+ * defaults around a block-Jacobi preconditioned conjugate-gradient solve, all in float64 (definitions, schedule and the order of every
+ * sum: dvo_slam_amd/csrc/pose_graph.h).  The result is deterministic: a function of the vertices and of the edges
+ * in the order given -- not independent of that order -- and the same bits run after run.  The optimised poses are what dvo_hip_map_move
+ * takes as new_poses.
+ * Poses and measurements: row-major 4 x 4 doubles, camera -> world, n x 16 / m x 16 like the map's.  Information: m x 36, row-major,
+ * rows and columns translation first, then rotation, taken AS GIVEN: the reference hands Result.Information (twist order) straight to
+ * setInformation (keyframe_graph.cpp:628); hand dvo_hip_result::information over the same way to get what it gets.
+ * Limits: n <= 2^20 vertices, m <= 2^22 edges; an edge costs about 1 KB of device memory, a vertex about 1 KB.
+ * Errors: DVO_HIP_ERR_INVALID for from == to, an index out of range, a non-finite entry, delta < 0, n <= 0, or a graph of another
+ * context -- checked before anything is launched or changed; DVO_HIP_ERR_NO_DEVICE without a gfx950, as everywhere else. */
+typedef struct dvo_hip_graph dvo_hip_graph;
+
+/* status of an optimisation (dvo_hip_graph_report::status) */
+#define DVO_HIP_GRAPH_CONVERGED 0          /* an accepted step lowered the cost by less than min_relative_decrease, or the gradient is zero */
+#define DVO_HIP_GRAPH_ITERATION_CAP 1
+#define DVO_HIP_GRAPH_DAMPING_OVERFLOW 2
+#define DVO_HIP_GRAPH_STALLED 3            /* ten rejected trials in a row (g2o's maxTrialsAfterFailure) */
+#define DVO_HIP_GRAPH_NOTHING_TO_DO 4      /* no free vertex or no edge: the graph optimises to itself */
+/* status of one conjugate-gradient solve (dvo_hip_graph_iteration::cg_status) */
+#define DVO_HIP_GRAPH_CG_CONVERGED 1
+#define DVO_HIP_GRAPH_CG_BREAKDOWN 2       /* p^T A p or r^T z not positive and finite: the trial is rejected, no pose takes a NaN */
+#define DVO_HIP_GRAPH_CG_CHOLESKY 3        /* a vertex's diagonal block plus damping has no Cholesky factor */
+#define DVO_HIP_GRAPH_CG_ZERO_RHS 4
+#define DVO_HIP_GRAPH_CG_ITERATION_CAP 5   /* the step the cap left is used, as g2o uses it */
+
+typedef struct dvo_hip_graph_params {
+  int32_t max_iterations;          /* Levenberg-Marquardt trials, accepted or not (default 50) */
+  int32_t cg_max_iterations;       /* default 200 */
+  double cg_tolerance;             /* relative residual in the M^-1 norm, sqrt(r^T M^-1 r / b^T M^-1 b) (default 1e-8) */
+  double min_relative_decrease;    /* default 1e-9 */
+  double initial_damping_scale;    /* g2o's tau: lambda_0 = tau * the largest diagonal entry of H (default 1e-5) */
+  double reserved[3];
+} dvo_hip_graph_params;
+
+typedef struct dvo_hip_graph_iteration {
+  double cost_before, cost_after;  /* sum of rho at the estimate and at the stepped poses */
+  double damping;                  /* lambda of this trial */
+  int32_t cg_iterations, cg_status, accepted, reserved;
+} dvo_hip_graph_iteration;
+
+typedef struct dvo_hip_graph_report {
+  int32_t status, iterations, accepted, cg_iterations;
+  double initial_cost, final_cost, final_damping;
+  double reserved[4];
+} dvo_hip_graph_report;
+
+int dvo_hip_graph_create(dvo_hip_context* ctx, dvo_hip_graph** out);
+void dvo_hip_graph_destroy(dvo_hip_context* ctx, dvo_hip_graph* graph);
+/* The vertices (g2o: addVertex + setEstimate + setFixed, keyframe_graph.cpp:702-739, local_map.cpp:88-98).  fixed: n bytes, non-zero =
+ * held, or null.  Drops the edges of an earlier set. */
+int dvo_hip_graph_set_vertices(dvo_hip_context* ctx, dvo_hip_graph* graph, int n, const double* poses, const unsigned char* fixed_or_null);
+/* a new estimate for the same n vertices and the same edges (setEstimate, local_map.cpp:153-168) */
+int dvo_hip_graph_set_poses(dvo_hip_context* ctx, dvo_hip_graph* graph, int n, const double* poses);
+/* The edges, replacing all earlier ones (addEdge, keyframe_graph.cpp:620-636; local_map.cpp:104-116).  delta: the Cauchy kernel's
+ * width per edge, 0 = no kernel; null = none has one.  m = 0 removes them all.  The per-vertex incidence lists are built here. */
+int dvo_hip_graph_set_edges(dvo_hip_context* ctx, dvo_hip_graph* graph, int m, const int32_t* from, const int32_t* to, const double* measurements,
+                            const double* information, const double* delta_or_null);
+dvo_hip_graph_params dvo_hip_graph_params_default(void);
+/* initializeOptimization + optimize (keyframe_graph.cpp:475-489, local_map.cpp:208-213).  params null = the defaults.  records (may be
+ * null): one per trial, the first max_records of them.  The estimate becomes the last accepted one. */
+int dvo_hip_graph_optimize(dvo_hip_context* ctx, dvo_hip_graph* graph, const dvo_hip_graph_params* params, dvo_hip_graph_report* out,
+                           dvo_hip_graph_iteration* records_or_null, int max_records);
+int dvo_hip_graph_get_poses(dvo_hip_context* ctx, dvo_hip_graph* graph, int n, double* poses_out);
+/* chi2 = e^T Omega e and the kernel's weight (1 without a kernel) of every edge at the current estimate: what
+ * removeOutlierConstraints thresholds (keyframe_graph.cpp:643-674) */
+int dvo_hip_graph_edge_stats(dvo_hip_context* ctx, dvo_hip_graph* graph, int m, double* chi2_out, double* weight_out);
+/* One stage each, results to the host -- the test hooks, as dvo_hip_level_iteration is for match().  Every output may be null.
+ * linearise: per edge the error (m x 6), chi2, weight, the blocks w Ji^T Omega Ji | w Ji^T Omega Jj | w Jj^T Omega Jj (m x 108, row-major
+ * 6 x 6 each), the gradient parts -w Ji^T Omega e | -w Jj^T Omega e (m x 12), and the cost.  multiply: linearises, gathers, factorises
+ * D_v + damping I, then y = (H + damping I) p over the free vertices for the given p (n x 6): y (n x 6), p^T y, the gathered diagonal
+ * blocks (n x 36), right-hand side (n x 6) and block inverses (n x 36). */
+int dvo_hip_graph_linearise(dvo_hip_context* ctx, dvo_hip_graph* graph, double* error_out, double* chi2_out, double* weight_out, double* blocks_out,
+                            double* gradient_out, double* cost_out);
+int dvo_hip_graph_multiply(dvo_hip_context* ctx, dvo_hip_graph* graph, double damping, const double* p, double* y_out, double* pty_out,
+                           double* diagonal_out, double* rhs_out, double* inverse_out);
+
 const char* dvo_hip_version(void);
 
 #ifdef __cplusplus

@@ -2,15 +2,19 @@
 //
 // Interface of the reference's LocalMap (dvo_slam/include/dvo_slam/local_map.h:44-88) as the tracking front-end uses
 // it (local_tracker.cpp:141-216): keyframe, active frame, pose of the active frame = keyframe pose * last keyframe
-// measurement (local_map.cpp:196-200).  The reference stores the measurements as a g2o pose graph and can optimise it;
-// graph optimisation is outside this engine's scope, so the measurements are kept as a plain edge
-// list (`measurements()`) that a g2o-equipped back-end can load in place of getGraph().
+// measurement (local_map.cpp:196-200).  The reference stores the measurements as a g2o pose graph with the keyframe's vertex
+// fixed (local_map.cpp:79-88) and optimises it for 50 iterations when the map is closed (local_map.cpp:208-213).  Here the
+// measurements are kept as a plain edge list (`measurements()`); optimize() loads them into a dvo_slam::PoseGraph
+// (dvo_slam/pose_graph.h: vertex 0 the keyframe, fixed; vertex k the k-th frame; edge i the i-th measurement), runs the
+// engine's pose-graph optimiser on the device and writes the poses of the frames back.  There is no getGraph(): a back end that
+// merges local maps into its keyframe graph (keyframe_graph.cpp:702-739) reads measurements() and the poses instead.
 #pragma once
 
 #include <memory>
 #include <vector>
 
 #include "dvo/core/rgbd_image.h"
+#include "dvo_slam/pose_graph.h"
 #include "dvo_slam/tracking_result_evaluation.h"
 
 namespace dvo_slam {
@@ -65,6 +69,26 @@ class LocalMap {
   }
 
   const std::vector<Measurement>& measurements() const { return measurements_; }
+  // pose estimate of the k-th frame added (k from 0)
+  const dvo::core::AffineTransformd& getFramePose(size_t k) const { return poses_[k]; }
+
+  // the map as a pose graph: vertex 0 the keyframe, fixed (local_map.cpp:79-88); vertex k the k-th frame; edge i measurement i
+  void load(PoseGraph& graph) const {
+    graph.addVertex(0, keyframe_pose_, true);
+    for (size_t k = 0; k < poses_.size(); ++k) graph.addVertex(int(k) + 1, poses_[k], false);
+    for (size_t i = 0; i < measurements_.size(); ++i)
+      graph.addEdge(int(i), measurements_[i].from, measurements_[i].to, measurements_[i].transformation, measurements_[i].information);
+  }
+  // The reference's optimize() (local_map.cpp:208-213): 50 iterations over the map's graph, the keyframe held.  Returns the
+  // Levenberg-Marquardt trials run, or -1 on an error (dvo_hip_last_error), the poses then as they were.
+  int optimize(int iterations = 50) {
+    PoseGraph graph;
+    load(graph);
+    const int trials = graph.optimize(iterations);
+    if (trials < 0) return trials;
+    for (size_t k = 0; k < poses_.size(); ++k) poses_[k] = graph.estimate(int(k) + 1);
+    return trials;
+  }
   const std::vector<dvo::core::RgbdImagePyramid::Ptr>& frames() const { return frames_; }
 
  private:
