@@ -412,6 +412,57 @@ def spd(rng, scale=100.0):
     return scale * (A @ A.T / 6 + np.eye(6))
 
 
+# ---- the same for many poses at once: the graphs of edge_graphs() reach 196613 vertices, where one random_pose call per vertex takes seconds ----
+
+def quat_matrices(w, v):
+    """quat_matrix for w [k] and v [k, 3]: [k, 3, 3]; (w, v) of unit length, w of either sign"""
+    x, y, z = v[:, 0], v[:, 1], v[:, 2]
+    R = np.empty((len(w), 3, 3))
+    R[:, 0, 0], R[:, 0, 1], R[:, 0, 2] = 1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)
+    R[:, 1, 0], R[:, 1, 1], R[:, 1, 2] = 2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)
+    R[:, 2, 0], R[:, 2, 1], R[:, 2, 2] = 2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)
+    return R
+
+
+def poses_of(t, w, v):
+    """[k, 4, 4] poses with translations t [k, 3] and the rotations of the unit quaternions (w [k], v [k, 3])"""
+    X = np.zeros((len(w), 4, 4))
+    X[:, :3, :3], X[:, :3, 3], X[:, 3, 3] = quat_matrices(w, v), t, 1.0
+    return X
+
+
+def random_poses(rng, k, spread=2.0, turn=0.6):
+    """k poses as random_pose draws one"""
+    v = rng.normal(size=(k, 3))
+    v *= (rng.uniform(0, turn, k) / np.linalg.norm(v, axis=1))[:, None]
+    return poses_of(rng.uniform(-spread, spread, (k, 3)), np.sqrt(1 - (v * v).sum(1)), v)
+
+
+def spds(rng, k, scale=100.0):
+    A = rng.normal(size=(k, 6, 6))
+    return scale * (A @ A.transpose(0, 2, 1) / 6 + np.eye(6))
+
+
+def ring_with_chords(n, m, rng):
+    """(from, to) of m edges: the ring a -> a + 1 first, then random chords (repeats allowed, none from a vertex to itself)"""
+    a = np.arange(min(n, m))
+    i, j = a, (a + 1) % n
+    if m > len(a):
+        ci = rng.integers(0, n, m - len(a))
+        i, j = np.concatenate([i, ci]), np.concatenate([j, (ci + rng.integers(1, n, m - len(a))) % n])
+    return i.astype(np.int32), j.astype(np.int32)
+
+
+def graph_of(n, i, j, seed, kernel_every=3):
+    """The conventions of the GPU tier's random_graph, from arrays: n random poses, edges i -> j measured a few centimetres and 0.05 off,
+    dense positive definite information, a kernel of width 2 on every third edge, every seventh vertex fixed (the first of fewer than four)"""
+    rng = np.random.default_rng(seed)
+    X = random_poses(rng, n)
+    Z = np.linalg.inv(X[i]) @ X[j] @ random_poses(rng, len(i), 0.1, 0.05)
+    fixed = np.arange(n) % 7 == 3 if n > 3 else np.arange(n) == 0
+    return dict(start=X, fixed=fixed, edges=(i, j, Z, spds(rng, len(i))), delta=np.where(np.arange(len(i)) % kernel_every == 0, 2.0, 0.0))
+
+
 # ---- the graphs of the convergence tests (tests/test_gpu_pose_graph.py runs the same three on the device) ---------------------------------
 
 def helix(n):
@@ -496,6 +547,222 @@ def yardstick_run(name):
     return g, report, h.poses(), h.edge_stats()[1], h
 
 
+# ---- the inputs of tests/test_gpu_pose_graph_edges.py: what each is there for is asserted on the yardstick below, without a GPU ------------
+
+HALF_TURNS = (125.0, 170.0, 179.999, 180.0, 200.0)                   # degrees of the relative rotation error; 200 = 160 about the opposite axis
+HALF_TURN_DELTAS = (0.0, 1e-3, 2.0, 1e6)
+
+
+def half_turn_graph():
+    """70 poses, the ring and 80 chords.  Five edges of six have an error Z^-1 X_i^-1 X_j that turns by HALF_TURNS in turn about an axis
+    dominated by x, y, z in turn and lies 0.1 off, under a kernel of width HALF_TURN_DELTAS in turn (60 combinations, each at least
+    twice); the sixth is an ordinary edge of graph_of.  Every angle is beyond 120 degrees, where the trace turns negative."""
+    g = graph_of(70, *ring_with_chords(70, 150, np.random.default_rng(31)), 32)
+    rng = np.random.default_rng(33)
+    i, j, Z, W = g["edges"]
+    at = np.nonzero(np.arange(150) % 6 != 5)[0]
+    h = np.arange(len(at))
+    half = np.radians(np.array(HALF_TURNS))[h % 5] / 2
+    axis = np.array([[1.0, 0.2, -0.1], [0.15, 1.0, 0.25], [-0.2, 0.1, 1.0]])[h % 3] + rng.uniform(-0.05, 0.05, (len(at), 3))
+    axis /= np.linalg.norm(axis, axis=1)[:, None]
+    w = np.where(h % 5 == 3, 0.0, np.cos(half))                       # (exactly a half turn: w = 0, a symmetric matrix)
+    t = rng.normal(size=(len(at), 3))
+    error = poses_of(0.1 * t / np.linalg.norm(t, axis=1)[:, None], w, axis * np.where(h % 5 == 3, 1.0, np.sin(half))[:, None])
+    Z, delta = Z.copy(), g["delta"].copy()
+    Z[at] = np.linalg.inv(g["start"][i[at]]) @ g["start"][j[at]] @ np.linalg.inv(error)
+    delta[at] = np.array(HALF_TURN_DELTAS)[h % 4]
+    return dict(g, edges=(i, j, Z, W), delta=delta, half_turns=at)
+
+
+def chain_graph(kind):
+    """300 vertices, edges k -> k + 1, vertex 0 fixed, dense positive definite information.  "exact": poses and measurements whose
+    error is exactly zero (translations by dyadic fractions).  Else the helix at its true poses, every measurement 1 cm and 0.01 off;
+    "negative_last": the last edge (298 -> 299) carries -1e3 I, so the only blocks without a factor belong to vertices of the second
+    workgroup; "indefinite_100": edge 100 carries 100 A, A the identity with A[0, 1] = A[1, 0] = 5."""
+    n = 300
+    rng = np.random.default_rng(41)
+    i = np.arange(n - 1, dtype=np.int32)
+    W = spds(rng, n - 1)
+    if kind == "exact":
+        X = np.tile(np.eye(4), (n, 1, 1))
+        X[:, 0, 3], X[:, 1, 3] = 0.25 * np.arange(n), 0.125 * np.arange(n)
+        Z = np.tile(pose([0.25, 0.125, 0.0], [0, 0, 0]), (n - 1, 1, 1))
+    else:
+        X = helix(n)
+        dt, dv = rng.normal(size=(n - 1, 3)), rng.normal(size=(n - 1, 3))
+        dv *= 0.01 / np.linalg.norm(dv, axis=1)[:, None]
+        Z = np.linalg.inv(X[:-1]) @ X[1:] @ poses_of(0.01 * dt / np.linalg.norm(dt, axis=1)[:, None], np.sqrt(1 - (dv * dv).sum(1)), dv)
+        if kind == "negative_last":
+            W[298] = -1e3 * np.eye(6)
+        if kind == "indefinite_100":
+            W[100] = 100.0 * np.eye(6)
+            W[100, 0, 1] = W[100, 1, 0] = 500.0
+    return dict(start=X, fixed=np.arange(n) == 0, edges=(i, i + 1, Z, W), delta=None)
+
+
+def no_edges(n):
+    g = graph_of(n, np.zeros(0, np.int32), np.zeros(0, np.int32), 50 + n)
+    return dict(g, delta=None)
+
+
+# name: builder.  (n, m) and what the kernels do there: tests/test_gpu_pose_graph_edges.py
+EDGE_GRAPHS = {
+    "full_block": lambda: graph_of(256, *ring_with_chords(256, 256, np.random.default_rng(61)), 62),
+    "three_blocks": lambda: graph_of(513, *ring_with_chords(513, 1281, np.random.default_rng(63)), 64),
+    "ring_65537": lambda: graph_of(65537, *ring_with_chords(65537, 65537, np.random.default_rng(65)), 66),
+    "few_vertices": lambda: graph_of(90, *ring_with_chords(90, 65537, np.random.default_rng(67)), 68),
+    "ring_196613": lambda: graph_of(196613, *ring_with_chords(196613, 196613, np.random.default_rng(69)), 70),
+    "half_turns": half_turn_graph,
+    "no_edges_1": lambda: no_edges(1),
+    "no_edges_300": lambda: no_edges(300),
+    "two": lambda: graph_of(2, *ring_with_chords(2, 1, np.random.default_rng(71)), 72),
+    "small": lambda: graph_of(90, *ring_with_chords(90, 260, np.random.default_rng(73)), 74),
+    "ring_600": lambda: graph_of(600, *ring_with_chords(600, 1500, np.random.default_rng(75)), 76),
+    "chain_exact": lambda: chain_graph("exact"),
+    "chain_off": lambda: chain_graph("off"),
+    "chain_negative_last": lambda: chain_graph("negative_last"),
+    "chain_indefinite_100": lambda: chain_graph("indefinite_100"),
+}
+
+# name: (graph, parameters of optimize, the status the optimisation must end in or None, CG statuses that must occur in the records)
+EDGE_RUNS = {
+    "many_workgroups": ("ring_600", dict(max_iterations=8), None, ()),
+    "long_tree": ("ring_65537", dict(max_iterations=2, cg_max_iterations=5), "iteration_cap", ("iteration_cap",)),
+    "cg_cap_1": ("ring_600", dict(max_iterations=6, cg_max_iterations=1), None, ("iteration_cap",)),
+    "cg_cap_2": ("ring_600", dict(max_iterations=6, cg_max_iterations=2), None, ("iteration_cap",)),
+    "cg_cap_3": ("ring_600", dict(max_iterations=6, cg_max_iterations=3), None, ("iteration_cap",)),
+    "cg_cap_4": ("ring_600", dict(max_iterations=6, cg_max_iterations=4), None, ("iteration_cap",)),
+    "zero_rhs": ("chain_exact", dict(), "converged", ("zero_rhs",)),
+    "cholesky_in_workgroup_1": ("chain_negative_last", dict(max_iterations=15), None, ("cholesky",)),
+    "breakdown": ("chain_indefinite_100", dict(max_iterations=15), None, ("cholesky", "breakdown")),
+    "damping_overflow": ("chain_off", dict(initial_damping_scale=1e300), "damping_overflow", ()),
+    "lm_iteration_cap": ("chain_off", dict(max_iterations=3), "iteration_cap", ()),
+    "large_steps": ("half_turns", dict(max_iterations=20), None, ()),
+    "reuse_two": ("two", dict(max_iterations=2), None, ()),
+    "reuse_three_blocks": ("three_blocks", dict(max_iterations=2), None, ()),
+    "small": ("small", dict(), None, ()),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def edge_graph(name):
+    """one of EDGE_GRAPHS as load() takes it: built once, shared, not modified"""
+    return EDGE_GRAPHS[name]()
+
+
+def edge_graphs():
+    """every named input of the GPU tier's edge cases"""
+    return {name: edge_graph(name) for name in EDGE_GRAPHS}
+
+
+@functools.lru_cache(maxsize=None)
+def edge_run(name):
+    """(graph, report, final poses, final weights) of the yardstick on one of EDGE_RUNS: computed once, shared, not modified"""
+    graph, params, _, _ = EDGE_RUNS[name]
+    h = load(HostGraph(), edge_graph(graph))
+    report = h.optimize(**params)
+    out = edge_graph(graph), report, h.poses(), h.edge_stats()[1]
+    h.close()
+    return out
+
+
+def quat_branches(g):
+    """per edge, the branch pg_quat takes on the rotation of Z^-1 X_i^-1 X_j: 0 for a positive trace, else 1 + the index of the largest
+    diagonal entry"""
+    i, j, Z, _ = g["edges"]
+    R = (np.linalg.inv(Z) @ np.linalg.inv(g["start"][i]) @ g["start"][j])[:, :3, :3]
+    diagonal = np.stack([R[:, 0, 0], R[:, 1, 1], R[:, 2, 2]], 1)
+    return np.where(diagonal.sum(1) > 0, 0, 1 + diagonal.argmax(1))
+
+
+def test_the_batched_builder_makes_rigid_poses_and_a_long_ring_quickly():
+    import time
+    seconds = []
+    while len(seconds) < 3 and min(seconds, default=1.0) >= 1.0:      # (the best of at most three: a busy machine is not a slow builder)
+        t0 = time.perf_counter()
+        g = EDGE_GRAPHS["ring_65537"]()
+        seconds.append(time.perf_counter() - t0)
+    X, (i, j, Z, W) = g["start"], g["edges"]
+    print("65537 vertices and edges built in", seconds, "s")
+    assert min(seconds) < 1.0                                         # (the loop over random_pose took 1.7 s)
+    for T in (X, Z):
+        R = T[:, :3, :3]
+        assert np.abs(R @ R.transpose(0, 2, 1) - np.eye(3)).max() <= 16 * EPS and np.all(np.linalg.det(R) > 0.99) and np.all(T[:, 3] == [0, 0, 0, 1])
+    assert np.array_equal(i, np.arange(65537)) and np.array_equal(j, (np.arange(65537) + 1) % 65537)
+    assert np.all(np.linalg.eigvalsh(W[:100]) >= 100.0 * (1 - 1e-12)) and np.array_equal(W, W.transpose(0, 2, 1))
+    assert g["fixed"][3] and g["fixed"].sum() == (65537 + 3) // 7 and 0 < (g["delta"] > 0).sum() < len(i)
+    rng = np.random.default_rng(9)
+    one = random_poses(rng, 1)[0]
+    assert np.abs(quat_matrices(np.array([0.5]), np.array([[0.5, -0.5, 0.5]]))[0] - quat_matrix(0.5, [0.5, -0.5, 0.5])).max() == 0 and one.shape == (4, 4)
+    i, j = ring_with_chords(90, 65537, rng)
+    assert np.all(i != j) and 1300 < np.bincount(np.concatenate([i, j]), minlength=90).min()
+
+
+def test_the_edge_graphs_do_what_they_are_there_for():
+    """Each input of the GPU tier's edge cases on the yardstick: the endings occur, the branches are taken.  A change to a generator that
+    turns a case into an easy one fails here, without a GPU."""
+    shapes = dict(full_block=(256, 256), three_blocks=(513, 1281), ring_65537=(65537, 65537), few_vertices=(90, 65537), ring_196613=(196613, 196613),
+                  half_turns=(70, 150), no_edges_1=(1, 0), no_edges_300=(300, 0), two=(2, 1), small=(90, 260), ring_600=(600, 1500),
+                  chain_exact=(300, 299), chain_off=(300, 299), chain_negative_last=(300, 299), chain_indefinite_100=(300, 299))
+    for name, g in edge_graphs().items():
+        i, j, Z, W = g["edges"]
+        assert (len(g["start"]), len(i)) == shapes[name] and Z.shape == (len(i), 4, 4) and W.shape == (len(i), 6, 6) and np.all(i != j), name
+        assert all(np.all(np.isfinite(a)) for a in (g["start"], Z, W)) and g["fixed"].shape == (len(g["start"]),), name
+        assert i.dtype == j.dtype == np.int32 and (not len(i) or (min(i.min(), j.min()) >= 0 and max(i.max(), j.max()) < len(g["start"]))), name
+    assert sorted(shapes) == sorted(EDGE_GRAPHS) and all(graph in EDGE_GRAPHS for graph, _, _, _ in EDGE_RUNS.values())
+    for name, (graph, params, lm_status, cg_statuses) in EDGE_RUNS.items():
+        g, report, poses, _ = edge_run(name)
+        seen = [r["cg_status"] for r in report["records"]]
+        print(name, report["status"], report["iterations"], report["accepted"], {s: seen.count(s) for s in sorted(set(seen))})
+        assert lm_status is None or report["status"] == lm_status, name
+        for status in cg_statuses:
+            assert status in seen, (name, status)
+        assert np.all(np.isfinite(poses)), name
+    # across workgroups: three vertex blocks, an optimisation that moves
+    report = edge_run("many_workgroups")[1]
+    assert report["accepted"] >= 3 and report["final_cost"] < report["initial_cost"] and report["cg_iterations"] > 8 * 4
+    # the long tree: the first trial accepted, so the second's damping went through the scale's tree
+    records = edge_run("long_tree")[1]["records"]
+    assert len(records) == 2 and records[0]["accepted"] and records[1]["damping"] != records[0]["damping"]
+    assert [r["cg_iterations"] for r in records] == [5, 5]
+    for cap in (1, 2, 3, 4):
+        records = edge_run("cg_cap_%d" % cap)[1]["records"]
+        assert len(records) == 6 and all(r["cg_status"] == "iteration_cap" and r["cg_iterations"] == cap for r in records)
+    report = edge_run("zero_rhs")[1]
+    assert report["initial_cost"] == 0.0 and report["iterations"] == 1 and report["accepted"] == 0
+    # the blocks without a factor: vertices of the second workgroup only
+    g = edge_graph("chain_negative_last")
+    h = load(HostGraph(), g)
+    damping = edge_run("cholesky_in_workgroup_1")[1]["records"][0]["damping"]
+    out = h.multiply(damping, np.zeros((300, 6)))
+    no_factor = np.nonzero(~out["inverse"].any(axis=(1, 2)) & ~g["fixed"])[0]
+    assert len(no_factor) and no_factor.min() >= 256, no_factor
+    h.close()
+    seen = [r["cg_status"] for r in edge_run("cholesky_in_workgroup_1")[1]["records"]]
+    assert seen[0] == "cholesky" and "converged" in seen              # (the damping grows past the block, then trials solve)
+    assert edge_run("damping_overflow")[1]["iterations"] < 50 and edge_run("lm_iteration_cap")[1]["iterations"] == 3
+    # the half turns: every branch of pg_quat, both ends of pg_log1p, a step beyond the unit quaternion
+    g = edge_graph("half_turns")
+    branches = np.bincount(quat_branches(g), minlength=4)
+    print("pg_quat branches", branches)
+    assert np.all(branches >= 5) and np.all(quat_branches(g)[g["half_turns"]] > 0)
+    h = load(HostGraph(), g)
+    ratio = h.linearise()["chi2"][g["delta"] > 0] / g["delta"][g["delta"] > 0] ** 2
+    assert ratio.max() > 1e6 and ratio.min() < 1e-6
+    h.multiply(0.0, np.zeros((70, 6)))
+    x, status, _ = h.solve(edge_run("large_steps")[1]["records"][0]["damping"], DEFAULTS["cg_tolerance"], DEFAULTS["cg_max_iterations"])
+    beyond = int(((x[:, 3:] ** 2).sum(1) > 1).sum())
+    print("the first trial's step:", status, beyond, "vertices beyond |v| = 1")
+    assert beyond >= 1
+    h.close()
+    R = edge_run("large_steps")[2][:, :3, :3]
+    assert np.abs(R @ R.transpose(0, 2, 1) - np.eye(3)).max() <= 1e-14
+    for name in ("no_edges_1", "no_edges_300"):
+        h = load(HostGraph(), edge_graph(name))
+        assert h.optimize()["status"] == "nothing_to_do" and h.linearise()["cost"] == 0.0 and not h.multiply(3.7, np.ones((h.n, 6)))["y"].any()
+        h.close()
+
+
 # ---- the definitions, independent of the header --------------------------------------------------------------------------------------------
 
 def test_error_chi2_weight_and_rho_equal_the_numpy_restatement():
@@ -533,7 +800,7 @@ def test_log1p_is_within_four_ulp_of_the_libm():
 
 def test_the_tree_sum_is_the_adjacent_pair_tree():
     rng = np.random.default_rng(2)
-    for n in (1, 2, 3, 64, 65, 255, 256, 257, 1000):
+    for n in (1, 2, 3, 64, 65, 255, 256, 257, 1000, 65536, 65537, 196613):      # (the last three: the sizes of edge_graphs())
         a = rng.normal(size=n) * 10.0 ** rng.integers(-8, 8, n)
         t = np.concatenate([a, np.zeros((1 << int(np.ceil(np.log2(n))) if n > 1 else 1) - n)])
         while len(t) > 1:
