@@ -102,6 +102,8 @@ class GraphReport(C.Structure):
 GRAPH_STATUS = {0: "converged", 1: "iteration_cap", 2: "damping_overflow", 3: "stalled", 4: "nothing_to_do"}
 GRAPH_CG_STATUS = {1: "converged", 2: "breakdown", 3: "cholesky", 4: "zero_rhs", 5: "iteration_cap"}
 GRAPH_MAX_VERTICES, GRAPH_MAX_EDGES = 1 << 20, 1 << 22
+# a resident-sized graph (pose_graph.h: kPgResidentMaxVertices, kPgResidentMaxEdges): what dvo_hip_graph_optimize_batch takes
+GRAPH_RESIDENT_MAX_VERTICES, GRAPH_RESIDENT_MAX_EDGES = 1024, 4096
 
 # every symbol include/dvo_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
@@ -125,7 +127,7 @@ EXPORTS = [
     "dvo_hip_render_params_default", "dvo_hip_map_render", "dvo_hip_map_render_frames", "dvo_hip_time_map_render",
     "dvo_hip_graph_create", "dvo_hip_graph_destroy", "dvo_hip_graph_set_vertices", "dvo_hip_graph_set_poses", "dvo_hip_graph_set_edges",
     "dvo_hip_graph_params_default", "dvo_hip_graph_optimize", "dvo_hip_graph_get_poses", "dvo_hip_graph_edge_stats",
-    "dvo_hip_graph_linearise", "dvo_hip_graph_multiply",
+    "dvo_hip_graph_linearise", "dvo_hip_graph_multiply", "dvo_hip_graph_optimize_batch",
 ]
 
 ROLE_CURRENT, ROLE_REFERENCE = 0, 1
@@ -265,6 +267,8 @@ def lib():
         L.dvo_hip_graph_params_default.argtypes = []
         L.dvo_hip_graph_params_default.restype = GraphParams
         L.dvo_hip_graph_optimize.argtypes = [vp, vp, C.POINTER(GraphParams), C.POINTER(GraphReport), C.POINTER(GraphIteration), C.c_int]
+        L.dvo_hip_graph_optimize_batch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(GraphParams), C.POINTER(GraphReport), C.POINTER(GraphIteration),
+                                                   C.c_int]
         L.dvo_hip_graph_get_poses.argtypes = [vp, vp, C.c_int, dp]
         L.dvo_hip_graph_edge_stats.argtypes = [vp, vp, C.c_int, dp, dp]
         L.dvo_hip_graph_linearise.argtypes = [vp, vp, dp, dp, dp, dp, dp, dp]

@@ -10,6 +10,7 @@
 #include <xmmintrin.h>
 
 #include <algorithm>
+#include <functional>
 #include <climits>
 #include <cstddef>
 #include <cmath>
@@ -393,6 +394,10 @@ struct dvo_hip_context {
   long long depth_registrations = 0;   // frames whose depth was registered at ingest (dvo_hip_frames_set_depth_rig), counter "depth_registrations"
   long long map_inserts = 0, map_points = 0, map_dropped = 0;   // frames / points a keyframe map took, points it dropped (dvo_hip_map_insert); counters of the same names
   long long map_removes = 0, map_rehashes = 0;   // frames subtracted from a keyframe map (dvo_hip_map_remove, dvo_hip_map_move), tables rebuilt (dvo_hip_map_rehash); counters of the same names
+  // option "graph_resident": dvo_hip_graph_optimize hands a resident-sized graph to the resident kernel (capi_graph.inc); counter
+  // "graph_resident_solves": graphs that kernel has optimised, by that way or by dvo_hip_graph_optimize_batch
+  int opt_graph_resident = 0;
+  long long graph_resident_solves = 0;
   long long map_renders = 0;       // views rendered out of a keyframe map (dvo_hip_map_render, dvo_hip_map_render_frames), counter "map_renders"
   // Option "defer_ingest": a batched re-ingest (dvo_hip_frames_update_raw_device_as) is only recorded, and carried out by the next
   // dvo_hip_match_batch right behind the first launches of its first level (or by whatever entry point comes first).  A streaming
@@ -508,6 +513,7 @@ struct dvo_hip_context {
   DevBuf sel_tbl_main, sel_tbl_build;                 // tables of the caller-selection apply pass, one per stream (apply_selection)
   unsigned long long sel_visits = 0;
   DevBuf lens_tbl;                                    // table of the rectify pass (rectify_frames; allocated by the first lens ingest)
+  DevBuf graph_jobs, graph_outs;                      // the job records and results of a resident pose-graph launch (capi_graph.inc)
   DevBuf rig_tbl;                                     // table of the register pass (register_frames; allocated by the first rig ingest)
   DevBuf map_tbl, map_stage;                          // the frame table of a keyframe-map launch and the staging area of results that go to host memory (capi_map.inc)
   DevBuf render_tbl, render_zbuf, render_planes;      // a render's view table, its z-buffers and -- dvo_hip_map_render_frames -- the planes the frames ingest (capi_map.inc)
@@ -858,7 +864,7 @@ void dvo_hip_context_destroy(dvo_hip_context* ctx) {
   if (ctx->build_stream) (void)hipStreamDestroy(ctx->build_stream);
   for (DevBuf& b : ctx->build_tbl) b.release();
   for (DevBuf* b : {&ctx->misc, &ctx->role_tbl_cur, &ctx->role_tbl_ref, &ctx->prep_tbl_cur, &ctx->prep_tbl_ref, &ctx->rcp_table, &ctx->ref_order_planes,
-                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl, &ctx->rig_tbl, &ctx->map_tbl, &ctx->map_stage, &ctx->render_tbl, &ctx->render_zbuf, &ctx->render_planes}) b->release();
+                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl, &ctx->rig_tbl, &ctx->graph_jobs, &ctx->graph_outs, &ctx->map_tbl, &ctx->map_stage, &ctx->render_tbl, &ctx->render_zbuf, &ctx->render_planes}) b->release();
   if (ctx->render_done) (void)hipEventDestroy(ctx->render_done);
   for (DevBuf& b : ctx->upload_buf) b.release();
   for (const dvo_hip_context::PooledBlock& b : ctx->frame_pool) (void)hipFree(b.p);

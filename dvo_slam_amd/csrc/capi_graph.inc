@@ -1,8 +1,11 @@
 // capi_graph.inc -- the keyframe pose graph behind the C-ABI (include/dvo_hip.h, dvo_hip_graph_*; arithmetic and schedule: pose_graph.h;
 // kernels: pose_graph.hip).  Every launch runs on the context's main stream; arguments are checked before anything is launched or
-// changed.  The host enqueues one Levenberg-Marquardt trial -- the start of the solve, cg_max_iterations pairs of launches that return
-// at once when the solve has ended, the step, the cost at the stepped poses -- reads one small record, and judges the trial with
-// pg_lm_judge.  Textually included by capi.hip inside its extern "C" block.
+// changed.  Two schedules of the same statements.  The launch path: the host enqueues one Levenberg-Marquardt trial -- the start of the
+// solve, cg_max_iterations pairs of launches that return at once when the solve has ended, the step, the cost at the stepped poses --
+// reads one small record, and judges the trial with pg_lm_judge.  The resident path (dvo_hip_graph_optimize_batch; dvo_hip_graph_optimize
+// under option "graph_resident"): graphs of at most kPgResidentMaxVertices vertices and kPgResidentMaxEdges edges, one workgroup each, in
+// ONE launch of k_pg_resident that judges its trials itself; one read afterwards.  The same bits either way.  Textually included by
+// capi.hip inside its extern "C" block.
 struct dvo_hip_graph {
   dvo_hip_context* ctx = nullptr;
   int n = 0, m = 0;
@@ -132,6 +135,81 @@ int graph_download_rows(dvo_hip_context* ctx, const double* device, int count, i
   return DVO_HIP_OK;
 }
 
+// the rules of a parameter set, for both schedules
+bool graph_params_ok(const dvo_hip_graph_params& prm) {
+  return prm.max_iterations >= 0 && prm.cg_max_iterations >= 1 && prm.cg_max_iterations <= 100000 && prm.cg_tolerance > 0.0 && prm.cg_tolerance < 1.0 &&
+         prm.min_relative_decrease >= 0.0 && pg_finite(prm.min_relative_decrease) && prm.initial_damping_scale > 0.0 &&
+         pg_finite(prm.initial_damping_scale);
+}
+const char* const kGraphParamRules = "need max_iterations >= 0, 1 <= cg_max_iterations <= 100000, 0 < cg_tolerance < 1, "
+                                     "min_relative_decrease >= 0 and initial_damping_scale > 0";
+
+bool graph_resident_sized(const dvo_hip_graph* g) { return g->n <= kPgResidentMaxVertices && g->m <= kPgResidentMaxEdges; }
+
+static_assert(sizeof(PgResidentIteration) == sizeof(dvo_hip_graph_iteration), "k_pg_resident writes the records as the caller reads them");
+
+// The resident schedule (k_pg_resident): every graph optimised from start to end by one workgroup of ONE launch, then one
+// synchronisation and one read.  The arguments have been checked: resident-sized graphs of this context, each once, good parameters.
+// params: one per graph.  records (may be null): max_records per graph.
+int graph_optimize_resident(dvo_hip_context* ctx, int n_graphs, dvo_hip_graph* const* graphs, const dvo_hip_graph_params* params,
+                            dvo_hip_graph_report* reports, dvo_hip_graph_iteration* records, int max_records) {
+  int stride = 0;                                                   // records the kernel keeps per graph: no trial beyond max_iterations is run
+  for (int i = 0; i < n_graphs; ++i) stride = params[i].max_iterations > stride ? params[i].max_iterations : stride;
+  stride = stride < max_records ? stride : max_records;
+  std::vector<PgResidentJob> jobs(static_cast<size_t>(n_graphs));
+  for (int i = 0; i < n_graphs; ++i) {
+    const dvo_hip_graph* g = graphs[i];
+    PgResidentJob& job = jobs[size_t(i)];
+    job.g = graph_view(g);
+    job.poses[0] = g->poses[0].as<double>();
+    job.poses[1] = g->poses[1].as<double>();
+    job.cur = g->cur;
+    job.any_free = g->any_free ? 1 : 0;
+    job.max_iterations = params[i].max_iterations;
+    job.cg_max_iterations = params[i].cg_max_iterations;
+    job.cg_tolerance = params[i].cg_tolerance;
+    job.min_relative_decrease = params[i].min_relative_decrease;
+    job.initial_damping_scale = params[i].initial_damping_scale;
+  }
+  const size_t job_bytes = jobs.size() * sizeof(PgResidentJob), out_bytes = jobs.size() * sizeof(PgResidentOut);
+  const size_t record_bytes = jobs.size() * size_t(stride) * sizeof(PgResidentIteration);
+  DVO_HIP_TRY(ctx, ctx->graph_jobs.reserve(job_bytes));
+  DVO_HIP_TRY(ctx, ctx->graph_outs.reserve(out_bytes + record_bytes));
+  PgResidentOut* outs = ctx->graph_outs.as<PgResidentOut>();
+  PgResidentIteration* device_records = reinterpret_cast<PgResidentIteration*>(outs + n_graphs);
+  DVO_HIP_TRY(ctx, hipMemcpyAsync(ctx->graph_jobs.p, jobs.data(), job_bytes, hipMemcpyHostToDevice, ctx->stream));
+  size_t stage_bytes = 0;                                           // the LDS of a workgroup: what the largest graph that fits needs
+  for (int i = 0; i < n_graphs; ++i) {
+    const size_t need = graphs[i]->m > 0 ? pg_resident_stage_bytes(graphs[i]->n, graphs[i]->m) : 0;
+    if (need <= size_t(kPgResidentStageBytes) && need > stage_bytes) stage_bytes = need;
+  }
+  launch_pg_resident(ctx->stream, ctx->graph_jobs.as<PgResidentJob>(), n_graphs, outs, device_records, stride, stage_bytes);
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  std::vector<unsigned char> host(out_bytes + record_bytes);
+  DVO_HIP_TRY(ctx, hipMemcpyAsync(host.data(), ctx->graph_outs.p, host.size(), hipMemcpyDeviceToHost, ctx->stream));
+  DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < n_graphs; ++i) {
+    PgResidentOut o;
+    std::memcpy(&o, host.data() + size_t(i) * sizeof(PgResidentOut), sizeof o);
+    dvo_hip_graph_report& r = reports[i];
+    std::memset(&r, 0, sizeof r);
+    r.status = o.status;
+    r.iterations = o.iterations;
+    r.accepted = o.accepted;
+    r.cg_iterations = o.cg_iterations;
+    r.initial_cost = o.initial_cost;
+    r.final_cost = o.final_cost;
+    r.final_damping = o.final_damping;
+    graphs[i]->cur = o.cur & 1;
+    const int kept = o.iterations < stride ? o.iterations : stride;
+    if (kept > 0)
+      std::memcpy(records + size_t(i) * size_t(max_records), host.data() + out_bytes + size_t(i) * size_t(stride) * sizeof(PgResidentIteration),
+                  size_t(kept) * sizeof(PgResidentIteration));
+  }
+  ctx->graph_resident_solves += n_graphs;
+  return DVO_HIP_OK;
+}
+
 }  // namespace
 
 int dvo_hip_graph_create(dvo_hip_context* ctx, dvo_hip_graph** out) {
@@ -239,12 +317,9 @@ int dvo_hip_graph_optimize(dvo_hip_context* ctx, dvo_hip_graph* g, const dvo_hip
   if (rc != DVO_HIP_OK) return rc;
   const dvo_hip_graph_params prm = params ? *params : dvo_hip_graph_params_default();
   if (!out || g->n <= 0 || max_records < 0 || (max_records > 0 && !records)) return fail(ctx, DVO_HIP_ERR_INVALID, "graph_optimize: bad argument");
-  if (prm.max_iterations < 0 || prm.cg_max_iterations < 1 || prm.cg_max_iterations > 100000 || !(prm.cg_tolerance > 0.0 && prm.cg_tolerance < 1.0) ||
-      !(prm.min_relative_decrease >= 0.0 && pg_finite(prm.min_relative_decrease)) ||
-      !(prm.initial_damping_scale > 0.0 && pg_finite(prm.initial_damping_scale)))
-    return fail(ctx, DVO_HIP_ERR_INVALID, "graph_optimize: need max_iterations >= 0, 1 <= cg_max_iterations <= 100000, 0 < cg_tolerance < 1, "
-                                          "min_relative_decrease >= 0 and initial_damping_scale > 0");
+  if (!graph_params_ok(prm)) return fail(ctx, DVO_HIP_ERR_INVALID, "graph_optimize", kGraphParamRules);
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (ctx->opt_graph_resident && graph_resident_sized(g)) return graph_optimize_resident(ctx, 1, &g, &prm, out, records, max_records);
   std::memset(out, 0, sizeof *out);
   out->status = DVO_HIP_GRAPH_NOTHING_TO_DO;
   if (g->m == 0) return DVO_HIP_OK;
@@ -310,6 +385,29 @@ int dvo_hip_graph_optimize(dvo_hip_context* ctx, dvo_hip_graph* g, const dvo_hip
   out->final_cost = lm.cost;
   out->final_damping = lm.lambda;
   return DVO_HIP_OK;
+}
+
+int dvo_hip_graph_optimize_batch(dvo_hip_context* ctx, int n_graphs, dvo_hip_graph* const* graphs, const dvo_hip_graph_params* params,
+                                 dvo_hip_graph_report* reports, dvo_hip_graph_iteration* records, int max_records) {
+  DVO_LOCK(ctx);
+  const char* who = "graph_optimize_batch";
+  if (!ctx) return dvo_hip_device_count() > 0 ? DVO_HIP_ERR_INVALID : DVO_HIP_ERR_NO_DEVICE;
+  if (n_graphs <= 0 || !graphs || !reports || max_records < 0 || (max_records > 0 && !records)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  for (int i = 0; i < n_graphs; ++i) {
+    const int rc = check_graph(ctx, graphs[i], who);
+    if (rc != DVO_HIP_OK) return rc;
+    if (graphs[i]->n <= 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a graph without vertices");
+    if (!graph_resident_sized(graphs[i])) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a graph beyond 1024 vertices or 4096 edges: dvo_hip_graph_optimize takes it");
+  }
+  std::vector<const dvo_hip_graph*> sorted(graphs, graphs + n_graphs);
+  std::sort(sorted.begin(), sorted.end(), std::less<const dvo_hip_graph*>());
+  if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the same graph twice");
+  std::vector<dvo_hip_graph_params> prm(static_cast<size_t>(n_graphs), dvo_hip_graph_params_default());
+  if (params) prm.assign(params, params + n_graphs);
+  for (int i = 0; i < n_graphs; ++i)
+    if (!graph_params_ok(prm[size_t(i)])) return fail(ctx, DVO_HIP_ERR_INVALID, who, kGraphParamRules);
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return graph_optimize_resident(ctx, n_graphs, graphs, prm.data(), reports, records, max_records);
 }
 
 int dvo_hip_graph_get_poses(dvo_hip_context* ctx, dvo_hip_graph* g, int n, double* poses_out) {

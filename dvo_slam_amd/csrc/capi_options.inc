@@ -45,6 +45,7 @@ int dvo_hip_get_counter(dvo_hip_context* ctx, const char* key, long long* value)
   else if (std::strcmp(key, "map_renders") == 0) *value = ctx->map_renders;
   else if (std::strcmp(key, "map_points") == 0) *value = ctx->map_points;
   else if (std::strcmp(key, "map_dropped") == 0) *value = ctx->map_dropped;
+  else if (std::strcmp(key, "graph_resident_solves") == 0) *value = ctx->graph_resident_solves;
   else if (std::strcmp(key, "warmup_wait_us") == 0) *value = ctx->warmup_wait_us;
   else if (std::strcmp(key, "rendezvous_pairs") == 0) {
     std::lock_guard<std::mutex> lock(ctx->rendezvous_mutex);
@@ -252,6 +253,11 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value) {
     if (value != 0 && value != 1) return fail(ctx, DVO_HIP_ERR_INVALID, "table_cache must be 0 or 1");
     ctx->tables.cache = value != 0;
     for (PinnedRing::Sent& c : ctx->tables.sent) c.dst = nullptr;
+    return DVO_HIP_OK;
+  }
+  if (std::strcmp(key, "graph_resident") == 0) {
+    if (value != 0 && value != 1) return fail(ctx, DVO_HIP_ERR_INVALID, "graph_resident must be 0 or 1 (dvo_hip_graph_optimize runs a resident-sized graph in one launch)");
+    ctx->opt_graph_resident = value;
     return DVO_HIP_OK;
   }
   if (std::strcmp(key, "fused_ll_pixels") == 0) {

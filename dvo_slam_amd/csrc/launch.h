@@ -119,6 +119,14 @@ void launch_pg_multiply(hipStream_t s, const PgGraph& g, PgCgState* st, const do
 void launch_pg_cg_update(hipStream_t s, const PgGraph& g, PgCgState* st, const double* pap_partials, double* rz_partials, int it);
 void launch_pg_apply(hipStream_t s, const PgGraph& g, double lambda, const double* poses, double* out, double* scale_partials);
 void launch_pg_reduce(hipStream_t s, const double* a, int n_a, const double* b, int n_b, double* out);
+// the resident schedule: n_graphs resident-sized graphs, each optimised from start to end by one workgroup of one launch.  outs: one per
+// graph; records: max_records per graph, the first of its trials; stage_bytes: the LDS a workgroup gets to keep its graph's solve in
+// (pose_graph.h: pg_resident_stage_bytes of the largest graph that is to be staged, at most kPgResidentStageBytes)
+struct PgResidentJob;
+struct PgResidentOut;
+struct PgResidentIteration;
+void launch_pg_resident(hipStream_t s, const PgResidentJob* jobs, int n_graphs, PgResidentOut* outs, PgResidentIteration* records, int max_records,
+                        size_t stage_bytes);
 
 // align_kernels.hip / align_mfma.hip
 // variant 5 (default): Gram accumulation on the matrix cores (align_mfma.hip); variant 0: the all-VALU schedule with the DPP + LDS

@@ -28,6 +28,13 @@ constexpr int kPgBlock = 256;              // vertices or edges per workgroup: t
 constexpr int kPgTreeLevels = 26;
 constexpr int kPgMaxVertices = 1 << 20;    // 4096 partials per vertex scalar
 constexpr int kPgMaxEdges = 1 << 22;       // 16384 partials of the cost
+// a resident-sized graph: within both.  k_pg_resident (pose_graph.hip) optimises such a graph start to end in one workgroup, and
+// keeps the at most 4 / 16 partials of a scalar in LDS
+constexpr int kPgResidentMaxVertices = 1024;
+constexpr int kPgResidentMaxEdges = 4096;
+// ... and it STAGES a graph whose solve fits this much LDS (of the 160 KB of a compute unit): the vertex records, the edges' off-diagonal
+// blocks and the index arrays, pg_resident_stage_bytes of them.  A larger resident-sized graph is solved from memory.
+constexpr int kPgResidentStageBytes = 144 * 1024;
 
 // the per-edge record, component-major: component c of edge k at E[c * m + k] (a wavefront's stores coalesce)
 enum { kPgE = 0, kPgS = 6, kPgW = 7, kPgRho = 8, kPgAii = 9, kPgAij = 45, kPgAjj = 81, kPgGi = 117, kPgGj = 123, kPgEdgeComps = 129 };
@@ -558,5 +565,35 @@ DVO_HD bool pg_lm_judge(PgLm& lm, double cost_new, double scale, int cg_status, 
   if (*stop < 0 && !pg_finite(lm.lambda)) *stop = kPgDampingOverflow;
   return accepted;
 }
+
+// ---- the resident schedule: one graph, one workgroup, one launch (k_pg_resident) -------------------------------------------------------
+
+DVO_HD size_t pg_resident_stage_bytes(int n, int m) {
+  const size_t bytes = 8 * (size_t(kPgVertexComps) * size_t(n) + 36 * size_t(m)) + 4 * (size_t(n) + 1 + 4 * size_t(m)) + size_t(n);
+  return (bytes + 15) / 16 * 16;
+}
+
+// what a workgroup of k_pg_resident is handed: the graph where it lies, both pose buffers, which holds the estimate, the parameters
+struct PgResidentJob {
+  PgGraph g;
+  double* poses[2];
+  int cur;                    // poses[cur] is the estimate
+  int any_free;               // a vertex that is neither fixed nor without an edge
+  int max_iterations, cg_max_iterations;
+  double cg_tolerance, min_relative_decrease, initial_damping_scale;
+};
+
+// ... and what it leaves: the report's numbers (dvo_hip_graph_report) and the pose buffer the final estimate is in
+struct PgResidentOut {
+  int status, iterations, accepted, cg_iterations;
+  double initial_cost, final_cost, final_damping;
+  int cur, reserved;
+};
+
+// one trial, laid out like dvo_hip_graph_iteration
+struct PgResidentIteration {
+  double cost_before, cost_after, damping;
+  int cg_iterations, cg_status, accepted, reserved;
+};
 
 }  // namespace dvo_hip

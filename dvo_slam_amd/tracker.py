@@ -919,6 +919,15 @@ def graph_params_struct(**params):
     return out
 
 
+def _graph_report(rep, recs):
+    """a dvo_hip_graph_report and the records of its trials as PoseGraph.optimize returns them"""
+    out = {k: getattr(rep, k) for k in ("iterations", "accepted", "cg_iterations", "initial_cost", "final_cost", "final_damping")}
+    out["status"] = _lib.GRAPH_STATUS[rep.status]
+    out["records"] = [dict(cost_before=r.cost_before, cost_after=r.cost_after, damping=r.damping, cg_iterations=r.cg_iterations,
+                           cg_status=_lib.GRAPH_CG_STATUS[r.cg_status], accepted=bool(r.accepted)) for r in recs]
+    return out
+
+
 def _graph_array(a, shape_tail, who, what):
     """a as a contiguous float64 array of shape (k,) + shape_tail with finite entries, or ValueError / TypeError"""
     try:
@@ -1017,11 +1026,55 @@ class PoseGraph:
         rep = _lib.GraphReport()
         recs = (_lib.GraphIteration * max(prm.max_iterations, 1))()
         self.ctx.check(self.ctx._lib.dvo_hip_graph_optimize(self.ctx.ptr, self.ptr, C.byref(prm), C.byref(rep), recs, prm.max_iterations))
-        out = {k: getattr(rep, k) for k in ("iterations", "accepted", "cg_iterations", "initial_cost", "final_cost", "final_damping")}
-        out["status"] = _lib.GRAPH_STATUS[rep.status]
-        out["records"] = [dict(cost_before=r.cost_before, cost_after=r.cost_after, damping=r.damping, cg_iterations=r.cg_iterations,
-                               cg_status=_lib.GRAPH_CG_STATUS[r.cg_status], accepted=bool(r.accepted)) for r in recs[:rep.iterations]]
-        return out
+        return _graph_report(rep, recs[:rep.iterations])
+
+    @staticmethod
+    def optimize_batch(graphs, params=None, max_records=None):
+        """Many small graphs in ONE launch, one workgroup each (dvo_hip_graph_optimize_batch): every graph of the list is left as its
+        own optimize() would have left it, bit for bit.  graphs: PoseGraph objects of one context, each once, each resident-sized (at
+        most _lib.GRAPH_RESIDENT_MAX_VERTICES vertices and _lib.GRAPH_RESIDENT_MAX_EDGES edges).  params: a dict of optimize()'s
+        parameters for all of them, or a list of one dict per graph; None = the defaults.  max_records: trials recorded per graph
+        (None = every trial).  Returns a list of reports shaped like optimize()'s."""
+        who = "PoseGraph.optimize_batch"
+        graphs = list(graphs)
+        if not graphs:
+            raise ValueError("%s: no graph" % who)
+        for g in graphs:
+            if not isinstance(g, PoseGraph):
+                raise TypeError("%s: graphs must be PoseGraph objects" % who)
+        if len(set(id(g) for g in graphs)) != len(graphs):
+            raise ValueError("%s: the same graph twice" % who)
+        ctx = graphs[0].ctx
+        for g in graphs:
+            if g.ctx is not ctx:
+                raise ValueError("%s: graphs of more than one context" % who)
+            if g.n < 1:
+                raise ValueError("%s: set the vertices first" % who)
+            if g.n > _lib.GRAPH_RESIDENT_MAX_VERTICES or g.m > _lib.GRAPH_RESIDENT_MAX_EDGES:
+                raise ValueError("%s: a graph of %d vertices and %d edges is beyond %d / %d; optimize() takes it" % (
+                    who, g.n, g.m, _lib.GRAPH_RESIDENT_MAX_VERTICES, _lib.GRAPH_RESIDENT_MAX_EDGES))
+        if params is None or isinstance(params, dict):
+            params = [params or {}] * len(graphs)
+        else:
+            params = list(params)
+            if len(params) != len(graphs):
+                raise ValueError("%s: %d parameter sets for %d graphs" % (who, len(params), len(graphs)))
+            for p in params:
+                if not isinstance(p, dict):
+                    raise TypeError("%s: params must be a dict or a list of dicts" % who)
+        prm = (_lib.GraphParams * len(graphs))(*[graph_params_struct(**p) for p in params])
+        if max_records is None:
+            max_records = max(p.max_iterations for p in prm)
+        if isinstance(max_records, bool) or not isinstance(max_records, (int, np.integer)):
+            raise TypeError("%s: max_records must be an integer" % who)
+        if max_records < 0:
+            raise ValueError("%s: max_records must be >= 0" % who)
+        max_records = int(max_records)
+        reps = (_lib.GraphReport * len(graphs))()
+        recs = (_lib.GraphIteration * max(len(graphs) * max_records, 1))()
+        ptrs = (C.c_void_p * len(graphs))(*[g.ptr.value if isinstance(g.ptr, C.c_void_p) else g.ptr for g in graphs])
+        ctx.check(ctx._lib.dvo_hip_graph_optimize_batch(ctx.ptr, len(graphs), ptrs, prm, reps, recs, max_records))
+        return [_graph_report(rep, recs[k * max_records:k * max_records + min(rep.iterations, max_records)]) for k, rep in enumerate(reps)]
 
     def poses(self):
         """the current estimate, [n, 4, 4]"""

@@ -906,6 +906,15 @@ int dvo_hip_gather_records(dvo_hip_comm* comm, const void* mine, size_t bytes_mi
  * rows and columns translation first, then rotation, taken AS GIVEN: the reference hands Result.Information (twist order) straight to
  * setInformation (keyframe_graph.cpp:628); hand dvo_hip_result::information over the same way to get what it gets.
  * Limits: n <= 2^20 vertices, m <= 2^22 edges; an edge costs about 1 KB of device memory, a vertex about 1 KB.
+ * Two schedules, the same bits.  The launch path (dvo_hip_graph_optimize by default) enqueues every stage of a trial as a launch of its
+ * own over all vertices or edges: any size, but two launch latencies per conjugate-gradient iteration however small the graph.  The
+ * resident path optimises a RESIDENT-SIZED graph -- at most 1024 vertices and at most 4096 edges -- from start to end inside ONE launch
+ * by ONE workgroup, and a batch of such graphs (many trackers' local maps, several edge subsets of one graph) by one workgroup each in
+ * the same launch: dvo_hip_graph_optimize_batch.  A graph whose solve fits 144 KB of LDS (114 n + 36 m doubles: about 100 vertices with
+ * 125 edges) is solved out of LDS; a larger resident-sized one from memory, where a single graph is slower than on the launch path
+ * (profiles/pose_graph.md).  Option "graph_resident" (dvo_hip_set_option; default 0): 1 = dvo_hip_graph_optimize
+ * takes the resident path for a resident-sized graph, as a batch of one; a larger graph takes the launch path as before.  Counter
+ * "graph_resident_solves" (dvo_hip_get_counter): graphs optimised by the resident path.
  * Errors: DVO_HIP_ERR_INVALID for from == to, an index out of range, a non-finite entry, delta < 0, n <= 0, or a graph of another
  * context -- checked before anything is launched or changed; DVO_HIP_ERR_NO_DEVICE without a gfx950, as everywhere else. */
 typedef struct dvo_hip_graph dvo_hip_graph;
@@ -960,6 +969,14 @@ dvo_hip_graph_params dvo_hip_graph_params_default(void);
  * null): one per trial, the first max_records of them.  The estimate becomes the last accepted one. */
 int dvo_hip_graph_optimize(dvo_hip_context* ctx, dvo_hip_graph* graph, const dvo_hip_graph_params* params, dvo_hip_graph_report* out,
                            dvo_hip_graph_iteration* records_or_null, int max_records);
+/* n_graphs resident-sized graphs of this context, each given once, optimised in ONE launch, one workgroup each; every graph is left as
+ * dvo_hip_graph_optimize with its parameters would have left it, bit for bit, whatever its place in the batch.  params: n_graphs of
+ * them, null = the defaults for all.  reports: n_graphs.  records (may be null): graph i's at records[i * max_records ...], the first
+ * max_records of its trials.  DVO_HIP_ERR_INVALID, before anything is launched or changed: n_graphs <= 0, a null entry, a graph of
+ * another context, the same graph twice, a graph without vertices or beyond 1024 vertices / 4096 edges, a parameter set
+ * dvo_hip_graph_optimize would refuse, null reports, max_records < 0, max_records > 0 without records. */
+int dvo_hip_graph_optimize_batch(dvo_hip_context* ctx, int n_graphs, dvo_hip_graph* const* graphs, const dvo_hip_graph_params* params_or_null,
+                                 dvo_hip_graph_report* reports, dvo_hip_graph_iteration* records_or_null, int max_records);
 int dvo_hip_graph_get_poses(dvo_hip_context* ctx, dvo_hip_graph* graph, int n, double* poses_out);
 /* chi2 = e^T Omega e and the kernel's weight (1 without a kernel) of every edge at the current estimate: what
  * removeOutlierConstraints thresholds (keyframe_graph.cpp:643-674) */

@@ -97,6 +97,38 @@ class PoseGraph {
     if (dvo_hip_graph_optimize(ctx_, graph_, &params, &report_, 0, 0) != DVO_HIP_OK) return -1;
     return download() ? report_.iterations : -1;
   }
+  // Many small graphs in ONE launch, one workgroup each (dvo_hip_graph_optimize_batch): the local maps of several trackers, or several
+  // edge subsets of one graph held as graphs of their own.  Every graph is left as its own optimize() would have left it, bit for bit.
+  // Each graph once, none null, all on one context, each within 1024 vertices and 4096 edges; params: one set for all, or one per
+  // graph.  Returns the number of graphs optimised, -1 on an error (nothing has been optimised then).
+  static int optimizeBatch(const std::vector<PoseGraph*>& graphs, int iterations) {
+    dvo_hip_graph_params p = dvo_hip_graph_params_default();
+    p.max_iterations = iterations;
+    return optimizeBatch(graphs, std::vector<dvo_hip_graph_params>(1, p));
+  }
+  static int optimizeBatch(const std::vector<PoseGraph*>& graphs, const std::vector<dvo_hip_graph_params>& params = std::vector<dvo_hip_graph_params>()) {
+    const size_t count = graphs.size();
+    if (count == 0 || (params.size() > 1 && params.size() != count)) return -1;
+    for (size_t i = 0; i < count; ++i) {
+      if (!graphs[i] || graphs[i]->vertices_.empty()) return -1;
+      for (size_t k = 0; k < i; ++k)
+        if (graphs[k] == graphs[i]) return -1;
+    }
+    std::vector<dvo_hip_graph*> handles(count);
+    for (size_t i = 0; i < count; ++i) {
+      if (!graphs[i]->upload() || graphs[i]->ctx_ != graphs[0]->ctx_) return -1;
+      handles[i] = graphs[i]->graph_;
+    }
+    std::vector<dvo_hip_graph_params> each(params);
+    if (each.size() == 1) each.assign(count, params[0]);
+    std::vector<dvo_hip_graph_report> reports(count);
+    if (dvo_hip_graph_optimize_batch(graphs[0]->ctx_, int(count), handles.data(), each.empty() ? 0 : each.data(), reports.data(), 0, 0) != DVO_HIP_OK) return -1;
+    for (size_t i = 0; i < count; ++i) {
+      graphs[i]->report_ = reports[i];
+      if (!graphs[i]->download()) return -1;
+    }
+    return int(count);
+  }
   // chi2 and weights at the current estimates, without a step
   bool computeErrors() {
     if (vertices_.empty() || !upload()) return false;

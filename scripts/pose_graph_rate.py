@@ -18,7 +18,18 @@ odometry.  Per size (default 64, 512, 4096, 32768):
 The kernels' own times come from
     rocprofv3 --kernel-trace --stats -- python scripts/pose_graph_rate.py --sizes 4096
 
+--resident: the resident schedule instead (one workgroup per graph, one launch per call: dvo_hip_graph_optimize_batch).  Per size
+(default 8, 64, 512 vertices: 10, 80, 640 edges), default schedule, wall clock around the synchronous call, one JSON line:
+  launch_ms          one graph (seed 1) by the launch path;
+  resident_ms        the same graph by PoseGraph.optimize() under option "graph_resident";
+  batch_ms           batches of 16, 256 and 1024 DISTINCT graphs (seeds 1 .. 1024) in one optimize_batch each (no records asked for), and
+                     batch_us_per_graph, that over the batch size;
+  host_ms            the host yardstick on the graph of seed 1, one thread;
+  host_equals_device every graph of every leg against its own yardstick run: poses and report, and the records of a run that asks for
+                     them (the yardstick runs spread over --host-threads threads; that time is not reported).
+
     python scripts/pose_graph_rate.py [--sizes 64,512,4096,32768] [--trials 3] [--no-host] [--host-max-n 4096]
+    python scripts/pose_graph_rate.py --resident [--sizes 8,64,512] [--batches 16,256,1024] [--host-threads 16]
 """
 import argparse
 import json
@@ -72,13 +83,89 @@ def timed(graph, start, **params):
     return (time.perf_counter() - t0) * 1e3, report
 
 
+def same_report(got, want):
+    return {k: v for k, v in got.items() if k != "records"} == {k: v for k, v in want.items() if k != "records"}
+
+
+def resident_leg(n, batches, host_threads):
+    from concurrent.futures import ThreadPoolExecutor
+    import test_pose_graph as tpg
+    count = max(batches)
+    inputs = [ring_with_loops(n, seed) for seed in range(1, count + 1)]
+    m = len(inputs[0][2][0])
+    print("n = %d: %d graphs built" % (n, count), file=sys.stderr, flush=True)
+
+    def host_run(k):
+        start, fixed, edges, delta = inputs[k]
+        h = tpg.HostGraph()
+        h.set_vertices(start, fixed)
+        h.set_edges(*edges, delta)
+        t0 = time.perf_counter()
+        report = h.optimize()
+        ms = (time.perf_counter() - t0) * 1e3
+        out = report, h.poses(), ms
+        h.close()
+        return out
+    tpg.host_lib()
+    host_ms = host_run(0)[2]                                         # (alone: one thread, nothing beside it)
+    with ThreadPoolExecutor(host_threads) as pool:
+        host = list(pool.map(host_run, range(count)))
+    print("n = %d: the yardstick has run" % n, file=sys.stderr, flush=True)
+    ctx = d.default_context()
+    graphs = []
+    for start, fixed, edges, delta in inputs:
+        g = d.PoseGraph(ctx)
+        g.set_vertices(start, fixed)
+        g.set_edges(*edges, delta)
+        graphs.append(g)
+
+    def rewind(k):
+        for g, (start, _, _, _) in zip(graphs[:k], inputs):
+            g.set_poses(start)
+
+    def equal(k, reports, records):
+        return all(same_report(r, host[i][0]) and (not records or r["records"] == host[i][0]["records"]) and np.array_equal(graphs[i].poses(), host[i][1])
+                   for i, r in enumerate(reports[:k]))
+    timed(graphs[0], inputs[0][0], max_iterations=2)                 # warm-up of both paths
+    d.PoseGraph.optimize_batch(graphs[:2], dict(max_iterations=2))
+    launch_ms, report = timed(graphs[0], inputs[0][0])
+    same = equal(1, [report], True)
+    ctx.set_option("graph_resident", 1)
+    before = ctx.counter("graph_resident_solves")
+    resident_ms, resident_report = timed(graphs[0], inputs[0][0])
+    same = same and equal(1, [resident_report], True) and ctx.counter("graph_resident_solves") == before + 1
+    ctx.set_option("graph_resident", 0)
+    batch_ms = {}
+    for k in batches:
+        rewind(k)
+        t0 = time.perf_counter()
+        reports = d.PoseGraph.optimize_batch(graphs[:k], max_records=0)
+        batch_ms[k] = (time.perf_counter() - t0) * 1e3
+        same = same and equal(k, reports, False)
+    rewind(count)
+    same = same and equal(count, d.PoseGraph.optimize_batch(graphs), True)
+    for g in graphs:
+        g.close()
+    return dict(n=n, m=m, status=report["status"], lm_trials=report["iterations"], cg_iterations=report["cg_iterations"], launch_ms=launch_ms,
+                resident_ms=resident_ms, batch_ms={str(k): v for k, v in batch_ms.items()},
+                batch_us_per_graph={str(k): v * 1e3 / k for k, v in batch_ms.items()}, host_ms=host_ms, host_equals_device=bool(same))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--sizes", default="64,512,4096,32768")
+    ap.add_argument("--sizes", default=None)
+    ap.add_argument("--resident", action="store_true")
+    ap.add_argument("--batches", default="16,256,1024")
+    ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--trials", type=int, default=3)
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--host-max-n", type=int, default=4096)          # (the yardstick's 50 trials of 200 iterations take minutes beyond)
     a = ap.parse_args()
+    if a.resident:
+        for n in (int(s) for s in (a.sizes or "8,64,512").split(",")):
+            print(json.dumps(resident_leg(n, [int(s) for s in a.batches.split(",")], a.host_threads)), flush=True)
+        return
+    a.sizes = a.sizes or "64,512,4096,32768"
     for n in (int(s) for s in a.sizes.split(",")):
         start, fixed, edges, delta = ring_with_loops(n)
         m = len(edges[0])
