@@ -125,6 +125,8 @@ EXPORTS = [
     "dvo_hip_map_create", "dvo_hip_map_destroy", "dvo_hip_map_clear", "dvo_hip_map_insert", "dvo_hip_map_stats", "dvo_hip_map_extract",
     "dvo_hip_frames_world_points", "dvo_hip_map_remove", "dvo_hip_map_move", "dvo_hip_map_rehash",
     "dvo_hip_render_params_default", "dvo_hip_map_render", "dvo_hip_map_render_frames", "dvo_hip_time_map_render",
+    "dvo_hip_frames_set_colour", "dvo_hip_frames_clear_colour", "dvo_hip_frame_download_colour", "dvo_hip_map_create_ex",
+    "dvo_hip_map_extract_colour", "dvo_hip_map_render_colour",
     "dvo_hip_graph_create", "dvo_hip_graph_destroy", "dvo_hip_graph_set_vertices", "dvo_hip_graph_set_poses", "dvo_hip_graph_set_edges",
     "dvo_hip_graph_params_default", "dvo_hip_graph_optimize", "dvo_hip_graph_get_poses", "dvo_hip_graph_edge_stats",
     "dvo_hip_graph_linearise", "dvo_hip_graph_multiply", "dvo_hip_graph_optimize_batch",
@@ -141,6 +143,7 @@ MIXED_PIXEL_CHANNELS = dict(PIXEL_CHANNELS, grey8=1)
 PIXEL_F32 = 5
 DEPTH_U16, DEPTH_F32 = 0, 1
 DEPTH_FORMATS = {"u16": DEPTH_U16, "f32": DEPTH_F32}
+MAP_COLOUR = 1   # DVO_HIP_MAP_COLOUR
 COMM_ID_BYTES = 128
 
 
@@ -256,6 +259,14 @@ def lib():
         L.dvo_hip_map_render.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, fp, dp, rp, C.POINTER(vp), C.POINTER(vp), C.c_int]
         L.dvo_hip_map_render_frames.argtypes = [vp, vp, C.c_int, C.POINTER(vp), dp, rp, C.c_int, C.POINTER(Config), C.c_uint]
         L.dvo_hip_time_map_render.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, fp, dp, rp, C.c_int, fp]
+    if hasattr(L, "dvo_hip_frames_set_colour"):   # (likewise: an older build's map is grey)
+        dp, rp = C.POINTER(C.c_double), C.POINTER(RenderParams)
+        L.dvo_hip_frames_set_colour.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.c_int, C.c_size_t, C.c_int]
+        L.dvo_hip_frames_clear_colour.argtypes = [vp, C.c_int, C.POINTER(vp)]
+        L.dvo_hip_frame_download_colour.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_uint32)]
+        L.dvo_hip_map_create_ex.argtypes = [vp, C.c_float, C.c_size_t, C.c_uint, C.POINTER(vp)]
+        L.dvo_hip_map_extract_colour.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
+        L.dvo_hip_map_render_colour.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, fp, dp, rp, C.POINTER(vp), C.POINTER(vp), C.c_int]
     if hasattr(L, "dvo_hip_graph_create"):   # (likewise: an older build optimises no pose graph)
         dp, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         L.dvo_hip_graph_create.argtypes = [vp, C.POINTER(vp)]

@@ -145,6 +145,10 @@ struct dvo_hip_frame {
   // sensor's own image and registers it into the frame's float plane Z of level 0 first (register_frames), ahead of the lens pass.
   bool rig_on = false;
   dvo_hip_depth_rig rig = {};
+  // The colour of the frame (dvo_hip_frames_set_colour, cloud_colour.h): its own level-0 plane of packed pixels, w0 * h0 dwords, written
+  // and read on the main stream only.  A property like the lens: kept across re-ingests until it is replaced or cleared.
+  bool colour_on = false;
+  DevBuf colour;
 };
 
 // Small host -> device transfers (pointer tables, initial guesses) go through slots of pinned memory: from a pageable
@@ -515,6 +519,7 @@ struct dvo_hip_context {
   DevBuf lens_tbl;                                    // table of the rectify pass (rectify_frames; allocated by the first lens ingest)
   DevBuf graph_jobs, graph_outs;                      // the job records and results of a resident pose-graph launch (capi_graph.inc)
   DevBuf rig_tbl;                                     // table of the register pass (register_frames; allocated by the first rig ingest)
+  DevBuf colour_tbl, colour_stage;                    // the plane table of a k_colour_pack launch and the staging area of host colour planes (capi_colour.inc)
   DevBuf map_tbl, map_stage;                          // the frame table of a keyframe-map launch and the staging area of results that go to host memory (capi_map.inc)
   DevBuf render_tbl, render_zbuf, render_planes;      // a render's view table, its z-buffers and -- dvo_hip_map_render_frames -- the planes the frames ingest (capi_map.inc)
   hipEvent_t render_done = nullptr;                   // recorded behind a render on the main stream: the build stream's ingest waits for it
@@ -864,7 +869,7 @@ void dvo_hip_context_destroy(dvo_hip_context* ctx) {
   if (ctx->build_stream) (void)hipStreamDestroy(ctx->build_stream);
   for (DevBuf& b : ctx->build_tbl) b.release();
   for (DevBuf* b : {&ctx->misc, &ctx->role_tbl_cur, &ctx->role_tbl_ref, &ctx->prep_tbl_cur, &ctx->prep_tbl_ref, &ctx->rcp_table, &ctx->ref_order_planes,
-                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl, &ctx->rig_tbl, &ctx->graph_jobs, &ctx->graph_outs, &ctx->map_tbl, &ctx->map_stage, &ctx->render_tbl, &ctx->render_zbuf, &ctx->render_planes}) b->release();
+                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl, &ctx->rig_tbl, &ctx->graph_jobs, &ctx->graph_outs, &ctx->map_tbl, &ctx->map_stage, &ctx->colour_tbl, &ctx->colour_stage, &ctx->render_tbl, &ctx->render_zbuf, &ctx->render_planes}) b->release();
   if (ctx->render_done) (void)hipEventDestroy(ctx->render_done);
   for (DevBuf& b : ctx->upload_buf) b.release();
   for (const dvo_hip_context::PooledBlock& b : ctx->frame_pool) (void)hipFree(b.p);
@@ -932,6 +937,7 @@ int prepare_roles(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* fram
 
 #include "capi_ingest.inc"   // the raw-frame ingest: dvo_hip_frame_create_*, dvo_hip_frames_update_*, dvo_hip_flush_deferred
 #include "capi_map.inc"      // the keyframe map: dvo_hip_map_*, dvo_hip_frames_world_points, dvo_hip_map_render*
+#include "capi_colour.inc"   // the colour of frames: dvo_hip_frames_set_colour, dvo_hip_frames_clear_colour, dvo_hip_frame_download_colour
 #include "capi_graph.inc"    // the keyframe pose graph: dvo_hip_graph_*
 
 int dvo_hip_upload_wait(dvo_hip_context* ctx) {
@@ -985,6 +991,7 @@ void dvo_hip_frame_destroy(dvo_hip_context* ctx, dvo_hip_frame* frame) {
     }
   }
   frame->sel_mask.release();
+  frame->colour.release();
   frame->pool.release();
   delete frame;
 }

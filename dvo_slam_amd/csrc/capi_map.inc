@@ -7,6 +7,8 @@ struct dvo_hip_map {
   float leaf = 0.0f;
   size_t capacity = 0;                 // slots, a power of two
   DevBuf slots, counters;
+  DevBuf colour;                       // a coloured map (DVO_HIP_MAP_COLOUR): the side table, capacity * sizeof(MapColourSlot); else empty
+  bool coloured = false;
   // kMapCntCandidates, kMapCntDropped and kMapCntUnmatched as last read back (zero after a clear)
   unsigned long long candidates = 0, dropped = 0, unmatched = 0;
 };
@@ -20,6 +22,7 @@ MapTable map_table(const dvo_hip_map* map) {
   t.counters = map->counters.as<unsigned long long>();
   t.capacity = map->capacity;
   t.leaf = map->leaf;
+  t.colour = map->coloured ? map->colour.as<MapColourSlot>() : nullptr;
   return t;
 }
 
@@ -41,6 +44,18 @@ int check_map_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* f
   return DVO_HIP_OK;
 }
 
+// ... and, for a coloured map, that every frame carries colour and that its level is level 0 halved (cloud_colour.h: every block lies inside)
+int check_map_colour(dvo_hip_context* ctx, const dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, int level, const char* who) {
+  if (!map->coloured) return DVO_HIP_OK;                       // (a grey map ignores attached colour)
+  for (int i = 0; i < n_frames; ++i) {
+    const dvo_hip_frame* f = frames[i];
+    if (!f->colour_on) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a coloured map takes frames that carry colour (dvo_hip_frames_set_colour)");
+    if (f->lv[level].w != f->lv[0].w >> level || f->lv[level].h != f->lv[0].h >> level)
+      return fail(ctx, DVO_HIP_ERR_INVALID, who, "the level is not level 0 halved (cloud_colour.h)");
+  }
+  return DVO_HIP_OK;
+}
+
 // one entry of a launch's frame table: a frame under a pose, added (+1) or -- dvo_hip_map_remove, dvo_hip_map_move -- subtracted (-1)
 struct MapEntry {
   dvo_hip_frame* frame;
@@ -51,7 +66,8 @@ struct MapEntry {
 
 // The frame table of one launch on the main stream: the {I, Z} pairs of `level` come from plane C where the frame holds it, else from the
 // taps A (built now where missing: what dvo_hip_frame_download_plane reads planes 0 and 1 from).  A frame may stand in several entries.
-int upload_map_entries(dvo_hip_context* ctx, const std::vector<MapEntry>& entries, int level, int* total_blocks) {
+// coloured: the entries also name the frames' colour planes (checked: check_map_colour).
+int upload_map_entries(dvo_hip_context* ctx, const std::vector<MapEntry>& entries, int level, int* total_blocks, bool coloured = false) {
   std::vector<dvo_hip_frame*> frames;
   for (const MapEntry& e : entries)
     if (std::find(frames.begin(), frames.end(), e.frame) == frames.end()) frames.push_back(e.frame);
@@ -86,6 +102,9 @@ int upload_map_entries(dvo_hip_context* ctx, const std::vector<MapEntry>& entrie
     m.h = L.h;
     m.first_block = blocks;
     m.sign = entries[i].sign;
+    m.colour = coloured ? f->colour.as<uint32_t>() : nullptr;
+    m.colour_pitch = f->lv[0].w;
+    m.shift = level;
     blocks += (L.w * L.h + 255) / 256;
   }
   std::memset(&host[entries.size()], 0, sizeof(MapFrame));
@@ -99,10 +118,10 @@ int upload_map_entries(dvo_hip_context* ctx, const std::vector<MapEntry>& entrie
 
 // ... of n frames under poses[16 * i ..], all added.  outs (may be null): MapFrame::out.
 int upload_map_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float* const* outs,
-                      int* total_blocks) {
+                      int* total_blocks, bool coloured = false) {
   std::vector<MapEntry> entries;
   for (int i = 0; i < n_frames; ++i) entries.push_back(MapEntry{frames[i], map_pose_prepare(poses + size_t(i) * 16), 1, outs ? outs[i] : nullptr});
-  return upload_map_entries(ctx, entries, level, total_blocks);
+  return upload_map_entries(ctx, entries, level, total_blocks, coloured);
 }
 
 // (only k_map_insert moves the candidates, the dropped and the unmatched points, and every insert, remove and move ends with this read:
@@ -125,9 +144,14 @@ int check_map(dvo_hip_context* ctx, const dvo_hip_map* map, const char* who) {
 }  // namespace
 
 int dvo_hip_map_create(dvo_hip_context* ctx, float leaf, size_t capacity_slots, dvo_hip_map** out) {
+  return dvo_hip_map_create_ex(ctx, leaf, capacity_slots, 0u, out);
+}
+
+int dvo_hip_map_create_ex(dvo_hip_context* ctx, float leaf, size_t capacity_slots, unsigned flags, dvo_hip_map** out) {
   DVO_LOCK(ctx);
   if (!ctx || !out) return fail(ctx, DVO_HIP_ERR_INVALID, "map_create: bad argument");
   *out = nullptr;
+  if (flags & ~DVO_HIP_MAP_COLOUR) return fail(ctx, DVO_HIP_ERR_INVALID, "map_create: unknown flag");
   if (!(leaf > 0.0f && leaf < INFINITY)) return fail(ctx, DVO_HIP_ERR_INVALID, "map_create: the leaf size must be finite and > 0");
   if (capacity_slots > (size_t(1) << 32)) return fail(ctx, DVO_HIP_ERR_INVALID, "map_create: at most 2^32 slots");
   size_t capacity = 64;
@@ -137,7 +161,9 @@ int dvo_hip_map_create(dvo_hip_context* ctx, float leaf, size_t capacity_slots, 
   map->ctx = ctx;
   map->leaf = leaf;
   map->capacity = capacity;
+  map->coloured = (flags & DVO_HIP_MAP_COLOUR) != 0;
   hipError_t e = map->slots.reserve(capacity * sizeof(MapSlot));
+  if (e == hipSuccess && map->coloured) e = map->colour.reserve(capacity * sizeof(MapColourSlot));
   if (e == hipSuccess) e = map->counters.reserve(sizeof(unsigned long long) * kMapCounters);
   if (e == hipSuccess) {
     launch_map_clear(ctx->stream, map_table(map));
@@ -145,6 +171,7 @@ int dvo_hip_map_create(dvo_hip_context* ctx, float leaf, size_t capacity_slots, 
   }
   if (e != hipSuccess) {
     map->slots.release();
+    map->colour.release();
     map->counters.release();
     delete map;
     ctx->err = std::string("map_create: ") + hipGetErrorString(e);
@@ -162,6 +189,7 @@ void dvo_hip_map_destroy(dvo_hip_context* ctx, dvo_hip_map* map) {
     (void)hipStreamSynchronize(ctx->stream);
   }
   map->slots.release();
+  map->colour.release();
   map->counters.release();
   delete map;
 }
@@ -182,14 +210,15 @@ int dvo_hip_map_insert(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo
   DVO_ENTER(ctx);
   int rc = check_map(ctx, map, "map_insert");
   if (rc == DVO_HIP_OK) rc = check_map_frames(ctx, n_frames, frames, poses, level, min_depth, max_depth, "map_insert");
+  if (rc == DVO_HIP_OK) rc = check_map_colour(ctx, map, n_frames, frames, level, "map_insert");
   if (rc != DVO_HIP_OK) return rc;
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const unsigned long long candidates_before = map->candidates, dropped_before = map->dropped;
   unsigned long long after[kMapCounters];
   int blocks = 0;
-  rc = upload_map_frames(ctx, n_frames, frames, poses, level, nullptr, &blocks);
+  rc = upload_map_frames(ctx, n_frames, frames, poses, level, nullptr, &blocks, map->coloured);
   if (rc != DVO_HIP_OK) return rc;
-  launch_map_insert(ctx->stream, ctx->map_tbl.as<MapFrame>(), n_frames, blocks, map_table(map), min_depth, max_depth);
+  (map->coloured ? launch_map_insert_colour : launch_map_insert)(ctx->stream, ctx->map_tbl.as<MapFrame>(), n_frames, blocks, map_table(map), min_depth, max_depth);
   DVO_HIP_TRY(ctx, hipGetLastError());
   rc = read_map_counters(ctx, map, after);
   if (rc != DVO_HIP_OK) return rc;
@@ -208,6 +237,7 @@ int map_update(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_fra
                bool move, int level, float min_depth, float max_depth, const char* who) {
   int rc = check_map(ctx, map, who);
   if (rc == DVO_HIP_OK) rc = check_map_frames(ctx, n_frames, frames, poses_old, level, min_depth, max_depth, who, move ? 2 : 1);
+  if (rc == DVO_HIP_OK) rc = check_map_colour(ctx, map, n_frames, frames, level, who);
   if (rc != DVO_HIP_OK) return rc;
   if (move && !poses_new) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
   if (map->dropped != 0)
@@ -232,9 +262,9 @@ int map_update(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_fra
   const unsigned long long candidates_before = map->candidates, dropped_before = map->dropped, unmatched_before = map->unmatched;
   unsigned long long after[kMapCounters];
   int blocks = 0;
-  rc = upload_map_entries(ctx, entries, level, &blocks);
+  rc = upload_map_entries(ctx, entries, level, &blocks, map->coloured);
   if (rc != DVO_HIP_OK) return rc;
-  launch_map_update(ctx->stream, ctx->map_tbl.as<MapFrame>(), int(entries.size()), blocks, map_table(map), min_depth, max_depth);
+  (map->coloured ? launch_map_update_colour : launch_map_update)(ctx->stream, ctx->map_tbl.as<MapFrame>(), int(entries.size()), blocks, map_table(map), min_depth, max_depth);
   DVO_HIP_TRY(ctx, hipGetLastError());
   rc = read_map_counters(ctx, map, after);
   if (rc != DVO_HIP_OK) return rc;
@@ -275,8 +305,9 @@ int dvo_hip_map_rehash(dvo_hip_context* ctx, dvo_hip_map* map, size_t capacity_s
     return fail(ctx, DVO_HIP_ERR_INVALID, "map_rehash: the capacity must be a power of two, 64 .. 2^32 slots (0: as it is)");
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   // the second table and its counters: both tables exist during this call only
-  DevBuf slots, counters;
+  DevBuf slots, counters, colour;
   hipError_t e = slots.reserve(capacity * sizeof(MapSlot));
+  if (e == hipSuccess && map->coloured) e = colour.reserve(capacity * sizeof(MapColourSlot));
   if (e == hipSuccess) e = counters.reserve(sizeof(unsigned long long) * kMapCounters);
   unsigned long long was[kMapCounters], now[kMapCounters];
   if (e == hipSuccess) {
@@ -284,6 +315,7 @@ int dvo_hip_map_rehash(dvo_hip_context* ctx, dvo_hip_map* map, size_t capacity_s
     to.slots = slots.as<MapSlot>();
     to.counters = counters.as<unsigned long long>();
     to.capacity = capacity;
+    to.colour = map->coloured ? colour.as<MapColourSlot>() : nullptr;
     launch_map_rehash(ctx->stream, map_table(map), to);
     e = hipGetLastError();
   }
@@ -301,6 +333,7 @@ int dvo_hip_map_rehash(dvo_hip_context* ctx, dvo_hip_map* map, size_t capacity_s
   if (e != hipSuccess || !fits) {
     if (e != hipSuccess) (void)hipStreamSynchronize(ctx->stream);   // (nothing still writes the table that is freed)
     slots.release();
+    colour.release();
     counters.release();
     if (e != hipSuccess) {
       ctx->err = std::string("map_rehash: ") + hipGetErrorString(e);
@@ -310,8 +343,10 @@ int dvo_hip_map_rehash(dvo_hip_context* ctx, dvo_hip_map* map, size_t capacity_s
     return DVO_HIP_ERR_CAPACITY;
   }
   std::swap(map->slots, slots);
+  std::swap(map->colour, colour);
   std::swap(map->counters, counters);
   slots.release();
+  colour.release();
   counters.release();
   map->capacity = capacity;
   map->candidates = now[kMapCntCandidates];
@@ -347,13 +382,17 @@ int dvo_hip_map_stats(dvo_hip_context* ctx, dvo_hip_map* map, struct dvo_hip_map
   return DVO_HIP_OK;
 }
 
-int dvo_hip_map_extract(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_points, float* xyzi, uint32_t* counts_or_null, uint64_t* keys_or_null,
-                        int out_on_device, size_t* n_points) {
-  DVO_LOCK(ctx);
-  const int rc0 = check_map(ctx, map, "map_extract");
+namespace {
+
+// dvo_hip_map_extract (with_colour false, rgba null) and dvo_hip_map_extract_colour
+int map_extract(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_points, float* xyzi, bool with_colour, uint32_t* rgba, uint32_t* counts_or_null,
+                uint64_t* keys_or_null, int out_on_device, size_t* n_points, const char* who) {
+  const int rc0 = check_map(ctx, map, who);
   if (rc0 != DVO_HIP_OK) return rc0;
-  if (!n_points || (max_points > 0 && !xyzi)) return fail(ctx, DVO_HIP_ERR_INVALID, "map_extract: bad argument");
-  if (out_on_device && xyzi && reinterpret_cast<uintptr_t>(xyzi) % 16 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, "map_extract: a device xyzi must be 16-byte aligned");
+  if (with_colour && !map->coloured) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no colour (dvo_hip_map_create_ex, DVO_HIP_MAP_COLOUR)");
+  if (!n_points || (max_points > 0 && (!xyzi || (with_colour && !rgba)))) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  if (out_on_device && xyzi && reinterpret_cast<uintptr_t>(xyzi) % 16 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device xyzi must be 16-byte aligned");
+  if (out_on_device && rgba && reinterpret_cast<uintptr_t>(rgba) % 4 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device rgba must be 4-byte aligned");
   *n_points = 0;
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const MapTable t = map_table(map);
@@ -368,26 +407,43 @@ int dvo_hip_map_extract(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_point
   if (take > 0) {
     float4* d_xyzi = reinterpret_cast<float4*>(xyzi);
     uint32_t* d_counts = counts_or_null;
+    uint32_t* d_rgba = rgba;
     unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(keys_or_null);
     if (!out_on_device) {
-      DVO_HIP_TRY(ctx, ctx->map_stage.reserve(take * 28));
+      DVO_HIP_TRY(ctx, ctx->map_stage.reserve(take * 32));
+      d_rgba = rgba ? reinterpret_cast<uint32_t*>(ctx->map_stage.as<char>() + take * 28) : nullptr;
       d_xyzi = ctx->map_stage.as<float4>();
       d_keys = keys_or_null ? reinterpret_cast<unsigned long long*>(ctx->map_stage.as<char>() + take * 16) : nullptr;
       d_counts = counts_or_null ? reinterpret_cast<uint32_t*>(ctx->map_stage.as<char>() + take * 24) : nullptr;
     }
-    DVO_HIP_TRY(ctx, launch_map_extract(ctx->stream, t, take, d_xyzi, d_counts, d_keys));
+    DVO_HIP_TRY(ctx, launch_map_extract_colour(ctx->stream, t, take, d_xyzi, d_counts, d_keys, d_rgba));
     DVO_HIP_TRY(ctx, hipGetLastError());
     if (!out_on_device) {
       DVO_HIP_TRY(ctx, hipMemcpyAsync(xyzi, d_xyzi, take * 16, hipMemcpyDeviceToHost, ctx->stream));
       if (keys_or_null) DVO_HIP_TRY(ctx, hipMemcpyAsync(keys_or_null, d_keys, take * 8, hipMemcpyDeviceToHost, ctx->stream));
       if (counts_or_null) DVO_HIP_TRY(ctx, hipMemcpyAsync(counts_or_null, d_counts, take * 4, hipMemcpyDeviceToHost, ctx->stream));
+      if (rgba) DVO_HIP_TRY(ctx, hipMemcpyAsync(rgba, d_rgba, take * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   *n_points = take;
-  if (occupied > max_points) return fail(ctx, DVO_HIP_ERR_CAPACITY, "map_extract: max_points is smaller than the number of occupied voxels (dvo_hip_map_stats)");
-  if (over != 0) return fail(ctx, DVO_HIP_ERR_CAPACITY, "map_extract: a voxel holds more than 2^20 points; its sums may have wrapped");
+  if (occupied > max_points) return fail(ctx, DVO_HIP_ERR_CAPACITY, who, "max_points is smaller than the number of occupied voxels (dvo_hip_map_stats)");
+  if (over != 0) return fail(ctx, DVO_HIP_ERR_CAPACITY, who, "a voxel holds more than 2^20 points; its sums may have wrapped");
   return DVO_HIP_OK;
+}
+
+}  // namespace
+
+int dvo_hip_map_extract(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_points, float* xyzi, uint32_t* counts_or_null, uint64_t* keys_or_null,
+                        int out_on_device, size_t* n_points) {
+  DVO_LOCK(ctx);
+  return map_extract(ctx, map, max_points, xyzi, false, nullptr, counts_or_null, keys_or_null, out_on_device, n_points, "map_extract");
+}
+
+int dvo_hip_map_extract_colour(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_points, float* xyzi, uint32_t* rgba, uint32_t* counts_or_null,
+                               uint64_t* keys_or_null, int out_on_device, size_t* n_points) {
+  DVO_LOCK(ctx);
+  return map_extract(ctx, map, max_points, xyzi, true, rgba, counts_or_null, keys_or_null, out_on_device, n_points, "map_extract_colour");
 }
 
 int dvo_hip_frames_world_points(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float min_depth,
@@ -522,6 +578,50 @@ int dvo_hip_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int 
   if (!out_on_device) {
     for (int i = 0; i < n_views; ++i) {
       DVO_HIP_TRY(ctx, hipMemcpyAsync(intensity_out[i], si[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(depth_out[i], sz[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_map_render_colour(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float K[4], const double* poses,
+                              const dvo_hip_render_params* params, uint32_t* const* rgba_out, float* const* depth_out, int out_on_device) {
+  DVO_ENTER(ctx);
+  const char* who = "map_render_colour";
+  RenderArgs args;
+  const int rc0 = check_render(ctx, map, n_views, width, height, K, poses, params, &args, who);
+  if (rc0 != DVO_HIP_OK) return rc0;
+  if (!map->coloured) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no colour (dvo_hip_map_create_ex, DVO_HIP_MAP_COLOUR)");
+  if (!rgba_out || !depth_out) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  for (int i = 0; i < n_views; ++i) {
+    if (!rgba_out[i] || !depth_out[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null output");
+    if (out_on_device && (!aligned_to(rgba_out[i], 16) || !aligned_to(depth_out[i], 16)))
+      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device plane must be 16-byte aligned");
+  }
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t pixels = size_t(width) * size_t(height), plane = (pixels * 4 + 15) & ~size_t(15);
+  // (RenderPlanes::I holds the address of the uint32 rgba plane of a colour view: k_render_resolve stores the bits as they are)
+  std::vector<float*> sc, sz;
+  for (int i = 0; i < n_views; ++i) {
+    if (out_on_device) {
+      sc.push_back(reinterpret_cast<float*>(rgba_out[i]));
+      sz.push_back(depth_out[i]);
+    } else {
+      if (i == 0) DVO_HIP_TRY(ctx, ctx->map_stage.reserve(plane * 2 * size_t(n_views)));
+      sc.push_back(reinterpret_cast<float*>(ctx->map_stage.as<char>() + plane * (2 * size_t(i))));
+      sz.push_back(reinterpret_cast<float*>(ctx->map_stage.as<char>() + plane * (2 * size_t(i) + 1)));
+    }
+  }
+  const int rc = upload_views(ctx, n_views, width, height, K, poses, sc.data(), sz.data());
+  if (rc != DVO_HIP_OK) return rc;
+  launch_map_render_colour(ctx->stream, map_table(map), render_views(ctx), render_outs(ctx, n_views), n_views, (long long)pixels, args,
+                           ctx->render_zbuf.as<unsigned long long>());
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  ctx->map_renders += n_views;
+  if (!out_on_device) {
+    for (int i = 0; i < n_views; ++i) {
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(rgba_out[i], sc[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
       DVO_HIP_TRY(ctx, hipMemcpyAsync(depth_out[i], sz[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -23,6 +23,14 @@
 // lane that wins the slot's CAS is its only writer (live keys are unique) and stores the 24 bytes of sums with plain vector stores.
 // k_map_extract compacts the occupied slots into the caller's arrays, one atomic add of the active-lane count per wavefront on the
 // output cursor, bounded by max_points; the order of the output is unspecified.  No LDS, no barriers, 256-thread workgroups.
+// A COLOURED map (cloud_colour.h; MapTable::colour, a side table of 16 bytes per slot at the slot's index) runs the COLOUR instantiation
+// of k_map_insert: a valid lane forms the colour of its pixel from the frame's level-0 plane of packed pixels (dword loads: the rows of
+// an odd-width plane are not 16-byte aligned; 4 B per pixel at level 0, the 2^L x 2^L block above it), the run folding carries two more
+// packed words through the same suffix sum (r | g << 16 and b: 64 * 255 = 16320 < 2^16, no carry between the halves), and the leader
+// issues two more return-less adds on colour[at] ({sr, sg} as a 64-bit word, sb as a 32-bit one), negated for a minus frame.  Probing,
+// claiming and counting are untouched, and the instantiations without COLOUR are the kernels of a grey map as they were.  k_map_clear
+// zeroes the side table with the slots, k_map_rehash's winning lane copies the old index's 16 bytes to the new one, k_map_extract writes
+// the colour record at the xyzi record's index where it is given an array for it.
 #include "global_ptr.h"
 #include "launch.h"
 #include "cloud_map.h"
@@ -73,7 +81,8 @@ __global__ __launch_bounds__(256) void k_world_points(const MapFrame* __restrict
 }
 
 // MIXED: the frames carry signs (a remove or a move); without it every frame is inserted and MapFrame::sign is not read
-template <bool COMBINE, bool MIXED>
+// COLOUR: the map has a side table of colour sums (m.colour) and every frame a plane of packed pixels (MapFrame::colour)
+template <bool COMBINE, bool MIXED, bool COLOUR>
 __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__ tbl, int n_frames, MapTable m, float min_depth, float max_depth) {
 #pragma clang fp contract(off)
   const MapFrame& f = tbl[map_frame_of(tbl, n_frames, int(blockIdx.x))];
@@ -83,7 +92,7 @@ __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__
   const bool active = i < f.w * f.h;
   bool unusable = false, out_of_range = false, valid = false;
   unsigned long long key = 0;
-  uint32_t q[4] = {0, 0, 0, 0};
+  uint32_t q[4] = {0, 0, 0, 0}, rgb = 0;
   if (active) {
     const GlobalF32x2 iz = *(Global<const GlobalF32x2>)global_ptr(f.iz + size_t(i) * f.stride);
     const float K[4] = {f.K[0], f.K[1], f.K[2], f.K[3]};
@@ -93,6 +102,10 @@ __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__
     else if (!map_key_of(P, iz.x, m.leaf, &k, q)) out_of_range = true;
     else valid = true;
     key = k;
+    if constexpr (COLOUR) {
+      // (valid: 0 <= u < w, 0 <= v < h of the level, so the block lies inside the level-0 plane, cloud_colour.h)
+      if (valid) rgb = colour_level(f.colour, f.colour_pitch, i % f.w, i / f.w, f.shift);
+    }
   }
   const unsigned long long validmask = __ballot(valid);
   if (minus) {
@@ -107,6 +120,8 @@ __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__
 
   // what this lane adds: {qx | qy << 16}, {qz | n << 16}, qi
   uint32_t a = valid ? q[0] | q[1] << 16 : 0u, b = valid ? q[2] | 1u << 16 : 0u, c = valid ? q[3] : 0u;
+  // ... and to the side table of a coloured map: {r | g << 16}, b (0 from a lane that is not valid)
+  uint32_t cw = colour_r(rgb) | colour_g(rgb) << 16, cb = colour_b(rgb);
   bool leader = valid;
   if constexpr (COMBINE) {
     const unsigned long long prev_key = __shfl_up(key, 1);
@@ -119,6 +134,10 @@ __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__
       // lanes lane + 1 .. lane + d all continue this lane's run: lane + d holds the sum of the next (up to) d lanes of the same run
       const bool same_run = lane + d < 64 && ((breaks >> (lane + 1)) & ((1ull << d) - 1ull)) == 0;
       if (same_run) { a += ua; b += ub; c += uc; }
+      if constexpr (COLOUR) {
+        const uint32_t uw = __shfl_down(cw, d), uv = __shfl_down(cb, d);
+        if (same_run) { cw += uw; cb += uv; }
+      }
     }
   }
   const uint32_t n = b >> 16, sx = a & 0xffffu, sy = a >> 16, sz = b & 0xffffu, si = c;
@@ -141,6 +160,12 @@ __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__
       (void)__hip_atomic_fetch_add(words + 1, minus ? map_negate(w1) : w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       (void)__hip_atomic_fetch_add(words + 2, minus ? map_negate(w2) : w2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       (void)__hip_atomic_fetch_add(&slot->si, minus ? 0u - si : si, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if constexpr (COLOUR) {
+        MapColourSlot* tint = m.colour + at;                   // (the side table has the slots' capacity)
+        const unsigned long long w3 = colour_word(cw & 0xffffu, cw >> 16);
+        (void)__hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(tint), minus ? map_negate(w3) : w3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        (void)__hip_atomic_fetch_add(&tint->sb, minus ? 0u - cb : cb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
       placed = true;
       break;
     }
@@ -151,9 +176,10 @@ __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__
   wave_count(m.counters + kMapCntOccupied, __ballot(claimed), lane);
 }
 
-// xyzi == null: count only (live slots into the cursor, voxels over the limit, vacant slots)
+// xyzi == null: count only (live slots into the cursor, voxels over the limit, vacant slots).  rgba (a coloured map, or null): the
+// voxel's colour record at the index of its xyzi record
 __global__ __launch_bounds__(256) void k_map_extract(MapTable m, unsigned long long max_points, float4* __restrict__ xyzi, uint32_t* __restrict__ counts,
-                                                     unsigned long long* __restrict__ keys) {
+                                                     unsigned long long* __restrict__ keys, uint32_t* __restrict__ rgba) {
 #pragma clang fp contract(off)
   const int lane = int(threadIdx.x) & 63;
   const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
@@ -178,6 +204,10 @@ __global__ __launch_bounds__(256) void k_map_extract(MapTable m, unsigned long l
       gstore((Global<float4>)global_ptr(xyzi) + idx, make_float4(rec[0], rec[1], rec[2], rec[3]));
       if (counts) counts[idx] = n;
       if (keys) keys[idx] = key;
+      if (rgba) {
+        const GlobalU32x4 t = *(Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(m.colour + at));   // sr sg sb pad
+        rgba[idx] = colour_extract(n, t.x, t.y, t.z);
+      }
     }
   }
 }
@@ -205,6 +235,9 @@ __global__ __launch_bounds__(256) void k_map_rehash(MapTable from, MapTable to) 
         const GlobalU32x2 n_sx = {lo.z, lo.w};
         *(Global<GlobalU32x2>)global_ptr(reinterpret_cast<GlobalU32x2*>(words + 1)) = n_sx;
         *(Global<GlobalU32x4>)global_ptr(reinterpret_cast<GlobalU32x4*>(words + 2)) = hi;
+        if (from.colour)                                       // (a coloured map: both tables have a side table)
+          *(Global<GlobalU32x4>)global_ptr(reinterpret_cast<GlobalU32x4*>(to.colour + at)) =
+              *(Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(from.colour + src));
         placed = true;
         break;
       }
@@ -221,6 +254,7 @@ __global__ __launch_bounds__(256) void k_map_clear(MapTable m) {
     const auto words = (Global<GlobalU32x4>)global_ptr(reinterpret_cast<GlobalU32x4*>(m.slots + at));
     words[0] = lo;
     words[1] = hi;
+    if (m.colour) *(Global<GlobalU32x4>)global_ptr(reinterpret_cast<GlobalU32x4*>(m.colour + at)) = hi;
   }
   if (blockIdx.x == 0 && threadIdx.x < kMapCounters) m.counters[threadIdx.x] = 0ull;
 }
@@ -237,11 +271,19 @@ void launch_world_points(hipStream_t s, const MapFrame* tbl, int n_frames, int t
 }
 
 void launch_map_insert(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth) {
-  k_map_insert<DVO_MAP_COMBINE_RUNS != 0, false><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+  k_map_insert<DVO_MAP_COMBINE_RUNS != 0, false, false><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
 }
 
 void launch_map_update(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth) {
-  k_map_insert<DVO_MAP_COMBINE_RUNS != 0, true><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+  k_map_insert<DVO_MAP_COMBINE_RUNS != 0, true, false><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+}
+
+void launch_map_insert_colour(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth) {
+  k_map_insert<DVO_MAP_COMBINE_RUNS != 0, false, true><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+}
+
+void launch_map_update_colour(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth) {
+  k_map_insert<DVO_MAP_COMBINE_RUNS != 0, true, true><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
 }
 
 void launch_map_rehash(hipStream_t s, const MapTable& from, const MapTable& to) {
@@ -252,10 +294,15 @@ void launch_map_rehash(hipStream_t s, const MapTable& from, const MapTable& to) 
 bool map_insert_combines_runs() { return DVO_MAP_COMBINE_RUNS != 0; }
 
 hipError_t launch_map_extract(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys) {
+  return launch_map_extract_colour(s, m, max_points, xyzi, counts, keys, nullptr);
+}
+
+hipError_t launch_map_extract_colour(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys,
+                                     uint32_t* rgba) {
   static_assert(kMapCntCursor == kMapCntOverLimit + 1 && kMapCntVacant == kMapCntOverLimit + 2, "what a pass counts lies together");
   const hipError_t e = hipMemsetAsync(m.counters + kMapCntOverLimit, 0, 3 * sizeof(unsigned long long), s);
   if (e != hipSuccess) return e;
-  k_map_extract<<<dim3(table_grid(m.capacity)), dim3(256), 0, s>>>(m, max_points, xyzi, counts, keys);
+  k_map_extract<<<dim3(table_grid(m.capacity)), dim3(256), 0, s>>>(m, max_points, xyzi, counts, keys, m.colour ? rgba : nullptr);
   return hipSuccess;
 }
 

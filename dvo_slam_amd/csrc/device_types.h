@@ -7,6 +7,7 @@
 #include "lens.h"
 #include "depth_rig.h"
 #include "cloud_map.h"
+#include "cloud_colour.h"
 #include "map_render.h"
 
 #include "../../include/dvo_hip.h"
@@ -200,6 +201,8 @@ struct MapFrame {
   int w, h, stride;
   int first_block;
   int sign;                            // k_map_insert: +1 the frame's points are added, -1 they are subtracted (cloud_map.h, Removal)
+  const uint32_t* colour;              // coloured map: the frame's level-0 plane of packed pixels (cloud_colour.h); else null, not read
+  int colour_pitch, shift;             // ... its dwords per row, and the level the frame's pixels are taken at (a block of 2^shift a side)
 };
 // the table and the counters of a map as the kernels see them; counters: kMapCnt* (cloud_map.hip)
 struct MapTable {
@@ -207,8 +210,18 @@ struct MapTable {
   unsigned long long* counters;
   unsigned long long capacity;         // a power of two
   float leaf;
+  MapColourSlot* colour;               // the side table of a coloured map (cloud_colour.h), same index as slots; null for a grey map
 };
-// the tight float planes of one rendered view (k_render_resolve, map_render.hip; include/dvo_hip.h, dvo_hip_map_render)
+// one plane of a k_colour_pack launch (cloud_colour.hip; include/dvo_hip.h, dvo_hip_frames_set_colour): the caller's 8-bit colour plane ->
+// the frame's plane of packed pixels, w * h dwords, tight.  Planes of different sizes share a launch like MapFrame's.
+struct ColourPlane {
+  const uint8_t* src;                  // rows of `pitch` bytes, `channels` bytes per pixel
+  uint32_t* dst;
+  int w, h, pitch;
+  int first_block;
+};
+// the tight planes of one rendered view (k_render_resolve, map_render.hip; include/dvo_hip.h, dvo_hip_map_render): floats -- or, of a
+// colour view (dvo_hip_map_render_colour), I holds the address of the uint32 rgba plane
 struct RenderPlanes {
   float* I;
   float* Z;

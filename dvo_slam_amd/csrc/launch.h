@@ -92,6 +92,19 @@ void launch_map_rehash(hipStream_t s, const MapTable& from, const MapTable& to);
 bool map_insert_combines_runs();
 hipError_t launch_map_extract(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys);
 void launch_map_clear(hipStream_t s, const MapTable& m);
+// ... of a COLOURED map (m.colour is its side table, every MapFrame carries a plane of packed pixels; cloud_colour.h): the same launches
+// with the colour sums carried along; launch_map_extract_colour writes the colour records into rgba as well (null: not wanted).
+// launch_map_clear and launch_map_rehash handle the side table wherever the table has one.
+void launch_map_insert_colour(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth);
+void launch_map_update_colour(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth);
+hipError_t launch_map_extract_colour(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys,
+                                     uint32_t* rgba);
+
+// cloud_colour.hip: the colour planes of frames (cloud_colour.h).  launch_colour_pack: n_planes 8-bit colour planes of one pixel format
+// into planes of packed pixels (tbl: n_planes entries and one more whose first_block is total_blocks).  launch_colour_level: the
+// level-`shift` colour plane (w x h, tight) of a level-0 plane of packed pixels with rows of `pitch` dwords.
+void launch_colour_pack(hipStream_t s, const ColourPlane* tbl, int n_planes, int total_blocks, int pixel_format);
+void launch_colour_level(hipStream_t s, const uint32_t* plane, int pitch, int shift, int w, int h, uint32_t* out);
 
 // map_render.hip: views of the keyframe map (map_render.h).  n_views views of `pixels` = w * h pixels each; zbuf: pixels * n_views
 // elements.  launch_render_fill: every element ~0.  launch_render_splat: every voxel of the table into every view, an atomic minimum per
@@ -101,6 +114,11 @@ void launch_render_splat(hipStream_t s, const MapTable& m, const MapView* views,
 void launch_render_resolve(hipStream_t s, const unsigned long long* zbuf, const RenderPlanes* out, int n_views, long long pixels);
 void launch_map_render(hipStream_t s, const MapTable& m, const MapView* views, const RenderPlanes* out, int n_views, long long pixels, const RenderArgs& a,
                        unsigned long long* zbuf);
+// ... of a colour view (cloud_colour.h): the element's low half is the voxel's colour, out[view].I holds the address of the uint32 rgba plane
+void launch_render_splat_colour(hipStream_t s, const MapTable& m, const MapView* views, int n_views, const RenderArgs& a, unsigned long long* zbuf);
+void launch_render_resolve_colour(hipStream_t s, const unsigned long long* zbuf, const RenderPlanes* out, int n_views, long long pixels);
+void launch_map_render_colour(hipStream_t s, const MapTable& m, const MapView* views, const RenderPlanes* out, int n_views, long long pixels,
+                              const RenderArgs& a, unsigned long long* zbuf);
 bool map_render_preloads();
 
 // pose_graph.hip: the stages of the pose-graph optimiser (pose_graph.h), kPgBlock edges or vertices per workgroup.  *_partials: one

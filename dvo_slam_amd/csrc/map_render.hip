@@ -14,6 +14,9 @@
 // so a stale value can only send a lane to the atomic, which decides.
 // k_render_resolve turns the z-buffer into the planes: 8 B read, 4 B stored to I and 4 B to Z per pixel, a lane per pixel, a wavefront
 // 64 consecutive pixels (256 contiguous bytes per plane), the view again in the grid's y.  No LDS, no barriers, 256-thread workgroups.
+// A colour view (cloud_colour.h; dvo_hip_map_render_colour) runs the COLOUR instantiations: the splat reads 16 more bytes per live voxel
+// (the side table's sums) and puts the voxel's colour where the intensity's bits were -- the depth half of the element, the footprint and
+// the atomic are the grey view's -- and the resolve stores the colour word in place of I.
 #include "global_ptr.h"
 #include "launch.h"
 #include "map_render.h"
@@ -38,7 +41,7 @@ __global__ __launch_bounds__(256) void k_render_fill(unsigned long long* __restr
   if ((elements & 1) && blockIdx.x == 0 && threadIdx.x == 0) zbuf[elements - 1] = kRenderEmpty;
 }
 
-template <bool PRELOAD>
+template <bool PRELOAD, bool COLOUR>
 __global__ __launch_bounds__(256) void k_map_render(MapTable m, const MapView* __restrict__ views, int n_views, RenderArgs a,
                                                     unsigned long long* __restrict__ zbuf) {
 #pragma clang fp contract(off)
@@ -56,6 +59,10 @@ __global__ __launch_bounds__(256) void k_map_render(MapTable m, const MapView* _
       const GlobalU32x2 ns = words[1], yz = words[2], ip = words[3];   // n sx | sy sz | si pad
       RenderFootprint f;
       if (!map_render_voxel(v, a, key, ns.x, ns.y, yz.x, yz.y, ip.x, &f)) continue;
+      if constexpr (COLOUR) {
+        const GlobalU32x4 t = *(Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(m.colour + at));   // sr sg sb pad
+        f.value = colour_render_value(f.value, colour_extract(ns.x, t.x, t.y, t.z));   // (drawn: n >= min_points >= 1)
+      }
       // f lies inside the image (map_render_axis clips): 0 <= u0 <= u1 <= w - 1, 0 <= v0 <= v1 <= h - 1
       const int nu = f.u1 - f.u0 + 1, nv = f.v1 - f.v0 + 1;
       for (int dy = 0; dy < max_splat; ++dy) {
@@ -73,6 +80,7 @@ __global__ __launch_bounds__(256) void k_map_render(MapTable m, const MapView* _
   }
 }
 
+template <bool COLOUR>
 __global__ __launch_bounds__(256) void k_render_resolve(const unsigned long long* __restrict__ zbuf, const RenderPlanes* __restrict__ out, int n_views,
                                                         long long pixels) {
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -82,10 +90,17 @@ __global__ __launch_bounds__(256) void k_render_resolve(const unsigned long long
     const auto Zout = (Global<float>)global_ptr(out[view].Z);
     for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < pixels; p += stride) {   // (p < pixels: inside the view's planes)
       const GlobalU32x2 e = E[p];
-      float I, Z;
-      map_render_resolve((unsigned long long)e.x | (unsigned long long)e.y << 32, &I, &Z);
-      Iout[p] = I;
-      Zout[p] = Z;
+      if constexpr (COLOUR) {
+        uint32_t rgba, z;
+        colour_render_resolve((unsigned long long)e.x | (unsigned long long)e.y << 32, &rgba, &z);
+        Iout[p] = __uint_as_float(rgba);                       // (the plane is the caller's uint32 plane: the bits are stored as they are)
+        Zout[p] = __uint_as_float(z);
+      } else {
+        float I, Z;
+        map_render_resolve((unsigned long long)e.x | (unsigned long long)e.y << 32, &I, &Z);
+        Iout[p] = I;
+        Zout[p] = Z;
+      }
     }
   }
 }
@@ -111,11 +126,11 @@ void launch_render_fill(hipStream_t s, unsigned long long* zbuf, long long eleme
 }
 
 void launch_render_splat(hipStream_t s, const MapTable& m, const MapView* views, int n_views, const RenderArgs& a, unsigned long long* zbuf) {
-  k_map_render<DVO_RENDER_PRELOAD != 0><<<view_grid((long long)m.capacity, n_views), dim3(256), 0, s>>>(m, views, n_views, a, zbuf);
+  k_map_render<DVO_RENDER_PRELOAD != 0, false><<<view_grid((long long)m.capacity, n_views), dim3(256), 0, s>>>(m, views, n_views, a, zbuf);
 }
 
 void launch_render_resolve(hipStream_t s, const unsigned long long* zbuf, const RenderPlanes* out, int n_views, long long pixels) {
-  k_render_resolve<<<view_grid(pixels, n_views), dim3(256), 0, s>>>(zbuf, out, n_views, pixels);
+  k_render_resolve<false><<<view_grid(pixels, n_views), dim3(256), 0, s>>>(zbuf, out, n_views, pixels);
 }
 
 void launch_map_render(hipStream_t s, const MapTable& m, const MapView* views, const RenderPlanes* out, int n_views, long long pixels, const RenderArgs& a,
@@ -123,6 +138,21 @@ void launch_map_render(hipStream_t s, const MapTable& m, const MapView* views, c
   launch_render_fill(s, zbuf, pixels * n_views);
   launch_render_splat(s, m, views, n_views, a, zbuf);
   launch_render_resolve(s, zbuf, out, n_views, pixels);
+}
+
+void launch_render_splat_colour(hipStream_t s, const MapTable& m, const MapView* views, int n_views, const RenderArgs& a, unsigned long long* zbuf) {
+  k_map_render<DVO_RENDER_PRELOAD != 0, true><<<view_grid((long long)m.capacity, n_views), dim3(256), 0, s>>>(m, views, n_views, a, zbuf);
+}
+
+void launch_render_resolve_colour(hipStream_t s, const unsigned long long* zbuf, const RenderPlanes* out, int n_views, long long pixels) {
+  k_render_resolve<true><<<view_grid(pixels, n_views), dim3(256), 0, s>>>(zbuf, out, n_views, pixels);
+}
+
+void launch_map_render_colour(hipStream_t s, const MapTable& m, const MapView* views, const RenderPlanes* out, int n_views, long long pixels,
+                              const RenderArgs& a, unsigned long long* zbuf) {
+  launch_render_fill(s, zbuf, pixels * n_views);
+  launch_render_splat_colour(s, m, views, n_views, a, zbuf);
+  launch_render_resolve_colour(s, zbuf, out, n_views, pixels);
 }
 
 bool map_render_preloads() { return DVO_RENDER_PRELOAD != 0; }

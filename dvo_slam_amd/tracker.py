@@ -233,6 +233,12 @@ class RgbdImagePyramid:
         rig = getattr(self, "_depth_rig", None)
         if rig is not None:                                  # (... and the depth rig)
             set_depth_rig_batch([self], *rig)
+        colour = getattr(self, "_colour", None)
+        if colour is not None:                               # (... and the colour, from the host copy)
+            if not isinstance(colour[0], np.ndarray):
+                raise ValueError("RgbdImagePyramid.build: the pyramid holds colour from a device address; build it with all its levels "
+                                 "before set_colour, or clear_colour first")
+            set_colour_batch([self], [colour[0]], colour[1], colour[2])
 
     def set_selection(self, mask=None, min_depth=0.0, max_depth=float("inf"), pitch=0):
         """Caller selection of this frame's reference points (an extension over the reference API; include/dvo_hip.h,
@@ -266,6 +272,30 @@ class RgbdImagePyramid:
 
     def clear_depth_rig(self):
         clear_depth_rig_batch([self])
+
+    def set_colour(self, colour, pixel_format="bgr8", pitch=0):
+        """Colour of this frame (include/dvo_hip.h, dvo_hip_frames_set_colour; the reference's level(0).rgb, benchmark_slam.cpp:89-90): a
+        (height, width, 3 | 4) uint8 numpy array (rows may be padded), or a device address (e.g. torch_tensor.data_ptr()) of height rows
+        of `pitch` bytes (0 = tight).  pixel_format: "bgr8" | "rgb8" | "bgra8" | "rgba8".  What a KeyframeMap(colour=True) fuses.  Kept
+        across re-ingests until replaced or cleared: re-attach after re-ingesting other content.  A pyramid with a lens refuses."""
+        set_colour_batch([self], [colour], pixel_format, pitch)
+
+    def clear_colour(self):
+        clear_colour_batch([self])
+
+    def colour(self, level=0):
+        """The colour plane of `level` as the map's insertion sees it (dvo_hip_frame_download_colour): a (h_L, w_L) uint32 array of
+        packed pixels 0x00RRGGBB, per channel the rounded mean of the 2^L x 2^L block of level 0."""
+        if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+            raise TypeError("RgbdImagePyramid.colour: level must be an integer")
+        if not 0 <= level < self.levels:
+            raise ValueError("RgbdImagePyramid.colour: the pyramid has levels 0 .. %d" % (self.levels - 1))
+        if getattr(self, "_colour", None) is None:
+            raise ValueError("RgbdImagePyramid.colour: the pyramid carries no colour (set_colour)")
+        w, h = self.camera.width >> int(level), self.camera.height >> int(level)
+        out = np.empty((h, w), np.uint32)
+        self.ctx.check(self.ctx._lib.dvo_hip_frame_download_colour(self.ctx.ptr, self.ptr, int(level), out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
 
     compute = build                         # deprecated alias in the reference too
 
@@ -621,6 +651,64 @@ def clear_depth_rig_batch(pyramids):
         p._depth_rig = None
 
 
+def _colour_sources(pyramids, sources, pixel_format, pitch, who="set_colour"):
+    """(format, pitch, on_device, addresses, what to keep alive during the call, what each pyramid remembers) of a set_colour call, or
+    ValueError / TypeError: nothing reaches the library with a value it would refuse"""
+    fmt, ch = _pixel_format(pixel_format)
+    n = len(pyramids)
+    if n < 1:
+        raise ValueError("%s: no pyramids" % who)
+    if sources is None or len(sources) != n:
+        raise ValueError("%s: one colour plane per pyramid" % who)
+    if isinstance(pitch, bool) or not isinstance(pitch, (int, np.integer)):
+        raise TypeError("%s: pitch must be an integer" % who)
+    if len(set(id(p) for p in pyramids)) != n:
+        raise ValueError("%s: the same pyramid twice" % who)
+    arrays = [isinstance(a, np.ndarray) for a in sources]
+    if any(arrays) != all(arrays):
+        raise TypeError("%s: the planes of one call are all numpy arrays or all device addresses" % who)
+    for p in pyramids:
+        if p.ctx is not pyramids[0].ctx:
+            raise ValueError("%s: pyramids of more than one context" % who)
+        if getattr(p, "_lens", None) is not None:
+            raise ValueError("%s: a pyramid that carries a lens takes raw sensor planes; attach rectified colour to a pyramid without one" % who)
+    if all(arrays):
+        if int(pitch) != 0:
+            raise ValueError("%s: a numpy array brings its own row stride; pitch is for device addresses" % who)
+        planes = [_colour_plane(a, p.camera.height, p.camera.width, ch) for a, p in zip(sources, pyramids)]
+        tight = all(a.strides[0] == p.camera.width * ch for a, p in zip(planes, pyramids))
+        if not tight and len(set(a.strides[0] for a in planes)) != 1:
+            planes, tight = [np.ascontiguousarray(a) for a in planes], True   # (one pitch per call: mixed paddings go tight)
+        row = 0 if tight else planes[0].strides[0]
+        return fmt, row, 0, [a.ctypes.data for a in planes], planes, [np.array(a, copy=True) for a in planes]
+    for a in sources:
+        if isinstance(a, bool) or not isinstance(a, (int, np.integer)) or int(a) == 0:
+            raise TypeError("%s: a colour plane is a numpy uint8 array or a non-null device address, not %r" % (who, a))
+    for p in pyramids:
+        _pitch(pitch, p.camera.width, ch)
+    return fmt, int(pitch), 1, [int(a) for a in sources], None, [int(a) for a in sources]
+
+
+def set_colour_batch(pyramids, sources, pixel_format="bgr8", pitch=0):
+    """RgbdImagePyramid.set_colour for n pyramids in one launch (dvo_hip_frames_set_colour); they may differ in size."""
+    pyramids = list(pyramids)
+    fmt, row, on_device, addrs, keep, remember = _colour_sources(pyramids, sources, pixel_format, pitch)
+    ctx = pyramids[0].ctx
+    ctx.check(ctx._lib.dvo_hip_frames_set_colour(ctx.ptr, len(pyramids), _handles(pyramids), device_pointer_array(addrs), fmt, row, on_device))
+    for p, r in zip(pyramids, remember):
+        p._colour = (r, pixel_format, 0 if isinstance(r, np.ndarray) else int(pitch))
+
+
+def clear_colour_batch(pyramids):
+    pyramids = list(pyramids)
+    if len(pyramids) < 1:
+        raise ValueError("clear_colour: no pyramids")
+    ctx = pyramids[0].ctx
+    ctx.check(ctx._lib.dvo_hip_frames_clear_colour(ctx.ptr, len(pyramids), _handles(pyramids)))
+    for p in pyramids:
+        p._colour = None
+
+
 def _map_frames_args(pyramids, poses, level, min_depth, max_depth, who):
     """(n, poses as a contiguous [n, 4, 4] float64 array) of a keyframe-map call, or ValueError / TypeError: nothing reaches the library
     with a pose that is not 4 x 4, mismatched lengths, a level a pyramid does not have or an empty depth range."""
@@ -753,7 +841,11 @@ class KeyframeMap:
     does not depend on the order of insertion.  capacity: slots of the table, rounded up to a power of two; keep it at least four
     times the number of voxels (stats())."""
 
-    def __init__(self, ctx=None, leaf=0.01, capacity=1 << 22):
+    def __init__(self, ctx=None, leaf=0.01, capacity=1 << 22, colour=False):
+        """colour=True (dvo_hip_map_create_ex, DVO_HIP_MAP_COLOUR): the map fuses the colour its pyramids carry
+        (RgbdImagePyramid.set_colour) per voxel; every pyramid it is given must then carry colour."""
+        if not isinstance(colour, (bool, np.bool_)):
+            raise TypeError("KeyframeMap: colour must be a bool")
         leaf = float(leaf)
         if not (leaf > 0.0 and leaf < float("inf")):
             raise ValueError("KeyframeMap: the leaf size must be finite and > 0")
@@ -761,8 +853,18 @@ class KeyframeMap:
             raise ValueError("KeyframeMap: capacity must be positive")
         self.ctx = ctx or default_context()
         self.leaf = leaf
+        self.coloured = bool(colour)
         self.ptr = C.c_void_p()
-        self.ctx.check(self.ctx._lib.dvo_hip_map_create(self.ctx.ptr, leaf, int(capacity), C.byref(self.ptr)))
+        if self.coloured:
+            self.ctx.check(self.ctx._lib.dvo_hip_map_create_ex(self.ctx.ptr, leaf, int(capacity), _lib.MAP_COLOUR, C.byref(self.ptr)))
+        else:
+            self.ctx.check(self.ctx._lib.dvo_hip_map_create(self.ctx.ptr, leaf, int(capacity), C.byref(self.ptr)))
+
+    def _check_colour_of(self, pyramids, who):
+        if getattr(self, "coloured", False):
+            for p in pyramids:
+                if getattr(p, "_colour", None) is None:
+                    raise ValueError("%s: a coloured map takes pyramids that carry colour (set_colour)" % who)
 
     def insert(self, pyramids, poses, level=0, min_depth=0.0, max_depth=float("inf")):
         """Every usable point of `level` of the pyramids under their 4 x 4 poses (camera -> world).  Raises DvoHipError with code
@@ -770,6 +872,7 @@ class KeyframeMap:
         n, T = _map_frames_args(pyramids, poses, level, min_depth, max_depth, "KeyframeMap.insert")
         if pyramids[0].ctx is not self.ctx:
             raise ValueError("KeyframeMap.insert: the pyramids belong to another context than the map")
+        self._check_colour_of(pyramids, "KeyframeMap.insert")
         self.ctx.check(self.ctx._lib.dvo_hip_map_insert(self.ctx.ptr, self.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)),
                                                         int(level), float(min_depth), float(max_depth)))
 
@@ -780,6 +883,7 @@ class KeyframeMap:
         n, T = _map_frames_args(pyramids, poses, level, min_depth, max_depth, "KeyframeMap.remove")
         if pyramids[0].ctx is not self.ctx:
             raise ValueError("KeyframeMap.remove: the pyramids belong to another context than the map")
+        self._check_colour_of(pyramids, "KeyframeMap.remove")
         self.ctx.check(self.ctx._lib.dvo_hip_map_remove(self.ctx.ptr, self.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)),
                                                         int(level), float(min_depth), float(max_depth)))
 
@@ -790,6 +894,7 @@ class KeyframeMap:
         T_new = _map_frames_args(pyramids, poses_new, level, min_depth, max_depth, "KeyframeMap.move")[1]
         if pyramids[0].ctx is not self.ctx:
             raise ValueError("KeyframeMap.move: the pyramids belong to another context than the map")
+        self._check_colour_of(pyramids, "KeyframeMap.move")
         dp = C.POINTER(C.c_double)
         self.ctx.check(self.ctx._lib.dvo_hip_map_move(self.ctx.ptr, self.ptr, n, _handles(pyramids), T_old.ctypes.data_as(dp), T_new.ctypes.data_as(dp),
                                                       int(level), float(min_depth), float(max_depth)))
@@ -809,9 +914,12 @@ class KeyframeMap:
         self.ctx.check(self.ctx._lib.dvo_hip_map_stats(self.ctx.ptr, self.ptr, C.byref(s)))
         return {name: int(getattr(s, name)) for name, _ in _lib.MapStats._fields_ if name != "reserved"}
 
-    def extract(self, sort=False, device=False, max_points=None):
+    def extract(self, sort=False, device=False, max_points=None, colour=False):
         """(xyzi [n, 4] float32, counts [n] uint32, keys [n] uint64): one record per occupied voxel, in no particular order unless
-        sort=True (by key, on the host).  device=True: torch tensors on the GPU (counts as int32, keys as int64: the same bits)."""
+        sort=True (by key, on the host).  device=True: torch tensors on the GPU (counts as int32, keys as int64: the same bits).
+        colour=True (a coloured map only): a fourth array rgba [n] uint32, 0xFFRRGGBB per voxel (device=True: int32, the same bits)."""
+        if colour and not getattr(self, "coloured", False):
+            raise ValueError("KeyframeMap.extract: the map holds no colour (KeyframeMap(colour=True))")
         if sort and device:
             raise ValueError("KeyframeMap.extract: sort=True orders on the host; extract to the host, or sort the device tensors by key")
         cap = self.stats()["occupied"] if max_points is None else int(max_points)
@@ -822,16 +930,26 @@ class KeyframeMap:
             xyzi = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
             counts = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
             keys = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
-            ptrs = (xyzi.data_ptr(), counts.data_ptr(), keys.data_ptr())
+            rgba = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if colour else None
+            ptrs = (xyzi.data_ptr(), counts.data_ptr(), keys.data_ptr(), rgba.data_ptr() if colour else None)
         else:
             xyzi, counts, keys = np.empty((max(cap, 1), 4), np.float32), np.empty(max(cap, 1), np.uint32), np.empty(max(cap, 1), np.uint64)
-            ptrs = (xyzi.ctypes.data, counts.ctypes.data, keys.ctypes.data)
-        self.ctx.check(self.ctx._lib.dvo_hip_map_extract(self.ctx.ptr, self.ptr, cap, ptrs[0], ptrs[1], ptrs[2], 1 if device else 0, C.byref(got)))
+            rgba = np.empty(max(cap, 1), np.uint32) if colour else None
+            ptrs = (xyzi.ctypes.data, counts.ctypes.data, keys.ctypes.data, rgba.ctypes.data if colour else None)
+        if colour:
+            self.ctx.check(self.ctx._lib.dvo_hip_map_extract_colour(self.ctx.ptr, self.ptr, cap, ptrs[0], ptrs[3], ptrs[1], ptrs[2], 1 if device else 0,
+                                                                    C.byref(got)))
+        else:
+            self.ctx.check(self.ctx._lib.dvo_hip_map_extract(self.ctx.ptr, self.ptr, cap, ptrs[0], ptrs[1], ptrs[2], 1 if device else 0, C.byref(got)))
         xyzi, counts, keys = xyzi[:got.value], counts[:got.value], keys[:got.value]
+        if colour:
+            rgba = rgba[:got.value]
         if sort:
             order = np.argsort(keys, kind="stable")
             xyzi, counts, keys = xyzi[order], counts[order], keys[order]
-        return xyzi, counts, keys
+            if colour:
+                rgba = rgba[order]
+        return (xyzi, counts, keys, rgba) if colour else (xyzi, counts, keys)
 
     def render(self, K, width, height, poses, device=False, **params):
         """Views of the map (dvo_hip_map_render): the nearest voxel per pixel of a width x height pinhole camera K = fx, fy, ox, oy at
@@ -854,6 +972,31 @@ class KeyframeMap:
                                                         T.ctypes.data_as(C.POINTER(C.c_double)), C.byref(rp), device_pointer_array(ip),
                                                         device_pointer_array(zp), 1 if device else 0))
         return I, Z
+
+    def render_colour(self, K, width, height, poses, device=False, **params):
+        """Colour views of a coloured map (dvo_hip_map_render_colour): like render(), but returns (rgba, Z): uint32 words 0xFFRRGGBB of
+        shape (n, height, width) -- 0 where nothing was seen -- and the depth planes, bit for bit render()'s.  device=True: torch
+        tensors on the GPU (rgba as int32: the same bits)."""
+        who = "KeyframeMap.render_colour"
+        if not getattr(self, "coloured", False):
+            raise ValueError("%s: the map holds no colour (KeyframeMap(colour=True))" % who)
+        K, width, height, T = _render_view_args(K, width, height, poses, who)
+        rp = render_params_struct(**params)
+        n = T.shape[0]
+        if device:
+            import torch
+            dev = "cuda:%d" % self.ctx.device
+            pad = (width * height + 3) // 4 * 4             # (every view's plane 16-byte aligned: views apart by a multiple of 4 words)
+            rgba = torch.empty(n * pad, dtype=torch.int32, device=dev).as_strided((n, height, width), (pad, width, 1))
+            Z = torch.empty(n * pad, dtype=torch.float32, device=dev).as_strided((n, height, width), (pad, width, 1))
+            cp, zp = ([t[k].data_ptr() for k in range(n)] for t in (rgba, Z))
+        else:
+            rgba, Z = np.empty((n, height, width), np.uint32), np.empty((n, height, width), np.float32)
+            cp, zp = ([a[k].ctypes.data for k in range(n)] for a in (rgba, Z))
+        self.ctx.check(self.ctx._lib.dvo_hip_map_render_colour(self.ctx.ptr, self.ptr, n, width, height, K.ctypes.data_as(C.POINTER(C.c_float)),
+                                                               T.ctypes.data_as(C.POINTER(C.c_double)), C.byref(rp), device_pointer_array(cp),
+                                                               device_pointer_array(zp), 1 if device else 0))
+        return rgba, Z
 
     def render_into(self, pyramids, poses, role=None, config=None, flags=0, **params):
         """Views of the map straight into existing pyramids of one camera (dvo_hip_map_render_frames): pyramid i becomes the frame that the

@@ -181,9 +181,13 @@ inline float* pointcloud_ptr(PointCloud& p) { return p.d.data(); }
 struct IntensityPointCloud {
   typedef shared_ptr<IntensityPointCloud> Ptr;
   std::vector<float> x, y, z, intensity;
+  // PointXYZRGB::rgba per point, 0xFFRRGGBB -- filled only by a coloured source (PointCloudAggregator::setColour, a BuildJob over a
+  // pyramid that carries colour), else EMPTY
+  std::vector<uint32_t> rgba;
   size_t width, height;
   IntensityPointCloud() : width(0), height(1) {}
   size_t size() const { return x.size(); }
+  bool hasColour() const { return !x.empty() && rgba.size() == x.size(); }
   void resize(size_t n) { x.resize(n); y.resize(n); z.resize(n); intensity.resize(n); }
   // (PCL's default point: the origin)
   void push_back_default() { x.push_back(0.0f); y.push_back(0.0f); z.push_back(0.0f); intensity.push_back(0.0f); width = x.size(); height = 1; }
@@ -199,6 +203,9 @@ inline ImageMat image_create(int rows, int cols) { return ImageMat(rows, cols, C
 inline float* image_ptr_mut(ImageMat& m) { return m.ptr<float>(); }
 inline bool image_empty(const ImageMat& m) { return m.total() == 0; }
 inline const uint16_t* image_ptr_u16(const ImageMat& m) { return m.ptr<uint16_t>(); }
+inline int image_channels(const ImageMat& m) { return m.channels(); }
+inline bool image_is_float3(const ImageMat& m) { return m.type() == CV_32FC3 && m.isContinuous(); }
+inline ImageMat image_create3(int rows, int cols) { return ImageMat(rows, cols, CV_32FC3); }   // level(0).rgb: float B, G, R per pixel
 typedef cv::Vec<float, 8> Vec8f;
 typedef cv::Mat_<Vec8f> AccelerationMat;                                        // rgbd_image.h:175-176
 inline void acceleration_fill(AccelerationMat& a, int rows, int cols, const ImageMat* const planes[6]) {
@@ -215,10 +222,13 @@ inline void acceleration_fill(AccelerationMat& a, int rows, int cols, const Imag
 // single-channel float image with shared storage (cv::Mat_<float> stand-in)
 struct ImageMat {
   int rows, cols;
+  int chans;   // floats per pixel: 1, or 3 for level(0).rgb (CV_32FC3)
   std::shared_ptr<std::vector<float> > buf;
-  ImageMat() : rows(0), cols(0) {}
-  ImageMat(int r, int c) : rows(r), cols(c), buf(new std::vector<float>(size_t(r) * c)) {}
-  ImageMat(int r, int c, const float* src) : rows(r), cols(c), buf(new std::vector<float>(src, src + size_t(r) * c)) {}
+  ImageMat() : rows(0), cols(0), chans(1) {}
+  ImageMat(int r, int c) : rows(r), cols(c), chans(1), buf(new std::vector<float>(size_t(r) * c)) {}
+  ImageMat(int r, int c, const float* src) : rows(r), cols(c), chans(1), buf(new std::vector<float>(src, src + size_t(r) * c)) {}
+  ImageMat(int r, int c, int channels, int) : rows(r), cols(c), chans(channels), buf(new std::vector<float>(size_t(r) * c * channels)) {}
+  int channels() const { return chans; }
   bool empty() const { return rows == 0 || cols == 0; }
   size_t total() const { return size_t(rows) * cols; }
   template <typename T> T* ptr() { return reinterpret_cast<T*>(buf->data()); }
@@ -233,6 +243,9 @@ inline ImageMat image_create(int rows, int cols) { return ImageMat(rows, cols); 
 inline float* image_ptr_mut(ImageMat& m) { return m.ptr<float>(); }
 inline bool image_empty(const ImageMat& m) { return m.empty(); }
 inline const uint16_t* image_ptr_u16(const ImageMat& m) { return m.ptr<uint16_t>(); }   // (a 16-bit plane stored two per float slot)
+inline int image_channels(const ImageMat& m) { return m.chans; }
+inline bool image_is_float3(const ImageMat& m) { return m.chans == 3; }
+inline ImageMat image_create3(int rows, int cols) { return ImageMat(rows, cols, 3, 0); }   // level(0).rgb: float B, G, R per pixel
 struct Vec8f { float val[8]; };
 struct AccelerationMat {
   int rows, cols;

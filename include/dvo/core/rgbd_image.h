@@ -76,6 +76,12 @@ class DeviceContext {
     dvo_hip_context* previous_;
   };
   static void setErrorHandler(ErrorHandler h) { handler() = h; }
+  // something the caller should know that is no failure (PointCloudAggregator falling back to a grey map): to the handler if there is
+  // one, else to stderr; never aborts
+  static void warn(const char* what, const char* message) {
+    if (handler()) handler()(what, message);
+    else std::fprintf(stderr, "dvo (MI355X engine): %s: %s\n", what, message ? message : "?");
+  }
   static void fail(const char* what, const char* message) {
     if (handler()) {
       handler()(what, message);
@@ -428,6 +434,38 @@ class RgbdImagePyramid {
     has_rig_ = false;
   }
   bool hasDepthRig() const { return has_rig_; }
+  // ---- the colour of this frame (include/dvo_hip.h, dvo_hip_frames_set_colour; the reference keeps the camera image in level(0).rgb,
+  // dvo_benchmark/src/benchmark_slam.cpp:89-90, and AsyncPointCloudBuilder reads it, async_point_cloud_builder.cpp:72-104).  setColour:
+  // an 8-bit plane of the frame's level-0 size, rows `pitch` bytes apart (0 = tight), format DVO_HIP_PIXEL_{BGR8, RGB8, BGRA8, RGBA8};
+  // copied at once.  What a coloured PointCloudAggregator fuses.  Kept until replaced or cleared, across update(): re-attach after an
+  // update() with other content.  Returns false where the engine refuses (a pyramid with a lens: its colour must be attached rectified).
+  bool setColour(const uint8_t* bgr, size_t pitch = 0, int format = DVO_HIP_PIXEL_BGR8) {
+    dvo_hip_frame* one[1] = {device_frame()};
+    const void* planes[1] = {bgr};
+    if (!dvo_hip_check(ctx_, dvo_hip_frames_set_colour(ctx_, 1, one, planes, format, pitch, 0), "dvo_hip_frames_set_colour")) return false;
+    has_colour_ = true;
+    return true;
+  }
+  // ... from level(0).rgb where it is a three-channel float image (hasRgb()): converted on the host the way the reference's
+  // p.b = intensity_ptr[0], p.g = ..[1], p.r = ..[2] does -- channel order B, G, R, each float truncated to uint8 and saturated (a NaN
+  // gives 0).  False if level 0 has no such image.
+  bool setColourFromRgb() {
+    RgbdImage& l0 = level(0);
+    const int w = int(camera_.level(0).width()), h = int(camera_.level(0).height());
+    if (!l0.hasRgb() || dvo::compat::image_channels(l0.rgb) != 3 || !dvo::compat::image_is_float3(l0.rgb) ||
+        dvo::compat::image_rows(l0.rgb) != h || dvo::compat::image_cols(l0.rgb) != w)
+      return false;
+    const float* src = dvo::compat::image_ptr(l0.rgb);
+    std::vector<uint8_t> bgr(size_t(w) * h * 3);
+    for (size_t i = 0; i < bgr.size(); ++i) bgr[i] = src[i] >= 255.0f ? uint8_t(255) : src[i] >= 0.0f ? uint8_t(src[i]) : uint8_t(0);
+    return setColour(bgr.data(), 0, DVO_HIP_PIXEL_BGR8);
+  }
+  void clearColour() {
+    dvo_hip_frame* one[1] = {device_frame()};
+    dvo_hip_check(ctx_, dvo_hip_frames_clear_colour(ctx_, 1, one), "dvo_hip_frames_clear_colour");
+    has_colour_ = false;
+  }
+  bool hasColour() const { return has_colour_; }
   // the caller selection's verdict on a point of level `level` (host side: PointSelection with a caller-defined predicate)
   bool selectionKeeps(size_t level, size_t x, size_t y, float z) const {
     if (has_selection_mask_ && selection_mask_[(y << level) * size_t(camera_.level(0).width()) + (x << level)] == 0) return false;
@@ -469,6 +507,7 @@ class RgbdImagePyramid {
   bool has_selection_mask_ = false;
   bool has_lens_ = false;
   bool has_rig_ = false;
+  bool has_colour_ = false;
   float selection_min_ = 0.0f, selection_max_ = INFINITY;
   unsigned explicit_levels_ = 0u;
 };

@@ -3,7 +3,8 @@
 // dvo_core/src/visualization/async_point_cloud_builder.cpp:61-110): BuildJob(image, pose).build() returns pose.cast<float>() * pointcloud
 // plus intensity for every pixel of the image -- the ORGANISED cloud of level 0, NaN in x, y, z where the pixel has no usable depth
 // (include/dvo_hip.h, dvo_hip_frames_world_points).  There is no PCL here: the cloud is dvo::compat::IntensityPointCloud, and the job
-// holds the device pyramid instead of a host image.
+// holds the device pyramid instead of a host image.  Where the pyramid carries colour (RgbdImagePyramid::setColour; the reference's
+// hasRgb() branch, async_point_cloud_builder.cpp:72-104) the cloud's rgba is filled with the level-0 colour of every pixel, 0xFFRRGGBB.
 #pragma once
 
 #include <vector>
@@ -44,6 +45,15 @@ class AsyncPointCloudBuilder {
         cloud->y[i] = xyzi[4 * i + 1];
         cloud->z[i] = xyzi[4 * i + 2];
         cloud->intensity[i] = xyzi[4 * i + 3];
+      }
+      if (image.hasColour()) {
+        cloud->rgba.resize(cloud->size());
+        if (!dvo::core::dvo_hip_check(image.device_context(), dvo_hip_frame_download_colour(image.device_context(), one[0], 0, cloud->rgba.data()),
+                                      "dvo_hip_frame_download_colour")) {
+          cloud->rgba.clear();
+          return cloud;
+        }
+        for (size_t i = 0; i < cloud->size(); ++i) cloud->rgba[i] |= 0xFF000000u;   // (the frame's packed pixels have A = 0)
       }
       return cloud;
     }

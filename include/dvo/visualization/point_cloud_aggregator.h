@@ -15,6 +15,10 @@
 // registered pyramid must keep its content while it is in the map (update() it only after remove(), or add() it again afterwards).
 // Also not in the reference: render() and renderInto() give the map built last as a model view -- an RgbdImagePyramid seen from a pose
 // (include/dvo_hip.h, dvo_hip_map_render / dvo_hip_map_render_frames) -- that a DenseTracker can align a new frame against.
+// setColour(true) makes the map a COLOURED one, as the reference's is (it voxel-filters PointXYZRGB clouds): build() attaches level(0).rgb
+// of every registered pyramid that hasRgb() and does not carry colour yet (RgbdImagePyramid::setColourFromRgb), creates the device map
+// with DVO_HIP_MAP_COLOUR and fills the cloud's rgba (0xFFRRGGBB per voxel, include/dvo_hip.h, dvo_hip_map_extract_colour).  If some
+// registered pyramid has neither colour nor rgb, the build falls back to the grey map and says so (DeviceContext::warn); rgba stays empty.
 #pragma once
 
 #include <algorithm>
@@ -33,7 +37,7 @@ class PointCloudAggregator {
   typedef AsyncPointCloudBuilder::PointCloud PointCloud;
 
   // capacity_slots: the device table (32 bytes per slot); keep it at least four times the voxels of the map
-  explicit PointCloudAggregator(size_t capacity_slots = size_t(1) << 22) : capacity_(capacity_slots), ctx_(0), map_(0), incremental_(false) {}
+  explicit PointCloudAggregator(size_t capacity_slots = size_t(1) << 22) : capacity_(capacity_slots), ctx_(0), map_(0), incremental_(false), colour_(false), map_coloured_(false) {}
   ~PointCloudAggregator() {
     if (map_) dvo_hip_map_destroy(ctx_, map_);
   }
@@ -52,12 +56,21 @@ class PointCloudAggregator {
     if (!on) held_.clear();
   }
   bool incremental() const { return incremental_; }
+  // off (the default): a grey map.  on: build() fuses the pyramids' colour (see above)
+  void setColour(bool on) { colour_ = on; }
+  bool colour() const { return colour_; }
 
   PointCloud::Ptr build() {
     PointCloud::Ptr cloud(new PointCloud);
     if (clouds_.empty()) {
       cloud->push_back_default();
       return cloud;
+    }
+    const bool coloured = colour_ && attachColour();
+    if (map_ && coloured != map_coloured_) {   // (a map is grey or coloured for life: the other kind is made anew)
+      dvo_hip_map_destroy(ctx_, map_);
+      map_ = 0;
+      held_.clear();
     }
     if (incremental_ && clouds_.size() / size_t(50) <= size_t(1)) {
       dvo_hip_context* now = clouds_.begin()->second.pyramid->device_context();
@@ -82,7 +95,10 @@ class PointCloudAggregator {
     }
     ctx_ = ctx;
     using dvo::core::dvo_hip_check;
-    if (!map_ && !dvo_hip_check(ctx_, dvo_hip_map_create(ctx_, 0.01f, capacity_, &map_), "dvo_hip_map_create")) return cloud;
+    if (!map_) {
+      if (!dvo_hip_check(ctx_, dvo_hip_map_create_ex(ctx_, 0.01f, capacity_, coloured ? DVO_HIP_MAP_COLOUR : 0u, &map_), "dvo_hip_map_create_ex")) return cloud;
+      map_coloured_ = coloured;
+    }
     if (!dvo_hip_check(ctx_, dvo_hip_map_clear(ctx_, map_), "dvo_hip_map_clear")) return cloud;
     if (!dvo_hip_check(ctx_, dvo_hip_map_insert(ctx_, map_, int(frames.size()), frames.data(), poses.data(), 0, 0.0f, INFINITY), "dvo_hip_map_insert"))
       return cloud;
@@ -129,6 +145,19 @@ class PointCloudAggregator {
   PointCloudAggregator(const PointCloudAggregator&);
   PointCloudAggregator& operator=(const PointCloudAggregator&);
 
+  // every registered pyramid carries colour, attached now from level(0).rgb where it did not; false (and a warning): one has neither
+  bool attachColour() {
+    for (std::map<std::string, Entry>::iterator it = clouds_.begin(); it != clouds_.end(); ++it) {
+      dvo::core::RgbdImagePyramid& p = *it->second.pyramid;
+      if (p.hasColour()) continue;
+      if (!p.level(0).hasRgb() || !p.setColourFromRgb()) {
+        dvo::core::DeviceContext::warn("PointCloudAggregator::build", ("keyframe " + it->first + " has no rgb: the map is built grey").c_str());
+        return false;
+      }
+    }
+    return true;
+  }
+
   // the map's live voxels into `cloud`, sorted by key
   PointCloud::Ptr extract(PointCloud::Ptr cloud) {
     using dvo::core::dvo_hip_check;
@@ -137,12 +166,19 @@ class PointCloudAggregator {
     const size_t n = size_t(stats.occupied - stats.vacant);
     std::vector<float> xyzi(4 * std::max(n, size_t(1)));
     std::vector<uint64_t> keys(std::max(n, size_t(1)));
+    std::vector<uint32_t> rgba(map_coloured_ ? std::max(n, size_t(1)) : size_t(0));
     size_t got = 0;
-    if (!dvo_hip_check(ctx_, dvo_hip_map_extract(ctx_, map_, n, xyzi.data(), 0, keys.data(), 0, &got), "dvo_hip_map_extract")) return cloud;
+    if (map_coloured_) {
+      if (!dvo_hip_check(ctx_, dvo_hip_map_extract_colour(ctx_, map_, n, xyzi.data(), rgba.data(), 0, keys.data(), 0, &got), "dvo_hip_map_extract_colour"))
+        return cloud;
+    } else if (!dvo_hip_check(ctx_, dvo_hip_map_extract(ctx_, map_, n, xyzi.data(), 0, keys.data(), 0, &got), "dvo_hip_map_extract")) {
+      return cloud;
+    }
     std::vector<size_t> order(got);
     std::iota(order.begin(), order.end(), size_t(0));
     std::sort(order.begin(), order.end(), [&keys](size_t a, size_t b) { return keys[a] < keys[b]; });
     cloud->resize(got);
+    cloud->rgba.resize(map_coloured_ ? got : size_t(0));
     cloud->width = got;
     cloud->height = 1;
     for (size_t i = 0; i < got; ++i) {
@@ -151,6 +187,7 @@ class PointCloudAggregator {
       cloud->y[i] = p[1];
       cloud->z[i] = p[2];
       cloud->intensity[i] = p[3];
+      if (map_coloured_) cloud->rgba[i] = rgba[order[i]];
     }
     return cloud;
   }
@@ -202,6 +239,8 @@ class PointCloudAggregator {
   dvo_hip_context* ctx_;
   dvo_hip_map* map_;
   bool incremental_;
+  bool colour_;          // setColour
+  bool map_coloured_;    // what map_ was created as
 };
 
 }  // namespace visualization

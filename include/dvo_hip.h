@@ -619,6 +619,57 @@ int dvo_hip_map_render_frames(dvo_hip_context* ctx, dvo_hip_map* map, int n_fram
 int dvo_hip_time_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float K[4],
                             const double* poses /* n x 16 */, const dvo_hip_render_params* params, int reps, float ms[3]);
 
+/* ---- colour in the keyframe map: frames keep RGB, voxels fuse it -------------------------------------------------------------------------
+ * The reference's map is coloured: dvo_benchmark/src/benchmark_slam.cpp:89-90 keeps the camera image in level(0).rgb,
+ * AsyncPointCloudBuilder::BuildJob::build (dvo_core/src/visualization/async_point_cloud_builder.cpp:72-104) writes p.b, p.g, p.r from it
+ * whenever hasRgb(), and PointCloudAggregator::build voxel-filters PointXYZRGB clouds.  Here a frame may CARRY colour beside what it was
+ * ingested from, a map created with DVO_HIP_MAP_COLOUR fuses it per voxel, and the extraction and the views return it.  Tracking stays on
+ * intensity; a grey map, and every entry point above, behaves as it did.  All of it is integer arithmetic, stated once in
+ * dvo_slam_amd/csrc/cloud_colour.h, whose host build the device results equal BIT FOR BIT.
+ *   packed pixel  a uint32 0x00RRGGBB (PCL's PointXYZRGB::rgba layout with A = 0), from BGR8 / RGB8 / BGRA8 / RGBA8 bytes; alpha is ignored.
+ *   frame colour  dvo_hip_frames_set_colour packs n planes in one launch into frame-owned planes of level-0 size.  The colour is a frame
+ *                 PROPERTY like a lens or a selection: it stays until replaced or cleared, and a re-ingest does NOT touch it -- a caller
+ *                 that re-ingests other content into the frame re-attaches the colour that belongs to it.  The colour of level L at (u, v)
+ *                 is, per channel, the rounded mean of the 2^L x 2^L block of level 0 at (u << L, v << L):
+ *                 (sum + (1 << (2 L - 1))) >> 2 L; level sizes are w0 >> L, so every block lies inside level 0.
+ *                 dvo_hip_frame_download_colour returns that plane, exactly as an insertion sees it.
+ *   sums          a coloured map has a side table beside its slots (16 more bytes per slot): per voxel the sums of the three 8-bit
+ *                 channels of its points, uint32 each (255 * 2^20 < 2^28: nothing wraps up to the 2^20-point limit).  Insert, remove,
+ *                 move and rehash carry them like the other sums: integer adds, a removal subtracts exactly what the insertion added.
+ *   extraction    per channel c = (2 s + n) / (2 n) in unsigned 64-bit integer division (the mean, rounded half up), clamped to 255; the
+ *                 record is 0xFF000000 | r << 16 | g << 8 | b, at the index of the voxel's xyzi record.
+ *   views         the z-buffer element is uint64(bits(p.z)) << 32 | r << 16 | g << 8 | b: the nearest voxel, and of voxels at the same
+ *                 depth the one with the LOWER packed colour.  The depth plane equals dvo_hip_map_render's bit for bit.  A hole is
+ *                 Z = NaN (0x7FC00000) and colour word 0; a covered pixel has A = 0xFF.
+ *   streams       like the map calls: the main stream, behind earlier work, recorded ingests first.  dvo_hip_frames_set_colour returns
+ *                 when the caller's planes, host or device, may be reused.
+ *   refusals      DVO_HIP_ERR_INVALID, nothing launched, nothing changed: an unknown pixel format, a null entry, 0 < colour_pitch <
+ *                 width * channels, a frame of another context, the same frame twice in a call, and a frame that carries a LENS -- such a
+ *                 frame takes raw sensor planes, so its colour would have to be rectified first (a depth rig is fine: depth is
+ *                 registered INTO the colour camera); dvo_hip_frame_download_colour of a frame without colour or at a level it lacks;
+ *                 dvo_hip_map_insert / _remove / _move of a frame without colour into a COLOURED map (a grey map ignores attached
+ *                 colour); dvo_hip_map_extract_colour and dvo_hip_map_render_colour on a grey map; an unknown flag.
+ *   cost          profiles/keyframe_map_colour.md. */
+/* colour: n planes of frame i's level-0 size, pixel_format one of DVO_HIP_PIXEL_{BGR8, RGB8, BGRA8, RGBA8}, rows colour_pitch bytes
+ * apart (0 = tight); host memory, or device memory with on_device. */
+int dvo_hip_frames_set_colour(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour, int pixel_format,
+                              size_t colour_pitch, int on_device);
+int dvo_hip_frames_clear_colour(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames);
+/* the colour plane of `level` as packed pixels into out (host, w_L * h_L words, tight) */
+int dvo_hip_frame_download_colour(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, uint32_t* out);
+#define DVO_HIP_MAP_COLOUR 1u /* dvo_hip_map_create_ex: the map fuses colour */
+/* dvo_hip_map_create with flags: 0 is dvo_hip_map_create itself; DVO_HIP_MAP_COLOUR adds the side table (48 bytes per slot in all) */
+int dvo_hip_map_create_ex(dvo_hip_context* ctx, float leaf, size_t capacity_slots, unsigned flags, dvo_hip_map** out);
+/* dvo_hip_map_extract of a coloured map with the colour records into rgba (max_points words; host, or device with out_on_device).
+ * dvo_hip_map_extract itself returns of a coloured map what it returns of a grey one fed the same frames. */
+int dvo_hip_map_extract_colour(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_points, float* xyzi, uint32_t* rgba, uint32_t* counts_or_null,
+                               uint64_t* keys_or_null, int out_on_device, size_t* n_points);
+/* dvo_hip_map_render of a coloured map: the colour words into rgba_out[i], Z into depth_out[i], width * height elements each, tight; host
+ * arrays, or device arrays (16-byte aligned) with out_on_device.  View preparation, footprint, parameters and refusals are the grey view's. */
+int dvo_hip_map_render_colour(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float K[4],
+                              const double* poses /* n x 16 */, const dvo_hip_render_params* params, uint32_t* const* rgba_out,
+                              float* const* depth_out, int out_on_device);
+
 /* ---- the hot path --------------------------------------------------------------------------- */
 /* DenseTracker::match(RgbdImagePyramid& reference, RgbdImagePyramid& current, Result&)
  * (dvo_core/src/dense_tracking.cpp:123-376).  `levels`/`iters` may be NULL (no statistics).
