@@ -446,6 +446,258 @@ int dvo_hip_map_extract_colour(dvo_hip_context* ctx, dvo_hip_map* map, size_t ma
   return map_extract(ctx, map, max_points, xyzi, true, rgba, counts_or_null, keys_or_null, out_on_device, n_points, "map_extract_colour");
 }
 
+// ---- sub-maps: voxel tables and raw voxel records into and out of a map (cloud_map.h, Merge; kernels: map_merge.hip) ----
+
+namespace {
+
+// one source of a merge: a table or a record array in device memory, its leaf, and how it enters
+struct MergeSource {
+  const MapSlot* slots;
+  const MapColourSlot* colour;
+  unsigned long long count;
+  float leaf;
+  int sign;
+  MapPose pose;
+  const dvo_hip_map* map;              // the map the records are the table of: a PLAIN merge carries its out-of-range and unusable counts along; else null
+};
+
+bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; }
+
+bool pose_finite(const double* T16) {
+  for (int k = 0; k < 16; ++k)
+    if (!std::isfinite(T16[k])) return false;
+  return true;
+}
+
+// what every merge checks of one source once its pointers are known to be good: the sign, the leaf, the pose
+int check_merge_source(dvo_hip_context* ctx, const dvo_hip_map* dst, float leaf_src, int sign, const double* pose_or_null, const char* who) {
+  if (sign != 1 && sign != -1) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a sign is +1 or -1");
+  if (!(leaf_src > 0.0f && leaf_src < INFINITY)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the source's leaf size must be finite and > 0");
+  if (!pose_or_null && !same_bits(leaf_src, dst->leaf))
+    return fail(ctx, DVO_HIP_ERR_INVALID, who, "a plain merge adds voxels as they are: the source's leaf must be the destination's (a posed merge bins anew)");
+  if (pose_or_null && !pose_finite(pose_or_null)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a pose has an entry that is not finite");
+  if (sign < 0 && dst->dropped != 0)
+    return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map has dropped points since its last clear or rehash: what it holds of a sub-map is not known (dvo_hip_map_rehash into a larger table, or dvo_hip_map_clear)");
+  return DVO_HIP_OK;
+}
+
+// a source map of dvo_hip_map_merge / dvo_hip_map_move_submaps
+int check_merge_map(dvo_hip_context* ctx, const dvo_hip_map* dst, const dvo_hip_map* src, const char* who) {
+  if (!src) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null source map");
+  if (src->ctx != ctx) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a source map of another context (dvo_hip_map_export there, dvo_hip_map_merge_records here)");
+  if (src == dst) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a map cannot be merged into itself");
+  if (src->coloured != dst->coloured) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a coloured and a grey map do not merge");
+  return DVO_HIP_OK;
+}
+
+MergeSource merge_source_of(const dvo_hip_map* src, int sign, const double* pose_or_null) {
+  MergeSource s;
+  s.slots = src->slots.as<MapSlot>();
+  s.colour = src->coloured ? src->colour.as<MapColourSlot>() : nullptr;
+  s.count = src->capacity;
+  s.leaf = src->leaf;
+  s.sign = sign;
+  std::memset(&s.pose, 0, sizeof s.pose);
+  if (pose_or_null) s.pose = map_pose_prepare(pose_or_null);
+  s.map = pose_or_null ? nullptr : src;
+  return s;
+}
+
+// One launch of k_map_merge over checked sources (all posed or all plain) on the main stream, then the read-back of the counters.
+int run_map_merge(dvo_hip_context* ctx, dvo_hip_map* dst, const std::vector<MergeSource>& sources, bool posed, const char* who) {
+  if (sources.empty()) return DVO_HIP_OK;
+  long long blocks = 0;
+  for (const MergeSource& s : sources) blocks += (long long)((s.count + 255) / 256);
+  if (blocks > 0x7fffffffll) return fail(ctx, DVO_HIP_ERR_INVALID, who, "too many records for one call");
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // the counts a plain merge carries along from its source maps
+  std::vector<unsigned long long> theirs(sources.size() * size_t(kMapCounters), 0ull);
+  bool any = false;
+  for (size_t i = 0; i < sources.size(); ++i)
+    if (sources[i].map) {
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(&theirs[i * kMapCounters], sources[i].map->counters.p, sizeof(unsigned long long) * kMapCounters,
+                                      hipMemcpyDeviceToHost, ctx->stream));
+      any = true;
+    }
+  if (any) DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<MapMergeEntry> host(sources.size() + 1);
+  std::memset(host.data(), 0, host.size() * sizeof(MapMergeEntry));
+  int at = 0;
+  for (size_t i = 0; i < sources.size(); ++i) {
+    const MergeSource& s = sources[i];
+    MapMergeEntry& e = host[i];
+    e.slots = s.slots;
+    e.colour = dst->coloured ? s.colour : nullptr;
+    e.count = s.count;
+    const unsigned long long oor = theirs[i * kMapCounters + kMapCntOutOfRange], unusable = theirs[i * kMapCounters + kMapCntUnusable];
+    e.out_of_range = s.sign < 0 ? 0ull - oor : oor;
+    e.unusable = s.sign < 0 ? 0ull - unusable : unusable;
+    e.pose = s.pose;
+    e.leaf_src = s.leaf;
+    e.sign = s.sign;
+    e.first_block = at;
+    at += int((s.count + 255) / 256);
+  }
+  host[sources.size()].first_block = at;
+  const size_t bytes = host.size() * sizeof(MapMergeEntry);
+  DVO_HIP_TRY(ctx, ctx->map_tbl.reserve(bytes));
+  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->map_tbl.p, host.data(), bytes));
+  const unsigned long long candidates_before = dst->candidates, dropped_before = dst->dropped, unmatched_before = dst->unmatched;
+  launch_map_merge(ctx->stream, ctx->map_tbl.as<MapMergeEntry>(), int(sources.size()), at, map_table(dst), posed);
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  unsigned long long after[kMapCounters];
+  const int rc = read_map_counters(ctx, dst, after);
+  if (rc != DVO_HIP_OK) return rc;
+  const unsigned long long dropped = after[kMapCntDropped] - dropped_before, unmatched = after[kMapCntUnmatched] - unmatched_before;
+  ctx->map_points += (long long)(after[kMapCntCandidates] - candidates_before - dropped);
+  ctx->map_dropped += (long long)dropped;
+  if (dropped != 0) return fail(ctx, DVO_HIP_ERR_CAPACITY, who, "the table dropped points (no free slot within the probe bound); the map keeps what it took");
+  if (unmatched != 0) {
+    ctx->err = std::string(who) + ": " + std::to_string(unmatched) +
+               " points found no voxel to leave (not the sub-map, or not the pose, that was merged?); the map keeps what it did";
+    return DVO_HIP_ERR_INVALID;
+  }
+  return DVO_HIP_OK;
+}
+
+}  // namespace
+static_assert(sizeof(MapSlot) == 32 && sizeof(MapColourSlot) == 16, "a voxel record is 32 bytes, its colour record 16 (include/dvo_hip.h)");
+
+int dvo_hip_map_info(dvo_hip_context* ctx, dvo_hip_map* map, float* leaf, unsigned* flags, uint64_t* capacity) {
+  DVO_LOCK(ctx);
+  const int rc = check_map(ctx, map, "map_info");
+  if (rc != DVO_HIP_OK) return rc;
+  if (leaf) *leaf = map->leaf;
+  if (flags) *flags = map->coloured ? DVO_HIP_MAP_COLOUR : 0u;
+  if (capacity) *capacity = map->capacity;
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_map_merge(dvo_hip_context* ctx, dvo_hip_map* dst, int n_src, dvo_hip_map* const* src, const int* signs_or_null, const double* poses_or_null) {
+  DVO_LOCK(ctx);
+  const char* who = "map_merge";
+  int rc = check_map(ctx, dst, who);
+  if (rc != DVO_HIP_OK) return rc;
+  if (n_src < 0 || (n_src > 0 && !src)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  std::vector<MergeSource> sources;
+  for (int i = 0; i < n_src; ++i) {
+    const double* pose = poses_or_null ? poses_or_null + size_t(i) * 16 : nullptr;
+    const int sign = signs_or_null ? signs_or_null[i] : 1;
+    rc = check_merge_map(ctx, dst, src[i], who);
+    if (rc == DVO_HIP_OK) rc = check_merge_source(ctx, dst, src[i]->leaf, sign, pose, who);
+    if (rc != DVO_HIP_OK) return rc;
+    sources.push_back(merge_source_of(src[i], sign, pose));
+  }
+  return run_map_merge(ctx, dst, sources, poses_or_null != nullptr, who);
+}
+
+int dvo_hip_map_move_submaps(dvo_hip_context* ctx, dvo_hip_map* dst, int n_src, dvo_hip_map* const* src, const double* poses_old,
+                             const double* poses_new) {
+  DVO_LOCK(ctx);
+  const char* who = "map_move_submaps";
+  int rc = check_map(ctx, dst, who);
+  if (rc != DVO_HIP_OK) return rc;
+  if (n_src < 0 || (n_src > 0 && (!src || !poses_old || !poses_new))) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  std::vector<MergeSource> sources;
+  for (int i = 0; i < n_src; ++i) {
+    const double *from = poses_old + size_t(i) * 16, *to = poses_new + size_t(i) * 16;
+    rc = check_merge_map(ctx, dst, src[i], who);
+    if (rc == DVO_HIP_OK) rc = check_merge_source(ctx, dst, src[i]->leaf, -1, from, who);
+    if (rc == DVO_HIP_OK) rc = check_merge_source(ctx, dst, src[i]->leaf, 1, to, who);
+    if (rc != DVO_HIP_OK) return rc;
+    const MergeSource out = merge_source_of(src[i], -1, from), in = merge_source_of(src[i], 1, to);
+    if (std::memcmp(&out.pose, &in.pose, sizeof out.pose) == 0) continue;   // (the same twelve floats: the same records, nothing to do)
+    sources.push_back(out);
+    sources.push_back(in);
+  }
+  return run_map_merge(ctx, dst, sources, true, who);
+}
+
+int dvo_hip_map_export(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_records, void* records, void* colour_records_or_null, int out_on_device,
+                       size_t* n_records) {
+  DVO_LOCK(ctx);
+  const char* who = "map_export";
+  const int rc0 = check_map(ctx, map, who);
+  if (rc0 != DVO_HIP_OK) return rc0;
+  if (!n_records || (max_records > 0 && !records)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  if (colour_records_or_null && !map->coloured) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no colour (dvo_hip_map_create_ex, DVO_HIP_MAP_COLOUR)");
+  if (out_on_device && ((records && !aligned_to(records, 16)) || (colour_records_or_null && !aligned_to(colour_records_or_null, 16))))
+    return fail(ctx, DVO_HIP_ERR_INVALID, who, "device records must be 16-byte aligned");
+  *n_records = 0;
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const MapTable t = map_table(map);
+  unsigned long long c[kMapCounters];
+  // how many there are, then the records: a host destination is staged for just that many
+  DVO_HIP_TRY(ctx, launch_map_export(ctx->stream, t, 0, nullptr, nullptr));
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  const int rc = read_map_counters(ctx, map, c);
+  if (rc != DVO_HIP_OK) return rc;
+  const unsigned long long live = c[kMapCntCursor];
+  if (!records) {                                            // (max_records is 0: the caller asks how many there are)
+    *n_records = size_t(live);
+    return DVO_HIP_OK;
+  }
+  const size_t take = size_t(live < max_records ? live : max_records);
+  if (take > 0) {
+    MapSlot* d_records = static_cast<MapSlot*>(records);
+    MapColourSlot* d_colour = static_cast<MapColourSlot*>(colour_records_or_null);
+    if (!out_on_device) {
+      DVO_HIP_TRY(ctx, ctx->map_stage.reserve(take * (sizeof(MapSlot) + sizeof(MapColourSlot))));
+      d_records = ctx->map_stage.as<MapSlot>();
+      d_colour = colour_records_or_null ? reinterpret_cast<MapColourSlot*>(ctx->map_stage.as<char>() + take * sizeof(MapSlot)) : nullptr;
+    }
+    DVO_HIP_TRY(ctx, launch_map_export(ctx->stream, t, take, d_records, d_colour));
+    DVO_HIP_TRY(ctx, hipGetLastError());
+    if (!out_on_device) {
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(records, d_records, take * sizeof(MapSlot), hipMemcpyDeviceToHost, ctx->stream));
+      if (d_colour) DVO_HIP_TRY(ctx, hipMemcpyAsync(colour_records_or_null, d_colour, take * sizeof(MapColourSlot), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  *n_records = take;
+  if (live > max_records) return fail(ctx, DVO_HIP_ERR_CAPACITY, who, "max_records is smaller than the number of live voxels (dvo_hip_map_stats: occupied - vacant)");
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_map_merge_records(dvo_hip_context* ctx, dvo_hip_map* dst, size_t n_records, const void* records, const void* colour_or_null, int on_device,
+                              float leaf_src, int sign, const double* pose_or_null) {
+  DVO_LOCK(ctx);
+  const char* who = "map_merge_records";
+  int rc = check_map(ctx, dst, who);
+  if (rc != DVO_HIP_OK) return rc;
+  if (n_records > (size_t(1) << 32)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "at most 2^32 records");
+  if (n_records > 0 && !records) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  if (dst->coloured && n_records > 0 && !colour_or_null) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a coloured map takes records with colour records");
+  if (!dst->coloured && colour_or_null) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a grey map takes no colour records");
+  if (on_device && ((records && !aligned_to(records, 16)) || (colour_or_null && !aligned_to(colour_or_null, 16))))
+    return fail(ctx, DVO_HIP_ERR_INVALID, who, "device records must be 16-byte aligned");
+  rc = check_merge_source(ctx, dst, leaf_src, sign, pose_or_null, who);
+  if (rc != DVO_HIP_OK) return rc;
+  if (n_records == 0) return DVO_HIP_OK;
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  MergeSource s;
+  s.slots = static_cast<const MapSlot*>(records);
+  s.colour = static_cast<const MapColourSlot*>(colour_or_null);
+  if (!on_device) {
+    // host records: staged on the main stream, then the same kernel
+    DVO_HIP_TRY(ctx, ctx->map_stage.reserve(n_records * (sizeof(MapSlot) + sizeof(MapColourSlot))));
+    char* stage = ctx->map_stage.as<char>();
+    DVO_HIP_TRY(ctx, hipMemcpyAsync(stage, records, n_records * sizeof(MapSlot), hipMemcpyHostToDevice, ctx->stream));
+    s.slots = reinterpret_cast<const MapSlot*>(stage);
+    if (colour_or_null) {
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(stage + n_records * sizeof(MapSlot), colour_or_null, n_records * sizeof(MapColourSlot), hipMemcpyHostToDevice, ctx->stream));
+      s.colour = reinterpret_cast<const MapColourSlot*>(stage + n_records * sizeof(MapSlot));
+    }
+  }
+  s.count = n_records;
+  s.leaf = leaf_src;
+  s.sign = sign;
+  std::memset(&s.pose, 0, sizeof s.pose);
+  if (pose_or_null) s.pose = map_pose_prepare(pose_or_null);
+  s.map = nullptr;
+  return run_map_merge(ctx, dst, std::vector<MergeSource>(1, s), pose_or_null != nullptr, who);
+}
+
 int dvo_hip_frames_world_points(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float min_depth,
                                 float max_depth, float* const* out, int out_on_device) {
   DVO_ENTER(ctx);

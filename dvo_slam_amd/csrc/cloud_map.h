@@ -3,7 +3,7 @@
 // of the reference's map building -- AsyncPointCloudBuilder::BuildJob::build (dvo_core/src/visualization/async_point_cloud_builder.cpp:61-110:
 // pose.cast<float>() * image.pointcloud, plus intensity) and PointCloudAggregator::build (point_cloud_aggregator.cpp:74-109: concatenate,
 // then a 1 cm voxel grid) -- with an EXACT per-voxel centroid in place of PCL's ApproximateVoxelGrid.  Shared by the kernels
-// (cloud_map.hip: k_world_points, k_map_insert, k_map_rehash, k_map_extract, k_map_clear) and the host compiler of the CPU tier (tests/test_cloud_map.py),
+// (cloud_map.hip: k_world_points, k_map_insert, k_map_rehash, k_map_extract, k_map_clear; map_merge.hip: k_map_merge, k_map_export) and the host compiler of the CPU tier (tests/test_cloud_map.py),
 // which is the yardstick the device results are compared with bit for bit: float32 throughout (the extraction alone is double), compiled
 // without contraction (clang: the pragma below; a host compiler: -ffp-contract=off), division correctly rounded on both sides.  Every
 // product, quotient and sum is rounded on its own, left to right as parenthesised.
@@ -50,6 +50,36 @@
 // its five sums unchanged; vacant slots stay behind.  Live keys are unique in the old table: whoever claims a slot of the new one (one
 // 64-bit CAS, the same probe sequence and bound) is its only writer and stores the sums plainly.  A record that finds no slot is counted,
 // and the new table replaces the old one only if there was none; else the map is unchanged.
+//
+// Merge (dvo_hip_map_merge, dvo_hip_map_move_submaps, dvo_hip_map_export, dvo_hip_map_merge_records; map_merge.hip: k_map_merge, k_map_export).
+// A RECORD is 32 bytes with the layout of MapSlot, {key, n, sx, sy, sz, si, pad}; of a coloured map also the 16 bytes of MapColourSlot
+// (cloud_colour.h) at the same index.  A record with key == kMapEmptyKey or n == 0 is not live and is skipped (map_slot_live): a raw dump
+// of a table is a valid record array, and so is what an export compacts out of one.
+// Plain merge, sign +1.  Source and destination have the same leaf (as bits).  The record's key is probed in the destination exactly as an
+// insertion probes (map_hash, linear, kMapMaxProbes, an empty slot is claimed), and the WHOLE WORDS are added: map_word(n, sx),
+// map_word(sy, sz), si, and of a coloured map colour_word(sr, sg), sb.  That is the arithmetic modulo 2^64 of inserting the record's
+// points one at a time: the sum of two sub-maps is, bit for bit in what an extraction and a render return, the map built from all their
+// keyframes at once -- voxels beyond kMapVoxelMaxPoints included.  A record that finds no slot is DROPPED, by its n points.
+// Plain merge, sign -1.  A lookup that never claims, as in a removal; the two's complement of the same words is added (map_negate).  A
+// record that finds no slot is UNMATCHED by its n points.  Subtracting a sub-map restores the words as a removal of its frames does.
+// Posed merge (map_pose_record).  The source lies in its own coordinates -- those of its anchor keyframe -- and enters under T = [R | t],
+// the row-major 4 x 4 double cast to float once (map_pose_prepare):
+//   1. c[0..2] = the voxel's centroid, map_extract_voxel with the SOURCE's leaf: double, rounded to float once;
+//   2. P = R c + t, each row as ((r0 c0 + r1 c1) + r2 c2) + t in float, every operation rounded on its own (map_pose_point: the shape
+//      of map_world_point);
+//   3. P not finite: the record's n points are UNUSABLE;
+//   4. else map_key_of(P, 0, leaf of the DESTINATION, &key2, q); false: the n points are OUT OF RANGE;
+//   5. else the record added under key2 is {n, n * q[0], n * q[1], n * q[2], si}, the products in uint32 (they wrap like every other
+//      sum: a source voxel beyond kMapVoxelMaxPoints makes the destination voxel one, which n reports); the colour sums go unchanged.
+// The sign -1 form computes the same key2 and addends and subtracts them: a posed subtraction of what was posed-merged under the same
+// float pose restores the destination bit for bit.  The source's leaf may differ from the destination's: the record is binned anew.
+// ACCURACY.  A posed merge treats a source voxel's n points as n copies of their centroid: a point may land up to one source leaf from
+// where a rebuild from the frames would put it, and voxels at the faces of the destination's grid differ from such a rebuild.  The
+// point-weighted mean position is kept to quantisation: per axis within (leaf_src + leaf_dst) / 2048 of the source's, transformed, plus
+// the float rounding of the transform.  This is the sub-map approximation (a LocalMap moves rigidly with its keyframe), not a rebuild.
+// Statistics.  A plus merge adds the n of every live record in range to the usable points, a minus merge to the points being removed;
+// dropped and unmatched count points, not records.  A plain merge from a MAP also adds (sign -1: takes back) the source's out-of-range
+// and unusable counts: the merged map's points, out_of_range, unusable, dropped and over_limit are those of the single build.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -171,6 +201,37 @@ DVO_HD void map_extract_voxel(uint64_t key, uint32_t n, uint32_t sx, uint32_t sy
   out[1] = float((double(iy) + (double(sy) / dn + 0.5) / 1024.0) * dl);
   out[2] = float((double(iz) + (double(sz) / dn + 0.5) / 1024.0) * dl);
   out[3] = float(double(si) / dn / 16.0);
+}
+
+// P = R c + t in float, every operation rounded on its own, each row as ((r0 c0 + r1 c1) + r2 c2) + t (the shape of map_world_point)
+DVO_HD void map_pose_point(const MapPose& p, const float c[3], float P[3]) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  P[0] = ((p.r[0] * c[0] + p.r[1] * c[1]) + p.r[2] * c[2]) + p.t[0];
+  P[1] = ((p.r[3] * c[0] + p.r[4] * c[1]) + p.r[5] * c[2]) + p.t[1];
+  P[2] = ((p.r[6] * c[0] + p.r[7] * c[1]) + p.r[8] * c[2]) + p.t[2];
+}
+
+// what became of a record under a pose (Merge above)
+constexpr int kMapPosePlaced = 0, kMapPoseUnusable = 1, kMapPoseOutOfRange = 2;
+
+// The live record {key, n, sx, sy, sz, si} of a table of leaf leaf_src under the pose p, for a table of leaf leaf_dst: its key there and
+// add[0..4] = {n, n q0, n q1, n q2, si}, or why it has none.
+DVO_HD int map_pose_record(const MapPose& p, uint64_t key, uint32_t n, uint32_t sx, uint32_t sy, uint32_t sz, uint32_t si, float leaf_src,
+                           float leaf_dst, uint64_t* key2, uint32_t add[5]) {
+  float c[4], P[3];
+  uint32_t q[4];
+  map_extract_voxel(key, n, sx, sy, sz, si, leaf_src, c);
+  map_pose_point(p, c, P);
+  if (!(map_finite(P[0]) && map_finite(P[1]) && map_finite(P[2]))) return kMapPoseUnusable;
+  if (!map_key_of(P, 0.0f, leaf_dst, key2, q)) return kMapPoseOutOfRange;
+  add[0] = n;
+  add[1] = n * q[0];
+  add[2] = n * q[1];
+  add[3] = n * q[2];
+  add[4] = si;
+  return kMapPosePlaced;
 }
 
 }  // namespace dvo_hip

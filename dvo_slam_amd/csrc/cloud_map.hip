@@ -34,6 +34,7 @@
 #include "global_ptr.h"
 #include "launch.h"
 #include "cloud_map.h"
+#include "map_device.h"
 
 #ifndef DVO_MAP_COMBINE_RUNS
 #define DVO_MAP_COMBINE_RUNS 1
@@ -45,26 +46,6 @@ namespace {
 
 typedef unsigned GlobalU32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned GlobalU32x2 __attribute__((ext_vector_type(2)));
-
-// the frame that owns workgroup b: first_block is strictly increasing (every frame has at least one pixel), tbl[n_frames] ends the list
-__device__ __forceinline__ int map_frame_of(const MapFrame* __restrict__ tbl, int n_frames, int b) {
-  int lo = 0, hi = n_frames;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (tbl[mid].first_block <= b) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ void wave_count(unsigned long long* counter, unsigned long long mask, int lane) {
-  if (lane == 0 && mask != 0) (void)__hip_atomic_fetch_add(counter, (unsigned long long)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ... or, for a frame that is being removed, the count taken back (two's complement: the counter holds what the map's frames added)
-__device__ __forceinline__ void wave_uncount(unsigned long long* counter, unsigned long long mask, int lane) {
-  if (lane == 0 && mask != 0) (void)__hip_atomic_fetch_add(counter, 0ull - (unsigned long long)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 __global__ __launch_bounds__(256) void k_world_points(const MapFrame* __restrict__ tbl, int n_frames, float min_depth, float max_depth) {
 #pragma clang fp contract(off)

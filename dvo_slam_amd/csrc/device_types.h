@@ -212,6 +212,22 @@ struct MapTable {
   float leaf;
   MapColourSlot* colour;               // the side table of a coloured map (cloud_colour.h), same index as slots; null for a grey map
 };
+// one source of a k_map_merge launch (map_merge.hip; include/dvo_hip.h, dvo_hip_map_merge / _move_submaps / _merge_records; cloud_map.h,
+// Merge): a table, or a record array, that goes into (+1) or out of (-1) the launch's destination.  Sources of different sizes share a
+// launch like MapFrame's: each owns the workgroups first_block .. first_block + ceil(count / 256) - 1, and the table ends with one more
+// entry that carries only the launch's block count.  A source may stand in a table twice: a move of a sub-map lists it under its old
+// pose with sign -1 and under its new one with sign +1.
+struct MapMergeEntry {
+  const MapSlot* slots;                // `count` records of 32 bytes (a table: its capacity)
+  const MapColourSlot* colour;         // coloured destination: the colour records at the same indices; else null, not read
+  unsigned long long count;            // at least 1
+  unsigned long long out_of_range, unusable;   // added to the destination's counters once per entry (a plain merge from a map: the
+                                       // source's own counts, two's complement for sign -1; else 0)
+  MapPose pose;                        // the POSED instantiation: source coordinates -> destination coordinates
+  float leaf_src;                      // ... and the leaf the source's records were binned with
+  int sign;
+  int first_block;
+};
 // one plane of a k_colour_pack launch (cloud_colour.hip; include/dvo_hip.h, dvo_hip_frames_set_colour): the caller's 8-bit colour plane ->
 // the frame's plane of packed pixels, w * h dwords, tight.  Planes of different sizes share a launch like MapFrame's.
 struct ColourPlane {

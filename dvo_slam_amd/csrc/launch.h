@@ -100,6 +100,14 @@ void launch_map_update_colour(hipStream_t s, const MapFrame* tbl, int n_frames, 
 hipError_t launch_map_extract_colour(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys,
                                      uint32_t* rgba);
 
+// map_merge.hip: voxel tables and record arrays into and out of a map (cloud_map.h, Merge).  tbl: n_entries entries and one more whose
+// first_block is total_blocks, the launch's grid.  launch_map_merge: every live record of every entry into (sign +1) or out of (-1) the
+// table m, which has a side table iff the entries carry colour records; posed: under each entry's pose, binned anew with m.leaf.
+// launch_map_export: the live slots of m as raw records (and colour records at the same indices, where m has a side table and colour is
+// given), at most max_records; records null: count only.  Zeroes and then sets kMapCntCursor (live slots seen).
+void launch_map_merge(hipStream_t s, const MapMergeEntry* tbl, int n_entries, int total_blocks, const MapTable& m, bool posed);
+hipError_t launch_map_export(hipStream_t s, const MapTable& m, unsigned long long max_records, MapSlot* records, MapColourSlot* colour);
+
 // cloud_colour.hip: the colour planes of frames (cloud_colour.h).  launch_colour_pack: n_planes 8-bit colour planes of one pixel format
 // into planes of packed pixels (tbl: n_planes entries and one more whose first_block is total_blocks).  launch_colour_level: the
 // level-`shift` colour plane (w x h, tight) of a level-0 plane of packed pixels with rows of `pitch` dwords.

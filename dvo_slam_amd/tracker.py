@@ -835,6 +835,43 @@ def _render_view_args(K, width, height, poses, who):
     return K, int(width), int(height), T
 
 
+def _merge_poses(poses, n, who):
+    """the poses of a posed merge as a contiguous [n, 4, 4] float64 array with finite entries, or ValueError / TypeError"""
+    try:
+        T = np.ascontiguousarray(poses, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("%s: poses must be real numbers, one 4 x 4 matrix per source" % who)
+    if T.ndim == 2 and n == 1:
+        T = T[None]
+    if T.ndim != 3 or T.shape[1:] != (4, 4):
+        raise ValueError("%s: a pose is a 4 x 4 matrix (source -> destination), got shape %s" % (who, T.shape))
+    if T.shape[0] != n:
+        raise ValueError("%s: %d sources but %d poses" % (who, n, T.shape[0]))
+    if not np.all(np.isfinite(T)):
+        raise ValueError("%s: a pose has an entry that is not finite" % who)
+    return T
+
+
+def _record_array(a, fields, words, who, what):
+    """(address, number of records, on the device?) of a record array: a structured numpy array with the fields of the header -- made
+    contiguous here, and kept alive by the caller's reference for the duration of the call -- or a contiguous torch int32 tensor of shape
+    [n, words] on the GPU"""
+    if isinstance(a, np.ndarray):
+        if a.dtype != np.dtype(fields) or a.ndim != 1:
+            raise TypeError("%s: %s is a one-dimensional numpy array of dtype %s" % (who, what, np.dtype(fields)))
+        if not a.flags["C_CONTIGUOUS"]:
+            raise ValueError("%s: %s must be contiguous" % (who, what))
+        return a.ctypes.data, a.shape[0], False
+    if hasattr(a, "data_ptr") and hasattr(a, "is_cuda"):
+        import torch
+        if not a.is_cuda or a.dtype != torch.int32 or a.dim() != 2 or a.shape[1] != words or not a.is_contiguous():
+            raise TypeError("%s: device %s is a contiguous torch int32 tensor of shape [n, %d] on the GPU" % (who, what, words))
+        if a.data_ptr() % 16 != 0:
+            raise ValueError("%s: device %s must be 16-byte aligned" % (who, what))
+        return a.data_ptr(), int(a.shape[0]), True
+    raise TypeError("%s: %s is a structured numpy array (export()) or a torch tensor on the GPU (export(device=True))" % (who, what))
+
+
 class KeyframeMap:
     """A voxel-grid map of keyframes on the device (dvo_hip_map_*; the reference's PointCloudAggregator::build with an exact per-voxel
     centroid): insert() fuses one level of n pyramids under their poses, extract() returns one point per occupied voxel.  The result
@@ -950,6 +987,157 @@ class KeyframeMap:
             if colour:
                 rgba = rgba[order]
         return (xyzi, counts, keys, rgba) if colour else (xyzi, counts, keys)
+
+    # ---- sub-maps (dvo_hip_map_merge, _move_submaps, _export, _merge_records; dvo_slam_amd/csrc/cloud_map.h, Merge) ----
+
+    def info(self):
+        """dict: leaf (the float32 the map bins with), colour, capacity (dvo_hip_map_info)"""
+        leaf, flags, capacity = C.c_float(), C.c_uint(), C.c_uint64()
+        self.ctx.check(self.ctx._lib.dvo_hip_map_info(self.ctx.ptr, self.ptr, C.byref(leaf), C.byref(flags), C.byref(capacity)))
+        return dict(leaf=float(leaf.value), colour=bool(flags.value & _lib.MAP_COLOUR), capacity=int(capacity.value))
+
+    def _merge_sources(self, sources, poses, who):
+        """(list of source maps, their poses as [n, 4, 4] float64 or None), or ValueError / TypeError: nothing reaches the library with a
+        source it would refuse"""
+        if isinstance(sources, KeyframeMap):
+            sources = [sources]
+        sources = list(sources)
+        for s in sources:
+            if not isinstance(s, KeyframeMap):
+                raise TypeError("%s: a source is a KeyframeMap" % who)
+            if s is self:
+                raise ValueError("%s: a map cannot be merged into itself" % who)
+            if getattr(s, "ptr", None) is None:
+                raise ValueError("%s: a source map is closed" % who)
+            if s.ctx is not self.ctx:
+                raise ValueError("%s: a source map belongs to another context (export() there, absorb() here)" % who)
+            if bool(getattr(s, "coloured", False)) != bool(getattr(self, "coloured", False)):
+                raise ValueError("%s: a coloured and a grey map do not merge" % who)
+            if poses is None and np.float32(s.leaf) != np.float32(self.leaf):
+                raise ValueError("%s: a plain merge needs the destination's leaf size (a posed merge bins anew)" % who)
+        T = None if poses is None else _merge_poses(poses, len(sources), who)
+        return sources, T
+
+    def merge(self, sources, signs=None, poses=None):
+        """The voxel tables of other maps into this one in one launch (dvo_hip_map_merge).  poses None: a PLAIN merge -- same leaf; the
+        result is bit for bit the map built from all their keyframes at once.  poses [n, 4, 4] (source -> this map's coordinates): a
+        POSED merge -- every source voxel enters as its n points at its transformed centroid (the sub-map approximation).  signs: +1
+        or -1 per source (None: all +1); -1 subtracts what a merge under the same pose added, exactly.  Raises DvoHipError with code
+        ERR_CAPACITY if points were dropped, ERR_INVALID if points found no voxel to leave; the map keeps what the call did."""
+        who = "KeyframeMap.merge"
+        sources, T = self._merge_sources(sources, poses, who)
+        n = len(sources)
+        sg = None
+        if signs is not None:
+            signs = list(signs)
+            if len(signs) != n:
+                raise ValueError("%s: %d sources but %d signs" % (who, n, len(signs)))
+            for s in signs:
+                if isinstance(s, bool) or not isinstance(s, (int, np.integer)):
+                    raise TypeError("%s: a sign is the integer +1 or -1" % who)
+                if s not in (1, -1):
+                    raise ValueError("%s: a sign is +1 or -1" % who)
+            sg = (C.c_int * max(n, 1))(*[int(s) for s in signs])
+        if n == 0:
+            return
+        self.ctx.check(self.ctx._lib.dvo_hip_map_merge(self.ctx.ptr, self.ptr, n, _handles(sources), sg,
+                                                       None if T is None else T.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def subtract(self, sources, poses=None):
+        """merge() with every sign -1: takes out what merge(sources, poses=poses) put in, exactly."""
+        if isinstance(sources, KeyframeMap):
+            sources = [sources]
+        sources = list(sources)
+        self.merge(sources, signs=[-1] * len(sources), poses=poses)
+
+    def move_submaps(self, sources, poses_old, poses_new):
+        """After a pose-graph optimisation (dvo_hip_map_move_submaps): the sub-maps leave this map under poses_old and enter it under
+        poses_new in one launch, bit for bit subtract(poses_old) followed by merge(poses_new); a sub-map whose pose stays is skipped.
+        No frame is read: the keyframes' pyramids may have been destroyed."""
+        who = "KeyframeMap.move_submaps"
+        if poses_old is None or poses_new is None:
+            raise ValueError("%s: needs the old and the new poses" % who)
+        sources, T_old = self._merge_sources(sources, poses_old, who)
+        T_new = _merge_poses(poses_new, len(sources), who)
+        if not sources:
+            return
+        dp = C.POINTER(C.c_double)
+        self.ctx.check(self.ctx._lib.dvo_hip_map_move_submaps(self.ctx.ptr, self.ptr, len(sources), _handles(sources), T_old.ctypes.data_as(dp),
+                                                              T_new.ctypes.data_as(dp)))
+
+    def export(self, device=False):
+        """(records, colour_records or None): the live voxels as raw records in no particular order (dvo_hip_map_export) -- structured
+        numpy arrays with the fields key, n, sx, sy, sz, si, pad and (a coloured map) sr, sg, sb, pad.  device=True: torch int32 tensors
+        of shape [n, 8] and [n, 4] on the GPU, the same bytes.  With info() they are the whole map: absorb() takes them back."""
+        coloured = bool(getattr(self, "coloured", False))
+        got = C.c_size_t(0)
+        self.ctx.check(self.ctx._lib.dvo_hip_map_export(self.ctx.ptr, self.ptr, 0, None, None, 0, C.byref(got)))
+        n = got.value
+        if device:
+            import torch
+            dev = "cuda:%d" % self.ctx.device
+            records = torch.empty((max(n, 1), 8), dtype=torch.int32, device=dev)
+            colour = torch.empty((max(n, 1), 4), dtype=torch.int32, device=dev) if coloured else None
+            ptrs = (records.data_ptr(), colour.data_ptr() if coloured else None)
+        else:
+            records = np.zeros(max(n, 1), np.dtype(_lib.MAP_RECORD))
+            colour = np.zeros(max(n, 1), np.dtype(_lib.MAP_COLOUR_RECORD)) if coloured else None
+            ptrs = (records.ctypes.data, colour.ctypes.data if coloured else None)
+        if n > 0:
+            self.ctx.check(self.ctx._lib.dvo_hip_map_export(self.ctx.ptr, self.ptr, n, ptrs[0], ptrs[1], 1 if device else 0, C.byref(got)))
+        return records[:got.value], (colour[:got.value] if coloured else None)
+
+    def absorb(self, records, colour=None, leaf=None, sign=1, pose=None):
+        """Raw voxel records -- what export() returned, here or in another context, or a table's raw dump -- into (sign +1) or out of
+        (-1) the map (dvo_hip_map_merge_records).  leaf: the leaf size the records were binned with (None: this map's).  pose None:
+        a plain merge, same leaf; a 4 x 4 pose (records' coordinates -> this map's): a posed one.  Equal keys are summed."""
+        who = "KeyframeMap.absorb"
+        ptr, n, on_device = _record_array(records, _lib.MAP_RECORD, 8, who, "records")
+        coloured = bool(getattr(self, "coloured", False))
+        if coloured and colour is None:
+            raise ValueError("%s: a coloured map takes records with colour records" % who)
+        if not coloured and colour is not None:
+            raise ValueError("%s: a grey map takes no colour records" % who)
+        cptr = None
+        if colour is not None:
+            cptr, cn, c_on_device = _record_array(colour, _lib.MAP_COLOUR_RECORD, 4, who, "colour")
+            if cn != n or c_on_device != on_device:
+                raise ValueError("%s: %d records but %d colour records (both on the host, or both on the device)" % (who, n, cn))
+        if n > 1 << 32:
+            raise ValueError("%s: at most 2^32 records" % who)
+        if isinstance(sign, bool) or not isinstance(sign, (int, np.integer)):
+            raise TypeError("%s: sign is the integer +1 or -1" % who)
+        if sign not in (1, -1):
+            raise ValueError("%s: sign is +1 or -1" % who)
+        leaf = float(np.float32(self.leaf if leaf is None else leaf))
+        if not (leaf > 0.0 and leaf < float("inf")):
+            raise ValueError("%s: the leaf size must be finite and > 0" % who)
+        if pose is None and np.float32(leaf) != np.float32(self.leaf):
+            raise ValueError("%s: a plain merge needs the map's own leaf size (a posed merge bins anew)" % who)
+        T = None if pose is None else _merge_poses(pose, 1, who)
+        if n == 0:
+            return
+        self.ctx.check(self.ctx._lib.dvo_hip_map_merge_records(self.ctx.ptr, self.ptr, n, ptr, cptr, 1 if on_device else 0, leaf, int(sign),
+                                                               None if T is None else T.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def save(self, path):
+        """The map into a file (numpy.savez: leaf, flags, capacity and the exported records); KeyframeMap.load reads it back."""
+        info = self.info()
+        records, colour = self.export()
+        with open(path, "wb") as f:
+            np.savez(f, leaf=np.float32(info["leaf"]), flags=np.uint32(_lib.MAP_COLOUR if info["colour"] else 0), capacity=np.uint64(info["capacity"]),
+                     records=records, colour=colour if colour is not None else np.zeros(0, np.dtype(_lib.MAP_COLOUR_RECORD)))
+
+    @classmethod
+    def load(cls, path, ctx=None, capacity=None):
+        """A new map with the voxels of a file written by save(); capacity None: the saved map's."""
+        with np.load(path) as z:
+            leaf, flags, saved_capacity = float(z["leaf"]), int(z["flags"]), int(z["capacity"])
+            records, colour = z["records"], z["colour"]
+        coloured = bool(flags & _lib.MAP_COLOUR)
+        m = cls(ctx=ctx, leaf=leaf, capacity=saved_capacity if capacity is None else capacity, colour=coloured)
+        m.absorb(records, colour if coloured else None)
+        return m
 
     def render(self, K, width, height, poses, device=False, **params):
         """Views of the map (dvo_hip_map_render): the nearest voxel per pixel of a width x height pinhole camera K = fx, fy, ox, oy at

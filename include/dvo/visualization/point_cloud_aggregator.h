@@ -19,6 +19,9 @@
 // of every registered pyramid that hasRgb() and does not carry colour yet (RgbdImagePyramid::setColourFromRgb), creates the device map
 // with DVO_HIP_MAP_COLOUR and fills the cloud's rgba (0xFFRRGGBB per voxel, include/dvo_hip.h, dvo_hip_map_extract_colour).  If some
 // registered pyramid has neither colour nor rgb, the build falls back to the grey map and says so (DeviceContext::warn); rgba stays empty.
+// merge() / subtract() / moveSubmaps() / exportRecords() / absorbRecords() work on the device maps themselves (include/dvo_hip.h,
+// dvo_hip_map_merge ...): an aggregator built in the coordinates of an anchor keyframe is a SUB-MAP that enters another aggregator's map
+// under the anchor's pose and follows a pose-graph optimisation without its keyframes' pyramids (see "sub-maps" below).
 #pragma once
 
 #include <algorithm>
@@ -137,11 +140,90 @@ class PointCloudAggregator {
     return true;
   }
 
+  // ---- sub-maps (include/dvo_hip.h, dvo_hip_map_merge / _move_submaps / _export / _merge_records) ----
+  // An aggregator whose keyframes were added under poses RELATIVE to an anchor keyframe (T_anchor^-1 * T_i) and built is a sub-map; the
+  // calls below put the device maps of such aggregators into this one's, take them out again and re-pose them, from the voxel tables
+  // alone.  They work on the map build() made last (an aggregator without keyframes gets an empty map of the first source's context and
+  // kind) and last until the next build() that rebuilds; cloud() returns the map as it stands.  All return false on a refusal or an error
+  // (dvo_hip_last_error says which) and, unlike build(), do not go through DeviceContext::fail: a refusal is an answer, not a fault.
+  struct VoxelRecord {       // 32 bytes: a slot of the device table
+    uint64_t key;
+    uint32_t n, sx, sy, sz, si, pad;
+  };
+  struct VoxelColourRecord {  // 16 bytes: the slot's colour sums (a coloured map)
+    uint32_t sr, sg, sb, pad;
+  };
+
+  // plain: the sum is, bit for bit, the map built from the keyframes of both
+  bool merge(const PointCloudAggregator& other) { return mergeOne(other, 1, 0); }
+  bool subtract(const PointCloudAggregator& other) { return mergeOne(other, -1, 0); }
+  // posed: `pose` takes the sub-map's coordinates to this map's (the anchor keyframe's pose)
+  bool merge(const PointCloudAggregator& other, const dvo::compat::Affine3d& pose) { return mergeOne(other, 1, &pose); }
+  bool subtract(const PointCloudAggregator& other, const dvo::compat::Affine3d& pose) { return mergeOne(other, -1, &pose); }
+  // after a pose-graph optimisation: every sub-map from its old anchor pose to its new one, in one launch
+  bool moveSubmaps(const std::vector<const PointCloudAggregator*>& submaps, const std::vector<dvo::compat::Affine3d>& poses_old,
+                   const std::vector<dvo::compat::Affine3d>& poses_new) {
+    if (!map_ || submaps.size() != poses_old.size() || submaps.size() != poses_new.size()) return false;
+    std::vector<dvo_hip_map*> maps;
+    std::vector<double> from(16 * submaps.size()), to(16 * submaps.size());
+    for (size_t i = 0; i < submaps.size(); ++i) {
+      if (!submaps[i] || !submaps[i]->map_) return false;
+      maps.push_back(submaps[i]->map_);
+      dvo::compat::affine_to_rowmajor(poses_old[i], &from[16 * i]);
+      dvo::compat::affine_to_rowmajor(poses_new[i], &to[16 * i]);
+    }
+    return dvo_hip_map_move_submaps(ctx_, map_, int(maps.size()), maps.data(), from.data(), to.data()) == DVO_HIP_OK;
+  }
+  // the live voxels as raw records (colour: filled for a coloured map, else emptied), in no particular order; *leaf = the map's leaf
+  bool exportRecords(std::vector<VoxelRecord>& records, std::vector<VoxelColourRecord>& colour, float* leaf = 0) const {
+    if (!map_) return false;
+    size_t n = 0, got = 0;
+    if (dvo_hip_map_export(ctx_, map_, 0, 0, 0, 0, &n) != DVO_HIP_OK) return false;
+    if (leaf && dvo_hip_map_info(ctx_, map_, leaf, 0, 0) != DVO_HIP_OK) return false;
+    records.resize(n);
+    colour.resize(map_coloured_ ? n : size_t(0));
+    if (n == 0) return true;
+    return dvo_hip_map_export(ctx_, map_, n, records.data(), map_coloured_ ? colour.data() : 0, 0, &got) == DVO_HIP_OK && got == n;
+  }
+  // records (of another context, another process, a file) into or out of the map; pose null: plain, leaf must be the map's
+  bool absorbRecords(const std::vector<VoxelRecord>& records, const std::vector<VoxelColourRecord>& colour, float leaf = 0.01f, int sign = 1,
+                     const dvo::compat::Affine3d* pose = 0) {
+    if (!map_ || (map_coloured_ && colour.size() != records.size()) || (!map_coloured_ && !colour.empty())) return false;
+    double T[16];
+    if (pose) dvo::compat::affine_to_rowmajor(*pose, T);
+    return dvo_hip_map_merge_records(ctx_, map_, records.size(), records.data(), map_coloured_ ? colour.data() : 0, 0, leaf, sign, pose ? T : 0) == DVO_HIP_OK;
+  }
+  // the map as it stands -- after merges -- one point per voxel, sorted by voxel key (build() without rebuilding)
+  PointCloud::Ptr cloud() {
+    PointCloud::Ptr out(new PointCloud);
+    if (!map_) {
+      out->push_back_default();
+      return out;
+    }
+    return extract(out);
+  }
+
  private:
   struct Entry {
     dvo::core::RgbdImagePyramidPtr pyramid;
     dvo::compat::Affine3d pose;
   };
+  static_assert(sizeof(VoxelRecord) == 32 && sizeof(VoxelColourRecord) == 16, "the records of include/dvo_hip.h, dvo_hip_map_export");
+
+  bool mergeOne(const PointCloudAggregator& other, int sign, const dvo::compat::Affine3d* pose) {
+    if (!other.map_) return false;
+    using dvo::core::dvo_hip_check;
+    if (!map_) {                               // an aggregator that only collects sub-maps: an empty map like the first one
+      ctx_ = other.ctx_;
+      if (!dvo_hip_check(ctx_, dvo_hip_map_create_ex(ctx_, 0.01f, capacity_, other.map_coloured_ ? DVO_HIP_MAP_COLOUR : 0u, &map_), "dvo_hip_map_create_ex")) return false;
+      map_coloured_ = other.map_coloured_;
+    }
+    double T[16];
+    if (pose) dvo::compat::affine_to_rowmajor(*pose, T);
+    dvo_hip_map* src[1] = {other.map_};
+    const int signs[1] = {sign};
+    return dvo_hip_map_merge(ctx_, map_, 1, src, signs, pose ? T : 0) == DVO_HIP_OK;
+  }
   PointCloudAggregator(const PointCloudAggregator&);
   PointCloudAggregator& operator=(const PointCloudAggregator&);
 

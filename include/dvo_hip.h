@@ -670,6 +670,63 @@ int dvo_hip_map_render_colour(dvo_hip_context* ctx, dvo_hip_map* map, int n_view
                               const double* poses /* n x 16 */, const dvo_hip_render_params* params, uint32_t* const* rgba_out,
                               float* const* depth_out, int out_on_device);
 
+/* ---- keyframe sub-maps: merge, subtract, re-pose and export voxel tables -------------------------------------------------------------
+ * The reference's LocalMap (dvo_slam/include/dvo_slam/local_map.h) is a keyframe with a handful of frames around it; the pose graph moves
+ * keyframes and everything attached to one moves rigidly with it.  A SUB-MAP is a dvo_hip_map built in the coordinates of its anchor
+ * keyframe (insertion poses T_anchor^-1 * T_i); the global map is the sum of the sub-maps under their anchors' poses, and follows
+ * dvo_hip_graph_optimize from the voxel tables alone -- 32 bytes per voxel (48 with colour) -- so the frames can be destroyed.
+ *   record      32 bytes, the layout of a slot: {uint64 key; uint32 n, sx, sy, sz, si, pad} (dvo_slam_amd/csrc/cloud_map.h, MapSlot); of a
+ *               coloured map also 16 bytes {uint32 sr, sg, sb, pad} at the same index of a second array.  A record whose key is ~0 or
+ *               whose n is 0 is not live and is skipped.
+ *   plain       sources of the destination's leaf (equal as bits).  Sign +1: a record's key is probed like an inserted point's and the
+ *               record's integer sums are ADDED to the voxel's as whole words, which is the arithmetic of inserting its points one at a
+ *               time: the sum of two sub-maps is, BIT FOR BIT in what dvo_hip_map_extract and dvo_hip_map_render give, the map built from all
+ *               their keyframes at once.  Sign -1: a lookup that claims nothing, the same words subtracted, as dvo_hip_map_remove does: what
+ *               was merged leaves exactly.  A record without a slot is dropped (+1) or unmatched (-1), counted by its n points.
+ *   posed       the source enters under a pose T (source coordinates -> destination coordinates, row-major 4 x 4 double cast to float
+ *               once): a source voxel's centroid (what dvo_hip_map_extract returns for it) is transformed in float, binned with the
+ *               DESTINATION's leaf, and added there as n points at that position with the voxel's intensity (and colour) sums unchanged.
+ *               Deterministic and equal to the host build of cloud_map.h (map_pose_record) bit for bit; subtracting under the same pose
+ *               restores the destination bit for bit.  The leaves may differ.
+ *   accuracy    a posed merge treats a source voxel's points as n copies of their centroid: a point may land up to one source leaf from
+ *               where a rebuild from the frames would put it.  The point-weighted mean position is kept to quantisation, per axis
+ *               (leaf_src + leaf_dst) / 2048 plus float rounding of the transform.  It is the sub-map approximation, not a rebuild.
+ *   statistics  a plus merge adds the points it placed to `points`, a minus merge takes them back (and adds them to `removed`); dropped and
+ *               unmatched count points.  A posed merge counts a record whose transformed centroid is not finite as n unusable points,
+ *               one beyond +-2^20 voxels as n out of range.  A plain merge from a map adds (-1: takes back) the source's out_of_range
+ *               and unusable: points, out_of_range, unusable, dropped and over_limit of a merged map are those of the single build.
+ *   returns     as dvo_hip_map_move: DVO_HIP_ERR_CAPACITY if the call dropped points, else DVO_HIP_ERR_INVALID if it left unmatched
+ *               points, else DVO_HIP_OK; the map keeps what the call did.  Every call runs on the main stream and waits for it, as
+ *               dvo_hip_map_insert does.
+ *   refusals    DVO_HIP_ERR_INVALID, nothing launched, nothing changed: a source that is the destination; a null map or one of another
+ *               context (that way leads through dvo_hip_map_export and dvo_hip_map_merge_records); coloured against grey, or a coloured
+ *               destination given records without colour records; a plain merge whose source leaf is not the destination's; a sign
+ *               other than +1 and -1; a pose with an entry that is not finite; a minus entry into a destination that has dropped
+ *               points since its last clear or rehash; n_src < 0; more than 2^32 records; device records not 16-byte aligned.
+ *   cost        profiles/keyframe_map_merge.md. */
+/* leaf, flags (DVO_HIP_MAP_COLOUR or 0) and slots of a map; any of the three may be NULL */
+int dvo_hip_map_info(dvo_hip_context* ctx, dvo_hip_map* map, float* leaf, unsigned* flags, uint64_t* capacity);
+/* n_src source maps into (sign +1) or out of (-1) dst in ONE launch.  signs_or_null NULL: +1 for every source.  poses_or_null NULL: a
+ * plain merge of every source; else a posed merge of source i under poses[16 * i ..].  A source may appear more than once. */
+int dvo_hip_map_merge(dvo_hip_context* ctx, dvo_hip_map* dst, int n_src, dvo_hip_map* const* src, const int* signs_or_null,
+                      const double* poses_or_null /* n x 16 */);
+/* After a pose-graph optimisation: every sub-map leaves dst under poses_old and enters it under poses_new, in ONE launch over 2 n
+ * entries -- bit for bit the posed subtraction followed by the posed merge.  A sub-map whose two poses are equal once cast to float is
+ * left out (a call in which every one is launches nothing and returns DVO_HIP_OK). */
+int dvo_hip_map_move_submaps(dvo_hip_context* ctx, dvo_hip_map* dst, int n_src, dvo_hip_map* const* src, const double* poses_old /* n x 16 */,
+                             const double* poses_new /* n x 16 */);
+/* The live voxels of a map as raw records, in unspecified order: records (max_records x 32 bytes) and, of a coloured map, their colour
+ * records into colour_records_or_null (max_records x 16 bytes) where that is not NULL; host arrays, or device arrays (16-byte aligned) with
+ * out_on_device.  *n_records = records written.  DVO_HIP_ERR_CAPACITY if the map holds more live voxels than max_records (the first
+ * max_records found are written).  records NULL with max_records 0 only counts: *n_records = the live voxels, DVO_HIP_OK.  With the leaf and the flags (dvo_hip_map_info) the
+ * records are the whole map: save them, or hand them to another context or device. */
+int dvo_hip_map_export(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_records, void* records, void* colour_records_or_null, int out_on_device,
+                       size_t* n_records);
+/* dvo_hip_map_merge of one source given as n_records records (and colour records) in host memory -- staged on the main stream -- or in
+ * device memory (on_device, 16-byte aligned), binned with leaf_src.  pose_or_null NULL: plain.  Equal keys in the array are summed. */
+int dvo_hip_map_merge_records(dvo_hip_context* ctx, dvo_hip_map* dst, size_t n_records, const void* records, const void* colour_or_null,
+                              int on_device, float leaf_src, int sign, const double* pose_or_null /* 16 */);
+
 /* ---- the hot path --------------------------------------------------------------------------- */
 /* DenseTracker::match(RgbdImagePyramid& reference, RgbdImagePyramid& current, Result&)
  * (dvo_core/src/dense_tracking.cpp:123-376).  `levels`/`iters` may be NULL (no statistics).
