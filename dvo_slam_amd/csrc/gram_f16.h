@@ -5,6 +5,16 @@
 // this with the 2x2 precision) is accumulated as  H H^T + H L^T + (H L^T)^T  with v = H + L split into f16 high and low parts: two
 // v_mfma_f32_16x16x32_f16 per 32 pixels that run beside the vector ALU, where the f32 form (16 v_mfma_f32_16x16x4_f32 per 64 pixels)
 // takes the vector ALU's issue slots.  The dropped L L^T term is 2^-22 of the result.
+//
+// Range of the split (split_pairs): both parts are rounded to nearest, so |v - hi - lo| <= max(2^-22 |v|, 2^-25).  The relative bound
+// needs a NORMAL low part; |lo| <= 2^-11 |v|, and below 2^-14 an f16 is subnormal with an absolute step of 2^-24: for |v| < 2^-3 the
+// error is up to 2^-25 whatever |v| is, below 2^-14 the high part is subnormal too, and a component below 2^-25 vanishes.  (Subnormal
+// halves are kept by the conversion and by the matrix pipe: measured, tests/test_gpu_scales.py.)  kResidualScale lifts the two residual
+// components out of that range; the twelve Jacobian components have no such factor.  Their translation entries are about
+// sqrt(w) fx (grey step per pixel) / z: they shrink with a dim or low-contrast frame and with a far scene, and the sums then lose
+// precision gradually -- nothing is flagged (the range guard below is for the overflow side only).  Measured envelope and what
+// happens outside it: DESIGN.md section 2, "Scale envelope" (every bound holds down to 2^-16 of the 8-bit range at the test scenes'
+// depths); the f32 Gram (variant 6) has no such floor.
 #pragma once
 #include "sweep_parts.h"
 
@@ -16,24 +26,25 @@ namespace dvo_hip {
 // wavefront instead of 5120: with the window that is 29.4 KB per workgroup, five workgroups per compute unit instead of four).
 constexpr int kHalfRow = 40;                            // halfs per pixel row
 constexpr int kSlabFloatsF16 = 32 * kHalfRow / 2;       // 640 floats = 2560 B (>= the 512 floats the Gram matrices need at the end)
-constexpr float kResidualScale = 256.0f;                // the two residual components are lifted out of the f16 subnormal range
+constexpr float kResidualScale = 256.0f;                // the two residual components are lifted out of the f16 subnormal range (at 8-bit grey levels and metres)
 
 typedef _Float16 __attribute__((ext_vector_type(8))) f16x8;
 typedef __fp16 __attribute__((__vector_size__(4 * sizeof(__fp16)))) fp16x4;
 typedef __fp16 __attribute__((ext_vector_type(2))) fp16x2;
 typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
 
-// v = hi + lo with hi, lo in f16; two components per call, packed as the two halves of a register.  hi is rounded toward zero (it
-// saturates at the largest f16 instead of becoming infinite), lo = f16(v - hi) with the subtraction exact in f32:
-// v_fma_mix_f32 reads the f16 half of `hi` directly and subtracts in f32 (the compiler emits a conversion and a subtraction
-// unless it can fold a multiplication in); the two differences are packed with round toward zero as well.
+// v = hi + lo with hi, lo in f16; two components per call, packed as the two halves of a register.  hi = f16(v) rounded to nearest
+// even, lo = f16(v - hi) with the subtraction exact in f32: v_fma_mix_f32 reads the f16 half of `hi` directly and subtracts in f32
+// (the compiler emits a conversion and a subtraction unless it can fold a multiplication in); the two differences are packed with
+// round to nearest even as well.  Subnormal halves are kept, in both parts.
 // Range: a component beyond +-65504 has an INFINITE high part (round to nearest) and the sum no longer represents it; the epilogue
 // finds the infinity (or the not-a-number it turns into) in H H^T and the batch is repeated with the f32 Gram (capi.hip, counter
 // "f16_range_repeats").
 // (seven pairs at a time, each step for all pairs before the next: an instruction never waits for the one right before it)
 __device__ __forceinline__ void split_pairs(const float (&v)[14], unsigned (&hi)[7], unsigned (&lo)[7]) {
-  // (round to nearest even -- v_cvt_pk_f16_f32, gfx950 -- for both parts: |v - hi - lo| <= 2^-22 |v|, four times closer than with
-  // round toward zero, which matters where the stopping precision of a level is near the noise of the normal equations)
+  // (round to nearest even -- v_cvt_pk_f16_f32, gfx950 -- for both parts: |v - hi - lo| <= 2^-22 |v| while lo is a normal f16, i.e.
+  // for |v| >= 2^-3, and <= 2^-25 absolute below that (see the head of this file); four times closer than with round toward zero,
+  // which matters where the stopping precision of a level is near the noise of the normal equations)
   typedef float __attribute__((ext_vector_type(2))) f32pair;
   typedef _Float16 __attribute__((ext_vector_type(2))) f16pair;
 #pragma unroll

@@ -223,6 +223,15 @@ int dvo_hip_frames_update_colour_as_ex(dvo_hip_context* ctx, int n_frames, dvo_h
  *   image plane  DVO_HIP_PIXEL_F32: one float per pixel, 0..255, taken as is (no clamp, no rounding); its pitch follows the colour
  *                pitch rules, in bytes, 0 = tight (width * 4).  Or an 8-bit plane: DVO_HIP_PIXEL_GREY8 (one byte per pixel) or one of
  *                the four colour formats, converted as by the colour ingest.
+ *   scale        "taken as is" includes the scale: a float image in [0, 1], a dim or low-contrast frame and depths in other units than
+ *                the test scenes' 0.4-12 m are legal.  The f32-Gram schedules (option "variant" 0, 5, 6) do not depend on the
+ *                intensity's scale by one bit.  The default schedule forms its normal equations from f16 high + low parts, which have
+ *                an absolute floor: measured on an MI355X, with the grey levels x 2^ki and the depths x 2^kz against 8-bit levels at
+ *                those depths, it keeps every documented bound for ki >= -16 and ki - kz >= -16 -- a [0, 1] image
+ *                is ki = -8 -- and for depth scales of 1/64 ... 256 at 8-bit levels.  Outside that range nothing is flagged and no pair
+ *                is repeated (the "f16_range_repeats" guard is for components too LARGE for f16): residuals, constraints, precision
+ *                matrix and log-likelihood keep their accuracy, the normal equations lose about a factor of four of it per factor of
+ *                four in scale (1.3e-4 instead of 1e-5 at ki = -16, kz = 4).  Rescale such planes, or run them under "variant" 6.
  *   depth plane  DVO_HIP_DEPTH_F32: one float per pixel, metres, NaN = hole, with a pitch of its own in bytes, 0 = tight (width * 4).
  *                The stored depth is z * depth_scale, one rounding of its own (depth_scale 1 is exact; float millimetres are
  *                depth_scale 1e-3f).  Nothing else is done to a value: NaN stays NaN (a hole); 0, negative values and +-infinity are
@@ -246,7 +255,7 @@ int dvo_hip_frames_update_colour_as_ex(dvo_hip_context* ctx, int n_frames, dvo_h
  * below width * 4 (or width * channels), a pitch above 2^31 - 1, a misaligned float plane, frames of differing cameras or level
  * counts, DVO_HIP_INGEST_DEFER with host planes. */
 #define DVO_HIP_PIXEL_GREY8 0 /* one byte per pixel; the float-depth entry points only (the colour entry points refuse it) */
-#define DVO_HIP_PIXEL_F32 5   /* one float per pixel, 0..255 */
+#define DVO_HIP_PIXEL_F32 5   /* one float per pixel, 0..255 (other scales: "scale" above) */
 #define DVO_HIP_DEPTH_U16 0   /* 0 -> NaN, else value * depth_scale */
 #define DVO_HIP_DEPTH_F32 1   /* metres * depth_scale, NaN = hole */
 /* the device counterpart of dvo_hip_frame_create_f32 (both planes tight): asynchronous on the build stream like

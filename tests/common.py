@@ -318,6 +318,98 @@ def compare_runs(a, b):
     return summary
 
 
+# ---- scenes at another scale of intensity and depth (tests/test_scales.py, tests/test_gpu_scales.py) ---------------------------------
+# The warp of the single-linearisation tests (test_default_schedule_single_linearisation_against_oracle), as a twist (v, omega)
+SCALE_XI = (0.004, -0.003, 0.002, 0.005, -0.004, 0.003)
+
+
+def scaled_pair(pair, ki, kz):
+    """The float32 planes of `pair` (synth / scenes.edge_scene) with the grey levels x 2^ki and the converted depth (metres) x 2^kz: a
+    dimmer or lower-contrast frame, a nearer or farther scene.  Both products are exact (powers of two, no under- or overflow for the
+    exponents the tests use: asserted), NaN = no depth stays NaN.  xi_true's translation is x 2^kz, as the true motion of the scaled
+    scene is.  -> dict(grey_ref, depth_ref, grey_cur, depth_cur: float32; K; xi_true; ki; kz)"""
+    si, sz = np.ldexp(np.float32(1.0), ki), np.ldexp(np.float32(1.0), kz)
+    out = dict(K=pair["K"], ki=ki, kz=kz)
+    for v in ("ref", "cur"):
+        g = pair["grey_" + v].astype(np.float32)
+        z = po.convert_raw_depth(pair["depth_" + v])
+        gs, zs = g * si, z * sz
+        assert np.array_equal(gs / si, g) and np.array_equal(zs / sz, z, equal_nan=True) and np.isfinite(gs).all()
+        out["grey_" + v], out["depth_" + v] = gs, zs
+    xi = np.array(pair["xi_true"], np.float64)
+    xi[:3] *= 2.0 ** kz
+    out["xi_true"] = xi
+    return out
+
+
+def scaled_warp(xi, kz):
+    """exp(xi) as the 3 x 4 a linearisation takes, its translation x 2^kz (exact, in float32 too): the same warp of the scaled scene"""
+    T34 = np.array(po.se3_exp(np.asarray(xi, np.float64))[:3])
+    T34[:, 3] *= 2.0 ** kz
+    return T34
+
+
+def scaled_oracle_pyramids(sp, levels):
+    return tuple(po.Pyramid(sp["grey_" + v], sp["depth_" + v], sp["K"], levels) for v in ("ref", "cur"))
+
+
+def scaled_gpu_frames(ctx, sp, levels):
+    """the frames of a scaled_pair through the float ingest (RgbdCameraPyramid.create: intensity "taken as is", depth in metres)"""
+    import dvo_slam_amd as d
+    h, w = sp["grey_ref"].shape
+    cam = d.RgbdCameraPyramid(w, h, sp["K"], ctx)
+    cam.build(levels)
+    return cam.create(sp["grey_ref"], sp["depth_ref"]), cam.create(sp["grey_cur"], sp["depth_cur"])
+
+
+def kappa0(M):
+    """max|M| / min_i M_ii of a symmetric positive matrix: "1e-5 of the largest entry" is 1e-5 kappa0 in the metric of scale_errors"""
+    M = np.asarray(M, np.float64)
+    return float(np.abs(M).max() / np.diag(M).min())
+
+
+def kappa0_b(A, b):
+    """the same for the right-hand side: (max|b| / min_i D_i) / max|D^-1 b| with D = sqrt(diag A) -- an error of 1e-5 max|b| in the entry
+    with the smallest D_i, in the metric of scale_errors"""
+    D = np.sqrt(np.diag(np.asarray(A, np.float64)))
+    b = np.asarray(b, np.float64)
+    return float(np.abs(b).max() / D.min() / np.abs(b / D).max())
+
+
+def scale_errors(g, o):
+    """One linearisation `g` against the reference `o` (dicts with A, b, P) in a metric that survives a change of units of the twist's
+    translation, of the intensity or of the depth: with D = sqrt(diag(A_o)),
+      errA = max |D^-1 (A_g - A_o) D^-1|          (every entry relative to the geometric mean of its two diagonal entries),
+      errb = max |D^-1 (b_g - b_o)| / max |D^-1 b_o|,
+      errP = max |E^-1 (P_g - P_o) E^-1|  with E = sqrt(diag(P_o)).
+    A block of A (or an entry of P) that is a thousand times smaller than the largest one is held as tightly as that one."""
+    Ao, Po = np.asarray(o["A"], np.float64), np.asarray(o["P"], np.float64)
+    D, E = np.sqrt(np.diag(Ao)), np.sqrt(np.diag(Po))
+    dA = (np.asarray(g["A"], np.float64) - Ao) / np.outer(D, D)
+    db = (np.asarray(g["b"], np.float64) - np.asarray(o["b"], np.float64)) / D
+    dP = (np.asarray(g["P"], np.float64) - Po) / np.outer(E, E)
+    return dict(errA=float(np.abs(dA).max()), errb=float(np.abs(db).max() / np.abs(np.asarray(o["b"], np.float64) / D).max()),
+                errP=float(np.abs(dP).max()))
+
+
+def unscaled_run(run, kz):
+    """A match() result dict of a scene whose depth is x 2^kz, in the units of the unscaled scene: the translation of T and of every
+    increment divided by 2^kz, the information matrices multiplied blockwise (exact: powers of two).  compare_runs then holds a far
+    scene's translation as tightly as the near one's."""
+    s = 2.0 ** kz
+    S = np.array([s, s, s, 1.0, 1.0, 1.0])
+    out = dict(run)
+    T = np.array(run["T"], np.float64)
+    T[:3, 3] /= s
+    out["T"] = T
+    out["information"] = np.asarray(run["information"]) * np.outer(S, S)
+    out["levels"] = []
+    for L in run["levels"]:
+        its = [dict(it, x=np.asarray(it["x"]) / S, A=np.asarray(it["A"]) * np.outer(S, S)) for it in L["iterations"]]
+        out["levels"].append(dict(L, iterations=its))
+    return out
+
+
 # ---- the reference's own callers on the engine (tests/dropin) -------------------------------------------------------
 _dropin = None
 
