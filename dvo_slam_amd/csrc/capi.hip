@@ -659,6 +659,38 @@ int fail(dvo_hip_context* ctx, int code, const char* who, const char* rule) {
   return code;
 }
 
+// The checks of a list of frames that every entry point shares; `who` names the entry point in the error text.  The list itself
+// (others: the call's other mandatory pointers are there) ...
+int check_frame_count(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const char* who, bool others = true) {
+  if (!ctx || n_frames < 1 || !frames || !others) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  return DVO_HIP_OK;
+}
+// ... one frame of it (own_context: it must be a frame of a camera of this context) ...
+int check_frame(dvo_hip_context* ctx, const dvo_hip_frame* f, const char* who, bool own_context = false) {
+  if (!f) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null frame");
+  if (own_context && std::find(ctx->cameras.begin(), ctx->cameras.end(), f->cam) == ctx->cameras.end())
+    return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame of another context");
+  return DVO_HIP_OK;
+}
+// ... and both, for an entry point that checks nothing in between
+int check_frame_list(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const char* who, bool own_context = false) {
+  int rc = check_frame_count(ctx, n_frames, frames, who);
+  for (int i = 0; i < n_frames && rc == DVO_HIP_OK; ++i) rc = check_frame(ctx, frames[i], who, own_context);
+  return rc;
+}
+
+// The table of a launch whose workgroups find their entry by bisecting first_block (map_device.h), into `tbl` on the main stream: `host`
+// holds the launch's entries, their first_block set, and one more, which becomes the end of the list at total_blocks.
+template <typename Entry>
+int upload_block_table(dvo_hip_context* ctx, DevBuf& tbl, std::vector<Entry>& host, int total_blocks) {
+  std::memset(&host.back(), 0, sizeof(Entry));
+  host.back().first_block = total_blocks;
+  const size_t bytes = host.size() * sizeof(Entry);
+  DVO_HIP_TRY(ctx, tbl.reserve(bytes));
+  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, tbl.p, host.data(), bytes));
+  return DVO_HIP_OK;
+}
+
 // The raw planes of a batch of frames (capi_ingest.inc), in host or in device memory: an 8-bit intensity or colour plane and a u16 depth
 // plane per frame, one format and one row pitch for all of them
 struct IngestSource {
@@ -1065,10 +1097,12 @@ int dvo_hip_frame_select(dvo_hip_context* ctx, dvo_hip_frame* frame, int level, 
 int dvo_hip_frames_set_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const uint8_t* const* masks,
                                  size_t mask_pitch, int masks_on_device, float min_depth, float max_depth) {
   DVO_ENTER(ctx);
-  if (!ctx || n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_selection: bad argument");
+  int rc = check_frame_count(ctx, n_frames, frames, "frames_set_selection");
+  if (rc != DVO_HIP_OK) return rc;
   if (!(min_depth <= max_depth)) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_selection: need min_depth <= max_depth (no NaN)");
   for (int i = 0; i < n_frames; ++i) {
-    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_selection: null frame");
+    rc = check_frame(ctx, frames[i], "frames_set_selection");
+    if (rc != DVO_HIP_OK) return rc;
     const size_t w0 = size_t(frames[i]->lv[0].w);
     if (masks && masks[i] && mask_pitch != 0 && mask_pitch < w0) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_selection: mask_pitch < width");
   }
@@ -1094,7 +1128,7 @@ int dvo_hip_frames_set_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_fra
     invalidate_reference_role(f);
   }
   if (any_mask) {
-    const int rc = stamp_build(ctx, n_frames, frames);
+    rc = stamp_build(ctx, n_frames, frames);
     if (rc != DVO_HIP_OK) return rc;
   }
   if (any_host) DVO_HIP_TRY(ctx, hipStreamSynchronize(bs));   // (the caller may reuse a host mask at once)
@@ -1103,9 +1137,8 @@ int dvo_hip_frames_set_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_fra
 
 int dvo_hip_frames_clear_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames) {
   DVO_ENTER(ctx);
-  if (!ctx || n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_selection: bad argument");
-  for (int i = 0; i < n_frames; ++i)
-    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_selection: null frame");
+  const int rc = check_frame_list(ctx, n_frames, frames, "frames_clear_selection");
+  if (rc != DVO_HIP_OK) return rc;
   for (int i = 0; i < n_frames; ++i) {
     dvo_hip_frame* f = frames[i];
     if (!f->sel_on) continue;
@@ -1119,14 +1152,15 @@ int dvo_hip_frames_clear_selection(dvo_hip_context* ctx, int n_frames, dvo_hip_f
 
 int dvo_hip_frames_set_lens(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const dvo_hip_lens* lens) {
   DVO_ENTER(ctx);                                              // (a recorded ingest of these frames is carried out with the lens it was recorded under)
-  if (!ctx || n_frames < 1 || !frames || !lens) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_lens: bad argument");
+  int rc = check_frame_count(ctx, n_frames, frames, "frames_set_lens", lens != nullptr);
+  if (rc != DVO_HIP_OK) return rc;
   for (int k = 0; k < 4; ++k)
     if (!std::isfinite(lens->K_raw[k])) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_lens: K_raw is not finite");
   for (int k = 0; k < 8; ++k)
     if (!std::isfinite(lens->D[k])) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_lens: D is not finite");
   if (!(lens->K_raw[0] > 0.0f) || !(lens->K_raw[1] > 0.0f)) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_lens: need fx_raw > 0 and fy_raw > 0");
-  for (int i = 0; i < n_frames; ++i)
-    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_lens: null frame");
+  for (int i = 0; i < n_frames && rc == DVO_HIP_OK; ++i) rc = check_frame(ctx, frames[i], "frames_set_lens");
+  if (rc != DVO_HIP_OK) return rc;
   // (a depth rig projects into the rectified pinhole K: its output is rectified depth already)
   for (int i = 0; i < n_frames; ++i)
     if (frames[i]->rig_on && lens->rectify_depth != 0)
@@ -1144,9 +1178,8 @@ int dvo_hip_frames_set_lens(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* c
 
 int dvo_hip_frames_clear_lens(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames) {
   DVO_ENTER(ctx);
-  if (!ctx || n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_lens: bad argument");
-  for (int i = 0; i < n_frames; ++i)
-    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_lens: null frame");
+  const int rc = check_frame_list(ctx, n_frames, frames, "frames_clear_lens");
+  if (rc != DVO_HIP_OK) return rc;
   for (int i = 0; i < n_frames; ++i) {
     frames[i]->lens_on = false;
     frames[i]->lens = dvo_hip_lens{};
@@ -1156,15 +1189,16 @@ int dvo_hip_frames_clear_lens(dvo_hip_context* ctx, int n_frames, dvo_hip_frame*
 
 int dvo_hip_frames_set_depth_rig(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const dvo_hip_depth_rig* rig) {
   DVO_ENTER(ctx);                                              // (a recorded ingest of these frames is carried out with the rig it was recorded under)
-  if (!ctx || n_frames < 1 || !frames || !rig) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: bad argument");
+  int rc = check_frame_count(ctx, n_frames, frames, "frames_set_depth_rig", rig != nullptr);
+  if (rc != DVO_HIP_OK) return rc;
   for (int k = 0; k < 4; ++k)
     if (!std::isfinite(rig->K_depth[k])) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: K_depth is not finite");
   for (int k = 0; k < 12; ++k)
     if (!std::isfinite(rig->T[k])) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: T is not finite");
   if (!(rig->K_depth[0] > 0.0f) || !(rig->K_depth[1] > 0.0f)) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: need fx_d > 0 and fy_d > 0");
   if (rig->reserved[0] != 0 || rig->reserved[1] != 0) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: reserved must be 0");
-  for (int i = 0; i < n_frames; ++i)
-    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: null frame");
+  for (int i = 0; i < n_frames && rc == DVO_HIP_OK; ++i) rc = check_frame(ctx, frames[i], "frames_set_depth_rig");
+  if (rc != DVO_HIP_OK) return rc;
   for (int i = 0; i < n_frames; ++i)
     if (frames[i]->lens_on && frames[i]->lens.rectify_depth != 0)
       return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_rig: the frame's lens rectifies depth (a rig's output is rectified already: rectify_depth = 0)");
@@ -1177,9 +1211,8 @@ int dvo_hip_frames_set_depth_rig(dvo_hip_context* ctx, int n_frames, dvo_hip_fra
 
 int dvo_hip_frames_clear_depth_rig(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames) {
   DVO_ENTER(ctx);
-  if (!ctx || n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_depth_rig: bad argument");
-  for (int i = 0; i < n_frames; ++i)
-    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_clear_depth_rig: null frame");
+  const int rc = check_frame_list(ctx, n_frames, frames, "frames_clear_depth_rig");
+  if (rc != DVO_HIP_OK) return rc;
   for (int i = 0; i < n_frames; ++i) {
     frames[i]->rig_on = false;
     frames[i]->rig = dvo_hip_depth_rig{};

@@ -2,25 +2,11 @@
 // dvo_hip_frame_download_colour; semantics: cloud_colour.h; kernels: cloud_colour.hip).  A frame's colour is its own level-0 plane of
 // packed pixels, written and read on the context's main stream only -- the stream every map call runs on -- so it needs no event of its
 // own; arguments are checked before anything is launched or changed.  Textually included by capi.hip inside its extern "C" block.
-namespace {
-
-int check_colour_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const char* who) {
-  if (!ctx || n_frames < 1 || !frames) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
-  for (int i = 0; i < n_frames; ++i) {
-    if (!frames[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null frame");
-    if (std::find(ctx->cameras.begin(), ctx->cameras.end(), frames[i]->cam) == ctx->cameras.end())
-      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame of another context");
-  }
-  return DVO_HIP_OK;
-}
-
-}  // namespace
-
 int dvo_hip_frames_set_colour(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour, int pixel_format,
                               size_t colour_pitch, int on_device) {
   DVO_ENTER(ctx);
   const char* who = "frames_set_colour";
-  int rc = check_colour_frames(ctx, n_frames, frames, who);
+  int rc = check_frame_list(ctx, n_frames, frames, who, /*own_context=*/true);
   if (rc != DVO_HIP_OK) return rc;
   const int channels = pixel_channels(pixel_format);
   if (channels == 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "unknown pixel format");
@@ -78,11 +64,8 @@ int dvo_hip_frames_set_colour(dvo_hip_context* ctx, int n_frames, dvo_hip_frame*
     p.first_block = at_block;
     at_block += (w * h + 255) / 256;
   }
-  std::memset(&host[size_t(n_frames)], 0, sizeof(ColourPlane));
-  host[size_t(n_frames)].first_block = at_block;
-  const size_t bytes = host.size() * sizeof(ColourPlane);
-  DVO_HIP_TRY(ctx, ctx->colour_tbl.reserve(bytes));
-  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->colour_tbl.p, host.data(), bytes));
+  rc = upload_block_table(ctx, ctx->colour_tbl, host, at_block);
+  if (rc != DVO_HIP_OK) return rc;
   launch_colour_pack(ctx->stream, ctx->colour_tbl.as<ColourPlane>(), n_frames, at_block, pixel_format);
   DVO_HIP_TRY(ctx, hipGetLastError());
   // the caller's memory, host or device, may be reused when the call returns
@@ -93,7 +76,7 @@ int dvo_hip_frames_set_colour(dvo_hip_context* ctx, int n_frames, dvo_hip_frame*
 
 int dvo_hip_frames_clear_colour(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames) {
   DVO_ENTER(ctx);
-  const int rc = check_colour_frames(ctx, n_frames, frames, "frames_clear_colour");
+  const int rc = check_frame_list(ctx, n_frames, frames, "frames_clear_colour", /*own_context=*/true);
   if (rc != DVO_HIP_OK) return rc;
   for (int i = 0; i < n_frames; ++i) frames[i]->colour_on = false;   // (the plane is kept for the next colour)
   return DVO_HIP_OK;
@@ -103,7 +86,7 @@ int dvo_hip_frame_download_colour(dvo_hip_context* ctx, dvo_hip_frame* frame, in
   DVO_ENTER(ctx);
   const char* who = "frame_download_colour";
   dvo_hip_frame* one[1] = {frame};
-  const int rc = check_colour_frames(ctx, frame ? 1 : 0, one, who);
+  const int rc = check_frame_list(ctx, frame ? 1 : 0, one, who, /*own_context=*/true);
   if (rc != DVO_HIP_OK) return rc;
   if (!out) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
   if (level < 0 || level >= frame->levels) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the frame does not have that level");

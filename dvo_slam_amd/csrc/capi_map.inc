@@ -29,14 +29,14 @@ MapTable map_table(const dvo_hip_map* map) {
 // frames, poses, level and depth range of a keyframe-map call; `who` names the entry point in the error text
 int check_map_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float min_depth,
                      float max_depth, const char* who, int entries_per_frame = 1) {
-  if (!ctx || n_frames < 1 || !frames || !poses) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  int rc = check_frame_count(ctx, n_frames, frames, who, poses != nullptr);
+  if (rc != DVO_HIP_OK) return rc;
   if (!(min_depth <= max_depth)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "need min_depth <= max_depth (no NaN)");
   long long blocks = 0;
   for (int i = 0; i < n_frames; ++i) {
     const dvo_hip_frame* f = frames[i];
-    if (!f) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null frame");
-    if (std::find(ctx->cameras.begin(), ctx->cameras.end(), f->cam) == ctx->cameras.end())
-      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame of another context");
+    rc = check_frame(ctx, f, who, /*own_context=*/true);
+    if (rc != DVO_HIP_OK) return rc;
     if (level < 0 || level >= f->levels) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame does not have that level");
     blocks += entries_per_frame * ((static_cast<long long>(f->lv[level].w) * f->lv[level].h + 255) / 256);
   }
@@ -107,13 +107,8 @@ int upload_map_entries(dvo_hip_context* ctx, const std::vector<MapEntry>& entrie
     m.shift = level;
     blocks += (L.w * L.h + 255) / 256;
   }
-  std::memset(&host[entries.size()], 0, sizeof(MapFrame));
-  host[entries.size()].first_block = blocks;
-  const size_t bytes = host.size() * sizeof(MapFrame);
-  DVO_HIP_TRY(ctx, ctx->map_tbl.reserve(bytes));
-  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->map_tbl.p, host.data(), bytes));
   *total_blocks = blocks;
-  return DVO_HIP_OK;
+  return upload_block_table(ctx, ctx->map_tbl, host, blocks);
 }
 
 // ... of n frames under poses[16 * i ..], all added.  outs (may be null): MapFrame::out.
@@ -205,95 +200,86 @@ int dvo_hip_map_clear(dvo_hip_context* ctx, dvo_hip_map* map) {
   return DVO_HIP_OK;
 }
 
-int dvo_hip_map_insert(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level,
-                       float min_depth, float max_depth) {
-  DVO_ENTER(ctx);
-  int rc = check_map(ctx, map, "map_insert");
-  if (rc == DVO_HIP_OK) rc = check_map_frames(ctx, n_frames, frames, poses, level, min_depth, max_depth, "map_insert");
-  if (rc == DVO_HIP_OK) rc = check_map_colour(ctx, map, n_frames, frames, level, "map_insert");
-  if (rc != DVO_HIP_OK) return rc;
-  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const unsigned long long candidates_before = map->candidates, dropped_before = map->dropped;
-  unsigned long long after[kMapCounters];
-  int blocks = 0;
-  rc = upload_map_frames(ctx, n_frames, frames, poses, level, nullptr, &blocks, map->coloured);
-  if (rc != DVO_HIP_OK) return rc;
-  (map->coloured ? launch_map_insert_colour : launch_map_insert)(ctx->stream, ctx->map_tbl.as<MapFrame>(), n_frames, blocks, map_table(map), min_depth, max_depth);
-  DVO_HIP_TRY(ctx, hipGetLastError());
-  rc = read_map_counters(ctx, map, after);
-  if (rc != DVO_HIP_OK) return rc;
-  const unsigned long long dropped = after[kMapCntDropped] - dropped_before;
-  ctx->map_inserts += n_frames;
-  ctx->map_points += (long long)(after[kMapCntCandidates] - candidates_before - dropped);
-  ctx->map_dropped += (long long)dropped;
-  if (dropped != 0) return fail(ctx, DVO_HIP_ERR_CAPACITY, "map_insert: the table dropped points (no free slot within the probe bound); the map keeps what it took");
-  return DVO_HIP_OK;
-}
-
 namespace {
 
-// dvo_hip_map_remove (poses_new null) and dvo_hip_map_move: one launch of k_map_insert over signed entries
-int map_update(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses_old, const double* poses_new,
-               bool move, int level, float min_depth, float max_depth, const char* who) {
-  int rc = check_map(ctx, map, who);
-  if (rc == DVO_HIP_OK) rc = check_map_frames(ctx, n_frames, frames, poses_old, level, min_depth, max_depth, who, move ? 2 : 1);
-  if (rc == DVO_HIP_OK) rc = check_map_colour(ctx, map, n_frames, frames, level, who);
-  if (rc != DVO_HIP_OK) return rc;
-  if (move && !poses_new) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
-  if (map->dropped != 0)
-    return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map has dropped points since its last clear or rehash: what it holds of a frame is not known (dvo_hip_map_rehash into a larger table, or dvo_hip_map_clear)");
-  std::vector<MapEntry> entries;
-  int removes = 0, inserts = 0;
-  for (int i = 0; i < n_frames; ++i) {
-    const MapPose from = map_pose_prepare(poses_old + size_t(i) * 16);
-    if (move) {
-      const MapPose to = map_pose_prepare(poses_new + size_t(i) * 16);
-      if (std::memcmp(&from, &to, sizeof from) == 0) continue;   // (the same twelve floats: the same points, nothing to do)
-      entries.push_back(MapEntry{frames[i], from, -1, nullptr});
-      entries.push_back(MapEntry{frames[i], to, 1, nullptr});
-      ++inserts;
-    } else {
-      entries.push_back(MapEntry{frames[i], from, -1, nullptr});
-    }
-    ++removes;
-  }
-  if (entries.empty()) return DVO_HIP_OK;
-  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+// The end of every launch that writes a map (k_map_insert, k_map_merge), called right behind it: reads the counters back -- the map's copy
+// of them is what they held before the launch -- books the points the launch added and dropped, and the frames it inserted and removed,
+// into the context's counters, and reports dropped and unmatched points.  hint: what may differ where points found no voxel to leave.
+int finish_map_write(dvo_hip_context* ctx, dvo_hip_map* map, int inserts, int removes, const char* who, const char* hint) {
+  DVO_HIP_TRY(ctx, hipGetLastError());
   const unsigned long long candidates_before = map->candidates, dropped_before = map->dropped, unmatched_before = map->unmatched;
   unsigned long long after[kMapCounters];
-  int blocks = 0;
-  rc = upload_map_entries(ctx, entries, level, &blocks, map->coloured);
-  if (rc != DVO_HIP_OK) return rc;
-  (map->coloured ? launch_map_update_colour : launch_map_update)(ctx->stream, ctx->map_tbl.as<MapFrame>(), int(entries.size()), blocks, map_table(map), min_depth, max_depth);
-  DVO_HIP_TRY(ctx, hipGetLastError());
-  rc = read_map_counters(ctx, map, after);
+  const int rc = read_map_counters(ctx, map, after);
   if (rc != DVO_HIP_OK) return rc;
   const unsigned long long dropped = after[kMapCntDropped] - dropped_before, unmatched = after[kMapCntUnmatched] - unmatched_before;
-  ctx->map_removes += removes;
   ctx->map_inserts += inserts;
+  ctx->map_removes += removes;
   ctx->map_points += (long long)(after[kMapCntCandidates] - candidates_before - dropped);
   ctx->map_dropped += (long long)dropped;
   if (dropped != 0) return fail(ctx, DVO_HIP_ERR_CAPACITY, who, "the table dropped points (no free slot within the probe bound); the map keeps what it took");
   if (unmatched != 0) {
-    ctx->err = std::string(who) + ": " + std::to_string(unmatched) +
-               " points found no voxel to leave (not the frame content, level, pose or depth range of the insertion?); the map keeps what it did";
+    ctx->err = std::string(who) + ": " + std::to_string(unmatched) + " points found no voxel to leave (" + hint + "); the map keeps what it did";
     return DVO_HIP_ERR_INVALID;
   }
   return DVO_HIP_OK;
 }
 
+enum MapUpdateMode { kMapInsert, kMapRemove, kMapMove };
+
+// dvo_hip_map_insert (poses: where the frames enter), dvo_hip_map_remove (poses: where they leave; both with poses_new null) and
+// dvo_hip_map_move: one launch of k_map_insert, over signed entries unless every frame is inserted
+int map_update(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses, const double* poses_new,
+               MapUpdateMode mode, int level, float min_depth, float max_depth, const char* who) {
+  const bool move = mode == kMapMove, insert = mode == kMapInsert;
+  int rc = check_map(ctx, map, who);
+  if (rc == DVO_HIP_OK) rc = check_map_frames(ctx, n_frames, frames, poses, level, min_depth, max_depth, who, move ? 2 : 1);
+  if (rc == DVO_HIP_OK) rc = check_map_colour(ctx, map, n_frames, frames, level, who);
+  if (rc != DVO_HIP_OK) return rc;
+  if (move && !poses_new) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  if (!insert && map->dropped != 0)
+    return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map has dropped points since its last clear or rehash: what it holds of a frame is not known (dvo_hip_map_rehash into a larger table, or dvo_hip_map_clear)");
+  std::vector<MapEntry> entries;
+  int removes = 0, inserts = 0;
+  for (int i = 0; i < n_frames; ++i) {
+    const MapPose at = map_pose_prepare(poses + size_t(i) * 16);
+    if (move) {
+      const MapPose to = map_pose_prepare(poses_new + size_t(i) * 16);
+      if (std::memcmp(&at, &to, sizeof at) == 0) continue;     // (the same twelve floats: the same points, nothing to do)
+      entries.push_back(MapEntry{frames[i], at, -1, nullptr});
+      entries.push_back(MapEntry{frames[i], to, 1, nullptr});
+    } else {
+      entries.push_back(MapEntry{frames[i], at, insert ? 1 : -1, nullptr});
+    }
+    inserts += insert || move;
+    removes += !insert;
+  }
+  if (entries.empty()) return DVO_HIP_OK;
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int blocks = 0;
+  rc = upload_map_entries(ctx, entries, level, &blocks, map->coloured);
+  if (rc != DVO_HIP_OK) return rc;
+  launch_map_insert(ctx->stream, ctx->map_tbl.as<MapFrame>(), int(entries.size()), blocks, map_table(map), min_depth, max_depth, /*mixed=*/!insert);
+  return finish_map_write(ctx, map, inserts, removes, who, "not the frame content, level, pose or depth range of the insertion?");
+}
+
 }  // namespace
+
+int dvo_hip_map_insert(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level,
+                       float min_depth, float max_depth) {
+  DVO_ENTER(ctx);
+  return map_update(ctx, map, n_frames, frames, poses, nullptr, kMapInsert, level, min_depth, max_depth, "map_insert");
+}
 
 int dvo_hip_map_remove(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level,
                        float min_depth, float max_depth) {
   DVO_ENTER(ctx);
-  return map_update(ctx, map, n_frames, frames, poses, nullptr, false, level, min_depth, max_depth, "map_remove");
+  return map_update(ctx, map, n_frames, frames, poses, nullptr, kMapRemove, level, min_depth, max_depth, "map_remove");
 }
 
 int dvo_hip_map_move(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses_old,
                      const double* poses_new, int level, float min_depth, float max_depth) {
   DVO_ENTER(ctx);
-  return map_update(ctx, map, n_frames, frames, poses_old, poses_new, true, level, min_depth, max_depth, "map_move");
+  return map_update(ctx, map, n_frames, frames, poses_old, poses_new, kMapMove, level, min_depth, max_depth, "map_move");
 }
 
 int dvo_hip_map_rehash(dvo_hip_context* ctx, dvo_hip_map* map, size_t capacity_slots) {
@@ -362,7 +348,7 @@ int dvo_hip_map_stats(dvo_hip_context* ctx, dvo_hip_map* map, struct dvo_hip_map
   if (rc0 != DVO_HIP_OK) return rc0;
   if (!out) return fail(ctx, DVO_HIP_ERR_INVALID, "map_stats: bad argument");
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  DVO_HIP_TRY(ctx, launch_map_extract(ctx->stream, map_table(map), 0, nullptr, nullptr, nullptr));   // (counts the voxels over the limit)
+  DVO_HIP_TRY(ctx, launch_map_extract(ctx->stream, map_table(map), 0, nullptr, nullptr, nullptr, nullptr));   // (counts the voxels over the limit)
   DVO_HIP_TRY(ctx, hipGetLastError());
   unsigned long long c[kMapCounters];
   const int rc = read_map_counters(ctx, map, c);
@@ -384,6 +370,46 @@ int dvo_hip_map_stats(dvo_hip_context* ctx, dvo_hip_map* map, struct dvo_hip_map
 
 namespace {
 
+// one output array of a read-out: the caller's array (null: not wanted) and the bytes of one record in it
+struct ReadOutArray {
+  void* dst;
+  size_t record_bytes;
+};
+
+// The read-out of a map's live voxels on the main stream (dvo_hip_map_extract, dvo_hip_map_extract_colour, dvo_hip_map_export):
+// pass(n, dev) walks the table and writes at most n records to the device arrays dev[k] (null: not wanted).  The first pass counts
+// (n = 0, every array null; c: the counters behind it, c[kMapCntCursor] the live voxels), the second fills *take = min(live, max) records:
+// a host destination is staged for just that many out of ctx->map_stage and copied out; one synchronise.  outs: in the order of falling
+// record sizes, powers of two, so every staged array is aligned to its record.
+int map_read_out(dvo_hip_context* ctx, dvo_hip_map* map, size_t max, const std::vector<ReadOutArray>& outs, int out_on_device,
+                 const std::function<hipError_t(unsigned long long, void* const*)>& pass, unsigned long long c[kMapCounters], size_t* take) {
+  *take = 0;
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<void*> dev(outs.size(), nullptr);
+  DVO_HIP_TRY(ctx, pass(0, dev.data()));
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  const int rc = read_map_counters(ctx, map, c);
+  if (rc != DVO_HIP_OK) return rc;
+  const size_t n = size_t(c[kMapCntCursor] < max ? c[kMapCntCursor] : max);
+  if (n == 0) return DVO_HIP_OK;
+  size_t bytes = 0;
+  for (const ReadOutArray& o : outs) bytes += o.dst ? n * o.record_bytes : 0;
+  if (!out_on_device) DVO_HIP_TRY(ctx, ctx->map_stage.reserve(bytes));
+  size_t at = 0;
+  for (size_t k = 0; k < outs.size(); ++k) {
+    if (!outs[k].dst) continue;
+    dev[k] = out_on_device ? outs[k].dst : ctx->map_stage.as<char>() + at;
+    at += n * outs[k].record_bytes;
+  }
+  DVO_HIP_TRY(ctx, pass(n, dev.data()));
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  for (size_t k = 0; k < outs.size() && !out_on_device; ++k)
+    if (outs[k].dst) DVO_HIP_TRY(ctx, hipMemcpyAsync(outs[k].dst, dev[k], n * outs[k].record_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *take = n;
+  return DVO_HIP_OK;
+}
+
 // dvo_hip_map_extract (with_colour false, rgba null) and dvo_hip_map_extract_colour
 int map_extract(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_points, float* xyzi, bool with_colour, uint32_t* rgba, uint32_t* counts_or_null,
                 uint64_t* keys_or_null, int out_on_device, size_t* n_points, const char* who) {
@@ -393,42 +419,17 @@ int map_extract(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_points, float
   if (!n_points || (max_points > 0 && (!xyzi || (with_colour && !rgba)))) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
   if (out_on_device && xyzi && reinterpret_cast<uintptr_t>(xyzi) % 16 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device xyzi must be 16-byte aligned");
   if (out_on_device && rgba && reinterpret_cast<uintptr_t>(rgba) % 4 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device rgba must be 4-byte aligned");
-  *n_points = 0;
-  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const MapTable t = map_table(map);
   unsigned long long c[kMapCounters];
-  // how many there are (and whether a voxel is over the limit), then the records: a host destination is staged for just that many
-  DVO_HIP_TRY(ctx, launch_map_extract(ctx->stream, t, 0, nullptr, nullptr, nullptr));
-  DVO_HIP_TRY(ctx, hipGetLastError());
-  int rc = read_map_counters(ctx, map, c);
+  const int rc = map_read_out(ctx, map, max_points, {{xyzi, 16}, {keys_or_null, 8}, {counts_or_null, 4}, {rgba, 4}}, out_on_device,
+                              [&](unsigned long long n, void* const* dev) {
+                                return launch_map_extract(ctx->stream, t, n, static_cast<float4*>(dev[0]), static_cast<uint32_t*>(dev[2]),
+                                                          static_cast<unsigned long long*>(dev[1]), static_cast<uint32_t*>(dev[3]));
+                              },
+                              c, n_points);
   if (rc != DVO_HIP_OK) return rc;
-  const unsigned long long occupied = c[kMapCntCursor], over = c[kMapCntOverLimit];
-  const size_t take = size_t(occupied < max_points ? occupied : max_points);
-  if (take > 0) {
-    float4* d_xyzi = reinterpret_cast<float4*>(xyzi);
-    uint32_t* d_counts = counts_or_null;
-    uint32_t* d_rgba = rgba;
-    unsigned long long* d_keys = reinterpret_cast<unsigned long long*>(keys_or_null);
-    if (!out_on_device) {
-      DVO_HIP_TRY(ctx, ctx->map_stage.reserve(take * 32));
-      d_rgba = rgba ? reinterpret_cast<uint32_t*>(ctx->map_stage.as<char>() + take * 28) : nullptr;
-      d_xyzi = ctx->map_stage.as<float4>();
-      d_keys = keys_or_null ? reinterpret_cast<unsigned long long*>(ctx->map_stage.as<char>() + take * 16) : nullptr;
-      d_counts = counts_or_null ? reinterpret_cast<uint32_t*>(ctx->map_stage.as<char>() + take * 24) : nullptr;
-    }
-    DVO_HIP_TRY(ctx, launch_map_extract_colour(ctx->stream, t, take, d_xyzi, d_counts, d_keys, d_rgba));
-    DVO_HIP_TRY(ctx, hipGetLastError());
-    if (!out_on_device) {
-      DVO_HIP_TRY(ctx, hipMemcpyAsync(xyzi, d_xyzi, take * 16, hipMemcpyDeviceToHost, ctx->stream));
-      if (keys_or_null) DVO_HIP_TRY(ctx, hipMemcpyAsync(keys_or_null, d_keys, take * 8, hipMemcpyDeviceToHost, ctx->stream));
-      if (counts_or_null) DVO_HIP_TRY(ctx, hipMemcpyAsync(counts_or_null, d_counts, take * 4, hipMemcpyDeviceToHost, ctx->stream));
-      if (rgba) DVO_HIP_TRY(ctx, hipMemcpyAsync(rgba, d_rgba, take * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  *n_points = take;
-  if (occupied > max_points) return fail(ctx, DVO_HIP_ERR_CAPACITY, who, "max_points is smaller than the number of occupied voxels (dvo_hip_map_stats)");
-  if (over != 0) return fail(ctx, DVO_HIP_ERR_CAPACITY, who, "a voxel holds more than 2^20 points; its sums may have wrapped");
+  if (c[kMapCntCursor] > max_points) return fail(ctx, DVO_HIP_ERR_CAPACITY, who, "max_points is smaller than the number of occupied voxels (dvo_hip_map_stats)");
+  if (c[kMapCntOverLimit] != 0) return fail(ctx, DVO_HIP_ERR_CAPACITY, who, "a voxel holds more than 2^20 points; its sums may have wrapped");
   return DVO_HIP_OK;
 }
 
@@ -538,26 +539,10 @@ int run_map_merge(dvo_hip_context* ctx, dvo_hip_map* dst, const std::vector<Merg
     e.first_block = at;
     at += int((s.count + 255) / 256);
   }
-  host[sources.size()].first_block = at;
-  const size_t bytes = host.size() * sizeof(MapMergeEntry);
-  DVO_HIP_TRY(ctx, ctx->map_tbl.reserve(bytes));
-  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->map_tbl.p, host.data(), bytes));
-  const unsigned long long candidates_before = dst->candidates, dropped_before = dst->dropped, unmatched_before = dst->unmatched;
-  launch_map_merge(ctx->stream, ctx->map_tbl.as<MapMergeEntry>(), int(sources.size()), at, map_table(dst), posed);
-  DVO_HIP_TRY(ctx, hipGetLastError());
-  unsigned long long after[kMapCounters];
-  const int rc = read_map_counters(ctx, dst, after);
+  const int rc = upload_block_table(ctx, ctx->map_tbl, host, at);
   if (rc != DVO_HIP_OK) return rc;
-  const unsigned long long dropped = after[kMapCntDropped] - dropped_before, unmatched = after[kMapCntUnmatched] - unmatched_before;
-  ctx->map_points += (long long)(after[kMapCntCandidates] - candidates_before - dropped);
-  ctx->map_dropped += (long long)dropped;
-  if (dropped != 0) return fail(ctx, DVO_HIP_ERR_CAPACITY, who, "the table dropped points (no free slot within the probe bound); the map keeps what it took");
-  if (unmatched != 0) {
-    ctx->err = std::string(who) + ": " + std::to_string(unmatched) +
-               " points found no voxel to leave (not the sub-map, or not the pose, that was merged?); the map keeps what it did";
-    return DVO_HIP_ERR_INVALID;
-  }
-  return DVO_HIP_OK;
+  launch_map_merge(ctx->stream, ctx->map_tbl.as<MapMergeEntry>(), int(sources.size()), at, map_table(dst), posed);
+  return finish_map_write(ctx, dst, 0, 0, who, "not the sub-map, or not the pose, that was merged?");
 }
 
 }  // namespace
@@ -623,39 +608,19 @@ int dvo_hip_map_export(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_record
   if (colour_records_or_null && !map->coloured) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no colour (dvo_hip_map_create_ex, DVO_HIP_MAP_COLOUR)");
   if (out_on_device && ((records && !aligned_to(records, 16)) || (colour_records_or_null && !aligned_to(colour_records_or_null, 16))))
     return fail(ctx, DVO_HIP_ERR_INVALID, who, "device records must be 16-byte aligned");
-  *n_records = 0;
-  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const MapTable t = map_table(map);
   unsigned long long c[kMapCounters];
-  // how many there are, then the records: a host destination is staged for just that many
-  DVO_HIP_TRY(ctx, launch_map_export(ctx->stream, t, 0, nullptr, nullptr));
-  DVO_HIP_TRY(ctx, hipGetLastError());
-  const int rc = read_map_counters(ctx, map, c);
+  const int rc = map_read_out(ctx, map, max_records, {{records, sizeof(MapSlot)}, {colour_records_or_null, sizeof(MapColourSlot)}}, out_on_device,
+                              [&](unsigned long long n, void* const* dev) {
+                                return launch_map_export(ctx->stream, t, n, static_cast<MapSlot*>(dev[0]), static_cast<MapColourSlot*>(dev[1]));
+                              },
+                              c, n_records);
   if (rc != DVO_HIP_OK) return rc;
-  const unsigned long long live = c[kMapCntCursor];
   if (!records) {                                            // (max_records is 0: the caller asks how many there are)
-    *n_records = size_t(live);
+    *n_records = size_t(c[kMapCntCursor]);
     return DVO_HIP_OK;
   }
-  const size_t take = size_t(live < max_records ? live : max_records);
-  if (take > 0) {
-    MapSlot* d_records = static_cast<MapSlot*>(records);
-    MapColourSlot* d_colour = static_cast<MapColourSlot*>(colour_records_or_null);
-    if (!out_on_device) {
-      DVO_HIP_TRY(ctx, ctx->map_stage.reserve(take * (sizeof(MapSlot) + sizeof(MapColourSlot))));
-      d_records = ctx->map_stage.as<MapSlot>();
-      d_colour = colour_records_or_null ? reinterpret_cast<MapColourSlot*>(ctx->map_stage.as<char>() + take * sizeof(MapSlot)) : nullptr;
-    }
-    DVO_HIP_TRY(ctx, launch_map_export(ctx->stream, t, take, d_records, d_colour));
-    DVO_HIP_TRY(ctx, hipGetLastError());
-    if (!out_on_device) {
-      DVO_HIP_TRY(ctx, hipMemcpyAsync(records, d_records, take * sizeof(MapSlot), hipMemcpyDeviceToHost, ctx->stream));
-      if (d_colour) DVO_HIP_TRY(ctx, hipMemcpyAsync(colour_records_or_null, d_colour, take * sizeof(MapColourSlot), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  *n_records = take;
-  if (live > max_records) return fail(ctx, DVO_HIP_ERR_CAPACITY, who, "max_records is smaller than the number of live voxels (dvo_hip_map_stats: occupied - vacant)");
+  if (c[kMapCntCursor] > max_records) return fail(ctx, DVO_HIP_ERR_CAPACITY, who, "max_records is smaller than the number of live voxels (dvo_hip_map_stats: occupied - vacant)");
   return DVO_HIP_OK;
 }
 
@@ -779,6 +744,16 @@ int upload_views(dvo_hip_context* ctx, int n_views, int width, int height, const
   return DVO_HIP_OK;
 }
 
+// n pairs of planes of `plane` bytes each in one block of the context, (re)allocated here: pair i's first plane at plane * 2i, its second behind it
+int reserve_plane_pairs(dvo_hip_context* ctx, DevBuf& block, size_t plane, int n, std::vector<float*>* first, std::vector<float*>* second) {
+  DVO_HIP_TRY(ctx, block.reserve(plane * 2 * size_t(n)));
+  for (int i = 0; i < n; ++i) {
+    first->push_back(reinterpret_cast<float*>(block.as<char>() + plane * (2 * size_t(i))));
+    second->push_back(reinterpret_cast<float*>(block.as<char>() + plane * (2 * size_t(i) + 1)));
+  }
+  return DVO_HIP_OK;
+}
+
 const MapView* render_views(const dvo_hip_context* ctx) { return ctx->render_tbl.as<MapView>(); }
 const RenderPlanes* render_outs(const dvo_hip_context* ctx, int n_views) {
   return reinterpret_cast<const RenderPlanes*>(ctx->render_tbl.as<char>() + size_t(n_views) * sizeof(MapView));
@@ -799,37 +774,39 @@ dvo_hip_render_params dvo_hip_render_params_default(void) {
   return p;
 }
 
-int dvo_hip_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float K[4], const double* poses,
-                       const dvo_hip_render_params* params, float* const* intensity_out, float* const* depth_out, int out_on_device) {
-  DVO_ENTER(ctx);
+namespace {
+
+// dvo_hip_map_render (first_out: float intensity planes) and -- colour -- dvo_hip_map_render_colour (first_out: uint32 rgba planes)
+int map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float* K, const double* poses,
+               const dvo_hip_render_params* params, bool colour, void* const* first_out, float* const* depth_out, int out_on_device, const char* who) {
   RenderArgs args;
-  const int rc0 = check_render(ctx, map, n_views, width, height, K, poses, params, &args, "map_render");
-  if (rc0 != DVO_HIP_OK) return rc0;
-  if (!intensity_out || !depth_out) return fail(ctx, DVO_HIP_ERR_INVALID, "map_render: bad argument");
+  int rc = check_render(ctx, map, n_views, width, height, K, poses, params, &args, who);
+  if (rc != DVO_HIP_OK) return rc;
+  if (colour && !map->coloured) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no colour (dvo_hip_map_create_ex, DVO_HIP_MAP_COLOUR)");
+  if (!first_out || !depth_out) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
   for (int i = 0; i < n_views; ++i) {
-    if (!intensity_out[i] || !depth_out[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "map_render: null output");
-    if (out_on_device && (!aligned_to(intensity_out[i], 16) || !aligned_to(depth_out[i], 16)))
-      return fail(ctx, DVO_HIP_ERR_INVALID, "map_render: a device plane must be 16-byte aligned");
+    if (!first_out[i] || !depth_out[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null output");
+    if (out_on_device && (!aligned_to(first_out[i], 16) || !aligned_to(depth_out[i], 16)))
+      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device plane must be 16-byte aligned");
   }
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t pixels = size_t(width) * size_t(height), plane = (pixels * 4 + 15) & ~size_t(15);
+  // (RenderPlanes::I holds the address of the uint32 rgba plane of a colour view: k_render_resolve stores the bits as they are)
   std::vector<float*> si, sz;
-  if (!out_on_device) {
-    DVO_HIP_TRY(ctx, ctx->map_stage.reserve(plane * 2 * size_t(n_views)));
-    for (int i = 0; i < n_views; ++i) {
-      si.push_back(reinterpret_cast<float*>(ctx->map_stage.as<char>() + plane * (2 * size_t(i))));
-      sz.push_back(reinterpret_cast<float*>(ctx->map_stage.as<char>() + plane * (2 * size_t(i) + 1)));
-    }
+  for (int i = 0; i < n_views && out_on_device; ++i) {
+    si.push_back(static_cast<float*>(first_out[i]));
+    sz.push_back(depth_out[i]);
   }
-  const int rc = upload_views(ctx, n_views, width, height, K, poses, out_on_device ? intensity_out : si.data(), out_on_device ? depth_out : sz.data());
+  if (!out_on_device) rc = reserve_plane_pairs(ctx, ctx->map_stage, plane, n_views, &si, &sz);
+  if (rc == DVO_HIP_OK) rc = upload_views(ctx, n_views, width, height, K, poses, si.data(), sz.data());
   if (rc != DVO_HIP_OK) return rc;
   launch_map_render(ctx->stream, map_table(map), render_views(ctx), render_outs(ctx, n_views), n_views, (long long)pixels, args,
-                    ctx->render_zbuf.as<unsigned long long>());
+                    ctx->render_zbuf.as<unsigned long long>(), colour);
   DVO_HIP_TRY(ctx, hipGetLastError());
   ctx->map_renders += n_views;
   if (!out_on_device) {
     for (int i = 0; i < n_views; ++i) {
-      DVO_HIP_TRY(ctx, hipMemcpyAsync(intensity_out[i], si[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(first_out[i], si[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
       DVO_HIP_TRY(ctx, hipMemcpyAsync(depth_out[i], sz[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -837,48 +814,20 @@ int dvo_hip_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int 
   return DVO_HIP_OK;
 }
 
+}  // namespace
+
+int dvo_hip_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float K[4], const double* poses,
+                       const dvo_hip_render_params* params, float* const* intensity_out, float* const* depth_out, int out_on_device) {
+  DVO_ENTER(ctx);
+  return map_render(ctx, map, n_views, width, height, K, poses, params, false, reinterpret_cast<void* const*>(intensity_out), depth_out, out_on_device,
+                    "map_render");
+}
+
 int dvo_hip_map_render_colour(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float K[4], const double* poses,
                               const dvo_hip_render_params* params, uint32_t* const* rgba_out, float* const* depth_out, int out_on_device) {
   DVO_ENTER(ctx);
-  const char* who = "map_render_colour";
-  RenderArgs args;
-  const int rc0 = check_render(ctx, map, n_views, width, height, K, poses, params, &args, who);
-  if (rc0 != DVO_HIP_OK) return rc0;
-  if (!map->coloured) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no colour (dvo_hip_map_create_ex, DVO_HIP_MAP_COLOUR)");
-  if (!rgba_out || !depth_out) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
-  for (int i = 0; i < n_views; ++i) {
-    if (!rgba_out[i] || !depth_out[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null output");
-    if (out_on_device && (!aligned_to(rgba_out[i], 16) || !aligned_to(depth_out[i], 16)))
-      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device plane must be 16-byte aligned");
-  }
-  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t pixels = size_t(width) * size_t(height), plane = (pixels * 4 + 15) & ~size_t(15);
-  // (RenderPlanes::I holds the address of the uint32 rgba plane of a colour view: k_render_resolve stores the bits as they are)
-  std::vector<float*> sc, sz;
-  for (int i = 0; i < n_views; ++i) {
-    if (out_on_device) {
-      sc.push_back(reinterpret_cast<float*>(rgba_out[i]));
-      sz.push_back(depth_out[i]);
-    } else {
-      if (i == 0) DVO_HIP_TRY(ctx, ctx->map_stage.reserve(plane * 2 * size_t(n_views)));
-      sc.push_back(reinterpret_cast<float*>(ctx->map_stage.as<char>() + plane * (2 * size_t(i))));
-      sz.push_back(reinterpret_cast<float*>(ctx->map_stage.as<char>() + plane * (2 * size_t(i) + 1)));
-    }
-  }
-  const int rc = upload_views(ctx, n_views, width, height, K, poses, sc.data(), sz.data());
-  if (rc != DVO_HIP_OK) return rc;
-  launch_map_render_colour(ctx->stream, map_table(map), render_views(ctx), render_outs(ctx, n_views), n_views, (long long)pixels, args,
-                           ctx->render_zbuf.as<unsigned long long>());
-  DVO_HIP_TRY(ctx, hipGetLastError());
-  ctx->map_renders += n_views;
-  if (!out_on_device) {
-    for (int i = 0; i < n_views; ++i) {
-      DVO_HIP_TRY(ctx, hipMemcpyAsync(rgba_out[i], sc[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
-      DVO_HIP_TRY(ctx, hipMemcpyAsync(depth_out[i], sz[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return DVO_HIP_OK;
+  return map_render(ctx, map, n_views, width, height, K, poses, params, true, reinterpret_cast<void* const*>(rgba_out), depth_out, out_on_device,
+                    "map_render_colour");
 }
 
 int dvo_hip_map_render_frames(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_frame* const* frames, const double* poses,
@@ -887,13 +836,13 @@ int dvo_hip_map_render_frames(dvo_hip_context* ctx, dvo_hip_map* map, int n_fram
   const char* who = "map_render_frames";
   int rc = check_map(ctx, map, who);
   if (rc != DVO_HIP_OK) return rc;
-  if (n_frames < 1 || !frames || !poses) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  rc = check_frame_count(ctx, n_frames, frames, who, poses != nullptr);
+  if (rc != DVO_HIP_OK) return rc;
   if (flags & DVO_HIP_INGEST_DEFER) return fail(ctx, DVO_HIP_ERR_INVALID, who, "DVO_HIP_INGEST_DEFER: a render is not recorded");
   for (int i = 0; i < n_frames; ++i) {
     const dvo_hip_frame* f = frames[i];
-    if (!f) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null frame");
-    if (std::find(ctx->cameras.begin(), ctx->cameras.end(), f->cam) == ctx->cameras.end())
-      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame of another context");
+    rc = check_frame(ctx, f, who, /*own_context=*/true);
+    if (rc != DVO_HIP_OK) return rc;
     if (f->lens_on || f->rig_on)
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a lens or a depth rig takes raw sensor planes; rendered planes are rectified and registered already");
   }
@@ -906,15 +855,10 @@ int dvo_hip_map_render_frames(dvo_hip_context* ctx, dvo_hip_map* map, int n_fram
   // the planes the frames ingest: scratch of the context.  Its last readers are the builds of the previous call's frames, which the main
   // stream waits for at the end of that call
   const size_t pixels = size_t(width) * size_t(height), plane = (pixels * 4 + 255) & ~size_t(255);
-  DVO_HIP_TRY(ctx, ctx->render_planes.reserve(plane * 2 * size_t(n_frames)));
   std::vector<float*> pi, pz;
-  std::vector<const void*> ci, cz;
-  for (int i = 0; i < n_frames; ++i) {
-    pi.push_back(reinterpret_cast<float*>(ctx->render_planes.as<char>() + plane * (2 * size_t(i))));
-    pz.push_back(reinterpret_cast<float*>(ctx->render_planes.as<char>() + plane * (2 * size_t(i) + 1)));
-    ci.push_back(pi.back());
-    cz.push_back(pz.back());
-  }
+  rc = reserve_plane_pairs(ctx, ctx->render_planes, plane, n_frames, &pi, &pz);
+  if (rc != DVO_HIP_OK) return rc;
+  const std::vector<const void*> ci(pi.begin(), pi.end()), cz(pz.begin(), pz.end());
   IngestSource src{ci.data(), DVO_HIP_PIXEL_F32, 0, cz.data(), 1.0f, DVO_HIP_DEPTH_F32, 0};
   IngestSource probe = src;
   rc = check_ingest(ctx, who, n_frames, frames, &probe, /*plain_ok=*/true, role, cfg);   // (role, cfg, one camera: before anything is launched)
@@ -922,7 +866,7 @@ int dvo_hip_map_render_frames(dvo_hip_context* ctx, dvo_hip_map* map, int n_fram
   rc = upload_views(ctx, n_frames, width, height, cam->K[0], poses, pi.data(), pz.data());
   if (rc != DVO_HIP_OK) return rc;
   launch_map_render(ctx->stream, map_table(map), render_views(ctx), render_outs(ctx, n_frames), n_frames, (long long)pixels, args,
-                    ctx->render_zbuf.as<unsigned long long>());
+                    ctx->render_zbuf.as<unsigned long long>(), /*colour=*/false);
   DVO_HIP_TRY(ctx, hipGetLastError());
   DVO_HIP_TRY(ctx, hipEventRecord(ctx->render_done, ctx->stream));
   DVO_HIP_TRY(ctx, hipStreamWaitEvent(ctx->build_stream, ctx->render_done, 0));
@@ -942,13 +886,9 @@ int dvo_hip_time_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views,
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t pixels = size_t(width) * size_t(height), plane = (pixels * 4 + 255) & ~size_t(255);
   DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->build_stream));   // (the scratch planes may still be read by an ingest)
-  DVO_HIP_TRY(ctx, ctx->render_planes.reserve(plane * 2 * size_t(n_views)));
   std::vector<float*> pi, pz;
-  for (int i = 0; i < n_views; ++i) {
-    pi.push_back(reinterpret_cast<float*>(ctx->render_planes.as<char>() + plane * (2 * size_t(i))));
-    pz.push_back(reinterpret_cast<float*>(ctx->render_planes.as<char>() + plane * (2 * size_t(i) + 1)));
-  }
-  rc = upload_views(ctx, n_views, width, height, K, poses, pi.data(), pz.data());
+  rc = reserve_plane_pairs(ctx, ctx->render_planes, plane, n_views, &pi, &pz);
+  if (rc == DVO_HIP_OK) rc = upload_views(ctx, n_views, width, height, K, poses, pi.data(), pz.data());
   if (rc != DVO_HIP_OK) return rc;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   hipError_t e = hipSuccess;
@@ -961,9 +901,9 @@ int dvo_hip_time_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views,
     e = hipEventRecord(ev[0], ctx->stream);
     launch_render_fill(ctx->stream, zbuf, (long long)pixels * n_views);
     if (e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
-    launch_render_splat(ctx->stream, table, render_views(ctx), n_views, args, zbuf);
+    launch_render_splat(ctx->stream, table, render_views(ctx), n_views, args, zbuf, /*colour=*/false);
     if (e == hipSuccess) e = hipEventRecord(ev[2], ctx->stream);
-    launch_render_resolve(ctx->stream, zbuf, render_outs(ctx, n_views), n_views, (long long)pixels);
+    launch_render_resolve(ctx->stream, zbuf, render_outs(ctx, n_views), n_views, (long long)pixels, /*colour=*/false);
     if (e == hipSuccess) e = hipEventRecord(ev[3], ctx->stream);
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipEventSynchronize(ev[3]);

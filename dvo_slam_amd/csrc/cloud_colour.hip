@@ -4,31 +4,21 @@
 //
 // k_colour_pack runs over planes x pixels in one launch: a lane owns one pixel, a wavefront 64 consecutive pixels in raster order, a
 // workgroup 256; planes of different sizes share the launch, a workgroup finds its plane by bisecting the table's first_block column
-// (as k_map_insert does, cloud_map.hip).  A lane reads its 3 or 4 bytes with byte loads -- a 3-byte pixel is aligned to nothing, and
+// (map_device.h, as k_map_insert does).  A lane reads its 3 or 4 bytes with byte loads -- a 3-byte pixel is aligned to nothing, and
 // this runs once per keyframe, not per match -- and stores one dword, coalesced.
 // k_colour_level: a lane per pixel of the level, the 2^L x 2^L block of level 0 read with dword loads (the rows of an odd-width plane are
 // not 16-byte aligned), one dword stored.  No LDS, no barriers, no atomics, 256-thread workgroups.
 #include "global_ptr.h"
 #include "launch.h"
 #include "cloud_colour.h"
+#include "map_device.h"
 
 namespace dvo_hip {
 
 namespace {
 
-// the plane that owns workgroup b: first_block is strictly increasing (every plane has at least one pixel), tbl[n_planes] ends the list
-__device__ __forceinline__ int colour_plane_of(const ColourPlane* __restrict__ tbl, int n_planes, int b) {
-  int lo = 0, hi = n_planes;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (tbl[mid].first_block <= b) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(256) void k_colour_pack(const ColourPlane* __restrict__ tbl, int n_planes, int pixel_format) {
-  const ColourPlane& f = tbl[colour_plane_of(tbl, n_planes, int(blockIdx.x))];
+  const ColourPlane& f = tbl[map_frame_of(tbl, n_planes, int(blockIdx.x))];
   const int i = (int(blockIdx.x) - f.first_block) * 256 + int(threadIdx.x);
   if (i >= f.w * f.h) return;                                  // (i < w * h: inside both planes)
   const int u = i % f.w, v = i / f.w, channels = pixel_channels(pixel_format);

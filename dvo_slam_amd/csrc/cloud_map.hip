@@ -240,53 +240,40 @@ __global__ __launch_bounds__(256) void k_map_clear(MapTable m) {
   if (blockIdx.x == 0 && threadIdx.x < kMapCounters) m.counters[threadIdx.x] = 0ull;
 }
 
-int table_grid(unsigned long long capacity) {
-  const unsigned long long blocks = (capacity + 255) / 256;
-  return int(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
-}
-
 }  // namespace
 
 void launch_world_points(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, float min_depth, float max_depth) {
   k_world_points<<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, min_depth, max_depth);
 }
 
-void launch_map_insert(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth) {
-  k_map_insert<DVO_MAP_COMBINE_RUNS != 0, false, false><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
-}
-
-void launch_map_update(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth) {
-  k_map_insert<DVO_MAP_COMBINE_RUNS != 0, true, false><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
-}
-
-void launch_map_insert_colour(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth) {
-  k_map_insert<DVO_MAP_COMBINE_RUNS != 0, false, true><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
-}
-
-void launch_map_update_colour(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth) {
-  k_map_insert<DVO_MAP_COMBINE_RUNS != 0, true, true><<<dim3(total_blocks), dim3(256), 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+void launch_map_insert(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth, bool mixed) {
+  const dim3 grid(total_blocks), block(256);
+  constexpr bool kCombine = DVO_MAP_COMBINE_RUNS != 0;
+  if (mixed) {
+    if (m.colour) k_map_insert<kCombine, true, true><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+    else k_map_insert<kCombine, true, false><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+  } else {
+    if (m.colour) k_map_insert<kCombine, false, true><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+    else k_map_insert<kCombine, false, false><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+  }
 }
 
 void launch_map_rehash(hipStream_t s, const MapTable& from, const MapTable& to) {
-  k_map_clear<<<dim3(table_grid(to.capacity)), dim3(256), 0, s>>>(to);
-  k_map_rehash<<<dim3(table_grid(from.capacity)), dim3(256), 0, s>>>(from, to);
+  k_map_clear<<<dim3(stride_grid(to.capacity)), dim3(256), 0, s>>>(to);
+  k_map_rehash<<<dim3(stride_grid(from.capacity)), dim3(256), 0, s>>>(from, to);
 }
 
 bool map_insert_combines_runs() { return DVO_MAP_COMBINE_RUNS != 0; }
 
-hipError_t launch_map_extract(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys) {
-  return launch_map_extract_colour(s, m, max_points, xyzi, counts, keys, nullptr);
-}
-
-hipError_t launch_map_extract_colour(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys,
-                                     uint32_t* rgba) {
+hipError_t launch_map_extract(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys,
+                              uint32_t* rgba) {
   static_assert(kMapCntCursor == kMapCntOverLimit + 1 && kMapCntVacant == kMapCntOverLimit + 2, "what a pass counts lies together");
   const hipError_t e = hipMemsetAsync(m.counters + kMapCntOverLimit, 0, 3 * sizeof(unsigned long long), s);
   if (e != hipSuccess) return e;
-  k_map_extract<<<dim3(table_grid(m.capacity)), dim3(256), 0, s>>>(m, max_points, xyzi, counts, keys, m.colour ? rgba : nullptr);
+  k_map_extract<<<dim3(stride_grid(m.capacity)), dim3(256), 0, s>>>(m, max_points, xyzi, counts, keys, m.colour ? rgba : nullptr);
   return hipSuccess;
 }
 
-void launch_map_clear(hipStream_t s, const MapTable& m) { k_map_clear<<<dim3(table_grid(m.capacity)), dim3(256), 0, s>>>(m); }
+void launch_map_clear(hipStream_t s, const MapTable& m) { k_map_clear<<<dim3(stride_grid(m.capacity)), dim3(256), 0, s>>>(m); }
 
 }  // namespace dvo_hip

@@ -77,28 +77,29 @@ void launch_rectify(hipStream_t s, const RectifyPtrs* tbl, int n_frames, const R
 void launch_depth_register(hipStream_t s, const DepthRigPtrs* tbl, int n_frames, const DepthRigArgs& a, bool depth_f32, int max_workgroups,
                            bool stream_nt);
 
+// the grid of a kernel that walks `items` elements with a grid stride, 256 per workgroup: 1 .. 8192 workgroups
+inline int stride_grid(unsigned long long items) {
+  const unsigned long long blocks = (items + 255) / 256;
+  return int(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
+}
+
 // cloud_map.hip: the keyframe map (cloud_map.h).  tbl: n_frames entries and one more whose first_block is total_blocks, the launch's grid.
 // launch_world_points: every frame's organised cloud into MapFrame::out.  launch_map_insert: every usable pixel into the table m (with the
-// wavefront's run folding unless the library was built with DVO_MAP_COMBINE_RUNS=0: map_insert_combines_runs).  launch_map_extract: the
-// occupied slots into xyzi / counts / keys (null: not wanted; xyzi null: count only), at most max_points; zeroes and then sets the
-// counters kMapCntCursor (live slots seen), kMapCntOverLimit and -- counting only -- kMapCntVacant.  launch_map_clear: keys empty, sums
-// and all counters zero.  launch_map_update: launch_map_insert over frames that carry signs (MapFrame::sign): those with -1 are removed.
+// wavefront's run folding unless the library was built with DVO_MAP_COMBINE_RUNS=0: map_insert_combines_runs); mixed: the frames carry
+// signs (MapFrame::sign), those with -1 are removed.  launch_map_extract: the occupied slots into xyzi / counts / keys / rgba (null: not
+// wanted; xyzi null: count only), at most max_points; zeroes and then sets the counters kMapCntCursor (live slots seen), kMapCntOverLimit
+// and -- counting only -- kMapCntVacant.  launch_map_clear: keys empty, sums and all counters zero.
 // launch_map_rehash: clears `to` (its counters too) and places every live slot of `from` in it; to's kMapCntOccupied and kMapCntDropped
 // (records without a slot) say how that went.
+// A COLOURED map (m.colour is its side table, every MapFrame carries a plane of packed pixels; cloud_colour.h) takes the same launches:
+// they carry the colour sums along, resp. handle the side table, wherever the table has one; rgba is written for a coloured map only.
 void launch_world_points(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, float min_depth, float max_depth);
-void launch_map_insert(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth);
-void launch_map_update(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth);
+void launch_map_insert(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth, bool mixed);
 void launch_map_rehash(hipStream_t s, const MapTable& from, const MapTable& to);
 bool map_insert_combines_runs();
-hipError_t launch_map_extract(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys);
+hipError_t launch_map_extract(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys,
+                              uint32_t* rgba);
 void launch_map_clear(hipStream_t s, const MapTable& m);
-// ... of a COLOURED map (m.colour is its side table, every MapFrame carries a plane of packed pixels; cloud_colour.h): the same launches
-// with the colour sums carried along; launch_map_extract_colour writes the colour records into rgba as well (null: not wanted).
-// launch_map_clear and launch_map_rehash handle the side table wherever the table has one.
-void launch_map_insert_colour(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth);
-void launch_map_update_colour(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth);
-hipError_t launch_map_extract_colour(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys,
-                                     uint32_t* rgba);
 
 // map_merge.hip: voxel tables and record arrays into and out of a map (cloud_map.h, Merge).  tbl: n_entries entries and one more whose
 // first_block is total_blocks, the launch's grid.  launch_map_merge: every live record of every entry into (sign +1) or out of (-1) the
@@ -117,16 +118,13 @@ void launch_colour_level(hipStream_t s, const uint32_t* plane, int pitch, int sh
 // map_render.hip: views of the keyframe map (map_render.h).  n_views views of `pixels` = w * h pixels each; zbuf: pixels * n_views
 // elements.  launch_render_fill: every element ~0.  launch_render_splat: every voxel of the table into every view, an atomic minimum per
 // covered pixel.  launch_render_resolve: the z-buffers into the planes out[view].  launch_map_render: the three, in that order.
+// colour: a colour view of a coloured map (cloud_colour.h): the element's low half is the voxel's colour, out[view].I holds the address
+// of the uint32 rgba plane
 void launch_render_fill(hipStream_t s, unsigned long long* zbuf, long long elements);
-void launch_render_splat(hipStream_t s, const MapTable& m, const MapView* views, int n_views, const RenderArgs& a, unsigned long long* zbuf);
-void launch_render_resolve(hipStream_t s, const unsigned long long* zbuf, const RenderPlanes* out, int n_views, long long pixels);
+void launch_render_splat(hipStream_t s, const MapTable& m, const MapView* views, int n_views, const RenderArgs& a, unsigned long long* zbuf, bool colour);
+void launch_render_resolve(hipStream_t s, const unsigned long long* zbuf, const RenderPlanes* out, int n_views, long long pixels, bool colour);
 void launch_map_render(hipStream_t s, const MapTable& m, const MapView* views, const RenderPlanes* out, int n_views, long long pixels, const RenderArgs& a,
-                       unsigned long long* zbuf);
-// ... of a colour view (cloud_colour.h): the element's low half is the voxel's colour, out[view].I holds the address of the uint32 rgba plane
-void launch_render_splat_colour(hipStream_t s, const MapTable& m, const MapView* views, int n_views, const RenderArgs& a, unsigned long long* zbuf);
-void launch_render_resolve_colour(hipStream_t s, const unsigned long long* zbuf, const RenderPlanes* out, int n_views, long long pixels);
-void launch_map_render_colour(hipStream_t s, const MapTable& m, const MapView* views, const RenderPlanes* out, int n_views, long long pixels,
-                              const RenderArgs& a, unsigned long long* zbuf);
+                       unsigned long long* zbuf, bool colour);
 bool map_render_preloads();
 
 // pose_graph.hip: the stages of the pose-graph optimiser (pose_graph.h), kPgBlock edges or vertices per workgroup.  *_partials: one

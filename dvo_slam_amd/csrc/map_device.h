@@ -1,11 +1,11 @@
-// map_device.h -- what the kernels of the keyframe map share on the device (cloud_map.hip, map_merge.hip): which entry of a launch's table
-// a workgroup belongs to, and the per-wavefront counter updates.
+// map_device.h -- what the kernels of the keyframe map share on the device (cloud_map.hip, map_merge.hip, cloud_colour.hip): which entry of
+// a launch's table a workgroup belongs to, and the per-wavefront counter updates.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace dvo_hip {
 
-// the entry (a MapFrame, a MapMergeEntry) that owns workgroup b: first_block is strictly increasing (every entry has at least one
+// the entry (a MapFrame, a MapMergeEntry, a ColourPlane) that owns workgroup b: first_block is strictly increasing (every entry has at least one
 // pixel or record), tbl[n_entries] ends the list
 template <typename Entry>
 __device__ __forceinline__ int map_frame_of(const Entry* __restrict__ tbl, int n_entries, int b) {

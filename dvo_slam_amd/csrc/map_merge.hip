@@ -149,11 +149,6 @@ __global__ __launch_bounds__(256) void k_map_export(MapTable m, unsigned long lo
   }
 }
 
-int export_grid(unsigned long long capacity) {
-  const unsigned long long blocks = (capacity + 255) / 256;
-  return int(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
-}
-
 }  // namespace
 
 void launch_map_merge(hipStream_t s, const MapMergeEntry* tbl, int n_entries, int total_blocks, const MapTable& m, bool posed) {
@@ -170,7 +165,7 @@ void launch_map_merge(hipStream_t s, const MapMergeEntry* tbl, int n_entries, in
 hipError_t launch_map_export(hipStream_t s, const MapTable& m, unsigned long long max_records, MapSlot* records, MapColourSlot* colour) {
   const hipError_t e = hipMemsetAsync(m.counters + kMapCntCursor, 0, sizeof(unsigned long long), s);
   if (e != hipSuccess) return e;
-  k_map_export<<<dim3(export_grid(m.capacity)), dim3(256), 0, s>>>(m, max_records, records, m.colour ? colour : nullptr);
+  k_map_export<<<dim3(stride_grid(m.capacity)), dim3(256), 0, s>>>(m, max_records, records, m.colour ? colour : nullptr);
   return hipSuccess;
 }
 

@@ -114,45 +114,29 @@ dim3 view_grid(long long items, int n_views) {
   return dim3(unsigned(blocks), unsigned(rows));
 }
 
-int stride_grid(long long items) {
-  const long long blocks = (items + 255) / 256;
-  return int(blocks < 1 ? 1 : blocks > 8192 ? 8192 : blocks);
-}
-
 }  // namespace
 
 void launch_render_fill(hipStream_t s, unsigned long long* zbuf, long long elements) {
   k_render_fill<<<dim3(stride_grid(elements >> 1)), dim3(256), 0, s>>>(zbuf, elements);
 }
 
-void launch_render_splat(hipStream_t s, const MapTable& m, const MapView* views, int n_views, const RenderArgs& a, unsigned long long* zbuf) {
-  k_map_render<DVO_RENDER_PRELOAD != 0, false><<<view_grid((long long)m.capacity, n_views), dim3(256), 0, s>>>(m, views, n_views, a, zbuf);
+void launch_render_splat(hipStream_t s, const MapTable& m, const MapView* views, int n_views, const RenderArgs& a, unsigned long long* zbuf, bool colour) {
+  const dim3 grid = view_grid((long long)m.capacity, n_views), block(256);
+  if (colour) k_map_render<DVO_RENDER_PRELOAD != 0, true><<<grid, block, 0, s>>>(m, views, n_views, a, zbuf);
+  else k_map_render<DVO_RENDER_PRELOAD != 0, false><<<grid, block, 0, s>>>(m, views, n_views, a, zbuf);
 }
 
-void launch_render_resolve(hipStream_t s, const unsigned long long* zbuf, const RenderPlanes* out, int n_views, long long pixels) {
-  k_render_resolve<false><<<view_grid(pixels, n_views), dim3(256), 0, s>>>(zbuf, out, n_views, pixels);
+void launch_render_resolve(hipStream_t s, const unsigned long long* zbuf, const RenderPlanes* out, int n_views, long long pixels, bool colour) {
+  const dim3 grid = view_grid(pixels, n_views), block(256);
+  if (colour) k_render_resolve<true><<<grid, block, 0, s>>>(zbuf, out, n_views, pixels);
+  else k_render_resolve<false><<<grid, block, 0, s>>>(zbuf, out, n_views, pixels);
 }
 
 void launch_map_render(hipStream_t s, const MapTable& m, const MapView* views, const RenderPlanes* out, int n_views, long long pixels, const RenderArgs& a,
-                       unsigned long long* zbuf) {
+                       unsigned long long* zbuf, bool colour) {
   launch_render_fill(s, zbuf, pixels * n_views);
-  launch_render_splat(s, m, views, n_views, a, zbuf);
-  launch_render_resolve(s, zbuf, out, n_views, pixels);
-}
-
-void launch_render_splat_colour(hipStream_t s, const MapTable& m, const MapView* views, int n_views, const RenderArgs& a, unsigned long long* zbuf) {
-  k_map_render<DVO_RENDER_PRELOAD != 0, true><<<view_grid((long long)m.capacity, n_views), dim3(256), 0, s>>>(m, views, n_views, a, zbuf);
-}
-
-void launch_render_resolve_colour(hipStream_t s, const unsigned long long* zbuf, const RenderPlanes* out, int n_views, long long pixels) {
-  k_render_resolve<true><<<view_grid(pixels, n_views), dim3(256), 0, s>>>(zbuf, out, n_views, pixels);
-}
-
-void launch_map_render_colour(hipStream_t s, const MapTable& m, const MapView* views, const RenderPlanes* out, int n_views, long long pixels,
-                              const RenderArgs& a, unsigned long long* zbuf) {
-  launch_render_fill(s, zbuf, pixels * n_views);
-  launch_render_splat_colour(s, m, views, n_views, a, zbuf);
-  launch_render_resolve_colour(s, zbuf, out, n_views, pixels);
+  launch_render_splat(s, m, views, n_views, a, zbuf, colour);
+  launch_render_resolve(s, zbuf, out, n_views, pixels, colour);
 }
 
 bool map_render_preloads() { return DVO_RENDER_PRELOAD != 0; }

@@ -709,22 +709,58 @@ def clear_colour_batch(pyramids):
         p._colour = None
 
 
+def _pose_array(poses, n, who, per="pyramid", counted="pyramids", maps="camera -> world", some=False, finite=False):
+    """poses as a contiguous [n, 4, 4] float64 array (n None: as many as there are; one 4 x 4 matrix is one pose), or ValueError /
+    TypeError.  per, counted, maps: what a pose belongs to, what n counts and what a pose maps, for the messages; some: an empty array
+    is refused as a shape; finite: an entry that is not finite is refused"""
+    try:
+        T = np.ascontiguousarray(poses, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError("%s: poses must be real numbers, one 4 x 4 matrix per %s" % (who, per))
+    if T.ndim == 2 and n in (None, 1):
+        T = T[None]
+    if T.ndim != 3 or T.shape[1:] != (4, 4) or (some and T.shape[0] < 1):
+        raise ValueError("%s: a pose is a 4 x 4 matrix (%s), got shape %s" % (who, maps, T.shape))
+    if n is not None and T.shape[0] != n:
+        raise ValueError("%s: %d %s but %d poses" % (who, n, counted, T.shape[0]))
+    if finite and not np.all(np.isfinite(T)):
+        raise ValueError("%s: a pose has an entry that is not finite" % who)
+    return T
+
+
+_VIEW_POSES = dict(per="view", some=True)                                                             # KeyframeMap.render*, render_into
+_MERGE_POSES = dict(per="source", counted="sources", maps="source -> destination", finite=True)      # KeyframeMap.merge, move_submaps, absorb
+
+
+_MAP_RECORD, _MAP_COLOUR_RECORD = np.dtype(_lib.MAP_RECORD), np.dtype(_lib.MAP_COLOUR_RECORD)
+_TORCH_DTYPES = {}                                           # numpy dtype -> torch dtype of the same bits, filled at the first device array
+
+
+def _out_array(ctx, shape, dtype, device):
+    """an uninitialised output array of a C-ABI call: a numpy array or -- device -- a torch tensor on the context's GPU, which has the
+    signed type of the same width for an unsigned one and int32 words for a record type: the same bits"""
+    if not device:
+        return np.empty(shape, dtype)
+    import torch
+    if not _TORCH_DTYPES:
+        _TORCH_DTYPES.update({np.dtype(np.float32): torch.float32, np.dtype(np.uint32): torch.int32, np.dtype(np.uint64): torch.int64})
+    dt = np.dtype(dtype)
+    if dt.fields:
+        shape, dt = (shape, dt.itemsize // 4), np.dtype(np.uint32)
+    return torch.empty(shape, dtype=_TORCH_DTYPES[dt], device="cuda:%d" % ctx.device)
+
+
+def _address(a):
+    return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+
 def _map_frames_args(pyramids, poses, level, min_depth, max_depth, who):
     """(n, poses as a contiguous [n, 4, 4] float64 array) of a keyframe-map call, or ValueError / TypeError: nothing reaches the library
     with a pose that is not 4 x 4, mismatched lengths, a level a pyramid does not have or an empty depth range."""
     n = len(pyramids)
     if n < 1:
         raise ValueError("%s: no pyramids" % who)
-    try:
-        T = np.ascontiguousarray(poses, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise TypeError("%s: poses must be real numbers, one 4 x 4 matrix per pyramid" % who)
-    if T.ndim == 2 and n == 1:
-        T = T[None]
-    if T.ndim != 3 or T.shape[1:] != (4, 4):
-        raise ValueError("%s: a pose is a 4 x 4 matrix (camera -> world), got shape %s" % (who, T.shape))
-    if T.shape[0] != n:
-        raise ValueError("%s: %d pyramids but %d poses" % (who, n, T.shape[0]))
+    T = _pose_array(poses, n, who)
     if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
         raise TypeError("%s: level must be an integer" % who)
     for p in pyramids:
@@ -748,15 +784,10 @@ def world_points_batch(pyramids, poses, level=0, min_depth=0.0, max_depth=float(
         w, h = C.c_int(), C.c_int()
         ctx.check(ctx._lib.dvo_hip_frame_info(p.ptr, level, C.byref(w), C.byref(h), None))
         shapes.append((h.value, w.value, 4))
-    if device:
-        import torch
-        out = [torch.empty(s, dtype=torch.float32, device="cuda:%d" % ctx.device) for s in shapes]
-        ptrs = device_pointer_array([t.data_ptr() for t in out])
-    else:
-        out = [np.empty(s, np.float32) for s in shapes]
-        ptrs = device_pointer_array([a.ctypes.data for a in out])
+    out = [_out_array(ctx, s, np.float32, device) for s in shapes]
     ctx.check(ctx._lib.dvo_hip_frames_world_points(ctx.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)), int(level),
-                                                   float(min_depth), float(max_depth), ptrs, 1 if device else 0))
+                                                   float(min_depth), float(max_depth), device_pointer_array([_address(a) for a in out]),
+                                                   1 if device else 0))
     return out
 
 
@@ -799,21 +830,6 @@ def render_params_struct(**params):
     return out
 
 
-def _render_poses(poses, n, who):
-    """poses as a contiguous [n, 4, 4] float64 array (n None: as many as there are; one 4 x 4 matrix is one view)"""
-    try:
-        T = np.ascontiguousarray(poses, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise TypeError("%s: poses must be real numbers, one 4 x 4 matrix per view" % who)
-    if T.ndim == 2 and n in (None, 1):
-        T = T[None]
-    if T.ndim != 3 or T.shape[1:] != (4, 4) or T.shape[0] < 1:
-        raise ValueError("%s: a pose is a 4 x 4 matrix (camera -> world), got shape %s" % (who, T.shape))
-    if n is not None and T.shape[0] != n:
-        raise ValueError("%s: %d pyramids but %d poses" % (who, n, T.shape[0]))
-    return T
-
-
 def _render_view_args(K, width, height, poses, who):
     """(K as float32[4], width, height, poses [n, 4, 4]) of KeyframeMap.render, or ValueError / TypeError"""
     for name, v in (("width", width), ("height", height)):
@@ -829,27 +845,10 @@ def _render_view_args(K, width, height, poses, who):
         raise ValueError("%s: K is fx, fy, ox, oy, got shape %s" % (who, K.shape))
     if not np.all(np.isfinite(K)) or not (K[0] > 0 and K[1] > 0):
         raise ValueError("%s: K must be finite with fx > 0 and fy > 0" % who)
-    T = _render_poses(poses, None, who)
+    T = _pose_array(poses, None, who, **_VIEW_POSES)
     if int(width) * int(height) * T.shape[0] > (1 << 31) - 1:
         raise ValueError("%s: more than 2^31 - 1 pixels in one call" % who)
     return K, int(width), int(height), T
-
-
-def _merge_poses(poses, n, who):
-    """the poses of a posed merge as a contiguous [n, 4, 4] float64 array with finite entries, or ValueError / TypeError"""
-    try:
-        T = np.ascontiguousarray(poses, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise TypeError("%s: poses must be real numbers, one 4 x 4 matrix per source" % who)
-    if T.ndim == 2 and n == 1:
-        T = T[None]
-    if T.ndim != 3 or T.shape[1:] != (4, 4):
-        raise ValueError("%s: a pose is a 4 x 4 matrix (source -> destination), got shape %s" % (who, T.shape))
-    if T.shape[0] != n:
-        raise ValueError("%s: %d sources but %d poses" % (who, n, T.shape[0]))
-    if not np.all(np.isfinite(T)):
-        raise ValueError("%s: a pose has an entry that is not finite" % who)
-    return T
 
 
 def _record_array(a, fields, words, who, what):
@@ -903,38 +902,32 @@ class KeyframeMap:
                 if getattr(p, "_colour", None) is None:
                     raise ValueError("%s: a coloured map takes pyramids that carry colour (set_colour)" % who)
 
+    def _update(self, name, pyramids, level, min_depth, max_depth, *poses):
+        """insert(), remove() and move(): the checks, then dvo_hip_map_<name> with one pose array per element of `poses`"""
+        who = "KeyframeMap." + name
+        n, T = len(pyramids), [_map_frames_args(pyramids, p, level, min_depth, max_depth, who)[1] for p in poses]
+        if pyramids[0].ctx is not self.ctx:
+            raise ValueError("%s: the pyramids belong to another context than the map" % who)
+        self._check_colour_of(pyramids, who)
+        self.ctx.check(getattr(self.ctx._lib, "dvo_hip_map_" + name)(self.ctx.ptr, self.ptr, n, _handles(pyramids),
+                                                                     *[t.ctypes.data_as(C.POINTER(C.c_double)) for t in T],
+                                                                     int(level), float(min_depth), float(max_depth)))
+
     def insert(self, pyramids, poses, level=0, min_depth=0.0, max_depth=float("inf")):
         """Every usable point of `level` of the pyramids under their 4 x 4 poses (camera -> world).  Raises DvoHipError with code
         ERR_CAPACITY if the table dropped points; the map keeps what it took."""
-        n, T = _map_frames_args(pyramids, poses, level, min_depth, max_depth, "KeyframeMap.insert")
-        if pyramids[0].ctx is not self.ctx:
-            raise ValueError("KeyframeMap.insert: the pyramids belong to another context than the map")
-        self._check_colour_of(pyramids, "KeyframeMap.insert")
-        self.ctx.check(self.ctx._lib.dvo_hip_map_insert(self.ctx.ptr, self.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)),
-                                                        int(level), float(min_depth), float(max_depth)))
+        self._update("insert", pyramids, level, min_depth, max_depth, poses)
 
     def remove(self, pyramids, poses, level=0, min_depth=0.0, max_depth=float("inf")):
         """The inverse of insert() (dvo_hip_map_remove): the same pyramids -- with the content they had then -- poses, level and depth range
         take their points out of the map again, exactly.  Raises DvoHipError with code ERR_INVALID if points found no voxel to leave
         (stats()["unmatched"]) or if the map has dropped points since its last clear() or rehash()."""
-        n, T = _map_frames_args(pyramids, poses, level, min_depth, max_depth, "KeyframeMap.remove")
-        if pyramids[0].ctx is not self.ctx:
-            raise ValueError("KeyframeMap.remove: the pyramids belong to another context than the map")
-        self._check_colour_of(pyramids, "KeyframeMap.remove")
-        self.ctx.check(self.ctx._lib.dvo_hip_map_remove(self.ctx.ptr, self.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)),
-                                                        int(level), float(min_depth), float(max_depth)))
+        self._update("remove", pyramids, level, min_depth, max_depth, poses)
 
     def move(self, pyramids, poses_old, poses_new, level=0, min_depth=0.0, max_depth=float("inf")):
         """After a pose-graph optimisation (dvo_hip_map_move): the pyramids leave the map under poses_old and enter it under poses_new in
         one launch, bit for bit remove(poses_old) followed by insert(poses_new); a pyramid whose pose stays is skipped."""
-        n, T_old = _map_frames_args(pyramids, poses_old, level, min_depth, max_depth, "KeyframeMap.move")
-        T_new = _map_frames_args(pyramids, poses_new, level, min_depth, max_depth, "KeyframeMap.move")[1]
-        if pyramids[0].ctx is not self.ctx:
-            raise ValueError("KeyframeMap.move: the pyramids belong to another context than the map")
-        self._check_colour_of(pyramids, "KeyframeMap.move")
-        dp = C.POINTER(C.c_double)
-        self.ctx.check(self.ctx._lib.dvo_hip_map_move(self.ctx.ptr, self.ptr, n, _handles(pyramids), T_old.ctypes.data_as(dp), T_new.ctypes.data_as(dp),
-                                                      int(level), float(min_depth), float(max_depth)))
+        self._update("move", pyramids, level, min_depth, max_depth, poses_old, poses_new)
 
     def rehash(self, capacity=None):
         """Rebuilds the table (dvo_hip_map_rehash) with `capacity` slots, a power of two of at least 64 (None: as many as it has): vacant
@@ -961,23 +954,15 @@ class KeyframeMap:
             raise ValueError("KeyframeMap.extract: sort=True orders on the host; extract to the host, or sort the device tensors by key")
         cap = self.stats()["occupied"] if max_points is None else int(max_points)
         got = C.c_size_t(0)
-        if device:
-            import torch
-            dev = "cuda:%d" % self.ctx.device
-            xyzi = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
-            counts = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-            keys = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
-            rgba = torch.empty(max(cap, 1), dtype=torch.int32, device=dev) if colour else None
-            ptrs = (xyzi.data_ptr(), counts.data_ptr(), keys.data_ptr(), rgba.data_ptr() if colour else None)
-        else:
-            xyzi, counts, keys = np.empty((max(cap, 1), 4), np.float32), np.empty(max(cap, 1), np.uint32), np.empty(max(cap, 1), np.uint64)
-            rgba = np.empty(max(cap, 1), np.uint32) if colour else None
-            ptrs = (xyzi.ctypes.data, counts.ctypes.data, keys.ctypes.data, rgba.ctypes.data if colour else None)
+        m = max(cap, 1)
+        xyzi, counts, keys = (_out_array(self.ctx, shape, dt, device) for shape, dt in (((m, 4), np.float32), (m, np.uint32), (m, np.uint64)))
         if colour:
-            self.ctx.check(self.ctx._lib.dvo_hip_map_extract_colour(self.ctx.ptr, self.ptr, cap, ptrs[0], ptrs[3], ptrs[1], ptrs[2], 1 if device else 0,
-                                                                    C.byref(got)))
+            rgba = _out_array(self.ctx, m, np.uint32, device)
+            self.ctx.check(self.ctx._lib.dvo_hip_map_extract_colour(self.ctx.ptr, self.ptr, cap, _address(xyzi), _address(rgba), _address(counts),
+                                                                    _address(keys), 1 if device else 0, C.byref(got)))
         else:
-            self.ctx.check(self.ctx._lib.dvo_hip_map_extract(self.ctx.ptr, self.ptr, cap, ptrs[0], ptrs[1], ptrs[2], 1 if device else 0, C.byref(got)))
+            self.ctx.check(self.ctx._lib.dvo_hip_map_extract(self.ctx.ptr, self.ptr, cap, _address(xyzi), _address(counts), _address(keys),
+                                                             1 if device else 0, C.byref(got)))
         xyzi, counts, keys = xyzi[:got.value], counts[:got.value], keys[:got.value]
         if colour:
             rgba = rgba[:got.value]
@@ -1015,7 +1000,7 @@ class KeyframeMap:
                 raise ValueError("%s: a coloured and a grey map do not merge" % who)
             if poses is None and np.float32(s.leaf) != np.float32(self.leaf):
                 raise ValueError("%s: a plain merge needs the destination's leaf size (a posed merge bins anew)" % who)
-        T = None if poses is None else _merge_poses(poses, len(sources), who)
+        T = None if poses is None else _pose_array(poses, len(sources), who, **_MERGE_POSES)
         return sources, T
 
     def merge(self, sources, signs=None, poses=None):
@@ -1058,7 +1043,7 @@ class KeyframeMap:
         if poses_old is None or poses_new is None:
             raise ValueError("%s: needs the old and the new poses" % who)
         sources, T_old = self._merge_sources(sources, poses_old, who)
-        T_new = _merge_poses(poses_new, len(sources), who)
+        T_new = _pose_array(poses_new, len(sources), who, **_MERGE_POSES)
         if not sources:
             return
         dp = C.POINTER(C.c_double)
@@ -1073,18 +1058,11 @@ class KeyframeMap:
         got = C.c_size_t(0)
         self.ctx.check(self.ctx._lib.dvo_hip_map_export(self.ctx.ptr, self.ptr, 0, None, None, 0, C.byref(got)))
         n = got.value
-        if device:
-            import torch
-            dev = "cuda:%d" % self.ctx.device
-            records = torch.empty((max(n, 1), 8), dtype=torch.int32, device=dev)
-            colour = torch.empty((max(n, 1), 4), dtype=torch.int32, device=dev) if coloured else None
-            ptrs = (records.data_ptr(), colour.data_ptr() if coloured else None)
-        else:
-            records = np.zeros(max(n, 1), np.dtype(_lib.MAP_RECORD))
-            colour = np.zeros(max(n, 1), np.dtype(_lib.MAP_COLOUR_RECORD)) if coloured else None
-            ptrs = (records.ctypes.data, colour.ctypes.data if coloured else None)
+        records = _out_array(self.ctx, max(n, 1), _MAP_RECORD, device)
+        colour = _out_array(self.ctx, max(n, 1), _MAP_COLOUR_RECORD, device) if coloured else None
         if n > 0:
-            self.ctx.check(self.ctx._lib.dvo_hip_map_export(self.ctx.ptr, self.ptr, n, ptrs[0], ptrs[1], 1 if device else 0, C.byref(got)))
+            self.ctx.check(self.ctx._lib.dvo_hip_map_export(self.ctx.ptr, self.ptr, n, _address(records), _address(colour) if coloured else None,
+                                                            1 if device else 0, C.byref(got)))
         return records[:got.value], (colour[:got.value] if coloured else None)
 
     def absorb(self, records, colour=None, leaf=None, sign=1, pose=None):
@@ -1114,7 +1092,7 @@ class KeyframeMap:
             raise ValueError("%s: the leaf size must be finite and > 0" % who)
         if pose is None and np.float32(leaf) != np.float32(self.leaf):
             raise ValueError("%s: a plain merge needs the map's own leaf size (a posed merge bins anew)" % who)
-        T = None if pose is None else _merge_poses(pose, 1, who)
+        T = None if pose is None else _pose_array(pose, 1, who, **_MERGE_POSES)
         if n == 0:
             return
         self.ctx.check(self.ctx._lib.dvo_hip_map_merge_records(self.ctx.ptr, self.ptr, n, ptr, cptr, 1 if on_device else 0, leaf, int(sign),
@@ -1139,52 +1117,36 @@ class KeyframeMap:
         m.absorb(records, colour if coloured else None)
         return m
 
+    def _render(self, name, first, K, width, height, poses, device, params):
+        """render() and render_colour(): dvo_hip_map_<name> into planes of dtype `first` and float32 depth planes"""
+        K, width, height, T = _render_view_args(K, width, height, poses, "KeyframeMap." + name)
+        rp = render_params_struct(**params)
+        n = T.shape[0]
+        if device:
+            pad = (width * height + 3) // 4 * 4             # (every view's plane 16-byte aligned: views apart by a multiple of 4 words)
+            planes = [_out_array(self.ctx, n * pad, dt, True).as_strided((n, height, width), (pad, width, 1)) for dt in (first, np.float32)]
+        else:
+            planes = [_out_array(self.ctx, (n, height, width), dt, False) for dt in (first, np.float32)]
+        ptrs = [device_pointer_array([_address(a[k]) for k in range(n)]) for a in planes]
+        self.ctx.check(getattr(self.ctx._lib, "dvo_hip_map_" + name)(self.ctx.ptr, self.ptr, n, width, height, K.ctypes.data_as(C.POINTER(C.c_float)),
+                                                                     T.ctypes.data_as(C.POINTER(C.c_double)), C.byref(rp), ptrs[0], ptrs[1],
+                                                                     1 if device else 0))
+        return tuple(planes)
+
     def render(self, K, width, height, poses, device=False, **params):
         """Views of the map (dvo_hip_map_render): the nearest voxel per pixel of a width x height pinhole camera K = fx, fy, ox, oy at
         each 4 x 4 pose (camera -> world).  Returns (I, Z), float32 arrays of shape (n, height, width): intensity (0 where nothing was
         seen) and depth in metres (NaN where nothing was seen).  device=True: torch tensors on the GPU, ordered on the context's stream.
         params: min_depth, max_depth, splat, max_splat, min_points (render_params_struct)."""
-        K, width, height, T = _render_view_args(K, width, height, poses, "KeyframeMap.render")
-        rp = render_params_struct(**params)
-        n = T.shape[0]
-        if device:
-            import torch
-            dev = "cuda:%d" % self.ctx.device
-            pad = (width * height + 3) // 4 * 4             # (every view's plane 16-byte aligned: views apart by a multiple of 4 floats)
-            I, Z = (torch.empty(n * pad, dtype=torch.float32, device=dev).as_strided((n, height, width), (pad, width, 1)) for _ in range(2))
-            ip, zp = ([t[k].data_ptr() for k in range(n)] for t in (I, Z))
-        else:
-            I, Z = np.empty((n, height, width), np.float32), np.empty((n, height, width), np.float32)
-            ip, zp = ([a[k].ctypes.data for k in range(n)] for a in (I, Z))
-        self.ctx.check(self.ctx._lib.dvo_hip_map_render(self.ctx.ptr, self.ptr, n, width, height, K.ctypes.data_as(C.POINTER(C.c_float)),
-                                                        T.ctypes.data_as(C.POINTER(C.c_double)), C.byref(rp), device_pointer_array(ip),
-                                                        device_pointer_array(zp), 1 if device else 0))
-        return I, Z
+        return self._render("render", np.float32, K, width, height, poses, device, params)
 
     def render_colour(self, K, width, height, poses, device=False, **params):
         """Colour views of a coloured map (dvo_hip_map_render_colour): like render(), but returns (rgba, Z): uint32 words 0xFFRRGGBB of
         shape (n, height, width) -- 0 where nothing was seen -- and the depth planes, bit for bit render()'s.  device=True: torch
         tensors on the GPU (rgba as int32: the same bits)."""
-        who = "KeyframeMap.render_colour"
         if not getattr(self, "coloured", False):
-            raise ValueError("%s: the map holds no colour (KeyframeMap(colour=True))" % who)
-        K, width, height, T = _render_view_args(K, width, height, poses, who)
-        rp = render_params_struct(**params)
-        n = T.shape[0]
-        if device:
-            import torch
-            dev = "cuda:%d" % self.ctx.device
-            pad = (width * height + 3) // 4 * 4             # (every view's plane 16-byte aligned: views apart by a multiple of 4 words)
-            rgba = torch.empty(n * pad, dtype=torch.int32, device=dev).as_strided((n, height, width), (pad, width, 1))
-            Z = torch.empty(n * pad, dtype=torch.float32, device=dev).as_strided((n, height, width), (pad, width, 1))
-            cp, zp = ([t[k].data_ptr() for k in range(n)] for t in (rgba, Z))
-        else:
-            rgba, Z = np.empty((n, height, width), np.uint32), np.empty((n, height, width), np.float32)
-            cp, zp = ([a[k].ctypes.data for k in range(n)] for a in (rgba, Z))
-        self.ctx.check(self.ctx._lib.dvo_hip_map_render_colour(self.ctx.ptr, self.ptr, n, width, height, K.ctypes.data_as(C.POINTER(C.c_float)),
-                                                               T.ctypes.data_as(C.POINTER(C.c_double)), C.byref(rp), device_pointer_array(cp),
-                                                               device_pointer_array(zp), 1 if device else 0))
-        return rgba, Z
+            raise ValueError("KeyframeMap.render_colour: the map holds no colour (KeyframeMap(colour=True))")
+        return self._render("render_colour", np.uint32, K, width, height, poses, device, params)
 
     def render_into(self, pyramids, poses, role=None, config=None, flags=0, **params):
         """Views of the map straight into existing pyramids of one camera (dvo_hip_map_render_frames): pyramid i becomes the frame that the
@@ -1194,7 +1156,7 @@ class KeyframeMap:
         n = len(pyramids)
         if n < 1:
             raise ValueError("%s: no pyramids" % who)
-        T = _render_poses(poses, n, who)
+        T = _pose_array(poses, n, who, **_VIEW_POSES)
         for p in pyramids:
             if p.ctx is not self.ctx:
                 raise ValueError("%s: the pyramids belong to another context than the map" % who)
