@@ -304,6 +304,26 @@ struct PinnedRing {
   }
 };
 
+// What the slow lane of a batch keeps from one batch to the next (capi_lane.inc, option "overlap_tails"): the stragglers of the levels run on
+// a stream of their own beside the batch's chain, with partial rows, residual pairs and log-likelihood sums of their own (two levels index
+// those by different tile counts), the pairs' flag bytes and the lane's two lists of them.  (Here and not in capi_lane.inc: the
+// workspace holds one, and the lane's code needs the context, which holds the workspace.)
+struct LaneResources {
+  hipStream_t stream = nullptr;
+  hipEvent_t split = nullptr;                  // the chain has marked its stragglers
+  hipEvent_t end[2] = {nullptr, nullptr};      // per list: the launches given it so far are through (the current list's: all of the lane's)
+  DevBuf partials, scratch, ll, flags, lists;
+  hipError_t quiesce() { return stream ? hipStreamSynchronize(stream) : hipSuccess; }
+  void release() {
+    for (DevBuf* b : {&partials, &scratch, &ll, &flags, &lists}) b->release();
+    if (!stream) return;
+    (void)quiesce();
+    (void)hipStreamDestroy(stream);
+    for (hipEvent_t e : {split, end[0], end[1]}) (void)hipEventDestroy(e);
+    stream = nullptr;
+  }
+};
+
 // The batch workspace: one HIP stream, device scratch and the pinned poll words of the Gauss-Newton loop.
 // (Splitting a batch into concurrently iterating pair groups on several streams was measured and dropped: the coarse
 // levels are bound by the host's launch rate, which more streams only divide -- profiles/r01_d_groups.txt.)
@@ -334,11 +354,8 @@ struct Workspace {
   bool device_may_lag = true;      // the last batch returned without waiting for the stream (the resident kernel's direct path)
   int resident_error_word = 0;     // index of the current resident launch's error word in host_status (a ring, see kResidentErrorWords)
   unsigned resident_launch_counter = 0;
-  // the slow lane of a batch (run_batch, option "overlap_tails"): the stragglers of the levels run on a stream of their own beside the
-  // batch's chain, with partial rows, residual pairs and log-likelihood sums of their own (two levels index those by different tile counts)
-  hipStream_t tail_stream = nullptr;
-  hipEvent_t tail_split = nullptr, tail_end = nullptr;
-  DevBuf tail_partials, tail_scratch, tail_ll, tail_flags, tail_list;
+  LaneResources lane;              // the slow lane of a batch (capi_lane.inc)
+  DevBuf chain_list;               // option "tail_lists": the pairs the chain's last steps of a level cover (capi_schedule.inc, chain_level)
   // option "ref_order": the rows' records of a pass (RefOrderSeg, the largest level's height per pair) and the pairs' RefOrderPair
   DevBuf ref_rows, ref_pairs;
 };
@@ -459,7 +476,7 @@ struct dvo_hip_context {
   // in is built for 96 (five workgroups per compute unit), and the spilled step takes 40-50 us instead of 15
   int opt_sweep_tail = 0;
   long long tail_steps = 0;        // Gauss-Newton steps enqueued as ONE launch (sweep with a tail)
-  // The overlapped tail of a level (round 6, run_batch): once at most opt_overlap_fraction-th of a large batch's pairs is still on a level, the
+  // The overlapped tail of a level (round 6, capi_lane.inc): once at most opt_overlap_fraction-th of a large batch's pairs is still on a level, the
   // others begin the next level and the stragglers finish theirs beside it, on a stream of their own -- each pair leaves its level
   // independently, like the reference's match() calls do (dense_tracking.cpp:357).  0: off; 1: on (levels whose log-likelihood pass
   // runs inside the solver step, batches beyond the solver steps' hand-over).
@@ -628,16 +645,9 @@ void workspace_destroy(Workspace& w) {
   (void)hipStreamSynchronize(w.stream);
   for (DevBuf& b : w.pair_ptrs) b.release();
   for (DevBuf* b : {&w.states, &w.partials, &w.scratch, &w.ll_partials, &w.lvl_stats, &w.it_stats, &w.results,
-                    &w.t_init, &w.counters, &w.exchange, &w.win_fallbacks, &w.pair_sums, &w.tail_partials, &w.tail_scratch, &w.tail_ll, &w.tail_flags, &w.tail_list,
-                    &w.ref_rows, &w.ref_pairs})
+                    &w.t_init, &w.counters, &w.exchange, &w.win_fallbacks, &w.pair_sums, &w.chain_list, &w.ref_rows, &w.ref_pairs})
     b->release();
-  if (w.tail_stream) {
-    (void)hipStreamSynchronize(w.tail_stream);
-    (void)hipStreamDestroy(w.tail_stream);
-    (void)hipEventDestroy(w.tail_split);
-    (void)hipEventDestroy(w.tail_end);
-    w.tail_stream = nullptr;
-  }
+  w.lane.release();
   if (w.host_status) (void)hipHostFree(w.host_status);
   w.host_status = nullptr;
   w.host_status_words = 0;
@@ -704,7 +714,7 @@ struct IngestSource {
 };
 
 #include "capi_frames.inc"     // cameras, frame allocation and build, role planes (ensure_roles)
-#include "capi_schedule.inc"   // batch plan, buffers, waits, resident / coarse plans, run_batch
+#include "capi_schedule.inc"   // batch plan, buffers, waits, resident / coarse plans, run_batch in parts (and, in front of those, capi_lane.inc)
 
 // The Gram schedule of a batch, decided ONCE, before the planes of the roles are prepared for it (round-4 advisor finding: deciding it
 // inside run_batch prepared two flavours of the current role for every new frame).  The default accumulates on the f16 matrix pipe
@@ -1440,11 +1450,14 @@ int dvo_hip_level_iteration(dvo_hip_context* ctx, dvo_hip_frame* reference, dvo_
   PairState* states = ctx->ws[0].states.as<PairState>();
   DVO_HIP_TRY(ctx, hipMemsetAsync(states, 0, sizeof(PairState), s));
   launch_set_fixed_state(s, states, g, d_T, d_P, first_iteration_on_level ? 1 : 0);
-  const PairPtrs* pp = bp.pair_ptrs + size_t(level);
-  launch_residual_reduce(s, ctx->opt_variant, bp.rpw[level], level == 0, g, pp, states, 1, ctx->ws[0].partials.as<float>(), ctx->ws[0].scratch.as<float2>(),
-                         ctx->ws[0].win_fallbacks.as<unsigned long long>(), ctx->ws[0].f16_range_flag);
-  if (ref_order) launch_ref_order(s, g, states, 1, w0.scratch.as<float2>(), w0.ref_rows.as<RefOrderSeg>(), ref_order);
-  launch_loglik(s, g, states, 1, ctx->ws[0].partials.as<float>(), ctx->ws[0].scratch.as<float2>(), ctx->ws[0].ll_partials.as<double>(), kLlBlocksPerPair, false, ref_order);
+  // the sweep, the passes of option "ref_order", the log-likelihood pass (`range_flag`: where an f16 Gram schedule reports that it left its range)
+  auto sweep_and_passes = [&](int variant, int* range_flag) {
+    launch_residual_reduce(s, variant, bp.rpw[level], level == 0, g, bp.pair_ptrs + size_t(level), states, 1, w0.partials.as<float>(), w0.scratch.as<float2>(),
+                           w0.win_fallbacks.as<unsigned long long>(), range_flag);
+    if (ref_order) launch_ref_order(s, g, states, 1, w0.scratch.as<float2>(), w0.ref_rows.as<RefOrderSeg>(), ref_order);
+    launch_loglik(s, g, states, 1, w0.partials.as<float>(), w0.scratch.as<float2>(), w0.ll_partials.as<double>(), kLlBlocksPerPair, false, ref_order);
+  };
+  sweep_and_passes(ctx->opt_variant, w0.f16_range_flag);
   int n_sel = 0;
   DVO_HIP_TRY(ctx, hipMemcpyAsync(&n_sel, reference->sel_count + level, sizeof(int), hipMemcpyDeviceToHost, s));
   DVO_HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -1458,11 +1471,7 @@ int dvo_hip_level_iteration(dvo_hip_context* ctx, dvo_hip_frame* reference, dvo_
     ctx->opt_variant = keep_variant;
     if (rc != DVO_HIP_OK) return rc;
     g = bp.geom[level];
-    pp = bp.pair_ptrs + size_t(level);
-    launch_residual_reduce(s, 6, bp.rpw[level], level == 0, g, pp, states, 1, ctx->ws[0].partials.as<float>(), ctx->ws[0].scratch.as<float2>(),
-                           ctx->ws[0].win_fallbacks.as<unsigned long long>());
-    if (ref_order) launch_ref_order(s, g, states, 1, w0.scratch.as<float2>(), w0.ref_rows.as<RefOrderSeg>(), ref_order);
-    launch_loglik(s, g, states, 1, ctx->ws[0].partials.as<float>(), ctx->ws[0].scratch.as<float2>(), ctx->ws[0].ll_partials.as<double>(), kLlBlocksPerPair, false, ref_order);
+    sweep_and_passes(6, nullptr);
     DVO_HIP_TRY(ctx, hipStreamSynchronize(s));
   }
   launch_single_shot_out(s, g, ctx->ws[0].partials.as<float>(), ctx->ws[0].ll_partials.as<double>(), kLlBlocksPerPair, n_sel, d_out, ref_order);

@@ -91,9 +91,9 @@ int apply_selection(dvo_hip_context* ctx, hipStream_t stream, int n, dvo_hip_fra
 constexpr int kResidentErrorWords = 8;
 
 const int kLlBlocksPerPair = 32;
-const size_t kCostlyEmptyStepWorkgroups = 131072;   // (see run_batch: from here on the step ahead of the poll is held back on a level's tail)
+const size_t kCostlyEmptyStepWorkgroups = 131072;   // (see chain_level: from here on the step ahead of the poll is held back on a level's tail)
 const int kFusedLoglikMaxPixels = 160 * 120;      // any batch
-const int kFusedLoglikMaxPixelsBatch = 320 * 240;  // batches of 512 pairs and more (run_batch)
+const int kFusedLoglikMaxPixelsBatch = 320 * 240;  // batches of 512 pairs and more (schedule_of)
 
 // RgbdCameraPyramid::build (rgbd_image.cpp:283-296) + RgbdCamera ctor template (:186-204)
 int get_camera(dvo_hip_context* ctx, int w, int h, const float K[4], int levels, const CameraGeom** out) {

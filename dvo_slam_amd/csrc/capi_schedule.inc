@@ -1,6 +1,8 @@
 // capi_schedule.inc -- how a batch is run: its plan (levels, tiles, buffers), the waits on the device's status words, which levels the resident
-// and the fused coarse-level kernels take, and run_batch, the coarse-to-fine Gauss-Newton driver of a batch on the launch path (with the slow
-// lane of its stragglers).  Textually included by capi.hip inside its anonymous namespace, behind capi_frames.inc.
+// and the fused coarse-level kernels take, and run_batch, the coarse-to-fine Gauss-Newton driver of a batch on the launch path, in parts:
+// preparation, the one-launch prefixes, one level of the chain, the way out, the repeats.  The slow lane of a batch's stragglers is a unit
+// of its own, capi_lane.inc, included in front of those parts.  Textually included by capi.hip inside its anonymous namespace, behind
+// capi_frames.inc.
 struct BatchPlan {
   int n = 0, nlev = 0, cap_levels = 0, cap_iters = 0;
   SolverParams prm;
@@ -521,517 +523,567 @@ std::mutex g_rare_path_mutex;   // (see run_batch: the repeat of pairs that left
 
 constexpr int kF32GramHoldBatches = 32;   // after a batch left the f16 range of the Gram operands: this many batches go straight to the f32 Gram
 
-hipEvent_t g_trace_ev[2] = {nullptr, nullptr};   // DVO_HIP_TRACE_SLOW: device time stamps around a batch's preparation
-
-// The coarse-to-fine Gauss-Newton driver of a batch (dense_tracking.cpp:131-376 for every pair at once).
-int run_batch(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_frame* const* curs, const dvo_hip_config* cfg,
-              dvo_hip_result* results, dvo_hip_level_stats* levels, int cap_levels, dvo_hip_iteration_stats* iters, int cap_iters) {
-  Workspace& w = ctx->ws[0];
-  hipStream_t s = w.stream;
-  // DVO_HIP_TRACE_SLOW=<ms>: where the host thread spent the time before the first launch of a batch whose preparation took longer
-  static const double trace_slow_ms = std::getenv("DVO_HIP_TRACE_SLOW") ? std::atof(std::getenv("DVO_HIP_TRACE_SLOW")) : 0.0;
-  double mark_ms[5] = {0, 0, 0, 0, 0};
-  auto mark = [&](int k) { if (trace_slow_ms > 0.0) mark_ms[k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->batch_entry).count(); };
-  mark(0);                                                     // roles ensured (dvo_hip_match_batch)
-  if (trace_slow_ms > 0.0) {
-    if (!g_trace_ev[0]) { (void)hipEventCreate(&g_trace_ev[0]); (void)hipEventCreate(&g_trace_ev[1]); }
-    (void)hipEventRecord(g_trace_ev[0], s);
-  }
-  // (the Gram schedule of the batch -- f16 high + low operand pairs or f32 -- was decided by the caller, effective_variant_scope; what
-  // this function changes for a repeat is undone when it returns)
-  struct VariantScope {
-    dvo_hip_context* c; int keep;
-    ~VariantScope() { c->opt_variant = keep; }
-  } variant_scope{ctx, ctx->opt_variant};
+// ---- run_batch, the coarse-to-fine Gauss-Newton driver of a batch, in parts ----------------------------------------------------------
+// What the parts share: the batch as the caller gave it, what was planned for it, the typed device pointers of its buffers and the
+// count of the steps enqueued so far.
+struct BatchRun {
+  dvo_hip_context* const ctx;
+  Workspace& w;
+  const hipStream_t s;
+  const dvo_hip_config* const cfg;
+  const int n;
+  const BatchPolicy policy;                                    // every batch-size threshold below: batch_policy.h
   BatchPlan bp;
+  ResidentPlan rp;
+  std::vector<double> tinit;                                   // the initial guesses, 16 doubles per pair
+  size_t main_steps = 0, n_steps = 0;                          // status words and tallies: the chain's, and with the slow lane's behind them
+  int level_from = 0;                                          // the launch chain's first level (the one-launch kernels take those above it)
+  PairState* states = nullptr;
+  dvo_hip_level_stats* d_levels = nullptr;
+  dvo_hip_iteration_stats* d_iters = nullptr;
+  float* partials = nullptr;
+  float2* scratch = nullptr;
+  double* ll_partials = nullptr;
+  RefOrderPair* ref_order = nullptr;                           // (option "ref_order")
+  unsigned long long* tallies = nullptr;
+  int* arrivals = nullptr;
+  int per_level = 0, per_sync = 1;
+  int step = kResidentErrorWords;                              // the first status words belong to the resident kernel's launches
+  BatchRun(dvo_hip_context* c, const dvo_hip_config* config, int n_pairs)
+      : ctx(c), w(c->ws[0]), s(c->ws[0].stream), cfg(config), n(n_pairs), policy(c->compute_units) {}
+};
+
+// How the launches of one iteration on `level` are put together; the chain and the slow lane run their pairs by the same rule.
+struct LevelSchedule {
+  bool fused_ll = false, two_waves = false;
+  int ll_blocks = 0;
+};
+LevelSchedule schedule_of(const BatchRun& b, int level) {
+  const dvo_hip_context* ctx = b.ctx;
+  const LevelGeom& g = b.bp.geom[level];
+  LevelSchedule ls;
+  const int fuse_opt = ctx->opt_fused_ll_pixels;
+  // levels this small run the log-likelihood sweep inside the solver workgroup (one launch less per iteration)
+  // (measured, scripts/ab_match.py fused_ll_pixels: 128 pairs 2.152 -> 2.117 ms with level 1 fused; 16 pairs 0.756 -> 0.799, one
+  // pair 0.524 -> 0.547: a lone workgroup per pair is slower than 32 blocks when the chip is empty)
+  // (round 5, packed residual pairs, the streaming step beside its ingest, scripts/r5_midsize.py: level 1 in a launch of its own
+  // 64 pairs 1.456 -> 1.378 ms, 128 pairs 1.939 -> 1.908, 256 pairs 3.308 -> 3.286, 512 pairs 5.859 -> 5.880: fused from 512 pairs)
+  // (option "ref_order": the log-likelihood pass of its own on every level, k_loglik with the pairs' RefOrderPair)
+  ls.fused_ll = !b.bp.ref_order && g.w * g.h <= (fuse_opt > 0 ? fuse_opt : (b.policy.fused_loglik_on_large_levels(b.n) && !ctx->opt_deterministic ? kFusedLoglikMaxPixelsBatch : kFusedLoglikMaxPixels));
+  // workgroups per pair of the log-likelihood pass: each begins by reducing the pair's scale sums (a latency chain of ~10 us), which
+  // a batch that fills the device anyway pays once per workgroup for nothing -- fewer, longer ones then (option ll_blocks to override)
+  // (round 5, mid-size batches, scripts/r5_midsize.py: 16 instead of 32 workgroups per pair 64 / 128 / 200 pairs 1.179 -> 1.173 /
+  // 1.775 -> 1.760 / 2.558 -> 2.538 ms per step; 8: 1.183 / 1.760 / 2.546)
+  ls.ll_blocks = ctx->opt_ll_blocks > 0 ? std::min(ctx->opt_ll_blocks, kLlBlocksPerPair)
+                 : (!g.compact || ctx->opt_deterministic ? kLlBlocksPerPair : b.policy.loglik_blocks(b.n));
+  // the solver step of the smallest levels in two-wavefront workgroups (four per compute unit instead of two): a batch that otherwise
+  // needs two goes of 512 resident workgroups (option solver_waves 2 / 4 to force; the records do not depend on it).  Measured at
+  // 1024 pairs (scripts/r4_trace.sh): 80 x 60 46 -> 36 us per step; 160 x 120 with packed residuals 77 -> 90 (two wavefronts walk
+  // its 96 slots in six rounds instead of three), 320 x 240 and the finest level level: those keep four.
+  ls.two_waves = ctx->opt_solver_waves == 2 ||
+                 (ctx->opt_solver_waves == 0 && ls.fused_ll && !g.compact && g.tiles_x * g.tiles_y <= 32 && b.policy.solver_two_waves(b.n));
+  return ls;
+}
+
+#include "capi_lane.inc"       // the slow lane of a batch (SlowLane): needs the above, and the chain below needs it
+
+// DVO_HIP_TRACE_SLOW=<ms>: where the host thread spent the time before the first launch of a batch whose preparation took longer (stderr).
+// prepare_batch sets the marks: 0 roles ensured (dvo_hip_match_batch), 1 plan + buffers + tables, 2 initial guesses + drain, 3 status
+// words, 4 stream wait + reset.
+hipEvent_t g_trace_ev[2] = {nullptr, nullptr};   // device time stamps around a batch's preparation
+struct PrepTrace {
+  const dvo_hip_context* ctx;
+  hipStream_t s;
+  double limit_ms;
+  double ms[5] = {0, 0, 0, 0, 0};
+  PrepTrace(const dvo_hip_context* c, hipStream_t stream) : ctx(c), s(stream) {
+    static const double trace_slow_ms = std::getenv("DVO_HIP_TRACE_SLOW") ? std::atof(std::getenv("DVO_HIP_TRACE_SLOW")) : 0.0;
+    limit_ms = trace_slow_ms;
+    mark(0);
+    if (limit_ms > 0.0) {
+      if (!g_trace_ev[0]) { (void)hipEventCreate(&g_trace_ev[0]); (void)hipEventCreate(&g_trace_ev[1]); }
+      (void)hipEventRecord(g_trace_ev[0], s);
+    }
+  }
+  void mark(int k) { if (limit_ms > 0.0) ms[k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ctx->batch_entry).count(); }
+  void before_stream_wait() { if (limit_ms > 0.0) (void)hipEventRecord(g_trace_ev[1], s); }
+  void after_stream_wait() {
+    if (limit_ms <= 0.0) return;
+    mark(4);
+    float gpu_ms = -1.0f;
+    if (ms[4] - ms[3] > limit_ms && hipEventElapsedTime(&gpu_ms, g_trace_ev[0], g_trace_ev[1]) == hipSuccess)
+      std::fprintf(stderr, "dvo_hip: the stream wait took %.3f ms on the host; on the device %.3f ms passed between the batch's first and last command so far\n",
+                   ms[4] - ms[3], gpu_ms);
+  }
+  void report(int n) {
+    mark(4);
+    if (limit_ms > 0.0 && ms[4] > limit_ms)
+      std::fprintf(stderr, "dvo_hip: slow preparation of a %d-pair batch: roles %.3f, plan + buffers + tables %.3f, initial guesses + drain %.3f, status words %.3f, "
+                   "stream wait + reset %.3f ms\n", n, ms[0], ms[1] - ms[0], ms[2] - ms[1], ms[3] - ms[2], ms[4] - ms[3]);
+  }
+};
+
+// Preparation: the plan, the buffers, the initial guesses, the drain of a batch that ended early, the status words and their reset.
+int prepare_batch(BatchRun& b, SlowLane& lane, dvo_hip_frame* const* refs, dvo_hip_frame* const* curs, const dvo_hip_result* results) {
+  dvo_hip_context* ctx = b.ctx;
+  Workspace& w = b.w;
+  const dvo_hip_config* cfg = b.cfg;
+  const int n = b.n;
+  BatchPlan& bp = b.bp;
+  PrepTrace trace(ctx, b.s);
   make_plan(ctx, refs[0]->cam, cfg, n, bp);
-  const BatchPolicy policy(ctx->compute_units);               // every batch-size threshold below: batch_policy.h
   // The coarse levels -- for a small batch every level -- run inside ONE launch (align_resident.hip): no launch per iteration, no
   // host poll, the pairs of a batch do not wait for each other.
-  const ResidentPlan rp = plan_paths(ctx, cfg, bp, window_taps_missing(ctx, cfg, n, curs));
-  const bool tables_inline = rp.direct && n <= kResidentInline;   // plane pointers and initial guesses travel as kernel arguments
+  b.rp = plan_paths(ctx, cfg, bp, window_taps_missing(ctx, cfg, n, curs));
+  const bool tables_inline = b.rp.direct && n <= kResidentInline;   // plane pointers and initial guesses travel as kernel arguments
   int rc = prepare_buffers(w, cfg, refs, curs, bp, !tables_inline);
   if (rc != DVO_HIP_OK) return rc;
-  mark(1);
+  trace.mark(1);
 
   // initial guesses (Result.Transformation is in/out, dense_tracking.cpp:137-147)
-  std::vector<double> tinit(size_t(n) * 16);
-  for (int i = 0; i < n; ++i) std::memcpy(&tinit[size_t(i) * 16], results[i].transformation, 16 * sizeof(double));
-  if (!tables_inline) DVO_WS_TRY(w, w.tables->upload(s, w.t_init.p, tinit.data(), tinit.size() * sizeof(double)));
+  b.tinit.resize(size_t(n) * 16);
+  for (int i = 0; i < n; ++i) std::memcpy(&b.tinit[size_t(i) * 16], results[i].transformation, 16 * sizeof(double));
+  if (!tables_inline) DVO_WS_TRY(w, w.tables->upload(b.s, w.t_init.p, b.tinit.data(), b.tinit.size() * sizeof(double)));
   // per-step tallies (device) and status words (pinned host memory the device writes, see publish_step)
-  const size_t main_steps = size_t(bp.cap_iters) + 8 + kResidentErrorWords;
-  // The slow lane of a batch (option "overlap_tails"): see in front of the level loop below.  Batches whose levels are begun by launches
-  // (beyond the solver steps' hand-over), the plain launch chain (no step in the sweep's tail), more than one level on this path.
-  bool overlap_batch = ctx->opt_overlap_tails != 0 && !ctx->opt_ref_order && !policy.level_hand_over(n) && ctx->opt_sweep_tail == 0 && rp.levels == 0 && bp.coarse_levels == 0 &&
-                       cfg->first_level > cfg->last_level;
-  for (int l = cfg->last_level; l <= cfg->first_level; ++l)   // (the lane passes through every level: each one's sweep must take a list of pairs)
-    overlap_batch = overlap_batch && sweep_takes_pair_list(ctx->opt_variant, bp.rpw[l], bp.geom[l]);
-  const size_t tail_steps_cap = overlap_batch ? size_t(bp.cap_iters) + 12 * size_t(bp.nlev) + 8 : 0;   // (per level: the passes of its slowest pair, and up to eight steps enqueued ahead of what is known)
-  const size_t n_steps = main_steps + tail_steps_cap;         // (the tail's status words and tallies lie behind the main chain's)
-  if (overlap_batch) {
-    size_t t_tiles = 1, t_entries = 0;
-    for (int l = cfg->last_level; l <= cfg->first_level; ++l) {
-      t_tiles = std::max(t_tiles, size_t(bp.geom[l].tiles_x) * bp.geom[l].tiles_y);
-      t_entries = std::max(t_entries, residual_entries(bp.geom[l]));
-    }
-    DVO_WS_TRY(w, w.tail_partials.reserve(size_t(n) * t_tiles * kAccStride * sizeof(float)));
-    DVO_WS_TRY(w, w.tail_scratch.reserve(size_t(n) * t_entries * sizeof(float2)));
-    DVO_WS_TRY(w, w.tail_flags.reserve(align_up(size_t(n), 256)));
-    DVO_WS_TRY(w, w.tail_ll.reserve(size_t(n) * kLlBlocksPerPair * sizeof(double)));
-
-    DVO_WS_TRY(w, w.counters.reserve(n_steps * sizeof(unsigned long long) + align_up(size_t(n) * sizeof(int), 8)));
-    if (!w.tail_stream) {
-      int prio_least = 0, prio_greatest = 0;
-      DVO_WS_TRY(w, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-      DVO_WS_TRY(w, hipStreamCreateWithPriority(&w.tail_stream, hipStreamNonBlocking, prio_greatest));
-      DVO_WS_TRY(w, hipEventCreateWithFlags(&w.tail_split, hipEventDisableTiming));
-      DVO_WS_TRY(w, hipEventCreateWithFlags(&w.tail_end, hipEventDisableTiming));
-    }
-  }
-  // (the lane's two lists -- the one in use and the one being made -- and the chain's own active-pair list)
-  if (overlap_batch || ctx->opt_tail_lists) DVO_WS_TRY(w, w.tail_list.reserve(3 * align_up(size_t(n), 64) * sizeof(int)));
+  b.main_steps = size_t(bp.cap_iters) + 8 + kResidentErrorWords;
+  rc = lane.reserve();                                         // the slow lane of the batch (option "overlap_tails"), where it gets one
+  if (rc != DVO_HIP_OK) return rc;
+  b.n_steps = b.main_steps + lane.steps_cap();                 // (the lane's status words and tallies lie behind the main chain's)
+  // (option "tail_lists": the chain's own active-pair list, chain_level)
+  if (ctx->opt_tail_lists) DVO_WS_TRY(w, w.chain_list.reserve(align_up(size_t(n), 64) * sizeof(int)));
   // a batch that ended early (time-out, HIP error) may have left steps queued: nothing of it may still be running when the
   // status words and tallies are reset
   if (w.needs_drain) {
-    if (w.tail_stream) DVO_WS_TRY(w, hipStreamSynchronize(w.tail_stream));
-    DVO_WS_TRY(w, sync_stream(s));
+    DVO_WS_TRY(w, w.lane.quiesce());
+    DVO_WS_TRY(w, sync_stream(b.s));
     // ... and the f16 range words it may have raised are nobody's business any more (they are cleared where they are read, at a batch's
     // regular end: left standing, the next batch would repeat unrelated pairs at the same indices -- round-5 advisor finding)
     if (w.f16_range_flag) std::memset(w.f16_range_flag, 0, w.f16_range_words * sizeof(int));
   }
   w.needs_drain = true;                                        // until this batch has come to its regular end
-  mark(2);
-  rc = ensure_host_status(w, n_steps);
+  trace.mark(2);
+  rc = ensure_host_status(w, b.n_steps);
   if (rc != DVO_HIP_OK) return rc;
-  mark(3);
+  trace.mark(3);
   w.resident_error_word = int(w.resident_launch_counter++ % kResidentErrorWords);
-  if (rp.direct) {
+  if (b.rp.direct) {
     w.host_status[w.resident_error_word] = 0;
   } else {
     // (the previous batch may have ended on the host's side before the device was through with the step words: the direct path)
     // (only then: a batch that ended with a stream wait left nothing behind, and a wait for the table uploads just enqueued has been
     // seen to return 14-24 ms after the device was done with them -- 19 microseconds by its own time stamps: r03, the validator's
     // 128-pair batches in the first process on a box, never under the profiler)
-    if (trace_slow_ms > 0.0) (void)hipEventRecord(g_trace_ev[1], s);
-    if (w.device_may_lag) DVO_WS_TRY(w, sync_stream(s));
+    trace.before_stream_wait();
+    if (w.device_may_lag) DVO_WS_TRY(w, sync_stream(b.s));
     w.device_may_lag = false;
-    if (trace_slow_ms > 0.0) {
-      mark(4);
-      float gpu_ms = -1.0f;
-      if (mark_ms[4] - mark_ms[3] > trace_slow_ms && hipEventElapsedTime(&gpu_ms, g_trace_ev[0], g_trace_ev[1]) == hipSuccess)
-        std::fprintf(stderr, "dvo_hip: the stream wait took %.3f ms on the host; on the device %.3f ms passed between the batch's first and last command so far\n",
-                     mark_ms[4] - mark_ms[3], gpu_ms);
-    }
-    std::memset(w.host_status, 0, n_steps * sizeof(int));
-    DVO_WS_TRY(w, hipMemsetAsync(w.counters.p, 0, n_steps * sizeof(unsigned long long) + align_up(size_t(n) * sizeof(int), 8), s));
+    trace.after_stream_wait();
+    std::memset(w.host_status, 0, b.n_steps * sizeof(int));
+    DVO_WS_TRY(w, hipMemsetAsync(w.counters.p, 0, b.n_steps * sizeof(unsigned long long) + align_up(size_t(n) * sizeof(int), 8), b.s));
   }
 
-  PairState* states = w.states.as<PairState>();
-  dvo_hip_level_stats* d_levels = w.lvl_stats.as<dvo_hip_level_stats>();
-  dvo_hip_iteration_stats* d_iters = w.it_stats.as<dvo_hip_iteration_stats>();
-  float* partials = w.partials.as<float>();
-  float2* scratch = w.scratch.as<float2>();
-  double* ll_partials = w.ll_partials.as<double>();
-  RefOrderPair* const ref_order = bp.ref_order ? w.ref_pairs.as<RefOrderPair>() : nullptr;   // (option "ref_order")
-  unsigned long long* tallies = w.counters.as<unsigned long long>();
-  int* arrivals = reinterpret_cast<int*>(tallies + n_steps);
-  const int per_level = cfg->max_iterations_per_level;
-  const int per_sync = ctx->opt_iters_per_sync > 0 ? ctx->opt_iters_per_sync : 1;
-  int step = kResidentErrorWords;                           // the first status words belong to the resident kernel's launches
-  mark(4);
-  if (trace_slow_ms > 0.0 && mark_ms[4] > trace_slow_ms)
-    std::fprintf(stderr, "dvo_hip: slow preparation of a %d-pair batch: roles %.3f, plan + buffers + tables %.3f, initial guesses + drain %.3f, status words %.3f, "
-                 "stream wait + reset %.3f ms\n", n, mark_ms[0], mark_ms[1] - mark_ms[0], mark_ms[2] - mark_ms[1], mark_ms[3] - mark_ms[2], mark_ms[4] - mark_ms[3]);
-  const auto t_launch = std::chrono::steady_clock::now();
-  int level_from = cfg->first_level;
-  const bool want_stats = (levels && cap_levels > 0) || (iters && cap_iters > 0);
-  ResidentBudget::Hold compute_units;                          // released when this batch is through with the device
-  if (rp.levels > 0 && rp.group > 1)
-    compute_units.take(ResidentBudget::of(ctx->device), n * rp.group, ctx->compute_units > 0 ? ctx->compute_units : 256);
-  if (rp.levels > 0) {
+  b.states = w.states.as<PairState>();
+  b.d_levels = w.lvl_stats.as<dvo_hip_level_stats>();
+  b.d_iters = w.it_stats.as<dvo_hip_iteration_stats>();
+  b.partials = w.partials.as<float>();
+  b.scratch = w.scratch.as<float2>();
+  b.ll_partials = w.ll_partials.as<double>();
+  b.ref_order = bp.ref_order ? w.ref_pairs.as<RefOrderPair>() : nullptr;
+  b.tallies = w.counters.as<unsigned long long>();
+  b.arrivals = reinterpret_cast<int*>(b.tallies + b.n_steps);
+  b.per_level = cfg->max_iterations_per_level;
+  b.per_sync = ctx->opt_iters_per_sync > 0 ? ctx->opt_iters_per_sync : 1;
+  trace.report(n);
+  return DVO_HIP_OK;
+}
+
+// A recorded ingest of the caller's next batch (option "defer_ingest") is carried out now, behind what this batch has enqueued so far;
+// the text of its error becomes the batch's.
+int flush_recorded_ingest(BatchRun& b) {
+  if (b.ctx->deferred.empty()) return DVO_HIP_OK;
+  const int rc_deferred = flush_deferred(b.ctx);
+  if (rc_deferred != DVO_HIP_OK) b.w.err = b.ctx->err;
+  return rc_deferred;
+}
+
+// The one-launch prefixes: the leading levels of the match in the resident kernel or in the fused coarse-level kernel, where the plan
+// gave them any; the launch chain begins behind them (level_from).
+int run_prefixes(BatchRun& b, bool want_stats) {
+  const dvo_hip_config* cfg = b.cfg;
+  b.level_from = cfg->first_level;
+  if (b.rp.levels > 0) {
     Range range("resident");
-    rc = run_resident(ctx, w, cfg, bp, rp, tinit.data(), want_stats);
+    int rc = run_resident(b.ctx, b.w, cfg, b.bp, b.rp, b.tinit.data(), want_stats);
+    if (rc == DVO_HIP_OK) rc = flush_recorded_ingest(b);       // (see the launch path, chain_level)
     if (rc != DVO_HIP_OK) return rc;
-    if (!ctx->deferred.empty()) {                              // (see the launch path below)
-      const int rc_deferred = flush_deferred(ctx);
-      if (rc_deferred != DVO_HIP_OK) {
-        w.err = ctx->err;
-        return rc_deferred;
-      }
-    }
-    level_from = cfg->first_level - rp.levels;
+    b.level_from = cfg->first_level - b.rp.levels;
   }
-  if (bp.coarse_levels > 0) {
+  if (b.bp.coarse_levels > 0) {
     // the coarse levels of every pair in ONE launch, a workgroup per pair (align_coarse.hip): nothing to poll -- the host goes on to
     // enqueue the first steps of the level behind them
     Range range("coarse");
-    rc = run_coarse(ctx, w, cfg, bp);
+    int rc = run_coarse(b.ctx, b.w, cfg, b.bp);
+    if (rc == DVO_HIP_OK) rc = flush_recorded_ingest(b);
     if (rc != DVO_HIP_OK) return rc;
-    if (!ctx->deferred.empty()) {
-      const int rc_deferred = flush_deferred(ctx);
-      if (rc_deferred != DVO_HIP_OK) {
-        w.err = ctx->err;
-        return rc_deferred;
-      }
-    }
-    level_from = cfg->first_level - bp.coarse_levels;
+    b.level_from = cfg->first_level - b.bp.coarse_levels;
   }
-  // ---- the slow lane of a batch (round 6, option "overlap_tails") ------------------------------------------------------------------------
-  // The pairs of a batch need different numbers of passes on a level, and the launch chain runs a level until its LAST pair has left it: on
-  // the bench's 1024-pair batches 11 of a step's 32 iterations are such tail launches, a few dozen pairs each, while the chip waits (1.1 ms
-  // of 11).  In the reference every match() runs on its own from start to end (dense_tracking.cpp:200-357).  Here, once at most 1/8 of
-  // the pairs is still on a level, those pairs leave the batch's chain for good: they get a flag byte and a place in a list
-  // (k_mark_stragglers), the chain goes on to the next level without them (LevelGeom::skip_flags), and a SLOW LANE -- a second stream, its
-  // own partial rows and residual pairs, its own status words -- runs them to the end of the match with launches over the list
-  // (LevelGeom::pair_list): the rest of that level, then level after level behind the main chain, taking up the stragglers the chain
-  // sheds on the way.  The lane works on one level at a time and never gets ahead of the chain: it leaves a level when none of its members is
-  // active on it AND the chain has left it (so nobody can still arrive there).  The batch ends when both have.  A pair's arithmetic does
-  // not know in which launch it runs: the records are the synchronous chain's bit for bit (tests/test_gpu_overlap.py).
-  struct LevelSchedule {
-    bool fused_ll = false, two_waves = false;
-    int ll_blocks = 0;
-  };
-  auto schedule_of = [&](int level) {
-    const LevelGeom& g = bp.geom[level];
-    LevelSchedule ls;
-    const int fuse_opt = ctx->opt_fused_ll_pixels;
-    // (option "ref_order": the log-likelihood pass of its own on every level, k_loglik with the pairs' RefOrderPair)
-    ls.fused_ll = !bp.ref_order && g.w * g.h <= (fuse_opt > 0 ? fuse_opt : (policy.fused_loglik_on_large_levels(n) && !ctx->opt_deterministic ? kFusedLoglikMaxPixelsBatch : kFusedLoglikMaxPixels));
-    ls.ll_blocks = ctx->opt_ll_blocks > 0 ? std::min(ctx->opt_ll_blocks, kLlBlocksPerPair)
-                   : (!g.compact || ctx->opt_deterministic ? kLlBlocksPerPair : policy.loglik_blocks(n));
-    ls.two_waves = ctx->opt_solver_waves == 2 ||
-                   (ctx->opt_solver_waves == 0 && ls.fused_ll && !g.compact && g.tiles_x * g.tiles_y <= 32 && policy.solver_two_waves(n));
-    return ls;
-  };
-  struct SlowLane {
-    bool live = false, done = false;
-    int level = -1;                  // the level its launches work on
-    int cap = 0;                     // entries of the current list: an upper bound of the flagged pairs
-    int list_sel = 0;                // which of the two list buffers is the current one (the other may still be read by launches in flight)
-    int seen = 0;                    // status words of the lane read so far (they complete in order: one stream)
-    int valid_from = 0;              // steps before this one say nothing about the lane's level as it is now (another level, or members have arrived since)
-    int last_active = -1;
-  } sl;
-  int tail_next = 0;                 // steps of the lane enqueued in this batch (index of its next status word, behind the chain's)
-  int main_level = level_from;       // the level the batch's own chain works on (below last_level: through)
-  unsigned char* const lane_flags = w.tail_flags.as<unsigned char>();
-  auto lane_list = [&](int sel) { return w.tail_list.as<int>() + size_t(sel) * align_up(size_t(n), 64); };
-  if (overlap_batch) launch_clear_flags(s, lane_flags, n);
-  auto tail_enqueue = [&](int count) {
-    const LevelSchedule ls = schedule_of(sl.level);
-    LevelGeom g = bp.geom[sl.level];
-    g.pair_list = lane_list(sl.list_sel);
-    const PairPtrs* pp = bp.pair_ptrs + size_t(sl.level) * n;
-    float* lp = w.tail_partials.as<float>();
-    float2* lscr = w.tail_scratch.as<float2>();
-    double* lll = w.tail_ll.as<double>();
-    for (int c = 0; c < count && size_t(tail_next) < tail_steps_cap; ++c, ++tail_next) {
-      const size_t idx = main_steps + size_t(tail_next);
-      launch_residual_reduce(w.tail_stream, ctx->opt_variant, bp.rpw[sl.level], sl.level == 0, g, pp, states, sl.cap, lp, lscr, w.win_fallbacks.as<unsigned long long>(),
-                             w.f16_range_flag);
-      if (!ls.fused_ll) launch_loglik(w.tail_stream, g, states, sl.cap, lp, lscr, lll, ls.ll_blocks, ctx->opt_deterministic != 0);
-      launch_solver_step(w.tail_stream, states, sl.cap, bp.prm, g, lp, lll, ls.ll_blocks, ls.fused_ll ? lscr : nullptr, d_levels, d_iters,
-                         tallies + idx, w.host_status + idx, false, cfg->first_level - sl.level, nullptr);
-      ctx->overlapped_steps += 1;
-    }
-    (void)hipEventRecord(w.tail_end, w.tail_stream);           // (the batch's end waits for the latest record: everything enqueued so far)
-  };
-  // what the lane's status words say by now, and what follows from it (never waits)
-  auto tail_service = [&]() {
-    if (!sl.live || sl.done) return;
-    while (sl.seen < tail_next) {
-      const int v = static_cast<volatile int*>(w.host_status)[main_steps + size_t(sl.seen)];
-      if (!(v & kStepDoneFlag)) break;
-      if (sl.seen >= sl.valid_from) sl.last_active = v & ~kStepDoneFlag;
-      sl.seen += 1;
-    }
-    if (sl.seen > sl.valid_from && sl.last_active == 0) {      // nobody of the lane is active on its level
-      if (sl.level <= main_level) return;                      // (the chain is still on it: its stragglers may yet arrive)
-      if (sl.level == cfg->last_level) {
-        sl.done = true;
-        return;
-      }
-      // on to the next level: the members that have left this one begin it (those that arrived further down are on theirs already)
-      const int lv = sl.level - 1;
-      launch_level_begin(w.tail_stream, states, n, bp.prm, bp.geom[lv], lv, bp.pair_ptrs + size_t(lv) * n, d_levels, nullptr, lane_flags, 1, sl.level);
-      sl.level = lv;
-      sl.valid_from = tail_next;
-      sl.last_active = -1;
-      tail_enqueue(3);
-      return;
-    }
-    if (tail_next - sl.seen < 2) tail_enqueue(2);
-  };
-  // the chain sheds the pairs still active on `level` (at most `active` of them) to the lane
-  auto tail_shed = [&](int level, int active) -> int {
-    Range range("shed");
-    const int next_sel = sl.live ? sl.list_sel ^ 1 : 0;
-    const int cap = std::min(n, sl.cap + active);
-    launch_mark_stragglers(s, states, n, level, lane_flags, lane_list(next_sel), cap);
-    DVO_WS_TRY(w, hipEventRecord(w.tail_split, s));
-    DVO_WS_TRY(w, hipStreamWaitEvent(w.tail_stream, w.tail_split, 0));
-    sl.cap = cap;
-    sl.list_sel = next_sel;
-    if (!sl.live) {
-      sl.live = true;
-      sl.level = level;
-    }
-    sl.valid_from = tail_next;                                 // (whatever level the lane is on: its launches read the new list from here on)
-    sl.last_active = -1;
-    tail_enqueue(3);
-    ctx->overlapped_tails += 1;
-    return DVO_HIP_OK;
-  };
-  // the chain's wait for a step, looking after the lane meanwhile
-  auto wait_main = [&](int idx, int* active) -> int {
-    if (!sl.live || sl.done) return wait_for_step(w, idx, active);
-    volatile int* word = w.host_status + idx;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 1;; ++spins) {
-      const int v = *word;
-      if (v & kStepDoneFlag) {
-        *active = v & ~kStepDoneFlag;
-        tail_service();
-        return DVO_HIP_OK;
-      }
-      if ((spins & 0x3f) == 0) tail_service();
-      if ((spins & 0xfffff) == 0) {
-        const int rc_check = step_wait_check(w, t0);
-        if (rc_check != DVO_HIP_OK) return rc_check;
-      }
-    }
-  };
+  return DVO_HIP_OK;
+}
 
-  for (int level = level_from; level >= cfg->last_level; --level) {
-    main_level = level;
-    LevelGeom g = bp.geom[level];
-    if (sl.live) g.skip_flags = lane_flags;                    // (the lane's pairs are not this chain's any more)
-    const PairPtrs* pp = bp.pair_ptrs + size_t(level) * n;
-    static const char* const kPrep[kMaxLevels] = {"prep L0", "prep L1", "prep L2", "prep L3", "prep L4", "prep L5", "prep L6", "prep L7"};
-    static const char* const kErr[kMaxLevels] = {"err L0", "err L1", "err L2", "err L3", "err L4", "err L5", "err L6", "err L7"};
-    static const char* const kLinsys[kMaxLevels] = {"linsys L0", "linsys L1", "linsys L2", "linsys L3", "linsys L4", "linsys L5", "linsys L6", "linsys L7"};
-    // Batches of up to 256 pairs: every level but the launch path's first is begun pair by pair by the solver steps of the level before
-    // it, and the results are written by the steps behind the last level (NextLevel) -- no launch between two levels, none at the end:
-    // builds alternated on one box, 16 / 64 / 128 pairs 0.558 -> 0.553 / 1.196 -> 1.187 / 1.825 -> 1.807 ms per step; 256 and 1024
-    // pairs level, 512 pairs 5.79 -> 5.88 (the launches k_level_begin / k_finish stay there)
-    const bool hand_over = policy.level_hand_over(n);
-    if (level == level_from || !hand_over) {
-      Range range(kPrep[level]);
-      // (the slow lane's pairs begin their levels there)
-      launch_level_begin(s, states, n, bp.prm, g, level, pp, d_levels, level == cfg->first_level ? w.t_init.as<double>() : nullptr,
-                         sl.live ? lane_flags : nullptr, 0);
+// ---- one level of the launch chain ---------------------------------------------------------------------------------------------------
+const char* const kRangePrep[kMaxLevels] = {"prep L0", "prep L1", "prep L2", "prep L3", "prep L4", "prep L5", "prep L6", "prep L7"};
+const char* const kRangeErr[kMaxLevels] = {"err L0", "err L1", "err L2", "err L3", "err L4", "err L5", "err L6", "err L7"};
+const char* const kRangeLinsys[kMaxLevels] = {"linsys L0", "linsys L1", "linsys L2", "linsys L3", "linsys L4", "linsys L5", "linsys L6", "linsys L7"};
+
+// what the chain's launches of a level share
+struct LevelRun {
+  int level = 0;
+  LevelGeom g;                                                 // every pair of the batch but the slow lane's
+  const PairPtrs* pp = nullptr;
+  NextLevel next;                                              // where the solver steps hand a pair that has left the level over to
+  LevelSchedule schedule;
+  bool tail = false;                                           // the step runs in the sweep's launch
+  double* pair_sums = nullptr;                                 // ... its wide half only (option "sweep_tail" 2)
+  // what the launches cover: every pair, or -- the level's last steps, see "hold" in chain_level -- the list of those still active
+  LevelGeom g_run;
+  int n_run = 0;
+};
+
+// One step in the sweep's launch (round 6): where the log-likelihood pass runs inside the solver step anyway and the level's sweep
+// has the instantiation, the workgroup that completes a pair's last tile runs the pair's step -- ONE launch per iteration
+// (option 2: the WIDE half of the step -- reduction and log-likelihood, its memory round trips -- in the sweep's tail, the serial half
+// in a one-wavefront launch behind it)
+void enqueue_step_in_sweep(BatchRun& b, const LevelRun& L) {
+  Workspace& w = b.w;
+  Range range(kRangeErr[L.level]);
+  const SolverStepArgs a = make_solver_step_args(b.states, b.n, b.bp.prm, b.partials, b.ll_partials, L.schedule.ll_blocks, b.scratch, b.d_levels, b.d_iters, b.tallies + b.step,
+                                                 w.host_status + b.step, b.cfg->first_level - L.level, &L.next, b.arrivals, L.pair_sums);
+  launch_residual_reduce(b.s, b.ctx->opt_variant, b.bp.rpw[L.level], L.level == 0, L.g, L.pp, b.states, b.n, b.partials, b.scratch, w.win_fallbacks.as<unsigned long long>(),
+                         w.f16_range_flag, &a);
+  if (L.pair_sums) {
+    Range range2(kRangeLinsys[L.level]);
+    launch_solver_serial(b.s, b.n, L.g, a);
+  }
+  b.ctx->tail_steps += 1;
+}
+
+// One step of the plain chain: the sweep, the passes of option "ref_order", the log-likelihood pass where it is a launch of its own, the
+// solver step
+void enqueue_step(BatchRun& b, const LevelRun& L) {
+  dvo_hip_context* ctx = b.ctx;
+  Workspace& w = b.w;
+  const bool fused_ll = L.schedule.fused_ll;
+  {
+    Range range(kRangeErr[L.level]);
+    launch_residual_reduce(b.s, ctx->opt_variant, b.bp.rpw[L.level], L.level == 0, L.g_run, L.pp, b.states, L.n_run, b.partials, b.scratch, w.win_fallbacks.as<unsigned long long>(),
+                           w.f16_range_flag);
+    if (b.ref_order) {
+      launch_ref_order(b.s, L.g_run, b.states, L.n_run, b.scratch, w.ref_rows.as<RefOrderSeg>(), b.ref_order);
+      ctx->ref_order_passes += 1;
     }
-    NextLevel next;
-    std::memset(&next, 0, sizeof(next));
-    if (hand_over && level > cfg->last_level) {
-      const LevelGeom& gn = bp.geom[level - 1];
-      next.valid = 1;
-      next.level = level - 1;
-      next.fx = gn.fx; next.fy = gn.fy; next.ox = gn.ox; next.oy = gn.oy;
-      next.pairs = bp.pair_ptrs + size_t(level - 1) * n;
-    } else if (hand_over) {
-      next.results = w.results.as<dvo_hip_result>();           // the last level: a pair that has left it gets its result written
-    }
-    // levels this small run the log-likelihood sweep inside the solver workgroup (one launch less per iteration)
-    // (measured, scripts/ab_match.py fused_ll_pixels: 128 pairs 2.152 -> 2.117 ms with level 1 fused; 16 pairs 0.756 -> 0.799, one
-    // pair 0.524 -> 0.547: a lone workgroup per pair is slower than 32 blocks when the chip is empty)
-    // (round 5, packed residual pairs, the streaming step beside its ingest, scripts/r5_midsize.py: level 1 in a launch of its own
-    // 64 pairs 1.456 -> 1.378 ms, 128 pairs 1.939 -> 1.908, 256 pairs 3.308 -> 3.286, 512 pairs 5.859 -> 5.880: fused from 512 pairs)
-    const LevelSchedule schedule = schedule_of(level);         // (the rule: schedule_of, above -- the slow lane runs its pairs by the same one)
-    const bool fused_ll = schedule.fused_ll;
-    // Chunks of `per_sync` iterations are enqueued ONE AHEAD of the poll: while the host waits for the status word of
-    // chunk k, chunk k+1 is already queued, so the GPU never idles for a host round trip.  Iterations enqueued past the
-    // end of the level are no-ops (workgroups exit on !active).
-    // workgroups per pair of the log-likelihood pass: each begins by reducing the pair's scale sums (a latency chain of ~10 us), which
-    // a batch that fills the device anyway pays once per workgroup for nothing -- fewer, longer ones then (option ll_blocks to override)
-    // (round 5, mid-size batches, scripts/r5_midsize.py: 16 instead of 32 workgroups per pair 64 / 128 / 200 pairs 1.179 -> 1.173 /
-    // 1.775 -> 1.760 / 2.558 -> 2.538 ms per step; 8: 1.183 / 1.760 / 2.546)
-    const int ll_blocks = schedule.ll_blocks;
-    // the solver step of the smallest levels in two-wavefront workgroups (four per compute unit instead of two): a batch that otherwise
-    // needs two goes of 512 resident workgroups (option solver_waves 2 / 4 to force; the records do not depend on it).  Measured at
-    // 1024 pairs (scripts/r4_trace.sh): 80 x 60 46 -> 36 us per step; 160 x 120 with packed residuals 77 -> 90 (two wavefronts walk
-    // its 96 slots in six rounds instead of three), 320 x 240 and the finest level level: those keep four.
-    const bool solver_two_waves = schedule.two_waves;
-    // The step in the sweep's launch (round 6): where the log-likelihood pass runs inside the solver step anyway and the level's sweep
-    // has the instantiation, the workgroup that completes a pair's last tile runs the pair's step -- ONE launch per iteration
-    const bool tail = ctx->opt_sweep_tail != 0 && fused_ll && sweep_has_tail(ctx->opt_variant, bp.rpw[level], g);
-    // (option 2: the WIDE half of the step -- reduction and log-likelihood, its memory round trips -- in the sweep's tail, the serial half
-    // in a one-wavefront launch behind it)
-    double* pair_sums = tail && ctx->opt_sweep_tail == 2 ? w.pair_sums.as<double>() : nullptr;
-    // (what the chain's launches of this level cover: every pair, or -- its last steps, see "hold" below -- the list of those still active)
-    LevelGeom g_run = g;
-    int n_run = n;
-    auto enqueue_chunk = [&](int count) {
-      for (int c = 0; c < count; ++c, ++step) {
-        if (tail) {
-          Range range(kErr[level]);
-          const SolverStepArgs a = make_solver_step_args(states, n, bp.prm, partials, ll_partials, ll_blocks, scratch, d_levels, d_iters, tallies + step, w.host_status + step,
-                                                         cfg->first_level - level, &next, arrivals, pair_sums);
-          launch_residual_reduce(s, ctx->opt_variant, bp.rpw[level], level == 0, g, pp, states, n, partials, scratch, w.win_fallbacks.as<unsigned long long>(),
-                                 w.f16_range_flag, &a);
-          if (pair_sums) {
-            Range range2(kLinsys[level]);
-            launch_solver_serial(s, n, g, a);
-          }
-          ctx->tail_steps += 1;
-          continue;
-        }
-        {
-          Range range(kErr[level]);
-          launch_residual_reduce(s, ctx->opt_variant, bp.rpw[level], level == 0, g_run, pp, states, n_run, partials, scratch, w.win_fallbacks.as<unsigned long long>(),
-                                 w.f16_range_flag);
-          if (ref_order) {
-            launch_ref_order(s, g_run, states, n_run, scratch, w.ref_rows.as<RefOrderSeg>(), ref_order);
-            ctx->ref_order_passes += 1;
-          }
-          if (!fused_ll) launch_loglik(s, g_run, states, n_run, partials, scratch, ll_partials, ll_blocks, ctx->opt_deterministic != 0, ref_order);
-        }
-        if (g_run.pair_list) ctx->listed_steps += 1;
-        Range range(kLinsys[level]);
-        launch_solver_step(s, states, n_run, bp.prm, g_run, partials, ll_partials, ll_blocks, fused_ll ? scratch : nullptr, d_levels, d_iters,
-                           tallies + step, w.host_status + step, solver_two_waves, cfg->first_level - level, &next, ref_order);   // (the level record every pair on this level is at: fetched with the state)
-      }
-    };
-    int enqueued = std::min(per_sync, per_level);
-    enqueue_chunk(enqueued);
-    // (option "defer_ingest_pixels": not before the chain has reached a level of that many pixels -- the frame build is bound by memory, and
-    // beside it the latency-bound sweeps and steps of the SMALL levels run 30-50 % longer (80 x 60: 52 -> 77 us, 160 x 120: 159 -> 212 us per
-    // 1024-pair launch), the issue-bound sweeps of the large ones 2 %: a large batch's ingest belongs beside levels 1 and 0)
-    const bool flush_here = ctx->opt_defer_ingest_pixels <= 0 || g.w * g.h >= ctx->opt_defer_ingest_pixels || level == cfg->last_level;
-    if (!ctx->deferred.empty() && flush_here) {
-      // A recorded ingest of the caller's next batch (option "defer_ingest") is carried out now, behind the first launches of this
-      // batch.  It is ~0.1-0.5 ms of host time during which nothing more would be enqueued here: where the level's steps are short,
-      // a few more of them go out first (a pair needs more than four passes on its first level; a step too many exits at once).
-      // (how many: the ingest of 2 n frames is ~0.3 us of host time per frame, a step of a small level ~20 us -- measured, builds
-      // alternated on one box: seven instead of three more 256 pairs 3.288 -> 3.216 ms per step, 128 pairs 1.837 -> 1.856, 64 pairs
-      // 1.199 -> 1.210)
-      if (size_t(g.tiles_x) * g.tiles_y * size_t(n) < 65536) {
-        const int lead = std::min(policy.deferred_ingest_lead(n) * per_sync, per_level - enqueued);
-        if (lead > 0) {
-          enqueue_chunk(lead);
-          enqueued += lead;
-        }
-      }
-      const int rc_deferred = flush_deferred(ctx);
-      if (rc_deferred != DVO_HIP_OK) {
-        w.err = ctx->err;
-        return rc_deferred;
+    if (!fused_ll) launch_loglik(b.s, L.g_run, b.states, L.n_run, b.partials, b.scratch, b.ll_partials, L.schedule.ll_blocks, ctx->opt_deterministic != 0, b.ref_order);
+  }
+  if (L.g_run.pair_list) ctx->listed_steps += 1;
+  Range range(kRangeLinsys[L.level]);
+  launch_solver_step(b.s, b.states, L.n_run, b.bp.prm, L.g_run, b.partials, b.ll_partials, L.schedule.ll_blocks, fused_ll ? b.scratch : nullptr, b.d_levels, b.d_iters,
+                     b.tallies + b.step, w.host_status + b.step, L.schedule.two_waves, b.cfg->first_level - L.level, &L.next, b.ref_order);   // (the level record every pair on this level is at: fetched with the state)
+}
+
+void enqueue_chunk(BatchRun& b, const LevelRun& L, int count) {
+  for (int c = 0; c < count; ++c, ++b.step) {
+    if (L.tail) enqueue_step_in_sweep(b, L);
+    else enqueue_step(b, L);
+  }
+}
+
+// The level's pairs begin it (by a launch, or the solver steps of the level before have done it), and what its steps share is put together.
+LevelRun begin_level(BatchRun& b, SlowLane& lane, int level) {
+  const dvo_hip_context* ctx = b.ctx;
+  const dvo_hip_config* cfg = b.cfg;
+  const BatchPlan& bp = b.bp;
+  const int n = b.n;
+  LevelRun L;
+  L.level = level;
+  L.g = bp.geom[level];
+  if (lane.skip_flags()) L.g.skip_flags = lane.skip_flags();   // (the lane's pairs are not this chain's any more)
+  L.pp = bp.pair_ptrs + size_t(level) * n;
+  // Batches of up to 256 pairs: every level but the launch path's first is begun pair by pair by the solver steps of the level before
+  // it, and the results are written by the steps behind the last level (NextLevel) -- no launch between two levels, none at the end:
+  // builds alternated on one box, 16 / 64 / 128 pairs 0.558 -> 0.553 / 1.196 -> 1.187 / 1.825 -> 1.807 ms per step; 256 and 1024
+  // pairs level, 512 pairs 5.79 -> 5.88 (the launches k_level_begin / k_finish stay there)
+  const bool hand_over = b.policy.level_hand_over(n);
+  if (level == b.level_from || !hand_over) {
+    Range range(kRangePrep[level]);
+    // (the slow lane's pairs begin their levels there)
+    launch_level_begin(b.s, b.states, n, bp.prm, L.g, level, L.pp, b.d_levels, level == cfg->first_level ? b.w.t_init.as<double>() : nullptr,
+                       lane.skip_flags(), 0);
+  }
+  std::memset(&L.next, 0, sizeof(L.next));
+  if (hand_over && level > cfg->last_level) {
+    const LevelGeom& gn = bp.geom[level - 1];
+    L.next.valid = 1;
+    L.next.level = level - 1;
+    L.next.fx = gn.fx; L.next.fy = gn.fy; L.next.ox = gn.ox; L.next.oy = gn.oy;
+    L.next.pairs = bp.pair_ptrs + size_t(level - 1) * n;
+  } else if (hand_over) {
+    L.next.results = b.w.results.as<dvo_hip_result>();         // the last level: a pair that has left it gets its result written
+  }
+  L.schedule = schedule_of(b, level);
+  L.tail = ctx->opt_sweep_tail != 0 && L.schedule.fused_ll && sweep_has_tail(ctx->opt_variant, bp.rpw[level], L.g);   // (enqueue_step_in_sweep)
+  L.pair_sums = L.tail && ctx->opt_sweep_tail == 2 ? b.w.pair_sums.as<double>() : nullptr;
+  L.g_run = L.g;
+  L.n_run = n;
+  return L;
+}
+
+// One level of the chain: its steps go out until no pair is left on it, or the slow lane has taken the last ones.
+int chain_level(BatchRun& b, SlowLane& lane, int level) {
+  dvo_hip_context* ctx = b.ctx;
+  const dvo_hip_config* cfg = b.cfg;
+  const int n = b.n, per_sync = b.per_sync, per_level = b.per_level;
+  lane.chain_enters(level);
+  LevelRun L = begin_level(b, lane, level);
+  const LevelGeom& g = L.g;
+  const bool hand_over = b.policy.level_hand_over(n);
+  // Chunks of `per_sync` iterations are enqueued ONE AHEAD of the poll: while the host waits for the status word of
+  // chunk k, chunk k+1 is already queued, so the GPU never idles for a host round trip.  Iterations enqueued past the
+  // end of the level are no-ops (workgroups exit on !active).
+  int enqueued = std::min(per_sync, per_level);
+  enqueue_chunk(b, L, enqueued);
+  // (option "defer_ingest_pixels": not before the chain has reached a level of that many pixels -- the frame build is bound by memory, and
+  // beside it the latency-bound sweeps and steps of the SMALL levels run 30-50 % longer (80 x 60: 52 -> 77 us, 160 x 120: 159 -> 212 us per
+  // 1024-pair launch), the issue-bound sweeps of the large ones 2 %: a large batch's ingest belongs beside levels 1 and 0)
+  const bool flush_here = ctx->opt_defer_ingest_pixels <= 0 || g.w * g.h >= ctx->opt_defer_ingest_pixels || level == cfg->last_level;
+  if (!ctx->deferred.empty() && flush_here) {
+    // A recorded ingest of the caller's next batch (option "defer_ingest") is carried out now, behind the first launches of this
+    // batch.  It is ~0.1-0.5 ms of host time during which nothing more would be enqueued here: where the level's steps are short,
+    // a few more of them go out first (a pair needs more than four passes on its first level; a step too many exits at once).
+    // (how many: the ingest of 2 n frames is ~0.3 us of host time per frame, a step of a small level ~20 us -- measured, builds
+    // alternated on one box: seven instead of three more 256 pairs 3.288 -> 3.216 ms per step, 128 pairs 1.837 -> 1.856, 64 pairs
+    // 1.199 -> 1.210)
+    if (size_t(g.tiles_x) * g.tiles_y * size_t(n) < 65536) {
+      const int lead = std::min(b.policy.deferred_ingest_lead(n) * per_sync, per_level - enqueued);
+      if (lead > 0) {
+        enqueue_chunk(b, L, lead);
+        enqueued += lead;
       }
     }
-    int watched = step - 1;                                  // last step of the chunk whose outcome is awaited
-    // (the slow lane: every level but the last may shed its stragglers to it -- on the last one nothing follows that they could run beside)
-    const bool list_tails = ctx->opt_tail_lists != 0 && !bp.ref_order && !tail && !hand_over && sweep_takes_pair_list(ctx->opt_variant, bp.rpw[level], g);
-    const bool may_shed = overlap_batch && level > cfg->last_level && !tail && sweep_takes_pair_list(ctx->opt_variant, bp.rpw[level], g);
-    // Where an EMPTY step is expensive -- the dispatcher needs 95 us for the 307 200 workgroups of a 1024-pair finest-level sweep
-    // that all exit at once, 114 us with its log-likelihood and solver launches -- the step ahead of the poll is not enqueued once
-    // only a few pairs are left on the level: the host then waits for the outcome first (a bubble of ~15 us if another step is
-    // needed).  Elsewhere the speculative step is cheaper than the bubble.
-    const bool empty_step_is_costly = size_t(g.tiles_x) * g.tiles_y * size_t(n) >= (ctx->opt_tail_speculation >= 2 ? size_t(ctx->opt_tail_speculation) : kCostlyEmptyStepWorkgroups) && ctx->opt_tail_speculation != 1;
-    int last_active = n;
-    for (;;) {
-      const bool hold = empty_step_is_costly && last_active * 8 <= n;
-      int more = hold ? 0 : std::min(per_sync, per_level - enqueued);
+    const int rc_deferred = flush_recorded_ingest(b);
+    if (rc_deferred != DVO_HIP_OK) return rc_deferred;
+  }
+  int watched = b.step - 1;                                  // last step of the chunk whose outcome is awaited
+  // (the slow lane: every level but the last may shed its stragglers to it -- on the last one nothing follows that they could run beside)
+  const bool list_tails = ctx->opt_tail_lists != 0 && !b.bp.ref_order && !L.tail && !hand_over && sweep_takes_pair_list(ctx->opt_variant, b.bp.rpw[level], g);
+  const bool may_shed = lane.on() && level > cfg->last_level && !L.tail && sweep_takes_pair_list(ctx->opt_variant, b.bp.rpw[level], g);
+  // Where an EMPTY step is expensive -- the dispatcher needs 95 us for the 307 200 workgroups of a 1024-pair finest-level sweep
+  // that all exit at once, 114 us with its log-likelihood and solver launches -- the step ahead of the poll is not enqueued once
+  // only a few pairs are left on the level: the host then waits for the outcome first (a bubble of ~15 us if another step is
+  // needed).  Elsewhere the speculative step is cheaper than the bubble.
+  const bool empty_step_is_costly = size_t(g.tiles_x) * g.tiles_y * size_t(n) >= (ctx->opt_tail_speculation >= 2 ? size_t(ctx->opt_tail_speculation) : kCostlyEmptyStepWorkgroups) && ctx->opt_tail_speculation != 1;
+  int last_active = n;
+  for (;;) {
+    const bool hold = empty_step_is_costly && last_active * 8 <= n;
+    int more = hold ? 0 : std::min(per_sync, per_level - enqueued);
+    if (more > 0) {
+      enqueue_chunk(b, L, more);
+      enqueued += more;
+    }
+    int active = 0;
+    int rc = lane.wait(watched, &active);
+    if (rc != DVO_HIP_OK) return rc;
+    last_active = active;
+    if (may_shed && active > 0 && size_t(active) * size_t(ctx->opt_overlap_fraction) <= size_t(n)) {
+      // the pairs still on the level (at most `active`: the steps enqueued ahead of this poll only take some away) go to the slow lane
+      rc = lane.shed(level, active);
+      if (rc != DVO_HIP_OK) return rc;
+      break;
+    }
+    if (hold && active > 0) {                                // (the held-back step is needed after all)
+      // ... by `active` pairs, none of whose steps is in flight: from here on the launches cover the list of them
+      if (list_tails && !L.g_run.pair_list) {
+        int* const own_list = b.w.chain_list.as<int>();
+        launch_mark_stragglers(b.s, b.states, n, level, lane.skip_flags(), own_list, active, true);
+        L.g_run.pair_list = own_list;
+        L.n_run = active;
+      }
+      more = std::min(per_sync, per_level - enqueued);
       if (more > 0) {
-        enqueue_chunk(more);
+        enqueue_chunk(b, L, more);
         enqueued += more;
       }
-      int active = 0;
-      rc = wait_main(watched, &active);
-      if (rc != DVO_HIP_OK) return rc;
-      last_active = active;
-      if (may_shed && active > 0 && size_t(active) * size_t(ctx->opt_overlap_fraction) <= size_t(n)) {
-        // the pairs still on the level (at most `active`: the steps enqueued ahead of this poll only take some away) go to the slow lane
-        rc = tail_shed(level, active);
-        if (rc != DVO_HIP_OK) return rc;
-        break;
-      }
-      if (hold && active > 0) {                              // (the held-back step is needed after all)
-        // ... by `active` pairs, none of whose steps is in flight: from here on the launches cover the list of them
-        if (list_tails && !g_run.pair_list) {
-          int* const own_list = w.tail_list.as<int>() + 2 * align_up(size_t(n), 64);
-          launch_mark_stragglers(s, states, n, level, sl.live ? lane_flags : nullptr, own_list, active, true);
-          g_run.pair_list = own_list;
-          n_run = active;
-        }
-        more = std::min(per_sync, per_level - enqueued);
-        if (more > 0) {
-          enqueue_chunk(more);
-          enqueued += more;
-        }
-      }
-      if (active == 0 || more <= 0) break;                   // every pair left this level (or the iteration cap is reached)
-      watched = step - 1;
     }
-    // The pairs that ended the level in the step just awaited are handed over (NextLevel) by the step that was enqueued ahead of the poll.
-    // If there is none -- the step was held back, or the iteration cap is reached -- one solver launch does nothing else.
-    if (hand_over && step - 1 <= watched) {
-      Range range(kLinsys[level]);
-      launch_solver_step(s, states, n, bp.prm, g, partials, ll_partials, ll_blocks, nullptr, d_levels, d_iters, tallies + step, w.host_status + step,
-                         solver_two_waves, cfg->first_level - level, &next, ref_order);
-      ++step;
-    }
+    if (active == 0 || more <= 0) break;                     // every pair left this level (or the iteration cap is reached)
+    watched = b.step - 1;
   }
+  // The pairs that ended the level in the step just awaited are handed over (NextLevel) by the step that was enqueued ahead of the poll.
+  // If there is none -- the step was held back, or the iteration cap is reached -- one solver launch does nothing else.
+  if (hand_over && b.step - 1 <= watched) {
+    Range range(kRangeLinsys[level]);
+    launch_solver_step(b.s, b.states, n, b.bp.prm, g, b.partials, b.ll_partials, L.schedule.ll_blocks, nullptr, b.d_levels, b.d_iters, b.tallies + b.step, b.w.host_status + b.step,
+                       L.schedule.two_waves, cfg->first_level - level, &L.next, b.ref_order);
+    ++b.step;
+  }
+  return DVO_HIP_OK;
+}
 
-  if (sl.live) {
-    // the chain is through; the slow lane runs its pairs to the end of the match (from here on it may leave any level)
-    main_level = cfg->last_level - 1;
-    const auto t_wait = std::chrono::steady_clock::now();
-    tail_service();
-    while (!sl.done) {
-      if (tail_next == 0 || size_t(tail_next) >= tail_steps_cap) {
-        w.err = "match: the slow lane of the batch ran out of steps";
-        return DVO_HIP_ERR_HIP;
-      }
-      int unused = 0;
-      rc = wait_for_step(w, int(main_steps) + tail_next - 1, &unused);
-      if (rc != DVO_HIP_OK) return rc;
-      tail_service();
-    }
-    ctx->tail_drains += 1;
-    ctx->tail_wait_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t_wait).count();
-    DVO_WS_TRY(w, hipStreamWaitEvent(s, w.tail_end, 0));       // (k_finish and the copies below follow the lane's last step)
-  }
-  const bool resident_used = rp.levels > 0;
+// ---- the way out -------------------------------------------------------------------------------------------------------------------------
+// where the batch's records are on the host once the device is through, and when the host got there
+struct CopyOut {
   std::vector<dvo_hip_level_stats> hl;
   std::vector<dvo_hip_iteration_stats> hi;
   const dvo_hip_level_stats* hl_src = nullptr;
   const dvo_hip_iteration_stats* hi_src = nullptr;
   std::chrono::steady_clock::time_point t_enqueued, t_done;
-  if (rp.direct) {
+};
+
+// The results into the caller's array, the statistics to where copy_statistics finds them: straight out of pinned memory (the resident
+// kernel's direct path) or by copies on the stream behind the last launch; the batch is over on the device when this returns.
+int copy_out(BatchRun& b, dvo_hip_result* results, bool want_levels, bool want_iters, CopyOut& out) {
+  Workspace& w = b.w;
+  const int n = b.n;
+  if (b.rp.direct) {
     // the kernel writes results (and statistics) into pinned host memory and counts the pairs done: the host thread watches that
     // word -- no copy command, no stream synchronisation on the way out
-    t_enqueued = std::chrono::steady_clock::now();
-    rc = wait_for_direct(w, n);
+    out.t_enqueued = std::chrono::steady_clock::now();
+    const int rc = wait_for_direct(w, n);
     w.device_may_lag = true;
     if (rc != DVO_HIP_OK) return rc;
-    t_done = std::chrono::steady_clock::now();
+    out.t_done = std::chrono::steady_clock::now();
     if (w.host_status[w.resident_error_word] == 0) {
       std::memcpy(results, w.direct_results.p, size_t(n) * sizeof(dvo_hip_result));
-      if (levels && cap_levels > 0) hl_src = w.direct_levels.as<dvo_hip_level_stats>();
-      if (iters && cap_iters > 0) hi_src = w.direct_iters.as<dvo_hip_iteration_stats>();
+      if (want_levels) out.hl_src = w.direct_levels.as<dvo_hip_level_stats>();
+      if (want_iters) out.hi_src = w.direct_iters.as<dvo_hip_iteration_stats>();
     } else {
-      DVO_WS_TRY(w, sync_stream(s));                           // every group has to be gone before the batch is repeated
+      DVO_WS_TRY(w, sync_stream(b.s));                         // every group has to be gone before the batch is repeated
     }
-  } else {
-    if (level_from >= cfg->last_level && policy.finish_launch(n)) launch_finish(s, states, n, bp.prm, d_levels, d_iters, w.results.as<dvo_hip_result>());
-    // (else the results are in place: written by the resident launch, or by the solver steps behind the pairs' last level)
-    DVO_WS_TRY(w, hipMemcpyAsync(results, w.results.p, size_t(n) * sizeof(dvo_hip_result), hipMemcpyDeviceToHost, s));
-    if (levels && cap_levels > 0) {
-      hl.resize(size_t(n) * bp.cap_levels);
-      DVO_WS_TRY(w, hipMemcpyAsync(hl.data(), d_levels, hl.size() * sizeof(dvo_hip_level_stats), hipMemcpyDeviceToHost, s));
-      hl_src = hl.data();
-    }
-    if (iters && cap_iters > 0) {
-      hi.resize(size_t(n) * bp.cap_iters);
-      DVO_WS_TRY(w, hipMemcpyAsync(hi.data(), d_iters, hi.size() * sizeof(dvo_hip_iteration_stats), hipMemcpyDeviceToHost, s));
-      hi_src = hi.data();
-    }
-    t_enqueued = std::chrono::steady_clock::now();
-    DVO_WS_TRY(w, sync_stream(s));
-    DVO_WS_TRY(w, hipGetLastError());
-    t_done = std::chrono::steady_clock::now();
+    return DVO_HIP_OK;
   }
-  if (resident_used && w.host_status[w.resident_error_word] != 0) {
+  if (b.level_from >= b.cfg->last_level && b.policy.finish_launch(n)) launch_finish(b.s, b.states, n, b.bp.prm, b.d_levels, b.d_iters, w.results.as<dvo_hip_result>());
+  // (else the results are in place: written by the resident launch, or by the solver steps behind the pairs' last level)
+  DVO_WS_TRY(w, hipMemcpyAsync(results, w.results.p, size_t(n) * sizeof(dvo_hip_result), hipMemcpyDeviceToHost, b.s));
+  if (want_levels) {
+    out.hl.resize(size_t(n) * b.bp.cap_levels);
+    DVO_WS_TRY(w, hipMemcpyAsync(out.hl.data(), b.d_levels, out.hl.size() * sizeof(dvo_hip_level_stats), hipMemcpyDeviceToHost, b.s));
+    out.hl_src = out.hl.data();
+  }
+  if (want_iters) {
+    out.hi.resize(size_t(n) * b.bp.cap_iters);
+    DVO_WS_TRY(w, hipMemcpyAsync(out.hi.data(), b.d_iters, out.hi.size() * sizeof(dvo_hip_iteration_stats), hipMemcpyDeviceToHost, b.s));
+    out.hi_src = out.hi.data();
+  }
+  out.t_enqueued = std::chrono::steady_clock::now();
+  DVO_WS_TRY(w, sync_stream(b.s));
+  DVO_WS_TRY(w, hipGetLastError());
+  out.t_done = std::chrono::steady_clock::now();
+  return DVO_HIP_OK;
+}
+
+// every pair's statistics into the caller's arrays, as far as those reach; true: some did not fit
+bool copy_statistics(const BatchRun& b, const CopyOut& out, const dvo_hip_result* results, dvo_hip_level_stats* levels, int cap_levels,
+                     dvo_hip_iteration_stats* iters, int cap_iters) {
+  bool truncated = false;
+  for (int i = 0; i < b.n; ++i) {
+    if (out.hl_src) {
+      const int nl = std::min(results[i].n_levels, std::min(cap_levels, b.bp.cap_levels));
+      std::memcpy(levels + size_t(i) * cap_levels, out.hl_src + size_t(i) * b.bp.cap_levels, size_t(nl) * sizeof(dvo_hip_level_stats));
+      truncated |= results[i].n_levels > cap_levels;
+    }
+    if (out.hi_src) {
+      const int ni = std::min(results[i].n_iterations_total, std::min(cap_iters, b.bp.cap_iters));
+      std::memcpy(iters + size_t(i) * cap_iters, out.hi_src + size_t(i) * b.bp.cap_iters, size_t(ni) * sizeof(dvo_hip_iteration_stats));
+      truncated |= results[i].n_iterations_total > cap_iters;
+    }
+  }
+  return truncated;
+}
+
+int run_batch(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_frame* const* curs, const dvo_hip_config* cfg,
+              dvo_hip_result* results, dvo_hip_level_stats* levels, int cap_levels, dvo_hip_iteration_stats* iters, int cap_iters);
+
+// What the three repeats of a batch share: `m` pairs of it (pair k is the batch's pair which[k]; null: all of them, in place) get their
+// initial guesses back, the roles are ensured again (another path or sweep may read another flavour of the current planes), and the
+// pairs run as a batch.  What makes the second run another one -- an option, the Gram schedule -- the caller has set.
+int run_again(const BatchRun& b, int m, const int* which, dvo_hip_frame* const* refs, dvo_hip_frame* const* curs, dvo_hip_result* results,
+              dvo_hip_level_stats* levels, int cap_levels, dvo_hip_iteration_stats* iters, int cap_iters) {
+  for (int k = 0; k < m; ++k) std::memcpy(results[k].transformation, &b.tinit[size_t(which ? which[k] : k) * 16], 16 * sizeof(double));
+  int rc = ensure_batch_roles(b.ctx, m, refs, curs, b.cfg);
+  if (rc == DVO_HIP_OK) rc = run_batch(b.ctx, m, refs, curs, b.cfg, results, levels, cap_levels, iters, cap_iters);
+  return rc;
+}
+
+// the pairs whose word in the f16 range array a sweep has raised; the words are cleared
+std::vector<int> take_out_of_range(const BatchRun& b) {
+  std::vector<int> out_of_range;
+  if (b.ctx->opt_variant >= 7)
+    for (int i = 0; i < b.n; ++i)
+      if (static_cast<volatile int*>(b.w.f16_range_flag)[i] != 0) {
+        static_cast<volatile int*>(b.w.f16_range_flag)[i] = 0;
+        out_of_range.push_back(i);
+      }
+  return out_of_range;
+}
+
+// the flagged pairs again, f32 Gram, as a batch of their own; their records replace the ones just copied out.  DVO_HIP_ERR_CAPACITY:
+// their statistics did not fit either (the results are valid).
+int repeat_out_of_range(const BatchRun& b, const std::vector<int>& out_of_range, dvo_hip_frame* const* refs, dvo_hip_frame* const* curs,
+                        dvo_hip_result* results, dvo_hip_level_stats* levels, int cap_levels, dvo_hip_iteration_stats* iters, int cap_iters) {
+  dvo_hip_context* ctx = b.ctx;
+  const int m = int(out_of_range.size());
+  ctx->f16_range_repeats += m;
+  std::vector<dvo_hip_frame*> r2(m), c2(m);
+  std::vector<dvo_hip_result> res2(m);
+  for (int k = 0; k < m; ++k) {
+    const int i = out_of_range[k];
+    r2[k] = refs[i];
+    c2[k] = curs[i];
+    res2[k] = results[i];
+  }
+  const bool want_l = levels && cap_levels > 0, want_i = iters && cap_iters > 0;
+  std::vector<dvo_hip_level_stats> l2(want_l ? size_t(m) * cap_levels : 0);
+  std::vector<dvo_hip_iteration_stats> i2(want_i ? size_t(m) * cap_iters : 0);
+  ctx->opt_variant = 6;                                        // (restored by run_batch's variant_scope)
+  const int rc = run_again(b, m, out_of_range.data(), r2.data(), c2.data(), res2.data(), want_l ? l2.data() : nullptr, cap_levels, want_i ? i2.data() : nullptr, cap_iters);
+  if (rc != DVO_HIP_OK && rc != DVO_HIP_ERR_CAPACITY) return rc;
+  for (int k = 0; k < m; ++k) {
+    const int i = out_of_range[k];
+    results[i] = res2[k];
+    if (want_l) std::memcpy(levels + size_t(i) * cap_levels, l2.data() + size_t(k) * cap_levels, size_t(cap_levels) * sizeof(dvo_hip_level_stats));
+    if (want_i) std::memcpy(iters + size_t(i) * cap_iters, i2.data() + size_t(k) * cap_iters, size_t(cap_iters) * sizeof(dvo_hip_iteration_stats));
+  }
+  return rc;
+}
+
+// The coarse-to-fine Gauss-Newton driver of a batch (dense_tracking.cpp:131-376 for every pair at once).
+int run_batch(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_frame* const* curs, const dvo_hip_config* cfg,
+              dvo_hip_result* results, dvo_hip_level_stats* levels, int cap_levels, dvo_hip_iteration_stats* iters, int cap_iters) {
+  // (the Gram schedule of the batch -- f16 high + low operand pairs or f32 -- was decided by the caller, effective_variant_scope; what
+  // this function changes for a repeat is undone when it returns)
+  struct VariantScope {
+    dvo_hip_context* c; int keep;
+    ~VariantScope() { c->opt_variant = keep; }
+  } variant_scope{ctx, ctx->opt_variant};
+  BatchRun b(ctx, cfg, n);
+  Workspace& w = b.w;
+  SlowLane lane(b);
+  int rc = prepare_batch(b, lane, refs, curs, results);
+  if (rc != DVO_HIP_OK) return rc;
+  const auto t_launch = std::chrono::steady_clock::now();
+  const bool want_levels = levels && cap_levels > 0, want_iters = iters && cap_iters > 0;
+  ResidentBudget::Hold compute_units;                          // released when this batch is through with the device
+  if (b.rp.levels > 0 && b.rp.group > 1)
+    compute_units.take(ResidentBudget::of(ctx->device), n * b.rp.group, ctx->compute_units > 0 ? ctx->compute_units : 256);
+  rc = run_prefixes(b, want_levels || want_iters);
+  if (rc != DVO_HIP_OK) return rc;
+  lane.begin(b.level_from);
+  for (int level = b.level_from; level >= cfg->last_level; --level) {
+    rc = chain_level(b, lane, level);
+    if (rc != DVO_HIP_OK) return rc;
+  }
+  rc = lane.drain();
+  if (rc != DVO_HIP_OK) return rc;
+  CopyOut out;
+  rc = copy_out(b, results, want_levels, want_iters, out);
+  if (rc != DVO_HIP_OK) return rc;
+  if (b.rp.levels > 0 && w.host_status[w.resident_error_word] != 0) {
     // A group of the resident kernel gave up waiting for its peers: its workgroups were not all on the device at once (the
     // device is shared with another process that does the same, or a compute-unit mask shrank it).  Nothing is wrong with the
     // batch: it runs again, one launch per step, and the context stops using groups.
@@ -1040,12 +1092,10 @@ int run_batch(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_f
     // (not after a single incident: a launch that started late once -- the device busy with another process for a moment -- is no
     // reason to give up the latency path for the rest of the context's life)
     if (ctx->resident_timeouts >= 3) ctx->opt_resident_group = 1;
-    for (int i = 0; i < n; ++i) std::memcpy(results[i].transformation, &tinit[size_t(i) * 16], 16 * sizeof(double));
     const int keep = ctx->opt_resident;
     ctx->opt_resident = 0;
     w.needs_drain = true;
-    rc = ensure_batch_roles(ctx, n, refs, curs, cfg);          // (the launch path may read another flavour of the current planes)
-    if (rc == DVO_HIP_OK) rc = run_batch(ctx, n, refs, curs, cfg, results, levels, cap_levels, iters, cap_iters);
+    rc = run_again(b, n, nullptr, refs, curs, results, levels, cap_levels, iters, cap_iters);   // (the launch path may read another flavour of the current planes)
     ctx->opt_resident = keep;
     return rc;
   }
@@ -1054,76 +1104,31 @@ int run_batch(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_f
   // family (variant 6): the whole batch when most of it is concerned (one chain of launches either way; the batches that follow then
   // start on the f32 Gram, kF32GramHoldBatches), otherwise ONLY the flagged pairs, as a batch of their own, behind the copy-out below
   // (round 5: a single close depth step used to repeat all 1024 pairs of a batch).
-  std::vector<int> out_of_range;
-  if (ctx->opt_variant >= 7)
-    for (int i = 0; i < n; ++i)
-      if (static_cast<volatile int*>(w.f16_range_flag)[i] != 0) {
-        static_cast<volatile int*>(w.f16_range_flag)[i] = 0;
-        out_of_range.push_back(i);
-      }
+  const std::vector<int> out_of_range = take_out_of_range(b);
   // (the repeats below prepare role planes and run another batch: two groups of one batch -- dvo_hip_match_batch -- do not do that at once)
   std::unique_lock<std::mutex> rare_path;
   if (!out_of_range.empty()) rare_path = std::unique_lock<std::mutex>(g_rare_path_mutex);
   if (!out_of_range.empty() && out_of_range.size() * 2 >= size_t(n)) {
     ctx->f16_range_repeats += (long long)out_of_range.size();
     ctx->f32_gram_hold = kF32GramHoldBatches;
-    for (int i = 0; i < n; ++i) std::memcpy(results[i].transformation, &tinit[size_t(i) * 16], 16 * sizeof(double));
     ctx->opt_variant = 6;                                      // (restored by variant_scope)
-    rc = ensure_batch_roles(ctx, n, refs, curs, cfg);          // (another sweep, maybe another flavour of the current planes)
-    if (rc != DVO_HIP_OK) return rc;
-    return run_batch(ctx, n, refs, curs, cfg, results, levels, cap_levels, iters, cap_iters);
+    return run_again(b, n, nullptr, refs, curs, results, levels, cap_levels, iters, cap_iters);   // (another sweep, maybe another flavour of the current planes)
   }
-  bool truncated = false;
-  for (int i = 0; i < n; ++i) {
-    if (hl_src) {
-      const int nl = std::min(results[i].n_levels, std::min(cap_levels, bp.cap_levels));
-      std::memcpy(levels + size_t(i) * cap_levels, hl_src + size_t(i) * bp.cap_levels, size_t(nl) * sizeof(dvo_hip_level_stats));
-      truncated |= results[i].n_levels > cap_levels;
-    }
-    if (hi_src) {
-      const int ni = std::min(results[i].n_iterations_total, std::min(cap_iters, bp.cap_iters));
-      std::memcpy(iters + size_t(i) * cap_iters, hi_src + size_t(i) * bp.cap_iters, size_t(ni) * sizeof(dvo_hip_iteration_stats));
-      truncated |= results[i].n_iterations_total > cap_iters;
-    }
-  }
+  bool truncated = copy_statistics(b, out, results, levels, cap_levels, iters, cap_iters);
   {
     using std::chrono::duration_cast;
     using std::chrono::nanoseconds;
     ctx->host_ns[0] += duration_cast<nanoseconds>(t_launch - ctx->batch_entry).count();
-    ctx->host_ns[1] += duration_cast<nanoseconds>(t_enqueued - t_launch).count();
-    ctx->host_ns[2] += duration_cast<nanoseconds>(t_done - t_enqueued).count();
-    ctx->host_ns[3] += duration_cast<nanoseconds>(std::chrono::steady_clock::now() - t_done).count();
+    ctx->host_ns[1] += duration_cast<nanoseconds>(out.t_enqueued - t_launch).count();
+    ctx->host_ns[2] += duration_cast<nanoseconds>(out.t_done - out.t_enqueued).count();
+    ctx->host_ns[3] += duration_cast<nanoseconds>(std::chrono::steady_clock::now() - out.t_done).count();
     ctx->host_batches += 1;
   }
   w.needs_drain = false;
   if (!out_of_range.empty()) {
-    // the flagged pairs again, f32 Gram, as a batch of their own; their records replace the ones just copied out
-    const int m = int(out_of_range.size());
-    ctx->f16_range_repeats += m;
-    std::vector<dvo_hip_frame*> r2(m), c2(m);
-    std::vector<dvo_hip_result> res2(m);
-    for (int k = 0; k < m; ++k) {
-      const int i = out_of_range[k];
-      r2[k] = refs[i];
-      c2[k] = curs[i];
-      res2[k] = results[i];
-      std::memcpy(res2[k].transformation, &tinit[size_t(i) * 16], 16 * sizeof(double));
-    }
-    const bool want_l = levels && cap_levels > 0, want_i = iters && cap_iters > 0;
-    std::vector<dvo_hip_level_stats> l2(want_l ? size_t(m) * cap_levels : 0);
-    std::vector<dvo_hip_iteration_stats> i2(want_i ? size_t(m) * cap_iters : 0);
-    ctx->opt_variant = 6;                                      // (restored by variant_scope)
-    rc = ensure_batch_roles(ctx, m, r2.data(), c2.data(), cfg);
-    if (rc == DVO_HIP_OK)
-      rc = run_batch(ctx, m, r2.data(), c2.data(), cfg, res2.data(), want_l ? l2.data() : nullptr, cap_levels, want_i ? i2.data() : nullptr, cap_iters);
+    rc = repeat_out_of_range(b, out_of_range, refs, curs, results, levels, cap_levels, iters, cap_iters);
     if (rc != DVO_HIP_OK && rc != DVO_HIP_ERR_CAPACITY) return rc;
     truncated |= rc == DVO_HIP_ERR_CAPACITY;
-    for (int k = 0; k < m; ++k) {
-      const int i = out_of_range[k];
-      results[i] = res2[k];
-      if (want_l) std::memcpy(levels + size_t(i) * cap_levels, l2.data() + size_t(k) * cap_levels, size_t(cap_levels) * sizeof(dvo_hip_level_stats));
-      if (want_i) std::memcpy(iters + size_t(i) * cap_iters, i2.data() + size_t(k) * cap_iters, size_t(cap_iters) * sizeof(dvo_hip_iteration_stats));
-    }
   }
   if (truncated) {
     w.err = "match: statistics arrays too small (results are valid)";
@@ -1131,4 +1136,3 @@ int run_batch(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, dvo_hip_f
   }
   return DVO_HIP_OK;
 }
-
