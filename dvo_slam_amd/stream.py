@@ -65,6 +65,13 @@ class StreamPipeline:
         self.L.dvo_stream_pack_records(self.n, self.cres, self._records.ctypes.data_as(C.POINTER(C.c_double)))
         return self._records
 
+    def set_device_planes(self, grey_ref, depth_ref, grey_cur, depth_cur):
+        """Other device addresses (n pointers each) for the raw planes of the batches step() ingests from now on: a caller whose
+        batches arrive in buffers of their own.  The planes a step read stay unchanged until the match of the frames they fed has returned."""
+        ptrs = [device_pointer_array(p) for p in (grey_ref, depth_ref, grey_cur, depth_cur)]
+        assert all(len(p) == self.n for p in ptrs), "n device pointers per role"
+        self.ptrs = ptrs
+
     def set_host_planes(self, grey_ref, depth_ref, grey_cur, depth_cur):
         """Host arrays (pinned, uint8 / uint16, C-contiguous, n each) the raw planes of every batch are DMA-ed from by step_host."""
         vp = C.c_void_p
