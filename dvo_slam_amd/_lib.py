@@ -141,6 +141,10 @@ PIXEL_CHANNELS = {"bgr8": 3, "rgb8": 3, "bgra8": 4, "rgba8": 4}
 # ... and of the image plane that comes with a float depth plane (dvo_hip_frames_update_colour_f32depth*): grey8 as well
 MIXED_PIXEL_FORMATS = dict(PIXEL_FORMATS, grey8=0)
 MIXED_PIXEL_CHANNELS = dict(PIXEL_CHANNELS, grey8=1)
+# the raw sensor formats every pixel_format argument takes as well (dvo_hip.h, DVO_HIP_PIXEL_BAYER_* / _YUYV8 / _UYVY8): Bayer mosaics,
+# named by the 2 x 2 block at the image's top-left corner, and YUV 4:2:2; their bytes per pixel
+SENSOR_PIXEL_FORMATS = {"bayer_rggb8": 16, "bayer_bggr8": 17, "bayer_gbrg8": 18, "bayer_grbg8": 19, "yuyv8": 20, "uyvy8": 21}
+SENSOR_PIXEL_CHANNELS = {"bayer_rggb8": 1, "bayer_bggr8": 1, "bayer_gbrg8": 1, "bayer_grbg8": 1, "yuyv8": 2, "uyvy8": 2}
 PIXEL_F32 = 5
 DEPTH_U16, DEPTH_F32 = 0, 1
 DEPTH_FORMATS = {"u16": DEPTH_U16, "f32": DEPTH_F32}

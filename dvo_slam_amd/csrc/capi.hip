@@ -29,6 +29,7 @@
 #include "device_types.h"
 #include "batch_policy.h"
 #include "colour.h"
+#include "sensor_formats.h"
 #include "launch.h"
 #include "pose_graph.h"
 #include "ref_order.h"
@@ -410,6 +411,7 @@ struct dvo_hip_context {
   long long f16_range_repeats = 0; // batches repeated with the f32 Gram because a Jacobian left the f16 range (counter "f16_range_repeats")
   long long strip_ingests = 0;     // frames ingested by the strip kernel (ingest_strips.hip), counter "strip_ingests"
   long long colour_ingests = 0;    // frames ingested from an 8-bit colour plane (colour.h), counter "colour_ingests"
+  long long sensor_ingests = 0;    // frames ingested from a raw sensor plane (sensor_formats.h), counter "sensor_ingests"
   long long f32_ingests = 0;       // frames ingested from a float depth plane (DVO_HIP_DEPTH_F32), counter "f32_ingests"
   long long lens_ingests = 0;      // frames rectified at ingest (dvo_hip_frames_set_lens), counter "lens_ingests"
   long long depth_registrations = 0;   // frames whose depth was registered at ingest (dvo_hip_frames_set_depth_rig), counter "depth_registrations"
@@ -534,6 +536,7 @@ struct dvo_hip_context {
   DevBuf sel_tbl_main, sel_tbl_build;                 // tables of the caller-selection apply pass, one per stream (apply_selection)
   unsigned long long sel_visits = 0;
   DevBuf lens_tbl;                                    // table of the rectify pass (rectify_frames; allocated by the first lens ingest)
+  DevBuf sensor_tbl;                                  // table of the sensor-format pass (sensor_frames; allocated by the first sensor ingest)
   DevBuf graph_jobs, graph_outs;                      // the job records and results of a resident pose-graph launch (capi_graph.inc)
   DevBuf rig_tbl;                                     // table of the register pass (register_frames; allocated by the first rig ingest)
   DevBuf colour_tbl, colour_stage;                    // the plane table of a k_colour_pack launch and the staging area of host colour planes (capi_colour.inc)
@@ -911,7 +914,7 @@ void dvo_hip_context_destroy(dvo_hip_context* ctx) {
   if (ctx->build_stream) (void)hipStreamDestroy(ctx->build_stream);
   for (DevBuf& b : ctx->build_tbl) b.release();
   for (DevBuf* b : {&ctx->misc, &ctx->role_tbl_cur, &ctx->role_tbl_ref, &ctx->prep_tbl_cur, &ctx->prep_tbl_ref, &ctx->rcp_table, &ctx->ref_order_planes,
-                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl, &ctx->rig_tbl, &ctx->graph_jobs, &ctx->graph_outs, &ctx->map_tbl, &ctx->map_stage, &ctx->colour_tbl, &ctx->colour_stage, &ctx->render_tbl, &ctx->render_zbuf, &ctx->render_planes}) b->release();
+                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl, &ctx->sensor_tbl, &ctx->rig_tbl, &ctx->graph_jobs, &ctx->graph_outs, &ctx->map_tbl, &ctx->map_stage, &ctx->colour_tbl, &ctx->colour_stage, &ctx->render_tbl, &ctx->render_zbuf, &ctx->render_planes}) b->release();
   if (ctx->render_done) (void)hipEventDestroy(ctx->render_done);
   for (DevBuf& b : ctx->upload_buf) b.release();
   for (const dvo_hip_context::PooledBlock& b : ctx->frame_pool) (void)hipFree(b.p);

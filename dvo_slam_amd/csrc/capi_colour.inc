@@ -8,7 +8,9 @@ int dvo_hip_frames_set_colour(dvo_hip_context* ctx, int n_frames, dvo_hip_frame*
   const char* who = "frames_set_colour";
   int rc = check_frame_list(ctx, n_frames, frames, who, /*own_context=*/true);
   if (rc != DVO_HIP_OK) return rc;
-  const int channels = pixel_channels(pixel_format);
+  // (a sensor format -- a Bayer mosaic, YUV 4:2:2, sensor_formats.h -- is converted by k_sensor_convert in place of k_colour_pack)
+  const bool sensor = sensor_bytes(pixel_format) != 0;
+  const int channels = sensor ? sensor_bytes(pixel_format) : pixel_channels(pixel_format);
   if (channels == 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "unknown pixel format");
   if (!colour) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
   long long blocks = 0;
@@ -19,6 +21,7 @@ int dvo_hip_frames_set_colour(dvo_hip_context* ctx, int n_frames, dvo_hip_frame*
     const size_t row = size_t(f->lv[0].w) * size_t(channels);
     if (colour_pitch != 0 && colour_pitch < row) return fail(ctx, DVO_HIP_ERR_INVALID, who, "colour_pitch < width * channels");
     if (colour_pitch > size_t(INT_MAX)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "colour_pitch is too large");
+    if (sensor_is_yuv(pixel_format) && f->lv[0].w % 2 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a YUV 4:2:2 plane needs an even width");
     if (f->lens_on)
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a lens takes raw sensor planes; its colour must be attached rectified (clear the lens first, or attach to a frame without one)");
     for (int k = 0; k < i; ++k)
@@ -64,9 +67,44 @@ int dvo_hip_frames_set_colour(dvo_hip_context* ctx, int n_frames, dvo_hip_frame*
     p.first_block = at_block;
     at_block += (w * h + 255) / 256;
   }
-  rc = upload_block_table(ctx, ctx->colour_tbl, host, at_block);
-  if (rc != DVO_HIP_OK) return rc;
-  launch_colour_pack(ctx->stream, ctx->colour_tbl.as<ColourPlane>(), n_frames, at_block, pixel_format);
+  if (sensor) {
+    // one launch per frame size (k_sensor_convert takes frames of one size): the table lists the frames size by size, each launch reads
+    // its own run of it
+    std::vector<SensorPtrs> table;
+    std::vector<int> order;
+    for (int i = 0; i < n_frames; ++i) {
+      if (std::find(order.begin(), order.end(), i) != order.end()) continue;
+      for (int k = i; k < n_frames; ++k)
+        if (host[size_t(k)].w == host[size_t(i)].w && host[size_t(k)].h == host[size_t(i)].h && host[size_t(k)].pitch == host[size_t(i)].pitch) order.push_back(k);
+    }
+    for (int k : order) table.push_back(SensorPtrs{host[size_t(k)].src, host[size_t(k)].dst});
+    const size_t bytes = table.size() * sizeof(SensorPtrs);
+    DVO_HIP_TRY(ctx, ctx->colour_tbl.reserve(bytes));
+    DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->colour_tbl.p, table.data(), bytes));
+    for (size_t at = 0; at < order.size();) {
+      const ColourPlane& first = host[size_t(order[at])];
+      SensorArgs a;
+      a.w = first.w;
+      a.h = first.h;
+      a.pitch = first.pitch;
+      a.format = pixel_format;
+      a.src_dwords = 1;
+      a.dst_wide = a.w % 4 == 0 ? 1 : 0;
+      size_t end = at;
+      for (; end < order.size(); ++end) {
+        const ColourPlane& p = host[size_t(order[end])];
+        if (p.w != a.w || p.h != a.h || p.pitch != a.pitch) break;
+        if (!sensor_src_dwords(p.src, size_t(p.pitch))) a.src_dwords = 0;
+        if (!aligned_to(p.dst, 16)) a.dst_wide = 0;
+      }
+      launch_sensor_convert(ctx->stream, ctx->colour_tbl.as<SensorPtrs>() + at, int(end - at), a, /*packed=*/true, 0, false);
+      at = end;
+    }
+  } else {
+    rc = upload_block_table(ctx, ctx->colour_tbl, host, at_block);
+    if (rc != DVO_HIP_OK) return rc;
+    launch_colour_pack(ctx->stream, ctx->colour_tbl.as<ColourPlane>(), n_frames, at_block, pixel_format);
+  }
   DVO_HIP_TRY(ctx, hipGetLastError());
   // the caller's memory, host or device, may be reused when the call returns
   DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -393,6 +393,32 @@ int register_frames(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, c
   return DVO_HIP_OK;
 }
 
+// The sensor-format pass of n frames fed a Bayer mosaic or a YUV 4:2:2 plane (sensor_formats.h, sensor_convert.hip), on the build stream:
+// the caller's planes -> the 8-bit grey of their BGR8 image in each frame's own u8 staging plane (staging_grey: no steady-state call
+// allocates; nothing the context owns but the pointer table).  What follows in frames_build reads a tight grey8 source at that address.
+int sensor_frames(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource& src) {
+  const CameraGeom* cam = frames[0]->cam;
+  std::vector<SensorPtrs> host(static_cast<size_t>(n));
+  SensorArgs a;
+  a.w = cam->w[0];
+  a.h = cam->h[0];
+  a.pitch = int(src.pitch);
+  a.format = src.format;
+  a.src_dwords = 1;
+  a.dst_wide = a.w % 4 == 0 ? 1 : 0;
+  for (int i = 0; i < n; ++i) {
+    host[size_t(i)] = SensorPtrs{static_cast<const uint8_t*>(src.planes[i]), staging_grey(frames[i])};
+    if (!sensor_src_dwords(src.planes[i], src.pitch)) a.src_dwords = 0;
+    if (!aligned_to(staging_grey(frames[i]), 4)) a.dst_wide = 0;
+  }
+  const size_t bytes = host.size() * sizeof(SensorPtrs);
+  DVO_HIP_TRY(ctx, ctx->sensor_tbl.reserve(bytes));
+  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->build_stream, ctx->sensor_tbl.p, host.data(), bytes));
+  launch_sensor_convert(ctx->build_stream, ctx->sensor_tbl.as<SensorPtrs>(), n, a, /*packed=*/false, ctx->opt_build_workgroups, ctx->opt_stream_policy != 0);
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  return DVO_HIP_OK;
+}
+
 // src: device planes whose pitch is resolved, of frames that share camera and levels (check_ingest has seen to both).  From a colour
 // source the kernels convert and leave grey in the frames' raw copies.
 int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource* src, int role = -1, float ithr = 0.0f,
@@ -410,6 +436,25 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
   // read their halo rows from it.  That is harmless only because the conversion is the identity here -- float depth of scale 1, z * 1.0f,
   // keeps every bit pattern, a NaN's payload included (kDepthRigHole is a quiet NaN) -- so a halo read sees the same bits before and
   // after a neighbour's store.  A conversion that changes any bit would need keep_planes 0 for Z, as under a lens.
+  // Frames fed a sensor format (a Bayer mosaic, YUV 4:2:2): the caller's plane is converted into the frames' own u8 staging plane first,
+  // and everything below -- the rig pass, the lens pass, the ingest -- takes a tight grey8 source at that address with the caller's depth:
+  // the frame ends as one fed the grey of the format's BGR8 image through the grey entry points would.  The raw-copy bookkeeping below
+  // needs no case of its own.  With u16 depth the source is not "in place" (the depth plane is the caller's), so an ingest that keeps a
+  // copy gets keep_grey = the staging plane it reads and keep_raw beside it: every lane stores the grey bytes it loaded back where it
+  // loaded them from, while other waves read their halo rows there -- harmless for the reason given for the rig's plane Z below, the
+  // store changes no bit -- and the copy is complete (raw_copy true).  An ingest that keeps none leaves raw_copy false, whatever the
+  // staging plane holds.  With float depth the copy is the float planes (keep_planes), as for any grey8 + float-depth ingest.
+  const bool sensor = src != nullptr && sensor_bytes(src->format) != 0;
+  std::vector<const void*> grey_planes;
+  IngestSource converted;
+  if (sensor) {
+    const int rc = sensor_frames(ctx, n, frames, *src);
+    if (rc != DVO_HIP_OK) return rc;
+    grey_planes.resize(size_t(n));
+    for (int i = 0; i < n; ++i) grey_planes[size_t(i)] = staging_grey(frames[i]);
+    converted = IngestSource{grey_planes.data(), 0, size_t(cam->w[0]), src->depth, src->depth_scale, src->depth_format, src->depth_pitch};
+    src = &converted;
+  }
   const bool rig = src != nullptr && frames[0]->rig_on;
   std::vector<const void*> reg_planes;
   IngestSource registered;
@@ -529,6 +574,7 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
     }
     if (strips) ctx->strip_ingests += n;
     if (colour) ctx->colour_ingests += n;
+    if (sensor) ctx->sensor_ingests += n;
     if (depth_f32) ctx->f32_ingests += n;
     if (lens) ctx->lens_ingests += n;
     if (rig) ctx->depth_registrations += n;

@@ -5,22 +5,28 @@
 // namespace does not keep a function's name out of the library's symbol table: the helpers are static.
 
 // bytes per pixel of an IngestSource's image plane, 0 for an unknown format
-static int source_channels(int format) { return format == 0 ? 1 : format == DVO_HIP_PIXEL_F32 ? 4 : pixel_channels(format); }
+static int source_channels(int format) {
+  return format == 0 ? 1 : format == DVO_HIP_PIXEL_F32 ? 4 : sensor_bytes(format) ? sensor_bytes(format) : pixel_channels(format);
+}
+// the pixel_format argument of a colour entry point as an IngestSource's format: 0 is grey in here and no DVO_HIP_PIXEL_* to a caller.
+// The colour formats and the sensor formats (sensor_formats.h)
+static int colour_format(int pixel_format) { return pixel_channels(pixel_format) || sensor_bytes(pixel_format) ? pixel_format : -1; }
 // the pixel_format argument of a float-depth entry point: DVO_HIP_PIXEL_GREY8 (0) is the grey plane there
-static int mixed_format(int pixel_format) { return pixel_format == DVO_HIP_PIXEL_GREY8 || pixel_channels(pixel_format) ? pixel_format : -1; }
-// the pixel_format argument of a colour entry point as an IngestSource's format: 0 is grey in here and no DVO_HIP_PIXEL_* to a caller
-static int colour_format(int pixel_format) { return pixel_channels(pixel_format) ? pixel_format : -1; }
+static int mixed_format(int pixel_format) { return pixel_format == DVO_HIP_PIXEL_GREY8 ? pixel_format : colour_format(pixel_format); }
 
-// The planes of an ingest of n frames `width` pixels wide: format, arrays and their entries, the pitch rules; resolves src->pitch.  With
+// The planes of an ingest of n frames of width x height pixels: format, arrays and their entries, the pitch rules; resolves src->pitch.  With
 // `frames` (entries not null), in the same pass: they share camera and levels -- a camera is shared by frames of any level count
 // (get_camera), and frames_build writes one table and launches once per level for all of them.
-static int check_source(dvo_hip_context* ctx, const char* who, int n, dvo_hip_frame* const* frames, int width, IngestSource* src) {
+static int check_source(dvo_hip_context* ctx, const char* who, int n, dvo_hip_frame* const* frames, int width, int height, IngestSource* src) {
   const int channels = src->format < 0 ? 0 : source_channels(src->format);
   if (channels == 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "unknown pixel format (DVO_HIP_PIXEL_*)");
   const bool image_f32 = src->format == DVO_HIP_PIXEL_F32, depth_f32 = src->depth_format == DVO_HIP_DEPTH_F32;
   if (!depth_f32 && src->depth_format != DVO_HIP_DEPTH_U16) return fail(ctx, DVO_HIP_ERR_INVALID, who, "unknown depth format (DVO_HIP_DEPTH_*)");
   if (image_f32 && !depth_f32) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a float image plane needs a float depth plane");
   if (!src->planes || !src->depth) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null argument");
+  // (sensor_formats.h: the reflection needs two samples a side, a YUV 4:2:2 row is made of pixel pairs)
+  if (sensor_is_bayer(src->format) && (width < 2 || height < 2)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a Bayer plane needs width >= 2 and height >= 2");
+  if (sensor_is_yuv(src->format) && width % 2 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a YUV 4:2:2 plane needs an even width");
   for (int i = 0; i < n; ++i) {
     if (frames && (!frames[i] || frames[i]->cam != frames[0]->cam || frames[i]->levels != frames[0]->levels))
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "frames of one build batch must share camera and levels");
@@ -87,7 +93,7 @@ static int check_ingest(dvo_hip_context* ctx, const char* who, int n_frames, dvo
     const int rc = check_prepare_args(ctx, n_frames, frames, role, cfg, who);
     if (rc != DVO_HIP_OK) return rc;
   }
-  return check_source(ctx, who, n_frames, frames, frames[0]->lv[0].w, src);
+  return check_source(ctx, who, n_frames, frames, frames[0]->lv[0].w, frames[0]->lv[0].h, src);
 }
 
 namespace {   // (flush_deferred is declared there at the head of capi.hip, for DVO_FLUSH_DEFERRED)
@@ -235,7 +241,7 @@ enum CreateRoute {
 static int frame_create_raw(dvo_hip_context* ctx, const char* who, int width, int height, const float K[4], int levels, IngestSource src, CreateRoute route,
                             dvo_hip_frame** out) {
   if (!ctx || !out || !K) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null argument");
-  int rc = check_source(ctx, who, 1, nullptr, width, &src);
+  int rc = check_source(ctx, who, 1, nullptr, width, height, &src);
   if (rc != DVO_HIP_OK) return rc;
   size_t raw_off;
   dvo_hip_frame* f = nullptr;

@@ -33,6 +33,7 @@ int dvo_hip_get_counter(dvo_hip_context* ctx, const char* key, long long* value)
   }
   else if (std::strcmp(key, "strip_ingests") == 0) *value = ctx->strip_ingests;
   else if (std::strcmp(key, "colour_ingests") == 0) *value = ctx->colour_ingests;
+  else if (std::strcmp(key, "sensor_ingests") == 0) *value = ctx->sensor_ingests;
   else if (std::strcmp(key, "f32_ingests") == 0) *value = ctx->f32_ingests;
   else if (std::strcmp(key, "lens_ingests") == 0) *value = ctx->lens_ingests;
   // (frames whose depth plane went through a depth rig, register_frames; and the bytes of the pass's pointer table: 0 until the first one)

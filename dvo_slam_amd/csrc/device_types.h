@@ -189,6 +189,21 @@ struct DepthRigArgs {
   float depth_scale;
 };
 
+// one frame of the sensor-format pass (k_sensor_convert, sensor_convert.hip; sensor_formats.h; include/dvo_hip.h, DVO_HIP_PIXEL_BAYER_* /
+// _YUYV8 / _UYVY8): the caller's sensor plane and the tight plane that receives the converted image
+struct SensorPtrs {
+  const uint8_t* src;                  // a Bayer mosaic (1 B per pixel) or a YUV 4:2:2 plane (2), rows of SensorArgs::pitch bytes
+  void* dst;                           // w * h bytes of grey, or w * h packed pixels 0x00RRGGBB (cloud_colour.h)
+};
+// ... and what the frames of one launch share
+struct SensorArgs {
+  int w, h;
+  int pitch;                           // bytes
+  int format;                          // DVO_HIP_PIXEL_BAYER_* / _YUYV8 / _UYVY8
+  int src_dwords;                      // every src and the pitch are 4-byte aligned: a lane loads its pixels as dwords, else byte by byte
+  int dst_wide;                        // w % 4 == 0 and every dst is aligned to a lane's store (4 B of grey, 16 B of packed pixels)
+};
+
 // one frame of a keyframe-map launch (k_world_points, k_map_insert, cloud_map.hip; include/dvo_hip.h, dvo_hip_map_insert / _remove / _move):
 // where the {I, Z} pairs of the level lie, the pose and the level's geometry.  Frames of different sizes share a launch: each owns the
 // workgroups first_block .. first_block + ceil(w * h / 256) - 1 (the table ends with one more entry that carries only the launch's block

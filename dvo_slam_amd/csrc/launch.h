@@ -77,6 +77,12 @@ void launch_rectify(hipStream_t s, const RectifyPtrs* tbl, int n_frames, const R
 void launch_depth_register(hipStream_t s, const DepthRigPtrs* tbl, int n_frames, const DepthRigArgs& a, bool depth_f32, int max_workgroups,
                            bool stream_nt);
 
+// sensor_convert.hip: the sensor planes (Bayer mosaics, YUV 4:2:2) of n frames of one size into tight planes of grey (packed false: the
+// ingest's pre-pass) or of packed pixels (packed true: dvo_hip_frames_set_colour), sensor_formats.h.  a.src_dwords / a.dst_wide: what
+// sensor_src_dwords and the caller's look at the destinations say.  stream_nt: planes read and written with the non-temporal policy
+bool sensor_src_dwords(const void* plane, size_t pitch);
+void launch_sensor_convert(hipStream_t s, const SensorPtrs* tbl, int n_frames, const SensorArgs& a, bool packed, int max_workgroups, bool stream_nt);
+
 // the grid of a kernel that walks `items` elements with a grid stride, 256 per workgroup: 1 .. 8192 workgroups
 inline int stride_grid(unsigned long long items) {
   const unsigned long long blocks = (items + 255) / 256;

@@ -276,7 +276,8 @@ class RgbdImagePyramid:
     def set_colour(self, colour, pixel_format="bgr8", pitch=0):
         """Colour of this frame (include/dvo_hip.h, dvo_hip_frames_set_colour; the reference's level(0).rgb, benchmark_slam.cpp:89-90): a
         (height, width, 3 | 4) uint8 numpy array (rows may be padded), or a device address (e.g. torch_tensor.data_ptr()) of height rows
-        of `pitch` bytes (0 = tight).  pixel_format: "bgr8" | "rgb8" | "bgra8" | "rgba8".  What a KeyframeMap(colour=True) fuses.  Kept
+        of `pitch` bytes (0 = tight).  pixel_format: "bgr8" | "rgb8" | "bgra8" | "rgba8", or a raw sensor format (see
+        RgbdCameraPyramid.create_colour; the colour stored is that of its BGR8 image).  What a KeyframeMap(colour=True) fuses.  Kept
         across re-ingests until replaced or cleared: re-attach after re-ingesting other content.  A pyramid with a lens refuses."""
         set_colour_batch([self], [colour], pixel_format, pitch)
 
@@ -376,9 +377,12 @@ class RgbdCameraPyramid:
     def create_colour(self, colour_u8, depth_u16, pixel_format="bgr8", depth_scale=1.0 / 5000.0, timestamp=0.0):
         """Ingest of an 8-bit colour plane [h, w, 3 | 4] + the u16 depth plane: the CV_BGR2GRAY conversion the reference's callers run on
         the host (benchmark_slam.cpp:55-69) happens on the device (dvo_hip_frame_create_colour).  pixel_format: "bgr8" | "rgb8" |
-        "bgra8" | "rgba8"; rows may be padded (a view with a larger row stride), pixels must be contiguous."""
-        fmt, ch = _pixel_format(pixel_format)
-        Cl = _colour_plane(colour_u8, self.height, self.width, ch)
+        "bgra8" | "rgba8"; rows may be padded (a view with a larger row stride), pixels must be contiguous.  Or a raw sensor plane as the
+        camera driver publishes it (_lib.SENSOR_PIXEL_FORMATS): a Bayer mosaic "bayer_rggb8" | "bayer_bggr8" | "bayer_gbrg8" |
+        "bayer_grbg8", [h, w] or [h, w, 1] uint8, or YUV 4:2:2 "yuyv8" | "uyvy8", [h, w, 2] uint8 with an even w -- demosaicked / converted
+        on the device (csrc/sensor_formats.h); so with every other pixel_format argument of this module."""
+        fmt, ch = _pixel_format(pixel_format, self.width, self.height)
+        Cl = _colour_plane(colour_u8, self.height, self.width, ch, flat_ok=pixel_format in _lib.SENSOR_PIXEL_FORMATS)
         D = _depth_plane(depth_u16, self.height, self.width)
 
         def make(levels):
@@ -391,7 +395,7 @@ class RgbdCameraPyramid:
 
     def create_colour_device(self, colour_dev_ptr, pixel_format, pitch, depth_dev_ptr, depth_scale=1.0 / 5000.0, timestamp=0.0):
         """A colour plane already resident in HBM (device pointer, row pitch in bytes, 0 = tight) + the u16 depth plane."""
-        fmt, ch = _pixel_format(pixel_format)
+        fmt, ch = _pixel_format(pixel_format, self.width, self.height)
         pitch = _pitch(pitch, self.width, ch)
 
         def make(levels):
@@ -419,9 +423,22 @@ class RgbdCameraPyramid:
         return RgbdImagePyramid(self, make, self.levels, timestamp)
 
 
-def _pixel_format(name):
+def _sensor_format(name, width, height):
+    """a raw sensor format (_lib.SENSOR_PIXEL_FORMATS) for planes of width x height pixels: the library's own size rules, raised here"""
+    fmt, ch = _lib.SENSOR_PIXEL_FORMATS[name], _lib.SENSOR_PIXEL_CHANNELS[name]
+    if ch == 1 and (width < 2 or height < 2):
+        raise ValueError("a Bayer plane needs width >= 2 and height >= 2, not %d x %d" % (width, height))
+    if ch == 2 and width % 2 != 0:
+        raise ValueError("a YUV 4:2:2 plane needs an even width, not %d" % width)
+    return fmt, ch
+
+
+def _pixel_format(name, width, height):
+    """(DVO_HIP_PIXEL_*, bytes per pixel) of a colour or a raw sensor format for planes of width x height pixels"""
+    if isinstance(name, str) and name in _lib.SENSOR_PIXEL_FORMATS:
+        return _sensor_format(name, width, height)
     if not isinstance(name, str) or name not in _lib.PIXEL_FORMATS:
-        raise ValueError("pixel_format must be one of %s, not %r" % (sorted(_lib.PIXEL_FORMATS), name))
+        raise ValueError("pixel_format must be one of %s, not %r" % (sorted(_lib.PIXEL_FORMATS) + sorted(_lib.SENSOR_PIXEL_FORMATS), name))
     return _lib.PIXEL_FORMATS[name], _lib.PIXEL_CHANNELS[name]
 
 
@@ -432,10 +449,13 @@ def _pitch(pitch, width, channels):
     return pitch
 
 
-def _colour_plane(a, h, w, channels):
-    """a colour image [h, w, channels] of uint8 with contiguous pixels (rows may be padded)"""
+def _colour_plane(a, h, w, channels, flat_ok=False):
+    """a colour image [h, w, channels] of uint8 with contiguous pixels (rows may be padded); flat_ok: a one-byte plane (a Bayer mosaic)
+    may also come as [h, w]"""
     if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
         raise TypeError("colour plane must be a numpy uint8 array")
+    if flat_ok and channels == 1 and a.shape == (h, w):
+        return a if a.strides[1] == 1 and a.strides[0] >= w else np.ascontiguousarray(a)
     if a.shape != (h, w, channels):
         raise ValueError("colour plane must have shape %s, not %s" % ((h, w, channels), a.shape))
     if a.strides[1:] != (channels, 1) or a.strides[0] < w * channels:
@@ -654,10 +674,12 @@ def clear_depth_rig_batch(pyramids):
 def _colour_sources(pyramids, sources, pixel_format, pitch, who="set_colour"):
     """(format, pitch, on_device, addresses, what to keep alive during the call, what each pyramid remembers) of a set_colour call, or
     ValueError / TypeError: nothing reaches the library with a value it would refuse"""
-    fmt, ch = _pixel_format(pixel_format)
     n = len(pyramids)
     if n < 1:
         raise ValueError("%s: no pyramids" % who)
+    for p in pyramids:
+        fmt, ch = _pixel_format(pixel_format, p.camera.width, p.camera.height)
+    flat_ok = pixel_format in _lib.SENSOR_PIXEL_FORMATS
     if sources is None or len(sources) != n:
         raise ValueError("%s: one colour plane per pyramid" % who)
     if isinstance(pitch, bool) or not isinstance(pitch, (int, np.integer)):
@@ -675,7 +697,7 @@ def _colour_sources(pyramids, sources, pixel_format, pitch, who="set_colour"):
     if all(arrays):
         if int(pitch) != 0:
             raise ValueError("%s: a numpy array brings its own row stride; pitch is for device addresses" % who)
-        planes = [_colour_plane(a, p.camera.height, p.camera.width, ch) for a, p in zip(sources, pyramids)]
+        planes = [_colour_plane(a, p.camera.height, p.camera.width, ch, flat_ok) for a, p in zip(sources, pyramids)]
         tight = all(a.strides[0] == p.camera.width * ch for a, p in zip(planes, pyramids))
         if not tight and len(set(a.strides[0] for a in planes)) != 1:
             planes, tight = [np.ascontiguousarray(a) for a in planes], True   # (one pitch per call: mixed paddings go tight)
@@ -1516,10 +1538,12 @@ def _depth_format(name):
     return _lib.DEPTH_FORMATS[name]
 
 
-def _mixed_pixel_format(name):
-    """the image formats that come with a float depth plane: the colour formats and "grey8" ([h, w] or [h, w, 1] uint8)"""
+def _mixed_pixel_format(name, width, height):
+    """the image formats that come with a float depth plane: the colour formats, the raw sensor formats and "grey8" ([h, w, 1] uint8)"""
+    if isinstance(name, str) and name in _lib.SENSOR_PIXEL_FORMATS:
+        return _sensor_format(name, width, height)
     if not isinstance(name, str) or name not in _lib.MIXED_PIXEL_FORMATS:
-        raise ValueError("pixel_format must be one of %s, not %r" % (sorted(_lib.MIXED_PIXEL_FORMATS), name))
+        raise ValueError("pixel_format must be one of %s, not %r" % (sorted(_lib.MIXED_PIXEL_FORMATS) + sorted(_lib.SENSOR_PIXEL_FORMATS), name))
     return _lib.MIXED_PIXEL_FORMATS[name], _lib.MIXED_PIXEL_CHANNELS[name]
 
 
@@ -1597,8 +1621,8 @@ def update_colour_device_batch(pyramids, colour_dev_ptrs, depth_dev_ptrs, pixel_
     depth_format "f32": the depth planes are float32 metres with NaN = hole and a row pitch of their own (depth_pitch, bytes, 0 = tight;
     dvo_hip_frames_update_colour_f32depth_device_as_ex); pixel_format may then also be "grey8".  Mind depth_scale: 1.0 for metres."""
     zf = _depth_format(depth_format) == _lib.DEPTH_F32
-    fmt, ch = _mixed_pixel_format(pixel_format) if zf else _pixel_format(pixel_format)
     pyr0 = pyramids[0]
+    fmt, ch = (_mixed_pixel_format if zf else _pixel_format)(pixel_format, pyr0.camera.width, pyr0.camera.height)
     pitch = _pitch(pitch, pyr0.camera.width, ch)
     if zf:
         depth_pitch = _f32_pitch(depth_pitch, pyr0.camera.width, "depth")
@@ -1625,13 +1649,13 @@ def update_colour_host_batch(pyramids, colour_host, depth_host, pixel_format="bg
     depth_format "f32": the depth planes are [h, w] float32 views (metres, NaN = hole; rows may be padded by the same stride;
     dvo_hip_frames_update_colour_f32depth_as_ex); pixel_format may then also be "grey8" ([h, w, 1] uint8).  Mind depth_scale: 1.0 for metres."""
     zf = _depth_format(depth_format) == _lib.DEPTH_F32
-    fmt, ch = _mixed_pixel_format(pixel_format) if zf else _pixel_format(pixel_format)
     cam = pyramids[0].camera
+    fmt, ch = (_mixed_pixel_format if zf else _pixel_format)(pixel_format, cam.width, cam.height)
     if len(colour_host) != len(pyramids) or len(depth_host) != len(pyramids):
         raise ValueError("one colour and one depth plane per pyramid")
     if zf and int(flags) & _lib.INGEST_DEFER:
         raise ValueError("INGEST_DEFER takes device planes")
-    cols = [_colour_plane(a, cam.height, cam.width, ch) for a in colour_host]
+    cols = [_colour_plane(a, cam.height, cam.width, ch, pixel_format in _lib.SENSOR_PIXEL_FORMATS) for a in colour_host]
     deps = [_f32_plane(b, cam.height, cam.width, "depth") if zf else _depth_plane(b, cam.height, cam.width) for b in depth_host]
     if any(a is not b for a, b in zip(cols, colour_host)) or any(a is not b for a, b in zip(deps, depth_host)):
         raise ValueError("host planes must be usable in place (pixels contiguous, depth C-contiguous): the transfer is asynchronous")

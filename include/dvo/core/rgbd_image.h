@@ -187,6 +187,8 @@ class RgbdCameraPyramid {
   // before create (dvo_benchmark/src/benchmark_slam.cpp:55-69) and the depth scaling happen on the device (dvo_hip_frame_create_colour);
   // the device frame is built here, with every level the size admits.  Level 0's host intensity / depth matrices are downloaded from
   // the device like those of the other levels: when the pyramid is built with host mirrors on, else by syncHostMirrors().
+  // pixel_format may also be a raw sensor format -- DVO_HIP_PIXEL_BAYER_{RGGB8, BGGR8, GBRG8, GRBG8} (1 byte per pixel) or
+  // DVO_HIP_PIXEL_YUYV8 / _UYVY8 (2, even width): the plane a camera driver publishes as image_raw, demosaicked / converted on the device.
   inline RgbdImagePyramidPtr createFromColour(const void* colour, int pixel_format, size_t colour_pitch, const uint16_t* raw_depth,
                                               float depth_scale = 1.0f / 5000.0f);
   // not in the reference: the pyramid of two float planes that already live in DEVICE memory (both tight; intensity 0..255, depth in
@@ -436,8 +438,8 @@ class RgbdImagePyramid {
   bool hasDepthRig() const { return has_rig_; }
   // ---- the colour of this frame (include/dvo_hip.h, dvo_hip_frames_set_colour; the reference keeps the camera image in level(0).rgb,
   // dvo_benchmark/src/benchmark_slam.cpp:89-90, and AsyncPointCloudBuilder reads it, async_point_cloud_builder.cpp:72-104).  setColour:
-  // an 8-bit plane of the frame's level-0 size, rows `pitch` bytes apart (0 = tight), format DVO_HIP_PIXEL_{BGR8, RGB8, BGRA8, RGBA8};
-  // copied at once.  What a coloured PointCloudAggregator fuses.  Kept until replaced or cleared, across update(): re-attach after an
+  // an 8-bit plane of the frame's level-0 size, rows `pitch` bytes apart (0 = tight), format DVO_HIP_PIXEL_{BGR8, RGB8, BGRA8, RGBA8} or a
+  // raw sensor format (DVO_HIP_PIXEL_BAYER_*, DVO_HIP_PIXEL_YUYV8 / _UYVY8: the colour of its BGR8 image); copied at once.  What a coloured PointCloudAggregator fuses.  Kept until replaced or cleared, across update(): re-attach after an
   // update() with other content.  Returns false where the engine refuses (a pyramid with a lens: its colour must be attached rectified).
   bool setColour(const uint8_t* bgr, size_t pitch = 0, int format = DVO_HIP_PIXEL_BGR8) {
     dvo_hip_frame* one[1] = {device_frame()};

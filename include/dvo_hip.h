@@ -196,6 +196,35 @@ int dvo_hip_frames_update_raw_as_ex(dvo_hip_context* ctx, int n_frames, dvo_hip_
 #define DVO_HIP_PIXEL_RGB8 2  /* TUM rgb PNGs, ROS "rgb8" */
 #define DVO_HIP_PIXEL_BGRA8 3 /* 4-byte pixels, alpha ignored */
 #define DVO_HIP_PIXEL_RGBA8 4
+/* ---- raw sensor planes: Bayer mosaics and YUV 4:2:2, as a camera driver publishes them (image_raw) ----------------------------------
+ * RGB-D sensors do not deliver BGR: the Kinect / OpenNI driver publishes a Bayer GRBG mosaic (1 B per pixel), Xtion, RealSense and UVC
+ * cameras YUV 4:2:2 (2 B per pixel); the reference's nodes sit behind image_proc, which debayers and rectifies on the CPU
+ * (dvo_ros/src/camera_base.cpp:30 subscribes to camera/rgb/image_rect).  Every entry point that takes a pixel_format takes these six
+ * too -- dvo_hip_frame_create_colour*, dvo_hip_frames_update_colour*_as_ex, dvo_hip_frames_update_colour_f32depth*,
+ * dvo_hip_frames_set_colour -- with everything the ingest combines: host or device planes, a pitch, a role, DVO_HIP_INGEST_DEFER (the
+ * request records the sensor planes and they are converted at the flush), DVO_HIP_INGEST_NO_RAW_COPY, a lens, a depth rig.
+ *   semantics   dvo_slam_amd/csrc/sensor_formats.h, integer only.  A sensor format is DEFINED by its BGR8 image -- a bilinear demosaic in
+ *               OpenCV's arithmetic with neighbours outside the image read by reflection (the interior is OpenCV's COLOR_Bayer*2BGR, the
+ *               one-pixel border is ours), or BT.601 limited range in 20-bit fixed point (meant to be OpenCV's COLOR_YUV2BGR_YUY2 /
+ *               _UYVY; that equality is not verified) -- and the frame is then a BGR8 frame: bit for bit the frame fed that BGR8 image,
+ *               or its CV_BGR2GRAY grey plane through the grey entry points, in every plane of every level, and
+ *               dvo_hip_frames_set_colour stores the 0x00RRGGBB of that image.  For YUV the grey is therefore NOT the Y byte.
+ *   planes      1 byte per pixel (Bayer) or 2 (YUV); colour_pitch 0 = tight, else at least width * bytes; any byte alignment of pointer
+ *               and pitch.  A Bayer plane needs width >= 2 and height >= 2, a YUV plane an even width: DVO_HIP_ERR_INVALID otherwise, like
+ *               every value in 6..15 and from 22 on, before anything is touched.
+ *   pipeline    one conversion pass on the build stream at the head of the ingest (k_sensor_convert, sensor_convert.hip) writes the
+ *               grey plane into the frame's own u8 staging plane; the rig pass, the lens pass and the ingest then run as for a grey8
+ *               source at that address.  From host memory the upload buffers carry the sensor plane itself: 1 or 2 B per pixel.
+ *   raw copy    the staging plane the pass wrote IS the grey half of the frame's raw copy: with u16 depth the ingest stores the depth
+ *               half beside it (and rewrites the grey bytes with the values it read), with float depth the copy is the float planes as
+ *               for any float-depth ingest.  keep_raw_copy, another role, a reselection and a download behave as after a grey ingest.
+ *   counters    "sensor_ingests" counts the frames; "colour_ingests" does not count them. */
+#define DVO_HIP_PIXEL_BAYER_RGGB8 16   /* named by the 2 x 2 block at the image's top-left corner, row-major: R G / G B */
+#define DVO_HIP_PIXEL_BAYER_BGGR8 17
+#define DVO_HIP_PIXEL_BAYER_GBRG8 18
+#define DVO_HIP_PIXEL_BAYER_GRBG8 19
+#define DVO_HIP_PIXEL_YUYV8       20   /* bytes Y0 U Y1 V per pixel pair (ROS "yuv422_yuy2") */
+#define DVO_HIP_PIXEL_UYVY8       21   /* bytes U Y0 V Y1 per pixel pair (ROS "yuv422") */
 /* the counterpart of dvo_hip_frame_create_raw: host planes (staged through the context's upload buffers) */
 int dvo_hip_frame_create_colour(dvo_hip_context* ctx, int width, int height, const float K[4], const void* colour, int pixel_format,
                                 size_t colour_pitch, const uint16_t* raw_depth, float depth_scale, int levels, dvo_hip_frame** out);
@@ -660,7 +689,8 @@ int dvo_hip_time_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views,
  *                 colour); dvo_hip_map_extract_colour and dvo_hip_map_render_colour on a grey map; an unknown flag.
  *   cost          profiles/keyframe_map_colour.md. */
 /* colour: n planes of frame i's level-0 size, pixel_format one of DVO_HIP_PIXEL_{BGR8, RGB8, BGRA8, RGBA8}, rows colour_pitch bytes
- * apart (0 = tight); host memory, or device memory with on_device. */
+ * apart (0 = tight); host memory, or device memory with on_device.  Or one of the six sensor formats (DVO_HIP_PIXEL_BAYER_*,
+ * DVO_HIP_PIXEL_YUYV8 / _UYVY8; their plane rules above): the plane stored is the packed BGR8 image of sensor_formats.h. */
 int dvo_hip_frames_set_colour(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const void* const* colour, int pixel_format,
                               size_t colour_pitch, int on_device);
 int dvo_hip_frames_clear_colour(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames);
@@ -962,6 +992,8 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value);
  * "strip_ingests" (frames whose raw planes went through the strip ingest, one 128 x 8 strip per wavefront -- even-width rows and
  * 4 / 8-byte aligned planes; the others take the tile kernel),
  * "colour_ingests" (frames ingested from an 8-bit colour plane, dvo_hip_frame_create_colour* / dvo_hip_frames_update_colour*),
+ * "sensor_ingests" (frames ingested from a raw sensor plane, DVO_HIP_PIXEL_BAYER_* / _YUYV8 / _UYVY8, through the same entry points;
+ * "colour_ingests" does not count them, "strip_ingests" counts those whose grey-plane ingest took the strip kernel),
  * "f32_ingests" (frames ingested from a float depth plane, dvo_hip_frame_create_f32_device / dvo_hip_frames_update_f32* /
  * dvo_hip_frames_update_colour_f32depth*; "strip_ingests" counts those of them that took the strip kernel),
  * "lens_ingests" (frames rectified at ingest because they carry a lens, dvo_hip_frames_set_lens; each is also one of "f32_ingests"),
