@@ -139,11 +139,11 @@ struct dvo_hip_frame {
   DevBuf sel_mask;
   unsigned long long sel_visit = 0;   // (apply_selection: the call that last listed the frame)
   // The lens of the frame's camera (dvo_hip_frames_set_lens, lens.h): every later ingest rectifies the caller's planes into the frame's
-  // float planes of level 0 first (rectify_frames).  The frame's, not the camera's: CameraGeom describes the rectified image.
+  // float planes of level 0 first (lens_stage).  The frame's, not the camera's: CameraGeom describes the rectified image.
   bool lens_on = false;
   dvo_hip_lens lens = {};
   // The depth rig of the frame's sensors (dvo_hip_frames_set_depth_rig, depth_rig.h): every later ingest takes its depth plane as the depth
-  // sensor's own image and registers it into the frame's float plane Z of level 0 first (register_frames), ahead of the lens pass.
+  // sensor's own image and registers it into the frame's float plane Z of level 0 first (rig_stage), ahead of the lens pass.
   bool rig_on = false;
   dvo_hip_depth_rig rig = {};
   // The colour of the frame (dvo_hip_frames_set_colour, cloud_colour.h): its own level-0 plane of packed pixels, w0 * h0 dwords, written
@@ -535,10 +535,10 @@ struct dvo_hip_context {
   DevBuf misc, role_tbl_cur, role_tbl_ref, prep_tbl_cur, prep_tbl_ref;
   DevBuf sel_tbl_main, sel_tbl_build;                 // tables of the caller-selection apply pass, one per stream (apply_selection)
   unsigned long long sel_visits = 0;
-  DevBuf lens_tbl;                                    // table of the rectify pass (rectify_frames; allocated by the first lens ingest)
-  DevBuf sensor_tbl;                                  // table of the sensor-format pass (sensor_frames; allocated by the first sensor ingest)
+  DevBuf lens_tbl;                                    // table of the rectify pass (lens_stage; allocated by the first lens ingest)
+  DevBuf sensor_tbl;                                  // table of the sensor-format pass (sensor_stage; allocated by the first sensor ingest)
   DevBuf graph_jobs, graph_outs;                      // the job records and results of a resident pose-graph launch (capi_graph.inc)
-  DevBuf rig_tbl;                                     // table of the register pass (register_frames; allocated by the first rig ingest)
+  DevBuf rig_tbl;                                     // table of the register pass (rig_stage; allocated by the first rig ingest)
   DevBuf colour_tbl, colour_stage;                    // the plane table of a k_colour_pack launch and the staging area of host colour planes (capi_colour.inc)
   DevBuf map_tbl, map_stage;                          // the frame table of a keyframe-map launch and the staging area of results that go to host memory (capi_map.inc)
   DevBuf render_tbl, render_zbuf, render_planes;      // a render's view table, its z-buffers and -- dvo_hip_map_render_frames -- the planes the frames ingest (capi_map.inc)

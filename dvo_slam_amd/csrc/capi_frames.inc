@@ -1,6 +1,7 @@
 // capi_frames.inc -- cameras, frames and their planes: build tickets, the per-level geometry of a camera, frame allocation, the batched frame
-// build (raw ingest + pyramid), and the role planes of a batch's frames (ensure_roles).  Textually included by capi.hip inside its anonymous
-// namespace (the context, the workspace and the error macros are defined there).
+// build in parts (frames_build: the ingest's pre-passes as a chain of stages, one frame's source and raw copy, the build table, the
+// launches), and the role planes of a batch's frames (ensure_roles: one RoleBuild per pass).  Textually included by capi.hip inside its
+// anonymous namespace (the context, the workspace and the error macros are defined there).
 // ticket + event for work just enqueued on the build stream; stamps the frames it wrote
 int stamp_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames) {
   const unsigned long long seq = ++ctx->build_seq;
@@ -323,11 +324,6 @@ uint8_t* staging_grey(dvo_hip_frame* f) { return f->pool.as<uint8_t>() + size_t(
 
 bool aligned_to(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
-// RgbdImagePyramid::build (rgbd_image.cpp:156-172) for n frames of one camera.  From float planes (src == null: level 0 is
-// already in place): the pyr-down chain, one launch per level for the whole batch; derived planes are built lazily per role
-// (ensure_roles), like the reference's buildAccelerationStructure / PointSelection caches.  From raw planes: one fused pass
-// (k_build_from_raw) that also writes level 0 in role `role` (-1: not known yet, 0: current, 1: reference with the given
-// thresholds) and leaves a copy of the raw planes in the frame unless the current-role planes make it redundant.
 // flavours of the current role a consumer of `n_frames` freshly built frames will most likely ask for at `level`: where the window
 // sweep handles the level, a batch too large for the resident kernel only ever reads the 8-byte plane C (a third of the bytes to
 // write); a small one may run the level resident (taps A + B) or on the launch path (C): both.  Whatever is missing at match time is
@@ -344,287 +340,334 @@ int eager_current_flavor(const dvo_hip_context* ctx, const CameraGeom* cam, int 
   return BatchPolicy(ctx->compute_units).ingest_skips_taps(n_frames) ? kCurC : (kCurAB | kCurC);
 }
 
-// The rectify pass of n frames that carry a lens (the same one: check_source), on the build stream: the caller's planes `src` through the
-// lens into each frame's own float planes I / Z of level 0, depth conversion included (lens.h, rectify.hip).  What follows in
-// frames_build is the float ingest of those planes, read where they lie: no staging, nothing the context owns but the pointer table.
-int rectify_frames(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource& src) {
-  const CameraGeom* cam = frames[0]->cam;
-  const dvo_hip_lens& lens = frames[0]->lens;
-  const bool image_f32 = src.format == DVO_HIP_PIXEL_F32, depth_f32 = src.depth_format == DVO_HIP_DEPTH_F32;
-  std::vector<RectifyPtrs> host(static_cast<size_t>(n));
-  for (int i = 0; i < n; ++i) host[i] = RectifyPtrs{src.planes[i], src.depth[i], frames[i]->lv[0].I, frames[i]->lv[0].Z};
-  RectifyArgs a;
-  a.map = lens_prepare(cam->K0, lens.K_raw, lens.D);
-  a.w = cam->w[0];
-  a.h = cam->h[0];
-  a.image_pitch = int(src.pitch);
-  a.depth_pitch = depth_f32 ? int(src.depth_pitch) : cam->w[0] * 2;   // (u16 depth planes are tight)
-  a.red_first = pixel_red_first(src.format) ? 1 : 0;
-  a.rectify_depth = lens.rectify_depth;
-  a.depth_scale = src.depth_scale;
-  const size_t bytes = host.size() * sizeof(RectifyPtrs);
-  DVO_HIP_TRY(ctx, ctx->lens_tbl.reserve(bytes));
-  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->build_stream, ctx->lens_tbl.p, host.data(), bytes));
-  launch_rectify(ctx->build_stream, ctx->lens_tbl.as<RectifyPtrs>(), n, a, image_f32 ? kChF32 : pixel_channels(src.format), depth_f32,
-                 ctx->opt_build_workgroups, ctx->opt_stream_policy != 0);
-  DVO_HIP_TRY(ctx, hipGetLastError());
-  return DVO_HIP_OK;
+// ---- the pre-passes of a raw ingest, as stages.  Each runs on the build stream in front of the ingest for frames that carry its
+// property (the same for all n: check_source), reads the planes of the IngestSource it is given, writes into the frames' own memory and
+// hands on the IngestSource the next stage -- or the ingest -- reads instead.  Nothing is launched or allocated for frames without the
+// property; a stage owns nothing but its pointer table.
+
+// the plane arrays a rewritten source points into; frames_build owns one for the duration of the call.  A stage fills its table from the
+// source it was given BEFORE it rewrites an array here (that source may point into the same array)
+struct StagePlanes { std::vector<const void*> image, depth; };
+
+// the pointer table of a stage: room in the stage's buffer, the records uploaded on the build stream; returns the device address (null:
+// DVO_HIP_ERR_HIP, the context holds the text)
+template <typename T>
+const T* stage_table(dvo_hip_context* ctx, DevBuf& buf, const std::vector<T>& host) {
+  const size_t bytes = host.size() * sizeof(T);
+  hipError_t e = buf.reserve(bytes);
+  if (e == hipSuccess) e = ctx->tables.upload(ctx->build_stream, buf.p, host.data(), bytes);
+  if (e != hipSuccess) ctx->err = std::string("stage table: ") + hipGetErrorString(e);
+  return e == hipSuccess ? buf.as<T>() : nullptr;
 }
 
-// The register pass of n frames that carry a depth rig (the same one: check_source), on the build stream: the depth sensor's planes of
-// `src` through the rig into each frame's own float plane Z of level 0, depth conversion included (depth_rig.h, depth_register.hip): a
-// fill with the hole pattern, then the scatter.  What follows in frames_build reads Z where it lies as float depth of scale 1.
-int register_frames(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource& src) {
-  const CameraGeom* cam = frames[0]->cam;
-  const bool depth_f32 = src.depth_format == DVO_HIP_DEPTH_F32;
-  std::vector<DepthRigPtrs> host(static_cast<size_t>(n));
-  for (int i = 0; i < n; ++i) host[i] = DepthRigPtrs{src.depth[i], frames[i]->lv[0].Z};
-  DepthRigArgs a;
-  a.map = depth_rig_prepare(cam->K0, frames[0]->rig);
-  a.w = cam->w[0];
-  a.h = cam->h[0];
-  a.depth_pitch = depth_f32 ? int(src.depth_pitch) : cam->w[0] * 2;   // (u16 depth planes are tight)
-  a.depth_scale = src.depth_scale;
-  const size_t bytes = host.size() * sizeof(DepthRigPtrs);
-  DVO_HIP_TRY(ctx, ctx->rig_tbl.reserve(bytes));
-  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->build_stream, ctx->rig_tbl.p, host.data(), bytes));
-  launch_depth_register(ctx->build_stream, ctx->rig_tbl.as<DepthRigPtrs>(), n, a, depth_f32, ctx->opt_build_workgroups, ctx->opt_stream_policy != 0);
-  DVO_HIP_TRY(ctx, hipGetLastError());
-  return DVO_HIP_OK;
-}
+typedef int IngestStage(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource& in, StagePlanes& planes, IngestSource* out);
 
-// The sensor-format pass of n frames fed a Bayer mosaic or a YUV 4:2:2 plane (sensor_formats.h, sensor_convert.hip), on the build stream:
-// the caller's planes -> the 8-bit grey of their BGR8 image in each frame's own u8 staging plane (staging_grey: no steady-state call
-// allocates; nothing the context owns but the pointer table).  What follows in frames_build reads a tight grey8 source at that address.
-int sensor_frames(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource& src) {
+// Frames fed a sensor format (a Bayer mosaic, YUV 4:2:2; sensor_formats.h, sensor_convert.hip): the caller's planes -> the 8-bit grey of
+// their BGR8 image in each frame's own u8 staging plane (staging_grey: no steady-state call allocates).  Hands on a tight grey8 source at
+// that address with the caller's depth: the frame ends as one fed that grey through the grey entry points would.  The raw copy needs no
+// case of its own (frame_source).  With u16 depth the source is not "in place" (the depth plane is the caller's), so an ingest that keeps
+// a copy gets keep_grey = the staging plane it reads: every lane stores the grey bytes it loaded back where it loaded them from, while
+// other waves read their halo rows there -- harmless for the reason given at the rig stage, the store changes no bit.
+int sensor_stage(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource& in, StagePlanes& planes, IngestSource* out) {
   const CameraGeom* cam = frames[0]->cam;
   std::vector<SensorPtrs> host(static_cast<size_t>(n));
   SensorArgs a;
-  a.w = cam->w[0];
-  a.h = cam->h[0];
-  a.pitch = int(src.pitch);
-  a.format = src.format;
+  a.w = cam->w[0]; a.h = cam->h[0];
+  a.pitch = int(in.pitch);
+  a.format = in.format;
   a.src_dwords = 1;
   a.dst_wide = a.w % 4 == 0 ? 1 : 0;
   for (int i = 0; i < n; ++i) {
-    host[size_t(i)] = SensorPtrs{static_cast<const uint8_t*>(src.planes[i]), staging_grey(frames[i])};
-    if (!sensor_src_dwords(src.planes[i], src.pitch)) a.src_dwords = 0;
+    host[size_t(i)] = SensorPtrs{static_cast<const uint8_t*>(in.planes[i]), staging_grey(frames[i])};
+    if (!sensor_src_dwords(in.planes[i], in.pitch)) a.src_dwords = 0;
     if (!aligned_to(staging_grey(frames[i]), 4)) a.dst_wide = 0;
   }
-  const size_t bytes = host.size() * sizeof(SensorPtrs);
-  DVO_HIP_TRY(ctx, ctx->sensor_tbl.reserve(bytes));
-  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->build_stream, ctx->sensor_tbl.p, host.data(), bytes));
-  launch_sensor_convert(ctx->build_stream, ctx->sensor_tbl.as<SensorPtrs>(), n, a, /*packed=*/false, ctx->opt_build_workgroups, ctx->opt_stream_policy != 0);
+  const SensorPtrs* tbl = stage_table(ctx, ctx->sensor_tbl, host);
+  if (!tbl) return DVO_HIP_ERR_HIP;
+  launch_sensor_convert(ctx->build_stream, tbl, n, a, /*packed=*/false, ctx->opt_build_workgroups, ctx->opt_stream_policy != 0);
   DVO_HIP_TRY(ctx, hipGetLastError());
+  planes.image.resize(size_t(n));
+  for (int i = 0; i < n; ++i) planes.image[size_t(i)] = staging_grey(frames[i]);
+  *out = IngestSource{planes.image.data(), 0, size_t(cam->w[0]), in.depth, in.depth_scale, in.depth_format, in.depth_pitch};
   return DVO_HIP_OK;
 }
 
+// Frames that carry a depth rig (depth_rig.h, depth_register.hip): the depth sensor's planes through the rig into each frame's own float
+// plane Z of level 0, depth conversion included: a fill with the hole pattern, then the scatter.  Hands on the caller's image in its own
+// format with float depth of scale 1 read from THAT plane, in place: the frame ends as a rig-less frame fed the image and the registered
+// plane would.  Without a lens the ingest keeps its planes (keep_planes 1) and so stores Z back into the plane it reads, while other
+// waves still read their halo rows from it.  That is harmless only because the conversion is the identity here -- float depth of scale
+// 1, z * 1.0f, keeps every bit pattern, a NaN's payload included (kDepthRigHole is a quiet NaN) -- so a halo read sees the same bits
+// before and after a neighbour's store.  A conversion that changes any bit would need keep_planes 0 for Z, as under a lens.
+int rig_stage(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource& in, StagePlanes& planes, IngestSource* out) {
+  const CameraGeom* cam = frames[0]->cam;
+  const bool depth_f32 = in.depth_format == DVO_HIP_DEPTH_F32;
+  std::vector<DepthRigPtrs> host(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) host[i] = DepthRigPtrs{in.depth[i], frames[i]->lv[0].Z};
+  DepthRigArgs a;
+  a.map = depth_rig_prepare(cam->K0, frames[0]->rig);
+  a.w = cam->w[0]; a.h = cam->h[0];
+  a.depth_pitch = depth_f32 ? int(in.depth_pitch) : cam->w[0] * 2;   // (u16 depth planes are tight)
+  a.depth_scale = in.depth_scale;
+  const DepthRigPtrs* tbl = stage_table(ctx, ctx->rig_tbl, host);
+  if (!tbl) return DVO_HIP_ERR_HIP;
+  launch_depth_register(ctx->build_stream, tbl, n, a, depth_f32, ctx->opt_build_workgroups, ctx->opt_stream_policy != 0);
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  planes.depth.resize(size_t(n));
+  for (int i = 0; i < n; ++i) planes.depth[size_t(i)] = frames[i]->lv[0].Z;
+  *out = IngestSource{in.planes, in.format, in.pitch, planes.depth.data(), 1.0f, DVO_HIP_DEPTH_F32, size_t(cam->w[0]) * 4};
+  return DVO_HIP_OK;
+}
+
+// Frames that carry a lens (lens.h, rectify.hip): the planes of `in` through the lens into each frame's own float planes I / Z of level
+// 0, depth conversion included.  Hands on float image and float depth of scale 1 at those planes: the ingest is the float ingest of THOSE
+// planes, read where they lie, and the frame ends as a lens-less frame fed the rectified pair would.  The rectified planes already lie
+// where a raw copy goes, so the ingest runs with keep_planes 0 (frame_source): nothing is written twice, and no lane stores into a plane
+// others still read.  Behind a rig (rectify_depth 0: dvo_hip_frames_set_depth_rig) each lane of k_rectify reads and writes only its own
+// element of Z.
+int lens_stage(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource& in, StagePlanes& planes, IngestSource* out) {
+  const CameraGeom* cam = frames[0]->cam;
+  const dvo_hip_lens& lens = frames[0]->lens;
+  const bool image_f32 = in.format == DVO_HIP_PIXEL_F32, depth_f32 = in.depth_format == DVO_HIP_DEPTH_F32;
+  std::vector<RectifyPtrs> host(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) host[i] = RectifyPtrs{in.planes[i], in.depth[i], frames[i]->lv[0].I, frames[i]->lv[0].Z};
+  RectifyArgs a;
+  a.map = lens_prepare(cam->K0, lens.K_raw, lens.D);
+  a.w = cam->w[0]; a.h = cam->h[0];
+  a.image_pitch = int(in.pitch);
+  a.depth_pitch = depth_f32 ? int(in.depth_pitch) : cam->w[0] * 2;   // (u16 depth planes are tight)
+  a.red_first = pixel_red_first(in.format) ? 1 : 0;
+  a.rectify_depth = lens.rectify_depth;
+  a.depth_scale = in.depth_scale;
+  const RectifyPtrs* tbl = stage_table(ctx, ctx->lens_tbl, host);
+  if (!tbl) return DVO_HIP_ERR_HIP;
+  launch_rectify(ctx->build_stream, tbl, n, a, image_f32 ? kChF32 : pixel_channels(in.format), depth_f32, ctx->opt_build_workgroups,
+                 ctx->opt_stream_policy != 0);
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  planes.image.resize(size_t(n));
+  planes.depth.resize(size_t(n));
+  for (int i = 0; i < n; ++i) {
+    planes.image[size_t(i)] = frames[i]->lv[0].I;
+    planes.depth[size_t(i)] = frames[i]->lv[0].Z;
+  }
+  const size_t row = size_t(cam->w[0]) * 4;
+  *out = IngestSource{planes.image.data(), DVO_HIP_PIXEL_F32, row, planes.depth.data(), 1.0f, DVO_HIP_DEPTH_F32, row};
+  return DVO_HIP_OK;
+}
+
+// which stages a call runs (frames_build runs them in this order)
+struct StagesRun { bool sensor, rig, lens; };
+
+// new pixels: every cached role plane of the frame is stale (PointSelection::setRgbdImagePyramid)
+void invalidate_roles(dvo_hip_frame* f) {
+  for (int l = 0; l < f->levels; ++l) f->lv[l].cur_have = 0;
+  invalidate_reference_role(f);
+}
+
+// what the kernels of an ingest are templated on: the formats of the (staged) source, `channels` = the kernels' CH; all false / 0 without one
+struct SourceKind { bool image_f32, depth_f32, colour; int channels; };
+SourceKind source_kind(const IngestSource* src) {
+  const bool image_f32 = src && src->format == DVO_HIP_PIXEL_F32, colour = src && src->format != 0 && !image_f32;
+  return SourceKind{image_f32, src && src->depth_format == DVO_HIP_DEPTH_F32, colour, image_f32 ? kChF32 : colour ? pixel_channels(src->format) : 0};
+}
+
+// One frame of a build: its entry `p` of the build table -- where the kernel reads frame i of the (staged) source `src` and where it
+// leaves a copy -- and, returned, what the frame then holds of its raw planes and its share of `wide` (every plane's address and pitch
+// suit the strip ingest's loads).  Without a source (a frame created from float planes: level 0 is in place) nothing but the planes.
+struct FrameSource { bool raw0, raw_copy, wide; };
+FrameSource frame_source(dvo_hip_frame* f, const IngestSource* src, int i, const SourceKind& kind, int role, bool keep_raw_copy, bool lens,
+                         FrameBuildPtrs& p) {
+  fill_build_ptrs(f, p);
+  if (!src) return FrameSource{false, false, true};
+  if (kind.colour || kind.image_f32) {
+    p.colour = static_cast<const uint8_t*>(src->planes[i]);
+    p.colour_format = src->format;
+  } else {
+    p.grey = static_cast<const uint8_t*>(src->planes[i]);
+  }
+  p.colour_pitch = int(src->pitch);   // (a grey plane's is read with float depth only: the u16 entry points take tight grey planes)
+  if (kind.depth_f32) {
+    p.depth_f32 = static_cast<const float*>(src->depth[i]);
+    p.depth_pitch = int(src->depth_pitch);
+  } else {
+    p.raw = static_cast<const uint16_t*>(src->depth[i]);
+  }
+  // The raw copy -- what another role, a reselection and a download can later derive level 0 from -- in one statement of cases.  An
+  // ingest without a role keeps one, one into the reference role unless told otherwise (option "keep_raw_copy" 0), one into the current
+  // role never: its planes A + B hold everything.
+  const bool keeps = role < 0 || (role == 1 && keep_raw_copy);
+  const bool in_place = !kind.depth_f32 && !kind.colour && p.raw == staging_depth(f) && p.grey == staging_grey(f);
+  FrameSource s{true, false, true};
+  if (kind.depth_f32 && keeps) {
+    // float depth: the copy is the frame's float planes I / Z of level 0 -- the state of a frame created from float planes (raw0 false).
+    // Rectified planes (lens) already lie where the copy goes: nothing is written twice
+    p.keep_planes = lens ? 0 : 1;
+    s.raw0 = false;
+  } else if (in_place) {
+    s.raw_copy = true;                 // u16 depth, read from the frame's own staging area: that IS the copy, whatever the role
+  } else if (!kind.depth_f32 && keeps) {
+    p.keep_grey = staging_grey(f);     // u16 depth from elsewhere: the kernel leaves grey and depth in the staging area
+    p.keep_raw = staging_depth(f);
+    s.raw_copy = true;
+  }                                    // else none: a raw-ingested frame that has nothing but the role planes just written
+  if (kind.depth_f32)
+    s.wide = f32_strips_aligned(p.depth_f32, src->depth_pitch) &&
+             (kind.image_f32 ? f32_strips_aligned(p.colour, src->pitch)
+                             : kind.colour ? colour_strips_aligned(p.colour, src->pitch, kind.channels) : aligned_to(p.grey, 2) && src->pitch % 2 == 0);
+  else
+    s.wide = (kind.colour ? colour_strips_aligned(p.colour, src->pitch, kind.channels) : aligned_to(p.grey, 4)) && aligned_to(p.raw, 8) &&
+             aligned_to(staging_grey(f), 4);
+  return s;
+}
+
+// The build table of these n frames on the build stream: in one of a few buffers -- the one that already holds this very table (a
+// streaming caller re-ingests the same frame sets from the same planes step after step), else the next in turn -- and remembered as
+// the table of this frame list (ensure_roles reuses it for an eager prepare of the same list).
+int upload_build_table(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const std::vector<FrameBuildPtrs>& host, const FrameBuildPtrs** tbl) {
+  const size_t bytes = size_t(n) * sizeof(FrameBuildPtrs);
+  int slot = ctx->tables.holder(ctx->build_tbl, dvo_hip_context::kTableSlots, ctx->build_stream, host.data(), bytes);
+  if (slot < 0) slot = int(ctx->build_tbl_next++ % dvo_hip_context::kTableSlots);
+  DevBuf& build_tbl = ctx->build_tbl[slot];
+  DVO_HIP_TRY(ctx, build_tbl.reserve(bytes));
+  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->build_stream, build_tbl.p, host.data(), bytes));
+  *tbl = build_tbl.as<FrameBuildPtrs>();
+  ctx->build_tbl_frames.assign(frames, frames + n);
+  ctx->build_tbl_cur = &build_tbl;
+  return DVO_HIP_OK;
+}
+
+// The launches of a raw ingest and its counters: level 0 in role `role` and the pyramid levels 1..3 in one pass, then the caller
+// selection of reference frames.  Current frames: the {I, Z} plane C of the pyramid levels the window sweep will read comes out of the
+// same pass (no neighbours needed), where the strip ingest runs (ingest_strips.hip).  *built: the levels the pass has written.
+int launch_raw_ingest(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const FrameBuildPtrs* tbl, const SourceKind& kind, bool wide,
+                      float depth_scale, int role, float ithr, float dthr, int flavor0, const StagesRun& ran, int* built) {
+  const CameraGeom* cam = frames[0]->cam;
+  const int levels = frames[0]->levels;
+  *built = levels < 4 ? levels : 4;
+  int c_levels = 0;
+  const bool strips = ingest_strips_supports(cam->w[0], wide, kind.image_f32);
+  if (role == 0 && strips) {
+    for (int l = 1; l < *built; ++l)
+      if (eager_current_flavor(ctx, cam, l, n) & kCurC) c_levels |= 1 << l;
+    for (int i = 0; i < n; ++i)
+      for (int l = 1; l < *built; ++l)
+        if ((c_levels >> l & 1) && frames[i]->lv[l].C) frames[i]->lv[l].cur_have |= kCurC;
+  }
+  launch_build_from_raw(ctx->build_stream, tbl, n, depth_scale, cam->w[0], cam->h[0], levels, role, strips, ithr, dthr, ctx->opt_build_workgroups,
+                        flavor0, c_levels, kind.channels, ctx->opt_stream_policy != 0, kind.depth_f32);
+  if (role == 1) {
+    const int rc = apply_selection(ctx, ctx->build_stream, n, frames, 0, 0, ctx->opt_build_workgroups);
+    if (rc != DVO_HIP_OK) return rc;
+  }
+  if (strips) ctx->strip_ingests += n;
+  if (kind.colour) ctx->colour_ingests += n;
+  if (ran.sensor) ctx->sensor_ingests += n;
+  if (kind.depth_f32) ctx->f32_ingests += n;
+  if (ran.lens) ctx->lens_ingests += n;
+  if (ran.rig) ctx->depth_registrations += n;
+  return DVO_HIP_OK;
+}
+
+// RgbdImagePyramid::build (rgbd_image.cpp:156-172) for n frames of one camera.  From float planes (src == null: level 0 is
+// already in place): the pyr-down chain, one launch per level for the whole batch; derived planes are built lazily per role
+// (ensure_roles), like the reference's buildAccelerationStructure / PointSelection caches.  From raw planes: the stages the frames
+// ask for (above), then one fused pass (k_build_from_raw) that also writes level 0 in role `role` (-1: not known yet, 0: current, 1:
+// reference with the given thresholds) and leaves a copy of the raw planes in the frame unless the role makes it redundant (frame_source).
 // src: device planes whose pitch is resolved, of frames that share camera and levels (check_ingest has seen to both).  From a colour
 // source the kernels convert and leave grey in the frames' raw copies.
 int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource* src, int role = -1, float ithr = 0.0f,
                  float dthr = 0.0f, bool keep_raw_copy = true) {
   Range range("build");
   const CameraGeom* cam = frames[0]->cam;
-  const int levels = frames[0]->levels;
-  // Frames that carry a lens: the caller's planes are rectified into the frames' float planes of level 0 (depth scaled there), and the
-  // ingest below is the float ingest of THOSE planes, in place -- the frame ends as a lens-less frame fed the rectified pair would.
-  // Frames that carry a depth rig: the depth sensor's plane is registered into the frames' float plane Z of level 0 first (depth scaled
-  // there), and everything below -- the lens pass, the ingest -- takes the caller's image plane in its own format with float depth of
-  // scale 1 read from THAT plane, in place: the frame ends as a rig-less frame fed the image and the registered plane would.  Under a
-  // lens (rectify_depth 0: dvo_hip_frames_set_depth_rig) each lane of k_rectify reads and writes only its own element of Z.
-  // Without a lens the ingest keeps its planes (keep_planes 1) and so stores Z back into the plane it reads, while other waves still
-  // read their halo rows from it.  That is harmless only because the conversion is the identity here -- float depth of scale 1, z * 1.0f,
-  // keeps every bit pattern, a NaN's payload included (kDepthRigHole is a quiet NaN) -- so a halo read sees the same bits before and
-  // after a neighbour's store.  A conversion that changes any bit would need keep_planes 0 for Z, as under a lens.
-  // Frames fed a sensor format (a Bayer mosaic, YUV 4:2:2): the caller's plane is converted into the frames' own u8 staging plane first,
-  // and everything below -- the rig pass, the lens pass, the ingest -- takes a tight grey8 source at that address with the caller's depth:
-  // the frame ends as one fed the grey of the format's BGR8 image through the grey entry points would.  The raw-copy bookkeeping below
-  // needs no case of its own.  With u16 depth the source is not "in place" (the depth plane is the caller's), so an ingest that keeps a
-  // copy gets keep_grey = the staging plane it reads and keep_raw beside it: every lane stores the grey bytes it loaded back where it
-  // loaded them from, while other waves read their halo rows there -- harmless for the reason given for the rig's plane Z below, the
-  // store changes no bit -- and the copy is complete (raw_copy true).  An ingest that keeps none leaves raw_copy false, whatever the
-  // staging plane holds.  With float depth the copy is the float planes (keep_planes), as for any grey8 + float-depth ingest.
-  const bool sensor = src != nullptr && sensor_bytes(src->format) != 0;
-  std::vector<const void*> grey_planes;
-  IngestSource converted;
-  if (sensor) {
-    const int rc = sensor_frames(ctx, n, frames, *src);
+  const StagesRun run{src && sensor_bytes(src->format) != 0, src && frames[0]->rig_on, src && frames[0]->lens_on};
+  // the stages, in their order: sensor format -> grey, depth rig -> registered Z, lens -> rectified I / Z; behind them src is what the ingest reads
+  const struct { bool on; IngestStage* stage; } chain[3] = {{run.sensor, sensor_stage}, {run.rig, rig_stage}, {run.lens, lens_stage}};
+  StagePlanes planes;
+  IngestSource staged;
+  for (const auto& link : chain) {
+    if (!link.on) continue;
+    const int rc = link.stage(ctx, n, frames, *src, planes, &staged);
     if (rc != DVO_HIP_OK) return rc;
-    grey_planes.resize(size_t(n));
-    for (int i = 0; i < n; ++i) grey_planes[size_t(i)] = staging_grey(frames[i]);
-    converted = IngestSource{grey_planes.data(), 0, size_t(cam->w[0]), src->depth, src->depth_scale, src->depth_format, src->depth_pitch};
-    src = &converted;
+    src = &staged;
   }
-  const bool rig = src != nullptr && frames[0]->rig_on;
-  std::vector<const void*> reg_planes;
-  IngestSource registered;
-  if (rig) {
-    const int rc = register_frames(ctx, n, frames, *src);
-    if (rc != DVO_HIP_OK) return rc;
-    reg_planes.resize(size_t(n));
-    for (int i = 0; i < n; ++i) reg_planes[size_t(i)] = frames[i]->lv[0].Z;
-    registered = IngestSource{src->planes, src->format, src->pitch, reg_planes.data(), 1.0f, DVO_HIP_DEPTH_F32, size_t(cam->w[0]) * 4};
-    src = &registered;
-  }
-  const bool lens = src != nullptr && frames[0]->lens_on;
-  std::vector<const void*> rect_planes;
-  IngestSource rectified;
-  if (lens) {
-    const int rc = rectify_frames(ctx, n, frames, *src);
-    if (rc != DVO_HIP_OK) return rc;
-    rect_planes.resize(2 * size_t(n));
-    for (int i = 0; i < n; ++i) {
-      rect_planes[size_t(i)] = frames[i]->lv[0].I;
-      rect_planes[size_t(n) + i] = frames[i]->lv[0].Z;
-    }
-    const size_t row = size_t(cam->w[0]) * 4;
-    rectified = IngestSource{rect_planes.data(), DVO_HIP_PIXEL_F32, row, rect_planes.data() + n, 1.0f, DVO_HIP_DEPTH_F32, row};
-    src = &rectified;
-  }
-  std::vector<FrameBuildPtrs> host(n);
-  bool wide = cam->w[0] % 4 == 0;
-  const bool from_raw = src != nullptr;
-  const bool image_f32 = from_raw && src->format == DVO_HIP_PIXEL_F32;
-  const bool depth_f32 = from_raw && src->depth_format == DVO_HIP_DEPTH_F32;
-  const bool colour = from_raw && src->format != 0 && !image_f32;
-  const int channels = image_f32 ? kChF32 : colour ? pixel_channels(src->format) : 0;   // (the kernels' CH)
-  if (image_f32) wide = cam->w[0] % 2 == 0;
-  const float depth_scale = from_raw ? src->depth_scale : 0.0f;
+  const SourceKind kind = source_kind(src);
+  const float depth_scale = src ? src->depth_scale : 0.0f;
   const int flavor0 = eager_current_flavor(ctx, cam, 0, n);
+  std::vector<FrameBuildPtrs> host(n);
+  bool wide = cam->w[0] % (kind.image_f32 ? 2 : 4) == 0;
   for (int i = 0; i < n; ++i) {
     dvo_hip_frame* f = frames[i];
-    fill_build_ptrs(f, host[i]);
-    for (int l = 0; l < levels; ++l) {   // new pixels: every cached role plane is stale (PointSelection::setRgbdImagePyramid)
-      f->lv[l].cur_have = 0;
-      f->lv[l].selected = false;
-      f->lv[l].explicit_sel = false;
-      f->lv[l].q3 = false;
-    }
-    f->raw0 = from_raw;
-    f->raw_copy = false;
+    invalidate_roles(f);
+    const FrameSource s = frame_source(f, src, i, kind, role, keep_raw_copy, run.lens, host[i]);
+    f->raw0 = s.raw0;
+    f->raw_copy = s.raw_copy;
     f->depth_scale = depth_scale;
-    if (!from_raw) continue;
-    if (role == 0) f->lv[0].cur_have = flavor0;
-    if (role == 1) mark_selected(f->lv[0], ithr, dthr);
-    if (colour || image_f32) {
-      host[i].colour = static_cast<const uint8_t*>(src->planes[i]);
-      host[i].colour_pitch = int(src->pitch);
-      host[i].colour_format = src->format;
-    } else {
-      host[i].grey = static_cast<const uint8_t*>(src->planes[i]);
-      host[i].colour_pitch = int(src->pitch);   // (read with float depth only: the u16 entry points take tight grey planes)
-    }
-    if (depth_f32) {
-      // Float depth: the frame's raw copy is its float planes I / Z of level 0 -- the state of a frame created from float planes
-      // (raw0 false), so another role, a reselection and a download derive from them like there.  Without a copy the frame is a
-      // raw-ingested one that has nothing but the role planes just written.
-      host[i].depth_f32 = static_cast<const float*>(src->depth[i]);
-      host[i].depth_pitch = int(src->depth_pitch);
-      if (role < 0 || (role == 1 && keep_raw_copy)) {
-        host[i].keep_planes = lens ? 0 : 1;                    // (rectified planes already lie where the copy goes: nothing is written twice)
-        f->raw0 = false;
-      }
-      wide = wide && f32_strips_aligned(host[i].depth_f32, src->depth_pitch) &&
-             (image_f32 ? f32_strips_aligned(host[i].colour, src->pitch)
-                        : colour ? colour_strips_aligned(host[i].colour, src->pitch, channels) : aligned_to(host[i].grey, 2) && src->pitch % 2 == 0);
-      continue;
-    }
-    host[i].raw = static_cast<const uint16_t*>(src->depth[i]);
-    const bool in_place = !colour && host[i].raw == staging_depth(f) && host[i].grey == staging_grey(f);
-    if (in_place) {
-      f->raw_copy = true;
-    } else if (role < 0 || (role == 1 && keep_raw_copy)) {
-      host[i].keep_grey = staging_grey(f);
-      host[i].keep_raw = staging_depth(f);
-      f->raw_copy = true;
-    }
-    wide = wide && (colour ? colour_strips_aligned(host[i].colour, src->pitch, channels) : aligned_to(host[i].grey, 4)) &&
-           aligned_to(host[i].raw, 8) && aligned_to(staging_grey(f), 4);
+    wide = wide && s.wide;
+    if (src && role == 0) f->lv[0].cur_have = flavor0;
+    if (src && role == 1) mark_selected(f->lv[0], ithr, dthr);
   }
-  hipStream_t bs = ctx->build_stream;
-  // (one of a few buffers: the one that already holds this very table -- a streaming caller re-ingests the same frame sets from the same
-  // planes step after step -- else the next in turn)
-  int slot = ctx->tables.holder(ctx->build_tbl, dvo_hip_context::kTableSlots, bs, host.data(), size_t(n) * sizeof(FrameBuildPtrs));
-  if (slot < 0) slot = int(ctx->build_tbl_next++ % dvo_hip_context::kTableSlots);
-  DevBuf& build_tbl = ctx->build_tbl[slot];
-  DVO_HIP_TRY(ctx, build_tbl.reserve(size_t(n) * sizeof(FrameBuildPtrs)));
-  DVO_HIP_TRY(ctx, ctx->tables.upload(bs, build_tbl.p, host.data(), size_t(n) * sizeof(FrameBuildPtrs)));
-  const FrameBuildPtrs* tbl = build_tbl.as<FrameBuildPtrs>();
-  ctx->build_tbl_frames.assign(frames, frames + n);
-  ctx->build_tbl_cur = &build_tbl;
+  const FrameBuildPtrs* tbl = nullptr;
+  int rc = upload_build_table(ctx, n, frames, host, &tbl);
+  if (rc != DVO_HIP_OK) return rc;
   int built = 1;                                       // float ingest: level 0 is already in place
-  if (from_raw) {
-    // current frames: the {I, Z} plane of the pyramid levels the window sweep will read comes out of the same pass (no neighbours
-    // needed), where the strip ingest runs (ingest_strips.hip)
-    built = levels < 4 ? levels : 4;
-    int c_levels = 0;
-    const bool strips = ingest_strips_supports(cam->w[0], wide, image_f32);
-    if (role == 0 && strips) {
-      for (int l = 1; l < built; ++l)
-        if (eager_current_flavor(ctx, cam, l, n) & kCurC) c_levels |= 1 << l;
-      for (int i = 0; i < n; ++i)
-        for (int l = 1; l < built; ++l)
-          if ((c_levels >> l & 1) && frames[i]->lv[l].C) frames[i]->lv[l].cur_have |= kCurC;
-    }
-    launch_build_from_raw(bs, tbl, n, depth_scale, cam->w[0], cam->h[0], levels, role, strips, ithr, dthr, ctx->opt_build_workgroups, flavor0, c_levels,
-                          channels, ctx->opt_stream_policy != 0, depth_f32);
-    if (role == 1) {
-      const int rc = apply_selection(ctx, bs, n, frames, 0, 0, ctx->opt_build_workgroups);
-      if (rc != DVO_HIP_OK) return rc;
-    }
-    if (strips) ctx->strip_ingests += n;
-    if (colour) ctx->colour_ingests += n;
-    if (sensor) ctx->sensor_ingests += n;
-    if (depth_f32) ctx->f32_ingests += n;
-    if (lens) ctx->lens_ingests += n;
-    if (rig) ctx->depth_registrations += n;
+  if (src) {
+    rc = launch_raw_ingest(ctx, n, frames, tbl, kind, wide, depth_scale, role, ithr, dthr, flavor0, run, &built);
+    if (rc != DVO_HIP_OK) return rc;
   }
-  for (int l = built; l < levels; ++l) launch_pyr_down(bs, tbl, n, l, cam->w[l - 1], cam->h[l - 1]);
+  for (int l = built; l < frames[0]->levels; ++l) launch_pyr_down(ctx->build_stream, tbl, n, l, cam->w[l - 1], cam->h[l - 1]);
   DVO_HIP_TRY(ctx, hipGetLastError());
   return stamp_build(ctx, n, frames);
 }
 
-// Build the missing role planes of a set of frames for levels [l0, l1]: role 0 = current (flavours `cur_want[level]`, kCurAB | kCurC;
-// null: the taps A + B), role 1 = reference (R + selection count for the given thresholds).  One launch per level (and source) for
-// all frames that need it.
-// `eager`: on the build stream (dvo_hip_frames_prepare), otherwise on the main stream right before the planes are used.
-int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int role, int l0, int l1, float ithr, float dthr, bool eager = false,
-                 const int* cur_want = nullptr) {
-  const CameraGeom* cam = frames[0]->cam;
-  const size_t slice = size_t(n) * sizeof(FrameBuildPtrs);
-  DevBuf& table = eager ? (role == 0 ? ctx->prep_tbl_cur : ctx->prep_tbl_ref) : (role == 0 ? ctx->role_tbl_cur : ctx->role_tbl_ref);
-  hipStream_t stream = eager ? ctx->build_stream : ctx->stream;
-  const int cap = eager ? ctx->opt_build_workgroups : 0;   // planes needed right now are built at full width
-  const bool stream_nt = eager && ctx->opt_stream_policy != 0;
+// One pass of ensure_roles over a frame list: what the role is built for and where (stream, table, grid cap), and the state the pass
+// gathers -- table slices used, whether anything was launched.
+struct RoleBuild {
+  dvo_hip_context* ctx;
+  int n;
+  dvo_hip_frame* const* frames;
+  int role;
+  float ithr, dthr;
+  bool eager;
+  const int* cur_want;
+  const CameraGeom* cam;
+  DevBuf& table;
+  hipStream_t stream;
+  int cap;                                                     // (eager only: planes needed right now are built at full width)
+  bool stream_nt;
+  int uploads = 0;                                             // table slices used so far (each launch reads its own)
+  bool launched = false;
+
+  RoleBuild(dvo_hip_context* c, int n_frames, dvo_hip_frame* const* fr, int r, float it, float dt, bool e, const int* want)
+      : ctx(c), n(n_frames), frames(fr), role(r), ithr(it), dthr(dt), eager(e), cur_want(want), cam(fr[0]->cam),
+        table(e ? (r == 0 ? c->prep_tbl_cur : c->prep_tbl_ref) : (r == 0 ? c->role_tbl_cur : c->role_tbl_ref)),
+        stream(e ? c->build_stream : c->stream), cap(e ? c->opt_build_workgroups : 0), stream_nt(e && c->opt_stream_policy != 0) {}
+
   // What frame f lacks at level l.  Current role: `miss` = the flavours wanted there (plane C only where the camera's frames have one)
   // that the frame does not hold; reference role: whether its selection stands for these thresholds (miss 0).
   struct Lack { int miss; bool need; };
-  auto lack_of = [&](const dvo_hip_frame* f, int l) -> Lack {
+  Lack lack_of(const dvo_hip_frame* f, int l) const {
     const FrameLevel& L = f->lv[l];
     if (role != 0) return Lack{0, !ref_ready(L, ithr, dthr)};
     const int want = (cur_want ? cur_want[l] : kCurAB) & (L.C ? (kCurAB | kCurC) : kCurAB);
     return Lack{want & ~L.cur_have, (want & ~L.cur_have) != 0};
-  };
-  // Every frame is checked before the state of any is touched: a frame ingested straight into a role without a copy of its raw planes
-  // (option "keep_raw_copy" 0) has nothing its level 0 could be derived from in another role, and the marks below -- planes "built" --
-  // are set while the launches are still being gathered (round-5 advisor finding: the error used to leave earlier frames of the list
-  // marked as built without their launches, and a retry aligned against stale planes).
-  if (l0 == 0)
-    for (int i = 0; i < n; ++i) {
-      const dvo_hip_frame* f = frames[i];
-      if (!f->raw0 || f->lv[0].cur_have != 0 || f->raw_copy) continue;
-      if (lack_of(f, 0).need) return fail(ctx, DVO_HIP_ERR_INVALID, "frame has neither sampling planes nor a raw copy at level 0");
-    }
-  bool launched = false;
-  int uploads = 0;                                           // table slices used so far (each launch reads its own)
-  auto upload = [&](const std::vector<FrameBuildPtrs>& host, const FrameBuildPtrs** tbl, bool plane_pointers_only = true) -> int {
+  }
+
+  void mark_built(FrameLevel& L, int flavours) const {
+    if (role == 0) L.cur_have |= flavours;
+    else mark_selected(L, ithr, dthr);
+  }
+
+  // `host` in a table slice of its own on the stream; plane_pointers_only: the launch reads nothing but the frames' plane pointers, so
+  // the table the ingest of these very frames left on this stream serves as well
+  int upload(const std::vector<FrameBuildPtrs>& host, const FrameBuildPtrs** tbl, bool plane_pointers_only = true) {
     if (plane_pointers_only && eager && ctx->build_tbl_cur && int(host.size()) == n && ctx->build_tbl_frames.size() == size_t(n) &&
         std::equal(frames, frames + n, ctx->build_tbl_frames.begin())) {
-      *tbl = ctx->build_tbl_cur->as<FrameBuildPtrs>();      // the ingest of these very frames left their table on this stream
+      *tbl = ctx->build_tbl_cur->as<FrameBuildPtrs>();
       return DVO_HIP_OK;
     }
     constexpr int kSlices = 4 * kMaxLevels;
-    if (uploads == kSlices) {                                // (never in practice: a slice per level and source)
+    const size_t slice = size_t(n) * sizeof(FrameBuildPtrs);
+    if (uploads == kSlices) {                                  // (never in practice: a slice per level and source)
       DVO_HIP_TRY(ctx, hipStreamSynchronize(stream));
       uploads = 0;
     }
@@ -633,17 +676,31 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
     DVO_HIP_TRY(ctx, ctx->tables.upload(stream, up, host.data(), host.size() * sizeof(FrameBuildPtrs)));
     *tbl = up;
     return DVO_HIP_OK;
-  };
-  // Several levels, every frame missing the same planes on each of them, all to be derived from the float planes I / Z (a camera
-  // frame that has just been built): ONE launch for all levels (k_derive_levels) instead of a table upload, a counter reset and a
-  // launch per level.
-  if (l1 > l0) {
+  }
+
+  // Every frame is checked before the state of any is touched: a frame ingested straight into a role without a copy of its raw planes
+  // (option "keep_raw_copy" 0) has nothing its level 0 could be derived from in another role, and the marks -- planes "built" -- are
+  // set while the launches are still being gathered (round-5 advisor finding: the error used to leave earlier frames of the list
+  // marked as built without their launches, and a retry aligned against stale planes).
+  int check_level0_sources() const {
+    for (int i = 0; i < n; ++i) {
+      const dvo_hip_frame* f = frames[i];
+      if (!f->raw0 || f->lv[0].cur_have != 0 || f->raw_copy) continue;
+      if (lack_of(f, 0).need) return fail(ctx, DVO_HIP_ERR_INVALID, "frame has neither sampling planes nor a raw copy at level 0");
+    }
+    return DVO_HIP_OK;
+  }
+
+  // Several levels, every frame missing the same planes on each of them, all to be derived from the float planes I / Z (a camera frame
+  // that has just been built): ONE launch for all levels (k_derive_levels) instead of a table upload, a counter reset and a launch per
+  // level.  *done: that was the case, and the levels are built.
+  int uniform_span(int l0, int l1, bool* done) {
     LevelSpan span = level_span(l0, l1, cam->w, cam->h);
-    bool uniform = n <= 64;                                                             // (the check below is quadratic; large batches come through the ingest.
-    // Round 6: the size test used to FOLLOW the double loop -- 524 288 comparisons per role of a 1024-pair batch, 0.4 ms of the host
-    // thread in front of every streaming step's first launch)
+    // (the duplicate check is quadratic; large batches come through the ingest.  Round 6: the size test used to FOLLOW the double loop --
+    // 524 288 comparisons per role of a 1024-pair batch, 0.4 ms of the host thread in front of every streaming step's first launch)
+    bool uniform = n <= 64;
     for (int i = 0; i < n && uniform; ++i)
-      for (int j = 0; j < i && uniform; ++j) uniform = frames[i] != frames[j];        // (a frame listed twice: the general path skips its second visit)
+      for (int j = 0; j < i && uniform; ++j) uniform = frames[i] != frames[j];   // (a frame listed twice: the general path skips its second visit)
     for (int l = l0; l <= l1 && uniform; ++l) {
       int miss_all = -1;
       for (int i = 0; i < n && uniform; ++i) {
@@ -654,87 +711,71 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
       }
       span.flavor[l] = miss_all;
     }
-    if (uniform) {
-      std::vector<FrameBuildPtrs> host(n);
-      for (int i = 0; i < n; ++i) fill_build_ptrs(frames[i], host[i]);
-      const FrameBuildPtrs* tbl = nullptr;
-      const int rc = upload(host, &tbl);
-      if (rc != DVO_HIP_OK) return rc;
-      launch_derive_levels(stream, tbl, n, span, role, ithr, dthr, cap);
-      for (int i = 0; i < n; ++i)
-        for (int l = l0; l <= l1; ++l) {
-          FrameLevel& L = frames[i]->lv[l];
-          if (role == 0) L.cur_have |= span.flavor[l];
-          else mark_selected(L, ithr, dthr);
-        }
-      if (role == 1) {
-        const int rc = apply_selection(ctx, stream, n, frames, l0, l1, cap);
-        if (rc != DVO_HIP_OK) return rc;
-      }
-      if (eager) {
-        const int rc2 = stamp_build(ctx, n, frames);
-        if (rc2 != DVO_HIP_OK) return rc2;
-      }
-      DVO_HIP_TRY(ctx, hipGetLastError());
-      return DVO_HIP_OK;
-    }
+    if (!uniform) return DVO_HIP_OK;
+    std::vector<FrameBuildPtrs> host(n);
+    for (int i = 0; i < n; ++i) fill_build_ptrs(frames[i], host[i]);
+    const FrameBuildPtrs* tbl = nullptr;
+    int rc = upload(host, &tbl);
+    if (rc != DVO_HIP_OK) return rc;
+    launch_derive_levels(stream, tbl, n, span, role, ithr, dthr, cap);
+    launched = true;
+    for (int i = 0; i < n; ++i)
+      for (int l = l0; l <= l1; ++l) mark_built(frames[i]->lv[l], span.flavor[l]);
+    if (role == 1) rc = apply_selection(ctx, stream, n, frames, l0, l1, cap);
+    *done = rc == DVO_HIP_OK;
+    return rc;
   }
-  for (int l = l0; l <= l1; ++l) {
-    // sources, per frame: float planes I / Z (levels >= 1, and level 0 of frames created from float planes); at level 0 of a frame
-    // ingested from raw planes: the other flavour of the current role, else the frame's copy of its raw planes
+
+  // One level of the general path: the frames that lack something there, sorted by what their planes are derived from -- the float
+  // planes I / Z (levels >= 1, and level 0 of frames created from float planes); at level 0 of a frame ingested from raw planes: the
+  // other flavour of the current role, else the frame's copy of its raw planes -- and one launch per source for all of them.
+  // *second_pass: raw copies of another depth scale than the launch gathered were left out (one kernel launch takes one scale).
+  int level(int l, bool* second_pass) {
     std::vector<FrameBuildPtrs> from_planes[4], from_raw[4], ab_from_c, c_from_a, ref_from_c;
     std::vector<dvo_hip_frame*> ref_from_ab, selected;
     float raw_scale = 0.0f;
-    bool deferred = false;                                   // frames of another depth scale than the launch gathered so far
     for (int i = 0; i < n; ++i) {
       dvo_hip_frame* f = frames[i];
       FrameLevel& L = f->lv[l];
       const Lack lack = lack_of(f, l);
-      const int miss = lack.miss;
       if (!lack.need) continue;   // also skips the second visit of a frame that is listed twice
       FrameBuildPtrs p;
       fill_build_ptrs(f, p);
-      if (l == 0 && f->raw0) {
-        if (role == 0 && (L.cur_have & kCurC)) {
-          ab_from_c.push_back(p);
-        } else if (role == 0 && (L.cur_have & kCurAB)) {
-          c_from_a.push_back(p);
-        } else if (role == 1 && (L.cur_have & kCurAB)) {
-          ref_from_ab.push_back(f);
-        } else if (role == 1 && (L.cur_have & kCurC)) {
-          ref_from_c.push_back(p);
-        } else if (f->raw_copy && (raw_scale == 0.0f || f->depth_scale == raw_scale)) {
-          raw_scale = f->depth_scale;
-          p.grey = staging_grey(f);
-          p.raw = staging_depth(f);
-          from_raw[miss].push_back(p);
-        } else if (f->raw_copy) {
-          deferred = true;     // another depth scale than the frames gathered so far: picked up by the pass below
-          continue;
-        } else {
-          return fail(ctx, DVO_HIP_ERR_INVALID, "frame has neither sampling planes nor a raw copy at level 0");
-        }
+      if (l != 0 || !f->raw0) {
+        from_planes[lack.miss].push_back(p);
+      } else if (role == 0 && (L.cur_have & kCurC)) {
+        ab_from_c.push_back(p);
+      } else if (role == 0 && (L.cur_have & kCurAB)) {
+        c_from_a.push_back(p);
+      } else if (role == 1 && (L.cur_have & kCurAB)) {
+        ref_from_ab.push_back(f);
+      } else if (role == 1 && (L.cur_have & kCurC)) {
+        ref_from_c.push_back(p);
+      } else if (f->raw_copy && (raw_scale == 0.0f || f->depth_scale == raw_scale)) {
+        raw_scale = f->depth_scale;
+        p.grey = staging_grey(f);
+        p.raw = staging_depth(f);
+        from_raw[lack.miss].push_back(p);
+      } else if (f->raw_copy) {
+        *second_pass = true;
+        continue;
       } else {
-        from_planes[miss].push_back(p);
+        return fail(ctx, DVO_HIP_ERR_INVALID, "frame has neither sampling planes nor a raw copy at level 0");
       }
-      if (role == 0) {
-        L.cur_have |= miss;
-      } else {
-        mark_selected(L, ithr, dthr);
-        selected.push_back(f);
-      }
+      mark_built(L, lack.miss);
+      if (role == 1) selected.push_back(f);
     }
     const FrameBuildPtrs* tbl = nullptr;
     for (int miss = 0; miss < 4; ++miss) {
       if (!from_planes[miss].empty()) {
-        int rc = upload(from_planes[miss], &tbl);
+        const int rc = upload(from_planes[miss], &tbl);
         if (rc != DVO_HIP_OK) return rc;
         if (role == 0) launch_derive_current(stream, tbl, int(from_planes[miss].size()), l, cam->w[l], cam->h[l], cap, miss, stream_nt);
         else launch_derive_reference(stream, tbl, int(from_planes[miss].size()), l, cam->w[l], cam->h[l], ithr, dthr, cap, stream_nt);
         launched = true;
       }
       if (!from_raw[miss].empty()) {
-        int rc = upload(from_raw[miss], &tbl, /*plane_pointers_only=*/false);
+        const int rc = upload(from_raw[miss], &tbl, /*plane_pointers_only=*/false);
         if (rc != DVO_HIP_OK) return rc;
         launch_build_from_raw(stream, tbl, int(from_raw[miss].size()), raw_scale, cam->w[0], cam->h[0], /*levels=*/1, role,
                               ingest_strips_supports(cam->w[0], /*wide=*/true), ithr, dthr, cap, miss, 0, 0, stream_nt);
@@ -744,7 +785,7 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
     const struct { std::vector<FrameBuildPtrs>* list; int mode; } conversions[3] = {{&ab_from_c, 0}, {&c_from_a, 1}, {&ref_from_c, 2}};
     for (const auto& c : conversions) {
       if (c.list->empty()) continue;
-      int rc = upload(*c.list, &tbl);
+      const int rc = upload(*c.list, &tbl);
       if (rc != DVO_HIP_OK) return rc;
       launch_from_current_plane(stream, tbl, int(c.list->size()), l, cam->w[l], cam->h[l], c.mode, ithr, dthr, cap);
       launched = true;
@@ -755,24 +796,35 @@ int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int 
       launch_select_pack(stream, L.A, L.B, L.w * L.h, ithr, dthr, L.R, f->sel_count, nullptr);
       launched = true;
     }
-    if (!selected.empty()) {
-      const int rc = apply_selection(ctx, stream, int(selected.size()), selected.data(), l, l, cap);
-      if (rc != DVO_HIP_OK) return rc;
-    }
-    if (deferred) {   // frames of a second depth scale (one kernel launch takes one scale): rare, one more pass each
-      if (eager && launched) {
-        const int rc = stamp_build(ctx, n, frames);
-        if (rc != DVO_HIP_OK) return rc;
-      }
-      DVO_HIP_TRY(ctx, hipStreamSynchronize(stream));   // the table slices are reused
-      return ensure_roles(ctx, n, frames, role, l0, l1, ithr, dthr, eager, cur_want);
-    }
+    if (selected.empty()) return DVO_HIP_OK;
+    return apply_selection(ctx, stream, int(selected.size()), selected.data(), l, l, cap);
   }
-  if (eager && launched) {
-    const int rc = stamp_build(ctx, n, frames);
-    if (rc != DVO_HIP_OK) return rc;
-  }
-  DVO_HIP_TRY(ctx, hipGetLastError());
-  return DVO_HIP_OK;
-}
 
+  // the levels l0 .. l1: the fast path where it applies, else level by level, up to and including a level that asks for a second pass
+  int run(int l0, int l1, bool* second_pass) {
+    int rc = l0 == 0 ? check_level0_sources() : DVO_HIP_OK;
+    bool done = false;
+    if (rc == DVO_HIP_OK && l1 > l0) rc = uniform_span(l0, l1, &done);
+    for (int l = l0; l <= l1 && rc == DVO_HIP_OK && !done && !*second_pass; ++l) rc = level(l, second_pass);
+    if (rc == DVO_HIP_OK && eager && launched) rc = stamp_build(ctx, n, frames);   // (the frames' ticket: behind everything this pass enqueued)
+    if (rc == DVO_HIP_OK && !*second_pass) DVO_HIP_TRY(ctx, hipGetLastError());
+    return rc;
+  }
+};
+
+// Build the missing role planes of a set of frames for levels [l0, l1]: role 0 = current (flavours `cur_want[level]`, kCurAB | kCurC;
+// null: the taps A + B), role 1 = reference (R + selection count for the given thresholds).  One launch per level (and source) for
+// all frames that need it.
+// `eager`: on the build stream (dvo_hip_frames_prepare), otherwise on the main stream right before the planes are used.
+int ensure_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, int role, int l0, int l1, float ithr, float dthr, bool eager = false,
+                 const int* cur_want = nullptr) {
+  for (;;) {
+    // A pass that met raw copies of a second depth scale re-enters HERE (rare, one more pass each): the whole list again, with the
+    // table slices from the start -- they are reused, so the stream drains first.
+    RoleBuild pass(ctx, n, frames, role, ithr, dthr, eager, cur_want);
+    bool second_pass = false;
+    const int rc = pass.run(l0, l1, &second_pass);
+    if (rc != DVO_HIP_OK || !second_pass) return rc;
+    DVO_HIP_TRY(ctx, hipStreamSynchronize(pass.stream));
+  }
+}

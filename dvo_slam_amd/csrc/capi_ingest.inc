@@ -14,6 +14,12 @@ static int colour_format(int pixel_format) { return pixel_channels(pixel_format)
 // the pixel_format argument of a float-depth entry point: DVO_HIP_PIXEL_GREY8 (0) is the grey plane there
 static int mixed_format(int pixel_format) { return pixel_format == DVO_HIP_PIXEL_GREY8 ? pixel_format : colour_format(pixel_format); }
 
+// the byte ranges [a, a + na) and [b, b + nb) meet
+static bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + nb && y < x + na;
+}
+
 // The planes of an ingest of n frames of width x height pixels: format, arrays and their entries, the pitch rules; resolves src->pitch.  With
 // `frames` (entries not null), in the same pass: they share camera and levels -- a camera is shared by frames of any level count
 // (get_camera), and frames_build writes one table and launches once per level for all of them.
@@ -30,10 +36,10 @@ static int check_source(dvo_hip_context* ctx, const char* who, int n, dvo_hip_fr
   for (int i = 0; i < n; ++i) {
     if (frames && (!frames[i] || frames[i]->cam != frames[0]->cam || frames[i]->levels != frames[0]->levels))
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "frames of one build batch must share camera and levels");
-    // (one rectify launch per ingest, one lens per launch: rectify_frames)
+    // (one rectify launch per ingest, one lens per launch: lens_stage)
     if (frames && (frames[i]->lens_on != frames[0]->lens_on || std::memcmp(&frames[i]->lens, &frames[0]->lens, sizeof(dvo_hip_lens)) != 0))
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "frames of one ingest must carry the same lens, or none (dvo_hip_frames_set_lens)");
-    // (likewise one register pass per ingest, one depth rig per launch: register_frames)
+    // (likewise one register pass per ingest, one depth rig per launch: rig_stage)
     if (frames && (frames[i]->rig_on != frames[0]->rig_on || std::memcmp(&frames[i]->rig, &frames[0]->rig, sizeof(dvo_hip_depth_rig)) != 0))
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "frames of one ingest must carry the same depth rig, or none (dvo_hip_frames_set_depth_rig)");
     if (!src->planes[i] || !src->depth[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null entry");
@@ -52,31 +58,20 @@ static int check_source(dvo_hip_context* ctx, const char* who, int n, dvo_hip_fr
     if (src->depth_pitch % 4 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a float plane's pitch must be a multiple of 4");
     if (src->depth_pitch == 0) src->depth_pitch = tight_z;
   }
-  // A frame with a lens is rectified INTO its own float planes of level 0 (rectify_frames) while the pass gathers taps from the caller's
+  // A frame with a lens is rectified INTO its own float planes of level 0 (lens_stage) while the pass gathers taps from the caller's
   // planes: a source that lies in those planes -- the in-place float ingest of a lens-less frame -- would be read while it is overwritten.
-  if (frames && frames[0]->lens_on) {
-    const size_t h = size_t(frames[0]->lv[0].h), own = size_t(width) * h * 4;
-    const size_t image_bytes = src->pitch * h, depth_bytes = (depth_f32 ? src->depth_pitch : size_t(width) * 2) * h;
-    auto overlaps = [](const void* a, size_t na, const void* b, size_t nb) {
-      const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-      return x < y + nb && y < x + na;
-    };
-    for (int i = 0; i < n; ++i)
-      for (const void* mine : {static_cast<const void*>(frames[i]->lv[0].I), static_cast<const void*>(frames[i]->lv[0].Z)})
-        if (overlaps(src->planes[i], image_bytes, mine, own) || overlaps(src->depth[i], depth_bytes, mine, own))
-          return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a lens cannot be ingested from its own level-0 planes");
-  }
-  // A frame with a depth rig is registered INTO its own float plane Z of level 0 (register_frames), a scatter: a source that lies in
+  // A frame with a depth rig is registered INTO its own float plane Z of level 0 (rig_stage), a scatter: a source that lies in
   // that plane -- depth or image -- would be overwritten by the fill before it is read.
-  if (frames && frames[0]->rig_on) {
+  if (frames && (frames[0]->lens_on || frames[0]->rig_on)) {
     const size_t h = size_t(frames[0]->lv[0].h), own = size_t(width) * h * 4;
     const size_t image_bytes = src->pitch * h, depth_bytes = (depth_f32 ? src->depth_pitch : size_t(width) * 2) * h;
-    for (int i = 0; i < n; ++i) {
-      const uintptr_t y = reinterpret_cast<uintptr_t>(frames[i]->lv[0].Z);
-      const uintptr_t x = reinterpret_cast<uintptr_t>(src->depth[i]), c = reinterpret_cast<uintptr_t>(src->planes[i]);
-      if ((x < y + own && y < x + depth_bytes) || (c < y + own && y < c + image_bytes))
+    auto reads = [&](int i, const void* mine) { return overlaps(src->planes[i], image_bytes, mine, own) || overlaps(src->depth[i], depth_bytes, mine, own); };
+    for (int i = 0; i < n && frames[0]->lens_on; ++i)
+      if (reads(i, frames[i]->lv[0].I) || reads(i, frames[i]->lv[0].Z))
+        return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a lens cannot be ingested from its own level-0 planes");
+    for (int i = 0; i < n && frames[0]->rig_on; ++i)
+      if (reads(i, frames[i]->lv[0].Z))
         return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a depth rig cannot be ingested from its own level-0 plane Z");
-    }
   }
   return DVO_HIP_OK;
 }

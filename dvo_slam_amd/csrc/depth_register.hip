@@ -11,6 +11,7 @@
 // used (unsigned minimum on the float's bits, relaxed, agent scope), at the DEFAULT cache policy: the ingest reads the plane back at
 // once.  Source planes are read with the non-temporal policy when the build stream's launches are ("stream_policy").  The result does
 // not depend on the order of the atomics.  ZF = float depth, else u16.  No LDS, no barriers, 256-thread workgroups.
+#include "dispatch.h"
 #include "global_ptr.h"
 #include "launch.h"
 #include "depth_rig.h"
@@ -79,17 +80,15 @@ void launch_depth_register(hipStream_t s, const DepthRigPtrs* tbl, int n_frames,
   const long long fill_items = ((long long)(pixels >> 2) * n_frames + 255) / 256;
   const long long fill_blocks = fill_items < 1 ? 1 : fill_items;
   const dim3 block(256);
-  k_depth_fill<<<dim3(int(max_workgroups > 0 && fill_blocks > max_workgroups ? max_workgroups : fill_blocks)), block, 0, s>>>(tbl, n_frames, pixels);
+  k_depth_fill<<<dim3(capped_grid(fill_blocks, max_workgroups)), block, 0, s>>>(tbl, n_frames, pixels);
   const int tx = (a.w + kRegW - 1) / kRegW, ty = (a.h + kRegH - 1) / kRegH;
   const long long total = (long long)tx * ty * n_frames;
-  const dim3 grid(int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total));
-#define DVO_LAUNCH_REGISTER(ZF, NT) k_depth_register<ZF, NT><<<grid, block, 0, s>>>(tbl, a, tx, ty, n_frames)
-  if (depth_f32) {
-    if (stream_nt) DVO_LAUNCH_REGISTER(true, true); else DVO_LAUNCH_REGISTER(true, false);
-  } else {
-    if (stream_nt) DVO_LAUNCH_REGISTER(false, true); else DVO_LAUNCH_REGISTER(false, false);
-  }
-#undef DVO_LAUNCH_REGISTER
+  const dim3 grid(capped_grid(total, max_workgroups));
+  with_bool(depth_f32, [&](auto ZF) {
+    with_bool(stream_nt, [&](auto NT) {
+      k_depth_register<decltype(ZF)::value, decltype(NT)::value><<<grid, block, 0, s>>>(tbl, a, tx, ty, n_frames);
+    });
+  });
 }
 
 }  // namespace dvo_hip

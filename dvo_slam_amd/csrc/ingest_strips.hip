@@ -366,7 +366,7 @@ void launch_derive_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames
                           int max_workgroups, int cur_flavor, bool stream_nt) {
   const int gx = (w + kStripW - 1) / kStripW, gy = (h + kStripH * kStripsPerGroup - 1) / (kStripH * kStripsPerGroup);
   const long long total = (long long)gx * gy * n_frames;
-  const dim3 grid(int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total)), block(256);
+  const dim3 grid(capped_grid(total, max_workgroups)), block(256);
   auto launch = [&](auto ROLE, auto TAPS) {
     with_bool(stream_nt && level <= 1, [&](auto NT) {
       k_derive_strips<decltype(ROLE)::value, decltype(TAPS)::value, decltype(NT)::value>
@@ -394,7 +394,7 @@ void launch_ingest_strips(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames
                           bool depth_f32) {
   const int gx = (w0 + kStripW - 1) / kStripW, gy = (h0 + kStripH * kStripsPerGroup - 1) / (kStripH * kStripsPerGroup);
   const long long total = (long long)gx * gy * n_frames;
-  const dim3 grid(int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total)), block(256);
+  const dim3 grid(capped_grid(total, max_workgroups)), block(256);
   const int lv = levels < 4 ? levels : 4;
   // TAPS follows the role: the reference role always, the current role with the gathered taps, never without a role
   with_value<1, 0, -1>(role, [&](auto ROLE) {

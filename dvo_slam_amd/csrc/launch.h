@@ -83,6 +83,10 @@ void launch_depth_register(hipStream_t s, const DepthRigPtrs* tbl, int n_frames,
 bool sensor_src_dwords(const void* plane, size_t pitch);
 void launch_sensor_convert(hipStream_t s, const SensorPtrs* tbl, int n_frames, const SensorArgs& a, bool packed, int max_workgroups, bool stream_nt);
 
+// the grid of a kernel that walks `total` tiles with a grid stride: a workgroup per tile, or max_workgroups of them where that cap is set
+// (> 0: a background build next to an alignment) and lower
+inline int capped_grid(long long total, int max_workgroups) { return int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total); }
+
 // the grid of a kernel that walks `items` elements with a grid stride, 256 per workgroup: 1 .. 8192 workgroups
 inline int stride_grid(unsigned long long items) {
   const unsigned long long blocks = (items + 255) / 256;

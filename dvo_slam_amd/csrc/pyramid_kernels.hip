@@ -417,12 +417,6 @@ __global__ void k_unpack_plane(const float4* __restrict__ A, const float2* __res
   out[i] = v;
 }
 
-// grid of a frame-build kernel: one workgroup per tile unless a cap is given (background build)
-static int capped_grid(int tiles_x, int tiles_y, int n_frames, int max_workgroups) {
-  const long long total = (long long)tiles_x * tiles_y * n_frames;
-  return int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total);
-}
-
 static void zero_counts(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int l0, int l1) {
   k_zero_counts_levels<<<dim3((n_frames + 63) / 64), dim3(64), 0, s>>>(tbl, n_frames, l0, l1);
 }
@@ -460,7 +454,7 @@ void launch_build_from_raw(hipStream_t s, const FrameBuildPtrs* tbl, int n_frame
     return;
   }
   const int tx = (w0 + kB0W - 1) / kB0W, ty = (h0 + kB0H - 1) / kB0H;
-  const dim3 grid(capped_grid(tx, ty, n_frames, max_workgroups)), block(256);
+  const dim3 grid(capped_grid((long long)tx * ty * n_frames, max_workgroups)), block(256);
   const int lv = levels < 4 ? levels : 4;
   with_value<0, 1, -1>(role, [&](auto ROLE) {
     with_value<3, 4, kChF32, 0>(colour_channels, [&](auto CH) {
@@ -492,7 +486,7 @@ void launch_derive_current(hipStream_t s, const FrameBuildPtrs* tbl, int n_frame
 void launch_from_current_plane(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, int level, int w, int h, int mode, float ithr, float dthr,
                                int max_workgroups) {
   const int tx = (w + 63) / 64, ty = (h + 3) / 4;
-  const dim3 grid(capped_grid(tx, ty, n_frames, max_workgroups)), block(64, 4);
+  const dim3 grid(capped_grid((long long)tx * ty * n_frames, max_workgroups)), block(64, 4);
   if (mode == 2) zero_counts(s, tbl, n_frames, level, level);
   with_value<0, 1, 2>(mode, [&](auto MODE) {
     k_from_current_plane<decltype(MODE)::value><<<grid, block, 0, s>>>(tbl, level, w, h, ithr, dthr, tx, ty, n_frames);
@@ -502,7 +496,7 @@ void launch_from_current_plane(hipStream_t s, const FrameBuildPtrs* tbl, int n_f
 void launch_derive_levels(hipStream_t s, const FrameBuildPtrs* tbl, int n_frames, const LevelSpan& span, int role, float ithr, float dthr,
                           int max_workgroups) {
   const int total = span.tile0[span.l1 + 1] * n_frames;
-  const dim3 grid(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total), block(64, 4);
+  const dim3 grid(capped_grid(total, max_workgroups)), block(64, 4);
   if (role == 1) zero_counts(s, tbl, n_frames, span.l0, span.l1);
   with_value<1, 0>(role, [&](auto ROLE) { k_derive_levels<decltype(ROLE)::value><<<grid, block, 0, s>>>(tbl, span, n_frames, ithr, dthr); });
 }
@@ -523,8 +517,7 @@ void launch_select_pack(hipStream_t s, const float4* A, const float2* B, int n, 
 
 void launch_apply_selection(hipStream_t s, const SelectionApply* tbl, int n_frames, const LevelSpan& span, int max_workgroups) {
   const int total = span.tile0[span.l1 + 1] * n_frames;
-  const int grid = max_workgroups > 0 && total > max_workgroups ? max_workgroups : total;
-  k_apply_selection<<<dim3(grid), dim3(256), 0, s>>>(tbl, span, n_frames);
+  k_apply_selection<<<dim3(capped_grid(total, max_workgroups)), dim3(256), 0, s>>>(tbl, span, n_frames);
 }
 
 void launch_pack_accepted(hipStream_t s, const float4* A, const uint8_t* accepted, int n, float2* R, int* count) {

@@ -11,6 +11,7 @@
 // float planes written with it: they are read back once, by the ingest behind this pass, and must not displace the coarse levels.
 // Templated on the caller's formats: CH = 0 grey8, 3 / 4 a colour format (byte order is a wave-uniform choice of weights), kChF32 a
 // float image; ZF = float depth, else u16.  Pitches as the ingest takes them.  No LDS, no barriers, 256-thread workgroups.
+#include "dispatch.h"
 #include "global_ptr.h"
 #include "launch.h"
 #include "lens.h"
@@ -69,19 +70,16 @@ void launch_rectify(hipStream_t s, const RectifyPtrs* tbl, int n_frames, const R
                     bool stream_nt) {
   const int tx = (a.w + kRectW - 1) / kRectW, ty = (a.h + kRectH - 1) / kRectH;
   const long long total = (long long)tx * ty * n_frames;
-  const dim3 grid(int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total)), block(256);
-#define DVO_LAUNCH_RECTIFY_NT(CH, ZF, NT) k_rectify<CH, ZF, NT><<<grid, block, 0, s>>>(tbl, a, tx, ty, n_frames)
-#define DVO_LAUNCH_RECTIFY(CH, ZF) \
-  do { if (stream_nt) DVO_LAUNCH_RECTIFY_NT(CH, ZF, true); else DVO_LAUNCH_RECTIFY_NT(CH, ZF, false); } while (0)
-#define DVO_LAUNCH_RECTIFY_DEPTH(CH) \
-  do { if (depth_f32) DVO_LAUNCH_RECTIFY(CH, true); else DVO_LAUNCH_RECTIFY(CH, false); } while (0)
-  if (channels == kChF32) DVO_LAUNCH_RECTIFY(kChF32, true);   // (a float image comes with float depth)
-  else if (channels == 3) DVO_LAUNCH_RECTIFY_DEPTH(3);
-  else if (channels == 4) DVO_LAUNCH_RECTIFY_DEPTH(4);
-  else DVO_LAUNCH_RECTIFY_DEPTH(0);
-#undef DVO_LAUNCH_RECTIFY_DEPTH
-#undef DVO_LAUNCH_RECTIFY
-#undef DVO_LAUNCH_RECTIFY_NT
+  const dim3 grid(capped_grid(total, max_workgroups)), block(256);
+  with_value<kChF32, 3, 4, 0>(channels, [&](auto CH) {
+    with_bool(depth_f32 || channels == kChF32, [&](auto ZF) {   // (a float image comes with float depth)
+      with_bool(stream_nt, [&](auto NT) {
+        constexpr int kCh = decltype(CH)::value;
+        constexpr bool kZf = decltype(ZF)::value;
+        if constexpr (kCh != kChF32 || kZf) k_rectify<kCh, kZf, decltype(NT)::value><<<grid, block, 0, s>>>(tbl, a, tx, ty, n_frames);
+      });
+    });
+  });
 }
 
 }  // namespace dvo_hip

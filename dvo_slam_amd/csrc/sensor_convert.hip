@@ -18,6 +18,7 @@
 //            (SensorArgs::dst_wide); else element by element.
 // NT: planes read, and the converted plane written, with the non-temporal policy when the build stream's launches are ("stream_policy"):
 // the plane is read back once, by the pass behind this one.
+#include "dispatch.h"
 #include "global_ptr.h"
 #include "launch.h"
 #include "sensor_formats.h"
@@ -160,17 +161,14 @@ bool sensor_src_dwords(const void* plane, size_t pitch) { return reinterpret_cas
 void launch_sensor_convert(hipStream_t s, const SensorPtrs* tbl, int n_frames, const SensorArgs& a, bool packed, int max_workgroups, bool stream_nt) {
   const int tx = (a.w + kSensorW - 1) / kSensorW, ty = (a.h + kSensorH - 1) / kSensorH;
   const long long total = (long long)tx * ty * n_frames;
-  const dim3 grid(int(max_workgroups > 0 && total > max_workgroups ? max_workgroups : total)), block(256);
-#define DVO_LAUNCH_SENSOR_NT(FMT, OUT, NT) k_sensor_convert<FMT, OUT, NT><<<grid, block, 0, s>>>(tbl, a, tx, ty, n_frames)
-#define DVO_LAUNCH_SENSOR(FMT, OUT) \
-  do { if (stream_nt) DVO_LAUNCH_SENSOR_NT(FMT, OUT, true); else DVO_LAUNCH_SENSOR_NT(FMT, OUT, false); } while (0)
-#define DVO_LAUNCH_SENSOR_OUT(FMT) \
-  do { if (packed) DVO_LAUNCH_SENSOR(FMT, 1); else DVO_LAUNCH_SENSOR(FMT, 0); } while (0)
-  if (sensor_is_bayer(a.format)) DVO_LAUNCH_SENSOR_OUT(0);
-  else DVO_LAUNCH_SENSOR_OUT(1);
-#undef DVO_LAUNCH_SENSOR_OUT
-#undef DVO_LAUNCH_SENSOR
-#undef DVO_LAUNCH_SENSOR_NT
+  const dim3 grid(capped_grid(total, max_workgroups)), block(256);
+  with_value<0, 1>(sensor_is_bayer(a.format) ? 0 : 1, [&](auto FMT) {
+    with_bool(packed, [&](auto OUT) {
+      with_bool(stream_nt, [&](auto NT) {
+        k_sensor_convert<decltype(FMT)::value, int(decltype(OUT)::value), decltype(NT)::value><<<grid, block, 0, s>>>(tbl, a, tx, ty, n_frames);
+      });
+    });
+  });
 }
 
 }  // namespace dvo_hip
