@@ -128,6 +128,8 @@ EXPORTS = [
     "dvo_hip_frames_set_colour", "dvo_hip_frames_clear_colour", "dvo_hip_frame_download_colour", "dvo_hip_map_create_ex",
     "dvo_hip_map_extract_colour", "dvo_hip_map_render_colour",
     "dvo_hip_map_info", "dvo_hip_map_merge", "dvo_hip_map_move_submaps", "dvo_hip_map_export", "dvo_hip_map_merge_records",
+    "dvo_hip_frames_normals", "dvo_hip_map_extract_normals", "dvo_hip_map_render_normals", "dvo_hip_map_export_ex",
+    "dvo_hip_map_merge_records_ex",
     "dvo_hip_graph_create", "dvo_hip_graph_destroy", "dvo_hip_graph_set_vertices", "dvo_hip_graph_set_poses", "dvo_hip_graph_set_edges",
     "dvo_hip_graph_params_default", "dvo_hip_graph_optimize", "dvo_hip_graph_get_poses", "dvo_hip_graph_edge_stats",
     "dvo_hip_graph_linearise", "dvo_hip_graph_multiply", "dvo_hip_graph_optimize_batch",
@@ -149,9 +151,12 @@ PIXEL_F32 = 5
 DEPTH_U16, DEPTH_F32 = 0, 1
 DEPTH_FORMATS = {"u16": DEPTH_U16, "f32": DEPTH_F32}
 MAP_COLOUR = 1   # DVO_HIP_MAP_COLOUR
+MAP_NORMALS = 4  # DVO_HIP_MAP_NORMALS (2 stays an unknown flag)
 # a voxel record of dvo_hip_map_export / dvo_hip_map_merge_records (32 bytes: cloud_map.h, MapSlot) and its colour record (16: MapColourSlot)
 MAP_RECORD = [("key", "<u8"), ("n", "<u4"), ("sx", "<u4"), ("sy", "<u4"), ("sz", "<u4"), ("si", "<u4"), ("pad", "<u4")]
 MAP_COLOUR_RECORD = [("sr", "<u4"), ("sg", "<u4"), ("sb", "<u4"), ("pad", "<u4")]
+# ... and its normal record (16: cloud_normal.h, MapNormalSlot; dvo_hip_map_export_ex / dvo_hip_map_merge_records_ex)
+MAP_NORMAL_RECORD = [("snx", "<u4"), ("sny", "<u4"), ("snz", "<u4"), ("nn", "<u4")]
 COMM_ID_BYTES = 128
 
 
@@ -282,6 +287,13 @@ def lib():
         L.dvo_hip_map_move_submaps.argtypes = [vp, vp, C.c_int, mp, dp, dp]
         L.dvo_hip_map_export.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
         L.dvo_hip_map_merge_records.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_int, C.c_float, C.c_int, dp]
+    if hasattr(L, "dvo_hip_frames_normals"):   # (likewise: an older build's map holds no normals)
+        dp, rp = C.POINTER(C.c_double), C.POINTER(RenderParams)
+        L.dvo_hip_frames_normals.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.c_int, C.c_float, C.c_float, C.POINTER(vp), C.c_int]
+        L.dvo_hip_map_extract_normals.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
+        L.dvo_hip_map_render_normals.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, fp, dp, rp, C.POINTER(vp), C.POINTER(vp), C.c_int]
+        L.dvo_hip_map_export_ex.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
+        L.dvo_hip_map_merge_records_ex.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_int, C.c_float, C.c_int, dp]
     if hasattr(L, "dvo_hip_graph_create"):   # (likewise: an older build optimises no pose graph)
         dp, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         L.dvo_hip_graph_create.argtypes = [vp, C.POINTER(vp)]

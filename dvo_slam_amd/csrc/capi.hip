@@ -983,6 +983,7 @@ int prepare_roles(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* fram
 #include "capi_ingest.inc"   // the raw-frame ingest: dvo_hip_frame_create_*, dvo_hip_frames_update_*, dvo_hip_flush_deferred
 #include "capi_map.inc"      // the keyframe map: dvo_hip_map_*, dvo_hip_frames_world_points, dvo_hip_map_render*
 #include "capi_colour.inc"   // the colour of frames: dvo_hip_frames_set_colour, dvo_hip_frames_clear_colour, dvo_hip_frame_download_colour
+#include "capi_normal.inc"   // surface normals: dvo_hip_frames_normals, dvo_hip_map_extract_normals, dvo_hip_map_render_normals
 #include "capi_graph.inc"    // the keyframe pose graph: dvo_hip_graph_*
 
 int dvo_hip_upload_wait(dvo_hip_context* ctx) {

@@ -9,6 +9,8 @@ struct dvo_hip_map {
   DevBuf slots, counters;
   DevBuf colour;                       // a coloured map (DVO_HIP_MAP_COLOUR): the side table, capacity * sizeof(MapColourSlot); else empty
   bool coloured = false;
+  DevBuf normals;                      // a map with normals (DVO_HIP_MAP_NORMALS): the side table, capacity * sizeof(MapNormalSlot); else empty
+  bool with_normals = false;
   // kMapCntCandidates, kMapCntDropped and kMapCntUnmatched as last read back (zero after a clear)
   unsigned long long candidates = 0, dropped = 0, unmatched = 0;
 };
@@ -23,6 +25,7 @@ MapTable map_table(const dvo_hip_map* map) {
   t.capacity = map->capacity;
   t.leaf = map->leaf;
   t.colour = map->coloured ? map->colour.as<MapColourSlot>() : nullptr;
+  t.normals = map->with_normals ? map->normals.as<MapNormalSlot>() : nullptr;
   return t;
 }
 
@@ -146,7 +149,7 @@ int dvo_hip_map_create_ex(dvo_hip_context* ctx, float leaf, size_t capacity_slot
   DVO_LOCK(ctx);
   if (!ctx || !out) return fail(ctx, DVO_HIP_ERR_INVALID, "map_create: bad argument");
   *out = nullptr;
-  if (flags & ~DVO_HIP_MAP_COLOUR) return fail(ctx, DVO_HIP_ERR_INVALID, "map_create: unknown flag");
+  if (flags & ~(DVO_HIP_MAP_COLOUR | DVO_HIP_MAP_NORMALS)) return fail(ctx, DVO_HIP_ERR_INVALID, "map_create: unknown flag");
   if (!(leaf > 0.0f && leaf < INFINITY)) return fail(ctx, DVO_HIP_ERR_INVALID, "map_create: the leaf size must be finite and > 0");
   if (capacity_slots > (size_t(1) << 32)) return fail(ctx, DVO_HIP_ERR_INVALID, "map_create: at most 2^32 slots");
   size_t capacity = 64;
@@ -157,8 +160,10 @@ int dvo_hip_map_create_ex(dvo_hip_context* ctx, float leaf, size_t capacity_slot
   map->leaf = leaf;
   map->capacity = capacity;
   map->coloured = (flags & DVO_HIP_MAP_COLOUR) != 0;
+  map->with_normals = (flags & DVO_HIP_MAP_NORMALS) != 0;
   hipError_t e = map->slots.reserve(capacity * sizeof(MapSlot));
   if (e == hipSuccess && map->coloured) e = map->colour.reserve(capacity * sizeof(MapColourSlot));
+  if (e == hipSuccess && map->with_normals) e = map->normals.reserve(capacity * sizeof(MapNormalSlot));
   if (e == hipSuccess) e = map->counters.reserve(sizeof(unsigned long long) * kMapCounters);
   if (e == hipSuccess) {
     launch_map_clear(ctx->stream, map_table(map));
@@ -167,6 +172,7 @@ int dvo_hip_map_create_ex(dvo_hip_context* ctx, float leaf, size_t capacity_slot
   if (e != hipSuccess) {
     map->slots.release();
     map->colour.release();
+    map->normals.release();
     map->counters.release();
     delete map;
     ctx->err = std::string("map_create: ") + hipGetErrorString(e);
@@ -185,6 +191,7 @@ void dvo_hip_map_destroy(dvo_hip_context* ctx, dvo_hip_map* map) {
   }
   map->slots.release();
   map->colour.release();
+  map->normals.release();
   map->counters.release();
   delete map;
 }
@@ -291,9 +298,10 @@ int dvo_hip_map_rehash(dvo_hip_context* ctx, dvo_hip_map* map, size_t capacity_s
     return fail(ctx, DVO_HIP_ERR_INVALID, "map_rehash: the capacity must be a power of two, 64 .. 2^32 slots (0: as it is)");
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   // the second table and its counters: both tables exist during this call only
-  DevBuf slots, counters, colour;
+  DevBuf slots, counters, colour, normals;
   hipError_t e = slots.reserve(capacity * sizeof(MapSlot));
   if (e == hipSuccess && map->coloured) e = colour.reserve(capacity * sizeof(MapColourSlot));
+  if (e == hipSuccess && map->with_normals) e = normals.reserve(capacity * sizeof(MapNormalSlot));
   if (e == hipSuccess) e = counters.reserve(sizeof(unsigned long long) * kMapCounters);
   unsigned long long was[kMapCounters], now[kMapCounters];
   if (e == hipSuccess) {
@@ -302,6 +310,7 @@ int dvo_hip_map_rehash(dvo_hip_context* ctx, dvo_hip_map* map, size_t capacity_s
     to.counters = counters.as<unsigned long long>();
     to.capacity = capacity;
     to.colour = map->coloured ? colour.as<MapColourSlot>() : nullptr;
+    to.normals = map->with_normals ? normals.as<MapNormalSlot>() : nullptr;
     launch_map_rehash(ctx->stream, map_table(map), to);
     e = hipGetLastError();
   }
@@ -320,6 +329,7 @@ int dvo_hip_map_rehash(dvo_hip_context* ctx, dvo_hip_map* map, size_t capacity_s
     if (e != hipSuccess) (void)hipStreamSynchronize(ctx->stream);   // (nothing still writes the table that is freed)
     slots.release();
     colour.release();
+    normals.release();
     counters.release();
     if (e != hipSuccess) {
       ctx->err = std::string("map_rehash: ") + hipGetErrorString(e);
@@ -330,9 +340,11 @@ int dvo_hip_map_rehash(dvo_hip_context* ctx, dvo_hip_map* map, size_t capacity_s
   }
   std::swap(map->slots, slots);
   std::swap(map->colour, colour);
+  std::swap(map->normals, normals);
   std::swap(map->counters, counters);
   slots.release();
   colour.release();
+  normals.release();
   counters.release();
   map->capacity = capacity;
   map->candidates = now[kMapCntCandidates];
@@ -410,21 +422,25 @@ int map_read_out(dvo_hip_context* ctx, dvo_hip_map* map, size_t max, const std::
   return DVO_HIP_OK;
 }
 
-// dvo_hip_map_extract (with_colour false, rgba null) and dvo_hip_map_extract_colour
+// dvo_hip_map_extract (with_colour false, rgba null), dvo_hip_map_extract_colour and -- with_normals, normals the records' array; rgba
+// may be given for a map that also has colour -- dvo_hip_map_extract_normals
 int map_extract(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_points, float* xyzi, bool with_colour, uint32_t* rgba, uint32_t* counts_or_null,
-                uint64_t* keys_or_null, int out_on_device, size_t* n_points, const char* who) {
+                uint64_t* keys_or_null, int out_on_device, size_t* n_points, const char* who, bool with_normals = false, float* normals = nullptr) {
   const int rc0 = check_map(ctx, map, who);
   if (rc0 != DVO_HIP_OK) return rc0;
-  if (with_colour && !map->coloured) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no colour (dvo_hip_map_create_ex, DVO_HIP_MAP_COLOUR)");
-  if (!n_points || (max_points > 0 && (!xyzi || (with_colour && !rgba)))) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  if (with_normals && !map->with_normals) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no normals (dvo_hip_map_create_ex, DVO_HIP_MAP_NORMALS)");
+  if ((with_colour || rgba) && !map->coloured) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no colour (dvo_hip_map_create_ex, DVO_HIP_MAP_COLOUR)");
+  if (!n_points || (max_points > 0 && (!xyzi || (with_colour && !rgba) || (with_normals && !normals)))) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
+  if (out_on_device && normals && reinterpret_cast<uintptr_t>(normals) % 16 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device normals array must be 16-byte aligned");
   if (out_on_device && xyzi && reinterpret_cast<uintptr_t>(xyzi) % 16 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device xyzi must be 16-byte aligned");
   if (out_on_device && rgba && reinterpret_cast<uintptr_t>(rgba) % 4 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device rgba must be 4-byte aligned");
   const MapTable t = map_table(map);
   unsigned long long c[kMapCounters];
-  const int rc = map_read_out(ctx, map, max_points, {{xyzi, 16}, {keys_or_null, 8}, {counts_or_null, 4}, {rgba, 4}}, out_on_device,
+  const int rc = map_read_out(ctx, map, max_points, {{xyzi, 16}, {normals, 16}, {keys_or_null, 8}, {counts_or_null, 4}, {rgba, 4}}, out_on_device,
                               [&](unsigned long long n, void* const* dev) {
-                                return launch_map_extract(ctx->stream, t, n, static_cast<float4*>(dev[0]), static_cast<uint32_t*>(dev[2]),
-                                                          static_cast<unsigned long long*>(dev[1]), static_cast<uint32_t*>(dev[3]));
+                                return launch_map_extract(ctx->stream, t, n, static_cast<float4*>(dev[0]), static_cast<uint32_t*>(dev[3]),
+                                                          static_cast<unsigned long long*>(dev[2]), static_cast<uint32_t*>(dev[4]),
+                                                          static_cast<float4*>(dev[1]));
                               },
                               c, n_points);
   if (rc != DVO_HIP_OK) return rc;
@@ -455,6 +471,7 @@ namespace {
 struct MergeSource {
   const MapSlot* slots;
   const MapColourSlot* colour;
+  const MapNormalSlot* normals;
   unsigned long long count;
   float leaf;
   int sign;
@@ -488,6 +505,7 @@ int check_merge_map(dvo_hip_context* ctx, const dvo_hip_map* dst, const dvo_hip_
   if (src->ctx != ctx) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a source map of another context (dvo_hip_map_export there, dvo_hip_map_merge_records here)");
   if (src == dst) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a map cannot be merged into itself");
   if (src->coloured != dst->coloured) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a coloured and a grey map do not merge");
+  if (src->with_normals != dst->with_normals) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a map with normals and one without do not merge");
   return DVO_HIP_OK;
 }
 
@@ -495,6 +513,7 @@ MergeSource merge_source_of(const dvo_hip_map* src, int sign, const double* pose
   MergeSource s;
   s.slots = src->slots.as<MapSlot>();
   s.colour = src->coloured ? src->colour.as<MapColourSlot>() : nullptr;
+  s.normals = src->with_normals ? src->normals.as<MapNormalSlot>() : nullptr;
   s.count = src->capacity;
   s.leaf = src->leaf;
   s.sign = sign;
@@ -529,6 +548,7 @@ int run_map_merge(dvo_hip_context* ctx, dvo_hip_map* dst, const std::vector<Merg
     MapMergeEntry& e = host[i];
     e.slots = s.slots;
     e.colour = dst->coloured ? s.colour : nullptr;
+    e.normals = dst->with_normals ? s.normals : nullptr;
     e.count = s.count;
     const unsigned long long oor = theirs[i * kMapCounters + kMapCntOutOfRange], unusable = theirs[i * kMapCounters + kMapCntUnusable];
     e.out_of_range = s.sign < 0 ? 0ull - oor : oor;
@@ -546,14 +566,15 @@ int run_map_merge(dvo_hip_context* ctx, dvo_hip_map* dst, const std::vector<Merg
 }
 
 }  // namespace
-static_assert(sizeof(MapSlot) == 32 && sizeof(MapColourSlot) == 16, "a voxel record is 32 bytes, its colour record 16 (include/dvo_hip.h)");
+static_assert(sizeof(MapSlot) == 32 && sizeof(MapColourSlot) == 16 && sizeof(MapNormalSlot) == 16,
+              "a voxel record is 32 bytes, its colour record and its normal record 16 each (include/dvo_hip.h)");
 
 int dvo_hip_map_info(dvo_hip_context* ctx, dvo_hip_map* map, float* leaf, unsigned* flags, uint64_t* capacity) {
   DVO_LOCK(ctx);
   const int rc = check_map(ctx, map, "map_info");
   if (rc != DVO_HIP_OK) return rc;
   if (leaf) *leaf = map->leaf;
-  if (flags) *flags = map->coloured ? DVO_HIP_MAP_COLOUR : 0u;
+  if (flags) *flags = (map->coloured ? DVO_HIP_MAP_COLOUR : 0u) | (map->with_normals ? DVO_HIP_MAP_NORMALS : 0u);
   if (capacity) *capacity = map->capacity;
   return DVO_HIP_OK;
 }
@@ -598,21 +619,27 @@ int dvo_hip_map_move_submaps(dvo_hip_context* ctx, dvo_hip_map* dst, int n_src, 
   return run_map_merge(ctx, dst, sources, true, who);
 }
 
-int dvo_hip_map_export(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_records, void* records, void* colour_records_or_null, int out_on_device,
-                       size_t* n_records) {
-  DVO_LOCK(ctx);
-  const char* who = "map_export";
+namespace {
+
+// dvo_hip_map_export (normal_records null) and dvo_hip_map_export_ex
+int map_export(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_records, void* records, void* colour_records_or_null, void* normal_records_or_null,
+               int out_on_device, size_t* n_records, const char* who) {
   const int rc0 = check_map(ctx, map, who);
   if (rc0 != DVO_HIP_OK) return rc0;
   if (!n_records || (max_records > 0 && !records)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
   if (colour_records_or_null && !map->coloured) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no colour (dvo_hip_map_create_ex, DVO_HIP_MAP_COLOUR)");
-  if (out_on_device && ((records && !aligned_to(records, 16)) || (colour_records_or_null && !aligned_to(colour_records_or_null, 16))))
+  if (normal_records_or_null && !map->with_normals) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no normals (dvo_hip_map_create_ex, DVO_HIP_MAP_NORMALS)");
+  if (out_on_device && ((records && !aligned_to(records, 16)) || (colour_records_or_null && !aligned_to(colour_records_or_null, 16)) ||
+                        (normal_records_or_null && !aligned_to(normal_records_or_null, 16))))
     return fail(ctx, DVO_HIP_ERR_INVALID, who, "device records must be 16-byte aligned");
   const MapTable t = map_table(map);
   unsigned long long c[kMapCounters];
-  const int rc = map_read_out(ctx, map, max_records, {{records, sizeof(MapSlot)}, {colour_records_or_null, sizeof(MapColourSlot)}}, out_on_device,
+  const int rc = map_read_out(ctx, map, max_records,
+                              {{records, sizeof(MapSlot)}, {colour_records_or_null, sizeof(MapColourSlot)}, {normal_records_or_null, sizeof(MapNormalSlot)}},
+                              out_on_device,
                               [&](unsigned long long n, void* const* dev) {
-                                return launch_map_export(ctx->stream, t, n, static_cast<MapSlot*>(dev[0]), static_cast<MapColourSlot*>(dev[1]));
+                                return launch_map_export(ctx->stream, t, n, static_cast<MapSlot*>(dev[0]), static_cast<MapColourSlot*>(dev[1]),
+                                                         static_cast<MapNormalSlot*>(dev[2]));
                               },
                               c, n_records);
   if (rc != DVO_HIP_OK) return rc;
@@ -624,17 +651,36 @@ int dvo_hip_map_export(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_record
   return DVO_HIP_OK;
 }
 
-int dvo_hip_map_merge_records(dvo_hip_context* ctx, dvo_hip_map* dst, size_t n_records, const void* records, const void* colour_or_null, int on_device,
-                              float leaf_src, int sign, const double* pose_or_null) {
+}  // namespace
+
+int dvo_hip_map_export(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_records, void* records, void* colour_records_or_null, int out_on_device,
+                       size_t* n_records) {
   DVO_LOCK(ctx);
-  const char* who = "map_merge_records";
+  return map_export(ctx, map, max_records, records, colour_records_or_null, nullptr, out_on_device, n_records, "map_export");
+}
+
+int dvo_hip_map_export_ex(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_records, void* records, void* colour_records_or_null,
+                          void* normal_records_or_null, int out_on_device, size_t* n_records) {
+  DVO_LOCK(ctx);
+  return map_export(ctx, map, max_records, records, colour_records_or_null, normal_records_or_null, out_on_device, n_records, "map_export_ex");
+}
+
+namespace {
+
+// dvo_hip_map_merge_records (normals null: refused by a destination with normals, which it cannot supply) and dvo_hip_map_merge_records_ex
+int map_merge_records(dvo_hip_context* ctx, dvo_hip_map* dst, size_t n_records, const void* records, const void* colour_or_null, const void* normals_or_null,
+                      int on_device, float leaf_src, int sign, const double* pose_or_null, const char* who) {
   int rc = check_map(ctx, dst, who);
   if (rc != DVO_HIP_OK) return rc;
+  if (dst->with_normals && n_records > 0 && !normals_or_null)
+    return fail(ctx, DVO_HIP_ERR_INVALID, who, "a map with normals takes records with normal records (dvo_hip_map_merge_records_ex)");
+  if (!dst->with_normals && normals_or_null) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a map without normals takes no normal records");
   if (n_records > (size_t(1) << 32)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "at most 2^32 records");
   if (n_records > 0 && !records) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
   if (dst->coloured && n_records > 0 && !colour_or_null) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a coloured map takes records with colour records");
   if (!dst->coloured && colour_or_null) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a grey map takes no colour records");
-  if (on_device && ((records && !aligned_to(records, 16)) || (colour_or_null && !aligned_to(colour_or_null, 16))))
+  if (on_device && ((records && !aligned_to(records, 16)) || (colour_or_null && !aligned_to(colour_or_null, 16)) ||
+                    (normals_or_null && !aligned_to(normals_or_null, 16))))
     return fail(ctx, DVO_HIP_ERR_INVALID, who, "device records must be 16-byte aligned");
   rc = check_merge_source(ctx, dst, leaf_src, sign, pose_or_null, who);
   if (rc != DVO_HIP_OK) return rc;
@@ -643,15 +689,21 @@ int dvo_hip_map_merge_records(dvo_hip_context* ctx, dvo_hip_map* dst, size_t n_r
   MergeSource s;
   s.slots = static_cast<const MapSlot*>(records);
   s.colour = static_cast<const MapColourSlot*>(colour_or_null);
+  s.normals = static_cast<const MapNormalSlot*>(normals_or_null);
   if (!on_device) {
     // host records: staged on the main stream, then the same kernel
-    DVO_HIP_TRY(ctx, ctx->map_stage.reserve(n_records * (sizeof(MapSlot) + sizeof(MapColourSlot))));
+    DVO_HIP_TRY(ctx, ctx->map_stage.reserve(n_records * (sizeof(MapSlot) + sizeof(MapColourSlot) + sizeof(MapNormalSlot))));
     char* stage = ctx->map_stage.as<char>();
     DVO_HIP_TRY(ctx, hipMemcpyAsync(stage, records, n_records * sizeof(MapSlot), hipMemcpyHostToDevice, ctx->stream));
     s.slots = reinterpret_cast<const MapSlot*>(stage);
     if (colour_or_null) {
       DVO_HIP_TRY(ctx, hipMemcpyAsync(stage + n_records * sizeof(MapSlot), colour_or_null, n_records * sizeof(MapColourSlot), hipMemcpyHostToDevice, ctx->stream));
       s.colour = reinterpret_cast<const MapColourSlot*>(stage + n_records * sizeof(MapSlot));
+    }
+    if (normals_or_null) {
+      char* at = stage + n_records * (sizeof(MapSlot) + sizeof(MapColourSlot));
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(at, normals_or_null, n_records * sizeof(MapNormalSlot), hipMemcpyHostToDevice, ctx->stream));
+      s.normals = reinterpret_cast<const MapNormalSlot*>(at);
     }
   }
   s.count = n_records;
@@ -663,16 +715,33 @@ int dvo_hip_map_merge_records(dvo_hip_context* ctx, dvo_hip_map* dst, size_t n_r
   return run_map_merge(ctx, dst, std::vector<MergeSource>(1, s), pose_or_null != nullptr, who);
 }
 
-int dvo_hip_frames_world_points(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float min_depth,
-                                float max_depth, float* const* out, int out_on_device) {
-  DVO_ENTER(ctx);
-  int rc = check_map_frames(ctx, n_frames, frames, poses, level, min_depth, max_depth, "frames_world_points");
+}  // namespace
+
+int dvo_hip_map_merge_records(dvo_hip_context* ctx, dvo_hip_map* dst, size_t n_records, const void* records, const void* colour_or_null, int on_device,
+                              float leaf_src, int sign, const double* pose_or_null) {
+  DVO_LOCK(ctx);
+  return map_merge_records(ctx, dst, n_records, records, colour_or_null, nullptr, on_device, leaf_src, sign, pose_or_null, "map_merge_records");
+}
+
+int dvo_hip_map_merge_records_ex(dvo_hip_context* ctx, dvo_hip_map* dst, size_t n_records, const void* records, const void* colour_or_null,
+                                 const void* normals_or_null, int on_device, float leaf_src, int sign, const double* pose_or_null) {
+  DVO_LOCK(ctx);
+  return map_merge_records(ctx, dst, n_records, records, colour_or_null, normals_or_null, on_device, leaf_src, sign, pose_or_null, "map_merge_records_ex");
+}
+
+namespace {
+
+// dvo_hip_frames_world_points and -- normals: k_frame_normals in place of k_world_points -- dvo_hip_frames_normals: one 16-byte record per
+// pixel of every frame's level
+int frames_organised(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float min_depth,
+                     float max_depth, float* const* out, int out_on_device, bool normals, const char* who) {
+  int rc = check_map_frames(ctx, n_frames, frames, poses, level, min_depth, max_depth, who);
   if (rc != DVO_HIP_OK) return rc;
-  if (!out) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_world_points: bad argument");
+  if (!out) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
   size_t pixels = 0;
   for (int i = 0; i < n_frames; ++i) {
-    if (!out[i]) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_world_points: null output");
-    if (out_on_device && reinterpret_cast<uintptr_t>(out[i]) % 16 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_world_points: a device output must be 16-byte aligned");
+    if (!out[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null output");
+    if (out_on_device && reinterpret_cast<uintptr_t>(out[i]) % 16 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device output must be 16-byte aligned");
     pixels += size_t(frames[i]->lv[level].w) * frames[i]->lv[level].h;
   }
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -689,13 +758,22 @@ int dvo_hip_frames_world_points(dvo_hip_context* ctx, int n_frames, dvo_hip_fram
   int blocks = 0;
   rc = upload_map_frames(ctx, n_frames, frames, poses, level, out_on_device ? out : staged.data(), &blocks);
   if (rc != DVO_HIP_OK) return rc;
-  launch_world_points(ctx->stream, ctx->map_tbl.as<MapFrame>(), n_frames, blocks, min_depth, max_depth);
+  if (normals) launch_frame_normals(ctx->stream, ctx->map_tbl.as<MapFrame>(), n_frames, blocks, min_depth, max_depth);
+  else launch_world_points(ctx->stream, ctx->map_tbl.as<MapFrame>(), n_frames, blocks, min_depth, max_depth);
   DVO_HIP_TRY(ctx, hipGetLastError());
   if (!out_on_device)
     for (int i = 0; i < n_frames; ++i)
       DVO_HIP_TRY(ctx, hipMemcpyAsync(out[i], staged[size_t(i)], size_t(frames[i]->lv[level].w) * frames[i]->lv[level].h * 16, hipMemcpyDeviceToHost, ctx->stream));
   DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return DVO_HIP_OK;
+}
+
+}  // namespace
+
+int dvo_hip_frames_world_points(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float min_depth,
+                                float max_depth, float* const* out, int out_on_device) {
+  DVO_ENTER(ctx);
+  return frames_organised(ctx, n_frames, frames, poses, level, min_depth, max_depth, out, out_on_device, false, "frames_world_points");
 }
 
 // ---- views of the map (map_render.h; kernels: map_render.hip) ----
@@ -776,13 +854,16 @@ dvo_hip_render_params dvo_hip_render_params_default(void) {
 
 namespace {
 
-// dvo_hip_map_render (first_out: float intensity planes) and -- colour -- dvo_hip_map_render_colour (first_out: uint32 rgba planes)
+// dvo_hip_map_render (first_out: float intensity planes), -- colour -- dvo_hip_map_render_colour (first_out: uint32 rgba planes) and
+// -- normals -- dvo_hip_map_render_normals (first_out: planes of 16-byte records)
 int map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float* K, const double* poses,
-               const dvo_hip_render_params* params, bool colour, void* const* first_out, float* const* depth_out, int out_on_device, const char* who) {
+               const dvo_hip_render_params* params, bool colour, void* const* first_out, float* const* depth_out, int out_on_device, const char* who,
+               bool normals = false) {
   RenderArgs args;
   int rc = check_render(ctx, map, n_views, width, height, K, poses, params, &args, who);
   if (rc != DVO_HIP_OK) return rc;
   if (colour && !map->coloured) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no colour (dvo_hip_map_create_ex, DVO_HIP_MAP_COLOUR)");
+  if (normals && !map->with_normals) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no normals (dvo_hip_map_create_ex, DVO_HIP_MAP_NORMALS)");
   if (!first_out || !depth_out) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
   for (int i = 0; i < n_views; ++i) {
     if (!first_out[i] || !depth_out[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null output");
@@ -790,23 +871,37 @@ int map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, i
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device plane must be 16-byte aligned");
   }
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t pixels = size_t(width) * size_t(height), plane = (pixels * 4 + 15) & ~size_t(15);
-  // (RenderPlanes::I holds the address of the uint32 rgba plane of a colour view: k_render_resolve stores the bits as they are)
+  const size_t pixels = size_t(width) * size_t(height), plane = (pixels * 4 + 15) & ~size_t(15), first_bytes = pixels * (normals ? 16 : 4);
+  // (RenderPlanes::I holds the address of the uint32 rgba plane of a colour view: k_render_resolve stores the bits as they are; of a
+  // normals view the address of the plane of records)
   std::vector<float*> si, sz;
   for (int i = 0; i < n_views && out_on_device; ++i) {
     si.push_back(static_cast<float*>(first_out[i]));
     sz.push_back(depth_out[i]);
   }
-  if (!out_on_device) rc = reserve_plane_pairs(ctx, ctx->map_stage, plane, n_views, &si, &sz);
+  if (!out_on_device && normals) {
+    // a view's records, then its depth plane: 5 planes of `plane` bytes per view, every record plane 16-byte aligned
+    DVO_HIP_TRY(ctx, ctx->map_stage.reserve(plane * 5 * size_t(n_views)));
+    for (int i = 0; i < n_views; ++i) {
+      si.push_back(reinterpret_cast<float*>(ctx->map_stage.as<char>() + plane * (5 * size_t(i))));
+      sz.push_back(reinterpret_cast<float*>(ctx->map_stage.as<char>() + plane * (5 * size_t(i) + 4)));
+    }
+  } else if (!out_on_device) {
+    rc = reserve_plane_pairs(ctx, ctx->map_stage, plane, n_views, &si, &sz);
+  }
   if (rc == DVO_HIP_OK) rc = upload_views(ctx, n_views, width, height, K, poses, si.data(), sz.data());
   if (rc != DVO_HIP_OK) return rc;
-  launch_map_render(ctx->stream, map_table(map), render_views(ctx), render_outs(ctx, n_views), n_views, (long long)pixels, args,
-                    ctx->render_zbuf.as<unsigned long long>(), colour);
+  if (normals)
+    launch_map_render_normals(ctx->stream, map_table(map), render_views(ctx), render_outs(ctx, n_views), n_views, (long long)pixels, args,
+                              ctx->render_zbuf.as<unsigned long long>());
+  else
+    launch_map_render(ctx->stream, map_table(map), render_views(ctx), render_outs(ctx, n_views), n_views, (long long)pixels, args,
+                      ctx->render_zbuf.as<unsigned long long>(), colour);
   DVO_HIP_TRY(ctx, hipGetLastError());
   ctx->map_renders += n_views;
   if (!out_on_device) {
     for (int i = 0; i < n_views; ++i) {
-      DVO_HIP_TRY(ctx, hipMemcpyAsync(first_out[i], si[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
+      DVO_HIP_TRY(ctx, hipMemcpyAsync(first_out[i], si[size_t(i)], first_bytes, hipMemcpyDeviceToHost, ctx->stream));
       DVO_HIP_TRY(ctx, hipMemcpyAsync(depth_out[i], sz[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
     }
     DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

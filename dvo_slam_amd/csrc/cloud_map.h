@@ -53,7 +53,8 @@
 //
 // Merge (dvo_hip_map_merge, dvo_hip_map_move_submaps, dvo_hip_map_export, dvo_hip_map_merge_records; map_merge.hip: k_map_merge, k_map_export).
 // A RECORD is 32 bytes with the layout of MapSlot, {key, n, sx, sy, sz, si, pad}; of a coloured map also the 16 bytes of MapColourSlot
-// (cloud_colour.h) at the same index.  A record with key == kMapEmptyKey or n == 0 is not live and is skipped (map_slot_live): a raw dump
+// (cloud_colour.h) at the same index, of a map with normals the 16 bytes of MapNormalSlot (cloud_normal.h, which also says how a posed
+// merge turns them).  A record with key == kMapEmptyKey or n == 0 is not live and is skipped (map_slot_live): a raw dump
 // of a table is a valid record array, and so is what an export compacts out of one.
 // Plain merge, sign +1.  Source and destination have the same leaf (as bits).  The record's key is probed in the destination exactly as an
 // insertion probes (map_hash, linear, kMapMaxProbes, an empty slot is claimed), and the WHOLE WORDS are added: map_word(n, sx),

@@ -31,6 +31,13 @@
 // claiming and counting are untouched, and the instantiations without COLOUR are the kernels of a grey map as they were.  k_map_clear
 // zeroes the side table with the slots, k_map_rehash's winning lane copies the old index's 16 bytes to the new one, k_map_extract writes
 // the colour record at the xyzi record's index where it is given an array for it.
+// A map WITH NORMALS (cloud_normal.h; MapTable::normals, a second side table of 16 bytes per slot) runs the NORMALS instantiation of
+// k_map_insert: a valid lane whose pixel is not on the border loads the four neighbouring depths (frame_normal, map_device.h: the left
+// and right ones lie in the wavefront's own cache lines, the rows above and below were or will be read by other wavefronts), forms the
+// world normal and quantises it to 10 bits a component; the run folding carries two more packed words (qx | qy << 16 and qz | 1 << 16:
+// 64 * 1022 = 65408 < 2^16, no carry between the halves) and the leader issues two more return-less 64-bit adds on normals[at] ({snx,
+// sny} and {snz, nn}), negated for a minus frame -- none where no point of the run has a normal.  COLOUR and NORMALS combine.  The
+// instantiations without NORMALS are the kernels as they were; k_map_clear, k_map_rehash and k_map_extract treat the table like colour's.
 #include "global_ptr.h"
 #include "launch.h"
 #include "cloud_map.h"
@@ -63,7 +70,8 @@ __global__ __launch_bounds__(256) void k_world_points(const MapFrame* __restrict
 
 // MIXED: the frames carry signs (a remove or a move); without it every frame is inserted and MapFrame::sign is not read
 // COLOUR: the map has a side table of colour sums (m.colour) and every frame a plane of packed pixels (MapFrame::colour)
-template <bool COMBINE, bool MIXED, bool COLOUR>
+// NORMALS: the map has a side table of normal sums (m.normals); a valid lane forms its pixel's normal from the four neighbouring depths
+template <bool COMBINE, bool MIXED, bool COLOUR, bool NORMALS>
 __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__ tbl, int n_frames, MapTable m, float min_depth, float max_depth) {
 #pragma clang fp contract(off)
   const MapFrame& f = tbl[map_frame_of(tbl, n_frames, int(blockIdx.x))];
@@ -74,6 +82,7 @@ __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__
   bool unusable = false, out_of_range = false, valid = false;
   unsigned long long key = 0;
   uint32_t q[4] = {0, 0, 0, 0}, rgb = 0;
+  uint32_t na = 0, nb = 0;                                   // NORMALS: {qnx | qny << 16}, {qnz | 1 << 16} of a lane whose pixel has a normal
   if (active) {
     const GlobalF32x2 iz = *(Global<const GlobalF32x2>)global_ptr(f.iz + size_t(i) * f.stride);
     const float K[4] = {f.K[0], f.K[1], f.K[2], f.K[3]};
@@ -86,6 +95,13 @@ __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__
     if constexpr (COLOUR) {
       // (valid: 0 <= u < w, 0 <= v < h of the level, so the block lies inside the level-0 plane, cloud_colour.h)
       if (valid) rgb = colour_level(f.colour, f.colour_pitch, i % f.w, i / f.w, f.shift);
+    }
+    if constexpr (NORMALS) {
+      float N[3];
+      if (frame_normal(f, K, i, i % f.w, i / f.w, iz.y, valid, N)) {
+        na = normal_quantise(N[0]) | normal_quantise(N[1]) << 16;
+        nb = normal_quantise(N[2]) | 1u << 16;
+      }
     }
   }
   const unsigned long long validmask = __ballot(valid);
@@ -119,6 +135,11 @@ __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__
         const uint32_t uw = __shfl_down(cw, d), uv = __shfl_down(cb, d);
         if (same_run) { cw += uw; cb += uv; }
       }
+      if constexpr (NORMALS) {
+        // (64 * 1022 = 65408 < 2^16: no carry between the halves)
+        const uint32_t ux = __shfl_down(na, d), uy = __shfl_down(nb, d);
+        if (same_run) { na += ux; nb += uy; }
+      }
     }
   }
   const uint32_t n = b >> 16, sx = a & 0xffffu, sy = a >> 16, sz = b & 0xffffu, si = c;
@@ -147,6 +168,14 @@ __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__
         (void)__hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(tint), minus ? map_negate(w3) : w3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         (void)__hip_atomic_fetch_add(&tint->sb, minus ? 0u - cb : cb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
+      if constexpr (NORMALS) {
+        if (nb != 0u) {                                        // (a run none of whose points has a normal adds nothing)
+          unsigned long long* facing = reinterpret_cast<unsigned long long*>(m.normals + at);   // (the side table has the slots' capacity)
+          const unsigned long long w4 = normal_word(na & 0xffffu, na >> 16), w5 = normal_word(nb & 0xffffu, nb >> 16);
+          (void)__hip_atomic_fetch_add(facing, minus ? map_negate(w4) : w4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          (void)__hip_atomic_fetch_add(facing + 1, minus ? map_negate(w5) : w5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
       placed = true;
       break;
     }
@@ -160,7 +189,7 @@ __global__ __launch_bounds__(256) void k_map_insert(const MapFrame* __restrict__
 // xyzi == null: count only (live slots into the cursor, voxels over the limit, vacant slots).  rgba (a coloured map, or null): the
 // voxel's colour record at the index of its xyzi record
 __global__ __launch_bounds__(256) void k_map_extract(MapTable m, unsigned long long max_points, float4* __restrict__ xyzi, uint32_t* __restrict__ counts,
-                                                     unsigned long long* __restrict__ keys, uint32_t* __restrict__ rgba) {
+                                                     unsigned long long* __restrict__ keys, uint32_t* __restrict__ rgba, float4* __restrict__ normals) {
 #pragma clang fp contract(off)
   const int lane = int(threadIdx.x) & 63;
   const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
@@ -188,6 +217,12 @@ __global__ __launch_bounds__(256) void k_map_extract(MapTable m, unsigned long l
       if (rgba) {
         const GlobalU32x4 t = *(Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(m.colour + at));   // sr sg sb pad
         rgba[idx] = colour_extract(n, t.x, t.y, t.z);
+      }
+      if (normals) {
+        const GlobalU32x4 t = *(Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(m.normals + at));   // snx sny snz nn
+        float nrec[4];
+        normal_extract(t.x, t.y, t.z, t.w, nrec);
+        gstore((Global<float4>)global_ptr(normals) + idx, make_float4(nrec[0], nrec[1], nrec[2], nrec[3]));
       }
     }
   }
@@ -219,6 +254,9 @@ __global__ __launch_bounds__(256) void k_map_rehash(MapTable from, MapTable to) 
         if (from.colour)                                       // (a coloured map: both tables have a side table)
           *(Global<GlobalU32x4>)global_ptr(reinterpret_cast<GlobalU32x4*>(to.colour + at)) =
               *(Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(from.colour + src));
+        if (from.normals)                                      // (a map with normals: both tables have that side table)
+          *(Global<GlobalU32x4>)global_ptr(reinterpret_cast<GlobalU32x4*>(to.normals + at)) =
+              *(Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(from.normals + src));
         placed = true;
         break;
       }
@@ -236,6 +274,7 @@ __global__ __launch_bounds__(256) void k_map_clear(MapTable m) {
     words[0] = lo;
     words[1] = hi;
     if (m.colour) *(Global<GlobalU32x4>)global_ptr(reinterpret_cast<GlobalU32x4*>(m.colour + at)) = hi;
+    if (m.normals) *(Global<GlobalU32x4>)global_ptr(reinterpret_cast<GlobalU32x4*>(m.normals + at)) = hi;
   }
   if (blockIdx.x == 0 && threadIdx.x < kMapCounters) m.counters[threadIdx.x] = 0ull;
 }
@@ -249,12 +288,20 @@ void launch_world_points(hipStream_t s, const MapFrame* tbl, int n_frames, int t
 void launch_map_insert(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, const MapTable& m, float min_depth, float max_depth, bool mixed) {
   const dim3 grid(total_blocks), block(256);
   constexpr bool kCombine = DVO_MAP_COMBINE_RUNS != 0;
-  if (mixed) {
-    if (m.colour) k_map_insert<kCombine, true, true><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
-    else k_map_insert<kCombine, true, false><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+  if (m.normals) {
+    if (mixed) {
+      if (m.colour) k_map_insert<kCombine, true, true, true><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+      else k_map_insert<kCombine, true, false, true><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+    } else {
+      if (m.colour) k_map_insert<kCombine, false, true, true><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+      else k_map_insert<kCombine, false, false, true><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+    }
+  } else if (mixed) {
+    if (m.colour) k_map_insert<kCombine, true, true, false><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+    else k_map_insert<kCombine, true, false, false><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
   } else {
-    if (m.colour) k_map_insert<kCombine, false, true><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
-    else k_map_insert<kCombine, false, false><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+    if (m.colour) k_map_insert<kCombine, false, true, false><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
+    else k_map_insert<kCombine, false, false, false><<<grid, block, 0, s>>>(tbl, n_frames, m, min_depth, max_depth);
   }
 }
 
@@ -266,11 +313,11 @@ void launch_map_rehash(hipStream_t s, const MapTable& from, const MapTable& to) 
 bool map_insert_combines_runs() { return DVO_MAP_COMBINE_RUNS != 0; }
 
 hipError_t launch_map_extract(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys,
-                              uint32_t* rgba) {
+                              uint32_t* rgba, float4* normals) {
   static_assert(kMapCntCursor == kMapCntOverLimit + 1 && kMapCntVacant == kMapCntOverLimit + 2, "what a pass counts lies together");
   const hipError_t e = hipMemsetAsync(m.counters + kMapCntOverLimit, 0, 3 * sizeof(unsigned long long), s);
   if (e != hipSuccess) return e;
-  k_map_extract<<<dim3(stride_grid(m.capacity)), dim3(256), 0, s>>>(m, max_points, xyzi, counts, keys, m.colour ? rgba : nullptr);
+  k_map_extract<<<dim3(stride_grid(m.capacity)), dim3(256), 0, s>>>(m, max_points, xyzi, counts, keys, m.colour ? rgba : nullptr, m.normals ? normals : nullptr);
   return hipSuccess;
 }
 

@@ -8,6 +8,7 @@
 #include "depth_rig.h"
 #include "cloud_map.h"
 #include "cloud_colour.h"
+#include "cloud_normal.h"
 #include "map_render.h"
 
 #include "../../include/dvo_hip.h"
@@ -226,6 +227,7 @@ struct MapTable {
   unsigned long long capacity;         // a power of two
   float leaf;
   MapColourSlot* colour;               // the side table of a coloured map (cloud_colour.h), same index as slots; null for a grey map
+  MapNormalSlot* normals;              // the side table of a map with normals (cloud_normal.h), same index as slots; null without them
 };
 // one source of a k_map_merge launch (map_merge.hip; include/dvo_hip.h, dvo_hip_map_merge / _move_submaps / _merge_records; cloud_map.h,
 // Merge): a table, or a record array, that goes into (+1) or out of (-1) the launch's destination.  Sources of different sizes share a
@@ -242,6 +244,7 @@ struct MapMergeEntry {
   float leaf_src;                      // ... and the leaf the source's records were binned with
   int sign;
   int first_block;
+  const MapNormalSlot* normals;        // destination with normals: the normal records at the same indices (cloud_normal.h); else null, not read
 };
 // one plane of a k_colour_pack launch (cloud_colour.hip; include/dvo_hip.h, dvo_hip_frames_set_colour): the caller's 8-bit colour plane ->
 // the frame's plane of packed pixels, w * h dwords, tight.  Planes of different sizes share a launch like MapFrame's.

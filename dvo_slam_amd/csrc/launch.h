@@ -108,16 +108,21 @@ void launch_map_insert(hipStream_t s, const MapFrame* tbl, int n_frames, int tot
 void launch_map_rehash(hipStream_t s, const MapTable& from, const MapTable& to);
 bool map_insert_combines_runs();
 hipError_t launch_map_extract(hipStream_t s, const MapTable& m, unsigned long long max_points, float4* xyzi, uint32_t* counts, unsigned long long* keys,
-                              uint32_t* rgba);
+                              uint32_t* rgba, float4* normals = nullptr);
 void launch_map_clear(hipStream_t s, const MapTable& m);
+// A map WITH NORMALS (m.normals is its side table; cloud_normal.h) takes the same launches too: k_map_insert forms every valid pixel's
+// normal and carries its sums along, clear and rehash handle the side table, `normals` (16-byte records) is written for such a map only.
+// cloud_normal.hip, launch_frame_normals: every frame's organised plane of world normals {N.x, N.y, N.z, has} into MapFrame::out.
+void launch_frame_normals(hipStream_t s, const MapFrame* tbl, int n_frames, int total_blocks, float min_depth, float max_depth);
 
 // map_merge.hip: voxel tables and record arrays into and out of a map (cloud_map.h, Merge).  tbl: n_entries entries and one more whose
 // first_block is total_blocks, the launch's grid.  launch_map_merge: every live record of every entry into (sign +1) or out of (-1) the
 // table m, which has a side table iff the entries carry colour records; posed: under each entry's pose, binned anew with m.leaf.
 // launch_map_export: the live slots of m as raw records (and colour records at the same indices, where m has a side table and colour is
-// given), at most max_records; records null: count only.  Zeroes and then sets kMapCntCursor (live slots seen).
+// given; likewise normal records where m has normals and `normals` is given), at most max_records; records null: count only.  Zeroes and then sets kMapCntCursor (live slots seen).
 void launch_map_merge(hipStream_t s, const MapMergeEntry* tbl, int n_entries, int total_blocks, const MapTable& m, bool posed);
-hipError_t launch_map_export(hipStream_t s, const MapTable& m, unsigned long long max_records, MapSlot* records, MapColourSlot* colour);
+hipError_t launch_map_export(hipStream_t s, const MapTable& m, unsigned long long max_records, MapSlot* records, MapColourSlot* colour,
+                             MapNormalSlot* normals = nullptr);
 
 // cloud_colour.hip: the colour planes of frames (cloud_colour.h).  launch_colour_pack: n_planes 8-bit colour planes of one pixel format
 // into planes of packed pixels (tbl: n_planes entries and one more whose first_block is total_blocks).  launch_colour_level: the
@@ -135,6 +140,10 @@ void launch_render_splat(hipStream_t s, const MapTable& m, const MapView* views,
 void launch_render_resolve(hipStream_t s, const unsigned long long* zbuf, const RenderPlanes* out, int n_views, long long pixels, bool colour);
 void launch_map_render(hipStream_t s, const MapTable& m, const MapView* views, const RenderPlanes* out, int n_views, long long pixels, const RenderArgs& a,
                        unsigned long long* zbuf, bool colour);
+// a normals view of a map with normals (cloud_normal.h): the element's low half is the voxel's quantised world normal, out[view].I holds
+// the address of the plane of 16-byte records {n.x, n.y, n.z, has} in the view's camera coordinates.  The same three launches.
+void launch_map_render_normals(hipStream_t s, const MapTable& m, const MapView* views, const RenderPlanes* out, int n_views, long long pixels,
+                               const RenderArgs& a, unsigned long long* zbuf);
 bool map_render_preloads();
 
 // pose_graph.hip: the stages of the pose-graph optimiser (pose_graph.h), kPgBlock edges or vertices per workgroup.  *_partials: one

@@ -9,7 +9,8 @@
 // instantiation: one whose record has a key under the entry's pose (map_pose_record) -- probes the destination like an insertion: a
 // relaxed load of the slot's key, a 64-bit atomicCAS where it reads empty and the entry's sign is +1 (sign -1 only looks up: an empty
 // slot ends it, the record is unmatched), then the record's words as return-less relaxed adds ({n, sx} and {sy, sz} as 64-bit words,
-// si as a 32-bit one; COLOUR: {sr, sg} and sb on the side table, the colour record loaded by live lanes only), negated for sign -1.
+// si as a 32-bit one; COLOUR: {sr, sg} and sb on the side table, the colour record loaded by live lanes only; NORMALS: {snx, sny} and
+// {snz, nn} on the normal side table, the sums turned by the entry's pose in the POSED instantiation, cloud_normal.h), negated for sign -1.
 // The probe loop is a `for` over kMapMaxProbes.  No LDS, no barriers, no spinning, no floating-point atomics.  There is no run folding:
 // neighbouring slots of a hashed table do not share keys, and equal keys in a caller's record array are summed by the atomics.
 // Counters: slot updates and claims are lane counts (one add per wavefront: wave_count); the usable points and the points being
@@ -38,7 +39,8 @@ __device__ __forceinline__ void wave_add(unsigned long long* counter, unsigned l
   if (lane == 0 && v != 0) counter_add(counter, v);
 }
 
-template <bool POSED, bool COLOUR>
+// NORMALS: the destination has a side table of normal sums (m.normals) and every entry normal records (MapMergeEntry::normals)
+template <bool POSED, bool COLOUR, bool NORMALS>
 __global__ __launch_bounds__(256) void k_map_merge(const MapMergeEntry* __restrict__ tbl, int n_entries, MapTable m) {
 #pragma clang fp contract(off)
   const MapMergeEntry& e = tbl[map_frame_of(tbl, n_entries, int(blockIdx.x))];
@@ -48,6 +50,7 @@ __global__ __launch_bounds__(256) void k_map_merge(const MapMergeEntry* __restri
   bool valid = false, unusable = false, out_of_range = false;
   unsigned long long key = 0;
   uint32_t add[5] = {0, 0, 0, 0, 0}, tint[3] = {0, 0, 0}, n_src = 0;
+  uint32_t facing[4] = {0, 0, 0, 0};                         // NORMALS: snx sny snz nn as they are added
   if (i < e.count) {                                         // (inside the source's records)
     const auto words = (Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(e.slots + i));
     const GlobalU32x4 lo = words[0], hi = words[1];         // key | n sx, sy sz si pad
@@ -70,6 +73,15 @@ __global__ __launch_bounds__(256) void k_map_merge(const MapMergeEntry* __restri
         if (valid) {
           const GlobalU32x4 t = *(Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(e.colour + i));   // sr sg sb pad
           tint[0] = t.x; tint[1] = t.y; tint[2] = t.z;
+        }
+      }
+      if constexpr (NORMALS) {
+        if (valid) {
+          const GlobalU32x4 t = *(Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(e.normals + i));   // snx sny snz nn
+          facing[0] = t.x; facing[1] = t.y; facing[2] = t.z; facing[3] = t.w;
+          if constexpr (POSED) {
+            if (t.w != 0u) normal_pose_sums(e.pose, t.x, t.y, t.z, t.w, facing);   // (the summed normal turns with the sub-map; nn stays)
+          }
         }
       }
     }
@@ -108,6 +120,14 @@ __global__ __launch_bounds__(256) void k_map_merge(const MapMergeEntry* __restri
         (void)__hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(to), minus ? map_negate(w3) : w3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         (void)__hip_atomic_fetch_add(&to->sb, minus ? 0u - tint[2] : tint[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
+      if constexpr (NORMALS) {
+        if (facing[3] != 0u) {                                 // (a record none of whose points had a normal adds nothing)
+          unsigned long long* to = reinterpret_cast<unsigned long long*>(m.normals + at);   // (the side table has the slots' capacity)
+          const unsigned long long w4 = normal_word(facing[0], facing[1]), w5 = normal_word(facing[2], facing[3]);
+          (void)__hip_atomic_fetch_add(to, minus ? map_negate(w4) : w4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          (void)__hip_atomic_fetch_add(to + 1, minus ? map_negate(w5) : w5, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      }
       placed = true;
       break;
     }
@@ -117,10 +137,10 @@ __global__ __launch_bounds__(256) void k_map_merge(const MapMergeEntry* __restri
   wave_count(m.counters + kMapCntOccupied, __ballot(claimed), lane);
 }
 
-// records == null: count only (live slots into the cursor).  colour (a coloured map, or null): the slot's colour record at the index of
-// its record
+// records == null: count only (live slots into the cursor).  colour (a coloured map, or null) and normals (a map with normals, or null):
+// the slot's colour record resp. normal record at the index of its record
 __global__ __launch_bounds__(256) void k_map_export(MapTable m, unsigned long long max_records, MapSlot* __restrict__ records,
-                                                    MapColourSlot* __restrict__ colour) {
+                                                    MapColourSlot* __restrict__ colour, MapNormalSlot* __restrict__ normals) {
   const int lane = int(threadIdx.x) & 63;
   const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
   // (capacity and the stride are multiples of 64: the lanes of a wavefront leave the loop together)
@@ -145,6 +165,9 @@ __global__ __launch_bounds__(256) void k_map_export(MapTable m, unsigned long lo
         const GlobalU32x4 rec = {t.x, t.y, t.z, 0u};
         *(Global<GlobalU32x4>)global_ptr(reinterpret_cast<GlobalU32x4*>(colour + idx)) = rec;
       }
+      if (normals)
+        *(Global<GlobalU32x4>)global_ptr(reinterpret_cast<GlobalU32x4*>(normals + idx)) =
+            *(Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(m.normals + at));   // snx sny snz nn
     }
   }
 }
@@ -153,19 +176,28 @@ __global__ __launch_bounds__(256) void k_map_export(MapTable m, unsigned long lo
 
 void launch_map_merge(hipStream_t s, const MapMergeEntry* tbl, int n_entries, int total_blocks, const MapTable& m, bool posed) {
   const dim3 grid(total_blocks), block(256);
-  if (posed) {
-    if (m.colour) k_map_merge<true, true><<<grid, block, 0, s>>>(tbl, n_entries, m);
-    else k_map_merge<true, false><<<grid, block, 0, s>>>(tbl, n_entries, m);
+  if (m.normals) {
+    if (posed) {
+      if (m.colour) k_map_merge<true, true, true><<<grid, block, 0, s>>>(tbl, n_entries, m);
+      else k_map_merge<true, false, true><<<grid, block, 0, s>>>(tbl, n_entries, m);
+    } else {
+      if (m.colour) k_map_merge<false, true, true><<<grid, block, 0, s>>>(tbl, n_entries, m);
+      else k_map_merge<false, false, true><<<grid, block, 0, s>>>(tbl, n_entries, m);
+    }
+  } else if (posed) {
+    if (m.colour) k_map_merge<true, true, false><<<grid, block, 0, s>>>(tbl, n_entries, m);
+    else k_map_merge<true, false, false><<<grid, block, 0, s>>>(tbl, n_entries, m);
   } else {
-    if (m.colour) k_map_merge<false, true><<<grid, block, 0, s>>>(tbl, n_entries, m);
-    else k_map_merge<false, false><<<grid, block, 0, s>>>(tbl, n_entries, m);
+    if (m.colour) k_map_merge<false, true, false><<<grid, block, 0, s>>>(tbl, n_entries, m);
+    else k_map_merge<false, false, false><<<grid, block, 0, s>>>(tbl, n_entries, m);
   }
 }
 
-hipError_t launch_map_export(hipStream_t s, const MapTable& m, unsigned long long max_records, MapSlot* records, MapColourSlot* colour) {
+hipError_t launch_map_export(hipStream_t s, const MapTable& m, unsigned long long max_records, MapSlot* records, MapColourSlot* colour,
+                             MapNormalSlot* normals) {
   const hipError_t e = hipMemsetAsync(m.counters + kMapCntCursor, 0, sizeof(unsigned long long), s);
   if (e != hipSuccess) return e;
-  k_map_export<<<dim3(stride_grid(m.capacity)), dim3(256), 0, s>>>(m, max_records, records, m.colour ? colour : nullptr);
+  k_map_export<<<dim3(stride_grid(m.capacity)), dim3(256), 0, s>>>(m, max_records, records, m.colour ? colour : nullptr, m.normals ? normals : nullptr);
   return hipSuccess;
 }
 

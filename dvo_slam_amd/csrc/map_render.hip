@@ -17,9 +17,13 @@
 // A colour view (cloud_colour.h; dvo_hip_map_render_colour) runs the COLOUR instantiations: the splat reads 16 more bytes per live voxel
 // (the side table's sums) and puts the voxel's colour where the intensity's bits were -- the depth half of the element, the footprint and
 // the atomic are the grey view's -- and the resolve stores the colour word in place of I.
+// A normals view (cloud_normal.h; dvo_hip_map_render_normals) runs the NORMALS instantiation of the splat: 16 more bytes per live voxel
+// (the normal side table's sums), the voxel's quantised world normal where the intensity's bits were; k_render_resolve_normals rotates
+// it into the view and stores one 16-byte record per pixel beside Z.
 #include "global_ptr.h"
 #include "launch.h"
 #include "map_render.h"
+#include "cloud_normal.h"
 
 #ifndef DVO_RENDER_PRELOAD
 #define DVO_RENDER_PRELOAD 0
@@ -41,7 +45,7 @@ __global__ __launch_bounds__(256) void k_render_fill(unsigned long long* __restr
   if ((elements & 1) && blockIdx.x == 0 && threadIdx.x == 0) zbuf[elements - 1] = kRenderEmpty;
 }
 
-template <bool PRELOAD, bool COLOUR>
+template <bool PRELOAD, bool COLOUR, bool NORMALS = false>
 __global__ __launch_bounds__(256) void k_map_render(MapTable m, const MapView* __restrict__ views, int n_views, RenderArgs a,
                                                     unsigned long long* __restrict__ zbuf) {
 #pragma clang fp contract(off)
@@ -62,6 +66,10 @@ __global__ __launch_bounds__(256) void k_map_render(MapTable m, const MapView* _
       if constexpr (COLOUR) {
         const GlobalU32x4 t = *(Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(m.colour + at));   // sr sg sb pad
         f.value = colour_render_value(f.value, colour_extract(ns.x, t.x, t.y, t.z));   // (drawn: n >= min_points >= 1)
+      }
+      if constexpr (NORMALS) {
+        const GlobalU32x4 t = *(Global<const GlobalU32x4>)global_ptr(reinterpret_cast<const GlobalU32x4*>(m.normals + at));   // snx sny snz nn
+        f.value = normal_render_value(f.value, t.x, t.y, t.z, t.w);
       }
       // f lies inside the image (map_render_axis clips): 0 <= u0 <= u1 <= w - 1, 0 <= v0 <= v1 <= h - 1
       const int nu = f.u1 - f.u0 + 1, nv = f.v1 - f.v0 + 1;
@@ -105,6 +113,28 @@ __global__ __launch_bounds__(256) void k_render_resolve(const unsigned long long
   }
 }
 
+// the normals view's resolve: 8 B read, one 16-byte record {n.x, n.y, n.z, has} (the view's camera coordinates) and 4 B of Z stored per pixel
+__global__ __launch_bounds__(256) void k_render_resolve_normals(const unsigned long long* __restrict__ zbuf, const MapView* __restrict__ views,
+                                                                const RenderPlanes* __restrict__ out, int n_views, long long pixels) {
+#pragma clang fp contract(off)
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (int view = int(blockIdx.y); view < n_views; view += int(gridDim.y)) {   // (view < n_views: inside the tables)
+    const MapView& v = views[view];
+    const auto E = (Global<const GlobalU32x2>)global_ptr(reinterpret_cast<const GlobalU32x2*>(zbuf + (size_t)view * (size_t)pixels));
+    const auto Nout = (Global<GlobalF32x4>)global_ptr(reinterpret_cast<GlobalF32x4*>(out[view].I));
+    const auto Zout = (Global<float>)global_ptr(out[view].Z);
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < pixels; p += stride) {   // (p < pixels: inside the view's planes)
+      const GlobalU32x2 e = E[p];
+      float n[4];
+      uint32_t z;
+      normal_render_resolve((unsigned long long)e.x | (unsigned long long)e.y << 32, v, n, &z);
+      const GlobalF32x4 rec = {n[0], n[1], n[2], n[3]};
+      Nout[p] = rec;
+      Zout[p] = __uint_as_float(z);
+    }
+  }
+}
+
 // x: grid-stride over the items of one view, y: the views (at most 1024 rows; the kernels walk the rest)
 dim3 view_grid(long long items, int n_views) {
   long long blocks = (items + 255) / 256;
@@ -137,6 +167,13 @@ void launch_map_render(hipStream_t s, const MapTable& m, const MapView* views, c
   launch_render_fill(s, zbuf, pixels * n_views);
   launch_render_splat(s, m, views, n_views, a, zbuf, colour);
   launch_render_resolve(s, zbuf, out, n_views, pixels, colour);
+}
+
+void launch_map_render_normals(hipStream_t s, const MapTable& m, const MapView* views, const RenderPlanes* out, int n_views, long long pixels,
+                               const RenderArgs& a, unsigned long long* zbuf) {
+  launch_render_fill(s, zbuf, pixels * n_views);
+  k_map_render<DVO_RENDER_PRELOAD != 0, false, true><<<view_grid((long long)m.capacity, n_views), dim3(256), 0, s>>>(m, views, n_views, a, zbuf);
+  k_render_resolve_normals<<<view_grid(pixels, n_views), dim3(256), 0, s>>>(zbuf, views, out, n_views, pixels);
 }
 
 bool map_render_preloads() { return DVO_RENDER_PRELOAD != 0; }

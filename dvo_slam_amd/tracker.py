@@ -754,7 +754,7 @@ _VIEW_POSES = dict(per="view", some=True)                                       
 _MERGE_POSES = dict(per="source", counted="sources", maps="source -> destination", finite=True)      # KeyframeMap.merge, move_submaps, absorb
 
 
-_MAP_RECORD, _MAP_COLOUR_RECORD = np.dtype(_lib.MAP_RECORD), np.dtype(_lib.MAP_COLOUR_RECORD)
+_MAP_RECORD, _MAP_COLOUR_RECORD, _MAP_NORMAL_RECORD = np.dtype(_lib.MAP_RECORD), np.dtype(_lib.MAP_COLOUR_RECORD), np.dtype(_lib.MAP_NORMAL_RECORD)
 _TORCH_DTYPES = {}                                           # numpy dtype -> torch dtype of the same bits, filled at the first device array
 
 
@@ -799,7 +799,12 @@ def world_points_batch(pyramids, poses, level=0, min_depth=0.0, max_depth=float(
     """The organised world clouds of n keyframes (dvo_hip_frames_world_points; the reference's AsyncPointCloudBuilder::BuildJob::build):
     per pyramid an [h, w, 4] float32 array {P.x, P.y, P.z, I} of level `level` under its 4 x 4 pose (camera -> world); unusable pixels
     have NaN in x, y, z.  device=True: torch tensors on the GPU instead of numpy arrays."""
-    n, T = _map_frames_args(pyramids, poses, level, min_depth, max_depth, "world_points_batch")
+    return _organised_batch("world_points", pyramids, poses, level, min_depth, max_depth, device)
+
+
+def _organised_batch(name, pyramids, poses, level, min_depth, max_depth, device):
+    """world_points_batch() and normals_batch(): dvo_hip_frames_<name> into one [h, w, 4] float32 array per pyramid"""
+    n, T = _map_frames_args(pyramids, poses, level, min_depth, max_depth, name + "_batch")
     ctx = pyramids[0].ctx
     shapes = []
     for p in pyramids:
@@ -807,10 +812,19 @@ def world_points_batch(pyramids, poses, level=0, min_depth=0.0, max_depth=float(
         ctx.check(ctx._lib.dvo_hip_frame_info(p.ptr, level, C.byref(w), C.byref(h), None))
         shapes.append((h.value, w.value, 4))
     out = [_out_array(ctx, s, np.float32, device) for s in shapes]
-    ctx.check(ctx._lib.dvo_hip_frames_world_points(ctx.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)), int(level),
-                                                   float(min_depth), float(max_depth), device_pointer_array([_address(a) for a in out]),
-                                                   1 if device else 0))
+    ctx.check(getattr(ctx._lib, "dvo_hip_frames_" + name)(ctx.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)), int(level),
+                                                          float(min_depth), float(max_depth), device_pointer_array([_address(a) for a in out]),
+                                                          1 if device else 0))
     return out
+
+
+def normals_batch(pyramids, poses, level=0, min_depth=0.0, max_depth=float("inf"), device=False):
+    """The organised planes of world normals of n keyframes (dvo_hip_frames_normals; dvo_slam_amd/csrc/cloud_normal.h): per pyramid an
+    [h, w, 4] float32 array {N.x, N.y, N.z, has} of level `level` under its 4 x 4 pose (camera -> world) -- the side of the surface that
+    faces the camera, from the level's own depth plane; has is 1 where the pixel has a normal, else 0 and N is 0 (the border, unusable
+    pixels, a neighbour without depth, a surface seen at a grazing angle or across a depth step).  Exactly what an insertion into
+    KeyframeMap(normals=True) sees.  device=True: torch tensors on the GPU instead of numpy arrays."""
+    return _organised_batch("normals", pyramids, poses, level, min_depth, max_depth, device)
 
 
 def _rehash_capacity(capacity):
@@ -899,11 +913,14 @@ class KeyframeMap:
     does not depend on the order of insertion.  capacity: slots of the table, rounded up to a power of two; keep it at least four
     times the number of voxels (stats())."""
 
-    def __init__(self, ctx=None, leaf=0.01, capacity=1 << 22, colour=False):
+    def __init__(self, ctx=None, leaf=0.01, capacity=1 << 22, colour=False, normals=False):
         """colour=True (dvo_hip_map_create_ex, DVO_HIP_MAP_COLOUR): the map fuses the colour its pyramids carry
-        (RgbdImagePyramid.set_colour) per voxel; every pyramid it is given must then carry colour."""
+        (RgbdImagePyramid.set_colour) per voxel; every pyramid it is given must then carry colour.  normals=True (DVO_HIP_MAP_NORMALS):
+        the map fuses the surface normal of every point that has one (normals_batch) per voxel; its export() returns a third array."""
         if not isinstance(colour, (bool, np.bool_)):
             raise TypeError("KeyframeMap: colour must be a bool")
+        if not isinstance(normals, (bool, np.bool_)):
+            raise TypeError("KeyframeMap: normals must be a bool")
         leaf = float(leaf)
         if not (leaf > 0.0 and leaf < float("inf")):
             raise ValueError("KeyframeMap: the leaf size must be finite and > 0")
@@ -912,9 +929,11 @@ class KeyframeMap:
         self.ctx = ctx or default_context()
         self.leaf = leaf
         self.coloured = bool(colour)
+        self.with_normals = bool(normals)
         self.ptr = C.c_void_p()
-        if self.coloured:
-            self.ctx.check(self.ctx._lib.dvo_hip_map_create_ex(self.ctx.ptr, leaf, int(capacity), _lib.MAP_COLOUR, C.byref(self.ptr)))
+        if self.coloured or self.with_normals:
+            flags = (_lib.MAP_COLOUR if self.coloured else 0) | (_lib.MAP_NORMALS if self.with_normals else 0)
+            self.ctx.check(self.ctx._lib.dvo_hip_map_create_ex(self.ctx.ptr, leaf, int(capacity), flags, C.byref(self.ptr)))
         else:
             self.ctx.check(self.ctx._lib.dvo_hip_map_create(self.ctx.ptr, leaf, int(capacity), C.byref(self.ptr)))
 
@@ -966,42 +985,53 @@ class KeyframeMap:
         self.ctx.check(self.ctx._lib.dvo_hip_map_stats(self.ctx.ptr, self.ptr, C.byref(s)))
         return {name: int(getattr(s, name)) for name, _ in _lib.MapStats._fields_ if name != "reserved"}
 
-    def extract(self, sort=False, device=False, max_points=None, colour=False):
+    def extract(self, sort=False, device=False, max_points=None, colour=False, normals=False):
         """(xyzi [n, 4] float32, counts [n] uint32, keys [n] uint64): one record per occupied voxel, in no particular order unless
         sort=True (by key, on the host).  device=True: torch tensors on the GPU (counts as int32, keys as int64: the same bits).
-        colour=True (a coloured map only): a fourth array rgba [n] uint32, 0xFFRRGGBB per voxel (device=True: int32, the same bits)."""
+        colour=True (a coloured map only): a fourth array rgba [n] uint32, 0xFFRRGGBB per voxel (device=True: int32, the same bits).
+        normals=True (a map with normals only): one more array, last, [n, 4] float32: the voxel's unit normal in world coordinates and
+        the agreement of the fused normals in [0, 1]; zeros for a voxel none of whose points had a normal."""
         if colour and not getattr(self, "coloured", False):
             raise ValueError("KeyframeMap.extract: the map holds no colour (KeyframeMap(colour=True))")
+        if normals and not getattr(self, "with_normals", False):
+            raise ValueError("KeyframeMap.extract: the map holds no normals (KeyframeMap(normals=True))")
         if sort and device:
             raise ValueError("KeyframeMap.extract: sort=True orders on the host; extract to the host, or sort the device tensors by key")
         cap = self.stats()["occupied"] if max_points is None else int(max_points)
         got = C.c_size_t(0)
         m = max(cap, 1)
         xyzi, counts, keys = (_out_array(self.ctx, shape, dt, device) for shape, dt in (((m, 4), np.float32), (m, np.uint32), (m, np.uint64)))
-        if colour:
-            rgba = _out_array(self.ctx, m, np.uint32, device)
+        rgba = _out_array(self.ctx, m, np.uint32, device) if colour else None
+        if normals:
+            nrm = _out_array(self.ctx, (m, 4), np.float32, device)
+            self.ctx.check(self.ctx._lib.dvo_hip_map_extract_normals(self.ctx.ptr, self.ptr, cap, _address(xyzi), _address(nrm),
+                                                                     _address(rgba) if colour else None, _address(counts), _address(keys),
+                                                                     1 if device else 0, C.byref(got)))
+        elif colour:
             self.ctx.check(self.ctx._lib.dvo_hip_map_extract_colour(self.ctx.ptr, self.ptr, cap, _address(xyzi), _address(rgba), _address(counts),
                                                                     _address(keys), 1 if device else 0, C.byref(got)))
         else:
             self.ctx.check(self.ctx._lib.dvo_hip_map_extract(self.ctx.ptr, self.ptr, cap, _address(xyzi), _address(counts), _address(keys),
                                                              1 if device else 0, C.byref(got)))
         xyzi, counts, keys = xyzi[:got.value], counts[:got.value], keys[:got.value]
-        if colour:
-            rgba = rgba[:got.value]
+        extra = ([rgba[:got.value]] if colour else []) + ([nrm[:got.value]] if normals else [])
         if sort:
             order = np.argsort(keys, kind="stable")
             xyzi, counts, keys = xyzi[order], counts[order], keys[order]
-            if colour:
-                rgba = rgba[order]
-        return (xyzi, counts, keys, rgba) if colour else (xyzi, counts, keys)
+            extra = [a[order] for a in extra]
+        return (xyzi, counts, keys, *extra)
 
     # ---- sub-maps (dvo_hip_map_merge, _move_submaps, _export, _merge_records; dvo_slam_amd/csrc/cloud_map.h, Merge) ----
 
     def info(self):
-        """dict: leaf (the float32 the map bins with), colour, capacity (dvo_hip_map_info)"""
+        """dict: leaf (the float32 the map bins with), colour, capacity (dvo_hip_map_info); of a map with normals also normals=True (a
+        map without them reports the three keys it always reported)"""
         leaf, flags, capacity = C.c_float(), C.c_uint(), C.c_uint64()
         self.ctx.check(self.ctx._lib.dvo_hip_map_info(self.ctx.ptr, self.ptr, C.byref(leaf), C.byref(flags), C.byref(capacity)))
-        return dict(leaf=float(leaf.value), colour=bool(flags.value & _lib.MAP_COLOUR), capacity=int(capacity.value))
+        out = dict(leaf=float(leaf.value), colour=bool(flags.value & _lib.MAP_COLOUR), capacity=int(capacity.value))
+        if flags.value & _lib.MAP_NORMALS:
+            out["normals"] = True
+        return out
 
     def _merge_sources(self, sources, poses, who):
         """(list of source maps, their poses as [n, 4, 4] float64 or None), or ValueError / TypeError: nothing reaches the library with a
@@ -1020,6 +1050,8 @@ class KeyframeMap:
                 raise ValueError("%s: a source map belongs to another context (export() there, absorb() here)" % who)
             if bool(getattr(s, "coloured", False)) != bool(getattr(self, "coloured", False)):
                 raise ValueError("%s: a coloured and a grey map do not merge" % who)
+            if bool(getattr(s, "with_normals", False)) != bool(getattr(self, "with_normals", False)):
+                raise ValueError("%s: a map with normals and one without do not merge" % who)
             if poses is None and np.float32(s.leaf) != np.float32(self.leaf):
                 raise ValueError("%s: a plain merge needs the destination's leaf size (a posed merge bins anew)" % who)
         T = None if poses is None else _pose_array(poses, len(sources), who, **_MERGE_POSES)
@@ -1075,24 +1107,43 @@ class KeyframeMap:
     def export(self, device=False):
         """(records, colour_records or None): the live voxels as raw records in no particular order (dvo_hip_map_export) -- structured
         numpy arrays with the fields key, n, sx, sy, sz, si, pad and (a coloured map) sr, sg, sb, pad.  device=True: torch int32 tensors
-        of shape [n, 8] and [n, 4] on the GPU, the same bytes.  With info() they are the whole map: absorb() takes them back."""
-        coloured = bool(getattr(self, "coloured", False))
+        of shape [n, 8] and [n, 4] on the GPU, the same bytes.  With info() they are the whole map: absorb() takes them back.
+        A map with normals (dvo_hip_map_export_ex) returns THREE arrays: (records, colour_records or None, normal_records) -- the
+        third with the fields snx, sny, snz, nn ([n, 4] on the GPU)."""
+        coloured, with_normals = bool(getattr(self, "coloured", False)), bool(getattr(self, "with_normals", False))
         got = C.c_size_t(0)
         self.ctx.check(self.ctx._lib.dvo_hip_map_export(self.ctx.ptr, self.ptr, 0, None, None, 0, C.byref(got)))
         n = got.value
         records = _out_array(self.ctx, max(n, 1), _MAP_RECORD, device)
         colour = _out_array(self.ctx, max(n, 1), _MAP_COLOUR_RECORD, device) if coloured else None
+        if not with_normals:
+            if n > 0:
+                self.ctx.check(self.ctx._lib.dvo_hip_map_export(self.ctx.ptr, self.ptr, n, _address(records), _address(colour) if coloured else None,
+                                                                1 if device else 0, C.byref(got)))
+            return records[:got.value], (colour[:got.value] if coloured else None)
+        normals = _out_array(self.ctx, max(n, 1), _MAP_NORMAL_RECORD, device)
         if n > 0:
-            self.ctx.check(self.ctx._lib.dvo_hip_map_export(self.ctx.ptr, self.ptr, n, _address(records), _address(colour) if coloured else None,
-                                                            1 if device else 0, C.byref(got)))
-        return records[:got.value], (colour[:got.value] if coloured else None)
+            self.ctx.check(self.ctx._lib.dvo_hip_map_export_ex(self.ctx.ptr, self.ptr, n, _address(records), _address(colour) if coloured else None,
+                                                               _address(normals), 1 if device else 0, C.byref(got)))
+        return records[:got.value], (colour[:got.value] if coloured else None), normals[:got.value]
 
-    def absorb(self, records, colour=None, leaf=None, sign=1, pose=None):
+    def absorb(self, records, colour=None, leaf=None, sign=1, pose=None, normals=None):
         """Raw voxel records -- what export() returned, here or in another context, or a table's raw dump -- into (sign +1) or out of
         (-1) the map (dvo_hip_map_merge_records).  leaf: the leaf size the records were binned with (None: this map's).  pose None:
-        a plain merge, same leaf; a 4 x 4 pose (records' coordinates -> this map's): a posed one.  Equal keys are summed."""
+        a plain merge, same leaf; a 4 x 4 pose (records' coordinates -> this map's): a posed one.  Equal keys are summed.
+        normals: the normal records of export(), which a map with normals needs (dvo_hip_map_merge_records_ex) and no other takes."""
         who = "KeyframeMap.absorb"
         ptr, n, on_device = _record_array(records, _lib.MAP_RECORD, 8, who, "records")
+        with_normals = bool(getattr(self, "with_normals", False))
+        if with_normals and normals is None:
+            raise ValueError("%s: a map with normals takes records with normal records" % who)
+        if not with_normals and normals is not None:
+            raise ValueError("%s: a map without normals takes no normal records" % who)
+        nptr = None
+        if normals is not None:
+            nptr, nn, n_on_device = _record_array(normals, _lib.MAP_NORMAL_RECORD, 4, who, "normals")
+            if nn != n or n_on_device != on_device:
+                raise ValueError("%s: %d records but %d normal records (both on the host, or both on the device)" % (who, n, nn))
         coloured = bool(getattr(self, "coloured", False))
         if coloured and colour is None:
             raise ValueError("%s: a coloured map takes records with colour records" % who)
@@ -1117,16 +1168,21 @@ class KeyframeMap:
         T = None if pose is None else _pose_array(pose, 1, who, **_MERGE_POSES)
         if n == 0:
             return
-        self.ctx.check(self.ctx._lib.dvo_hip_map_merge_records(self.ctx.ptr, self.ptr, n, ptr, cptr, 1 if on_device else 0, leaf, int(sign),
-                                                               None if T is None else T.ctypes.data_as(C.POINTER(C.c_double))))
+        Tp = None if T is None else T.ctypes.data_as(C.POINTER(C.c_double))
+        if with_normals:
+            self.ctx.check(self.ctx._lib.dvo_hip_map_merge_records_ex(self.ctx.ptr, self.ptr, n, ptr, cptr, nptr, 1 if on_device else 0, leaf, int(sign), Tp))
+        else:
+            self.ctx.check(self.ctx._lib.dvo_hip_map_merge_records(self.ctx.ptr, self.ptr, n, ptr, cptr, 1 if on_device else 0, leaf, int(sign), Tp))
 
     def save(self, path):
         """The map into a file (numpy.savez: leaf, flags, capacity and the exported records); KeyframeMap.load reads it back."""
         info = self.info()
-        records, colour = self.export()
+        records, colour, *normals = self.export()
+        flags = (_lib.MAP_COLOUR if info["colour"] else 0) | (_lib.MAP_NORMALS if info.get("normals") else 0)
+        extra = dict(normals=normals[0]) if normals else {}        # (a map without normals writes the file it always wrote)
         with open(path, "wb") as f:
-            np.savez(f, leaf=np.float32(info["leaf"]), flags=np.uint32(_lib.MAP_COLOUR if info["colour"] else 0), capacity=np.uint64(info["capacity"]),
-                     records=records, colour=colour if colour is not None else np.zeros(0, np.dtype(_lib.MAP_COLOUR_RECORD)))
+            np.savez(f, leaf=np.float32(info["leaf"]), flags=np.uint32(flags), capacity=np.uint64(info["capacity"]),
+                     records=records, colour=colour if colour is not None else np.zeros(0, np.dtype(_lib.MAP_COLOUR_RECORD)), **extra)
 
     @classmethod
     def load(cls, path, ctx=None, capacity=None):
@@ -1134,9 +1190,10 @@ class KeyframeMap:
         with np.load(path) as z:
             leaf, flags, saved_capacity = float(z["leaf"]), int(z["flags"]), int(z["capacity"])
             records, colour = z["records"], z["colour"]
+            normals = z["normals"] if flags & _lib.MAP_NORMALS else None
         coloured = bool(flags & _lib.MAP_COLOUR)
-        m = cls(ctx=ctx, leaf=leaf, capacity=saved_capacity if capacity is None else capacity, colour=coloured)
-        m.absorb(records, colour if coloured else None)
+        m = cls(ctx=ctx, leaf=leaf, capacity=saved_capacity if capacity is None else capacity, colour=coloured, normals=normals is not None)
+        m.absorb(records, colour if coloured else None, normals=normals)
         return m
 
     def _render(self, name, first, K, width, height, poses, device, params):
@@ -1169,6 +1226,30 @@ class KeyframeMap:
         if not getattr(self, "coloured", False):
             raise ValueError("KeyframeMap.render_colour: the map holds no colour (KeyframeMap(colour=True))")
         return self._render("render_colour", np.uint32, K, width, height, poses, device, params)
+
+    def render_normals(self, K, width, height, poses, device=False, **params):
+        """Normals views of a map with normals (dvo_hip_map_render_normals): like render(), but returns (normals, Z): float32 records
+        {n.x, n.y, n.z, has} of shape (n, height, width, 4) -- the nearest voxel's normal in the VIEW'S CAMERA coordinates (x right, y
+        down, z forward; a surface facing the camera has n.z < 0) and 1, or zeros where nothing was seen or the voxel has no normal --
+        and the depth planes, bit for bit render()'s.  The normals are dequantised from 10 bits per component and not renormalised:
+        their length is within 2e-3 of 1.  device=True: torch tensors on the GPU."""
+        who = "KeyframeMap.render_normals"
+        if not getattr(self, "with_normals", False):
+            raise ValueError("%s: the map holds no normals (KeyframeMap(normals=True))" % who)
+        K, width, height, T = _render_view_args(K, width, height, poses, who)
+        rp = render_params_struct(**params)
+        n = T.shape[0]
+        nrm = _out_array(self.ctx, (n, height, width, 4), np.float32, device)
+        if device:
+            pad = (width * height + 3) // 4 * 4             # (every view's plane 16-byte aligned)
+            Z = _out_array(self.ctx, n * pad, np.float32, True).as_strided((n, height, width), (pad, width, 1))
+        else:
+            Z = _out_array(self.ctx, (n, height, width), np.float32, False)
+        ptrs = [device_pointer_array([_address(a[k]) for k in range(n)]) for a in (nrm, Z)]
+        self.ctx.check(self.ctx._lib.dvo_hip_map_render_normals(self.ctx.ptr, self.ptr, n, width, height, K.ctypes.data_as(C.POINTER(C.c_float)),
+                                                                T.ctypes.data_as(C.POINTER(C.c_double)), C.byref(rp), ptrs[0], ptrs[1],
+                                                                1 if device else 0))
+        return nrm, Z
 
     def render_into(self, pyramids, poses, role=None, config=None, flags=0, **params):
         """Views of the map straight into existing pyramids of one camera (dvo_hip_map_render_frames): pyramid i becomes the frame that the

@@ -184,10 +184,14 @@ struct IntensityPointCloud {
   // PointXYZRGB::rgba per point, 0xFFRRGGBB -- filled only by a coloured source (PointCloudAggregator::setColour, a BuildJob over a
   // pyramid that carries colour), else EMPTY
   std::vector<uint32_t> rgba;
+  // PointXYZRGBNormal's normal per point and, in place of PCL's curvature, the AGREEMENT of the voxel's fused normals (about 1 on a flat
+  // patch, low on a crease; all four 0: the voxel has no normal) -- filled only by PointCloudAggregator::setNormals, else EMPTY
+  std::vector<float> normal_x, normal_y, normal_z, agreement;
   size_t width, height;
   IntensityPointCloud() : width(0), height(1) {}
   size_t size() const { return x.size(); }
   bool hasColour() const { return !x.empty() && rgba.size() == x.size(); }
+  bool hasNormals() const { return !x.empty() && normal_x.size() == x.size(); }
   void resize(size_t n) { x.resize(n); y.resize(n); z.resize(n); intensity.resize(n); }
   // (PCL's default point: the origin)
   void push_back_default() { x.push_back(0.0f); y.push_back(0.0f); z.push_back(0.0f); intensity.push_back(0.0f); width = x.size(); height = 1; }

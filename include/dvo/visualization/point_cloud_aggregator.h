@@ -19,6 +19,10 @@
 // of every registered pyramid that hasRgb() and does not carry colour yet (RgbdImagePyramid::setColourFromRgb), creates the device map
 // with DVO_HIP_MAP_COLOUR and fills the cloud's rgba (0xFFRRGGBB per voxel, include/dvo_hip.h, dvo_hip_map_extract_colour).  If some
 // registered pyramid has neither colour nor rgb, the build falls back to the grey map and says so (DeviceContext::warn); rgba stays empty.
+// setNormals(true) makes the map one WITH NORMALS (include/dvo_hip.h, DVO_HIP_MAP_NORMALS; combines with setColour): the device map fuses
+// the surface normal of every point that has one, the cloud gains normal_x / normal_y / normal_z and the agreement of the fused normals
+// per voxel (dvo_hip_map_extract_normals), and renderNormals() gives the map as a view of normals.  In the sub-map calls below such
+// a map merges with its like, and its records have a third array (VoxelNormalRecord; dvo_hip_map_export_ex, dvo_hip_map_merge_records_ex).
 // merge() / subtract() / moveSubmaps() / exportRecords() / absorbRecords() work on the device maps themselves (include/dvo_hip.h,
 // dvo_hip_map_merge ...): an aggregator built in the coordinates of an anchor keyframe is a SUB-MAP that enters another aggregator's map
 // under the anchor's pose and follows a pose-graph optimisation without its keyframes' pyramids (see "sub-maps" below).
@@ -40,7 +44,7 @@ class PointCloudAggregator {
   typedef AsyncPointCloudBuilder::PointCloud PointCloud;
 
   // capacity_slots: the device table (32 bytes per slot); keep it at least four times the voxels of the map
-  explicit PointCloudAggregator(size_t capacity_slots = size_t(1) << 22) : capacity_(capacity_slots), ctx_(0), map_(0), incremental_(false), colour_(false), map_coloured_(false) {}
+  explicit PointCloudAggregator(size_t capacity_slots = size_t(1) << 22) : capacity_(capacity_slots), ctx_(0), map_(0), incremental_(false), colour_(false), map_coloured_(false), normals_(false), map_normals_(false) {}
   ~PointCloudAggregator() {
     if (map_) dvo_hip_map_destroy(ctx_, map_);
   }
@@ -62,6 +66,9 @@ class PointCloudAggregator {
   // off (the default): a grey map.  on: build() fuses the pyramids' colour (see above)
   void setColour(bool on) { colour_ = on; }
   bool colour() const { return colour_; }
+  // off (the default): no normals.  on: build() fuses the points' surface normals (see above)
+  void setNormals(bool on) { normals_ = on; }
+  bool normals() const { return normals_; }
 
   PointCloud::Ptr build() {
     PointCloud::Ptr cloud(new PointCloud);
@@ -70,7 +77,7 @@ class PointCloudAggregator {
       return cloud;
     }
     const bool coloured = colour_ && attachColour();
-    if (map_ && coloured != map_coloured_) {   // (a map is grey or coloured for life: the other kind is made anew)
+    if (map_ && (coloured != map_coloured_ || normals_ != map_normals_)) {   // (a map is of one kind for life: another kind is made anew)
       dvo_hip_map_destroy(ctx_, map_);
       map_ = 0;
       held_.clear();
@@ -99,8 +106,10 @@ class PointCloudAggregator {
     ctx_ = ctx;
     using dvo::core::dvo_hip_check;
     if (!map_) {
-      if (!dvo_hip_check(ctx_, dvo_hip_map_create_ex(ctx_, 0.01f, capacity_, coloured ? DVO_HIP_MAP_COLOUR : 0u, &map_), "dvo_hip_map_create_ex")) return cloud;
+      const unsigned flags = (coloured ? DVO_HIP_MAP_COLOUR : 0u) | (normals_ ? DVO_HIP_MAP_NORMALS : 0u);
+      if (!dvo_hip_check(ctx_, dvo_hip_map_create_ex(ctx_, 0.01f, capacity_, flags, &map_), "dvo_hip_map_create_ex")) return cloud;
       map_coloured_ = coloured;
+      map_normals_ = normals_;
     }
     if (!dvo_hip_check(ctx_, dvo_hip_map_clear(ctx_, map_), "dvo_hip_map_clear")) return cloud;
     if (!dvo_hip_check(ctx_, dvo_hip_map_insert(ctx_, map_, int(frames.size()), frames.data(), poses.data(), 0, 0.0f, INFINITY), "dvo_hip_map_insert"))
@@ -140,6 +149,25 @@ class PointCloudAggregator {
     return true;
   }
 
+  // A view of the normals of the map build() made last (setNormals(true)) from `pose` (camera -> world) through level 0 of `camera`:
+  // normals = width * height records {n.x, n.y, n.z, has} in the VIEW'S CAMERA coordinates (zeros where nothing was seen or the voxel has
+  // no normal), depth = the view's depth plane, bit for bit render()'s (NaN where nothing was seen).  false before the first build(), for
+  // a map without normals, and on an error.
+  bool renderNormals(dvo::core::RgbdCameraPyramid& camera, const dvo::compat::Affine3d& pose, std::vector<float>& normals, std::vector<float>& depth,
+                     const dvo_hip_render_params& params = dvo_hip_render_params_default()) {
+    if (!map_ || !map_normals_) return false;
+    const dvo::core::RgbdCamera& c0 = camera.level(0);
+    const int w = int(c0.width()), h = int(c0.height());
+    const float K[4] = {c0.intrinsics().fx(), c0.intrinsics().fy(), c0.intrinsics().ox(), c0.intrinsics().oy()};
+    double T[16];
+    dvo::compat::affine_to_rowmajor(pose, T);
+    normals.assign(size_t(w) * size_t(h) * 4, 0.0f);
+    depth.assign(size_t(w) * size_t(h), 0.0f);
+    float* n[1] = {normals.data()};
+    float* z[1] = {depth.data()};
+    return dvo::core::dvo_hip_check(ctx_, dvo_hip_map_render_normals(ctx_, map_, 1, w, h, K, T, &params, n, z, 0), "dvo_hip_map_render_normals");
+  }
+
   // ---- sub-maps (include/dvo_hip.h, dvo_hip_map_merge / _move_submaps / _export / _merge_records) ----
   // An aggregator whose keyframes were added under poses RELATIVE to an anchor keyframe (T_anchor^-1 * T_i) and built is a sub-map; the
   // calls below put the device maps of such aggregators into this one's, take them out again and re-pose them, from the voxel tables
@@ -152,6 +180,10 @@ class PointCloudAggregator {
   };
   struct VoxelColourRecord {  // 16 bytes: the slot's colour sums (a coloured map)
     uint32_t sr, sg, sb, pad;
+  };
+
+  struct VoxelNormalRecord {  // 16 bytes: the slot's normal sums (a map with normals)
+    uint32_t snx, sny, snz, nn;
   };
 
   // plain: the sum is, bit for bit, the map built from the keyframes of both
@@ -193,6 +225,29 @@ class PointCloudAggregator {
     if (pose) dvo::compat::affine_to_rowmajor(*pose, T);
     return dvo_hip_map_merge_records(ctx_, map_, records.size(), records.data(), map_coloured_ ? colour.data() : 0, 0, leaf, sign, pose ? T : 0) == DVO_HIP_OK;
   }
+  // ... with the normal records of a map with normals (filled for such a map, else emptied) ...
+  bool exportRecords(std::vector<VoxelRecord>& records, std::vector<VoxelColourRecord>& colour, std::vector<VoxelNormalRecord>& normals, float* leaf = 0) const {
+    if (!map_) return false;
+    size_t n = 0, got = 0;
+    if (dvo_hip_map_export_ex(ctx_, map_, 0, 0, 0, 0, 0, &n) != DVO_HIP_OK) return false;
+    if (leaf && dvo_hip_map_info(ctx_, map_, leaf, 0, 0) != DVO_HIP_OK) return false;
+    records.resize(n);
+    colour.resize(map_coloured_ ? n : size_t(0));
+    normals.resize(map_normals_ ? n : size_t(0));
+    if (n == 0) return true;
+    return dvo_hip_map_export_ex(ctx_, map_, n, records.data(), map_coloured_ ? colour.data() : 0, map_normals_ ? normals.data() : 0, 0, &got) == DVO_HIP_OK &&
+           got == n;
+  }
+  // ... and back: a map with normals takes records WITH normal records, one without takes none
+  bool absorbRecords(const std::vector<VoxelRecord>& records, const std::vector<VoxelColourRecord>& colour, const std::vector<VoxelNormalRecord>& normals,
+                     float leaf = 0.01f, int sign = 1, const dvo::compat::Affine3d* pose = 0) {
+    if (!map_ || (map_coloured_ && colour.size() != records.size()) || (!map_coloured_ && !colour.empty())) return false;
+    if ((map_normals_ && normals.size() != records.size()) || (!map_normals_ && !normals.empty())) return false;
+    double T[16];
+    if (pose) dvo::compat::affine_to_rowmajor(*pose, T);
+    return dvo_hip_map_merge_records_ex(ctx_, map_, records.size(), records.data(), map_coloured_ ? colour.data() : 0, map_normals_ ? normals.data() : 0, 0,
+                                        leaf, sign, pose ? T : 0) == DVO_HIP_OK;
+  }
   // the map as it stands -- after merges -- one point per voxel, sorted by voxel key (build() without rebuilding)
   PointCloud::Ptr cloud() {
     PointCloud::Ptr out(new PointCloud);
@@ -208,15 +263,18 @@ class PointCloudAggregator {
     dvo::core::RgbdImagePyramidPtr pyramid;
     dvo::compat::Affine3d pose;
   };
-  static_assert(sizeof(VoxelRecord) == 32 && sizeof(VoxelColourRecord) == 16, "the records of include/dvo_hip.h, dvo_hip_map_export");
+  static_assert(sizeof(VoxelRecord) == 32 && sizeof(VoxelColourRecord) == 16 && sizeof(VoxelNormalRecord) == 16,
+                "the records of include/dvo_hip.h, dvo_hip_map_export_ex");
 
   bool mergeOne(const PointCloudAggregator& other, int sign, const dvo::compat::Affine3d* pose) {
     if (!other.map_) return false;
     using dvo::core::dvo_hip_check;
     if (!map_) {                               // an aggregator that only collects sub-maps: an empty map like the first one
       ctx_ = other.ctx_;
-      if (!dvo_hip_check(ctx_, dvo_hip_map_create_ex(ctx_, 0.01f, capacity_, other.map_coloured_ ? DVO_HIP_MAP_COLOUR : 0u, &map_), "dvo_hip_map_create_ex")) return false;
+      const unsigned flags = (other.map_coloured_ ? DVO_HIP_MAP_COLOUR : 0u) | (other.map_normals_ ? DVO_HIP_MAP_NORMALS : 0u);
+      if (!dvo_hip_check(ctx_, dvo_hip_map_create_ex(ctx_, 0.01f, capacity_, flags, &map_), "dvo_hip_map_create_ex")) return false;
       map_coloured_ = other.map_coloured_;
+      map_normals_ = other.map_normals_;
     }
     double T[16];
     if (pose) dvo::compat::affine_to_rowmajor(*pose, T);
@@ -249,8 +307,13 @@ class PointCloudAggregator {
     std::vector<float> xyzi(4 * std::max(n, size_t(1)));
     std::vector<uint64_t> keys(std::max(n, size_t(1)));
     std::vector<uint32_t> rgba(map_coloured_ ? std::max(n, size_t(1)) : size_t(0));
+    std::vector<float> normals(map_normals_ ? 4 * std::max(n, size_t(1)) : size_t(0));
     size_t got = 0;
-    if (map_coloured_) {
+    if (map_normals_) {
+      if (!dvo_hip_check(ctx_, dvo_hip_map_extract_normals(ctx_, map_, n, xyzi.data(), normals.data(), map_coloured_ ? rgba.data() : 0, 0, keys.data(), 0, &got),
+                         "dvo_hip_map_extract_normals"))
+        return cloud;
+    } else if (map_coloured_) {
       if (!dvo_hip_check(ctx_, dvo_hip_map_extract_colour(ctx_, map_, n, xyzi.data(), rgba.data(), 0, keys.data(), 0, &got), "dvo_hip_map_extract_colour"))
         return cloud;
     } else if (!dvo_hip_check(ctx_, dvo_hip_map_extract(ctx_, map_, n, xyzi.data(), 0, keys.data(), 0, &got), "dvo_hip_map_extract")) {
@@ -261,6 +324,7 @@ class PointCloudAggregator {
     std::sort(order.begin(), order.end(), [&keys](size_t a, size_t b) { return keys[a] < keys[b]; });
     cloud->resize(got);
     cloud->rgba.resize(map_coloured_ ? got : size_t(0));
+    for (std::vector<float>* v : {&cloud->normal_x, &cloud->normal_y, &cloud->normal_z, &cloud->agreement}) v->resize(map_normals_ ? got : size_t(0));
     cloud->width = got;
     cloud->height = 1;
     for (size_t i = 0; i < got; ++i) {
@@ -270,6 +334,13 @@ class PointCloudAggregator {
       cloud->z[i] = p[2];
       cloud->intensity[i] = p[3];
       if (map_coloured_) cloud->rgba[i] = rgba[order[i]];
+      if (map_normals_) {
+        const float* m = &normals[4 * order[i]];
+        cloud->normal_x[i] = m[0];
+        cloud->normal_y[i] = m[1];
+        cloud->normal_z[i] = m[2];
+        cloud->agreement[i] = m[3];
+      }
     }
     return cloud;
   }
@@ -323,6 +394,8 @@ class PointCloudAggregator {
   bool incremental_;
   bool colour_;          // setColour
   bool map_coloured_;    // what map_ was created as
+  bool normals_;         // setNormals
+  bool map_normals_;     // what map_ was created as
 };
 
 }  // namespace visualization

@@ -743,7 +743,7 @@ int dvo_hip_map_render_colour(dvo_hip_context* ctx, dvo_hip_map* map, int n_view
  *               other than +1 and -1; a pose with an entry that is not finite; a minus entry into a destination that has dropped
  *               points since its last clear or rehash; n_src < 0; more than 2^32 records; device records not 16-byte aligned.
  *   cost        profiles/keyframe_map_merge.md. */
-/* leaf, flags (DVO_HIP_MAP_COLOUR or 0) and slots of a map; any of the three may be NULL */
+/* leaf, flags (DVO_HIP_MAP_COLOUR | DVO_HIP_MAP_NORMALS, or 0) and slots of a map; any of the three may be NULL */
 int dvo_hip_map_info(dvo_hip_context* ctx, dvo_hip_map* map, float* leaf, unsigned* flags, uint64_t* capacity);
 /* n_src source maps into (sign +1) or out of (-1) dst in ONE launch.  signs_or_null NULL: +1 for every source.  poses_or_null NULL: a
  * plain merge of every source; else a posed merge of source i under poses[16 * i ..].  A source may appear more than once. */
@@ -765,6 +765,71 @@ int dvo_hip_map_export(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_record
  * device memory (on_device, 16-byte aligned), binned with leaf_src.  pose_or_null NULL: plain.  Equal keys in the array are summed. */
 int dvo_hip_map_merge_records(dvo_hip_context* ctx, dvo_hip_map* dst, size_t n_records, const void* records, const void* colour_or_null,
                               int on_device, float leaf_src, int sign, const double* pose_or_null /* 16 */);
+
+/* ---- surface normals in the keyframe map: frames give them, voxels fuse them ------------------------------------------------------------
+ * The reference's map is a PointXYZRGB cloud; whoever meshes it, shades it from a new pose or feeds a point-to-plane consumer needs the
+ * PointXYZRGBNormal, and would otherwise estimate normals on the host from the organised cloud.  Here every frame yields an organised plane
+ * of normals on the device, a map created with DVO_HIP_MAP_NORMALS fuses them per voxel, and an extraction and a view return them.  A map
+ * without the flag, and every entry point above, behaves as it did.  The arithmetic is stated once in dvo_slam_amd/csrc/cloud_normal.h,
+ * whose host build the device results equal BIT FOR BIT.
+ *   pixel normal  from the level's own depth plane (what dvo_hip_frame_download_plane returns) and K: the cross product of the central
+ *                 differences of the back-projected 4-neighbourhood, in float; normalised in double; facing the camera.  A pixel has a
+ *                 normal iff it is not on the level's border, it is usable as a map point (depth range included), its four neighbours
+ *                 have a finite depth > 0, and the surface is seen at a cosine of at least 0.1 (about 84 degrees) -- which also drops a
+ *                 stencil across a depth step above roughly 4 % of the depth at level 0.  That constant is a definition with no knob.
+ *                 It is NOT PCL's k-neighbour PCA, and there is no viewpoint ambiguity to resolve.
+ *   world normal  N = R n in float under the frame's pose: no translation, no renormalisation.  dvo_hip_frames_normals returns the plane
+ *                 of records {N.x, N.y, N.z, has}, has 1.0f or 0.0f (then N = 0), exactly as an insertion sees it.
+ *   sums          a map with normals has a side table beside its slots (16 more bytes per slot): per voxel the sums of the three components
+ *                 quantised to 10 bits with a bias (q = floor(N * 511 + 0.5) + 511 in [0, 1022]) and nn, the number of its points that
+ *                 had a normal; uint32 each, 1022 * 2^20 < 2^30.  A point without a normal is inserted as ever and adds nothing there.
+ *                 Insert, remove, move, rehash and clear carry the table: integer adds, a removal subtracts exactly what was added.
+ *   extraction    in double, rounded once: m = s - 511 nn per component, the record is {m / |m|, |m| / (511 nn)} -- the unit normal and the
+ *                 AGREEMENT of the fused normals, about 1 on a flat patch, low on a crease or a thin wall seen from both sides -- or
+ *                 {0, 0, 0, 0} where nn = 0 or m = 0; at the index of the voxel's xyzi record.
+ *   views         the z-buffer element is uint64(bits(p.z)) << 32 | payload, payload = 1 << 30 | qx << 20 | qy << 10 | qz of the voxel's
+ *                 extracted world normal, 0 for a voxel without one: the nearest voxel, and of voxels at the same depth the LOWER payload.
+ *                 The depth plane equals dvo_hip_map_render's bit for bit.  A pixel's record is the dequantised normal rotated into the
+ *                 VIEW'S CAMERA coordinates and 1.0f; {0, 0, 0, 0} for a hole (Z = NaN) and for a voxel without a normal.  It is not
+ *                 renormalised: its length is within the quantisation of 1.
+ *   sub-maps      dvo_hip_map_merge and dvo_hip_map_move_submaps take maps with normals without a change of signature (source and
+ *                 destination must agree in the flag).  A RECORD of such a map has 16 more bytes {uint32 snx, sny, snz, nn} at the same
+ *                 index of a third array: dvo_hip_map_export_ex and dvo_hip_map_merge_records_ex are the two record calls with that
+ *                 array.  A plain merge adds the sums as whole words: the sum of two sub-maps is bit for bit the single build.  A posed
+ *                 merge turns a voxel's SUMMED normal: m = s - 511 nn, M = R m in double, s' = clamp(rint(M) + 511 nn, 0, 1022 nn), nn
+ *                 unchanged; deterministic, and a posed subtraction under the same pose restores the words.  The old
+ *                 dvo_hip_map_export of a map with normals writes what it always wrote, without them; the old
+ *                 dvo_hip_map_merge_records into a map with normals is REFUSED: it cannot supply them.
+ *   other calls   dvo_hip_map_extract, dvo_hip_map_render and their colour forms return of a map with normals what they return of one
+ *                 without, fed the same frames.  DVO_HIP_MAP_COLOUR and DVO_HIP_MAP_NORMALS combine.
+ *   refusals      DVO_HIP_ERR_INVALID, nothing launched, nothing changed: dvo_hip_map_extract_normals and dvo_hip_map_render_normals on a
+ *                 map without the flag; a null output; a device array that is not 16-byte aligned; rgba given for a map without colour;
+ *                 what dvo_hip_frames_world_points, dvo_hip_map_extract_colour and dvo_hip_map_render refuse.
+ *   cost          profiles/keyframe_map_normals.md. */
+/* The value is 4, not 2: flags = 2 has been an unknown flag that is refused since the flags exist, callers may rely on that, and it stays
+ * refused.  DVO_HIP_MAP_NORMALS adds the normal side table (16 more bytes per slot); dvo_hip_map_info reports the bit. */
+#define DVO_HIP_MAP_NORMALS 4u /* dvo_hip_map_create_ex: the map fuses surface normals */
+/* The twin of dvo_hip_frames_world_points: w_L x h_L records of 4 floats {N.x, N.y, N.z, has} per frame into out[i]; host arrays, or device
+ * arrays (16-byte aligned) with out_on_device.  Streams, deferred ingests and refusals as there. */
+int dvo_hip_frames_normals(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses /* n x 16 */, int level,
+                           float min_depth, float max_depth, float* const* out, int out_on_device);
+/* dvo_hip_map_extract of a map with normals with the normal records (4 floats per voxel) into normals; rgba_or_null: the colour records
+ * of a map that also has colour, NULL for one without.  Otherwise as dvo_hip_map_extract_colour. */
+int dvo_hip_map_extract_normals(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_points, float* xyzi, float* normals, uint32_t* rgba_or_null,
+                                uint32_t* counts_or_null, uint64_t* keys_or_null, int out_on_device, size_t* n_points);
+/* dvo_hip_map_render of a map with normals: width * height records of 4 floats into normals_out[i], Z into depth_out[i], tight; host
+ * arrays, or device arrays (16-byte aligned) with out_on_device.  View preparation, footprint, parameters and refusals are the grey view's. */
+int dvo_hip_map_render_normals(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float K[4],
+                               const double* poses /* n x 16 */, const dvo_hip_render_params* params, float* const* normals_out,
+                               float* const* depth_out, int out_on_device);
+/* dvo_hip_map_export with one more array: the normal records (max_records x 16 bytes, {uint32 snx, sny, snz, nn}) of a map with normals
+ * into normal_records_or_null where that is not NULL (refused for a map without normals).  Otherwise as dvo_hip_map_export. */
+int dvo_hip_map_export_ex(dvo_hip_context* ctx, dvo_hip_map* map, size_t max_records, void* records, void* colour_records_or_null,
+                          void* normal_records_or_null, int out_on_device, size_t* n_records);
+/* dvo_hip_map_merge_records with one more array: a destination with normals takes records WITH normal records, one without takes none.
+ * Otherwise as dvo_hip_map_merge_records. */
+int dvo_hip_map_merge_records_ex(dvo_hip_context* ctx, dvo_hip_map* dst, size_t n_records, const void* records, const void* colour_or_null,
+                                 const void* normals_or_null, int on_device, float leaf_src, int sign, const double* pose_or_null /* 16 */);
 
 /* ---- the hot path --------------------------------------------------------------------------- */
 /* DenseTracker::match(RgbdImagePyramid& reference, RgbdImagePyramid& current, Result&)
