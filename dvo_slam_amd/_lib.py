@@ -80,6 +80,16 @@ class RenderParams(C.Structure):
                 ("min_points", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+class WarpParams(C.Structure):
+    """dvo_hip_warp_params: how frames are warped under a pose (dvo_hip_frames_warp_inverse, dvo_hip_frames_warp_forward)."""
+    _fields_ = [("mode", C.c_int32), ("occlusion_margin", C.c_float), ("min_depth", C.c_float), ("max_depth", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
+
+
+# DVO_HIP_WARP_*: the footprint of a forward warp
+WARP_MODES = {"nearest": 0, "splat": 1}
+
+
 class GraphParams(C.Structure):
     """dvo_hip_graph_params: the schedule of a pose-graph optimisation (dvo_hip_graph_optimize)."""
     _fields_ = [("max_iterations", C.c_int32), ("cg_max_iterations", C.c_int32), ("cg_tolerance", C.c_double),
@@ -130,6 +140,7 @@ EXPORTS = [
     "dvo_hip_map_info", "dvo_hip_map_merge", "dvo_hip_map_move_submaps", "dvo_hip_map_export", "dvo_hip_map_merge_records",
     "dvo_hip_frames_normals", "dvo_hip_map_extract_normals", "dvo_hip_map_render_normals", "dvo_hip_map_export_ex",
     "dvo_hip_map_merge_records_ex",
+    "dvo_hip_warp_params_default", "dvo_hip_frames_warp_inverse", "dvo_hip_frames_warp_forward",
     "dvo_hip_graph_create", "dvo_hip_graph_destroy", "dvo_hip_graph_set_vertices", "dvo_hip_graph_set_poses", "dvo_hip_graph_set_edges",
     "dvo_hip_graph_params_default", "dvo_hip_graph_optimize", "dvo_hip_graph_get_poses", "dvo_hip_graph_edge_stats",
     "dvo_hip_graph_linearise", "dvo_hip_graph_multiply", "dvo_hip_graph_optimize_batch",
@@ -294,6 +305,12 @@ def lib():
         L.dvo_hip_map_render_normals.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, fp, dp, rp, C.POINTER(vp), C.POINTER(vp), C.c_int]
         L.dvo_hip_map_export_ex.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_int, C.POINTER(C.c_size_t)]
         L.dvo_hip_map_merge_records_ex.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.c_int, C.c_float, C.c_int, dp]
+    if hasattr(L, "dvo_hip_frames_warp_inverse"):   # (likewise: an older build warps no frames)
+        dp, wp, pp = C.POINTER(C.c_double), C.POINTER(WarpParams), C.POINTER(vp)
+        L.dvo_hip_warp_params_default.argtypes = []
+        L.dvo_hip_warp_params_default.restype = WarpParams
+        L.dvo_hip_frames_warp_inverse.argtypes = [vp, C.c_int, pp, pp, dp, C.c_int, wp, pp, pp, pp, C.c_int]
+        L.dvo_hip_frames_warp_forward.argtypes = [vp, C.c_int, pp, dp, C.c_int, wp, pp, pp, C.c_int]
     if hasattr(L, "dvo_hip_graph_create"):   # (likewise: an older build optimises no pose graph)
         dp, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         L.dvo_hip_graph_create.argtypes = [vp, C.POINTER(vp)]

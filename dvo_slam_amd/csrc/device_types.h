@@ -260,6 +260,12 @@ struct RenderPlanes {
   float* I;
   float* Z;
 };
+// the tight planes of one item of an inverse warp (k_warp_inverse, frame_warp.hip; include/dvo_hip.h, dvo_hip_frames_warp_inverse)
+struct WarpPlanes {
+  float* I;
+  float* Z;
+  float* D;                            // the difference plane; null: not wanted
+};
 // (kMapCntOverLimit .. kMapCntVacant are what a pass of k_map_extract counts: contiguous, zeroed before every pass.  kMapCntRemoving: the
 // usable points in range of the frames a launch subtracts -- its kMapCntCandidates; kMapCntUnmatched of them found no voxel to leave)
 constexpr int kMapCntCandidates = 0, kMapCntDropped = 1, kMapCntOutOfRange = 2, kMapCntUnusable = 3, kMapCntUpdates = 4, kMapCntOccupied = 5,

@@ -146,6 +146,14 @@ void launch_map_render_normals(hipStream_t s, const MapTable& m, const MapView* 
                                const RenderArgs& a, unsigned long long* zbuf);
 bool map_render_preloads();
 
+// frame_warp.hip: frames warped under a pose (frame_warp.h).  launch_warp_inverse: n items; tbl holds 2n (+ 1) entries, entry 2i the
+// raster frame with the item's transform as its pose, entry 2i + 1 the sampled frame (same w and h); the planes of item i into outs[i];
+// max_pixels: the largest w * h of the items.  launch_warp_forward: n items of `pixels` = w * h pixels each (tbl[i]: the source frame, its
+// pose the transform) into the z-buffers zbuf (pixels * n elements, filled by launch_render_fill, resolved by launch_render_resolve).
+void launch_warp_inverse(hipStream_t s, const MapFrame* tbl, const WarpPlanes* outs, int n, long long max_pixels, float margin);
+void launch_warp_forward(hipStream_t s, const MapFrame* tbl, int n, long long pixels, int mode, float min_depth, float max_depth,
+                         unsigned long long* zbuf);
+
 // pose_graph.hip: the stages of the pose-graph optimiser (pose_graph.h), kPgBlock edges or vertices per workgroup.  *_partials: one
 // double per workgroup, a subtree of the scalar's tree (rz_partials: two rows of them).  launch_pg_linearise: every edge's record at
 // `poses` (with_blocks: the weighted blocks too) and the partials of the cost.  launch_pg_gather: D and b of every vertex and each

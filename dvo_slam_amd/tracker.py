@@ -827,6 +827,101 @@ def normals_batch(pyramids, poses, level=0, min_depth=0.0, max_depth=float("inf"
     return _organised_batch("normals", pyramids, poses, level, min_depth, max_depth, device)
 
 
+_WARP_POSES = dict(per="item", counted="items", maps="source camera -> target camera", finite=True)   # warp_inverse_batch, warp_forward_batch
+
+
+def warp_params_struct(mode="splat", occlusion_margin=0.05, min_depth=0.0, max_depth=float("inf")):
+    """dvo_hip_warp_params from its fields (the defaults: dvo_hip_warp_params_default), or ValueError / TypeError: nothing reaches the
+    library with a value it would refuse."""
+    if not isinstance(mode, str):
+        raise TypeError("warp: mode is a name, one of %s" % sorted(_lib.WARP_MODES))
+    if mode not in _lib.WARP_MODES:
+        raise ValueError("warp: unknown mode %r; known: %s" % (mode, sorted(_lib.WARP_MODES)))
+    try:
+        margin, lo, hi = float(occlusion_margin), float(min_depth), float(max_depth)
+    except (TypeError, ValueError):
+        raise TypeError("warp: occlusion_margin, min_depth and max_depth must be real numbers")
+    if not margin >= 0.0:
+        raise ValueError("warp: the occlusion margin must be >= 0 (no NaN)")
+    if not lo <= hi:
+        raise ValueError("warp: need min_depth <= max_depth (no NaN)")
+    out = _lib.WarpParams()
+    out.mode, out.occlusion_margin, out.min_depth, out.max_depth = _lib.WARP_MODES[mode], margin, lo, hi
+    return out
+
+
+def _warp_args(pyramids, others, transforms, level, who):
+    """(n, transforms as a contiguous [n, 4, 4] float64 array) of a warp call, or ValueError / TypeError: nothing reaches the library with
+    no items, mismatched lengths, a transform that is not 4 x 4 or not finite, a level a pyramid does not have, pyramids of different
+    contexts or -- others: the second pyramid of every pair -- a pair whose sizes differ."""
+    n = len(pyramids)
+    if n < 1:
+        raise ValueError("%s: no pyramids" % who)
+    if others is not None and len(others) != n:
+        raise ValueError("%s: %d raster pyramids but %d sampled pyramids" % (who, n, len(others)))
+    T = _pose_array(transforms, n, who, **_WARP_POSES)
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+        raise TypeError("%s: level must be an integer" % who)
+    for p in list(pyramids) + list(others or []):
+        if not 0 <= level < p.levels:
+            raise ValueError("%s: a pyramid of %d levels has no level %d" % (who, p.levels, level))
+        if p.ctx is not pyramids[0].ctx:
+            raise ValueError("%s: the pyramids belong to different contexts" % who)
+    for p, q in zip(pyramids, others or []):
+        if (p.camera.width, p.camera.height) != (q.camera.width, q.camera.height):
+            raise ValueError("%s: the pyramids of a pair differ in size" % who)
+    return n, T
+
+
+def _warp_planes(pyramids, level, count, device):
+    """count lists of one [h, w] float32 output plane per pyramid, and their pointer arrays"""
+    ctx = pyramids[0].ctx
+    shapes = []
+    for p in pyramids:
+        w, h = C.c_int(), C.c_int()
+        ctx.check(ctx._lib.dvo_hip_frame_info(p.ptr, level, C.byref(w), C.byref(h), None))
+        shapes.append((h.value, w.value))
+    out = [[_out_array(ctx, s, np.float32, device) for s in shapes] for _ in range(count)]
+    return out, [device_pointer_array([_address(a) for a in planes]) for planes in out]
+
+
+def warp_inverse_batch(raster_pyramids, sampled_pyramids, transforms, level=0, occlusion_margin=0.05, difference=False, device=False):
+    """The sampled images seen in the raster images' pixel grids (dvo_hip_frames_warp_inverse; the reference's RgbdImage::warpIntensity
+    with Interpolation::bilinearWithDepthBuffer).  Item i: every pixel of raster_pyramids[i] with depth is carried by transforms[i]
+    (4 x 4, the raster camera -> the sampled camera) into sampled_pyramids[i] and takes its bilinear intensity there, over the taps that
+    are not nearer than the point by more than occlusion_margin.  Returns (I, Z) -- with difference=True (I, Z, D), D = I - the raster
+    image -- lists of one [h, w] float32 array of level `level` per item; NaN where a pixel has no depth, lands outside the image or
+    behind the camera, or has no tap that counts.  device=True: torch tensors on the GPU instead of numpy arrays.
+    Result.transformation is current -> reference: to see the current image in the reference's raster pass the reference pyramid as
+    raster, the current one as sampled and numpy.linalg.inv(result.transformation)."""
+    who = "warp_inverse_batch"
+    n, T = _warp_args(raster_pyramids, sampled_pyramids, transforms, level, who)
+    params = warp_params_struct(occlusion_margin=occlusion_margin)
+    ctx = raster_pyramids[0].ctx
+    out, ptrs = _warp_planes(raster_pyramids, level, 3 if difference else 2, device)
+    ctx.check(ctx._lib.dvo_hip_frames_warp_inverse(ctx.ptr, n, _handles(raster_pyramids), _handles(sampled_pyramids),
+                                                   T.ctypes.data_as(C.POINTER(C.c_double)), int(level), C.byref(params), ptrs[0], ptrs[1],
+                                                   ptrs[2] if difference else None, 1 if device else 0))
+    return tuple(out)
+
+
+def warp_forward_batch(pyramids, transforms, level=0, mode="splat", min_depth=0.0, max_depth=float("inf"), device=False):
+    """The images the frames predict at other poses (dvo_hip_frames_warp_forward; the reference's RgbdImage::warpDepthForwardAdvanced --
+    mode "splat" -- and warpDepthForward / warpIntensityForward -- mode "nearest").  Item i: every pixel of pyramids[i] with a depth
+    in [min_depth, max_depth] is carried by transforms[i] (4 x 4, the frame's camera -> the target camera) and drawn into a target of
+    the frame's own size and intrinsics, the nearest surface per pixel.  Returns (I, Z), lists of one [h, w] float32 array of level
+    `level` per item: depth in metres (NaN where nothing landed) and that surface's intensity (0 there) -- planes
+    update_f32_device_batch takes.  device=True: torch tensors on the GPU instead of numpy arrays."""
+    who = "warp_forward_batch"
+    n, T = _warp_args(pyramids, None, transforms, level, who)
+    params = warp_params_struct(mode=mode, min_depth=min_depth, max_depth=max_depth)
+    ctx = pyramids[0].ctx
+    out, ptrs = _warp_planes(pyramids, level, 2, device)
+    ctx.check(ctx._lib.dvo_hip_frames_warp_forward(ctx.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)), int(level),
+                                                   C.byref(params), ptrs[0], ptrs[1], 1 if device else 0))
+    return tuple(out)
+
+
 def _rehash_capacity(capacity):
     """the capacity_slots of dvo_hip_map_rehash (None: 0, keep), or ValueError / TypeError"""
     if capacity is None:

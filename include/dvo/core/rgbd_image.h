@@ -237,6 +237,26 @@ class RgbdImage {
   // trackers (local_tracker.cpp:163-169).  Optional: match() builds whatever is missing.
   inline void buildAccelerationStructure();
   bool inImage(const float& x, const float& y) const { return x >= 0 && x < float(width) && y >= 0 && y < float(height); }
+  // rgbd_image.h:199-213, rgbd_image.cpp:545-781 -- the image warps, on the device (dvo_hip_frames_warp_inverse / _forward; the semantics
+  // and the deviations from the reference's loops: include/dvo_hip.h, "frames warped under a pose").  For images that belong to a
+  // pyramid; on a free-standing image they fail through the error handler.  The transformation is the double one of the rest of this
+  // facade (the library rounds it to float once, as the reference's cast does).  All fill result.intensity and result.depth (host
+  // matrices of this level's size); result may be any RgbdImage, this one included.
+  // warpIntensity: this image seen in `reference`'s raster under `transformation` (reference's camera -> this camera).  The reference
+  // passes the host point cloud of the raster image; here the image that owns it stands in (same level size).
+  inline void warpIntensity(const AffineTransformd& transformation, const RgbdImage& reference, RgbdImage& result);
+  // the forward warps into a target of this image's own size; `intrinsics` must equal the level's own (the library projects with them).
+  // warpIntensityForward and warpDepthForward draw one pixel per source pixel (DVO_HIP_WARP_NEAREST), warpDepthForwardAdvanced the
+  // reference's footprint (DVO_HIP_WARP_SPLAT)
+  void warpIntensityForward(const AffineTransformd& transformation, const IntrinsicMatrix& intrinsics, RgbdImage& result) {
+    warpForward(transformation, intrinsics, DVO_HIP_WARP_NEAREST, result);
+  }
+  void warpDepthForward(const AffineTransformd& transformation, const IntrinsicMatrix& intrinsics, RgbdImage& result) {
+    warpForward(transformation, intrinsics, DVO_HIP_WARP_NEAREST, result);
+  }
+  void warpDepthForwardAdvanced(const AffineTransformd& transformation, const IntrinsicMatrix& intrinsics, RgbdImage& result) {
+    warpForward(transformation, intrinsics, DVO_HIP_WARP_SPLAT, result);
+  }
 
   // ---- not in the reference: control over the host mirrors ---------------------------------------------------------
   enum { MirrorPlanes = 1, MirrorDerivatives = 2, MirrorPointCloud = 4, MirrorAcceleration = 8, MirrorAll = 15 };
@@ -252,6 +272,7 @@ class RgbdImage {
   RgbdImage(RgbdImagePyramid* owner, int level, const RgbdCamera& camera)
       : width(camera.width()), height(camera.height()), timestamp(0), owner_(owner), level_(level), camera_(camera) {}
   inline void download(int plane, dvo::compat::ImageMat& m);
+  inline void warpForward(const AffineTransformd& transformation, const IntrinsicMatrix& intrinsics, int mode, RgbdImage& result);
   RgbdImagePyramid* owner_;   // null for free-standing images (RgbdCamera::create)
   int level_;
   const RgbdCamera& camera_;
@@ -577,6 +598,57 @@ inline void RgbdImage::download(int plane, dvo::compat::ImageMat& m) {
   m = dvo::compat::image_create(int(height), int(width));
   dvo_hip_check(owner_->device_context(), dvo_hip_frame_download_plane(owner_->device_context(), owner_->device_frame(), level_, plane,
                                                                        dvo::compat::image_ptr_mut(m)), "dvo_hip_frame_download_plane");
+}
+
+inline void RgbdImage::warpIntensity(const AffineTransformd& transformation, const RgbdImage& reference, RgbdImage& result) {
+  if (!owner_ || !reference.owner_) {
+    DeviceContext::fail("RgbdImage::warpIntensity", "both images must belong to a pyramid");
+    return;
+  }
+  double m[16];
+  dvo::compat::affine_to_rowmajor(transformation, m);
+  dvo::compat::ImageMat I = dvo::compat::image_create(int(reference.height), int(reference.width));
+  dvo::compat::ImageMat Z = dvo::compat::image_create(int(reference.height), int(reference.width));
+  dvo_hip_frame* raster[1] = {reference.owner_->device_frame()};
+  dvo_hip_frame* sampled[1] = {owner_->device_frame()};
+  float* i[1] = {dvo::compat::image_ptr_mut(I)};
+  float* z[1] = {dvo::compat::image_ptr_mut(Z)};
+  if (level_ != reference.level_) {
+    DeviceContext::fail("RgbdImage::warpIntensity", "the images are of different pyramid levels");
+    return;
+  }
+  if (!dvo_hip_check(owner_->device_context(), dvo_hip_frames_warp_inverse(owner_->device_context(), 1, raster, sampled, m, level_, nullptr, i, z,
+                                                                           nullptr, 0), "dvo_hip_frames_warp_inverse"))
+    return;
+  result.intensity = I;
+  result.depth = Z;
+  result.initialize();
+}
+
+inline void RgbdImage::warpForward(const AffineTransformd& transformation, const IntrinsicMatrix& intrinsics, int mode, RgbdImage& result) {
+  if (!owner_) {
+    DeviceContext::fail("RgbdImage::warpForward", "the image must belong to a pyramid");
+    return;
+  }
+  const IntrinsicMatrix& own = camera_.intrinsics();
+  if (intrinsics.fx() != own.fx() || intrinsics.fy() != own.fy() || intrinsics.ox() != own.ox() || intrinsics.oy() != own.oy()) {
+    DeviceContext::fail("RgbdImage::warpForward", "the intrinsics must be those of the image's own level");
+    return;
+  }
+  double m[16];
+  dvo::compat::affine_to_rowmajor(transformation, m);
+  dvo::compat::ImageMat I = dvo::compat::image_create(int(height), int(width)), Z = dvo::compat::image_create(int(height), int(width));
+  dvo_hip_frame* one[1] = {owner_->device_frame()};
+  float* i[1] = {dvo::compat::image_ptr_mut(I)};
+  float* z[1] = {dvo::compat::image_ptr_mut(Z)};
+  dvo_hip_warp_params params = dvo_hip_warp_params_default();
+  params.mode = mode;
+  if (!dvo_hip_check(owner_->device_context(), dvo_hip_frames_warp_forward(owner_->device_context(), 1, one, m, level_, &params, i, z, 0),
+                     "dvo_hip_frames_warp_forward"))
+    return;
+  result.intensity = I;
+  result.depth = Z;
+  result.initialize();
 }
 
 // fills the requested host fields from the device planes (bit-identical to what the reference computes on the host:

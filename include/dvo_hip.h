@@ -657,6 +657,69 @@ int dvo_hip_map_render_frames(dvo_hip_context* ctx, dvo_hip_map* map, int n_fram
 int dvo_hip_time_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, int height, const float K[4],
                             const double* poses /* n x 16 */, const dvo_hip_render_params* params, int reps, float ms[3]);
 
+/* ---- frames warped under a pose: the reference's image warps --------------------------------------------------------------------------------
+ * RgbdImage::warpIntensity, warpIntensityForward, warpDepthForward and warpDepthForwardAdvanced (dvo_core/include/dvo/core/rgbd_image.h:199-213,
+ * dvo_core/src/core/rgbd_image.cpp:545-781, dvo_core/src/core/interpolation.cpp:55-110) for n frames in one launch, on the planes the
+ * frames hold on the device.  The INVERSE warp shows one image in another image's raster -- the picture a user of a direct method checks an
+ * alignment with, and its difference image.  The FORWARD warp predicts the depth (and intensity) image at a new pose from one frame, without
+ * a map: the planes the float ingest above takes ("a filtered, rendered or predicted depth image").  All arithmetic is float32 and stated
+ * once in dvo_slam_amd/csrc/frame_warp.h, whose host build the device planes equal BIT FOR BIT; every NaN stored is 0x7FC00000.
+ *   transform    the row-major 4 x 4 double of dvo_hip_result::transformation, rounded to float once per item; the linear part is applied
+ *                as given (no orthonormality check), each row as ((r0 X + r1 Y) + r2 z) + t.
+ *   inverse      (warpIntensity, rgbd_image.cpp:564-597, with Interpolation::bilinearWithDepthBuffer, interpolation.cpp:55-110.)  Item i:
+ *                a RASTER frame R (the owner of the reference's reference_pointcloud), a SAMPLED frame S (the reference's `this`) and T,
+ *                R's camera -> S's camera, at a level where both have the same size; K_R back-projects, K_S projects.  Per raster pixel
+ *                with depth z: p = T (((x - ox) / fx) z, ((y - oy) / fy) z, z); u = (p.x fx) / p.z + ox, v likewise.  I_w = Z_w = NaN where
+ *                z is not finite, p.z is not finite or <= 0, or (u, v) is outside 0 <= u < w, 0 <= v < h.  Else Z_w = p.z, and I_w is the
+ *                bilinear sample of I_S at (u, v) over the taps whose Z_S is finite and > p.z - occlusion_margin (the reference's 0.05),
+ *                renormalised by their weights; NaN when no tap counts, and NaN (Z_w stays) in the last row and column, where a tap
+ *                would lie outside.  The optional difference plane is D = I_w - I_R, NaN where I_w is NaN.
+ *                dvo_hip_result::transformation is current -> reference: to see the current image in the reference's raster pass its inverse
+ *                with R = the reference frame and S = the current one.
+ *   forward      (warpIntensityForward rgbd_image.cpp:654-721, warpDepthForward :604-652, warpDepthForwardAdvanced :723-781.)  Item i: a
+ *                source frame F and T, F's camera -> the target camera; the target has F's size and K at the level.  A source pixel is
+ *                skipped unless z is finite and > 0 and within [min_depth, max_depth] (0 and +INFINITY: off), and p.z is finite and > 0.
+ *                DVO_HIP_WARP_NEAREST: the pixel (floor(u), floor(v)) when it lies in the image.  DVO_HIP_WARP_SPLAT: the reference's
+ *                footprint (rgbd_image.cpp:734-763), xlen = ceil(zf1 + xf1 (X / z)) + 1 by ylen pixels from (floor(u), floor(v)), clipped
+ *                to the image, each length cut to 8.  Every covered pixel takes the unsigned minimum of bits(p.z) << 32 | bits(max(I, 0)),
+ *                the z-buffer element of the map views: the nearest surface wins, the intensity is that surface's, and the planes do not
+ *                depend on the order of the source pixels.  A pixel nothing covers is a hole: Z = NaN, I = 0.
+ *   deviations   the inverse warp refuses points behind the camera (the reference tests only finiteness).  The reference's
+ *                warpDepthForward keeps an order-dependent 5 cm hysteresis and stores the UNTRANSFORMED depth, warpIntensityForward lets
+ *                the last writer win and returns the source's depth: neither is followed, both modes give p.z of the nearest surface and
+ *                its intensity.  rotation() of an Eigen Affine is a decomposition; here the linear part is used.  The Z plane of SPLAT is,
+ *                for rigid T and footprints within the cap, exactly the reference's (its `!isfinite(*v) || *v > z` is a minimum).
+ *   streams      as dvo_hip_frames_world_points: the launches run on the context's main stream behind the builds of the frames, recorded
+ *                (deferred) ingests are carried out first, and the call waits for that stream: host AND device planes are complete on
+ *                return (device planes are thereby ordered before anything issued later on any stream of the context).  The forward
+ *                warp's z-buffers are the render scratch of the context, filled and resolved on the main stream like a map render's.
+ *   refusals     DVO_HIP_ERR_INVALID, nothing launched, no output touched, no counter moved: null or foreign handles, null outputs, a
+ *                null transforms; n <= 0; a level the frames do not have; a pair whose sizes differ at the level; a transform that is
+ *                not finite; an unknown mode; a margin that is negative or NaN; min_depth > max_depth or a NaN bound; a reserved field
+ *                that is not 0; a device plane that is not 16-byte aligned.
+ *   cost         profiles/frame_warp.md.  Counter "frame_warps" counts items. */
+#define DVO_HIP_WARP_NEAREST 0 /* warpDepthForward / warpIntensityForward: one pixel per source pixel */
+#define DVO_HIP_WARP_SPLAT 1   /* warpDepthForwardAdvanced: the reference's footprint, no holes on a surface that comes nearer */
+typedef struct {
+  int32_t mode;               /* forward: DVO_HIP_WARP_NEAREST or DVO_HIP_WARP_SPLAT; the inverse warp checks it and uses nothing of it */
+  float occlusion_margin;     /* inverse: a tap nearer than p.z - margin is left out; >= 0 */
+  float min_depth, max_depth; /* forward: of the source depth; 0 and +INFINITY: off */
+  uint32_t reserved[4];       /* 0 */
+} dvo_hip_warp_params;
+/* DVO_HIP_WARP_SPLAT, margin 0.05f, min_depth 0, max_depth +INFINITY */
+dvo_hip_warp_params dvo_hip_warp_params_default(void);
+/* Item i: raster_frames[i] and sampled_frames[i] under transforms[16 * i ..] (raster camera -> sampled camera) at `level`: I_w into
+ * intensity_out[i], Z_w into depth_out[i] and -- where difference_out_or_null is not NULL -- D into difference_out_or_null[i]; w_L * h_L
+ * floats each, tight; host arrays, or device arrays (16-byte aligned) with out_on_device.  params NULL: the defaults. */
+int dvo_hip_frames_warp_inverse(dvo_hip_context* ctx, int n, dvo_hip_frame* const* raster_frames, dvo_hip_frame* const* sampled_frames,
+                                const double* transforms /* n x 16 */, int level, const dvo_hip_warp_params* params_or_null,
+                                float* const* intensity_out, float* const* depth_out, float* const* difference_out_or_null, int out_on_device);
+/* Item i: frames[i] under transforms[16 * i ..] (its camera -> the target camera) at `level`: the predicted planes I into intensity_out[i]
+ * and Z into depth_out[i], as above. */
+int dvo_hip_frames_warp_forward(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const double* transforms /* n x 16 */, int level,
+                                const dvo_hip_warp_params* params_or_null, float* const* intensity_out, float* const* depth_out,
+                                int out_on_device);
+
 /* ---- colour in the keyframe map: frames keep RGB, voxels fuse it -------------------------------------------------------------------------
  * The reference's map is coloured: dvo_benchmark/src/benchmark_slam.cpp:89-90 keeps the camera image in level(0).rgb,
  * AsyncPointCloudBuilder::BuildJob::build (dvo_core/src/visualization/async_point_cloud_builder.cpp:72-104) writes p.b, p.g, p.r from it
@@ -1071,6 +1134,7 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value);
  * counts in neither) and "map_rehashes" (tables dvo_hip_map_rehash has replaced).  Refused calls count nothing, dvo_hip_map_clear resets
  * none of them,
  * "map_renders" (views dvo_hip_map_render and dvo_hip_map_render_frames have rendered; a refused call counts nothing),
+ * "frame_warps" (items dvo_hip_frames_warp_inverse and dvo_hip_frames_warp_forward have warped; a refused call counts nothing),
  * "warmup_wait_us" (the longest of the nine stream waits dvo_hip_context_create makes on trivial commands to warm up the runtime's wait
  * path, in microseconds: the first GPU process on a fresh box has been seen to spend 14-24 ms in its first wait),
  * "host_batches" and "host_ns_prepare" / "host_ns_enqueue" / "host_ns_wait" / "host_ns_finish" (nanoseconds the calling thread spent
