@@ -39,6 +39,7 @@
 // untransformed point (Q10), the accumulator layout, the deterministic reduction order.  Differences to variant 7 are rounding
 // differences of a few ulp in u, v and the blends (tests/test_gpu_parity.py::test_contracted_sweep_against_the_exact_one states and
 // checks the bounds); variants 6 / 7 stay in the tree as the bit-exact anchors.
+#include "dispatch.h"
 #include "fast_sweep.h"
 #include "solver_step.h"
 
@@ -101,66 +102,40 @@ __global__ __launch_bounds__(256, COMPAT == 2 ? 4 : 5) void k_sweep_fast(
   if constexpr (TAIL == 2) sweep_tail_wide(g, tail, pair, reinterpret_cast<char*>(win));
 }
 
-// the instantiations with a tail: the default schedule (variant 8, every low part of the Gram operands, no "ref_compat")
-bool sweep_fast_has_tail(int variant, const LevelGeom& g) { return variant == 8 && !g.rcp_table && !g.gram_hi_j && fast_sweep_supports(g); }
-
-bool fast_sweep_takes_width(int w) { return w >= kFastCols && w % 2 == 0; }
-
-bool fast_sweep_supports(const LevelGeom& g) {
-  // (a pair's planes and its residual buffer are addressed through 32-bit buffer offsets: 2 GB each at most -- a 16 384 x 16 384 level)
-  const long long plane_bytes = 8ll * g.w * g.h, packed_bytes = 8ll * kCompactTileEntries * g.tiles_x * g.tiles_y;
-  return !g.linear && fast_sweep_takes_width(g.w) && g.w < 32768 && g.h < 32768 && plane_bytes < (1ll << 31) && packed_bytes < (1ll << 31);
-}
-
-void launch_sweep_fast(hipStream_t s, int variant, const LevelGeom& g, const PairPtrs* pairs, const PairState* states, int n_pairs,
+// operand_store: SweepChoice::operand_store.  tail (the default schedule only: sweep_has_tail): the step, or with tail->pair_sums its wide
+// half, in the sweep's launch.
+void launch_sweep_fast(hipStream_t s, int operand_store, const LevelGeom& g, const PairPtrs* pairs, const PairState* states, int n_pairs,
                        float* partials, float2* scratch, unsigned long long* fallback_count, int* f16_range_flag, const SolverStepArgs* tail) {
   const int total = g.tiles_x * g.tiles_y * n_pairs;
   const int per_xcd = (total + 7) / 8;
   const dim3 grid(per_xcd * 8), block(256);
-  const bool partial = g.w % kTileW != 0, compact = g.compact != 0;
   const SolverStepArgs no_tail = {};
-  if (tail) {                                                // (the default schedule only: sweep_fast_has_tail)
-    auto with = [&](auto partial_tag, auto compact_tag) {
-      constexpr bool kP = decltype(partial_tag)::value, kC = decltype(compact_tag)::value;
-      if (tail->pair_sums) k_sweep_fast<2, kP, kC, 0, false, 2><<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, fallback_count, f16_range_flag, *tail);
-      else k_sweep_fast<2, kP, kC, 0, false, 1><<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, fallback_count, f16_range_flag, *tail);
-    };
-    if (compact) { if (partial) with(std::true_type{}, std::true_type{}); else with(std::false_type{}, std::true_type{}); }
-    else { if (partial) with(std::true_type{}, std::false_type{}); else with(std::false_type{}, std::false_type{}); }
-    return;
-  }
-  auto go = [&](auto store_tag, auto partial_tag, auto compact_tag, auto compat_tag) {
-    constexpr int kStore = decltype(store_tag)::value;
-    if (g.gram_hi_j && kStore == 2)
-      k_sweep_fast<2, decltype(partial_tag)::value, decltype(compact_tag)::value, decltype(compat_tag)::value, true, 0>
-          <<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, fallback_count, f16_range_flag, no_tail);
-    else
-      k_sweep_fast<kStore, decltype(partial_tag)::value, decltype(compact_tag)::value, decltype(compat_tag)::value, false, 0>
-          <<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, fallback_count, f16_range_flag, no_tail);
-  };
-  using S1 = std::integral_constant<int, 1>;
-  using S2 = std::integral_constant<int, 2>;
-  using T = std::true_type;
-  using F = std::false_type;
-  using C0 = std::integral_constant<int, 0>;
-  using C1 = std::integral_constant<int, 1>;
-  using C2 = std::integral_constant<int, 2>;
   // Option "ref_compat" VALUE 1 -> template COMPAT 2 (the table's 16-bit copy in LDS) when the table packs, else COMPAT 1; option VALUE 2
   // -> COMPAT 1 (the table through memory) always: the numbers run the other way round on purpose of history, not of meaning.  Under
   // "ref_compat" the operand store is STORE 2 whatever the variant: "variant" 9 (STORE 1, a measurement schedule) is the same as 8 there.
-  if (g.rcp_table && g.rcp_packed) {                           // option "ref_compat": the host's reciprocal table in projection and weights, from LDS
-    if (compact) { if (partial) go(S2{}, T{}, T{}, C2{}); else go(S2{}, F{}, T{}, C2{}); }
-    else { if (partial) go(S2{}, T{}, F{}, C2{}); else go(S2{}, F{}, F{}, C2{}); }
-  } else if (g.rcp_table) {                                    // ... a table that does not fit a 16-bit copy: from memory
-    if (compact) { if (partial) go(S2{}, T{}, T{}, C1{}); else go(S2{}, F{}, T{}, C1{}); }
-    else { if (partial) go(S2{}, T{}, F{}, C1{}); else go(S2{}, F{}, F{}, C1{}); }
-  } else if (variant == 8) {
-    if (compact) { if (partial) go(S2{}, T{}, T{}, C0{}); else go(S2{}, F{}, T{}, C0{}); }
-    else { if (partial) go(S2{}, T{}, F{}, C0{}); else go(S2{}, F{}, F{}, C0{}); }
-  } else {
-    if (compact) { if (partial) go(S1{}, T{}, T{}, C0{}); else go(S1{}, F{}, T{}, C0{}); }
-    else { if (partial) go(S1{}, T{}, F{}, C0{}); else go(S1{}, F{}, F{}, C0{}); }
-  }
+  const int tail_kind = !tail ? 0 : tail->pair_sums ? 2 : 1;
+  const int compat = tail || !g.rcp_table ? 0 : g.rcp_packed ? 2 : 1;
+  const int store = tail || compat ? 2 : operand_store;
+  const bool hi_j = !tail && store == 2 && g.gram_hi_j;
+  // (the values above only meet in the combinations that are built: the others are never instantiated)
+  with_value<2, 1>(store, [&](auto STORE) {
+    with_bool(g.w % kTileW != 0, [&](auto PARTIAL) {
+      with_bool(g.compact != 0, [&](auto COMPACT) {
+        with_value<0, 1, 2>(compat, [&](auto COMPAT) {
+          with_bool(hi_j, [&](auto HI_J) {
+            with_value<0, 1, 2>(tail_kind, [&](auto TAIL) {
+              constexpr int kStore = decltype(STORE)::value, kCompat = decltype(COMPAT)::value, kTail = decltype(TAIL)::value;
+              constexpr bool kHiJ = decltype(HI_J)::value;
+              // STORE 1 is the plain variant 9; a tail is the default schedule's: STORE 2, no table, every low part
+              if constexpr ((kStore == 2 || (kCompat == 0 && !kHiJ)) && (kTail == 0 || (kStore == 2 && kCompat == 0 && !kHiJ)))
+                k_sweep_fast<kStore, decltype(PARTIAL)::value, decltype(COMPACT)::value, kCompat, kHiJ, kTail>
+                    <<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, fallback_count, f16_range_flag, kTail ? *tail : no_tail);
+            });
+          });
+        });
+      });
+    });
+  });
 }
 
 }  // namespace dvo_hip

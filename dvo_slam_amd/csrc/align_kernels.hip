@@ -17,6 +17,7 @@
 // (align_mfma.hip) produces the same outputs 1.3x faster; variant 0 is kept as the independent second implementation the
 // parity tests compare it with.
 #include "align_common.h"
+#include "dispatch.h"
 #include "ref_order.h"
 
 namespace dvo_hip {
@@ -164,47 +165,25 @@ static void launch_rr(hipStream_t s, bool finest, const LevelGeom& g, const Pair
     k_residual_reduce<RPW, false><<<dim3(per_xcd * 8), dim3(kBlock), 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd);
 }
 
-// the sweep of this level has an instantiation that ends with the pairs' solver steps (launch_residual_reduce's own dispatch)
-bool sweep_has_tail(int variant, int rows_per_wave, const LevelGeom& g) {
-  if (g.small) return false;
-  if (variant >= 8 && rows_per_wave == 4 && fast_sweep_supports(g)) return sweep_fast_has_tail(variant, g);
-  if (variant >= 6 && rows_per_wave == 4 && window_sweep_supports(g)) return false;
-  return variant >= 5 && mfma_sweep_has_tail(variant, rows_per_wave, g);
-}
-
-// (the kernels that read LevelGeom::pair_list: k_sweep_fast and k_residual_reduce_mfma -- what launch_residual_reduce picks below for
-// the default schedule, variants 8 / 9, on every level but those of the opt-in small-level sweep and widths of 64 the exact window sweep takes)
-bool sweep_takes_pair_list(int variant, int rows_per_wave, const LevelGeom& g) {
-  if (variant < 8 || g.small) return false;
-  if (rows_per_wave == 4 && fast_sweep_supports(g)) return true;
-  return !(rows_per_wave == 4 && window_sweep_supports(g));
-}
-
-void launch_residual_reduce(hipStream_t s, int variant, int rows_per_wave, bool finest, const LevelGeom& g, const PairPtrs* pairs,
+void launch_residual_reduce(hipStream_t s, const SweepChoice& choice, int rows_per_wave, bool finest, const LevelGeom& g, const PairPtrs* pairs,
                             const PairState* states, int n_pairs, float* partials, float2* scratch, unsigned long long* window_fallbacks, int* f16_range_flag,
                             const SolverStepArgs* tail) {
-  if (g.small) {                                              // (the default schedule on a level small enough for LDS: align_small.hip)
-    launch_sweep_small(s, rows_per_wave, g, pairs, states, n_pairs, partials, scratch, f16_range_flag);
-    return;
-  }
-  if (variant >= 8 && rows_per_wave == 4 && fast_sweep_supports(g)) {
-    launch_sweep_fast(s, variant, g, pairs, states, n_pairs, partials, scratch, window_fallbacks, f16_range_flag, tail);
-    return;
-  }
-  if (variant >= 6 && rows_per_wave == 4 && window_sweep_supports(g)) {
-    launch_sweep_window(s, variant >= 7, g, pairs, states, n_pairs, partials, scratch, window_fallbacks, f16_range_flag);
-    return;
-  }
-  if (variant >= 5) {
-    launch_residual_reduce_mfma(s, rows_per_wave, finest, g, pairs, states, n_pairs, partials, scratch, variant >= 8 ? 2 : variant >= 7 ? 1 : 0, f16_range_flag, tail);
-    return;
-  }
-  switch (rows_per_wave) {
-    case 1: launch_rr<1>(s, finest, g, pairs, states, n_pairs, partials, scratch); break;
-    case 2: launch_rr<2>(s, finest, g, pairs, states, n_pairs, partials, scratch); break;
-    case 4: launch_rr<4>(s, finest, g, pairs, states, n_pairs, partials, scratch); break;
-    case 16: launch_rr<16>(s, finest, g, pairs, states, n_pairs, partials, scratch); break;
-    default: launch_rr<8>(s, finest, g, pairs, states, n_pairs, partials, scratch); break;
+  switch (choice.kernel) {
+    case SweepKernel::Small:                                   // (the default schedule on a level small enough for LDS: align_small.hip)
+      launch_sweep_small(s, rows_per_wave, g, pairs, states, n_pairs, partials, scratch, f16_range_flag);
+      break;
+    case SweepKernel::Fast:
+      launch_sweep_fast(s, choice.operand_store, g, pairs, states, n_pairs, partials, scratch, window_fallbacks, f16_range_flag, tail);
+      break;
+    case SweepKernel::Window:
+      launch_sweep_window(s, choice.mode >= 1, g, pairs, states, n_pairs, partials, scratch, window_fallbacks, f16_range_flag);
+      break;
+    case SweepKernel::Gather:
+      launch_residual_reduce_mfma(s, rows_per_wave, finest, g, pairs, states, n_pairs, partials, scratch, choice.mode, f16_range_flag, tail);
+      break;
+    case SweepKernel::Valu:
+      with_value<1, 2, 4, 16, 8>(rows_per_wave, [&](auto RPW) { launch_rr<decltype(RPW)::value>(s, finest, g, pairs, states, n_pairs, partials, scratch); });
+      break;
   }
 }
 

@@ -17,6 +17,7 @@
 // conflict-free ds_write_b128; the MFMA operand for pixel group g (lane l <- component l&15 of pixel 4g + l>>4)
 // is one conflict-free ds_read_b32 at a constant offset.  A == B (the sqrt(w)-scaled vector on both sides).
 // The LDS slab is private to the wavefront, so the row loop contains no barrier.
+#include "dispatch.h"
 #include "mfma_sweep.h"
 #include "solver_step.h"
 
@@ -74,57 +75,32 @@ __global__ __launch_bounds__(kBlock, TAIL ? 5 : 1) void k_residual_reduce_mfma(
   }
 }
 
-template <int RPW, int F16>
-static void launch_m(hipStream_t s, bool finest, const LevelGeom& g, const PairPtrs* pairs, const PairState* states, int n_pairs,
-                     float* partials, float2* scratch, int* f16_range_flag, const SolverStepArgs* tail) {
+// mode: SweepChoice::mode.  tail (sweep_has_tail: the contracted arithmetic at up to 8 rows per wavefront): the step, or with
+// tail->pair_sums its wide half, in the sweep's launch -- under the kernel name of the coarser levels also on the finest one.
+void launch_residual_reduce_mfma(hipStream_t s, int rows_per_wave, bool finest, const LevelGeom& g, const PairPtrs* pairs,
+                                 const PairState* states, int n_pairs, float* partials, float2* scratch, int mode, int* f16_range_flag,
+                                 const SolverStepArgs* tail) {
   const int total = g.tiles_x * g.tiles_y * n_pairs;
   const int per_xcd = (total + 7) / 8;
   const dim3 grid(per_xcd * 8), block(kBlock);
   const SolverStepArgs no_tail = {};
-  if constexpr (F16 == 2 && RPW <= 8) {
-    if (tail) {                                                // (the default schedule's gathering sweep, never the finest level: mfma_sweep_has_tail)
-      if (tail->pair_sums) {
-        if (g.linear) k_residual_reduce_mfma<RPW, false, true, 2, 2><<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, f16_range_flag, *tail);
-        else k_residual_reduce_mfma<RPW, false, false, 2, 2><<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, f16_range_flag, *tail);
-      } else {
-        if (g.linear) k_residual_reduce_mfma<RPW, false, true, 2, 1><<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, f16_range_flag, *tail);
-        else k_residual_reduce_mfma<RPW, false, false, 2, 1><<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, f16_range_flag, *tail);
-      }
-      return;
-    }
-  }
-  if (g.linear) {
-    if (finest) k_residual_reduce_mfma<RPW, true, true, F16, 0><<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, f16_range_flag, no_tail);
-    else k_residual_reduce_mfma<RPW, false, true, F16, 0><<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, f16_range_flag, no_tail);
-  } else {
-    if (finest) k_residual_reduce_mfma<RPW, true, false, F16, 0><<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, f16_range_flag, no_tail);
-    else k_residual_reduce_mfma<RPW, false, false, F16, 0><<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, f16_range_flag, no_tail);
-  }
-}
-
-template <int F16>
-static void launch_rpw(hipStream_t s, int rows_per_wave, bool finest, const LevelGeom& g, const PairPtrs* pairs, const PairState* states,
-                       int n_pairs, float* partials, float2* scratch, int* f16_range_flag, const SolverStepArgs* tail) {
-  switch (rows_per_wave) {
-    case 1: launch_m<1, F16>(s, finest, g, pairs, states, n_pairs, partials, scratch, f16_range_flag, tail); break;
-    case 2: launch_m<2, F16>(s, finest, g, pairs, states, n_pairs, partials, scratch, f16_range_flag, tail); break;
-    case 4: launch_m<4, F16>(s, finest, g, pairs, states, n_pairs, partials, scratch, f16_range_flag, tail); break;
-    case 16: launch_m<16, F16>(s, finest, g, pairs, states, n_pairs, partials, scratch, f16_range_flag, nullptr); break;
-    default: launch_m<8, F16>(s, finest, g, pairs, states, n_pairs, partials, scratch, f16_range_flag, tail); break;
-  }
-}
-
-// the instantiations with a tail: the contracted gathering sweep (what variant 8 runs where the window sweep does not take the level),
-// tiles of up to 8 rows per wavefront, no "ref_compat"
-bool mfma_sweep_has_tail(int variant, int rows_per_wave, const LevelGeom& g) { return variant >= 8 && !g.rcp_table && rows_per_wave != 16; }
-
-void launch_residual_reduce_mfma(hipStream_t s, int rows_per_wave, bool finest, const LevelGeom& g, const PairPtrs* pairs,
-                                 const PairState* states, int n_pairs, float* partials, float2* scratch, int mode, int* f16_range_flag,
-                                 const SolverStepArgs* tail) {
-  if (mode == 2 && g.rcp_table) mode = 1;                       // (option "ref_compat": the exact arithmetic with the table's reciprocal)
-  if (mode == 2) launch_rpw<2>(s, rows_per_wave, finest, g, pairs, states, n_pairs, partials, scratch, f16_range_flag, tail);
-  else if (mode == 1) launch_rpw<1>(s, rows_per_wave, finest, g, pairs, states, n_pairs, partials, scratch, f16_range_flag, nullptr);
-  else launch_rpw<0>(s, rows_per_wave, finest, g, pairs, states, n_pairs, partials, scratch, nullptr, nullptr);
+  if (mode == 0) f16_range_flag = nullptr;                     // (the f32 Gram has no range to leave)
+  const int tail_kind = !tail || mode != 2 || rows_per_wave == 16 ? 0 : tail->pair_sums ? 2 : 1;
+  with_value<1, 2, 4, 16, 8>(rows_per_wave, [&](auto RPW) {
+    with_value<2, 1, 0>(mode, [&](auto MODE) {
+      with_bool(finest && tail_kind == 0, [&](auto FINEST) {
+        with_bool(g.linear != 0, [&](auto LINEAR) {
+          with_value<0, 1, 2>(tail_kind, [&](auto TAIL) {
+            constexpr int kRpw = decltype(RPW)::value, kMode = decltype(MODE)::value, kTail = decltype(TAIL)::value;
+            constexpr bool kFinest = decltype(FINEST)::value;
+            if constexpr (kTail == 0 || (kMode == 2 && kRpw <= 8 && !kFinest))
+              k_residual_reduce_mfma<kRpw, kFinest, decltype(LINEAR)::value, kMode, kTail>
+                  <<<grid, block, 0, s>>>(g, pairs, states, n_pairs, partials, scratch, per_xcd, f16_range_flag, kTail ? *tail : no_tail);
+          });
+        });
+      });
+    });
+  });
 }
 
 #ifdef DVO_TAIL_CLOCKS

@@ -20,7 +20,6 @@
 
 namespace dvo_hip {
 
-constexpr int kSmallCells = 5376;                            // (w + 2) x (h + 2) cells of 8 B at most: 43 KB (80 x 60: 82 x 62 = 5084)
 constexpr int kSmallLoads = kSmallCells / kBlock;            // cells a thread copies (21)
 
 __global__ __launch_bounds__(kBlock, 3) void k_sweep_small(
@@ -150,11 +149,6 @@ __global__ __launch_bounds__(kBlock, 3) void k_sweep_small(
   if (lane == 0) counts[wave] = n_valid;
   __syncthreads();
   fast_epilogue(slab, counts, gram_entries, partials + (size_t(pair) * tiles + tile) * kAccStride, f16_range_flag ? f16_range_flag + pair : nullptr);
-}
-
-// the levels the kernel takes: even widths (the plane C of a level is built in pixel pairs), the whole level + border in kSmallCells
-bool small_sweep_takes(int w, int h) {
-  return w % 2 == 0 && w >= 4 && h >= 4 && (w + 2) * (h + 2) <= kSmallCells;
 }
 
 void launch_sweep_small(hipStream_t s, int rows_per_wave, const LevelGeom& g, const PairPtrs* pairs, const PairState* states, int n_pairs,

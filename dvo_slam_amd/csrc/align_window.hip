@@ -358,8 +358,6 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? 6 : (F16 ? 5 : 4)) void k_
   }
 }
 
-bool window_sweep_supports(const LevelGeom& g) { return !g.linear && g.w % kTileW == 0 && g.w < 32768 && g.h < 32768; }
-
 void launch_sweep_window(hipStream_t s, bool f16, const LevelGeom& g, const PairPtrs* pairs, const PairState* states, int n_pairs,
                          float* partials, float2* scratch, unsigned long long* fallback_count, int* f16_range_flag) {
   const int total = g.tiles_x * g.tiles_y * n_pairs;

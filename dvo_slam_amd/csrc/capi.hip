@@ -1457,13 +1457,13 @@ int dvo_hip_level_iteration(dvo_hip_context* ctx, dvo_hip_frame* reference, dvo_
   DVO_HIP_TRY(ctx, hipMemsetAsync(states, 0, sizeof(PairState), s));
   launch_set_fixed_state(s, states, g, d_T, d_P, first_iteration_on_level ? 1 : 0);
   // the sweep, the passes of option "ref_order", the log-likelihood pass (`range_flag`: where an f16 Gram schedule reports that it left its range)
-  auto sweep_and_passes = [&](int variant, int* range_flag) {
-    launch_residual_reduce(s, variant, bp.rpw[level], level == 0, g, bp.pair_ptrs + size_t(level), states, 1, w0.partials.as<float>(), w0.scratch.as<float2>(),
+  auto sweep_and_passes = [&](int* range_flag) {                // (by the plan's choice of the moment)
+    launch_residual_reduce(s, bp.choice[level], bp.rpw[level], level == 0, g, bp.pair_ptrs + size_t(level), states, 1, w0.partials.as<float>(), w0.scratch.as<float2>(),
                            w0.win_fallbacks.as<unsigned long long>(), range_flag);
     if (ref_order) launch_ref_order(s, g, states, 1, w0.scratch.as<float2>(), w0.ref_rows.as<RefOrderSeg>(), ref_order);
     launch_loglik(s, g, states, 1, w0.partials.as<float>(), w0.scratch.as<float2>(), w0.ll_partials.as<double>(), kLlBlocksPerPair, false, ref_order);
   };
-  sweep_and_passes(ctx->opt_variant, w0.f16_range_flag);
+  sweep_and_passes(w0.f16_range_flag);
   int n_sel = 0;
   DVO_HIP_TRY(ctx, hipMemcpyAsync(&n_sel, reference->sel_count + level, sizeof(int), hipMemcpyDeviceToHost, s));
   DVO_HIP_TRY(ctx, hipStreamSynchronize(s));
@@ -1477,7 +1477,7 @@ int dvo_hip_level_iteration(dvo_hip_context* ctx, dvo_hip_frame* reference, dvo_
     ctx->opt_variant = keep_variant;
     if (rc != DVO_HIP_OK) return rc;
     g = bp.geom[level];
-    sweep_and_passes(6, nullptr);
+    sweep_and_passes(nullptr);
     DVO_HIP_TRY(ctx, hipStreamSynchronize(s));
   }
   launch_single_shot_out(s, g, ctx->ws[0].partials.as<float>(), ctx->ws[0].ll_partials.as<double>(), kLlBlocksPerPair, n_sel, d_out, ref_order);
@@ -1524,7 +1524,7 @@ int dvo_hip_time_residual_kernel(dvo_hip_context* ctx, int n_pairs, dvo_hip_fram
   launch_init_pairs(s, states, bp.n, bp.prm, w.t_init.as<double>());
   launch_level_begin(s, states, bp.n, bp.prm, g, level, pp, w.lvl_stats.as<dvo_hip_level_stats>());
   auto sweep = [&]() {
-    launch_residual_reduce(s, ctx->opt_variant, bp.rpw[level], level == 0, g, pp, states, bp.n, w.partials.as<float>(), w.scratch.as<float2>(),
+    launch_residual_reduce(s, bp.choice[level], bp.rpw[level], level == 0, g, pp, states, bp.n, w.partials.as<float>(), w.scratch.as<float2>(),
                            w.win_fallbacks.as<unsigned long long>());
   };
   // `warm_iterations` Gauss-Newton steps first: the timed sweeps then run where the sweeps of a match run -- at the transform
@@ -1577,7 +1577,7 @@ int dvo_hip_time_stream_mix(dvo_hip_context* ctx, int n_pairs, dvo_hip_frame* co
   hipEvent_t e0, e1;
   DVO_HIP_TRY(ctx, hipEventCreate(&e0));
   DVO_HIP_TRY(ctx, hipEventCreate(&e1));
-  const bool window_planes = level_uses_window(ctx, g.w, g.h) || level_uses_small(ctx, g.w, g.h);   // the planes the level's sweep really reads
+  const bool window_planes = bp.choice[level].reads_c;   // the planes the level's sweep really reads
   launch_stream_mix(s, pp, bp.n, g.w * g.h, scratch, sink, window_planes);   // warm
   DVO_HIP_TRY(ctx, hipEventRecord(e0, s));
   for (int r = 0; r < reps; ++r) launch_stream_mix(s, pp, bp.n, g.w * g.h, scratch, sink, window_planes);

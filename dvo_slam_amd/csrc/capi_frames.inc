@@ -167,26 +167,13 @@ void level_tiles(int w, int h, int rows_per_wave, bool linear, int* tiles_x, int
   }
 }
 
-// the contracted window sweep (align_fast.hip, variants 8 / 9) also takes widths that are no multiple of its 64 columns (160 x 120)
-bool level_uses_fast_window(const dvo_hip_context* ctx, int w, int h) {
-  return ctx->opt_variant >= 8 && fast_sweep_takes_width(w) && w < 32768 && h < 32768;   // (option "ref_compat" included: the COMPAT instantiations)
+// the option values that bear on the choice of a level's sweep, as they stand now (sweep_choice.h; the Gram schedule of a batch or a repeat
+// rewrites opt_variant for a while: a plan made then holds the choices of that schedule)
+SweepOptions sweep_options(const dvo_hip_context* ctx) {
+  return SweepOptions{ctx->opt_variant, ctx->opt_small_sweep, ctx->opt_ref_compat, ctx->opt_ref_order, ctx->opt_compact_residuals};
 }
 
-// the sweep with the whole current level in LDS (align_small.hip): the default schedule's levels that the window sweeps do not take
-bool level_uses_small(const dvo_hip_context* ctx, int w, int h);
-
-bool level_is_linear(const dvo_hip_context* ctx, int w) { return ctx->opt_variant >= 5 && w % kTileW != 0 && !level_uses_fast_window(ctx, w, 4); }
-
-// the sweep that stages the current frame's window in LDS (align_window.hip, variants 6 / 7; align_fast.hip) handles this level; its tile is 64 x 16
-bool level_uses_window(const dvo_hip_context* ctx, int w, int h) {
-  return (ctx->opt_variant >= 6 && w % kTileW == 0 && w < 32768 && h < 32768) || level_uses_fast_window(ctx, w, h);
-}
-
-bool level_uses_small(const dvo_hip_context* ctx, int w, int h) {
-  return ctx->opt_small_sweep && ctx->opt_variant >= 8 && !ctx->opt_ref_compat && !ctx->opt_ref_order && !level_uses_window(ctx, w, h) && level_is_linear(ctx, w) && small_sweep_takes(w, h);
-}
-
-LevelGeom make_geom(const dvo_hip_context* ctx, const CameraGeom* cam, int level, int rows_per_wave) {
+LevelGeom make_geom(const dvo_hip_context* ctx, const CameraGeom* cam, int level, int rows_per_wave, const SweepChoice& choice) {
   LevelGeom g;
   g.w = cam->w[level]; g.h = cam->h[level];
   g.fx = cam->K[level][0]; g.fy = cam->K[level][1]; g.ox = cam->K[level][2]; g.oy = cam->K[level][3];
@@ -196,24 +183,24 @@ LevelGeom make_geom(const dvo_hip_context* ctx, const CameraGeom* cam, int level
   g.level = level;
   g.pair_list = nullptr;
   g.skip_flags = nullptr;
-  g.linear = level_is_linear(ctx, g.w) ? 1 : 0;
+  g.linear = choice.linear ? 1 : 0;
   level_tiles(g.w, g.h, rows_per_wave, g.linear != 0, &g.tiles_x, &g.tiles_y);
   g.rcp_table = ctx->opt_ref_compat ? ctx->rcp_table.as<float>() : nullptr;
   g.rcp_shift = ctx->rcp_shift;
   g.rcp_packed = ctx->opt_ref_compat == 1 ? ctx->rcp_packed : 0;   // (2: the table through memory, the path of a table that does not pack)
   // (not under "ref_compat": a run that is compared with the reference's own numbers keeps every low part -- round-5 advisor finding)
-  g.gram_hi_j = !ctx->opt_gram_lo_parts && !ctx->opt_deterministic && !ctx->opt_ref_compat && ctx->opt_variant == 8 && size_t(g.w) * g.h >= 150000 ? 1 : 0;
-  g.small = level_uses_small(ctx, g.w, g.h) ? 1 : 0;
-  // (not under "ref_order": its passes read the residual pairs by pixel, ref_order.hip)
-  g.compact = ctx->opt_compact_residuals && !ctx->opt_ref_order && ctx->opt_variant >= 8 && rows_per_wave == 4 && fast_sweep_supports(g) ? 1 : 0;   // (launch_residual_reduce's test)
+  // (variant 8 alone: operand store 2 of the contracted schedules, mode 2 = no "ref_compat")
+  g.gram_hi_j = !ctx->opt_gram_lo_parts && !ctx->opt_deterministic && choice.mode == 2 && choice.operand_store == 2 && size_t(g.w) * g.h >= 150000 ? 1 : 0;
+  g.small = choice.kernel == SweepKernel::Small ? 1 : 0;
+  g.compact = choice.compact ? 1 : 0;
   return g;
 }
 
 // rows of 64 pixels each wavefront sweeps: large tiles amortise the 85-value wave reduction, small tiles
 // keep all 256 CUs busy when the batch is small
-int pick_rows_per_wave(const dvo_hip_context* ctx, const CameraGeom* cam, int level, int n_pairs) {
-  if (level_uses_window(ctx, cam->w[level], cam->h[level])) return 4;
-  if (level_uses_small(ctx, cam->w[level], cam->h[level]) && ctx->opt_rows_per_wave == 0) {
+int pick_rows_per_wave(const dvo_hip_context* ctx, const CameraGeom* cam, int level, int n_pairs, const SweepChoice& choice) {
+  if (choice.tile_rows > 0) return choice.tile_rows;
+  if (choice.kernel == SweepKernel::Small && ctx->opt_rows_per_wave == 0) {
     // segments per wavefront such that a pair gets BatchPolicy::small_level_tiles workgroups
     const int tiles = ctx->opt_small_tiles > 0 ? ctx->opt_small_tiles : BatchPolicy(ctx->compute_units).small_level_tiles(n_pairs);
     const int segments = (cam->w[level] * cam->h[level] + kTileW - 1) / kTileW;
@@ -225,23 +212,18 @@ int pick_rows_per_wave(const dvo_hip_context* ctx, const CameraGeom* cam, int le
   // A large batch fills the device whatever the tile: short tiles (2 rows per wavefront: the schedule with the pinned prologue) run the
   // coarse levels' sweeps 6-11 % faster than tall ones since the f16 Gram (scripts/ab_sweep.py: 1024 pairs, 160x120 0.200 -> 0.187 ms,
   // 80x60 0.056 -> 0.050 ms; bench step 14.22 -> 13.89 ms)
-  if (BatchPolicy(ctx->compute_units).short_gather_tiles(n_pairs) && ctx->opt_variant >= 7) return 2;
+  if (BatchPolicy(ctx->compute_units).short_gather_tiles(n_pairs) && choice.mode >= 1) return 2;
   const int candidates[4] = {8, 4, 2, 1};   // measured (profiles/r01_c_tile_sweep.txt): 8 rows is at or near the optimum on every level
   // The tallest tile that still yields this many workgroups.  Fewer, taller tiles also mean fewer partial rows for the
   // bookkeeping kernel, which matters most when there are few pairs (whole-match timings: profiles/r01_f_tile_heuristic.txt).
   const size_t enough = ctx->opt_min_workgroups > 0 ? size_t(ctx->opt_min_workgroups) : size_t(BatchPolicy(ctx->compute_units).min_workgroups(n_pairs));
   for (int r : candidates) {
     int tx, ty;
-    level_tiles(cam->w[level], cam->h[level], r, level_is_linear(ctx, cam->w[level]), &tx, &ty);
+    level_tiles(cam->w[level], cam->h[level], r, choice.linear, &tx, &ty);
     if (size_t(tx) * ty * n_pairs >= enough) return r;
   }
   return 1;
 }
-
-// (whatever the schedule variant of the moment: a frame outlives option changes)
-static bool width_may_use_window(int w) { return w % kTileW == 0 || fast_sweep_takes_width(w); }
-// (... or the small-level sweep: both read plane C)
-static bool level_may_read_plane_c(int w, int h) { return width_may_use_window(w) || small_sweep_takes(w, h); }
 
 // device layout of a frame: [raw staging][per level: I Z A B R][sel counts]
 int frame_alloc(dvo_hip_context* ctx, int w, int h, const float K[4], int levels, dvo_hip_frame** out, size_t* raw_off) {
@@ -261,7 +243,7 @@ int frame_alloc(dvo_hip_context* ctx, int w, int h, const float K[4], int levels
   for (int l = 0; l < levels; ++l) {
     const size_t n = size_t(cam->w[l]) * cam->h[l];
     // (C = {I, Z} of a current frame, the plane the window sweep stages in LDS: levels that sweep can handle)
-    const size_t sz[6] = {n * 4, n * 4, n * 16, n * 8, n * 8, level_may_read_plane_c(cam->w[l], cam->h[l]) ? n * 8 : 0};
+    const size_t sz[6] = {n * 4, n * 4, n * 16, n * 8, n * 8, any_sweep_reads_plane_c(cam->w[l], cam->h[l]) ? n * 8 : 0};
     for (int k = 0; k < 6; ++k) {
       offs[l][k] = total;
       total += align_up(sz[k], 256);
@@ -293,7 +275,7 @@ int frame_alloc(dvo_hip_context* ctx, int w, int h, const float K[4], int levels
     L.A = reinterpret_cast<float4*>(base + offs[l][2]);
     L.B = reinterpret_cast<float2*>(base + offs[l][3]);
     L.R = reinterpret_cast<float2*>(base + offs[l][4]);
-    L.C = level_may_read_plane_c(cam->w[l], cam->h[l]) ? reinterpret_cast<float2*>(base + offs[l][5]) : nullptr;
+    L.C = any_sweep_reads_plane_c(cam->w[l], cam->h[l]) ? reinterpret_cast<float2*>(base + offs[l][5]) : nullptr;
   }
   f->sel_count = reinterpret_cast<int*>(base + cnt_off);
   *out = f;
@@ -329,11 +311,12 @@ bool aligned_to(const void* p, size_t a) { return reinterpret_cast<uintptr_t>(p)
 // write); a small one may run the level resident (taps A + B) or on the launch path (C): both.  Whatever is missing at match time is
 // derived then (ensure_roles).
 int eager_current_flavor(const dvo_hip_context* ctx, const CameraGeom* cam, int level, int n_frames) {
+  const SweepChoice choice = choose_sweep(sweep_options(ctx), cam->w[level], cam->h[level]);   // (no plan at ingest time)
+  if (!choice.reads_c) return kCurAB;
   // a small level (align_small.hip reads plane C): a batch that may still run this level in the resident kernel (the gathered taps) gets
   // both flavours -- 38 KB and 115 KB per frame at 80 x 60 -- a larger one plane C alone
-  if (level_uses_small(ctx, cam->w[level], cam->h[level]))
+  if (choice.kernel == SweepKernel::Small)
     return BatchPolicy(ctx->compute_units).resident_first_level_fits(n_frames) ? (kCurAB | kCurC) : kCurC;
-  if (!level_uses_window(ctx, cam->w[level], cam->h[level])) return kCurAB;
   // (round 5: from an eighth as many frames as compute units on, plane C alone -- the taps cost three times the bytes to write, and a
   // streaming step of 32 / 48 / 64 pairs that re-ingests them every step is 0.885 / 0.98 / 1.24 -> 0.783 / 0.93 / 1.09 ms without them and
   // with the first level alone resident: plan_resident looks at what the frames hold)

@@ -32,7 +32,7 @@ class SlowLane {
     on_ = ctx->opt_overlap_tails != 0 && !ctx->opt_ref_order && !b.policy.level_hand_over(n) && ctx->opt_sweep_tail == 0 && b.rp.levels == 0 && bp.coarse_levels == 0 &&
           cfg->first_level > cfg->last_level;
     for (int l = cfg->last_level; l <= cfg->first_level; ++l)   // (the lane passes through every level: each one's sweep must take a list of pairs)
-      on_ = on_ && sweep_takes_pair_list(ctx->opt_variant, bp.rpw[l], bp.geom[l]);
+      on_ = on_ && bp.choice[l].pair_list;
     steps_cap_ = on_ ? size_t(bp.cap_iters) + 12 * size_t(bp.nlev) + 8 : 0;   // (per level: the passes of its slowest pair, and up to eight steps enqueued ahead of what is known)
     if (!on_) return DVO_HIP_OK;
     size_t t_tiles = 1, t_entries = 0;
@@ -166,7 +166,7 @@ class SlowLane {
     double* lll = r.ll.as<double>();
     for (int c = 0; c < count && size_t(next) < steps_cap_; ++c, ++next) {
       const size_t idx = b.main_steps + size_t(next);
-      launch_residual_reduce(r.stream, ctx->opt_variant, bp.rpw[level], level == 0, g, pp, b.states, cap, lp, lscr, b.w.win_fallbacks.as<unsigned long long>(),
+      launch_residual_reduce(r.stream, bp.choice[level], bp.rpw[level], level == 0, g, pp, b.states, cap, lp, lscr, b.w.win_fallbacks.as<unsigned long long>(),
                              b.w.f16_range_flag);
       if (!ls.fused_ll) launch_loglik(r.stream, g, b.states, cap, lp, lscr, lll, ls.ll_blocks, ctx->opt_deterministic != 0);
       launch_solver_step(r.stream, b.states, cap, bp.prm, g, lp, lll, ls.ll_blocks, ls.fused_ll ? lscr : nullptr, b.d_levels, b.d_iters,

@@ -9,6 +9,8 @@ struct BatchPlan {
   const CameraGeom* cam = nullptr;
   std::vector<int> rpw;          // per absolute level
   std::vector<LevelGeom> geom;   // per absolute level
+  SweepOptions sweep;            // the options the choices were made under (sweep_options at make_plan's time)
+  std::vector<SweepChoice> choice;   // per absolute level: which sweep runs it (sweep_choice.h); geom and rpw follow from it
   PairPtrs* pair_ptrs = nullptr; // device [levels][n] (null when the table only travels in kernel arguments)
   std::vector<PairPtrs> host_ptrs;   // the same table on the host
   int coarse_levels = 0;         // leading levels (first_level, first_level - 1, ...) the fused coarse-level kernel runs (plan_coarse)
@@ -53,17 +55,19 @@ void make_plan(const dvo_hip_context* ctx, const CameraGeom* cam, const dvo_hip_
   bp.prm.record_prefilled = 0;
   bp.rpw.assign(need_levels, 1);
   bp.geom.resize(need_levels);
+  bp.sweep = sweep_options(ctx);
+  bp.choice.resize(need_levels);
   for (int l = cfg->last_level; l <= cfg->first_level; ++l) {
-    bp.rpw[l] = pick_rows_per_wave(ctx, cam, l, n);
-    bp.geom[l] = make_geom(ctx, cam, l, bp.rpw[l]);
+    bp.choice[l] = choose_sweep(bp.sweep, cam->w[l], cam->h[l]);
+    bp.rpw[l] = pick_rows_per_wave(ctx, cam, l, n, bp.choice[l]);
+    bp.geom[l] = make_geom(ctx, cam, l, bp.rpw[l], bp.choice[l]);
   }
 }
 
 // buildAccelerationStructure for the current frames, PointSelection::select for the reference frames (both cached per
 // frame and level); enqueued on the context's main stream
 // `launch_path_only`: the caller runs every level on the launch-per-step path (the parity / measurement entry points)
-int resident_levels_of(const dvo_hip_context* ctx, const dvo_hip_config* cfg, const CameraGeom* cam, int n, bool taps_missing);
-bool window_taps_missing(const dvo_hip_context* ctx, const dvo_hip_config* cfg, int n, dvo_hip_frame* const* curs);
+int resident_levels_of(const dvo_hip_context* ctx, const dvo_hip_config* cfg, BatchPlan& bp, dvo_hip_frame* const* curs);
 
 // Option "ref_order", Q3 (ref_order.hip::k_ref_order_drop_last): the reference planes R of a batch's levels lose the last selected pixel of
 // an odd selection, once per build of the plane (FrameLevel::q3).  The edit keeps the pixel it cleared in the frame's block of selection
@@ -104,11 +108,12 @@ int ensure_batch_roles(dvo_hip_context* ctx, int n, dvo_hip_frame* const* refs, 
   if (rc != DVO_HIP_OK) return rc;
   // the flavour of the current role each level is read in: the resident kernel and the gathering sweep read the taps A + B, the
   // window sweep the 8-byte plane C
-  const CameraGeom* cam = curs[0]->cam;
-  const int resident = launch_path_only ? 0 : resident_levels_of(ctx, cfg, cam, n, window_taps_missing(ctx, cfg, n, curs));
+  BatchPlan bp;
+  make_plan(ctx, curs[0]->cam, cfg, n, bp);
+  const int resident = launch_path_only ? 0 : resident_levels_of(ctx, cfg, bp, curs);
   int want[kMaxLevels];
-  for (int l = 0; l < kMaxLevels; ++l)
-    want[l] = l > cfg->first_level - resident || l >= cam->levels || !(level_uses_window(ctx, cam->w[l], cam->h[l]) || level_uses_small(ctx, cam->w[l], cam->h[l])) ? kCurAB : kCurC;
+  for (int l = 0; l < kMaxLevels; ++l)   // (ensure_roles looks at the batch's levels only)
+    want[l] = l < cfg->last_level || l > cfg->first_level - resident || !bp.choice[l].reads_c ? kCurAB : kCurC;
   rc = ensure_roles(ctx, n, curs, 0, cfg->last_level, cfg->first_level, 0.0f, 0.0f, /*eager=*/false, want);
   if (rc == DVO_HIP_OK)
     rc = ensure_roles(ctx, n, refs, 1, cfg->last_level, cfg->first_level, cfg->intensity_derivative_threshold, cfg->depth_derivative_threshold);
@@ -313,10 +318,10 @@ constexpr size_t kResidentDirectStatsBytes = size_t(64) << 20;
 // `taps_missing`: current frames of the batch hold plane C but not the taps A + B on the level below the first one (they were ingested
 // straight into their role in a batch of an eighth as many frames as compute units or more, eager_current_flavor): the resident kernel
 // would have to have the taps derived for it first
-bool window_taps_missing(const dvo_hip_context* ctx, const dvo_hip_config* cfg, int n, dvo_hip_frame* const* curs) {
+bool window_taps_missing(const dvo_hip_config* cfg, const BatchPlan& bp, dvo_hip_frame* const* curs) {
   const int level = cfg->first_level - 1;
-  if (level < cfg->last_level || level >= curs[0]->levels || !level_uses_window(ctx, curs[0]->cam->w[level], curs[0]->cam->h[level])) return false;
-  for (int i = 0; i < n; ++i) {
+  if (level < cfg->last_level || !bp.choice[level].windowed()) return false;
+  for (int i = 0; i < bp.n; ++i) {
     const int have = curs[i]->lv[level].cur_have;
     if ((have & kCurC) && !(have & kCurAB)) return true;
   }
@@ -349,7 +354,7 @@ ResidentPlan plan_resident(const dvo_hip_context* ctx, const dvo_hip_config* cfg
   const BatchPolicy policy(ctx->compute_units);
   const bool first_level_only = ctx->opt_resident < 0 && ctx->opt_resident_group == 0 &&
                                 (!policy.resident_takes_coarse_levels(bp.n) || (policy.taps_missing_prefers_first_level_only(bp.n) && taps_missing));
-  if (first_level_only && (!policy.resident_first_level_fits(bp.n) || level_uses_window(ctx, bp.cam->w[cfg->first_level], bp.cam->h[cfg->first_level]))) return rp;
+  if (first_level_only && (!policy.resident_first_level_fits(bp.n) || bp.choice[cfg->first_level].windowed())) return rp;
   // all workgroups of a launch with groups must be resident at once: one workgroup (8 wavefronts, up to 256 registers) per compute unit
   int group = 1;
   while (group * 2 <= kResidentMaxGroup && bp.n * group * 2 <= cus) group *= 2;
@@ -391,15 +396,15 @@ constexpr int kCoarseMaxPixels = 160 * 120;
 
 void plan_coarse(const dvo_hip_context* ctx, const dvo_hip_config* cfg, BatchPlan& bp, const ResidentPlan& rp) {
   bp.coarse_levels = 0;
-  if (ctx->opt_coarse == 0 || rp.levels > 0 || ctx->opt_variant != 8 || ctx->opt_ref_order) return;
+  if (ctx->opt_coarse == 0 || rp.levels > 0 || bp.sweep.variant != 8 || ctx->opt_ref_order) return;
   const int max_pixels = ctx->opt_coarse_pixels > 0 ? ctx->opt_coarse_pixels : kCoarseMaxPixels;
   for (int level = cfg->first_level; level >= cfg->last_level; --level) {
     if (bp.cam->w[level] * bp.cam->h[level] > max_pixels) break;
-    const bool window_level = level_uses_window(ctx, bp.cam->w[level], bp.cam->h[level]);
-    const int rpw = window_level ? 4 : kCoarseRowsPerWave;
-    if (!window_level && ctx->opt_rows_per_wave > 0 && ctx->opt_rows_per_wave != rpw) break;   // (a tile height asked for by name stays)
-    const LevelGeom g = make_geom(ctx, bp.cam, level, rpw);
-    if (!coarse_kernel_takes(g, window_level)) break;
+    const SweepChoice& choice = bp.choice[level];
+    const int rpw = choice.tile_rows > 0 ? choice.tile_rows : kCoarseRowsPerWave;
+    if (choice.tile_rows == 0 && ctx->opt_rows_per_wave > 0 && ctx->opt_rows_per_wave != rpw) break;   // (a tile height asked for by name stays)
+    const LevelGeom g = make_geom(ctx, bp.cam, level, rpw, choice);
+    if (!coarse_kernel_takes(choice, g)) break;
     bp.rpw[level] = rpw;
     bp.geom[level] = g;
     bp.coarse_levels += 1;
@@ -419,10 +424,8 @@ ResidentPlan plan_paths(const dvo_hip_context* ctx, const dvo_hip_config* cfg, B
   return rp;
 }
 
-int resident_levels_of(const dvo_hip_context* ctx, const dvo_hip_config* cfg, const CameraGeom* cam, int n, bool taps_missing) {
-  BatchPlan bp;
-  make_plan(ctx, cam, cfg, n, bp);
-  return plan_paths(ctx, cfg, bp, taps_missing).levels;
+int resident_levels_of(const dvo_hip_context* ctx, const dvo_hip_config* cfg, BatchPlan& bp, dvo_hip_frame* const* curs) {
+  return plan_paths(ctx, cfg, bp, window_taps_missing(cfg, bp, curs)).levels;
 }
 
 int run_resident(dvo_hip_context* ctx, Workspace& w, const dvo_hip_config* cfg, const BatchPlan& bp, const ResidentPlan& rp,
@@ -634,7 +637,7 @@ int prepare_batch(BatchRun& b, SlowLane& lane, dvo_hip_frame* const* refs, dvo_h
   make_plan(ctx, refs[0]->cam, cfg, n, bp);
   // The coarse levels -- for a small batch every level -- run inside ONE launch (align_resident.hip): no launch per iteration, no
   // host poll, the pairs of a batch do not wait for each other.
-  b.rp = plan_paths(ctx, cfg, bp, window_taps_missing(ctx, cfg, n, curs));
+  b.rp = plan_paths(ctx, cfg, bp, window_taps_missing(cfg, bp, curs));
   const bool tables_inline = b.rp.direct && n <= kResidentInline;   // plane pointers and initial guesses travel as kernel arguments
   int rc = prepare_buffers(w, cfg, refs, curs, bp, !tables_inline);
   if (rc != DVO_HIP_OK) return rc;
@@ -757,7 +760,7 @@ void enqueue_step_in_sweep(BatchRun& b, const LevelRun& L) {
   Range range(kRangeErr[L.level]);
   const SolverStepArgs a = make_solver_step_args(b.states, b.n, b.bp.prm, b.partials, b.ll_partials, L.schedule.ll_blocks, b.scratch, b.d_levels, b.d_iters, b.tallies + b.step,
                                                  w.host_status + b.step, b.cfg->first_level - L.level, &L.next, b.arrivals, L.pair_sums);
-  launch_residual_reduce(b.s, b.ctx->opt_variant, b.bp.rpw[L.level], L.level == 0, L.g, L.pp, b.states, b.n, b.partials, b.scratch, w.win_fallbacks.as<unsigned long long>(),
+  launch_residual_reduce(b.s, b.bp.choice[L.level], b.bp.rpw[L.level], L.level == 0, L.g, L.pp, b.states, b.n, b.partials, b.scratch, w.win_fallbacks.as<unsigned long long>(),
                          w.f16_range_flag, &a);
   if (L.pair_sums) {
     Range range2(kRangeLinsys[L.level]);
@@ -774,7 +777,7 @@ void enqueue_step(BatchRun& b, const LevelRun& L) {
   const bool fused_ll = L.schedule.fused_ll;
   {
     Range range(kRangeErr[L.level]);
-    launch_residual_reduce(b.s, ctx->opt_variant, b.bp.rpw[L.level], L.level == 0, L.g_run, L.pp, b.states, L.n_run, b.partials, b.scratch, w.win_fallbacks.as<unsigned long long>(),
+    launch_residual_reduce(b.s, b.bp.choice[L.level], b.bp.rpw[L.level], L.level == 0, L.g_run, L.pp, b.states, L.n_run, b.partials, b.scratch, w.win_fallbacks.as<unsigned long long>(),
                            w.f16_range_flag);
     if (b.ref_order) {
       launch_ref_order(b.s, L.g_run, b.states, L.n_run, b.scratch, w.ref_rows.as<RefOrderSeg>(), b.ref_order);
@@ -828,7 +831,7 @@ LevelRun begin_level(BatchRun& b, SlowLane& lane, int level) {
     L.next.results = b.w.results.as<dvo_hip_result>();         // the last level: a pair that has left it gets its result written
   }
   L.schedule = schedule_of(b, level);
-  L.tail = ctx->opt_sweep_tail != 0 && L.schedule.fused_ll && sweep_has_tail(ctx->opt_variant, bp.rpw[level], L.g);   // (enqueue_step_in_sweep)
+  L.tail = ctx->opt_sweep_tail != 0 && L.schedule.fused_ll && sweep_has_tail(bp.choice[level], bp.rpw[level], L.g.rcp_table != nullptr, L.g.gram_hi_j != 0);   // (enqueue_step_in_sweep)
   L.pair_sums = L.tail && ctx->opt_sweep_tail == 2 ? b.w.pair_sums.as<double>() : nullptr;
   L.g_run = L.g;
   L.n_run = n;
@@ -872,8 +875,8 @@ int chain_level(BatchRun& b, SlowLane& lane, int level) {
   }
   int watched = b.step - 1;                                  // last step of the chunk whose outcome is awaited
   // (the slow lane: every level but the last may shed its stragglers to it -- on the last one nothing follows that they could run beside)
-  const bool list_tails = ctx->opt_tail_lists != 0 && !b.bp.ref_order && !L.tail && !hand_over && sweep_takes_pair_list(ctx->opt_variant, b.bp.rpw[level], g);
-  const bool may_shed = lane.on() && level > cfg->last_level && !L.tail && sweep_takes_pair_list(ctx->opt_variant, b.bp.rpw[level], g);
+  const bool list_tails = ctx->opt_tail_lists != 0 && !b.bp.ref_order && !L.tail && !hand_over && b.bp.choice[level].pair_list;
+  const bool may_shed = lane.on() && level > cfg->last_level && !L.tail && b.bp.choice[level].pair_list;
   // Where an EMPTY step is expensive -- the dispatcher needs 95 us for the 307 200 workgroups of a 1024-pair finest-level sweep
   // that all exit at once, 114 us with its log-likelihood and solver launches -- the step ahead of the poll is not enqueued once
   // only a few pairs are left on the level: the host then waits for the outcome first (a bubble of ~15 us if another step is

@@ -10,6 +10,7 @@
 #include "cloud_colour.h"
 #include "cloud_normal.h"
 #include "map_render.h"
+#include "sweep_choice.h"
 
 #include "../../include/dvo_hip.h"
 
@@ -17,8 +18,7 @@ namespace dvo_hip {
 
 constexpr int kMaxLevels = DVO_HIP_MAX_LEVELS;
 constexpr int kBlock = 256;          // 4 wavefronts of 64
-constexpr int kWavesPerBlock = 4;
-constexpr int kTileW = 64;           // one wavefront spans 64 consecutive pixels of a row
+// (kWavesPerBlock, kTileW and kCompactTileEntries: sweep_choice.h)
 
 // Accumulator layout of the fused residual/Jacobian/reduce kernel (all float):
 //   0            n  (count of valid constraints)
@@ -106,7 +106,6 @@ struct NextLevel {
 
 // slot of the tile's partial row that holds count_0 + 512 count_1 (the next one: count_2 + 512 count_3), as exact floats
 constexpr int kAccCounts = kNumAcc;
-constexpr int kCompactTileEntries = 1024, kCompactWaveEntries = 256;
 
 // float2 entries of one pair's residual buffer at this level
 __host__ __device__ inline size_t residual_entries(const LevelGeom& g) {

@@ -11,7 +11,6 @@ namespace dvo_hip {
 
 constexpr int kFastTileRows = 16;                       // a 64 x 16 tile per workgroup, four rows per wavefront
 constexpr int kFastPitch = 96;                          // window pitch in cells (768 B: every window row starts at bank 0)
-constexpr int kFastCols = 84;                           // window columns in use: 64 + the taps' reach (3) + 17 of motion / parallax
 constexpr int kFastPairs = kFastCols / 2;               // 42 column pairs (16-byte loads)
 constexpr int kFastRows = 28;                           // window rows: 16 + the taps' reach (3) + 9
 constexpr int kFastRowGroups = 6;                       // 6 x 42 = 252 of the 256 threads fill the window, five rows each at most

@@ -179,39 +179,33 @@ struct PgResidentIteration;
 void launch_pg_resident(hipStream_t s, const PgResidentJob* jobs, int n_graphs, PgResidentOut* outs, PgResidentIteration* records, int max_records,
                         size_t stage_bytes);
 
-// align_kernels.hip / align_mfma.hip
-// variant 5 (default): Gram accumulation on the matrix cores (align_mfma.hip); variant 0: the all-VALU schedule with the DPP + LDS
-// two-stage reduction (align_kernels.hip).  Same outputs.
-void launch_residual_reduce(hipStream_t s, int variant, int rows_per_wave, bool finest_level, const LevelGeom& g, const PairPtrs* pairs,
-                            const PairState* states, int n_pairs, float* partials, float2* scratch, unsigned long long* window_fallbacks = nullptr,
-                            int* f16_range_flag = nullptr, const SolverStepArgs* tail = nullptr);
+// align_kernels.hip: the sweep of one level, by the kernel its SweepChoice names (sweep_choice.h; rows_per_wave: the plan's tile height,
+// choice.tile_rows where the kernel insists on one).  Same outputs whatever the kernel.
 // `tail` (non-null; only where sweep_has_tail says so): the workgroup that completes the last tile of a pair runs the pair's solver step
 // in the sweep's launch (solver_step.h) -- no launch_solver_step behind it
-bool sweep_has_tail(int variant, int rows_per_wave, const LevelGeom& g);
-bool sweep_fast_has_tail(int variant, const LevelGeom& g);
-bool mfma_sweep_has_tail(int variant, int rows_per_wave, const LevelGeom& g);
-// mode 0: f32 Gram (the f32 matrix instruction); 1: Gram accumulation on the f16 matrix pipe (gram_f16.h; variant 7); 2: 1 with the contracted
-// per-pixel arithmetic of align_fast.hip (variants 8 / 9 on the levels the window sweep does not take)
+void launch_residual_reduce(hipStream_t s, const SweepChoice& choice, int rows_per_wave, bool finest_level, const LevelGeom& g, const PairPtrs* pairs,
+                            const PairState* states, int n_pairs, float* partials, float2* scratch, unsigned long long* window_fallbacks = nullptr,
+                            int* f16_range_flag = nullptr, const SolverStepArgs* tail = nullptr);
+// align_mfma.hip: Gram accumulation on the matrix cores.  mode 0: f32 Gram (the f32 matrix instruction); 1: Gram accumulation on the f16
+// matrix pipe (gram_f16.h; variant 7); 2: 1 with the contracted per-pixel arithmetic of align_fast.hip (variants 8 / 9 on the levels the
+// window sweep does not take)
 void launch_residual_reduce_mfma(hipStream_t s, int rows_per_wave, bool finest_level, const LevelGeom& g, const PairPtrs* pairs,
                                  const PairState* states, int n_pairs, float* partials, float2* scratch, int mode = 0,
                                  int* f16_range_flag = nullptr, const SolverStepArgs* tail = nullptr);
 // align_window.hip: variants 6 (f32 Gram) and 7 (f16 hi/lo Gram) -- the current frame's {I, Z} window staged in LDS; tiled levels whose
-// width is a multiple of 64 only (window_sweep_supports), tile height 16 (rows_per_wave 4).  fallback_count (may be null): lanes
+// width is a multiple of 64 only, tile height 16 (rows_per_wave 4).  fallback_count (may be null): lanes
 // whose taps fell outside the staged window and were fetched from memory.  f16_range_flag (may be null; pinned host memory): set
 // to 1 by a workgroup of variant 7 whose Jacobian components left the f16 range -- the caller repeats the work with variant 6.
-bool window_sweep_supports(const LevelGeom& g);
 void launch_sweep_window(hipStream_t s, bool f16, const LevelGeom& g, const PairPtrs* pairs, const PairState* states, int n_pairs,
                          float* partials, float2* scratch, unsigned long long* fallback_count, int* f16_range_flag = nullptr);
 // align_fast.hip: variants 8 / 9 -- the window sweep with contracted per-pixel arithmetic (same function, rounding differences of a few
-// ulp against variants 6 / 7; window 84 x 28 cells at a pitch of 96; 8: high and low operand parts take turns in the slab, 9: side by side, moved with v_permlane32_swap).
-bool fast_sweep_takes_width(int w);   // (64-column tiles; a width that is no multiple of 64 leaves the last tile column partly empty)
-bool fast_sweep_supports(const LevelGeom& g);
-void launch_sweep_fast(hipStream_t s, int variant, const LevelGeom& g, const PairPtrs* pairs, const PairState* states, int n_pairs,
+// ulp against variants 6 / 7; window 84 x 28 cells at a pitch of 96; operand_store 2: high and low operand parts take turns in the slab,
+// 1: side by side, moved with v_permlane32_swap).
+void launch_sweep_fast(hipStream_t s, int operand_store, const LevelGeom& g, const PairPtrs* pairs, const PairState* states, int n_pairs,
                        float* partials, float2* scratch, unsigned long long* fallback_count, int* f16_range_flag = nullptr,
                        const SolverStepArgs* tail = nullptr);
 // align_small.hip: a level small enough for the whole current plane C to live in LDS ((w + 2) x (h + 2) cells of 8 B <= 43 KB, even width:
 // 80 x 60, 40 x 30 ...), walked linearly, rows_per_wave segments per wavefront and workgroup; contracted arithmetic, f16 Gram, residual pairs by pixel
-bool small_sweep_takes(int w, int h);
 void launch_sweep_small(hipStream_t s, int rows_per_wave, const LevelGeom& g, const PairPtrs* pairs, const PairState* states, int n_pairs,
                         float* partials, float2* scratch, int* f16_range_flag = nullptr);
 // scratch == null: read-only (one float per workgroup goes to `sink`, which must hold a float per (8 * 256)-pixel block)
@@ -233,7 +227,7 @@ hipError_t launch_match_resident(hipStream_t s, const ResidentArgs& args, bool c
 
 // align_coarse.hip: levels first_level..last_level of every pair in one launch, one workgroup per pair (no workgroup waits for another).
 // workgroups_per_cu: 4 (128 registers; default) or 3 (168)
-bool coarse_kernel_takes(const LevelGeom& g, bool window_level);
+bool coarse_kernel_takes(const SweepChoice& choice, const LevelGeom& g);
 hipError_t launch_match_coarse(hipStream_t s, const CoarseArgs& args, int workgroups_per_cu);
 
 // solver_kernels.hip
@@ -250,8 +244,7 @@ void launch_level_begin(hipStream_t s, PairState* states, int n_pairs, SolverPar
 // list_only: nothing is flagged; the list gets the unflagged pairs active on the level (flags may be null) -- the active-pair list of a level's last steps
 void launch_mark_stragglers(hipStream_t s, const PairState* states, int n_pairs, int level, unsigned char* flags, int* list, int cap, bool list_only = false);
 void launch_clear_flags(hipStream_t s, unsigned char* flags, int n_pairs);
-// ... which the sweep of the level must understand (the contracted window sweep and the gathering sweep of the default schedule do)
-bool sweep_takes_pair_list(int variant, int rows_per_wave, const LevelGeom& g);
+// ... which the sweep of the level must understand (SweepChoice::pair_list: the contracted window sweep and the gathering sweep of the default schedule do)
 void launch_solver_step(hipStream_t s, PairState* states, int n_pairs, SolverParams prm, LevelGeom g,
                         const float* partials, const double* ll_partials, int ll_blocks_per_pair, const float2* scratch_for_fused_ll,
                         dvo_hip_level_stats* levels, dvo_hip_iteration_stats* iters, unsigned long long* step_tally,

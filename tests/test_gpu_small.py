@@ -2,12 +2,14 @@
 default schedule's 80 x 60 / 40 x 30 levels -- what the contracted window sweep does not take -- against the gathering sweep they ran
 until round 6 and against the oracle.  Same function (dvo_core/src/dense_tracking_impl.cpp:148-281, dense_tracking.cpp:448-476), a few
 ulp apart in the blended gradients: one linearisation within the default schedule's bounds, whole matches to the stopping rule's precision."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 import common as cm
 import dvo_slam_amd as d
-from dvo_slam_amd import datagen
+from dvo_slam_amd import _lib, datagen
 from oracle import pyoracle as po
 from test_gpu_coarse import frames_of
 
@@ -94,3 +96,72 @@ def test_frames_carry_plane_c_of_their_small_levels_in_the_flavour_their_batch_r
         assert cm.twist_matrix_error(many["T"][k], small["T"][i]) < 2e-6
     again = trk.match_batch_arrays(refs, curs)
     assert np.array_equal(again["T"], small["T"])
+
+
+SCHEDULES = [dict(variant=8), dict(variant=5), dict(variant=7), dict(variant=8, small_sweep=1), dict(variant=0), dict(variant=6), dict(variant=9),
+             dict(variant=8, ref_compat=1), dict(variant=8)]
+# two cameras whose levels are every kind a schedule tells apart: a multiple of 64, even widths from 84 on, a small even one, an odd one
+CAMERAS = [(192, 80, 3), (170, 66, 2)]                           # 192 x 80, 96 x 40, 48 x 20; 170 x 66, 85 x 33
+
+
+def set_schedule(ctx, schedule, resident):
+    for key in ("variant", "small_sweep", "ref_compat"):
+        ctx.set_option(key, schedule.get(key, 8 if key == "variant" else 0))
+    if resident is not None:
+        ctx.set_option("resident", resident)
+
+
+def match_bytes(ctx, frames):
+    """Whole matches of each camera's pairs through the C-ABI: the results and the level and iteration records a pair wrote, as bytes."""
+    out = []
+    for (w, h, levels), (refs, curs) in zip(CAMERAS, frames):
+        n, cfg = len(refs), d.Config(FirstLevel=levels - 1, LastLevel=0)
+        nl, cap_it = levels, levels * cfg.MaxIterationsPerLevel
+        cres, lv, it = (_lib.Result * n)(), (_lib.LevelStats * (n * nl))(), (_lib.IterationStats * (n * cap_it))()
+        for i in range(n):
+            cres[i].transformation[:] = list(np.eye(4).reshape(16))
+        vp = C.c_void_p
+        ccfg = cfg.to_c()
+        ctx.check(ctx._lib.dvo_hip_match_batch(ctx.ptr, n, (vp * n)(*[p.ptr for p in refs]), (vp * n)(*[p.ptr for p in curs]), C.byref(ccfg),
+                                               cres, lv, nl, it, cap_it))
+        for i in range(n):
+            assert cres[i].n_levels == nl and 0 < cres[i].n_iterations_total <= cap_it
+            out.append((bytes(cres[i]), b"".join(bytes(x) for x in lv[i * nl:(i + 1) * nl]),
+                        b"".join(bytes(x) for x in it[i * cap_it:i * cap_it + cres[i].n_iterations_total])))
+    return out
+
+
+def camera_frames(ctx, batches):
+    frames = []
+    for (w, h, levels), b in zip(CAMERAS, batches):
+        refs, curs = frames_of(ctx, b, w, h, levels, 2)
+        for f in refs + curs:
+            f.build(levels)
+        frames.append((refs, curs))
+    return frames
+
+
+@pytest.mark.parametrize("resident", [0, None])
+def test_one_set_of_frames_through_every_schedule_in_turn(resident):
+    """Two pairs on each of two cameras, the SAME frame objects in one context, through a sequence of schedules that read different
+    flavours of the current role (taps A + B, plane C) on different levels: after every change of schedule the results and the level and
+    iteration records are byte for byte those of freshly created frames in a fresh context under that schedule alone -- a flavour left
+    over from another schedule is never read in place of the one the current schedule needs.  Once on the launch path (option "resident"
+    0), once with the default paths."""
+    batches = [datagen.synth_batch(5200 + w, 2, w, h) for w, h, _ in CAMERAS]
+    ctx = d.Context(0)
+    frames = camera_frames(ctx, batches)
+    fresh = {}
+    for step, schedule in enumerate(SCHEDULES):
+        key = tuple(sorted(schedule.items()))
+        if key not in fresh:
+            alone = d.Context(0)
+            set_schedule(alone, schedule, resident)
+            fresh[key] = match_bytes(alone, camera_frames(alone, batches))
+        set_schedule(ctx, schedule, resident)
+        got = match_bytes(ctx, frames)
+        for pair, (a, b) in enumerate(zip(got, fresh[key])):
+            for what, x, y in zip(("result", "level records", "iteration records"), a, b):
+                assert x == y, "step %d (%s), pair %d: %s differ from a fresh context's" % (step + 1, schedule, pair, what)
+    if resident == 0:                                             # (the schedules are not one computation under nine names)
+        assert len({tuple(v) for v in fresh.values()}) >= 3
