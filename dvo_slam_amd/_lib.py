@@ -90,6 +90,12 @@ class WarpParams(C.Structure):
 WARP_MODES = {"nearest": 0, "splat": 1}
 
 
+class CovisParams(C.Structure):
+    """dvo_hip_covis_params: how the pixels of a keyframe pair are classified (dvo_hip_frames_covisibility)."""
+    _fields_ = [("depth_tolerance", C.c_float), ("depth_tolerance_rel", C.c_float), ("min_depth", C.c_float), ("max_depth", C.c_float),
+                ("reserved", C.c_uint32 * 4)]
+
+
 class GraphParams(C.Structure):
     """dvo_hip_graph_params: the schedule of a pose-graph optimisation (dvo_hip_graph_optimize)."""
     _fields_ = [("max_iterations", C.c_int32), ("cg_max_iterations", C.c_int32), ("cg_tolerance", C.c_double),
@@ -141,6 +147,7 @@ EXPORTS = [
     "dvo_hip_frames_normals", "dvo_hip_map_extract_normals", "dvo_hip_map_render_normals", "dvo_hip_map_export_ex",
     "dvo_hip_map_merge_records_ex",
     "dvo_hip_warp_params_default", "dvo_hip_frames_warp_inverse", "dvo_hip_frames_warp_forward",
+    "dvo_hip_covis_params_default", "dvo_hip_frames_covisibility",
     "dvo_hip_graph_create", "dvo_hip_graph_destroy", "dvo_hip_graph_set_vertices", "dvo_hip_graph_set_poses", "dvo_hip_graph_set_edges",
     "dvo_hip_graph_params_default", "dvo_hip_graph_optimize", "dvo_hip_graph_get_poses", "dvo_hip_graph_edge_stats",
     "dvo_hip_graph_linearise", "dvo_hip_graph_multiply", "dvo_hip_graph_optimize_batch",
@@ -168,6 +175,9 @@ MAP_RECORD = [("key", "<u8"), ("n", "<u4"), ("sx", "<u4"), ("sy", "<u4"), ("sz",
 MAP_COLOUR_RECORD = [("sr", "<u4"), ("sg", "<u4"), ("sb", "<u4"), ("pad", "<u4")]
 # ... and its normal record (16: cloud_normal.h, MapNormalSlot; dvo_hip_map_export_ex / dvo_hip_map_merge_records_ex)
 MAP_NORMAL_RECORD = [("snx", "<u4"), ("sny", "<u4"), ("snz", "<u4"), ("nn", "<u4")]
+# the record of one keyframe pair (32 bytes: dvo_hip_covis_record; dvo_hip_frames_covisibility)
+COVIS_RECORD = [("valid", "<u4"), ("in_view", "<u4"), ("unknown", "<u4"), ("occluded", "<u4"), ("seen_through", "<u4"), ("consistent", "<u4"),
+                ("photo", "<u8")]
 COMM_ID_BYTES = 128
 
 
@@ -311,6 +321,11 @@ def lib():
         L.dvo_hip_warp_params_default.restype = WarpParams
         L.dvo_hip_frames_warp_inverse.argtypes = [vp, C.c_int, pp, pp, dp, C.c_int, wp, pp, pp, pp, C.c_int]
         L.dvo_hip_frames_warp_forward.argtypes = [vp, C.c_int, pp, dp, C.c_int, wp, pp, pp, C.c_int]
+    if hasattr(L, "dvo_hip_frames_covisibility"):   # (likewise: an older build counts no covisibility)
+        dp, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        L.dvo_hip_covis_params_default.argtypes = []
+        L.dvo_hip_covis_params_default.restype = CovisParams
+        L.dvo_hip_frames_covisibility.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_int, i32p, i32p, dp, C.c_int, C.POINTER(CovisParams), vp, C.c_int]
     if hasattr(L, "dvo_hip_graph_create"):   # (likewise: an older build optimises no pose graph)
         dp, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         L.dvo_hip_graph_create.argtypes = [vp, C.POINTER(vp)]

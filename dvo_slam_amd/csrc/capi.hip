@@ -423,6 +423,7 @@ struct dvo_hip_context {
   long long graph_resident_solves = 0;
   long long map_renders = 0;       // views rendered out of a keyframe map (dvo_hip_map_render, dvo_hip_map_render_frames), counter "map_renders"
   long long frame_warps = 0;       // items warped (dvo_hip_frames_warp_inverse, dvo_hip_frames_warp_forward), counter "frame_warps"
+  long long covisibility_pairs = 0;   // pairs counted (dvo_hip_frames_covisibility), counter "covisibility_pairs"
   // Option "defer_ingest": a batched re-ingest (dvo_hip_frames_update_raw_device_as) is only recorded, and carried out by the next
   // dvo_hip_match_batch right behind the first launches of its first level (or by whatever entry point comes first).  A streaming
   // caller re-ingests the next batch and then aligns the current one: enqueueing the ingest first keeps the alignment's stream idle
@@ -986,6 +987,7 @@ int prepare_roles(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* fram
 #include "capi_colour.inc"   // the colour of frames: dvo_hip_frames_set_colour, dvo_hip_frames_clear_colour, dvo_hip_frame_download_colour
 #include "capi_normal.inc"   // surface normals: dvo_hip_frames_normals, dvo_hip_map_extract_normals, dvo_hip_map_render_normals
 #include "capi_warp.inc"     // frames warped under a pose: dvo_hip_frames_warp_inverse, dvo_hip_frames_warp_forward
+#include "capi_covis.inc"    // keyframe covisibility: dvo_hip_frames_covisibility
 #include "capi_graph.inc"    // the keyframe pose graph: dvo_hip_graph_*
 
 int dvo_hip_upload_wait(dvo_hip_context* ctx) {

@@ -45,6 +45,7 @@ int dvo_hip_get_counter(dvo_hip_context* ctx, const char* key, long long* value)
   else if (std::strcmp(key, "map_rehashes") == 0) *value = ctx->map_rehashes;
   else if (std::strcmp(key, "map_renders") == 0) *value = ctx->map_renders;
   else if (std::strcmp(key, "frame_warps") == 0) *value = ctx->frame_warps;
+  else if (std::strcmp(key, "covisibility_pairs") == 0) *value = ctx->covisibility_pairs;
   else if (std::strcmp(key, "map_points") == 0) *value = ctx->map_points;
   else if (std::strcmp(key, "map_dropped") == 0) *value = ctx->map_dropped;
   else if (std::strcmp(key, "graph_resident_solves") == 0) *value = ctx->graph_resident_solves;

@@ -265,6 +265,12 @@ struct WarpPlanes {
   float* Z;
   float* D;                            // the difference plane; null: not wanted
 };
+// one ordered pair of a covisibility launch (k_covisibility, covisibility.hip; include/dvo_hip.h, dvo_hip_frames_covisibility): the
+// entries of the launch's frame table whose surface is carried (a) and which is looked into (b), and T, a's camera -> b's camera
+struct CovisPair {
+  int a, b;
+  MapPose T;
+};
 // (kMapCntOverLimit .. kMapCntVacant are what a pass of k_map_extract counts: contiguous, zeroed before every pass.  kMapCntRemoving: the
 // usable points in range of the frames a launch subtracts -- its kMapCntCandidates; kMapCntUnmatched of them found no voxel to leave)
 constexpr int kMapCntCandidates = 0, kMapCntDropped = 1, kMapCntOutOfRange = 2, kMapCntUnusable = 3, kMapCntUpdates = 4, kMapCntOccupied = 5,

@@ -154,6 +154,12 @@ void launch_warp_inverse(hipStream_t s, const MapFrame* tbl, const WarpPlanes* o
 void launch_warp_forward(hipStream_t s, const MapFrame* tbl, int n, long long pixels, int mode, float min_depth, float max_depth,
                          unsigned long long* zbuf);
 
+// covisibility.hip: keyframe covisibility (covisibility.h).  n pairs over the frame table tbl (every pair's a and b index it; no pose of
+// it is read); max_pixels: the largest w * h of the pairs' a; records: n records of four 64-bit words (dvo_hip_covis_record), 8-byte
+// aligned and ZEROED on the stream s before the launch, which only adds to them.
+void launch_covisibility(hipStream_t s, const MapFrame* tbl, const CovisPair* pairs, int n, long long max_pixels, const dvo_hip_covis_params& par,
+                         unsigned long long* records);
+
 // pose_graph.hip: the stages of the pose-graph optimiser (pose_graph.h), kPgBlock edges or vertices per workgroup.  *_partials: one
 // double per workgroup, a subtree of the scalar's tree (rz_partials: two rows of them).  launch_pg_linearise: every edge's record at
 // `poses` (with_blocks: the weighted blocks too) and the partials of the cost.  launch_pg_gather: D and b of every vertex and each

@@ -922,6 +922,180 @@ def warp_forward_batch(pyramids, transforms, level=0, mode="splat", min_depth=0.
     return tuple(out)
 
 
+COVIS_DTYPE = np.dtype(_lib.COVIS_RECORD)                         # dvo_hip_covis_record: 32 bytes
+COVIS_MAX_PAIRS = 1 << 22                                         # what one dvo_hip_frames_covisibility call takes
+_COVIS_POSES = dict(per="pair", counted="pairs", maps="a's camera -> b's camera", finite=True)   # covisibility_batch
+
+
+def covis_params_struct(depth_tolerance=0.05, depth_tolerance_rel=0.0, min_depth=0.0, max_depth=float("inf")):
+    """dvo_hip_covis_params from its fields (the defaults: dvo_hip_covis_params_default), or ValueError / TypeError: nothing reaches the
+    library with a value it would refuse."""
+    try:
+        tol, rel, lo, hi = float(depth_tolerance), float(depth_tolerance_rel), float(min_depth), float(max_depth)
+    except (TypeError, ValueError):
+        raise TypeError("covisibility: depth_tolerance, depth_tolerance_rel, min_depth and max_depth must be real numbers")
+    if not tol >= 0.0 or not rel >= 0.0:
+        raise ValueError("covisibility: the depth tolerances must be >= 0 (no NaN)")
+    if not lo <= hi:
+        raise ValueError("covisibility: need min_depth <= max_depth (no NaN)")
+    out = _lib.CovisParams()
+    out.depth_tolerance, out.depth_tolerance_rel, out.min_depth, out.max_depth = tol, rel, lo, hi
+    return out
+
+
+def _covis_args(pyramids, pairs, transforms, level, who):
+    """(pairs as a contiguous [n, 2] int32 array, transforms as a contiguous [n, 4, 4] float64 array) of a covisibility call, or
+    ValueError / TypeError: nothing reaches the library with no pyramids or pairs, too many pairs, an index that names no pyramid, a
+    transform that is not 4 x 4 or not finite, a level a pyramid does not have or pyramids of different contexts."""
+    if len(pyramids) < 1:
+        raise ValueError("%s: no pyramids" % who)
+    try:
+        P = np.asarray(pairs)
+    except (TypeError, ValueError):
+        raise TypeError("%s: pairs must be integers, one (a, b) per pair" % who)
+    if P.dtype == bool or not np.issubdtype(P.dtype, np.integer):
+        if P.size or P.dtype == bool:
+            raise TypeError("%s: pairs must be integers, one (a, b) per pair" % who)
+    if P.ndim == 1 and P.shape[0] == 2:
+        P = P[None]
+    if P.ndim != 2 or P.shape[1] != 2 or P.shape[0] < 1:
+        raise ValueError("%s: pairs is an [n, 2] array of indices (a, b), n >= 1, got shape %s" % (who, P.shape))
+    if P.shape[0] > COVIS_MAX_PAIRS:
+        raise ValueError("%s: %d pairs, one call takes %d" % (who, P.shape[0], COVIS_MAX_PAIRS))
+    if P.min() < 0 or P.max() >= len(pyramids):
+        raise ValueError("%s: a pair names a pyramid outside 0 .. %d" % (who, len(pyramids) - 1))
+    T = _pose_array(transforms, P.shape[0], who, **_COVIS_POSES)
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+        raise TypeError("%s: level must be an integer" % who)
+    for p in pyramids:
+        if not 0 <= level < p.levels:
+            raise ValueError("%s: a pyramid of %d levels has no level %d" % (who, p.levels, level))
+        if p.ctx is not pyramids[0].ctx:
+            raise ValueError("%s: the pyramids belong to different contexts" % who)
+    return np.ascontiguousarray(P, np.int32), T
+
+
+def covisibility_batch(pyramids, pairs, transforms, level=2, depth_tolerance=0.05, depth_tolerance_rel=0.0, min_depth=0.0,
+                       max_depth=float("inf"), device=False):
+    """How much of one keyframe's surface another keyframe also sees, for many ordered pairs in one launch
+    (dvo_hip_frames_covisibility; dvo_slam_amd/csrc/covisibility.h).  pairs: [n, 2] indices (a, b) into pyramids; transforms: [n, 4, 4],
+    a's camera -> b's camera (for poses camera -> world: inv(pose_b) @ pose_a).  Every pixel of a with a depth in [min_depth, max_depth]
+    counts as `valid`; carried into b's camera it is `in_view` when its nearest pixel lies in b's image, and there `unknown` (b has no
+    depth), `occluded` (b sees a nearer surface), `seen_through` (b sees past it: a free-space conflict) or `consistent` (b's depth
+    agrees within depth_tolerance + depth_tolerance_rel * depth), where `photo` sums |I_a - I_b| in sixteenths of a grey level.
+    Returns a COVIS_DTYPE array of n records; device=True: a torch uint8 tensor [n, 32] on the GPU holding the same bytes.  a and b
+    may differ in size and camera; a == b is allowed."""
+    who = "covisibility_batch"
+    P, T = _covis_args(pyramids, pairs, transforms, level, who)
+    params = covis_params_struct(depth_tolerance, depth_tolerance_rel, min_depth, max_depth)
+    ctx = pyramids[0].ctx
+    n = P.shape[0]
+    if device:
+        import torch
+        out = torch.empty((n, COVIS_DTYPE.itemsize), dtype=torch.uint8, device="cuda:%d" % ctx.device)
+    else:
+        out = np.empty(n, COVIS_DTYPE)
+    a, b = np.ascontiguousarray(P[:, 0]), np.ascontiguousarray(P[:, 1])
+    i32p = C.POINTER(C.c_int32)
+    ctx.check(ctx._lib.dvo_hip_frames_covisibility(ctx.ptr, len(pyramids), _handles(pyramids), n, a.ctypes.data_as(i32p), b.ctypes.data_as(i32p),
+                                                   T.ctypes.data_as(C.POINTER(C.c_double)), int(level), C.byref(params),
+                                                   C.c_void_p(_address(out)), 1 if device else 0))
+    return out
+
+
+def _covis_poses(pyramids, poses, who):
+    """poses of keyframes as a [n, 4, 4] float64 array (camera -> world) and their inverses, or ValueError / TypeError"""
+    if len(pyramids) < 1:
+        raise ValueError("%s: no pyramids" % who)
+    T = _pose_array(poses, len(pyramids), who, finite=True)
+    try:
+        return T, np.linalg.inv(T)
+    except np.linalg.LinAlgError:
+        raise ValueError("%s: a pose is singular" % who)
+
+
+def covisibility_matrix(pyramids, poses, level=2, depth_tolerance=0.05, depth_tolerance_rel=0.0, min_depth=0.0, max_depth=float("inf"),
+                        batch=None):
+    """The covisibility of ALL ordered pairs of n keyframes under their poses ([n, 4, 4], camera -> world), the diagonal included, in
+    one call: an [n, n] COVIS_DTYPE array whose entry [a, b] is a's surface as b sees it, T_ab = inv(pose_b) @ pose_a in float64 on the
+    host.  overlap(M, M.T) is the symmetric overlap of every two keyframes.  batch: the function that counts (covisibility_batch; the
+    tests put the host build of covisibility.h in its place)."""
+    who = "covisibility_matrix"
+    T, Tinv = _covis_poses(pyramids, poses, who)
+    n = len(pyramids)
+    a, b = (x.reshape(-1) for x in np.mgrid[0:n, 0:n])
+    rec = (batch or covisibility_batch)(pyramids, np.stack([a, b], 1), Tinv[b] @ T[a], level=level, depth_tolerance=depth_tolerance,
+                                        depth_tolerance_rel=depth_tolerance_rel, min_depth=min_depth, max_depth=max_depth)
+    return np.asarray(rec).reshape(n, n)
+
+
+def overlap(records_ab, records_ba):
+    """min(consistent_ab / valid_a, consistent_ba / valid_b) in float64, elementwise: the share of each keyframe's surface the other one
+    confirms, the smaller of the two -- 0 where either keyframe has no valid pixel."""
+    ab, ba = np.asarray(records_ab), np.asarray(records_ba)
+    if ab.dtype != COVIS_DTYPE or ba.dtype != COVIS_DTYPE:
+        raise TypeError("overlap: records are COVIS_DTYPE arrays (covisibility_batch, covisibility_matrix)")
+    if ab.shape != ba.shape:
+        raise ValueError("overlap: the two directions differ in shape, %s and %s" % (ab.shape, ba.shape))
+
+    def share(r):
+        valid = r["valid"].astype(np.float64)
+        return np.where(valid > 0, r["consistent"].astype(np.float64) / np.where(valid > 0, valid, 1.0), 0.0)
+
+    both = (ab["valid"] > 0) & (ba["valid"] > 0)
+    return np.where(both, np.minimum(share(ab), share(ba)), 0.0)
+
+
+def radius_set(poses, query, max_distance):
+    """The keyframes the reference's NearestNeighborConstraintSearch::findPossibleConstraints proposes for keyframe `query`: those whose
+    translation lies within max_distance of the query's, the query itself included, in index order.  As the reference's radius search:
+    float32 translations, squared distance <= max_distance squared."""
+    t = np.ascontiguousarray(np.asarray(poses, np.float64)[:, :3, 3], np.float32)
+    d = t - t[query]
+    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+    return np.nonzero(d2 <= np.float32(float(max_distance) * float(max_distance)))[0]
+
+
+def loop_closure_candidates(pyramids, poses, query, max_distance, min_overlap=0.0, level=2, depth_tolerance=0.05, depth_tolerance_rel=0.0,
+                            min_depth=0.0, max_depth=float("inf"), batch=None):
+    """The keyframes to validate keyframe `query` against: the reference's radius test on the translations (radius_set: the query itself
+    passes it, as in the reference), then the covisibility of the survivors with the query in both directions, in ONE call, and of
+    those the indices with overlap >= min_overlap, ordered by overlap descending and by index on ties.  poses: [n, 4, 4], camera ->
+    world.  batch: as covisibility_matrix."""
+    who = "loop_closure_candidates"
+    T, Tinv = _covis_poses(pyramids, poses, who)
+    n = len(pyramids)
+    if isinstance(query, bool) or not isinstance(query, (int, np.integer)):
+        raise TypeError("%s: query must be an integer" % who)
+    if not 0 <= query < n:
+        raise ValueError("%s: query names no pyramid of 0 .. %d" % (who, n - 1))
+    try:
+        radius, least = float(max_distance), float(min_overlap)
+    except (TypeError, ValueError):
+        raise TypeError("%s: max_distance and min_overlap must be real numbers" % who)
+    if not radius >= 0.0:
+        raise ValueError("%s: max_distance must be >= 0 (no NaN)" % who)
+    if not 0.0 <= least <= 1.0:
+        raise ValueError("%s: min_overlap is a share, 0 .. 1 (no NaN)" % who)
+    covis_params_struct(depth_tolerance, depth_tolerance_rel, min_depth, max_depth)
+    near = radius_set(T, query, radius)
+    if near.size == 0:
+        return np.zeros(0, np.int64)
+    # the frames of the call: the survivors and the query, each once
+    used = sorted(set(near.tolist()) | {int(query)})
+    at = {k: i for i, k in enumerate(used)}
+    q = np.full(near.size, at[int(query)])
+    j = np.array([at[int(k)] for k in near])
+    pairs = np.concatenate([np.stack([q, j], 1), np.stack([j, q], 1)])
+    transforms = np.concatenate([Tinv[near] @ T[query], Tinv[query] @ T[near]])
+    rec = np.asarray((batch or covisibility_batch)([pyramids[k] for k in used], pairs, transforms, level=level, depth_tolerance=depth_tolerance,
+                                                   depth_tolerance_rel=depth_tolerance_rel, min_depth=min_depth, max_depth=max_depth))
+    share = overlap(rec[:near.size], rec[near.size:])
+    keep = share >= least
+    order = np.lexsort((near[keep], -share[keep]))
+    return near[keep][order].astype(np.int64)
+
+
 def _rehash_capacity(capacity):
     """the capacity_slots of dvo_hip_map_rehash (None: 0, keep), or ValueError / TypeError"""
     if capacity is None:

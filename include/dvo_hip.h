@@ -720,6 +720,53 @@ int dvo_hip_frames_warp_forward(dvo_hip_context* ctx, int n, dvo_hip_frame* cons
                                 const dvo_hip_warp_params* params_or_null, float* const* intensity_out, float* const* depth_out,
                                 int out_on_device);
 
+/* ---- keyframe covisibility: loop-closure candidates counted on the device ---------------------------------------------------------------------
+ * Which keyframes a new keyframe should be validated against.  The reference asks only how far apart the cameras stand:
+ * NearestNeighborConstraintSearch::findPossibleConstraints (dvo_slam/src/keyframe_constraint_search.cpp:41-72, called from
+ * dvo_slam/src/keyframe_graph.cpp:233 and :456) radius-searches the keyframes' translations and hands every hit to the validator.  This
+ * call counts, for many ordered keyframe pairs in ONE launch, how much of one frame's surface the other frame also sees, and downloads
+ * nothing but a 32-byte record per pair: a proposal (dvo_slam::CovisibilityConstraintSearch, include/dvo_slam/keyframe_covisibility.h), a
+ * ranking of relocalisation candidates, which sub-maps overlap before a dvo_hip_map_merge, which keyframes are redundant.  All arithmetic
+ * is float32 and stated once in dvo_slam_amd/csrc/covisibility.h, whose host build the device records EQUAL (every output is an integer).
+ *   pair         (a, b, T): a = frames[pair_a[k]], b = frames[pair_b[k]], T = transforms[16 k ..], the row-major 4 x 4 double that carries
+ *                a's camera into b's camera, rounded to float once per pair, its linear part applied as given.  a and b are taken at
+ *                `level` with their own sizes and intrinsics: the two need not agree in size or camera.  a == b is allowed.
+ *   per pixel    of a with depth z and intensity I_a: skipped unless z is finite and > 0 and within [min_depth, max_depth] (0 and
+ *                +INFINITY: off); else `valid`.  p = T (((x - ox_a) / fx_a) z, ((y - oy_a) / fy_a) z, z); nothing more unless p.z is
+ *                finite and > 0.  u = (p.x fx_b) / p.z + ox_b, v likewise; the NEAREST pixel (floor(u + 0.5), floor(v + 0.5)) -- integer
+ *                coordinates are pixel centres -- and nothing more unless it lies in b's image; else `in_view`.  Z_b there not finite:
+ *                `unknown`.  Else with tol = depth_tolerance + depth_tolerance_rel p.z and d = Z_b - p.z: d < -tol `occluded` (b sees
+ *                a nearer surface), d > tol `seen_through` (b sees past the point: a free-space conflict -- a pose error or something that
+ *                moved), else `consistent` and photo += q(|I_a - I_b|), q(e) = (uint32)(e 16 + 0.5) for e < 4096, else (NaN too) 65535.
+ *   record       in_view == unknown + occluded + seen_through + consistent, in_view <= valid.  consistent / valid is the share of a's
+ *                surface b confirms; photo / (16 consistent) the mean absolute intensity difference over it, in grey levels.
+ *   streams      as dvo_hip_frames_world_points: one launch on the context's main stream behind the builds of the frames, recorded
+ *                (deferred) ingests are carried out first, and the call waits for that stream: host AND device records are complete
+ *                on return.  Every distinct frame is uploaded once, whatever the number of pairs.
+ *   refusals     DVO_HIP_ERR_INVALID, nothing launched, no output touched, no counter moved: null pointers; n_frames or n_pairs <= 0; more
+ *                than 2^22 pairs (checked before any pair is read); a null or foreign frame; a level a frame does not have; too many
+ *                pixels for one call (the blocks of 256 pixels of the listed frames exceed 2^31 / 256); an index outside [0, n_frames);
+ *                a transform that is not finite; a tolerance that is negative or NaN; min_depth > max_depth or a NaN bound; a reserved
+ *                field that is not 0; device records that are not 8-byte aligned.
+ *   cost         profiles/covisibility.md.  Counter "covisibility_pairs" counts pairs. */
+typedef struct dvo_hip_covis_params {
+  float depth_tolerance;      /* metres; >= 0 */
+  float depth_tolerance_rel;  /* added per metre of p.z; >= 0 */
+  float min_depth, max_depth; /* of a's depth; 0 and +INFINITY: off */
+  uint32_t reserved[4];       /* 0 */
+} dvo_hip_covis_params;       /* 32 B */
+typedef struct dvo_hip_covis_record {
+  uint32_t valid, in_view, unknown, occluded, seen_through, consistent;
+  uint64_t photo;
+} dvo_hip_covis_record;       /* 32 B */
+/* depth_tolerance 0.05f, depth_tolerance_rel 0, min_depth 0, max_depth +INFINITY */
+dvo_hip_covis_params dvo_hip_covis_params_default(void);
+/* Pair k: frames[pair_a[k]] seen by frames[pair_b[k]] under transforms[16 k ..] at `level` into records_out[k]; host memory, or device
+ * memory (8-byte aligned) with out_on_device.  params NULL: the defaults. */
+int dvo_hip_frames_covisibility(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, int n_pairs, const int32_t* pair_a,
+                                const int32_t* pair_b, const double* transforms /* n_pairs x 16 */, int level,
+                                const dvo_hip_covis_params* params_or_null, dvo_hip_covis_record* records_out, int out_on_device);
+
 /* ---- colour in the keyframe map: frames keep RGB, voxels fuse it -------------------------------------------------------------------------
  * The reference's map is coloured: dvo_benchmark/src/benchmark_slam.cpp:89-90 keeps the camera image in level(0).rgb,
  * AsyncPointCloudBuilder::BuildJob::build (dvo_core/src/visualization/async_point_cloud_builder.cpp:72-104) writes p.b, p.g, p.r from it
@@ -1135,6 +1182,7 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value);
  * none of them,
  * "map_renders" (views dvo_hip_map_render and dvo_hip_map_render_frames have rendered; a refused call counts nothing),
  * "frame_warps" (items dvo_hip_frames_warp_inverse and dvo_hip_frames_warp_forward have warped; a refused call counts nothing),
+ * "covisibility_pairs" (pairs dvo_hip_frames_covisibility has counted; a refused call counts nothing),
  * "warmup_wait_us" (the longest of the nine stream waits dvo_hip_context_create makes on trivial commands to warm up the runtime's wait
  * path, in microseconds: the first GPU process on a fresh box has been seen to spend 14-24 ms in its first wait),
  * "host_batches" and "host_ns_prepare" / "host_ns_enqueue" / "host_ns_wait" / "host_ns_finish" (nanoseconds the calling thread spent
