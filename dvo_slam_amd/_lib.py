@@ -121,6 +121,14 @@ GRAPH_MAX_VERTICES, GRAPH_MAX_EDGES = 1 << 20, 1 << 22
 # a resident-sized graph (pose_graph.h: kPgResidentMaxVertices, kPgResidentMaxEdges): what dvo_hip_graph_optimize_batch takes
 GRAPH_RESIDENT_MAX_VERTICES, GRAPH_RESIDENT_MAX_EDGES = 1024, 4096
 
+class DepthFilter(C.Structure):
+    """dvo_hip_depth_filter: smoothing window (radius, sigma_space), noise model sigma(z) = noise_a + noise_b z^2 and its gate, edge
+    rejection (edge_radius, tau(z) = edge_abs + edge_rel z), hole-border erosion (hole_radius)."""
+    _fields_ = [("radius", C.c_int32), ("sigma_space", C.c_float), ("noise_a", C.c_float), ("noise_b", C.c_float), ("gate", C.c_float),
+                ("edge_radius", C.c_int32), ("edge_abs", C.c_float), ("edge_rel", C.c_float), ("hole_radius", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
 # every symbol include/dvo_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "dvo_hip_context_create", "dvo_hip_context_destroy", "dvo_hip_last_error", "dvo_hip_context_stream",
@@ -138,6 +146,7 @@ EXPORTS = [
     "dvo_hip_frames_update_colour_f32depth_device_as_ex", "dvo_hip_frames_update_colour_f32depth_as_ex",
     "dvo_hip_frames_set_lens", "dvo_hip_frames_clear_lens",
     "dvo_hip_frames_set_depth_rig", "dvo_hip_frames_clear_depth_rig",
+    "dvo_hip_frames_set_depth_filter", "dvo_hip_frames_clear_depth_filter", "dvo_hip_depth_filter_default",
     "dvo_hip_map_create", "dvo_hip_map_destroy", "dvo_hip_map_clear", "dvo_hip_map_insert", "dvo_hip_map_stats", "dvo_hip_map_extract",
     "dvo_hip_frames_world_points", "dvo_hip_map_remove", "dvo_hip_map_move", "dvo_hip_map_rehash",
     "dvo_hip_render_params_default", "dvo_hip_map_render", "dvo_hip_map_render_frames", "dvo_hip_time_map_render",
@@ -272,6 +281,11 @@ def lib():
     if hasattr(L, "dvo_hip_frames_set_depth_rig"):   # (likewise: an older build has no depth rig)
         L.dvo_hip_frames_set_depth_rig.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(DepthRig)]
         L.dvo_hip_frames_clear_depth_rig.argtypes = [vp, C.c_int, C.POINTER(vp)]
+    if hasattr(L, "dvo_hip_frames_set_depth_filter"):   # (likewise: an older build has no depth filter)
+        L.dvo_hip_frames_set_depth_filter.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(DepthFilter)]
+        L.dvo_hip_frames_clear_depth_filter.argtypes = [vp, C.c_int, C.POINTER(vp)]
+        L.dvo_hip_depth_filter_default.argtypes = []
+        L.dvo_hip_depth_filter_default.restype = DepthFilter
     if hasattr(L, "dvo_hip_map_create"):   # (likewise: an older build has no keyframe map)
         dp = C.POINTER(C.c_double)
         L.dvo_hip_map_create.argtypes = [vp, C.c_float, C.c_size_t, C.POINTER(vp)]

@@ -146,6 +146,13 @@ struct dvo_hip_frame {
   // sensor's own image and registers it into the frame's float plane Z of level 0 first (rig_stage), ahead of the lens pass.
   bool rig_on = false;
   dvo_hip_depth_rig rig = {};
+  // The depth filter of the frame (dvo_hip_frames_set_depth_filter, depth_filter.h): every later ingest conditions the depth plane the
+  // other stages hand on -- flying pixels and hole borders rejected, noise smoothed -- into filter_plane first (filter_stage, the last
+  // stage), and the ingest reads THAT plane.  The plane (w x h floats) is allocated when the filter is set and freed when it is cleared:
+  // a steady-state ingest allocates nothing.
+  bool filter_on = false;
+  dvo_hip_depth_filter filter = {};
+  DevBuf filter_plane;
   // The colour of the frame (dvo_hip_frames_set_colour, cloud_colour.h): its own level-0 plane of packed pixels, w0 * h0 dwords, written
   // and read on the main stream only.  A property like the lens: kept across re-ingests until it is replaced or cleared.
   bool colour_on = false;
@@ -414,6 +421,7 @@ struct dvo_hip_context {
   long long sensor_ingests = 0;    // frames ingested from a raw sensor plane (sensor_formats.h), counter "sensor_ingests"
   long long f32_ingests = 0;       // frames ingested from a float depth plane (DVO_HIP_DEPTH_F32), counter "f32_ingests"
   long long lens_ingests = 0;      // frames rectified at ingest (dvo_hip_frames_set_lens), counter "lens_ingests"
+  long long depth_filter_ingests = 0;  // frames whose depth was filtered at ingest (dvo_hip_frames_set_depth_filter), counter "depth_filter_ingests"
   long long depth_registrations = 0;   // frames whose depth was registered at ingest (dvo_hip_frames_set_depth_rig), counter "depth_registrations"
   long long map_inserts = 0, map_points = 0, map_dropped = 0;   // frames / points a keyframe map took, points it dropped (dvo_hip_map_insert); counters of the same names
   long long map_removes = 0, map_rehashes = 0;   // frames subtracted from a keyframe map (dvo_hip_map_remove, dvo_hip_map_move), tables rebuilt (dvo_hip_map_rehash); counters of the same names
@@ -540,6 +548,7 @@ struct dvo_hip_context {
   DevBuf lens_tbl;                                    // table of the rectify pass (lens_stage; allocated by the first lens ingest)
   DevBuf sensor_tbl;                                  // table of the sensor-format pass (sensor_stage; allocated by the first sensor ingest)
   DevBuf graph_jobs, graph_outs;                      // the job records and results of a resident pose-graph launch (capi_graph.inc)
+  DevBuf filter_tbl;                                  // table of the filter pass (filter_stage; allocated by the first filtered ingest)
   DevBuf rig_tbl;                                     // table of the register pass (rig_stage; allocated by the first rig ingest)
   DevBuf colour_tbl, colour_stage;                    // the plane table of a k_colour_pack launch and the staging area of host colour planes (capi_colour.inc)
   DevBuf map_tbl, map_stage;                          // the frame table of a keyframe-map launch and the staging area of results that go to host memory (capi_map.inc)
@@ -916,7 +925,7 @@ void dvo_hip_context_destroy(dvo_hip_context* ctx) {
   if (ctx->build_stream) (void)hipStreamDestroy(ctx->build_stream);
   for (DevBuf& b : ctx->build_tbl) b.release();
   for (DevBuf* b : {&ctx->misc, &ctx->role_tbl_cur, &ctx->role_tbl_ref, &ctx->prep_tbl_cur, &ctx->prep_tbl_ref, &ctx->rcp_table, &ctx->ref_order_planes,
-                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl, &ctx->sensor_tbl, &ctx->rig_tbl, &ctx->graph_jobs, &ctx->graph_outs, &ctx->map_tbl, &ctx->map_stage, &ctx->colour_tbl, &ctx->colour_stage, &ctx->render_tbl, &ctx->render_zbuf, &ctx->render_planes}) b->release();
+                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl, &ctx->sensor_tbl, &ctx->rig_tbl, &ctx->filter_tbl, &ctx->graph_jobs, &ctx->graph_outs, &ctx->map_tbl, &ctx->map_stage, &ctx->colour_tbl, &ctx->colour_stage, &ctx->render_tbl, &ctx->render_zbuf, &ctx->render_planes}) b->release();
   if (ctx->render_done) (void)hipEventDestroy(ctx->render_done);
   for (DevBuf& b : ctx->upload_buf) b.release();
   for (const dvo_hip_context::PooledBlock& b : ctx->frame_pool) (void)hipFree(b.p);
@@ -1041,6 +1050,7 @@ void dvo_hip_frame_destroy(dvo_hip_context* ctx, dvo_hip_frame* frame) {
     }
   }
   frame->sel_mask.release();
+  frame->filter_plane.release();
   frame->colour.release();
   frame->pool.release();
   delete frame;
@@ -1234,6 +1244,42 @@ int dvo_hip_frames_clear_depth_rig(dvo_hip_context* ctx, int n_frames, dvo_hip_f
   for (int i = 0; i < n_frames; ++i) {
     frames[i]->rig_on = false;
     frames[i]->rig = dvo_hip_depth_rig{};
+  }
+  return DVO_HIP_OK;
+}
+
+dvo_hip_depth_filter dvo_hip_depth_filter_default(void) { return depth_filter_default_params(); }
+
+int dvo_hip_frames_set_depth_filter(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const dvo_hip_depth_filter* filter) {
+  DVO_ENTER(ctx);                                              // (a recorded ingest of these frames is carried out with the filter it was recorded under)
+  int rc = check_frame_count(ctx, n_frames, frames, "frames_set_depth_filter", filter != nullptr);
+  if (rc != DVO_HIP_OK) return rc;
+  if (const char* wrong = depth_filter_check(*filter)) return fail(ctx, DVO_HIP_ERR_INVALID, "frames_set_depth_filter", wrong);
+  for (int i = 0; i < n_frames && rc == DVO_HIP_OK; ++i) rc = check_frame(ctx, frames[i], "frames_set_depth_filter");
+  if (rc != DVO_HIP_OK) return rc;
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // every plane first: a frame whose plane cannot be had leaves every frame's filter as it was
+  for (int i = 0; i < n_frames; ++i)
+    DVO_HIP_TRY(ctx, frames[i]->filter_plane.reserve(size_t(frames[i]->lv[0].w) * frames[i]->lv[0].h * 4));
+  for (int i = 0; i < n_frames; ++i) {
+    frames[i]->filter_on = true;
+    frames[i]->filter = *filter;                               // (filters are compared bytewise: reserved is 0, there is no padding)
+  }
+  return DVO_HIP_OK;
+}
+
+int dvo_hip_frames_clear_depth_filter(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames) {
+  DVO_ENTER(ctx);
+  const int rc = check_frame_list(ctx, n_frames, frames, "frames_clear_depth_filter");
+  if (rc != DVO_HIP_OK) return rc;
+  bool any = false;
+  for (int i = 0; i < n_frames; ++i) any = any || frames[i]->filter_plane.p != nullptr;
+  // (the build stream may still read a plane that is about to go back to the allocator)
+  if (any && ctx->build_stream) DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->build_stream));
+  for (int i = 0; i < n_frames; ++i) {
+    frames[i]->filter_on = false;
+    frames[i]->filter = dvo_hip_depth_filter{};
+    frames[i]->filter_plane.release();
   }
   return DVO_HIP_OK;
 }

@@ -438,8 +438,37 @@ int lens_stage(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const 
   return DVO_HIP_OK;
 }
 
+// Frames that carry a depth filter (depth_filter.h, depth_filter.hip): the depth planes of `in` -- the caller's, or behind a rig or a lens
+// the frame's own float plane Z of level 0 -- through the filter into each frame's FILTER PLANE (dvo_hip_frame::filter_plane, allocated
+// when the filter was set), depth conversion included.  The last stage: it filters in the frame's own raster.  Hands on the image of
+// `in` unchanged with float depth of scale 1 at the filter plane: the frame ends as a filter-less frame (same lens, same rig) fed that
+// image and the filtered plane would.  The pass is NEVER in place -- a stencil must not write what its neighbours still read -- so the
+// filtered plane lies beside the frame's Z, and an ingest that keeps a copy runs with keep_planes 1 (frame_source) and stores it into
+// Z.  That holds behind a lens too, where the image it reads is the frame's own plane I: each lane then stores the I it loaded back
+// where it loaded it from, and the float conversion keeps every bit (see rig_stage), so a neighbour's halo read sees the same bits
+// before and after.  Nothing but the filter pass and the ingest behind it ever reads or writes the filter plane.
+int filter_stage(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, const IngestSource& in, StagePlanes& planes, IngestSource* out) {
+  const CameraGeom* cam = frames[0]->cam;
+  const bool depth_f32 = in.depth_format == DVO_HIP_DEPTH_F32;
+  std::vector<DepthFilterPtrs> host(static_cast<size_t>(n));
+  for (int i = 0; i < n; ++i) host[size_t(i)] = DepthFilterPtrs{in.depth[i], frames[i]->filter_plane.as<float>()};
+  DepthFilterArgs a;
+  a.P = depth_filter_prepare(frames[0]->filter);
+  a.w = cam->w[0]; a.h = cam->h[0];
+  a.depth_pitch = depth_f32 ? int(in.depth_pitch) : cam->w[0] * 2;   // (u16 depth planes are tight)
+  a.depth_scale = in.depth_scale;
+  const DepthFilterPtrs* tbl = stage_table(ctx, ctx->filter_tbl, host);
+  if (!tbl) return DVO_HIP_ERR_HIP;
+  launch_depth_filter(ctx->build_stream, tbl, n, a, depth_f32, ctx->opt_build_workgroups, ctx->opt_stream_policy != 0);
+  DVO_HIP_TRY(ctx, hipGetLastError());
+  planes.depth.resize(size_t(n));                            // (the table above was filled first: in.depth may be this very array)
+  for (int i = 0; i < n; ++i) planes.depth[size_t(i)] = frames[i]->filter_plane.p;
+  *out = IngestSource{in.planes, in.format, in.pitch, planes.depth.data(), 1.0f, DVO_HIP_DEPTH_F32, size_t(cam->w[0]) * 4};
+  return DVO_HIP_OK;
+}
+
 // which stages a call runs (frames_build runs them in this order)
-struct StagesRun { bool sensor, rig, lens; };
+struct StagesRun { bool sensor, rig, lens, filter; };
 
 // new pixels: every cached role plane of the frame is stale (PointSelection::setRgbdImagePyramid)
 void invalidate_roles(dvo_hip_frame* f) {
@@ -458,7 +487,7 @@ SourceKind source_kind(const IngestSource* src) {
 // leaves a copy -- and, returned, what the frame then holds of its raw planes and its share of `wide` (every plane's address and pitch
 // suit the strip ingest's loads).  Without a source (a frame created from float planes: level 0 is in place) nothing but the planes.
 struct FrameSource { bool raw0, raw_copy, wide; };
-FrameSource frame_source(dvo_hip_frame* f, const IngestSource* src, int i, const SourceKind& kind, int role, bool keep_raw_copy, bool lens,
+FrameSource frame_source(dvo_hip_frame* f, const IngestSource* src, int i, const SourceKind& kind, int role, bool keep_raw_copy, bool lens, bool filter,
                          FrameBuildPtrs& p) {
   fill_build_ptrs(f, p);
   if (!src) return FrameSource{false, false, true};
@@ -483,8 +512,9 @@ FrameSource frame_source(dvo_hip_frame* f, const IngestSource* src, int i, const
   FrameSource s{true, false, true};
   if (kind.depth_f32 && keeps) {
     // float depth: the copy is the frame's float planes I / Z of level 0 -- the state of a frame created from float planes (raw0 false).
-    // Rectified planes (lens) already lie where the copy goes: nothing is written twice
-    p.keep_planes = lens ? 0 : 1;
+    // Rectified planes (lens) already lie where the copy goes: nothing is written twice -- unless a filter stands behind the lens: the
+    // filtered depth lies in the frame's filter plane, and the copy puts it into Z (filter_stage)
+    p.keep_planes = lens && !filter ? 0 : 1;
     s.raw0 = false;
   } else if (in_place) {
     s.raw_copy = true;                 // u16 depth, read from the frame's own staging area: that IS the copy, whatever the role
@@ -548,6 +578,7 @@ int launch_raw_ingest(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames,
   if (kind.depth_f32) ctx->f32_ingests += n;
   if (ran.lens) ctx->lens_ingests += n;
   if (ran.rig) ctx->depth_registrations += n;
+  if (ran.filter) ctx->depth_filter_ingests += n;
   return DVO_HIP_OK;
 }
 
@@ -562,9 +593,11 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
                  float dthr = 0.0f, bool keep_raw_copy = true) {
   Range range("build");
   const CameraGeom* cam = frames[0]->cam;
-  const StagesRun run{src && sensor_bytes(src->format) != 0, src && frames[0]->rig_on, src && frames[0]->lens_on};
-  // the stages, in their order: sensor format -> grey, depth rig -> registered Z, lens -> rectified I / Z; behind them src is what the ingest reads
-  const struct { bool on; IngestStage* stage; } chain[3] = {{run.sensor, sensor_stage}, {run.rig, rig_stage}, {run.lens, lens_stage}};
+  const StagesRun run{src && sensor_bytes(src->format) != 0, src && frames[0]->rig_on, src && frames[0]->lens_on, src && frames[0]->filter_on};
+  // the stages, in their order: sensor format -> grey, depth rig -> registered Z, lens -> rectified I / Z, depth filter -> the filter plane;
+  // behind them src is what the ingest reads
+  const struct { bool on; IngestStage* stage; } chain[4] = {{run.sensor, sensor_stage}, {run.rig, rig_stage}, {run.lens, lens_stage},
+                                                           {run.filter, filter_stage}};
   StagePlanes planes;
   IngestSource staged;
   for (const auto& link : chain) {
@@ -581,7 +614,7 @@ int frames_build(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames, cons
   for (int i = 0; i < n; ++i) {
     dvo_hip_frame* f = frames[i];
     invalidate_roles(f);
-    const FrameSource s = frame_source(f, src, i, kind, role, keep_raw_copy, run.lens, host[i]);
+    const FrameSource s = frame_source(f, src, i, kind, role, keep_raw_copy, run.lens, run.filter, host[i]);
     f->raw0 = s.raw0;
     f->raw_copy = s.raw_copy;
     f->depth_scale = depth_scale;

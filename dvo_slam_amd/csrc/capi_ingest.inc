@@ -42,6 +42,9 @@ static int check_source(dvo_hip_context* ctx, const char* who, int n, dvo_hip_fr
     // (likewise one register pass per ingest, one depth rig per launch: rig_stage)
     if (frames && (frames[i]->rig_on != frames[0]->rig_on || std::memcmp(&frames[i]->rig, &frames[0]->rig, sizeof(dvo_hip_depth_rig)) != 0))
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "frames of one ingest must carry the same depth rig, or none (dvo_hip_frames_set_depth_rig)");
+    // (and one filter pass per ingest, one depth filter per launch: filter_stage)
+    if (frames && (frames[i]->filter_on != frames[0]->filter_on || std::memcmp(&frames[i]->filter, &frames[0]->filter, sizeof(dvo_hip_depth_filter)) != 0))
+      return fail(ctx, DVO_HIP_ERR_INVALID, who, "frames of one ingest must carry the same depth filter, or none (dvo_hip_frames_set_depth_filter)");
     if (!src->planes[i] || !src->depth[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null entry");
     if ((image_f32 && !aligned_to(src->planes[i], 4)) || (depth_f32 && !aligned_to(src->depth[i], 4)))
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "a float plane must be 4-byte aligned");
@@ -62,7 +65,9 @@ static int check_source(dvo_hip_context* ctx, const char* who, int n, dvo_hip_fr
   // planes: a source that lies in those planes -- the in-place float ingest of a lens-less frame -- would be read while it is overwritten.
   // A frame with a depth rig is registered INTO its own float plane Z of level 0 (rig_stage), a scatter: a source that lies in
   // that plane -- depth or image -- would be overwritten by the fill before it is read.
-  if (frames && (frames[0]->lens_on || frames[0]->rig_on)) {
+  // A frame with a depth filter is filtered INTO its filter plane, a stencil, and the ingest behind it stores the frame's level-0 planes
+  // while it reads that plane and the caller's image: a caller plane in any of the three is refused.
+  if (frames && (frames[0]->lens_on || frames[0]->rig_on || frames[0]->filter_on)) {
     const size_t h = size_t(frames[0]->lv[0].h), own = size_t(width) * h * 4;
     const size_t image_bytes = src->pitch * h, depth_bytes = (depth_f32 ? src->depth_pitch : size_t(width) * 2) * h;
     auto reads = [&](int i, const void* mine) { return overlaps(src->planes[i], image_bytes, mine, own) || overlaps(src->depth[i], depth_bytes, mine, own); };
@@ -72,6 +77,9 @@ static int check_source(dvo_hip_context* ctx, const char* who, int n, dvo_hip_fr
     for (int i = 0; i < n && frames[0]->rig_on; ++i)
       if (reads(i, frames[i]->lv[0].Z))
         return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a depth rig cannot be ingested from its own level-0 plane Z");
+    for (int i = 0; i < n && frames[0]->filter_on; ++i)
+      if (reads(i, frames[i]->lv[0].I) || reads(i, frames[i]->lv[0].Z) || reads(i, frames[i]->filter_plane.p))
+        return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a depth filter cannot be ingested from its own level-0 planes or its filter plane");
   }
   return DVO_HIP_OK;
 }

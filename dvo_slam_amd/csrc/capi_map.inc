@@ -938,8 +938,8 @@ int dvo_hip_map_render_frames(dvo_hip_context* ctx, dvo_hip_map* map, int n_fram
     const dvo_hip_frame* f = frames[i];
     rc = check_frame(ctx, f, who, /*own_context=*/true);
     if (rc != DVO_HIP_OK) return rc;
-    if (f->lens_on || f->rig_on)
-      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a lens or a depth rig takes raw sensor planes; rendered planes are rectified and registered already");
+    if (f->lens_on || f->rig_on || f->filter_on)
+      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a lens, a depth rig or a depth filter takes raw sensor planes; rendered planes are rectified, registered and free of sensor noise already");
   }
   const CameraGeom* cam = frames[0]->cam;
   const int width = frames[0]->lv[0].w, height = frames[0]->lv[0].h;

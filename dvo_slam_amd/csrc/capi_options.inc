@@ -38,6 +38,8 @@ int dvo_hip_get_counter(dvo_hip_context* ctx, const char* key, long long* value)
   else if (std::strcmp(key, "lens_ingests") == 0) *value = ctx->lens_ingests;
   // (frames whose depth plane went through a depth rig, rig_stage; and the bytes of the pass's pointer table: 0 until the first one)
   else if (std::strcmp(key, "depth_registrations") == 0) *value = ctx->depth_registrations;
+  // (frames whose depth plane went through a depth filter, filter_stage)
+  else if (std::strcmp(key, "depth_filter_ingests") == 0) *value = ctx->depth_filter_ingests;
   else if (std::strcmp(key, "depth_rig_table_bytes") == 0) *value = (long long)ctx->rig_tbl.bytes;
   // (the keyframe map, capi_map.inc: frames inserted, points the maps took, points they dropped)
   else if (std::strcmp(key, "map_inserts") == 0) *value = ctx->map_inserts;

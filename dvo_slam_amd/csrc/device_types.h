@@ -6,6 +6,7 @@
 #include "hd_compat.h"
 #include "lens.h"
 #include "depth_rig.h"
+#include "depth_filter.h"
 #include "cloud_map.h"
 #include "cloud_colour.h"
 #include "cloud_normal.h"
@@ -275,6 +276,21 @@ struct CovisPair {
 // usable points in range of the frames a launch subtracts -- its kMapCntCandidates; kMapCntUnmatched of them found no voxel to leave)
 constexpr int kMapCntCandidates = 0, kMapCntDropped = 1, kMapCntOutOfRange = 2, kMapCntUnusable = 3, kMapCntUpdates = 4, kMapCntOccupied = 5,
               kMapCntOverLimit = 6, kMapCntCursor = 7, kMapCntVacant = 8, kMapCntRemoving = 9, kMapCntUnmatched = 10, kMapCounters = 11;
+
+// one frame of the filter pass (k_depth_filter, depth_filter.hip; include/dvo_hip.h, dvo_hip_frames_set_depth_filter): the depth plane the
+// chain hands to the stage -- the caller's, or the frame's own float plane Z of level 0 behind a rig or a lens -- and the frame's filter
+// plane, which is never that plane
+struct DepthFilterPtrs {
+  const void* depth;                   // u16 (tight) or float, rows of DepthFilterArgs::depth_pitch bytes
+  float* out;                          // tight, w * h floats
+};
+// ... and what the frames of one launch share: the prepared filter, the plane geometry and the depth conversion
+struct DepthFilterArgs {
+  DepthFilterPrepared P;               // depth_filter.h
+  int w, h;
+  int depth_pitch;                     // bytes
+  float depth_scale;
+};
 
 // one frame of the caller-selection apply pass (k_apply_selection; include/dvo_hip.h, dvo_hip_frames_set_selection; rule: selection.h)
 struct SelectionApply {

@@ -77,6 +77,12 @@ void launch_rectify(hipStream_t s, const RectifyPtrs* tbl, int n_frames, const R
 void launch_depth_register(hipStream_t s, const DepthRigPtrs* tbl, int n_frames, const DepthRigArgs& a, bool depth_f32, int max_workgroups,
                            bool stream_nt);
 
+// depth_filter.hip: the depth planes of n frames through one depth filter (depth_filter.h) into their filter planes: flying pixels and
+// hole borders rejected, noise smoothed.  depth_f32: float depth planes, else u16.  stream_nt: the source planes are read and the filter
+// planes written with the non-temporal policy (option "stream_policy")
+void launch_depth_filter(hipStream_t s, const DepthFilterPtrs* tbl, int n_frames, const DepthFilterArgs& a, bool depth_f32, int max_workgroups,
+                         bool stream_nt);
+
 // sensor_convert.hip: the sensor planes (Bayer mosaics, YUV 4:2:2) of n frames of one size into tight planes of grey (packed false: the
 // ingest's pre-pass) or of packed pixels (packed true: dvo_hip_frames_set_colour), sensor_formats.h.  a.src_dwords / a.dst_wide: what
 // sensor_src_dwords and the caller's look at the destinations say.  stream_nt: planes read and written with the non-temporal policy

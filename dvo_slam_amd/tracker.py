@@ -233,6 +233,9 @@ class RgbdImagePyramid:
         rig = getattr(self, "_depth_rig", None)
         if rig is not None:                                  # (... and the depth rig)
             set_depth_rig_batch([self], *rig)
+        filt = getattr(self, "_depth_filter", None)
+        if filt is not None:                                 # (... and the depth filter)
+            set_depth_filter_batch([self], **filt)
         colour = getattr(self, "_colour", None)
         if colour is not None:                               # (... and the colour, from the host copy)
             if not isinstance(colour[0], np.ndarray):
@@ -272,6 +275,17 @@ class RgbdImagePyramid:
 
     def clear_depth_rig(self):
         clear_depth_rig_batch([self])
+
+    def set_depth_filter(self, **params):
+        """Depth filter of this frame (an extension over the reference API, which has no such pass; include/dvo_hip.h,
+        dvo_hip_frames_set_depth_filter): keyword arguments are the fields of dvo_hip_depth_filter -- radius, sigma_space, noise_a,
+        noise_b, gate, edge_radius, edge_abs, edge_rel, hole_radius -- over depth_filter_default().  Every later update_* of this
+        pyramid conditions its depth plane on the device first, behind the depth rig and the lens: flying pixels at depth edges and
+        hole borders become NaN, the noise of kept pixels is smoothed.  Kept across re-ingests until replaced or cleared."""
+        set_depth_filter_batch([self], **params)
+
+    def clear_depth_filter(self):
+        clear_depth_filter_batch([self])
 
     def set_colour(self, colour, pixel_format="bgr8", pitch=0):
         """Colour of this frame (include/dvo_hip.h, dvo_hip_frames_set_colour; the reference's level(0).rgb, benchmark_slam.cpp:89-90): a
@@ -1534,8 +1548,8 @@ class KeyframeMap:
                 raise ValueError("%s: the pyramids belong to another context than the map" % who)
             if p.camera is not pyramids[0].camera:
                 raise ValueError("%s: the pyramids of one call share a camera" % who)
-            if getattr(p, "_lens", None) is not None or getattr(p, "_depth_rig", None) is not None:
-                raise ValueError("%s: a pyramid that carries a lens or a depth rig takes raw sensor planes, not rendered ones" % who)
+            if getattr(p, "_lens", None) is not None or getattr(p, "_depth_rig", None) is not None or getattr(p, "_depth_filter", None) is not None:
+                raise ValueError("%s: a pyramid that carries a lens, a depth rig or a depth filter takes raw sensor planes, not rendered ones" % who)
         if int(flags) & _lib.INGEST_DEFER:
             raise ValueError("%s: a render cannot be deferred" % who)
         rp = render_params_struct(**params)
@@ -1811,6 +1825,74 @@ def select_outliers(weights, delta, threshold, n_max=-1):
     candidates = np.nonzero((delta > 0) & (weights < threshold))[0]
     order = candidates[np.argsort(weights[candidates], kind="stable")]
     return order if n_max < 0 else order[:n_max]
+
+
+_DEPTH_FILTER_DEFAULTS = dict(radius=2, sigma_space=1.5, noise_a=0.0012, noise_b=0.0019, gate=3.0, edge_radius=1, edge_abs=0.01, edge_rel=0.03,
+                              hole_radius=0)
+_DEPTH_FILTER_INTS = {"radius": 3, "edge_radius": 2, "hole_radius": 2}   # field -> largest value
+
+
+def depth_filter_default():
+    """The fields of dvo_hip_depth_filter_default() as a dict (values recalled from published Kinect axial-noise fits, NOT verified
+    by this project): what set_depth_filter starts from."""
+    return dict(_DEPTH_FILTER_DEFAULTS)
+
+
+def depth_filter_struct(**params):
+    """dvo_hip_depth_filter from keyword arguments over depth_filter_default(); raises before anything reaches the library."""
+    unknown = sorted(set(params) - set(_DEPTH_FILTER_DEFAULTS))
+    if unknown:
+        raise TypeError("set_depth_filter: unknown field %s" % ", ".join(unknown))
+    values = dict(_DEPTH_FILTER_DEFAULTS)
+    values.update(params)
+    filt = _lib.DepthFilter()
+    for name, v in values.items():
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError("set_depth_filter: %s must be a real number" % name)
+        if name in _DEPTH_FILTER_INTS:
+            if int(v) != v:
+                raise TypeError("set_depth_filter: %s must be an integer" % name)
+            if not 0 <= int(v) <= _DEPTH_FILTER_INTS[name]:
+                raise ValueError("set_depth_filter: %s must be 0..%d" % (name, _DEPTH_FILTER_INTS[name]))
+            setattr(filt, name, int(v))
+            continue
+        with np.errstate(over="ignore"):
+            v32 = np.float32(v)
+        if not np.isfinite(v32):
+            raise ValueError("set_depth_filter: %s must be finite" % name)
+        setattr(filt, name, float(v32))
+    if filt.radius > 0 and not filt.sigma_space > 0:
+        raise ValueError("set_depth_filter: sigma_space must be > 0 when radius > 0")
+    if not filt.gate > 0:
+        raise ValueError("set_depth_filter: gate must be > 0")
+    for name in ("noise_a", "noise_b", "edge_abs", "edge_rel"):
+        if getattr(filt, name) < 0:
+            raise ValueError("set_depth_filter: %s must not be negative" % name)
+    if not (filt.noise_a > 0 or filt.noise_b > 0):
+        raise ValueError("set_depth_filter: sigma(z) must be positive (noise_a and noise_b are both 0)")
+    filt.reserved[:] = [0, 0]
+    return filt
+
+
+def set_depth_filter_batch(pyramids, **params):
+    """RgbdImagePyramid.set_depth_filter for n pyramids of one context in one call (they then carry equal filters, as one ingest call wants)."""
+    filt = depth_filter_struct(**params)
+    if len(pyramids) < 1:
+        raise ValueError("set_depth_filter_batch: no pyramids")
+    ctx = pyramids[0].ctx
+    ctx.check(ctx._lib.dvo_hip_frames_set_depth_filter(ctx.ptr, len(pyramids), _handles(pyramids), C.byref(filt)))
+    kept = {name: getattr(filt, name) for name in _DEPTH_FILTER_DEFAULTS}
+    for p in pyramids:
+        p._depth_filter = dict(kept)                         # (kept for a frame that is built again with more levels)
+
+
+def clear_depth_filter_batch(pyramids):
+    if len(pyramids) < 1:
+        raise ValueError("clear_depth_filter_batch: no pyramids")
+    ctx = pyramids[0].ctx
+    ctx.check(ctx._lib.dvo_hip_frames_clear_depth_filter(ctx.ptr, len(pyramids), _handles(pyramids)))
+    for p in pyramids:
+        p._depth_filter = None
 
 
 def set_level_selection(pyramid, level, accepted):

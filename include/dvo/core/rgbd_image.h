@@ -343,7 +343,7 @@ class RgbdImagePyramid {
     dvo_hip_frame* one[1] = {frame_};
     if (dvo_hip_check(ctx_, dvo_hip_frames_update_f32_as_ex(ctx_, 1, one, i, 0, z, 0, 1.0f, -1, nullptr, 0u), "dvo_hip_frames_update_f32_as_ex"))
       dvo_hip_check(ctx_, dvo_hip_upload_wait(ctx_), "dvo_hip_upload_wait");
-    refreshMirrors(has_lens_ || has_rig_);
+    refreshMirrors(has_lens_ || has_rig_ || has_filter_);
   }
   // the device frame's pixels were replaced on the device (PointCloudAggregator::renderInto): the host matrices are dropped, every
   // level is mirrored from the device like the levels above 0
@@ -457,6 +457,25 @@ class RgbdImagePyramid {
     has_rig_ = false;
   }
   bool hasDepthRig() const { return has_rig_; }
+  // ---- extension over the reference API: the depth filter of this frame (include/dvo_hip.h, dvo_hip_frames_set_depth_filter; the
+  // reference has no such pass, SurfacePyramid::convertRawDepthImage only scales and maps 0 to NaN).  Every later update() conditions its
+  // depth matrix on the device first, behind the depth rig and the lens: flying pixels at depth edges and hole borders become NaN, the
+  // noise of kept pixels is smoothed.  The matrices the pyramid was created from were ingested as they are.  Kept until replaced or
+  // cleared.  Returns false where the engine refuses the filter (a field out of range or not finite).  dvo_hip_depth_filter_default()
+  // gives a filter to start from.  Host mirrors: as under a lens or a rig, update() under a filter does NOT rebind level(0).intensity /
+  // depth to the caller's matrices (the depth matrix is the unfiltered image): level 0 is mirrored from the device like every other level.
+  bool setDepthFilter(const dvo_hip_depth_filter& filter) {
+    dvo_hip_frame* one[1] = {device_frame()};
+    if (!dvo_hip_check(ctx_, dvo_hip_frames_set_depth_filter(ctx_, 1, one, &filter), "dvo_hip_frames_set_depth_filter")) return false;
+    has_filter_ = true;
+    return true;
+  }
+  void clearDepthFilter() {
+    dvo_hip_frame* one[1] = {device_frame()};
+    dvo_hip_check(ctx_, dvo_hip_frames_clear_depth_filter(ctx_, 1, one), "dvo_hip_frames_clear_depth_filter");
+    has_filter_ = false;
+  }
+  bool hasDepthFilter() const { return has_filter_; }
   // ---- the colour of this frame (include/dvo_hip.h, dvo_hip_frames_set_colour; the reference keeps the camera image in level(0).rgb,
   // dvo_benchmark/src/benchmark_slam.cpp:89-90, and AsyncPointCloudBuilder reads it, async_point_cloud_builder.cpp:72-104).  setColour:
   // an 8-bit plane of the frame's level-0 size, rows `pitch` bytes apart (0 = tight), format DVO_HIP_PIXEL_{BGR8, RGB8, BGRA8, RGBA8} or a
@@ -530,6 +549,7 @@ class RgbdImagePyramid {
   bool has_selection_mask_ = false;
   bool has_lens_ = false;
   bool has_rig_ = false;
+  bool has_filter_ = false;
   bool has_colour_ = false;
   float selection_min_ = 0.0f, selection_max_ = INFINITY;
   unsigned explicit_levels_ = 0u;

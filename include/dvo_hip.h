@@ -481,6 +481,69 @@ typedef struct {
 int dvo_hip_frames_set_depth_rig(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const dvo_hip_depth_rig* rig);
 int dvo_hip_frames_clear_depth_rig(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames);
 
+/* ---- depth filter: raw depth conditioned on the device at ingest -- flying pixels and hole borders rejected, axial noise smoothed (an
+ * extension: the reference has no such pass, SurfacePyramid::convertRawDepthImage only scales and maps 0 to NaN; users of
+ * camera/depth/image_raw run cv::bilateralFilter, PCL's fast bilateral filter or an edge erosion on the CPU) ------------------------
+ * A frame can carry a DEPTH FILTER.  Every later dvo_hip_frames_update_* / dvo_hip_frame_update_* of such a frame conditions its depth
+ * plane LAST of the ingest's pre-passes (sensor format -> depth rig -> lens -> depth filter), so in the frame's own raster.  With z_c
+ * the converted depth of a pixel (u16: 0 -> NaN, else value * depth_scale; float: value * depth_scale; behind a rig or a lens: what that
+ * pass left), valid iff finite and > 0, every output pixel is a function of the INPUT window alone:
+ *   hole     an invalid input gives the canonical quiet NaN 0x7FC00000;
+ *   edge     a valid pixel is rejected (that NaN) if any in-image valid tap within Chebyshev distance edge_radius has
+ *            |z_n - z_c| > edge_abs + edge_rel * z_c: both sides of a step go, each by its own threshold, and the mixed pixels between;
+ *   erosion  a valid pixel is rejected if any in-image tap within Chebyshev distance hole_radius is invalid (the image border erodes
+ *            nothing);
+ *   smooth   a kept pixel becomes z_c + sum(w d) / sum(w) over the valid in-image taps of the (2 radius + 1)^2 window, row-major,
+ *            d = z_n - z_c, t = |d| * inv, inv = 64 / (gate * (noise_a + noise_b * (z_c * z_c))), taps with t >= 64 left out,
+ *            w = ws[dy][dx] * wr[int(t)], ws = exp(-(dx^2 + dy^2) / (2 sigma_space^2)), wr[b] = exp(-((b + 0.5) gate / 64)^2 / 2), both
+ *            tables computed on the host in double and rounded to float once.  radius 0: a kept pixel keeps its bits.
+ * float32 throughout, the operation order fixed in dvo_slam_amd/csrc/depth_filter.h, whose host build the device equals bit for bit.
+ *   ownership    the filter belongs to the FRAME, like the depth rig, the lens and the caller selection: it persists across re-ingests
+ *                until it is replaced or cleared, and it is no part of the frame's camera -- frames with and without a filter align
+ *                with each other in one dvo_hip_match_batch as long as they share K.
+ *   scope        every dvo_hip_frames_update_* / dvo_hip_frame_update_* entry point in the format combinations it accepts today, host
+ *                or device planes, role-aware or plain, DVO_HIP_INGEST_DEFER and DVO_HIP_INGEST_NO_RAW_COPY included.
+ *                dvo_hip_frame_create_* ingests its planes as they are: create, set the filter, then update.
+ *                dvo_hip_map_render_frames refuses a frame with a filter, as it refuses one with a lens or a rig.
+ *   pending      setting or clearing a filter first carries out every recorded ingest (DVO_HIP_INGEST_DEFER), so a recorded ingest
+ *                runs with the filter its frames carried when it was recorded.
+ *   batches      the frames of ONE ingest call carry bytewise equal filters, or none: anything else is DVO_HIP_ERR_INVALID and leaves
+ *                every frame as it was.
+ *   invalid      DVO_HIP_ERR_INVALID, nothing changed, for a NULL filter, a non-finite field, radius outside 0..3, edge_radius or
+ *                hole_radius outside 0..2, sigma_space <= 0 with radius > 0, gate <= 0, a negative noise_* or edge_* field, noise_a
+ *                and noise_b both 0 (sigma(z) not positive), or a non-zero reserved.
+ *   aliasing     the pass writes the frame's filter plane (one more float plane of width x height, allocated when the filter is set
+ *                and freed when it is cleared: a steady-state ingest allocates nothing) and the ingest behind it the frame's level-0
+ *                planes: a caller plane, image or depth, that overlaps the frame's float planes I / Z of level 0 or its filter plane
+ *                is DVO_HIP_ERR_INVALID, every frame left as it was.  Planes that overlap ANOTHER frame's planes of the same call are
+ *                not checked and must not be passed.
+ *   raw copy     after the ingest the frame is in the state of a frame WITHOUT a filter (same lens, same rig) that was fed the same
+ *                image and the filtered float plane through the float-depth entry point of that image format, depth_scale 1, bit
+ *                for bit: its raw copy is its float planes I / Z of level 0, and a later role, dvo_hip_frame_select,
+ *                dvo_hip_frame_download_plane, DVO_HIP_INGEST_NO_RAW_COPY and the caller selection work as there.
+ *   counters     "depth_filter_ingests" counts the frames filtered.  The ingest behind the pass is a float-depth ingest and is
+ *                counted as one: "f32_ingests" counts such a frame, the other ingest counters count as for that ingest.
+ *   cost         one launch (k_depth_filter, depth_filter.hip) behind the other pre-passes, on the build stream: 2-4 B read and 4 B
+ *                written per pixel, the window staged in LDS (profiles/depth_filter.md).  Frames without a filter take the path they
+ *                always took: nothing is launched or allocated for them.
+ * dvo_hip_depth_filter_default() returns radius 2, sigma_space 1.5, noise_a 0.0012, noise_b 0.0019, gate 3, edge_radius 1, edge_abs
+ * 0.01, edge_rel 0.03, hole_radius 0: values recalled from published Kinect axial-noise fits, NOT verified here. */
+typedef struct {
+  int32_t radius;        /* 0..3: half-size of the smoothing window; 0 = no smoothing */
+  float sigma_space;     /* pixels; > 0 when radius > 0 */
+  float noise_a;         /* sigma(z) = noise_a + noise_b * (z * z), metres */
+  float noise_b;
+  float gate;            /* > 0: taps further than gate * sigma(z_c) from z_c take no part in the mean */
+  int32_t edge_radius;   /* 0..2; 0 = no edge rejection */
+  float edge_abs;        /* tau(z) = edge_abs + edge_rel * z, metres */
+  float edge_rel;
+  int32_t hole_radius;   /* 0..2; 0 = no hole-border erosion */
+  int32_t reserved[2];   /* 0 */
+} dvo_hip_depth_filter;
+dvo_hip_depth_filter dvo_hip_depth_filter_default(void);
+int dvo_hip_frames_set_depth_filter(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const dvo_hip_depth_filter* filter);
+int dvo_hip_frames_clear_depth_filter(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames);
+
 /* ---- keyframe map: world point clouds and a voxel-grid map of n keyframes, on the device ---------------------------------------------
  * Stands in for the reference's map building: AsyncPointCloudBuilder::BuildJob::build
  * (dvo_core/src/visualization/async_point_cloud_builder.cpp:61-110: pose.cast<float>() * image.pointcloud plus intensity, every pixel of a
@@ -1172,6 +1235,8 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value);
  * "f32_ingests" (frames ingested from a float depth plane, dvo_hip_frame_create_f32_device / dvo_hip_frames_update_f32* /
  * dvo_hip_frames_update_colour_f32depth*; "strip_ingests" counts those of them that took the strip kernel),
  * "lens_ingests" (frames rectified at ingest because they carry a lens, dvo_hip_frames_set_lens; each is also one of "f32_ingests"),
+ * "depth_filter_ingests" (frames whose depth plane was conditioned at ingest because they carry a depth filter,
+ * dvo_hip_frames_set_depth_filter; each is also one of "f32_ingests"),
  * "depth_registrations" (frames whose depth plane was registered at ingest because they carry a depth rig,
  * dvo_hip_frames_set_depth_rig; each is also one of "f32_ingests") and "depth_rig_table_bytes" (the size of that pass's pointer table:
  * 0 until the first such frame is ingested),
