@@ -10,4 +10,5 @@ from .tracker import (Config, Context, DenseTracker, IterationStats, LevelStats,
                       set_selection_batch, clear_selection_batch, set_level_selection, set_lens_batch, clear_lens_batch, lens_struct,
                       set_depth_rig_batch, clear_depth_rig_batch, depth_rig_struct, set_depth_filter_batch, clear_depth_filter_batch, depth_filter_struct, depth_filter_default, set_colour_batch, clear_colour_batch, KeyframeMap, world_points_batch, normals_batch,render_params_struct, warp_inverse_batch,
                       warp_forward_batch, warp_params_struct, COVIS_DTYPE, covis_params_struct, covisibility_batch, covisibility_matrix, overlap, radius_set,
-                      loop_closure_candidates, PoseGraph, graph_params_struct)
+                      loop_closure_candidates, FERN_DTYPE, CODE_MATCH_DTYPE, CODE_NONE, CODE_MASKED, CodebookLogic, KeyframeCodebook,
+                      relocalisation_candidates, loop_closure_candidates_by_appearance, PoseGraph, graph_params_struct)

@@ -157,6 +157,9 @@ EXPORTS = [
     "dvo_hip_map_merge_records_ex",
     "dvo_hip_warp_params_default", "dvo_hip_frames_warp_inverse", "dvo_hip_frames_warp_forward",
     "dvo_hip_covis_params_default", "dvo_hip_frames_covisibility",
+    "dvo_hip_codebook_create", "dvo_hip_codebook_destroy", "dvo_hip_codebook_clear", "dvo_hip_codebook_info", "dvo_hip_codebook_ferns",
+    "dvo_hip_frames_encode", "dvo_hip_codebook_add_frames", "dvo_hip_codebook_add_codes", "dvo_hip_codebook_remove",
+    "dvo_hip_codebook_read_codes", "dvo_hip_codebook_query_frames", "dvo_hip_codebook_query_codes", "dvo_hip_codebook_query_ids",
     "dvo_hip_graph_create", "dvo_hip_graph_destroy", "dvo_hip_graph_set_vertices", "dvo_hip_graph_set_poses", "dvo_hip_graph_set_edges",
     "dvo_hip_graph_params_default", "dvo_hip_graph_optimize", "dvo_hip_graph_get_poses", "dvo_hip_graph_edge_stats",
     "dvo_hip_graph_linearise", "dvo_hip_graph_multiply", "dvo_hip_graph_optimize_batch",
@@ -187,6 +190,9 @@ MAP_NORMAL_RECORD = [("snx", "<u4"), ("sny", "<u4"), ("snz", "<u4"), ("nn", "<u4
 # the record of one keyframe pair (32 bytes: dvo_hip_covis_record; dvo_hip_frames_covisibility)
 COVIS_RECORD = [("valid", "<u4"), ("in_view", "<u4"), ("unknown", "<u4"), ("occluded", "<u4"), ("seen_through", "<u4"), ("consistent", "<u4"),
                 ("photo", "<u8")]
+# a fern and a result record of a keyframe code book (16 and 8 bytes: dvo_hip_fern, dvo_hip_code_match; dvo_hip_codebook_*)
+FERN_RECORD = [("u", "<u2"), ("v", "<u2"), ("u2", "<u2"), ("v2", "<u2"), ("t_i", "<f4"), ("t_z", "<f4")]
+CODE_MATCH_RECORD = [("id", "<u4"), ("distance", "<u4")]
 COMM_ID_BYTES = 128
 
 
@@ -340,6 +346,22 @@ def lib():
         L.dvo_hip_covis_params_default.argtypes = []
         L.dvo_hip_covis_params_default.restype = CovisParams
         L.dvo_hip_frames_covisibility.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_int, i32p, i32p, dp, C.c_int, C.POINTER(CovisParams), vp, C.c_int]
+    if hasattr(L, "dvo_hip_codebook_create"):   # (likewise: an older build keeps no code book)
+        ip, u32p = C.POINTER(C.c_int), C.POINTER(C.c_uint32)
+        L.dvo_hip_codebook_create.argtypes = [vp, C.c_int, C.c_int, C.c_uint64, vp, C.c_float, C.c_float, C.POINTER(vp)]
+        L.dvo_hip_codebook_destroy.argtypes = [vp, vp]
+        L.dvo_hip_codebook_destroy.restype = None
+        L.dvo_hip_codebook_clear.argtypes = [vp, vp]
+        L.dvo_hip_codebook_info.argtypes = [vp, vp, ip, ip, ip, ip]
+        L.dvo_hip_codebook_ferns.argtypes = [vp, vp, vp]
+        L.dvo_hip_frames_encode.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.c_int, vp, C.c_int]
+        L.dvo_hip_codebook_add_frames.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.c_int, u32p]
+        L.dvo_hip_codebook_add_codes.argtypes = [vp, vp, C.c_int, vp, C.c_int, u32p]
+        L.dvo_hip_codebook_remove.argtypes = [vp, vp, C.c_int, u32p]
+        L.dvo_hip_codebook_read_codes.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.c_int]
+        L.dvo_hip_codebook_query_frames.argtypes = [vp, vp, C.c_int, C.POINTER(vp), C.c_int, C.c_int, u32p, u32p, vp, vp, C.c_int]
+        L.dvo_hip_codebook_query_codes.argtypes = [vp, vp, C.c_int, vp, C.c_int, C.c_int, u32p, u32p, vp, vp, C.c_int]
+        L.dvo_hip_codebook_query_ids.argtypes = [vp, vp, C.c_int, u32p, C.c_int, u32p, u32p, vp, vp, C.c_int]
     if hasattr(L, "dvo_hip_graph_create"):   # (likewise: an older build optimises no pose graph)
         dp, i32p = C.POINTER(C.c_double), C.POINTER(C.c_int32)
         L.dvo_hip_graph_create.argtypes = [vp, C.POINTER(vp)]

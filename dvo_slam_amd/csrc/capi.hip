@@ -21,6 +21,7 @@
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -31,6 +32,7 @@
 #include "colour.h"
 #include "sensor_formats.h"
 #include "launch.h"
+#include "keyframe_codes.h"
 #include "pose_graph.h"
 #include "ref_order.h"
 #include "selection.h"
@@ -432,6 +434,8 @@ struct dvo_hip_context {
   long long map_renders = 0;       // views rendered out of a keyframe map (dvo_hip_map_render, dvo_hip_map_render_frames), counter "map_renders"
   long long frame_warps = 0;       // items warped (dvo_hip_frames_warp_inverse, dvo_hip_frames_warp_forward), counter "frame_warps"
   long long covisibility_pairs = 0;   // pairs counted (dvo_hip_frames_covisibility), counter "covisibility_pairs"
+  long long codebook_encoded = 0;  // frames encoded (dvo_hip_frames_encode, dvo_hip_codebook_add_frames, _query_frames), counter "codebook_encoded"
+  long long codebook_queries = 0;  // queries answered (dvo_hip_codebook_query_*), counter "codebook_queries"
   // Option "defer_ingest": a batched re-ingest (dvo_hip_frames_update_raw_device_as) is only recorded, and carried out by the next
   // dvo_hip_match_batch right behind the first launches of its first level (or by whatever entry point comes first).  A streaming
   // caller re-ingests the next batch and then aligns the current one: enqueueing the ingest first keeps the alignment's stream idle
@@ -518,6 +522,7 @@ struct dvo_hip_context {
   int opt_small_sweep = 0;
   int opt_small_tiles = 0;         // its workgroups per pair (0 = BatchPolicy::small_level_tiles)
   int opt_coarse = 0;              // the fused coarse-level kernel (align_coarse.hip): 0 = off (default: measured and lost), 1 = whenever the levels admit it
+  int opt_codebook_round_kb = 256 * 1024;   // staging for one round's distance matrix (capi_codes.inc, run_query), option "codebook_round_kb"
   int opt_coarse_pixels = 0;       // levels of up to this many pixels run in it (0 = kCoarseMaxPixels)
   int opt_coarse_wgs = 0;          // its workgroups per compute unit: 0 / 4 (128 registers) or 3 (168)
   long long coarse_launches = 0, coarse_levels = 0;
@@ -997,6 +1002,7 @@ int prepare_roles(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* fram
 #include "capi_normal.inc"   // surface normals: dvo_hip_frames_normals, dvo_hip_map_extract_normals, dvo_hip_map_render_normals
 #include "capi_warp.inc"     // frames warped under a pose: dvo_hip_frames_warp_inverse, dvo_hip_frames_warp_forward
 #include "capi_covis.inc"    // keyframe covisibility: dvo_hip_frames_covisibility
+#include "capi_codes.inc"    // keyframes retrieved by appearance: dvo_hip_codebook_*, dvo_hip_frames_encode
 #include "capi_graph.inc"    // the keyframe pose graph: dvo_hip_graph_*
 
 int dvo_hip_upload_wait(dvo_hip_context* ctx) {

@@ -48,6 +48,8 @@ int dvo_hip_get_counter(dvo_hip_context* ctx, const char* key, long long* value)
   else if (std::strcmp(key, "map_renders") == 0) *value = ctx->map_renders;
   else if (std::strcmp(key, "frame_warps") == 0) *value = ctx->frame_warps;
   else if (std::strcmp(key, "covisibility_pairs") == 0) *value = ctx->covisibility_pairs;
+  else if (std::strcmp(key, "codebook_encoded") == 0) *value = ctx->codebook_encoded;
+  else if (std::strcmp(key, "codebook_queries") == 0) *value = ctx->codebook_queries;
   else if (std::strcmp(key, "map_points") == 0) *value = ctx->map_points;
   else if (std::strcmp(key, "map_dropped") == 0) *value = ctx->map_dropped;
   else if (std::strcmp(key, "graph_resident_solves") == 0) *value = ctx->graph_resident_solves;
@@ -168,6 +170,11 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value) {
   if (std::strcmp(key, "coarse") == 0) {
     if (value < 0 || value > 1) return fail(ctx, DVO_HIP_ERR_INVALID, "coarse must be 0 (off) or 1 (whenever the levels admit it)");
     ctx->opt_coarse = value;
+    return DVO_HIP_OK;
+  }
+  if (std::strcmp(key, "codebook_round_kb") == 0) {
+    if (value < 1) return fail(ctx, DVO_HIP_ERR_INVALID, "codebook_round_kb must be >= 1");
+    ctx->opt_codebook_round_kb = value;
     return DVO_HIP_OK;
   }
   if (std::strcmp(key, "coarse_pixels") == 0) {

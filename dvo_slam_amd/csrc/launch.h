@@ -166,6 +166,18 @@ void launch_warp_forward(hipStream_t s, const MapFrame* tbl, int n, long long pi
 void launch_covisibility(hipStream_t s, const MapFrame* tbl, const CovisPair* pairs, int n, long long max_pixels, const dvo_hip_covis_params& par,
                          unsigned long long* records);
 
+// keyframe_codes.hip: keyframes retrieved by appearance (keyframe_codes.h).  launch_encode_frames: the codes of the n frames of the frame
+// table tbl under the m ferns at `ferns` (16-byte aligned), m / 8 words each, into codes_out (4-byte aligned).  launch_code_search: the
+// n_queries x n uint16 distances of the queries (n_queries codes, 16-byte aligned) to the n stored codes (entry-major, 16-byte aligned;
+// live: a byte per entry; skip: n_queries pairs {from, to}, 8-byte aligned), 0xFFFF for a dead or skipped entry; n >= 1.
+// launch_code_topk: per row of that matrix the k least (distance, id) into rows (n_queries x k, padded); n may be 0.
+// launch_gather_codes: the codes of entries ids[0 .. n) into out.
+void launch_encode_frames(hipStream_t s, const MapFrame* tbl, int n, const dvo_hip_fern* ferns, int m, uint32_t* codes_out);
+void launch_code_search(hipStream_t s, const uint32_t* codes, const unsigned char* live, uint32_t n, int m, const uint32_t* queries, int n_queries,
+                        const uint32_t* skip, uint16_t* distances);
+void launch_code_topk(hipStream_t s, const uint16_t* distances, uint32_t n, int n_queries, int k, dvo_hip_code_match* rows);
+void launch_gather_codes(hipStream_t s, const uint32_t* codes, const uint32_t* ids, int n, int m, uint32_t* out);
+
 // pose_graph.hip: the stages of the pose-graph optimiser (pose_graph.h), kPgBlock edges or vertices per workgroup.  *_partials: one
 // double per workgroup, a subtree of the scalar's tree (rz_partials: two rows of them).  launch_pg_linearise: every edge's record at
 // `poses` (with_blocks: the weighted blocks too) and the partials of the cost.  launch_pg_gather: D and b of every vertex and each

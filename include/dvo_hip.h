@@ -830,6 +830,81 @@ int dvo_hip_frames_covisibility(dvo_hip_context* ctx, int n_frames, dvo_hip_fram
                                 const int32_t* pair_b, const double* transforms /* n_pairs x 16 */, int level,
                                 const dvo_hip_covis_params* params_or_null, dvo_hip_covis_record* records_out, int out_on_device);
 
+/* ---- keyframes retrieved by appearance: fern codes and their search on the device -----------------------------------------------------------
+ * Which keyframes a frame should be aligned against when NO pose can be trusted.  The reference's proposal
+ * (NearestNeighborConstraintSearch::findPossibleConstraints, dvo_slam/src/keyframe_constraint_search.cpp:41-72) and
+ * dvo_hip_frames_covisibility both start from a pose; a lost tracker, a loop that closes after drift and two sessions without common
+ * coordinates have none, and the reference has no answer to them.  These calls go beyond it with keyframe encoding by randomised ferns
+ * (Glocker et al., TVCG 2015): a frame becomes m 4-bit tests on a coarse pyramid level (a CODE of m / 2 bytes), similar views have codes
+ * that differ in few ferns, and retrieval is a search over all stored codes.  Everything is comparisons and integer counts, stated once
+ * in dvo_slam_amd/csrc/keyframe_codes.h, whose host build the device results EQUAL.
+ *   fern         {u, v, u2, v2, t_i, t_z}: on a level of w x h pixels x = (u w) >> 16, y = (v h) >> 16, likewise x2, y2.  Nibble: bit 0
+ *                I(x, y) > t_i; bit 1 I(x, y) > I(x2, y2); bit 2 Z(x, y) finite and > t_z; bit 3 Z(x, y) finite.  NaN compares false.
+ *   code         m nibbles, eight to a 32-bit word, fern 8 j + i in bits 4 i .. 4 i + 3 of word j.  m: a multiple of 128, 128 .. 2048.
+ *   distance     the number of ferns whose nibbles differ in any bit, 0 .. m.
+ *   book         dvo_hip_codebook: a device-resident set of codes under ONE fern table.  A slot's id is its index; ids are given in the
+ *                order of adding and are not reused before dvo_hip_codebook_clear; a removed slot stays dead.  The codes of `capacity`
+ *                entries (capacity m / 2 bytes) are allocated when the book is created.
+ *   answer       per query the k live entries outside its skipped id interval [skip_from, skip_to) of least (distance, id), ascending, a
+ *                tie in distance to the lower id; padded with {0xFFFFFFFF, 0xFFFFFFFF} where fewer than k qualify.
+ *   streams      every launch runs on the context's main stream behind the builds of the frames, recorded (deferred) ingests are carried
+ *                out first, and every call waits for that stream: host AND device outputs are complete on return.
+ *   refusals     DVO_HIP_ERR_INVALID, nothing launched, no book, output or counter touched: a null context, book or pointer; a book of
+ *                another context; m that is no multiple of 128 in 128 .. 2048; capacity outside 1 .. 2^24; z_lo or z_hi not finite or
+ *                z_lo > z_hi (without a table of the caller's); n <= 0; n_queries > 4096; k outside 1 .. 64; a null or foreign frame; a
+ *                level a frame does not have; a level wider or higher than 32767 pixels; more than 2^20 frames, or too many pixels for one
+ *                call (the blocks of 256 pixels of the listed frames exceed 2^31 / 256); an id (or first + n) beyond the book's size;
+ *                device codes that are not 4-byte aligned, device result rows that are not 8-byte aligned, device distances that are not
+ *                2-byte aligned.  A book too full for the call: DVO_HIP_ERR_CAPACITY, nothing added.
+ *   cost         profiles/keyframe_codes.md.  Counters "codebook_encoded" (frames encoded, into a book or not) and "codebook_queries". */
+typedef struct dvo_hip_fern {
+  uint16_t u, v, u2, v2;      /* positions as fractions of the level, / 65536 */
+  float t_i, t_z;             /* thresholds: grey levels, metres */
+} dvo_hip_fern;               /* 16 B */
+typedef struct dvo_hip_code_match {
+  uint32_t id, distance;
+} dvo_hip_code_match;         /* 8 B */
+typedef struct dvo_hip_codebook dvo_hip_codebook;
+/* A book of at most `capacity` codes of m ferns.  ferns_or_null: the caller's table of m ferns, else the stated generator's
+ * (keyframe_codes.h, fern_table) for `seed` with depth thresholds uniform in [z_lo, z_hi) (0.5 and 5 metres are the usual choice). */
+int dvo_hip_codebook_create(dvo_hip_context* ctx, int m, int capacity, uint64_t seed, const dvo_hip_fern* ferns_or_null, float z_lo, float z_hi,
+                            dvo_hip_codebook** book_out);
+void dvo_hip_codebook_destroy(dvo_hip_context* ctx, dvo_hip_codebook* book);
+/* forgets every entry: size 0, ids start at 0 again; the fern table stays */
+int dvo_hip_codebook_clear(dvo_hip_context* ctx, dvo_hip_codebook* book);
+/* any of the outputs may be NULL.  size: ids given so far; live: of those, not removed */
+int dvo_hip_codebook_info(dvo_hip_context* ctx, const dvo_hip_codebook* book, int* m, int* capacity, int* size, int* live);
+/* the book's m ferns into host memory */
+int dvo_hip_codebook_ferns(dvo_hip_context* ctx, const dvo_hip_codebook* book, dvo_hip_fern* ferns_out);
+/* The codes of n frames at `level` under the book's ferns, m / 8 words each, into codes_out (host, or device with out_on_device); the
+ * book is not changed.  Frames of different sizes and cameras share the call (one launch). */
+int dvo_hip_frames_encode(dvo_hip_context* ctx, const dvo_hip_codebook* book, int n, dvo_hip_frame* const* frames, int level,
+                          uint32_t* codes_out, int out_on_device);
+/* ... encoded straight into the book's next n slots; ids_out_or_null (host): the ids given */
+int dvo_hip_codebook_add_frames(dvo_hip_context* ctx, dvo_hip_codebook* book, int n, dvo_hip_frame* const* frames, int level,
+                                uint32_t* ids_out_or_null);
+/* n raw codes (host, or device with on_device) into the next n slots: codes of another context's book, or of a saved one */
+int dvo_hip_codebook_add_codes(dvo_hip_context* ctx, dvo_hip_codebook* book, int n, const uint32_t* codes, int on_device,
+                               uint32_t* ids_out_or_null);
+/* the listed entries die (an id may be listed twice, or be dead already); their slots are not given again */
+int dvo_hip_codebook_remove(dvo_hip_context* ctx, dvo_hip_codebook* book, int n, const uint32_t* ids);
+/* the stored codes of entries first .. first + n - 1, dead ones included */
+int dvo_hip_codebook_read_codes(dvo_hip_context* ctx, const dvo_hip_codebook* book, int first, int n, uint32_t* codes_out, int out_on_device);
+/* Three entry points over one query: the queries are frames encoded at `level`, raw codes, or the book's own entries `ids` (dead ones
+ * may ask too).  skip_from_or_null / skip_to_or_null (host, n_queries each, both or neither): ids skip_from[q] <= id < skip_to[q] are
+ * left out of query q -- the query itself and its neighbours in time, which are trivially similar.  results_out: n_queries x k records.
+ * distances_out_or_null: n_queries x size uint16, 0xFFFF for a dead or skipped entry -- the matrix of an all-against-all comparison.
+ * out_on_device: where results_out and distances_out lie. */
+int dvo_hip_codebook_query_frames(dvo_hip_context* ctx, dvo_hip_codebook* book, int n_queries, dvo_hip_frame* const* frames, int level, int k,
+                                  const uint32_t* skip_from_or_null, const uint32_t* skip_to_or_null, dvo_hip_code_match* results_out,
+                                  uint16_t* distances_out_or_null, int out_on_device);
+int dvo_hip_codebook_query_codes(dvo_hip_context* ctx, dvo_hip_codebook* book, int n_queries, const uint32_t* codes, int codes_on_device, int k,
+                                 const uint32_t* skip_from_or_null, const uint32_t* skip_to_or_null, dvo_hip_code_match* results_out,
+                                 uint16_t* distances_out_or_null, int out_on_device);
+int dvo_hip_codebook_query_ids(dvo_hip_context* ctx, dvo_hip_codebook* book, int n_queries, const uint32_t* ids, int k,
+                               const uint32_t* skip_from_or_null, const uint32_t* skip_to_or_null, dvo_hip_code_match* results_out,
+                               uint16_t* distances_out_or_null, int out_on_device);
+
 /* ---- colour in the keyframe map: frames keep RGB, voxels fuse it -------------------------------------------------------------------------
  * The reference's map is coloured: dvo_benchmark/src/benchmark_slam.cpp:89-90 keeps the camera image in level(0).rgb,
  * AsyncPointCloudBuilder::BuildJob::build (dvo_core/src/visualization/async_point_cloud_builder.cpp:72-104) writes p.b, p.g, p.r from it
@@ -1189,6 +1264,9 @@ int dvo_hip_time_stream_mix(dvo_hip_context* ctx, int n_pairs,
  * "coarse_pixels" (the largest level it takes, in pixels; 0 = 160 x 120.  Above that the launch path's log-likelihood schedule differs
  * and the records agree to the stopping rule's precision only), "coarse_workgroups" (its workgroups per compute unit: 4 with 128
  * registers, the default, or 3 with 168).
+ * "codebook_round_kb" (default 262144 = 256 MB; >= 1): the staging the dvo_hip_codebook_query_* calls may take for the distance matrix of
+ * one round of queries when the caller gives no device matrix -- more queries than fit are answered in rounds of as many as fit (at
+ * least one); the results do not depend on it.
  * "rendezvous" (default 1): two dvo_hip_match calls from two host threads with the SAME current frame and configuration -- the
  * reference's LocalTracker, dvo_slam/src/local_tracker.cpp:180-184 -- leave as one two-pair batch: the second caller's thread runs
  * it, the first waits at most 60 microseconds for a partner, and only on a context where concurrent callers have been seen
@@ -1248,6 +1326,8 @@ int dvo_hip_set_option(dvo_hip_context* ctx, const char* key, int value);
  * "map_renders" (views dvo_hip_map_render and dvo_hip_map_render_frames have rendered; a refused call counts nothing),
  * "frame_warps" (items dvo_hip_frames_warp_inverse and dvo_hip_frames_warp_forward have warped; a refused call counts nothing),
  * "covisibility_pairs" (pairs dvo_hip_frames_covisibility has counted; a refused call counts nothing),
+ * "codebook_encoded" (frames dvo_hip_frames_encode, dvo_hip_codebook_add_frames and dvo_hip_codebook_query_frames have encoded) and
+ * "codebook_queries" (queries the three dvo_hip_codebook_query_* have answered; a refused call counts nothing),
  * "warmup_wait_us" (the longest of the nine stream waits dvo_hip_context_create makes on trivial commands to warm up the runtime's wait
  * path, in microseconds: the first GPU process on a fresh box has been seen to spend 14-24 ms in its first wait),
  * "host_batches" and "host_ns_prepare" / "host_ns_enqueue" / "host_ns_wait" / "host_ns_finish" (nanoseconds the calling thread spent
