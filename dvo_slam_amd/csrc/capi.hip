@@ -556,8 +556,19 @@ struct dvo_hip_context {
   DevBuf filter_tbl;                                  // table of the filter pass (filter_stage; allocated by the first filtered ingest)
   DevBuf rig_tbl;                                     // table of the register pass (rig_stage; allocated by the first rig ingest)
   DevBuf colour_tbl, colour_stage;                    // the plane table of a k_colour_pack launch and the staging area of host colour planes (capi_colour.inc)
-  DevBuf map_tbl, map_stage;                          // the frame table of a keyframe-map launch and the staging area of results that go to host memory (capi_map.inc)
-  DevBuf render_tbl, render_zbuf, render_planes;      // a render's view table, its z-buffers and -- dvo_hip_map_render_frames -- the planes the frames ingest (capi_map.inc)
+  // The scratch of the calls that read frames at a level (capi_frame_calls.inc) and of the map's own calls.  Every use is a launch or a
+  // copy on the main stream, and every such call ends in a wait for that stream (a render to device planes excepted, behind which the
+  // next launch that reuses a buffer follows on the same stream): no call finds a buffer still in use, and may reallocate it.
+  //   frame_tbl      the launch's table (upload_block_table): MapFrame of every such call; MapMergeEntry of the merges
+  //   result_stage   results on their way to host memory (stage_results): map read-outs, world points and normals, renders, warps,
+  //                  covisibility records, codes, query rows and -- in front of them -- a query's distance matrix; host records on
+  //                  their way into a merge; a colour level (dvo_hip_frame_download_colour)
+  //   side_tbl       the launch's second table: a render's views and planes, a warp's planes, covisibility's pairs, a query's ids and
+  //                  skipped intervals
+  //   scratch_words  device-only words: the z-buffers of renders and forward warps, a query's codes
+  //   render_frame_planes  the planes a render hands to the frames' ingest (dvo_hip_map_render_frames, dvo_hip_time_map_render); read
+  //                  on the build stream, which that call waits for
+  DevBuf frame_tbl, result_stage, side_tbl, scratch_words, render_frame_planes;
   hipEvent_t render_done = nullptr;                   // recorded behind a render on the main stream: the build stream's ingest waits for it
   static const int kTableSlots = 4;
   DevBuf build_tbl[kTableSlots];   // (a few, picked by the list's first frame: see Workspace::pair_ptrs)
@@ -930,7 +941,7 @@ void dvo_hip_context_destroy(dvo_hip_context* ctx) {
   if (ctx->build_stream) (void)hipStreamDestroy(ctx->build_stream);
   for (DevBuf& b : ctx->build_tbl) b.release();
   for (DevBuf* b : {&ctx->misc, &ctx->role_tbl_cur, &ctx->role_tbl_ref, &ctx->prep_tbl_cur, &ctx->prep_tbl_ref, &ctx->rcp_table, &ctx->ref_order_planes,
-                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl, &ctx->sensor_tbl, &ctx->rig_tbl, &ctx->filter_tbl, &ctx->graph_jobs, &ctx->graph_outs, &ctx->map_tbl, &ctx->map_stage, &ctx->colour_tbl, &ctx->colour_stage, &ctx->render_tbl, &ctx->render_zbuf, &ctx->render_planes}) b->release();
+                    &ctx->sel_tbl_main, &ctx->sel_tbl_build, &ctx->lens_tbl, &ctx->sensor_tbl, &ctx->rig_tbl, &ctx->filter_tbl, &ctx->graph_jobs, &ctx->graph_outs, &ctx->frame_tbl, &ctx->result_stage, &ctx->colour_tbl, &ctx->colour_stage, &ctx->side_tbl, &ctx->scratch_words, &ctx->render_frame_planes}) b->release();
   if (ctx->render_done) (void)hipEventDestroy(ctx->render_done);
   for (DevBuf& b : ctx->upload_buf) b.release();
   for (const dvo_hip_context::PooledBlock& b : ctx->frame_pool) (void)hipFree(b.p);
@@ -997,6 +1008,7 @@ int prepare_roles(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* fram
 }  // namespace
 
 #include "capi_ingest.inc"   // the raw-frame ingest: dvo_hip_frame_create_*, dvo_hip_frames_update_*, dvo_hip_flush_deferred
+#include "capi_frame_calls.inc"   // calls that read frames at a level: the check of their frames, the frame table, results to the caller
 #include "capi_map.inc"      // the keyframe map: dvo_hip_map_*, dvo_hip_frames_world_points, dvo_hip_map_render*
 #include "capi_colour.inc"   // the colour of frames: dvo_hip_frames_set_colour, dvo_hip_frames_clear_colour, dvo_hip_frame_download_colour
 #include "capi_normal.inc"   // surface normals: dvo_hip_frames_normals, dvo_hip_map_extract_normals, dvo_hip_map_render_normals

@@ -1,10 +1,8 @@
 // capi_codes.inc -- keyframes retrieved by appearance behind the C-ABI (include/dvo_hip.h, dvo_hip_codebook_* and dvo_hip_frames_encode;
 // semantics: keyframe_codes.h; kernels: keyframe_codes.hip).  A book owns its codes, its fern table and a byte per entry that says whether
-// it is alive; everything a call needs beyond that is the context's existing scratch, every use ordered on the main stream: the frames
-// reach k_encode_frames through the frame table of the keyframe-map launches (upload_map_entries, capi_map.inc), the skipped intervals
-// (and, before them, the ids of dvo_hip_codebook_query_ids) go into the render scratch as tables through the context's upload ring, the
-// query codes lie in the z-buffer scratch, the distance matrix and host-bound results in the map staging area.  Arguments are checked before anything is launched or changed.
-// Textually included by capi.hip inside its extern "C" block.
+// it is alive.  The encoding calls read frames at a level (capi_frame_calls.inc); a query's codes lie in the context's scratch words, its
+// skipped intervals (and, before them, the ids of dvo_hip_codebook_query_ids) in the side table, its distance matrix in front of the
+// staged results.  Arguments are checked before anything is launched or changed.  Textually included by capi.hip inside its extern "C" block.
 struct dvo_hip_codebook {
   dvo_hip_context* ctx = nullptr;
   int m = 0, capacity = 0, size = 0, live_count = 0;
@@ -32,17 +30,10 @@ int check_code_frames(dvo_hip_context* ctx, int n, dvo_hip_frame* const* frames,
   int rc = check_frame_count(ctx, n, frames, who);
   if (rc != DVO_HIP_OK) return rc;
   if (n > kCodeMaxFrames) return fail(ctx, DVO_HIP_ERR_INVALID, who, "more than 2^20 frames");
-  long long blocks = 0;                                      // (the frame table counts the frames' blocks of 256 pixels in an int)
-  for (int i = 0; i < n; ++i) {
-    const dvo_hip_frame* f = frames[i];
-    rc = check_frame(ctx, f, who, /*own_context=*/true);
-    if (rc != DVO_HIP_OK) return rc;
-    if (level < 0 || level >= f->levels) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame does not have that level");
-    if (f->lv[level].w > 32767 || f->lv[level].h > 32767) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the level is wider or higher than 32767 pixels");
-    blocks += (static_cast<long long>(f->lv[level].w) * f->lv[level].h + 255) / 256;
-    if (blocks > 0x7fffffffll / 256) return fail(ctx, DVO_HIP_ERR_INVALID, who, "too many pixels for one call");
-  }
-  return DVO_HIP_OK;
+  return check_frames_at_level(ctx, n, frames, level, 1, kMaxPixelBlocks, /*budget_early=*/true, who, [&](int, const dvo_hip_frame* f) -> int {
+    if (f->lv[level].w <= 32767 && f->lv[level].h <= 32767) return DVO_HIP_OK;
+    return fail(ctx, DVO_HIP_ERR_INVALID, who, "the level is wider or higher than 32767 pixels");
+  });
 }
 
 // what the three queries share; the room for n more entries
@@ -63,12 +54,10 @@ int check_room(dvo_hip_context* ctx, const dvo_hip_codebook* b, int n, const cha
 
 // the codes of n checked frames into device memory `dst` (one launch on the main stream; not waited for)
 int encode_frames(dvo_hip_context* ctx, const dvo_hip_codebook* b, int n, dvo_hip_frame* const* frames, int level, uint32_t* dst) {
-  std::vector<MapEntry> entries;
-  for (int i = 0; i < n; ++i) entries.push_back(MapEntry{frames[i], MapPose{}, 1, nullptr});
   int blocks = 0;
-  const int rc = upload_map_entries(ctx, entries, level, &blocks);
+  const int rc = upload_frames(ctx, n, frames, nullptr, level, nullptr, &blocks);
   if (rc != DVO_HIP_OK) return rc;
-  launch_encode_frames(ctx->stream, ctx->map_tbl.as<MapFrame>(), n, b->ferns.as<dvo_hip_fern>(), b->m, dst);
+  launch_encode_frames(ctx->stream, ctx->frame_tbl.as<MapFrame>(), n, b->ferns.as<dvo_hip_fern>(), b->m, dst);
   DVO_HIP_TRY(ctx, hipGetLastError());
   ctx->codebook_encoded += n;
   return DVO_HIP_OK;
@@ -87,21 +76,21 @@ int book_grow(dvo_hip_context* ctx, dvo_hip_codebook* b, int n, uint32_t* ids_ou
 
 uint32_t* book_slot(const dvo_hip_codebook* b, int id) { return b->codes.as<uint32_t>() + size_t(id) * size_t(code_words(b->m)); }
 
-// a query's table into the render scratch, through the ring of pinned slots like every other table there (at most 48 KB)
+// a query's table into the side table, through the ring of pinned slots like every other table there (at most 48 KB)
 int upload_query_table(dvo_hip_context* ctx, const std::vector<uint32_t>& table) {
   const size_t bytes = table.size() * sizeof(uint32_t);
-  DVO_HIP_TRY(ctx, ctx->render_tbl.reserve(bytes));
-  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->render_tbl.p, table.data(), bytes));
+  DVO_HIP_TRY(ctx, ctx->side_tbl.reserve(bytes));
+  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->side_tbl.p, table.data(), bytes));
   return DVO_HIP_OK;
 }
 
-// The query all three entry points end in: n_queries codes lie at the start of the z-buffer scratch.  The distances of a round of
+// The query all three entry points end in: n_queries codes lie at the start of the scratch words.  The distances of a round of
 // queries go straight into the caller's device matrix, else into the staging area, as many queries at a time as option
 // "codebook_round_kb" holds (every offset below is the round's first query q0 times a row).
 int run_query(dvo_hip_context* ctx, dvo_hip_codebook* b, int n_queries, int k, const uint32_t* skip_from, const uint32_t* skip_to,
               dvo_hip_code_match* results_out, uint16_t* distances_out, int out_on_device) {
   const uint32_t n = uint32_t(b->size);
-  const uint32_t* queries = ctx->render_zbuf.as<uint32_t>();
+  const uint32_t* queries = ctx->scratch_words.as<uint32_t>();
   std::vector<uint32_t> skip(size_t(n_queries) * 2, 0u);
   for (int q = 0; q < n_queries && skip_from; ++q) {
     skip[size_t(q) * 2] = skip_from[q];
@@ -117,16 +106,18 @@ int run_query(dvo_hip_context* ctx, dvo_hip_codebook* b, int n_queries, int k, c
     per_round = int(std::max<size_t>(budget / row_bytes, 1));    // (fewer than n_queries; at least one query, whatever the budget)
     if (per_round >= 16) per_round -= per_round % 16;            // whole tiles of 16 queries
   }
-  // staging: the rounds' matrix, then (8-byte aligned) the host-bound result rows
-  const size_t matrix_bytes = direct ? 0 : (row_bytes * size_t(per_round) + 7) / 8 * 8;
-  DVO_HIP_TRY(ctx, ctx->map_stage.reserve(matrix_bytes + (out_on_device ? 0 : rows_bytes) + 8));
-  dvo_hip_code_match* rows = out_on_device ? results_out : reinterpret_cast<dvo_hip_code_match*>(ctx->map_stage.as<char>() + matrix_bytes);
+  // staging: the rounds' matrix, then the host-bound result rows
+  const std::vector<ResultArray> results = {{results_out, rows_bytes, 8}};
+  std::vector<void*> dev;
+  rc = stage_results(ctx, results, out_on_device, &dev, /*scratch=*/direct ? 0 : row_bytes * size_t(per_round));
+  if (rc != DVO_HIP_OK) return rc;
+  dvo_hip_code_match* rows = static_cast<dvo_hip_code_match*>(dev[0]);
   for (int q0 = 0; q0 < n_queries; q0 += per_round) {
     const int nq = std::min(per_round, n_queries - q0);
-    uint16_t* matrix = direct ? distances_out + size_t(q0) * size_t(n) : ctx->map_stage.as<uint16_t>();
+    uint16_t* matrix = direct ? distances_out + size_t(q0) * size_t(n) : ctx->result_stage.as<uint16_t>();
     if (n > 0u)
       launch_code_search(ctx->stream, b->codes.as<uint32_t>(), b->live.as<unsigned char>(), n, b->m, queries + size_t(q0) * size_t(code_words(b->m)),
-                         nq, ctx->render_tbl.as<uint32_t>() + size_t(q0) * 2, matrix);
+                         nq, ctx->side_tbl.as<uint32_t>() + size_t(q0) * 2, matrix);
     launch_code_topk(ctx->stream, matrix, n, nq, k, rows + size_t(q0) * size_t(k));
     DVO_HIP_TRY(ctx, hipGetLastError());
     if (distances_out && !direct && n > 0u)
@@ -134,9 +125,7 @@ int run_query(dvo_hip_context* ctx, dvo_hip_codebook* b, int n_queries, int k, c
                                       out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
   }
   ctx->codebook_queries += n_queries;
-  if (!out_on_device) DVO_HIP_TRY(ctx, hipMemcpyAsync(results_out, rows, rows_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return DVO_HIP_OK;
+  return finish_results(ctx, results, out_on_device, dev);
 }
 
 }  // namespace
@@ -223,16 +212,15 @@ int dvo_hip_frames_encode(dvo_hip_context* ctx, const dvo_hip_codebook* book, in
   int rc = check_book(ctx, book, who, codes_out, "null codes_out");
   if (rc == DVO_HIP_OK) rc = check_code_frames(ctx, n, frames, level, who);
   if (rc != DVO_HIP_OK) return rc;
-  if (out_on_device && !aligned_to(codes_out, 4)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "device codes must be 4-byte aligned");
-  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = size_t(n) * code_bytes(book);
-  if (!out_on_device) DVO_HIP_TRY(ctx, ctx->map_stage.reserve(bytes));
-  uint32_t* dst = out_on_device ? codes_out : ctx->map_stage.as<uint32_t>();
-  rc = encode_frames(ctx, book, n, frames, level, dst);
+  const std::vector<ResultArray> results = {{codes_out, size_t(n) * code_bytes(book), 4}};
+  rc = check_results(ctx, results, out_on_device, who, "null codes_out", "device codes must be 4-byte aligned");
   if (rc != DVO_HIP_OK) return rc;
-  if (!out_on_device) DVO_HIP_TRY(ctx, hipMemcpyAsync(codes_out, dst, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return DVO_HIP_OK;
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<void*> dev;
+  rc = stage_results(ctx, results, out_on_device, &dev);
+  if (rc == DVO_HIP_OK) rc = encode_frames(ctx, book, n, frames, level, static_cast<uint32_t*>(dev[0]));
+  if (rc != DVO_HIP_OK) return rc;
+  return finish_results(ctx, results, out_on_device, dev);
 }
 
 int dvo_hip_codebook_add_frames(dvo_hip_context* ctx, dvo_hip_codebook* book, int n, dvo_hip_frame* const* frames, int level,
@@ -310,8 +298,8 @@ int dvo_hip_codebook_query_frames(dvo_hip_context* ctx, dvo_hip_codebook* book, 
   if (rc == DVO_HIP_OK) rc = check_code_frames(ctx, n_queries, frames, level, who);
   if (rc != DVO_HIP_OK) return rc;
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  DVO_HIP_TRY(ctx, ctx->render_zbuf.reserve(size_t(n_queries) * code_bytes(book)));
-  rc = encode_frames(ctx, book, n_queries, frames, level, ctx->render_zbuf.as<uint32_t>());
+  DVO_HIP_TRY(ctx, ctx->scratch_words.reserve(size_t(n_queries) * code_bytes(book)));
+  rc = encode_frames(ctx, book, n_queries, frames, level, ctx->scratch_words.as<uint32_t>());
   if (rc != DVO_HIP_OK) return rc;
   return run_query(ctx, book, n_queries, k, skip_from_or_null, skip_to_or_null, results_out, distances_out_or_null, out_on_device);
 }
@@ -327,9 +315,9 @@ int dvo_hip_codebook_query_codes(dvo_hip_context* ctx, dvo_hip_codebook* book, i
   if (codes_on_device && !aligned_to(codes, 4)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "device codes must be 4-byte aligned");
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t bytes = size_t(n_queries) * code_bytes(book);
-  DVO_HIP_TRY(ctx, ctx->render_zbuf.reserve(bytes));
+  DVO_HIP_TRY(ctx, ctx->scratch_words.reserve(bytes));
   // (the kernel stages its queries with 16-byte loads: they go through the scratch whatever the caller's alignment)
-  DVO_HIP_TRY(ctx, hipMemcpyAsync(ctx->render_zbuf.p, codes, bytes, codes_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+  DVO_HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_words.p, codes, bytes, codes_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
   if (!codes_on_device) DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the caller's host array)
   return run_query(ctx, book, n_queries, k, skip_from_or_null, skip_to_or_null, results_out, distances_out_or_null, out_on_device);
 }
@@ -345,14 +333,14 @@ int dvo_hip_codebook_query_ids(dvo_hip_context* ctx, dvo_hip_codebook* book, int
   for (int q = 0; q < n_queries; ++q)
     if (ids[q] >= uint32_t(book->size)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "an id beyond the book's size");
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  DVO_HIP_TRY(ctx, ctx->render_zbuf.reserve(size_t(n_queries) * code_bytes(book)));
-  // the ids go through the render scratch as a table of their own; run_query's table replaces it behind the gather, on the same stream
+  DVO_HIP_TRY(ctx, ctx->scratch_words.reserve(size_t(n_queries) * code_bytes(book)));
+  // the ids go through the side table as a table of their own; run_query's table replaces it behind the gather, on the same stream
   // (reserved for that larger table now, so that nothing is reallocated between the two)
-  DVO_HIP_TRY(ctx, ctx->render_tbl.reserve(size_t(n_queries) * 2 * sizeof(uint32_t)));
+  DVO_HIP_TRY(ctx, ctx->side_tbl.reserve(size_t(n_queries) * 2 * sizeof(uint32_t)));
   rc = upload_query_table(ctx, std::vector<uint32_t>(ids, ids + n_queries));
   if (rc != DVO_HIP_OK) return rc;
-  const uint32_t* dev_ids = ctx->render_tbl.as<uint32_t>();
-  launch_gather_codes(ctx->stream, book->codes.as<uint32_t>(), dev_ids, n_queries, book->m, ctx->render_zbuf.as<uint32_t>());
+  const uint32_t* dev_ids = ctx->side_tbl.as<uint32_t>();
+  launch_gather_codes(ctx->stream, book->codes.as<uint32_t>(), dev_ids, n_queries, book->m, ctx->scratch_words.as<uint32_t>());
   DVO_HIP_TRY(ctx, hipGetLastError());
   return run_query(ctx, book, n_queries, k, skip_from_or_null, skip_to_or_null, results_out, distances_out_or_null, out_on_device);
 }

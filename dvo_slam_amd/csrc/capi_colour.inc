@@ -134,10 +134,10 @@ int dvo_hip_frame_download_colour(dvo_hip_context* ctx, dvo_hip_frame* frame, in
     return fail(ctx, DVO_HIP_ERR_INVALID, who, "the level is not level 0 halved (cloud_colour.h)");
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t bytes = size_t(w) * size_t(h) * 4;
-  DVO_HIP_TRY(ctx, ctx->map_stage.reserve(bytes));
-  launch_colour_level(ctx->stream, frame->colour.as<uint32_t>(), frame->lv[0].w, level, w, h, ctx->map_stage.as<uint32_t>());
+  DVO_HIP_TRY(ctx, ctx->result_stage.reserve(bytes));
+  launch_colour_level(ctx->stream, frame->colour.as<uint32_t>(), frame->lv[0].w, level, w, h, ctx->result_stage.as<uint32_t>());
   DVO_HIP_TRY(ctx, hipGetLastError());
-  DVO_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->map_stage.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  DVO_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->result_stage.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
   DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return DVO_HIP_OK;
 }

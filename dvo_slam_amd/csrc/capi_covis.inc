@@ -1,9 +1,7 @@
 // capi_covis.inc -- keyframe covisibility behind the C-ABI (include/dvo_hip.h, dvo_hip_frames_covisibility; semantics: covisibility.h;
-// kernel: covisibility.hip).  The frames reach the kernel through the frame table of the keyframe-map launches (upload_map_entries,
-// capi_map.inc: the launch runs on the main stream behind the builds of the frames, the {I, Z} pairs of the level are built where a frame
-// does not hold them), every listed frame ONCE; the pairs index that table.  The pair table lies in the render scratch, host records are
-// staged in the map staging area: scratch that the map renders and the warps use too, every use ordered on the main stream.
-// Arguments are checked before anything is launched or changed.  Textually included by capi.hip inside its extern "C" block.
+// kernel: covisibility.hip): a call that reads frames at a level (capi_frame_calls.inc), every listed frame ONCE in the frame table; the
+// pairs, in the side table, index it.  Arguments are checked before anything is launched or changed.  Textually included by capi.hip
+// inside its extern "C" block.
 static_assert(sizeof(dvo_hip_covis_params) == 32, "dvo_hip_covis_params: four fields and four reserved words");
 static_assert(sizeof(dvo_hip_covis_record) == 32 && offsetof(dvo_hip_covis_record, photo) == 24, "dvo_hip_covis_record: six counts and a sum");
 
@@ -22,23 +20,16 @@ namespace {
 constexpr int kCovisMaxPairs = 1 << 22;
 constexpr size_t kCovisRingBytes = 32 * 1024;        // pair tables up to this size (585 pairs) go through the ring of pinned slots
 
-// everything a covisibility call is refused for (as check_warp); *max_pixels: the largest a of the pairs
+// everything a covisibility call is refused for but a misaligned device array (as check_warp); *max_pixels: the largest a of the pairs
 int check_covis(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, int n_pairs, const int32_t* pair_a, const int32_t* pair_b,
-                const double* transforms, int level, const dvo_hip_covis_params* params, const dvo_hip_covis_record* records, int out_on_device,
+                const double* transforms, int level, const dvo_hip_covis_params* params, const dvo_hip_covis_record* records,
                 dvo_hip_covis_params* p, long long* max_pixels, const char* who) {
   int rc = check_frame_count(ctx, n_frames, frames, who, pair_a != nullptr && pair_b != nullptr && transforms != nullptr && records != nullptr);
   if (rc != DVO_HIP_OK) return rc;
   if (n_pairs < 1) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
   if (n_pairs > kCovisMaxPairs) return fail(ctx, DVO_HIP_ERR_INVALID, who, "more than 2^22 pairs");   // (before any pair is read)
-  long long blocks = 0;
-  for (int i = 0; i < n_frames; ++i) {
-    const dvo_hip_frame* f = frames[i];
-    rc = check_frame(ctx, f, who, /*own_context=*/true);
-    if (rc != DVO_HIP_OK) return rc;
-    if (level < 0 || level >= f->levels) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame does not have that level");
-    blocks += (static_cast<long long>(f->lv[level].w) * f->lv[level].h + 255) / 256;
-    if (blocks > 0x7fffffffll / 256) return fail(ctx, DVO_HIP_ERR_INVALID, who, "too many pixels for one call");
-  }
+  rc = check_frames_at_level(ctx, n_frames, frames, level, 1, kMaxPixelBlocks, /*budget_early=*/true, who);
+  if (rc != DVO_HIP_OK) return rc;
   *max_pixels = 0;
   for (int k = 0; k < n_pairs; ++k) {
     if (pair_a[k] < 0 || pair_a[k] >= n_frames || pair_b[k] < 0 || pair_b[k] >= n_frames)
@@ -46,16 +37,11 @@ int check_covis(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames
     const FrameLevel& L = frames[pair_a[k]]->lv[level];
     *max_pixels = std::max(*max_pixels, static_cast<long long>(L.w) * L.h);
   }
-  for (size_t k = 0; k < size_t(n_pairs) * 16; ++k)
-    if (!std::isfinite(transforms[k])) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a transform is not finite");
+  if (!transforms_finite(transforms, size_t(n_pairs))) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a transform is not finite");
   *p = params ? *params : dvo_hip_covis_params_default();
   if (!(p->depth_tolerance >= 0.0f) || !(p->depth_tolerance_rel >= 0.0f))
     return fail(ctx, DVO_HIP_ERR_INVALID, who, "the depth tolerances must be >= 0 (no NaN)");
-  if (!(p->min_depth <= p->max_depth)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "need min_depth <= max_depth (no NaN)");
-  for (uint32_t r : p->reserved)
-    if (r != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a reserved field is not 0");
-  if (out_on_device && !aligned_to(records, 8)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "device records must be 8-byte aligned");
-  return DVO_HIP_OK;
+  return check_range_and_reserved(ctx, p->min_depth, p->max_depth, p->reserved, 4, who);
 }
 
 }  // namespace
@@ -67,36 +53,36 @@ int dvo_hip_frames_covisibility(dvo_hip_context* ctx, int n_frames, dvo_hip_fram
   const char* who = "frames_covisibility";
   dvo_hip_covis_params p;
   long long max_pixels = 0;
-  int rc = check_covis(ctx, n_frames, frames, n_pairs, pair_a, pair_b, transforms, level, params_or_null, records_out, out_on_device, &p,
-                       &max_pixels, who);
+  int rc = check_covis(ctx, n_frames, frames, n_pairs, pair_a, pair_b, transforms, level, params_or_null, records_out, &p, &max_pixels, who);
+  if (rc != DVO_HIP_OK) return rc;
+  const size_t record_bytes = size_t(n_pairs) * sizeof(dvo_hip_covis_record);
+  const std::vector<ResultArray> results = {{records_out, record_bytes, 8}};
+  rc = check_results(ctx, results, out_on_device, who, "bad argument", "device records must be 8-byte aligned");
   if (rc != DVO_HIP_OK) return rc;
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t record_bytes = size_t(n_pairs) * sizeof(dvo_hip_covis_record);
-  if (!out_on_device) DVO_HIP_TRY(ctx, ctx->map_stage.reserve(record_bytes));
-  unsigned long long* records = out_on_device ? reinterpret_cast<unsigned long long*>(records_out) : ctx->map_stage.as<unsigned long long>();
+  std::vector<void*> dev;
+  rc = stage_results(ctx, results, out_on_device, &dev);
+  if (rc != DVO_HIP_OK) return rc;
+  unsigned long long* records = static_cast<unsigned long long*>(dev[0]);
   // the frame table: every listed frame once (no pose of it is read: the transform belongs to the pair)
-  std::vector<MapEntry> entries;
-  for (int i = 0; i < n_frames; ++i) entries.push_back(MapEntry{frames[i], MapPose{}, 1, nullptr});
   int blocks = 0;
-  rc = upload_map_entries(ctx, entries, level, &blocks);
+  rc = upload_frames(ctx, n_frames, frames, nullptr, level, nullptr, &blocks);
   if (rc != DVO_HIP_OK) return rc;
   std::vector<CovisPair> pairs(static_cast<size_t>(n_pairs));
   for (int k = 0; k < n_pairs; ++k) pairs[size_t(k)] = CovisPair{pair_a[k], pair_b[k], map_pose_prepare(transforms + size_t(k) * 16)};
   const size_t bytes = pairs.size() * sizeof(CovisPair);
-  DVO_HIP_TRY(ctx, ctx->render_tbl.reserve(bytes));
+  DVO_HIP_TRY(ctx, ctx->side_tbl.reserve(bytes));
   if (bytes <= kCovisRingBytes) {
-    DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->render_tbl.p, pairs.data(), bytes));
+    DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->side_tbl.p, pairs.data(), bytes));
   } else {
     // a long pair list (n x n of 256 keyframes is 3.5 MB) goes past the ring of pinned slots, which would grow to 48 slots of that size
     // and keep a host copy: one plain copy, ordered on the stream; the call waits for the stream before `pairs` goes out of scope
-    ctx->tables.forget(ctx->render_tbl.p);
-    DVO_HIP_TRY(ctx, hipMemcpyAsync(ctx->render_tbl.p, pairs.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    ctx->tables.forget(ctx->side_tbl.p);
+    DVO_HIP_TRY(ctx, hipMemcpyAsync(ctx->side_tbl.p, pairs.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
   }
   DVO_HIP_TRY(ctx, hipMemsetAsync(records, 0, record_bytes, ctx->stream));
-  launch_covisibility(ctx->stream, ctx->map_tbl.as<MapFrame>(), ctx->render_tbl.as<CovisPair>(), n_pairs, max_pixels, p, records);
+  launch_covisibility(ctx->stream, ctx->frame_tbl.as<MapFrame>(), ctx->side_tbl.as<CovisPair>(), n_pairs, max_pixels, p, records);
   DVO_HIP_TRY(ctx, hipGetLastError());
   ctx->covisibility_pairs += n_pairs;
-  if (!out_on_device) DVO_HIP_TRY(ctx, hipMemcpyAsync(records_out, records, record_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return DVO_HIP_OK;
+  return finish_results(ctx, results, out_on_device, dev);
 }

@@ -33,18 +33,9 @@ MapTable map_table(const dvo_hip_map* map) {
 int check_map_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float min_depth,
                      float max_depth, const char* who, int entries_per_frame = 1) {
   int rc = check_frame_count(ctx, n_frames, frames, who, poses != nullptr);
+  if (rc == DVO_HIP_OK) rc = check_range_and_reserved(ctx, min_depth, max_depth, nullptr, 0, who);
   if (rc != DVO_HIP_OK) return rc;
-  if (!(min_depth <= max_depth)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "need min_depth <= max_depth (no NaN)");
-  long long blocks = 0;
-  for (int i = 0; i < n_frames; ++i) {
-    const dvo_hip_frame* f = frames[i];
-    rc = check_frame(ctx, f, who, /*own_context=*/true);
-    if (rc != DVO_HIP_OK) return rc;
-    if (level < 0 || level >= f->levels) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame does not have that level");
-    blocks += entries_per_frame * ((static_cast<long long>(f->lv[level].w) * f->lv[level].h + 255) / 256);
-  }
-  if (blocks > 0x7fffffffll) return fail(ctx, DVO_HIP_ERR_INVALID, who, "too many pixels for one call");
-  return DVO_HIP_OK;
+  return check_frames_at_level(ctx, n_frames, frames, level, entries_per_frame, kMaxBlocks, /*budget_early=*/false, who);
 }
 
 // ... and, for a coloured map, that every frame carries colour and that its level is level 0 halved (cloud_colour.h: every block lies inside)
@@ -57,69 +48,6 @@ int check_map_colour(dvo_hip_context* ctx, const dvo_hip_map* map, int n_frames,
       return fail(ctx, DVO_HIP_ERR_INVALID, who, "the level is not level 0 halved (cloud_colour.h)");
   }
   return DVO_HIP_OK;
-}
-
-// one entry of a launch's frame table: a frame under a pose, added (+1) or -- dvo_hip_map_remove, dvo_hip_map_move -- subtracted (-1)
-struct MapEntry {
-  dvo_hip_frame* frame;
-  MapPose pose;
-  int sign;
-  float* out;                          // MapFrame::out (k_world_points), else null
-};
-
-// The frame table of one launch on the main stream: the {I, Z} pairs of `level` come from plane C where the frame holds it, else from the
-// taps A (built now where missing: what dvo_hip_frame_download_plane reads planes 0 and 1 from).  A frame may stand in several entries.
-// coloured: the entries also name the frames' colour planes (checked: check_map_colour).
-int upload_map_entries(dvo_hip_context* ctx, const std::vector<MapEntry>& entries, int level, int* total_blocks, bool coloured = false) {
-  std::vector<dvo_hip_frame*> frames;
-  for (const MapEntry& e : entries)
-    if (std::find(frames.begin(), frames.end(), e.frame) == frames.end()) frames.push_back(e.frame);
-  int rc = wait_for_build(ctx, int(frames.size()), frames.data());
-  if (rc != DVO_HIP_OK) return rc;
-  // the taps of the frames that hold neither flavour at this level, one ensure_roles per camera (it takes frames of one camera)
-  std::vector<dvo_hip_frame*> missing;
-  for (dvo_hip_frame* f : frames) {
-    const FrameLevel& L = f->lv[level];
-    if (!((L.cur_have & kCurC) && L.C) && !(L.cur_have & kCurAB)) missing.push_back(f);
-  }
-  while (!missing.empty()) {
-    std::vector<dvo_hip_frame*> group, rest;
-    for (dvo_hip_frame* f : missing) (f->cam == missing[0]->cam ? group : rest).push_back(f);
-    rc = ensure_roles(ctx, int(group.size()), group.data(), 0, level, level, 0.0f, 0.0f);
-    if (rc != DVO_HIP_OK) return rc;
-    missing.swap(rest);
-  }
-  std::vector<MapFrame> host(entries.size() + 1);
-  int blocks = 0;
-  for (size_t i = 0; i < entries.size(); ++i) {
-    const dvo_hip_frame* f = entries[i].frame;
-    const FrameLevel& L = f->lv[level];
-    MapFrame& m = host[i];
-    const bool from_c = (L.cur_have & kCurC) && L.C;
-    m.iz = from_c ? reinterpret_cast<const float*>(L.C) : reinterpret_cast<const float*>(L.A);
-    m.stride = from_c ? 2 : 4;
-    m.out = entries[i].out;
-    m.pose = entries[i].pose;
-    std::memcpy(m.K, f->cam->K[level], sizeof m.K);
-    m.w = L.w;
-    m.h = L.h;
-    m.first_block = blocks;
-    m.sign = entries[i].sign;
-    m.colour = coloured ? f->colour.as<uint32_t>() : nullptr;
-    m.colour_pitch = f->lv[0].w;
-    m.shift = level;
-    blocks += (L.w * L.h + 255) / 256;
-  }
-  *total_blocks = blocks;
-  return upload_block_table(ctx, ctx->map_tbl, host, blocks);
-}
-
-// ... of n frames under poses[16 * i ..], all added.  outs (may be null): MapFrame::out.
-int upload_map_frames(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* frames, const double* poses, int level, float* const* outs,
-                      int* total_blocks, bool coloured = false) {
-  std::vector<MapEntry> entries;
-  for (int i = 0; i < n_frames; ++i) entries.push_back(MapEntry{frames[i], map_pose_prepare(poses + size_t(i) * 16), 1, outs ? outs[i] : nullptr});
-  return upload_map_entries(ctx, entries, level, total_blocks, coloured);
 }
 
 // (only k_map_insert moves the candidates, the dropped and the unmatched points, and every insert, remove and move ends with this read:
@@ -245,17 +173,17 @@ int map_update(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_fra
   if (move && !poses_new) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
   if (!insert && map->dropped != 0)
     return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map has dropped points since its last clear or rehash: what it holds of a frame is not known (dvo_hip_map_rehash into a larger table, or dvo_hip_map_clear)");
-  std::vector<MapEntry> entries;
+  std::vector<FrameEntry> entries;
   int removes = 0, inserts = 0;
   for (int i = 0; i < n_frames; ++i) {
     const MapPose at = map_pose_prepare(poses + size_t(i) * 16);
     if (move) {
       const MapPose to = map_pose_prepare(poses_new + size_t(i) * 16);
       if (std::memcmp(&at, &to, sizeof at) == 0) continue;     // (the same twelve floats: the same points, nothing to do)
-      entries.push_back(MapEntry{frames[i], at, -1, nullptr});
-      entries.push_back(MapEntry{frames[i], to, 1, nullptr});
+      entries.push_back(FrameEntry{frames[i], at, -1, nullptr});
+      entries.push_back(FrameEntry{frames[i], to, 1, nullptr});
     } else {
-      entries.push_back(MapEntry{frames[i], at, insert ? 1 : -1, nullptr});
+      entries.push_back(FrameEntry{frames[i], at, insert ? 1 : -1, nullptr});
     }
     inserts += insert || move;
     removes += !insert;
@@ -263,9 +191,9 @@ int map_update(dvo_hip_context* ctx, dvo_hip_map* map, int n_frames, dvo_hip_fra
   if (entries.empty()) return DVO_HIP_OK;
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   int blocks = 0;
-  rc = upload_map_entries(ctx, entries, level, &blocks, map->coloured);
+  rc = upload_frame_entries(ctx, entries, level, &blocks, map->coloured);
   if (rc != DVO_HIP_OK) return rc;
-  launch_map_insert(ctx->stream, ctx->map_tbl.as<MapFrame>(), int(entries.size()), blocks, map_table(map), min_depth, max_depth, /*mixed=*/!insert);
+  launch_map_insert(ctx->stream, ctx->frame_tbl.as<MapFrame>(), int(entries.size()), blocks, map_table(map), min_depth, max_depth, /*mixed=*/!insert);
   return finish_map_write(ctx, map, inserts, removes, who, "not the frame content, level, pose or depth range of the insertion?");
 }
 
@@ -391,8 +319,7 @@ struct ReadOutArray {
 // The read-out of a map's live voxels on the main stream (dvo_hip_map_extract, dvo_hip_map_extract_colour, dvo_hip_map_export):
 // pass(n, dev) walks the table and writes at most n records to the device arrays dev[k] (null: not wanted).  The first pass counts
 // (n = 0, every array null; c: the counters behind it, c[kMapCntCursor] the live voxels), the second fills *take = min(live, max) records:
-// a host destination is staged for just that many out of ctx->map_stage and copied out; one synchronise.  outs: in the order of falling
-// record sizes, powers of two, so every staged array is aligned to its record.
+// a host destination is staged for just that many and copied out (stage_results, every array aligned to its record); one synchronise.
 int map_read_out(dvo_hip_context* ctx, dvo_hip_map* map, size_t max, const std::vector<ReadOutArray>& outs, int out_on_device,
                  const std::function<hipError_t(unsigned long long, void* const*)>& pass, unsigned long long c[kMapCounters], size_t* take) {
   *take = 0;
@@ -400,24 +327,18 @@ int map_read_out(dvo_hip_context* ctx, dvo_hip_map* map, size_t max, const std::
   std::vector<void*> dev(outs.size(), nullptr);
   DVO_HIP_TRY(ctx, pass(0, dev.data()));
   DVO_HIP_TRY(ctx, hipGetLastError());
-  const int rc = read_map_counters(ctx, map, c);
+  int rc = read_map_counters(ctx, map, c);
   if (rc != DVO_HIP_OK) return rc;
   const size_t n = size_t(c[kMapCntCursor] < max ? c[kMapCntCursor] : max);
   if (n == 0) return DVO_HIP_OK;
-  size_t bytes = 0;
-  for (const ReadOutArray& o : outs) bytes += o.dst ? n * o.record_bytes : 0;
-  if (!out_on_device) DVO_HIP_TRY(ctx, ctx->map_stage.reserve(bytes));
-  size_t at = 0;
-  for (size_t k = 0; k < outs.size(); ++k) {
-    if (!outs[k].dst) continue;
-    dev[k] = out_on_device ? outs[k].dst : ctx->map_stage.as<char>() + at;
-    at += n * outs[k].record_bytes;
-  }
+  std::vector<ResultArray> results;
+  for (const ReadOutArray& o : outs) results.push_back(ResultArray{o.dst, n * o.record_bytes, o.record_bytes});
+  rc = stage_results(ctx, results, out_on_device, &dev);
+  if (rc != DVO_HIP_OK) return rc;
   DVO_HIP_TRY(ctx, pass(n, dev.data()));
   DVO_HIP_TRY(ctx, hipGetLastError());
-  for (size_t k = 0; k < outs.size() && !out_on_device; ++k)
-    if (outs[k].dst) DVO_HIP_TRY(ctx, hipMemcpyAsync(outs[k].dst, dev[k], n * outs[k].record_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  rc = finish_results(ctx, results, out_on_device, dev);
+  if (rc != DVO_HIP_OK) return rc;
   *take = n;
   return DVO_HIP_OK;
 }
@@ -481,19 +402,13 @@ struct MergeSource {
 
 bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; }
 
-bool pose_finite(const double* T16) {
-  for (int k = 0; k < 16; ++k)
-    if (!std::isfinite(T16[k])) return false;
-  return true;
-}
-
 // what every merge checks of one source once its pointers are known to be good: the sign, the leaf, the pose
 int check_merge_source(dvo_hip_context* ctx, const dvo_hip_map* dst, float leaf_src, int sign, const double* pose_or_null, const char* who) {
   if (sign != 1 && sign != -1) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a sign is +1 or -1");
   if (!(leaf_src > 0.0f && leaf_src < INFINITY)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the source's leaf size must be finite and > 0");
   if (!pose_or_null && !same_bits(leaf_src, dst->leaf))
     return fail(ctx, DVO_HIP_ERR_INVALID, who, "a plain merge adds voxels as they are: the source's leaf must be the destination's (a posed merge bins anew)");
-  if (pose_or_null && !pose_finite(pose_or_null)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a pose has an entry that is not finite");
+  if (pose_or_null && !transforms_finite(pose_or_null, 1)) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a pose has an entry that is not finite");
   if (sign < 0 && dst->dropped != 0)
     return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map has dropped points since its last clear or rehash: what it holds of a sub-map is not known (dvo_hip_map_rehash into a larger table, or dvo_hip_map_clear)");
   return DVO_HIP_OK;
@@ -559,9 +474,9 @@ int run_map_merge(dvo_hip_context* ctx, dvo_hip_map* dst, const std::vector<Merg
     e.first_block = at;
     at += int((s.count + 255) / 256);
   }
-  const int rc = upload_block_table(ctx, ctx->map_tbl, host, at);
+  const int rc = upload_block_table(ctx, ctx->frame_tbl, host, at);
   if (rc != DVO_HIP_OK) return rc;
-  launch_map_merge(ctx->stream, ctx->map_tbl.as<MapMergeEntry>(), int(sources.size()), at, map_table(dst), posed);
+  launch_map_merge(ctx->stream, ctx->frame_tbl.as<MapMergeEntry>(), int(sources.size()), at, map_table(dst), posed);
   return finish_map_write(ctx, dst, 0, 0, who, "not the sub-map, or not the pose, that was merged?");
 }
 
@@ -692,8 +607,8 @@ int map_merge_records(dvo_hip_context* ctx, dvo_hip_map* dst, size_t n_records, 
   s.normals = static_cast<const MapNormalSlot*>(normals_or_null);
   if (!on_device) {
     // host records: staged on the main stream, then the same kernel
-    DVO_HIP_TRY(ctx, ctx->map_stage.reserve(n_records * (sizeof(MapSlot) + sizeof(MapColourSlot) + sizeof(MapNormalSlot))));
-    char* stage = ctx->map_stage.as<char>();
+    DVO_HIP_TRY(ctx, ctx->result_stage.reserve(n_records * (sizeof(MapSlot) + sizeof(MapColourSlot) + sizeof(MapNormalSlot))));
+    char* stage = ctx->result_stage.as<char>();
     DVO_HIP_TRY(ctx, hipMemcpyAsync(stage, records, n_records * sizeof(MapSlot), hipMemcpyHostToDevice, ctx->stream));
     s.slots = reinterpret_cast<const MapSlot*>(stage);
     if (colour_or_null) {
@@ -738,34 +653,19 @@ int frames_organised(dvo_hip_context* ctx, int n_frames, dvo_hip_frame* const* f
   int rc = check_map_frames(ctx, n_frames, frames, poses, level, min_depth, max_depth, who);
   if (rc != DVO_HIP_OK) return rc;
   if (!out) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
-  size_t pixels = 0;
-  for (int i = 0; i < n_frames; ++i) {
-    if (!out[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null output");
-    if (out_on_device && reinterpret_cast<uintptr_t>(out[i]) % 16 != 0) return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device output must be 16-byte aligned");
-    pixels += size_t(frames[i]->lv[level].w) * frames[i]->lv[level].h;
-  }
-  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::vector<float*> staged;
-  if (!out_on_device) {
-    DVO_HIP_TRY(ctx, ctx->map_stage.reserve(pixels * 16));
-    staged.resize(size_t(n_frames));
-    size_t at = 0;
-    for (int i = 0; i < n_frames; ++i) {
-      staged[size_t(i)] = ctx->map_stage.as<float>() + at * 4;
-      at += size_t(frames[i]->lv[level].w) * frames[i]->lv[level].h;
-    }
-  }
-  int blocks = 0;
-  rc = upload_map_frames(ctx, n_frames, frames, poses, level, out_on_device ? out : staged.data(), &blocks);
+  const std::vector<ResultArray> results = frame_planes(n_frames, frames, level, &out, 1, 16);
+  rc = check_results(ctx, results, out_on_device, who, "null output", "a device output must be 16-byte aligned");
   if (rc != DVO_HIP_OK) return rc;
-  if (normals) launch_frame_normals(ctx->stream, ctx->map_tbl.as<MapFrame>(), n_frames, blocks, min_depth, max_depth);
-  else launch_world_points(ctx->stream, ctx->map_tbl.as<MapFrame>(), n_frames, blocks, min_depth, max_depth);
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<void*> dev;
+  rc = stage_results(ctx, results, out_on_device, &dev);
+  int blocks = 0;
+  if (rc == DVO_HIP_OK) rc = upload_frames(ctx, n_frames, frames, poses, level, dev.data(), &blocks);
+  if (rc != DVO_HIP_OK) return rc;
+  if (normals) launch_frame_normals(ctx->stream, ctx->frame_tbl.as<MapFrame>(), n_frames, blocks, min_depth, max_depth);
+  else launch_world_points(ctx->stream, ctx->frame_tbl.as<MapFrame>(), n_frames, blocks, min_depth, max_depth);
   DVO_HIP_TRY(ctx, hipGetLastError());
-  if (!out_on_device)
-    for (int i = 0; i < n_frames; ++i)
-      DVO_HIP_TRY(ctx, hipMemcpyAsync(out[i], staged[size_t(i)], size_t(frames[i]->lv[level].w) * frames[i]->lv[level].h * 16, hipMemcpyDeviceToHost, ctx->stream));
-  DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  return DVO_HIP_OK;
+  return finish_results(ctx, results, out_on_device, dev);
 }
 
 }  // namespace
@@ -806,35 +706,33 @@ int check_render(dvo_hip_context* ctx, const dvo_hip_map* map, int n_views, int 
   return DVO_HIP_OK;
 }
 
-// the view table of a render on the main stream: n MapView, then n RenderPlanes; and the z-buffers
-int upload_views(dvo_hip_context* ctx, int n_views, int width, int height, const float* K, const double* poses, float* const* I, float* const* Z) {
+// the view table of a render on the main stream: n MapView, then n RenderPlanes (view i writes planes[2 i] and, its depth, planes[2 i + 1]);
+// and the z-buffers
+int upload_views(dvo_hip_context* ctx, int n_views, int width, int height, const float* K, const double* poses, void* const* planes) {
   const size_t views_bytes = size_t(n_views) * sizeof(MapView), bytes = views_bytes + size_t(n_views) * sizeof(RenderPlanes);
   std::vector<char> host(bytes);
   for (int i = 0; i < n_views; ++i) {
     const MapView v = map_view_prepare(poses + size_t(i) * 16, K, width, height);
-    const RenderPlanes o = {I[i], Z[i]};
+    const RenderPlanes o = {static_cast<float*>(planes[2 * i]), static_cast<float*>(planes[2 * i + 1])};
     std::memcpy(host.data() + size_t(i) * sizeof(MapView), &v, sizeof v);
     std::memcpy(host.data() + views_bytes + size_t(i) * sizeof(RenderPlanes), &o, sizeof o);
   }
-  DVO_HIP_TRY(ctx, ctx->render_tbl.reserve(bytes));
-  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->render_tbl.p, host.data(), bytes));
-  DVO_HIP_TRY(ctx, ctx->render_zbuf.reserve(size_t(n_views) * size_t(width) * size_t(height) * sizeof(unsigned long long)));
+  DVO_HIP_TRY(ctx, ctx->side_tbl.reserve(bytes));
+  DVO_HIP_TRY(ctx, ctx->tables.upload(ctx->stream, ctx->side_tbl.p, host.data(), bytes));
+  DVO_HIP_TRY(ctx, ctx->scratch_words.reserve(size_t(n_views) * size_t(width) * size_t(height) * sizeof(unsigned long long)));
   return DVO_HIP_OK;
 }
 
-// n pairs of planes of `plane` bytes each in one block of the context, (re)allocated here: pair i's first plane at plane * 2i, its second behind it
-int reserve_plane_pairs(dvo_hip_context* ctx, DevBuf& block, size_t plane, int n, std::vector<float*>* first, std::vector<float*>* second) {
+// n pairs of planes of `plane` bytes each in one block of the context, (re)allocated here: pair i's first plane is planes[2 i], its second behind it
+int reserve_plane_pairs(dvo_hip_context* ctx, DevBuf& block, size_t plane, int n, std::vector<void*>* planes) {
   DVO_HIP_TRY(ctx, block.reserve(plane * 2 * size_t(n)));
-  for (int i = 0; i < n; ++i) {
-    first->push_back(reinterpret_cast<float*>(block.as<char>() + plane * (2 * size_t(i))));
-    second->push_back(reinterpret_cast<float*>(block.as<char>() + plane * (2 * size_t(i) + 1)));
-  }
+  for (size_t k = 0; k < 2 * size_t(n); ++k) planes->push_back(block.as<char>() + plane * k);
   return DVO_HIP_OK;
 }
 
-const MapView* render_views(const dvo_hip_context* ctx) { return ctx->render_tbl.as<MapView>(); }
+const MapView* render_views(const dvo_hip_context* ctx) { return ctx->side_tbl.as<MapView>(); }
 const RenderPlanes* render_outs(const dvo_hip_context* ctx, int n_views) {
-  return reinterpret_cast<const RenderPlanes*>(ctx->render_tbl.as<char>() + size_t(n_views) * sizeof(MapView));
+  return reinterpret_cast<const RenderPlanes*>(ctx->side_tbl.as<char>() + size_t(n_views) * sizeof(MapView));
 }
 
 }  // namespace
@@ -865,48 +763,30 @@ int map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views, int width, i
   if (colour && !map->coloured) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no colour (dvo_hip_map_create_ex, DVO_HIP_MAP_COLOUR)");
   if (normals && !map->with_normals) return fail(ctx, DVO_HIP_ERR_INVALID, who, "the map holds no normals (dvo_hip_map_create_ex, DVO_HIP_MAP_NORMALS)");
   if (!first_out || !depth_out) return fail(ctx, DVO_HIP_ERR_INVALID, who, "bad argument");
-  for (int i = 0; i < n_views; ++i) {
-    if (!first_out[i] || !depth_out[i]) return fail(ctx, DVO_HIP_ERR_INVALID, who, "null output");
-    if (out_on_device && (!aligned_to(first_out[i], 16) || !aligned_to(depth_out[i], 16)))
-      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a device plane must be 16-byte aligned");
-  }
-  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t pixels = size_t(width) * size_t(height), plane = (pixels * 4 + 15) & ~size_t(15), first_bytes = pixels * (normals ? 16 : 4);
+  const size_t pixels = size_t(width) * size_t(height);
   // (RenderPlanes::I holds the address of the uint32 rgba plane of a colour view: k_render_resolve stores the bits as they are; of a
-  // normals view the address of the plane of records)
-  std::vector<float*> si, sz;
-  for (int i = 0; i < n_views && out_on_device; ++i) {
-    si.push_back(static_cast<float*>(first_out[i]));
-    sz.push_back(depth_out[i]);
+  // normals view the address of the plane of 16-byte records)
+  std::vector<ResultArray> results;
+  for (int i = 0; i < n_views; ++i) {
+    results.push_back(ResultArray{first_out[i], pixels * (normals ? 16 : 4), 16});
+    results.push_back(ResultArray{depth_out[i], pixels * 4, 16});
   }
-  if (!out_on_device && normals) {
-    // a view's records, then its depth plane: 5 planes of `plane` bytes per view, every record plane 16-byte aligned
-    DVO_HIP_TRY(ctx, ctx->map_stage.reserve(plane * 5 * size_t(n_views)));
-    for (int i = 0; i < n_views; ++i) {
-      si.push_back(reinterpret_cast<float*>(ctx->map_stage.as<char>() + plane * (5 * size_t(i))));
-      sz.push_back(reinterpret_cast<float*>(ctx->map_stage.as<char>() + plane * (5 * size_t(i) + 4)));
-    }
-  } else if (!out_on_device) {
-    rc = reserve_plane_pairs(ctx, ctx->map_stage, plane, n_views, &si, &sz);
-  }
-  if (rc == DVO_HIP_OK) rc = upload_views(ctx, n_views, width, height, K, poses, si.data(), sz.data());
+  rc = check_results(ctx, results, out_on_device, who, "null output", "a device plane must be 16-byte aligned", /*group=*/2);
+  if (rc != DVO_HIP_OK) return rc;
+  DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<void*> dev;
+  rc = stage_results(ctx, results, out_on_device, &dev);
+  if (rc == DVO_HIP_OK) rc = upload_views(ctx, n_views, width, height, K, poses, dev.data());
   if (rc != DVO_HIP_OK) return rc;
   if (normals)
     launch_map_render_normals(ctx->stream, map_table(map), render_views(ctx), render_outs(ctx, n_views), n_views, (long long)pixels, args,
-                              ctx->render_zbuf.as<unsigned long long>());
+                              ctx->scratch_words.as<unsigned long long>());
   else
     launch_map_render(ctx->stream, map_table(map), render_views(ctx), render_outs(ctx, n_views), n_views, (long long)pixels, args,
-                      ctx->render_zbuf.as<unsigned long long>(), colour);
+                      ctx->scratch_words.as<unsigned long long>(), colour);
   DVO_HIP_TRY(ctx, hipGetLastError());
   ctx->map_renders += n_views;
-  if (!out_on_device) {
-    for (int i = 0; i < n_views; ++i) {
-      DVO_HIP_TRY(ctx, hipMemcpyAsync(first_out[i], si[size_t(i)], first_bytes, hipMemcpyDeviceToHost, ctx->stream));
-      DVO_HIP_TRY(ctx, hipMemcpyAsync(depth_out[i], sz[size_t(i)], pixels * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return DVO_HIP_OK;
+  return out_on_device ? DVO_HIP_OK : finish_results(ctx, results, out_on_device, dev);   // (device planes are not waited for)
 }
 
 }  // namespace
@@ -934,13 +814,11 @@ int dvo_hip_map_render_frames(dvo_hip_context* ctx, dvo_hip_map* map, int n_fram
   rc = check_frame_count(ctx, n_frames, frames, who, poses != nullptr);
   if (rc != DVO_HIP_OK) return rc;
   if (flags & DVO_HIP_INGEST_DEFER) return fail(ctx, DVO_HIP_ERR_INVALID, who, "DVO_HIP_INGEST_DEFER: a render is not recorded");
-  for (int i = 0; i < n_frames; ++i) {
-    const dvo_hip_frame* f = frames[i];
-    rc = check_frame(ctx, f, who, /*own_context=*/true);
-    if (rc != DVO_HIP_OK) return rc;
-    if (f->lens_on || f->rig_on || f->filter_on)
-      return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a lens, a depth rig or a depth filter takes raw sensor planes; rendered planes are rectified, registered and free of sensor noise already");
-  }
+  rc = check_frames_at_level(ctx, n_frames, frames, 0, 1, kMaxBlocks, /*budget_early=*/false, who, [&](int, const dvo_hip_frame* f) -> int {
+    if (!(f->lens_on || f->rig_on || f->filter_on)) return DVO_HIP_OK;
+    return fail(ctx, DVO_HIP_ERR_INVALID, who, "a frame that carries a lens, a depth rig or a depth filter takes raw sensor planes; rendered planes are rectified, registered and free of sensor noise already");
+  });
+  if (rc != DVO_HIP_OK) return rc;
   const CameraGeom* cam = frames[0]->cam;
   const int width = frames[0]->lv[0].w, height = frames[0]->lv[0].h;
   RenderArgs args;
@@ -950,18 +828,19 @@ int dvo_hip_map_render_frames(dvo_hip_context* ctx, dvo_hip_map* map, int n_fram
   // the planes the frames ingest: scratch of the context.  Its last readers are the builds of the previous call's frames, which the main
   // stream waits for at the end of that call
   const size_t pixels = size_t(width) * size_t(height), plane = (pixels * 4 + 255) & ~size_t(255);
-  std::vector<float*> pi, pz;
-  rc = reserve_plane_pairs(ctx, ctx->render_planes, plane, n_frames, &pi, &pz);
+  std::vector<void*> planes;
+  rc = reserve_plane_pairs(ctx, ctx->render_frame_planes, plane, n_frames, &planes);
   if (rc != DVO_HIP_OK) return rc;
-  const std::vector<const void*> ci(pi.begin(), pi.end()), cz(pz.begin(), pz.end());
+  std::vector<const void*> ci, cz;
+  for (size_t k = 0; k < planes.size(); ++k) (k % 2 ? cz : ci).push_back(planes[k]);
   IngestSource src{ci.data(), DVO_HIP_PIXEL_F32, 0, cz.data(), 1.0f, DVO_HIP_DEPTH_F32, 0};
   IngestSource probe = src;
   rc = check_ingest(ctx, who, n_frames, frames, &probe, /*plain_ok=*/true, role, cfg);   // (role, cfg, one camera: before anything is launched)
   if (rc != DVO_HIP_OK) return rc;
-  rc = upload_views(ctx, n_frames, width, height, cam->K[0], poses, pi.data(), pz.data());
+  rc = upload_views(ctx, n_frames, width, height, cam->K[0], poses, planes.data());
   if (rc != DVO_HIP_OK) return rc;
   launch_map_render(ctx->stream, map_table(map), render_views(ctx), render_outs(ctx, n_frames), n_frames, (long long)pixels, args,
-                    ctx->render_zbuf.as<unsigned long long>(), /*colour=*/false);
+                    ctx->scratch_words.as<unsigned long long>(), /*colour=*/false);
   DVO_HIP_TRY(ctx, hipGetLastError());
   DVO_HIP_TRY(ctx, hipEventRecord(ctx->render_done, ctx->stream));
   DVO_HIP_TRY(ctx, hipStreamWaitEvent(ctx->build_stream, ctx->render_done, 0));
@@ -981,16 +860,16 @@ int dvo_hip_time_map_render(dvo_hip_context* ctx, dvo_hip_map* map, int n_views,
   DVO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t pixels = size_t(width) * size_t(height), plane = (pixels * 4 + 255) & ~size_t(255);
   DVO_HIP_TRY(ctx, hipStreamSynchronize(ctx->build_stream));   // (the scratch planes may still be read by an ingest)
-  std::vector<float*> pi, pz;
-  rc = reserve_plane_pairs(ctx, ctx->render_planes, plane, n_views, &pi, &pz);
-  if (rc == DVO_HIP_OK) rc = upload_views(ctx, n_views, width, height, K, poses, pi.data(), pz.data());
+  std::vector<void*> planes;
+  rc = reserve_plane_pairs(ctx, ctx->render_frame_planes, plane, n_views, &planes);
+  if (rc == DVO_HIP_OK) rc = upload_views(ctx, n_views, width, height, K, poses, planes.data());
   if (rc != DVO_HIP_OK) return rc;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   hipError_t e = hipSuccess;
   for (hipEvent_t& x : ev)
     if (e == hipSuccess) e = hipEventCreate(&x);
   std::vector<float> t[3];
-  unsigned long long* zbuf = ctx->render_zbuf.as<unsigned long long>();
+  unsigned long long* zbuf = ctx->scratch_words.as<unsigned long long>();
   const MapTable table = map_table(map);
   for (int r = 0; r < reps && e == hipSuccess; ++r) {
     e = hipEventRecord(ev[0], ctx->stream);

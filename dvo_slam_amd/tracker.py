@@ -791,20 +791,44 @@ def _address(a):
     return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
 
 
+def _pyramids_at_level(pyramids, level, who, then=None, others=(), limit=None, ctx=None, foreign="the pyramids belong to different contexts"):
+    """The pyramids of a call that reads them at one level, or ValueError / TypeError: a list that is not empty (limit: and no longer
+    than that), an integer level that every pyramid -- and every one of `others` -- has, and one context: ctx, else the first pyramid's
+    (False: any; foreign: what the message says of another).  then: called once the list has passed, before the level is looked at (the
+    call's other arguments, which it refuses first); its value is returned."""
+    if len(pyramids) < 1:
+        raise ValueError("%s: no pyramids" % who)
+    if limit is not None and len(pyramids) > limit:
+        raise ValueError("%s: %d pyramids, one call takes %d" % (who, len(pyramids), limit))
+    value = then() if then else None
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+        raise TypeError("%s: level must be an integer" % who)
+    ctx = pyramids[0].ctx if ctx is None else ctx
+    for p in list(pyramids) + list(others):
+        if not 0 <= level < p.levels:
+            raise ValueError("%s: a pyramid of %d levels has no level %d" % (who, p.levels, level))
+        if ctx is not False and p.ctx is not ctx:
+            raise ValueError("%s: %s" % (who, foreign))
+    return value
+
+
+def _level_outputs(pyramids, level, count, trailing, device):
+    """count lists of one float32 output array [h, w] + trailing per pyramid at `level`, and their pointer arrays"""
+    ctx = pyramids[0].ctx
+    shapes = []
+    for p in pyramids:
+        w, h = C.c_int(), C.c_int()
+        ctx.check(ctx._lib.dvo_hip_frame_info(p.ptr, level, C.byref(w), C.byref(h), None))
+        shapes.append((h.value, w.value) + trailing)
+    out = [[_out_array(ctx, s, np.float32, device) for s in shapes] for _ in range(count)]
+    return out, [device_pointer_array([_address(a) for a in arrays]) for arrays in out]
+
+
 def _map_frames_args(pyramids, poses, level, min_depth, max_depth, who):
     """(n, poses as a contiguous [n, 4, 4] float64 array) of a keyframe-map call, or ValueError / TypeError: nothing reaches the library
     with a pose that is not 4 x 4, mismatched lengths, a level a pyramid does not have or an empty depth range."""
     n = len(pyramids)
-    if n < 1:
-        raise ValueError("%s: no pyramids" % who)
-    T = _pose_array(poses, n, who)
-    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
-        raise TypeError("%s: level must be an integer" % who)
-    for p in pyramids:
-        if not 0 <= level < p.levels:
-            raise ValueError("%s: a pyramid of %d levels has no level %d" % (who, p.levels, level))
-        if p.ctx is not pyramids[0].ctx:
-            raise ValueError("%s: the pyramids belong to different contexts" % who)
+    T = _pyramids_at_level(pyramids, level, who, then=lambda: _pose_array(poses, n, who))
     if not float(min_depth) <= float(max_depth):
         raise ValueError("%s: need min_depth <= max_depth (no NaN)" % who)
     return n, T
@@ -821,15 +845,9 @@ def _organised_batch(name, pyramids, poses, level, min_depth, max_depth, device)
     """world_points_batch() and normals_batch(): dvo_hip_frames_<name> into one [h, w, 4] float32 array per pyramid"""
     n, T = _map_frames_args(pyramids, poses, level, min_depth, max_depth, name + "_batch")
     ctx = pyramids[0].ctx
-    shapes = []
-    for p in pyramids:
-        w, h = C.c_int(), C.c_int()
-        ctx.check(ctx._lib.dvo_hip_frame_info(p.ptr, level, C.byref(w), C.byref(h), None))
-        shapes.append((h.value, w.value, 4))
-    out = [_out_array(ctx, s, np.float32, device) for s in shapes]
+    (out,), (ptrs,) = _level_outputs(pyramids, level, 1, (4,), device)
     ctx.check(getattr(ctx._lib, "dvo_hip_frames_" + name)(ctx.ptr, n, _handles(pyramids), T.ctypes.data_as(C.POINTER(C.c_double)), int(level),
-                                                          float(min_depth), float(max_depth), device_pointer_array([_address(a) for a in out]),
-                                                          1 if device else 0))
+                                                          float(min_depth), float(max_depth), ptrs, 1 if device else 0))
     return out
 
 
@@ -870,18 +888,13 @@ def _warp_args(pyramids, others, transforms, level, who):
     no items, mismatched lengths, a transform that is not 4 x 4 or not finite, a level a pyramid does not have, pyramids of different
     contexts or -- others: the second pyramid of every pair -- a pair whose sizes differ."""
     n = len(pyramids)
-    if n < 1:
-        raise ValueError("%s: no pyramids" % who)
-    if others is not None and len(others) != n:
-        raise ValueError("%s: %d raster pyramids but %d sampled pyramids" % (who, n, len(others)))
-    T = _pose_array(transforms, n, who, **_WARP_POSES)
-    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
-        raise TypeError("%s: level must be an integer" % who)
-    for p in list(pyramids) + list(others or []):
-        if not 0 <= level < p.levels:
-            raise ValueError("%s: a pyramid of %d levels has no level %d" % (who, p.levels, level))
-        if p.ctx is not pyramids[0].ctx:
-            raise ValueError("%s: the pyramids belong to different contexts" % who)
+
+    def counts_and_transforms():
+        if others is not None and len(others) != n:
+            raise ValueError("%s: %d raster pyramids but %d sampled pyramids" % (who, n, len(others)))
+        return _pose_array(transforms, n, who, **_WARP_POSES)
+
+    T = _pyramids_at_level(pyramids, level, who, then=counts_and_transforms, others=others or ())
     for p, q in zip(pyramids, others or []):
         if (p.camera.width, p.camera.height) != (q.camera.width, q.camera.height):
             raise ValueError("%s: the pyramids of a pair differ in size" % who)
@@ -890,14 +903,7 @@ def _warp_args(pyramids, others, transforms, level, who):
 
 def _warp_planes(pyramids, level, count, device):
     """count lists of one [h, w] float32 output plane per pyramid, and their pointer arrays"""
-    ctx = pyramids[0].ctx
-    shapes = []
-    for p in pyramids:
-        w, h = C.c_int(), C.c_int()
-        ctx.check(ctx._lib.dvo_hip_frame_info(p.ptr, level, C.byref(w), C.byref(h), None))
-        shapes.append((h.value, w.value))
-    out = [[_out_array(ctx, s, np.float32, device) for s in shapes] for _ in range(count)]
-    return out, [device_pointer_array([_address(a) for a in planes]) for planes in out]
+    return _level_outputs(pyramids, level, count, (), device)
 
 
 def warp_inverse_batch(raster_pyramids, sampled_pyramids, transforms, level=0, occlusion_margin=0.05, difference=False, device=False):
@@ -962,32 +968,26 @@ def _covis_args(pyramids, pairs, transforms, level, who):
     """(pairs as a contiguous [n, 2] int32 array, transforms as a contiguous [n, 4, 4] float64 array) of a covisibility call, or
     ValueError / TypeError: nothing reaches the library with no pyramids or pairs, too many pairs, an index that names no pyramid, a
     transform that is not 4 x 4 or not finite, a level a pyramid does not have or pyramids of different contexts."""
-    if len(pyramids) < 1:
-        raise ValueError("%s: no pyramids" % who)
-    try:
-        P = np.asarray(pairs)
-    except (TypeError, ValueError):
-        raise TypeError("%s: pairs must be integers, one (a, b) per pair" % who)
-    if P.dtype == bool or not np.issubdtype(P.dtype, np.integer):
-        if P.size or P.dtype == bool:
+    def pairs_and_transforms():
+        try:
+            P = np.asarray(pairs)
+        except (TypeError, ValueError):
             raise TypeError("%s: pairs must be integers, one (a, b) per pair" % who)
-    if P.ndim == 1 and P.shape[0] == 2:
-        P = P[None]
-    if P.ndim != 2 or P.shape[1] != 2 or P.shape[0] < 1:
-        raise ValueError("%s: pairs is an [n, 2] array of indices (a, b), n >= 1, got shape %s" % (who, P.shape))
-    if P.shape[0] > COVIS_MAX_PAIRS:
-        raise ValueError("%s: %d pairs, one call takes %d" % (who, P.shape[0], COVIS_MAX_PAIRS))
-    if P.min() < 0 or P.max() >= len(pyramids):
-        raise ValueError("%s: a pair names a pyramid outside 0 .. %d" % (who, len(pyramids) - 1))
-    T = _pose_array(transforms, P.shape[0], who, **_COVIS_POSES)
-    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
-        raise TypeError("%s: level must be an integer" % who)
-    for p in pyramids:
-        if not 0 <= level < p.levels:
-            raise ValueError("%s: a pyramid of %d levels has no level %d" % (who, p.levels, level))
-        if p.ctx is not pyramids[0].ctx:
-            raise ValueError("%s: the pyramids belong to different contexts" % who)
-    return np.ascontiguousarray(P, np.int32), T
+        if P.dtype == bool or not np.issubdtype(P.dtype, np.integer):
+            if P.size or P.dtype == bool:
+                raise TypeError("%s: pairs must be integers, one (a, b) per pair" % who)
+        if P.ndim == 1 and P.shape[0] == 2:
+            P = P[None]
+        if P.ndim != 2 or P.shape[1] != 2 or P.shape[0] < 1:
+            raise ValueError("%s: pairs is an [n, 2] array of indices (a, b), n >= 1, got shape %s" % (who, P.shape))
+        if P.shape[0] > COVIS_MAX_PAIRS:
+            raise ValueError("%s: %d pairs, one call takes %d" % (who, P.shape[0], COVIS_MAX_PAIRS))
+        if P.min() < 0 or P.max() >= len(pyramids):
+            raise ValueError("%s: a pair names a pyramid outside 0 .. %d" % (who, len(pyramids) - 1))
+        T = _pose_array(transforms, P.shape[0], who, **_COVIS_POSES)
+        return np.ascontiguousarray(P, np.int32), T
+
+    return _pyramids_at_level(pyramids, level, who, then=pairs_and_transforms)
 
 
 def covisibility_batch(pyramids, pairs, transforms, level=2, depth_tolerance=0.05, depth_tolerance_rel=0.0, min_depth=0.0,
@@ -1184,17 +1184,8 @@ class CodebookLogic:
         return np.ascontiguousarray(A, np.uint32)
 
     def _frames_arg(self, pyramids, level, who, limit=None):
-        if len(pyramids) < 1:
-            raise ValueError("%s: no pyramids" % who)
-        if limit is not None and len(pyramids) > limit:
-            raise ValueError("%s: %d pyramids, one call takes %d" % (who, len(pyramids), limit))
-        if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
-            raise TypeError("%s: level must be an integer" % who)
-        for p in pyramids:
-            if not 0 <= level < p.levels:
-                raise ValueError("%s: a pyramid of %d levels has no level %d" % (who, p.levels, level))
-            if self.ctx is not None and p.ctx is not self.ctx:
-                raise ValueError("%s: a pyramid of another context than the book's" % who)
+        _pyramids_at_level(pyramids, level, who, limit=limit, ctx=False if self.ctx is None else self.ctx,
+                           foreign="a pyramid of another context than the book's")
         return list(pyramids)
 
     def _query_args(self, n, k, skip, who):
