@@ -13,7 +13,10 @@ import os
 import numpy as np
 
 from . import tum
-from .tracker import Config, DenseTracker, RgbdCameraPyramid, default_context
+from .api_types import Config
+from .context import default_context
+from .dense_tracker import DenseTracker
+from .frames import RgbdCameraPyramid
 
 # launch/benchmark.yaml of dvo_benchmark
 BENCHMARK_YAML = dict(FirstLevel=3, LastLevel=1, MaxIterationsPerLevel=50, Precision=1e-4, Mu=0.05, UseInitialEstimate=True)

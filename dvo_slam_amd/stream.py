@@ -7,7 +7,8 @@ import os
 import numpy as np
 
 from . import _lib
-from .tracker import FrameSet, device_pointer_array, _RESULT_DTYPE
+from .api_types import _RESULT_DTYPE
+from .planes import FrameSet, device_pointer_array
 
 class _Lane(C.Structure):
     """dvo_stream_lane (stream_pipeline.cpp)"""
